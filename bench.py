@@ -3,13 +3,21 @@
 decode (DecodeDetections: threshold 0.01, NMS 0.45, top-200) at batch 32 per GPU, synthetic
 300x300x3 batches resident in HBM, random-init weights (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `config`).
+--dump-outputs DIR writes what the last timed step returned ((batch, top_k, 6) float32, rank 0's images) as two finite
+arrays: DIR/detections.npy with the non-finite entries (boxes whose exp() overflowed) zeroed, and
+DIR/detections_nonfinite.npy coding each entry (0 finite, +1 +inf, -1 -inf, 2 NaN), so that two builds can be compared
+output for output on the same seeded inputs and weights.
+--full adds everything else below: the per-kernel decode timing and roofline, the convolution roofline, the tamed-heads
+step, the CPU baseline with its parity flags and the secondary legs of bench_extra.py.
 
 N > 1: under a launcher (torch.distributed.run sets WORLD_SIZE; the driver's way) this process is one rank; WITHOUT one,
 `python bench.py --gpus N` spawns the N ranks itself (torch.distributed.run, 127.0.0.1 rendezvous, one rank per GPU,
 RCCL) and asserts WORLD_SIZE == N either way.  The data path has no collective (every rank decodes its own 32 images:
 weak scaling), the barrier + max-over-ranks timing does; `rccl_ranks_seen` on the line is an all-reduce of ones.
-Rank 0 prints ONE JSON line.  Extra objects on that line:
+Rank 0 prints ONE JSON line.  Extra objects on that line with --full:
   roofline      the dominant hand-written kernel of the decode path against HBM bandwidth: algorithmic bytes of
                 the decode path per launch (N*(C+12)*4 read + top_k*6*4 written per image) / that
                 kernel's average launch duration, measured with events on the launch stream;
@@ -55,6 +63,11 @@ def parse():
                     help="create the --gpus N ranks, bring up the process group (RCCL on GPUs, gloo where there is none), all-reduce "
                          "a one per rank, print {'ranks_seen': N, ...} and exit: the launcher path without any measurement")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-spawned ranks (0: a free one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's detections to DIR/detections.npy (float32, non-finite "
+                         "entries zeroed) and DIR/detections_nonfinite.npy (their codes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (roofline, CPU baseline, parity flags, secondary legs)")
     return ap.parse_args()
 
 
@@ -247,6 +260,37 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # random-init weights overflow exp() in the box decode, so some box corners are infinite: stored losslessly as two finite
+        # arrays, the detections with those entries zeroed and a code per entry (0 finite, +1 +inf, -1 -inf, 2 NaN)
+        det = out.float().cpu().numpy()
+        fin = np.isfinite(det)
+        code = np.where(fin, 0.0, np.where(np.isnan(det), 2.0, np.sign(det))).astype(np.float32)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "detections.npy"), np.where(fin, det, 0.0).astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "detections_nonfinite.npy"), code)
+    ips = world * B * args.steps / elapsed
+    line = {"metric": "images/sec SSD300 fwd+decode @batch32", "value": round(ips, 2), "unit": "images/sec",
+            "n_gpus": world, "rccl_ranks_seen": ranks_seen, "collective_backend": backend if world > 1 else None,
+            "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "data": "synthetic",
+            "dtype": "f32 (decode, threshold, TF-style f32 NMS, top-k); %s conv backbone" % args.dtype,
+            "config": {"workload": "SSD300 VGG-16 inference (mode='inference': forward + DecodeDetections), 21 classes, "
+                                   "batch %d per GPU, conf 0.01 / NMS 0.45 / top-200, random-init weights, synthetic "
+                                   "300x300x3 uint8-range images" % B,
+                       "per_gpu_batch": B, "global_batch": world * B,
+                       "conv_dtype": args.dtype, "decode_dtype": "f32 decode + f32 IoU (DecodeDetections layer); decode_detections: f32 decode, f64 IoU", "parallelism": "replicas x%d" % world,
+                       "launch": launch, "gpu_ms_per_step": round(gpu_ms_per_step, 4),
+                       "untimed_graph_replays_before_the_timed_region": max(3, args.graph_warmup) if runner is not None else 0,
+                       "decode_stream": "second HIP stream, overlapped with the next forward" if args.overlap else
+                                        "same stream; DecodeDetections reads the head outputs directly (no y_pred in HBM)"}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     if args.overlap:
         decode_ms_in_step = float(np.mean([a.elapsed_time(b) for a, b in dec_ev]))
     else:
@@ -488,23 +532,8 @@ def main():
                 extra["train_step"] = tr
 
     if rank == 0:
-        ips = world * B * args.steps / elapsed
-        line = {"metric": "images/sec SSD300 fwd+decode @batch32", "value": round(ips, 2), "unit": "images/sec",
-                "n_gpus": world, "rccl_ranks_seen": ranks_seen, "collective_backend": backend if world > 1 else None,
-                "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "data": "synthetic",
-                "dtype": "f32 (decode, threshold, TF-style f32 NMS, top-k); %s conv backbone" % args.dtype,
-                "config": {"workload": "SSD300 VGG-16 inference (mode='inference': forward + DecodeDetections), 21 classes, "
-                                       "batch %d per GPU, conf 0.01 / NMS 0.45 / top-200, random-init weights, synthetic "
-                                       "300x300x3 uint8-range images" % B,
-                           "per_gpu_batch": B, "global_batch": world * B, "anchors": int(N), "classes": int(C),
-                           "conv_dtype": args.dtype, "decode_dtype": "f32 decode + f32 IoU (DecodeDetections layer); decode_detections: f32 decode, f64 IoU", "parallelism": "replicas x%d" % world,
-                           "launch": launch, "gpu_ms_per_step": round(gpu_ms_per_step, 4),
-                           "untimed_graph_replays_before_the_timed_region": max(3, args.graph_warmup) if runner is not None else 0,
-                           "decode_stream": "second HIP stream, overlapped with the next forward" if args.overlap else
-                                            "same stream; DecodeDetections reads the head outputs directly (no y_pred in HBM)"},
-                "value_tamed_heads": tamed, "roofline": roofline, "conv_roofline": conv, "cpu_baseline": cpu}
+        line["config"].update(anchors=int(N), classes=int(C))
+        line.update({"value_tamed_heads": tamed, "roofline": roofline, "conv_roofline": conv, "cpu_baseline": cpu})
         line.update(extra)
         # ---- scalars at the top level (the driver's record keeps scalar keys only) ----
         def dig_any(obj, *path):

@@ -221,7 +221,11 @@ def test_bench_gpus_flag_spawns_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher around it creates two ranks itself (the flag was parsed and
     never read); the dry launch brings the process group up and counts the ranks with an all-reduce of ones."""
     import json
-    res = _run_bench(["--gpus", "2", "--dry-launch"])
+    env = None
+    if torch.cuda.is_available() and torch.cuda.device_count() < 2:
+        # one GPU: both ranks on GPU 0 over gloo, the bench's own mode for exercising the launch path on such a machine
+        env = {"SSD_BENCH_SHARE_GPU": "1", "SSD_BENCH_BACKEND": "gloo"}
+    res = _run_bench(["--gpus", "2", "--dry-launch"], env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout                                   # rank 0 alone prints

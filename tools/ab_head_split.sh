@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 for rep in 1 2 3; do
 for v in "SSDHIP_HEAD_SPLIT=2" "SSDHIP_HEAD_SPLIT=3" "SSDHIP_HEAD_SPLIT=3 SSDHIP_HEAD_WGS=224" "SSDHIP_HEAD_SPLIT=3 SSDHIP_HEAD_WGS=200"; do
-  r=$(env $v timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extra 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline'].get('decode_ms_in_step'))")
+  r=$(env $v timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-extra 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['roofline'].get('decode_ms_in_step'))")
   echo "AB $v -> $r"
 done
 done

@@ -8,7 +8,7 @@ OUT=${1:-$R/gpurun_out/two_ranks}
 mkdir -p $OUT
 cd $R
 SSD_BENCH_BACKEND=gloo SSD_BENCH_SHARE_GPU=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_two_ranks.json 2> $OUT/bench_two_ranks.err
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_two_ranks.json 2> $OUT/bench_two_ranks.err
 echo "rc=$?"
 tail -c 600 $OUT/bench_two_ranks.err
 python - $OUT/bench_two_ranks.json <<'P'
