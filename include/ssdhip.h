@@ -636,6 +636,18 @@ int ssdhip_image_resize_cv_u8(const void* x, void* y, int B, int H, int W, int H
 int ssdhip_image_resize_gather_cv_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* plan_dev,
                                      const int* ix_dev, const double* wx_dev, int nx, const int* iy_dev, const double* wy_dev, int ny,
                                      const void* background_dev, void* stream);
+/* cv2.warpAffine on 8-bit images, INTER_LINEAR, BORDER_CONSTANT, with OpenCV 3.4 / 4.x (up to 4.10) arithmetic (imgproc/imgwarp.cpp;
+ * csrc/ssdhip_warp.hip): the pixels of Translate / Scale / Rotate (data_generator/object_detection_2d_geometric_ops.py:233-772) for a
+ * batch, every image with its own geometry.  x [B][H][W][C] uint8 -> y [B][Ho][Wo][C] (4-byte aligned), 1 <= C <= 4.
+ *   xtab [B][Wo][2] int32  per column (cvRound(M0 x 1024), cvRound(M3 x 1024)) of the INVERTED matrix,
+ *   ytab [B][Ho][2] int32  per row (cvRound((M1 y + M2) 1024) + 16, cvRound((M4 y + M5) 1024) + 16);
+ *   geo  [B][5] int32      flip, pre_dx, pre_dy, post_dx, post_dy: output column x reads warp column (flip ? Wo-1-x : x) - post_dx,
+ *                          row y - post_dy (outside Wo x Ho: background); the warp's neighbour (p, q) reads source pixel
+ *                          (p - pre_dx, q - pre_dy) when both lie inside W x H, background otherwise;
+ *   background [B][C] uint8.
+ * Identity tables with pre / post set are an exact integer translation. */
+int ssdhip_image_warp_affine_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* geo_dev, const int* xtab_dev,
+                                const int* ytab_dev, const void* background_dev, void* stream);
 int ssdhip_image_hist_u8(const void* x, long long n_pixels, int C, int channel, unsigned int* hist_dev, void* stream);
 int ssdhip_image_lut_u8(const void* x, void* y, long long n_values, int C, int channel_mask, const void* table_dev, void* stream);
 

@@ -2138,6 +2138,37 @@ def image_resize_gather_cv_u8(images, out_h, out_w, plans, ix, wx, iy, wy, backg
     return out
 
 
+def image_warp_affine_u8(images, out_h, out_w, geo, xtab, ytab, background):
+    """ssdhip_image_warp_affine_u8 (cv2.warpAffine, INTER_LINEAR, BORDER_CONSTANT, 8-bit; csrc/ssdhip_warp.hip): images (B, H, W, C)
+    CUDA uint8; geo (B, 5) int32 [flip, pre_dx, pre_dy, post_dx, post_dy]; per-image tables xtab (B, out_w, 2), ytab (B, out_h, 2) int32
+    (data_generator/_image_ops.warp_tables); background (B, C) uint8.  Returns the (B, out_h, out_w, C) uint8 batch."""
+    torch = _torch()
+    lib = _image_lib()
+    if not getattr(lib, "_warp_bound", False):
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        lib.ssdhip_image_warp_affine_u8.restype = ci
+        lib.ssdhip_image_warp_affine_u8.argtypes = [vp, vp] + [ci] * 6 + [vp] * 5
+        lib._warp_bound = True
+    require_cuda(images, "images")
+    if images.dtype != torch.uint8 or images.dim() != 4 or not images.is_contiguous():
+        raise SsdHipError("images must be a contiguous (B, H, W, C) uint8 tensor")
+    b, h, w, c = images.shape
+    dev = images.device
+    geo = to_device(geo, device=dev, dtype=torch.int32).contiguous()
+    xtab = to_device(xtab, device=dev, dtype=torch.int32).contiguous()
+    ytab = to_device(ytab, device=dev, dtype=torch.int32).contiguous()
+    bg = to_device(background, device=dev, dtype=torch.uint8).contiguous()
+    if (tuple(geo.shape) != (b, 5) or tuple(xtab.shape) != (b, out_w, 2) or tuple(ytab.shape) != (b, out_h, 2)
+            or tuple(bg.shape) != (b, c)):
+        raise SsdHipError("geo must be (B, 5), tables (B, out_w, 2) / (B, out_h, 2), background (B, C)")
+    out = torch.empty((b, out_h, out_w, c), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.ssdhip_image_warp_affine_u8(_ptr(images), _ptr(out), b, h, w, int(out_h), int(out_w), c, _ptr(geo), _ptr(xtab), _ptr(ytab),
+                                             _ptr(bg), current_stream_ptr(dev))
+    check(rc, "ssdhip_image_warp_affine_u8")
+    return out
+
+
 def image_hist_u8(image, channel):
     """256-bin histogram (CUDA int64 tensor) of one channel of an (..., C) uint8 CUDA image."""
     torch = _torch()

@@ -390,3 +390,162 @@ def equalize_channel(image, channel):
         return nat.image_lut_u8(dev, table, 1 << channel).cpu().numpy()
     table = equalize_table(nat.image_hist_u8(image.contiguous(), channel).cpu().numpy())
     return nat.image_lut_u8(image.contiguous(), table, 1 << channel)
+
+
+# ---- cv2.warpAffine for 8-bit images: OpenCV 3.4 / 4.x up to 4.10 (imgproc/imgwarp.cpp), the arithmetic runs in csrc/ssdhip_warp.hip ----
+# (4.11 moved warpAffine to float arithmetic; the reference predates it.)  INTER_LINEAR, BORDER_CONSTANT only -- every call the reference
+# makes (object_detection_2d_geometric_ops.py:287-291, 497-501, 703-705).  Without WARP_INVERSE_MAP the float64 matrix is inverted first
+# (D = 1 / (M0 M4 - M1 M3), ...); then per column adelta = cvRound(M0 x 1024), bdelta = cvRound(M3 x 1024), per row
+# X0 = cvRound((M1 y + M2) 1024) + 16, Y0 = cvRound((M4 y + M5) 1024) + 16, and the device does X = (X0 + adelta) >> 5, sx = X >> 5,
+# fx = X & 31 and remapBilinear's 15-bit weights 32 (32 - fx)(32 - fy), ... which sum to 32768 (the table fix-up never fires).
+def rotation_matrix_2d(center, angle, scale):
+    """cv2.getRotationMatrix2D: `center` is a Point2f (float32 coordinates), `angle *= CV_PI / 180`, float64 result (2, 3)."""
+    cx, cy = float(np.float32(center[0])), float(np.float32(center[1]))
+    rad = float(angle) * (_PI / 180)
+    a = _math.cos(rad) * float(scale)
+    b = _math.sin(rad) * float(scale)
+    return np.array([[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]], dtype=np.float64)
+
+
+def invert_affine(M):
+    """warpAffine's in-place inversion of the (float64-widened) forward matrix -> the six coefficients of the inverse map."""
+    m = [float(v) for v in np.asarray(M, dtype=np.float64).reshape(6)]
+    d = m[0] * m[4] - m[1] * m[3]
+    d = 1.0 / d if d != 0 else 0.0
+    a11, a22 = m[4] * d, m[0] * d
+    m[0], m[1], m[3], m[4] = a11, m[1] * -d, m[3] * -d, a22
+    b1 = -m[0] * m[2] - m[1] * m[5]
+    b2 = -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    return m
+
+
+def warp_tables(M, out_h, out_w):
+    """(xtab (out_w, 2), ytab (out_h, 2)) int32: (adelta, bdelta) per column and (X0, Y0) per row of the forward matrix M."""
+    m = invert_affine(M)
+    x = np.arange(out_w, dtype=np.float64)
+    y = np.arange(out_h, dtype=np.float64)
+    xtab = np.stack([np.rint(m[0] * x * 1024.0), np.rint(m[3] * x * 1024.0)], axis=1)
+    ytab = np.stack([np.rint((m[1] * y + m[2]) * 1024.0) + 16, np.rint((m[4] * y + m[5]) * 1024.0) + 16], axis=1)
+    return xtab.astype(np.int32), ytab.astype(np.int32)
+
+
+def border_value(background, channels):
+    """saturate_cast<uchar> of a cv::Scalar's first `channels` entries (missing entries are 0)."""
+    v = list(background) if isinstance(background, (list, tuple, np.ndarray)) else [background]
+    v = (v + [0, 0, 0, 0])[:channels]
+    return np.array([min(max(int(np.rint(float(a))), 0), 255) for a in v], dtype=np.uint8)
+
+
+_IDENTITY = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+
+
+def _integer_shift(M):
+    """(dx, dy) when M is a translation by whole pixels (an exact copy under warpAffine's arithmetic), else None."""
+    m = np.asarray(M, dtype=np.float64).reshape(2, 3)
+    if m[0, 0] == 1 and m[0, 1] == 0 and m[1, 0] == 0 and m[1, 1] == 1 and float(m[0, 2]).is_integer() and float(m[1, 2]).is_integer():
+        return int(m[0, 2]), int(m[1, 2])
+    return None
+
+
+class WarpImage:
+    """An image that exists only as a recorded geometry over an image resident on the device (like `GeoImage`): at most one non-integer
+    warp (`M`, its output size), integer translations before it (`pre`) and after it (`post`), and a horizontal flip at the end
+    (`[:, ::-1]`) -- what Translate / Scale / Rotate / RandomFlip do to it, executed once for a whole batch by `warp_batch`
+    (ssdhip_image_warp_affine_u8).  Anything else raises NotImplementedError."""
+
+    ndim = 3
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, height, width, src_h=None, src_w=None, M=None, pre=(0, 0), post=None, flip=False, background=None):
+        self.height, self.width = int(height), int(width)
+        self.src_h = self.height if src_h is None else int(src_h)
+        self.src_w = self.width if src_w is None else int(src_w)
+        self.M, self.pre, self.post, self.flip, self.background = M, tuple(pre), post, bool(flip), background
+
+    @classmethod
+    def of(cls, height, width):
+        return cls(height, width)
+
+    @property
+    def shape(self):
+        return (self.height, self.width, 3)
+
+    def _with(self, **kw):
+        d = dict(height=self.height, width=self.width, src_h=self.src_h, src_w=self.src_w, M=self.M, pre=self.pre, post=self.post,
+                 flip=self.flip, background=self.background)
+        d.update(kw)
+        return WarpImage(**d)
+
+    def _bg(self, background):
+        bg = tuple(int(v) for v in border_value(background, 3))
+        if self.background is not None and self.background != bg:
+            raise NotImplementedError("two warps with different background colours cannot be composed lazily")
+        return bg
+
+    def warp(self, M, dsize, background):
+        """cv2.warpAffine(self, M, dsize, borderMode=BORDER_CONSTANT, borderValue=background), recorded."""
+        out_w, out_h = int(dsize[0]), int(dsize[1])
+        if self.flip or self.post is not None:
+            raise NotImplementedError("a warp after a flip or after a second translation cannot be composed lazily")
+        bg = self._bg(background)
+        shift = _integer_shift(M)
+        if shift is not None and (out_h, out_w) == (self.height, self.width):
+            if self.M is None and self.pre == (0, 0):
+                return self._with(pre=shift, background=bg)
+            if self.M is None:
+                return self._with(M=_IDENTITY, post=shift, background=bg)
+            return self._with(post=shift, background=bg)
+        if self.M is not None:
+            raise NotImplementedError("two non-integer warps cannot be composed lazily")
+        if self.pre != (0, 0) and (out_h, out_w) != (self.height, self.width):
+            raise NotImplementedError("a translation before a warp that changes the image size cannot be composed lazily")
+        return self._with(height=out_h, width=out_w, M=np.asarray(M, dtype=np.float64).reshape(2, 3), background=bg)
+
+    def __getitem__(self, key):
+        if not isinstance(key, tuple):
+            key = (key,)
+        full = slice(None, None, None)
+        if len(key) == 2 and key[0] == full and key[1] == slice(None, None, -1) and not self.flip:
+            return self._with(flip=True)
+        raise NotImplementedError("lazy warped images take one horizontal flip ([:, ::-1]) only")
+
+    def plan(self):
+        """(geo (5,) int32, xtab, ytab, background (3,) uint8) of this image for ssdhip_image_warp_affine_u8."""
+        xtab, ytab = warp_tables(_IDENTITY if self.M is None else self.M, self.height, self.width)
+        post = self.post or (0, 0)
+        geo = np.array([int(self.flip), self.pre[0], self.pre[1], post[0], post[1]], dtype=np.int32)
+        bg = np.array(self.background if self.background is not None else (0, 0, 0), dtype=np.uint8)
+        return geo, xtab, ytab, bg
+
+
+def warp_batch(images, lazies):
+    """Execute the recorded geometry of a batch: images (B, H, W, 3) CUDA uint8, lazies[i] a `WarpImage` of image i -> the
+    (B, out_h, out_w, 3) uint8 batch, ONE launch."""
+    sizes = {(l.height, l.width) for l in lazies}
+    if len(sizes) != 1:
+        raise ValueError("every image of a batch must end in the same size")
+    if any((l.src_h, l.src_w) != (int(images.shape[1]), int(images.shape[2])) for l in lazies):
+        raise ValueError("the recorded geometry is not of these images")
+    out_h, out_w = sizes.pop()
+    plans = [l.plan() for l in lazies]
+    return nat.image_warp_affine_u8(images.contiguous(), out_h, out_w, np.stack([p[0] for p in plans]), np.stack([p[1] for p in plans]),
+                                    np.stack([p[2] for p in plans]), np.stack([p[3] for p in plans]))
+
+
+def warp_affine(image, M, dsize, background=0):
+    """cv2.warpAffine(image, M, dsize=(width, height), borderMode=BORDER_CONSTANT, borderValue=background) for uint8 images: a NumPy
+    (H, W[, C]) image (one upload, one launch, one download) or a `WarpImage` (recorded)."""
+    if isinstance(image, WarpImage):
+        return image.warp(M, dsize, background)
+    if not isinstance(image, np.ndarray):
+        raise TypeError("warp_affine takes a NumPy image or a lazy WarpImage")
+    if image.dtype != np.uint8:
+        raise TypeError("warp_affine takes uint8 images")
+    src = image if image.ndim == 3 else image[:, :, None]
+    out_w, out_h = int(dsize[0]), int(dsize[1])
+    xtab, ytab = warp_tables(M, out_h, out_w)
+    geo = np.zeros((1, 5), dtype=np.int32)
+    bg = border_value(background, src.shape[2])[None]
+    out = nat.image_warp_affine_u8(nat.to_device(np.ascontiguousarray(src)[None]), out_h, out_w, geo, xtab[None], ytab[None], bg)[0].cpu().numpy()
+    return out if image.ndim == 3 else out[:, :, 0]
