@@ -593,15 +593,6 @@ int ssdhip_conv1_block_nhwc_bf16(const void* x3, const void* w1, const void* b1,
 int ssdhip_conv3x3_cin3_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W,
                                   int Cin, int Cout, int relu, void* stream);
 
-/* The geometric half of SSDDataAugmentation (data_generator/data_augmentation_chain_original_ssd.py:208-280: expansion -> random crop ->
- * random flip -> resize with a random interpolation mode) for a whole batch in ONE launch: x [B, H, W, C] uint8 (device), y [B, Ho, Wo, C];
- * per image its own tap tables ix / wx [B][Wo][nx], iy / wy [B][Ho][ny]: the taps of cv2.resize on that image's patch, composed on the
- * host with its expansion / crop / flip index maps -- an index addresses a column / row of the ORIGINAL image, -1 = background
- * (background [B][C] uint8).  Arithmetic of ssdhip_image_resize_u8. */
-int ssdhip_image_resize_gather_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* ix_dev,
-                                  const double* wx_dev, int nx, const int* iy_dev, const double* wy_dev, int ny,
-                                  const void* background_dev, void* stream);
-
 /* ------------------------------------------------------------------------------------------
  * Image half of the training-time augmentation (csrc/ssdhip_image.hip): what the reference does per image on the host
  * through OpenCV (data_generator/object_detection_2d_photometric_ops.py:23-480, object_detection_2d_geometric_ops.py:27-148), for a
@@ -615,15 +606,10 @@ int ssdhip_image_resize_gather_u8(const void* x, void* y, int B, int H, int W, i
  *   results for uint8 images under 3 / 4; truncating in-place stores for 5 / 6 on uint8 images); 7 / 8 are cv2.cvtColor's 8-bit
  *   (H in [0, 180)) or float32 (H in [0, 360)) conversions.  out_dtype must be the dtype the program ends in.  ops / args: device arrays
  *   [n_images][16] (int32 / float64).
- * ssdhip_image_resize_u8 cv2.resize as separable resampling (object_detection_2d_geometric_ops.py:70-72): x [B,H,W,C] -> y [B,Ho,Wo,C],
- *   out = rint(sum_j wy[yo][j] * (sum_t wx[xo][t] * x[iy[yo][j]][ix[xo][t]])) clipped to [0, 255]; the caller builds the tap tables
- *   (device arrays [Wo][nx], [Ho][ny]; int32 indices, float64 weights) for the interpolation mode it wants.
  * ssdhip_image_hist_u8   256-bin histogram of one channel of an interleaved uint8 image (cv2.equalizeHist's first half, :407).
  * ssdhip_image_lut_u8    y = table[x] on the channels of channel_mask, x elsewhere (cv2.LUT :359 / the equalisation table). */
 int ssdhip_image_program(const void* x, int in_dtype, void* y, int out_dtype, int n_images, long long pixels_per_image,
                          const int* ops_dev, const double* args_dev, void* stream);
-int ssdhip_image_resize_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* ix_dev, const double* wx_dev,
-                           int nx, const int* iy_dev, const double* wy_dev, int ny, void* stream);
 /* cv2.resize on 8-bit images with OpenCV's own arithmetic (round 6; data_generator/object_detection_2d_geometric_ops.py:70-72 calls
  * cv2.resize -> imgproc/resize.cpp): `kind` 0 nearest, 1 linear (11-bit fixed-point coefficients, the two-stage vertical rounding),
  * 2 cubic / Lanczos-4 (fixed point, (sum + 2^21) >> 22), 3 area (float32 tables, cvRound), 4 fast area (block sum * (1.f / area)),
@@ -716,7 +702,7 @@ int ssdhip_sgd_momentum_step(int n_tensors, void* const* params_h, const void* c
  *   labels        [B][64][5] float64 rows (class_id, xmin, ymin, xmax, ymax), n_labels [B] <= 64 (int64 and float64 label arrays are
  *                 both exact in float64);
  *   geometry      [B][12] int32: expanded?, canvas top, left, height, width | cropped?, patch top, left, height, width | flipped?,
- *                 interpolation mode -- what the gather launch (ssdhip_image_resize_gather_u8) needs;
+ *                 interpolation mode -- what ssdhip_augment_plans needs;
  *   labels_out    [B][64][5] float64 + n_labels_out [B]: the surviving boxes in the output image's coordinates;
  *   mt_state_out  [B][625]: the generator states behind the chain. */
 typedef struct ssdhip_augment_params {
@@ -729,15 +715,11 @@ typedef struct ssdhip_augment_params {
     int n_modes, interpolation_modes[8], out_height, out_width;
     int max_rounds;                                  /* 0: 100 000 sampling rounds at most (the reference loops without a limit) */
 } ssdhip_augment_params;
-/* ssdhip_augment_taps: the tap tables of ssdhip_image_resize_gather_u8 for the batch, built on the device from `geometry` (as
- * ssdhip_ssd_augment_decide leaves it): cv2.resize's source indices / float64 weights of each image's interpolation mode (0 nearest, 1
- * linear, 2 cubic, 3 area, 4 Lanczos-4) composed with its flip, crop window and expansion canvas (-1: a canvas pixel).  ix / wx
- * [B][out_w][n_taps], iy / wy [B][out_h][n_taps]; n_taps >= 8 and >= ceil(largest source / output extent ratio) + 1 (the area filter). */
-int ssdhip_augment_taps(const int* geometry_dev, int B, int H, int W, int out_h, int out_w, int n_taps, int* ix_dev, double* wx_dev,
-                        int* iy_dev, double* wy_dev, void* stream);
-/* ssdhip_augment_plans (round 6): as ssdhip_augment_taps, with cv2.resize's own 8-bit arithmetic: plan [B][4] = kind, area, taps per
- * column, taps per row and the tables of ssdhip_image_resize_gather_cv_u8 (fixed-point shorts / float32 area weights / ones as float64
- * values); n_taps >= 8 and >= ceil(largest source / output extent ratio) + 2. */
+/* ssdhip_augment_plans (round 6): the per-image plans of ssdhip_image_resize_gather_cv_u8 for the batch, built on the device from
+ * `geometry` (as ssdhip_ssd_augment_decide leaves it) with cv2.resize's own 8-bit arithmetic: plan [B][4] = kind, area, taps per column,
+ * taps per row, and the tables (fixed-point shorts / float32 area weights / ones as float64 values) of each image's interpolation mode
+ * (0 nearest, 1 linear, 2 cubic, 3 area, 4 Lanczos-4) composed with its flip, crop window and expansion canvas (-1: a canvas pixel).
+ * ix / wx [B][out_w][n_taps], iy / wy [B][out_h][n_taps]; n_taps >= 8 and >= ceil(largest source / output extent ratio) + 2. */
 int ssdhip_augment_plans(const int* geometry_dev, int B, int H, int W, int out_h, int out_w, int n_taps, int* plan_dev, int* ix_dev,
                          double* wx_dev, int* iy_dev, double* wy_dev, void* stream);
 int ssdhip_ssd_augment_decide(const ssdhip_augment_params* params, int B, const unsigned int* mt_state, const double* labels,

@@ -9,9 +9,9 @@
 //                            dtype (float32 ops for float32 images, float64 for uint8 ones, truncating in-place stores), 8-bit and
 //                            float32 RGB <-> HSV, grey, channel permutations.  One launch distorts a whole batch, each image with
 //                            its own program (the random draws stay on the host, in the reference's order);
-//   * resize_taps_kernel     cv2.resize as separable resampling: the host builds, per output column / row, the source indices and
-//                            float64 weights of its taps (nearest 1, linear 2, cubic 4, Lanczos 8, area ceil(scale) + 1) -- one
-//                            kernel serves every interpolation mode; float64 accumulation in a fixed order, one rounding;
+//   * resize_cv_kernel / resize_gather_cv_kernel   cv2.resize with OpenCV's own 8-bit arithmetic, from a plan of source indices
+//                            and weights per output column / row (one plan for the batch, or one per image with the augmentation
+//                            chain's expansion / crop / flip composed in);
 //   * hist_u8_kernel / lut_u8_kernel   cv2.equalizeHist (histogram on the device, the 256-entry table on the host) and cv2.LUT.
 // Arithmetic is written operation by operation (-ffp-contract=off): bit-identical to the NumPy restatement in oracle/np_image.py.
 #include <hip/hip_runtime.h>
@@ -243,98 +243,8 @@ __global__ __launch_bounds__(256) void pixel_program_u8x4_kernel(const unsigned 
     }
 }
 
-// x [B,H,W,C] uint8 -> y [B,Ho,Wo,C] uint8.  ix [Wo][nx] / wx, iy [Ho][ny] / wy: the taps of every output column / row.
-// out = rint(sum_j wy[j] * (sum_t wx[t] * x[iy[j]][ix[t]])), rows outer, columns inner, float64, clipped to [0, 255].
-__global__ __launch_bounds__(256) void resize_taps_kernel(const unsigned char* __restrict__ x, unsigned char* __restrict__ y, int H, int W,
-                                                          int Ho, int Wo, int C, const int* __restrict__ ix, const double* __restrict__ wx,
-                                                          int nx, const int* __restrict__ iy, const double* __restrict__ wy, int ny) {
-    const int b = blockIdx.y;
-    const long long total = (long long)Ho * Wo * C;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int ch = (int)(i % C);
-        const long long t = i / C;
-        const int xo = (int)(t % Wo), yo = (int)(t / Wo);
-        const unsigned char* src = x + (size_t)b * H * W * C;
-        double acc = 0.0;
-        for (int j = 0; j < ny; ++j) {
-            const unsigned char* row = src + (size_t)iy[yo * ny + j] * W * C;
-            double racc = 0.0;
-            for (int k = 0; k < nx; ++k) racc = racc + wx[xo * nx + k] * (double)row[(size_t)ix[xo * nx + k] * C + ch];
-            acc = acc + wy[yo * ny + j] * racc;
-        }
-        const double r = rint(acc);
-        y[(size_t)b * total + i] = (unsigned char)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
-    }
-}
-
-// The same resampling with the work laid out for the memory system: one workgroup = 256 consecutive values of ONE output row (grid
-// y = row, z = image), so the row's vertical taps are wave-uniform (scalar loads), a thread keeps ITS column's horizontal taps in
-// registers for all the rows it combines (nx <= 8: every mode but strong 'area' shrinks), there is no 64-bit division per value, and the
-// 256 gathers of a tap fall into one short stretch of one source row.  Same operations in the same order: identical results.
-__global__ __launch_bounds__(256) void resize_rows_kernel(const unsigned char* __restrict__ x, unsigned char* __restrict__ y, int H, int W,
-                                                          int Ho, int Wo, int C, const int* __restrict__ ix, const double* __restrict__ wx,
-                                                          int nx, const int* __restrict__ iy, const double* __restrict__ wy, int ny) {
-    const int v = (int)blockIdx.x * 256 + (int)threadIdx.x, yo = (int)blockIdx.y, b = (int)blockIdx.z;
-    if (v >= Wo * C) return;
-    const int xo = v / C, ch = v - xo * C;
-    int ixr[8];
-    double wxr[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        ixr[k] = k < nx ? ix[xo * nx + k] * C + ch : 0;
-        wxr[k] = k < nx ? wx[xo * nx + k] : 0.0;
-    }
-    const unsigned char* src = x + (size_t)b * H * W * C;
-    double acc = 0.0;
-    for (int j = 0; j < ny; ++j) {
-        const unsigned char* row = src + (size_t)iy[yo * ny + j] * W * C;
-        double racc = 0.0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (k < nx) racc = racc + wxr[k] * (double)row[ixr[k]];
-        acc = acc + wy[yo * ny + j] * racc;
-    }
-    const double r = rint(acc);
-    y[((size_t)b * Ho + yo) * Wo * C + v] = (unsigned char)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
-}
-
-// The geometric half of the augmentation chain for a whole BATCH in one launch: every image has its OWN tap tables -- the taps of
-// cv2.resize on the image's crop, composed on the host with the crop / expansion / flip index maps, so a tap addresses a column (row) of
-// the ORIGINAL image, or -1 = a position the expansion filled with the background colour.  Nothing but the final 300 x 300 batch is ever
-// materialised (the reference builds the expanded canvas, the crop and the flipped view per image on the host).  Layout and arithmetic as
-// resize_rows_kernel: out = rint(sum_j wy[j] (sum_k wx[k] pixel)), float64, rows outer; unused taps carry weight 0 and a valid index.
-__global__ __launch_bounds__(256) void resize_gather_kernel(const unsigned char* __restrict__ x, unsigned char* __restrict__ y, int H, int W,
-                                                            int Ho, int Wo, int C, const int* __restrict__ ix, const double* __restrict__ wx,
-                                                            int nx, const int* __restrict__ iy, const double* __restrict__ wy, int ny,
-                                                            const unsigned char* __restrict__ background) {
-    const int v = (int)blockIdx.x * 256 + (int)threadIdx.x, yo = (int)blockIdx.y, b = (int)blockIdx.z;
-    if (v >= Wo * C) return;
-    const int xo = v / C, ch = v - xo * C;
-    const double bg = (double)background[b * C + ch];
-    const int* ixb = ix + ((size_t)b * Wo + xo) * nx;
-    const double* wxb = wx + ((size_t)b * Wo + xo) * nx;
-    const int* iyb = iy + ((size_t)b * Ho + yo) * ny;
-    const double* wyb = wy + ((size_t)b * Ho + yo) * ny;
-    const unsigned char* src = x + (size_t)b * H * W * C;
-    double acc = 0.0;
-    for (int j = 0; j < ny; ++j) {
-        const int sy = iyb[j];
-        const unsigned char* row = src + (size_t)(sy < 0 ? 0 : sy) * W * C;
-        double racc = 0.0;
-        for (int k = 0; k < nx; ++k) {
-            const int sx = ixb[k];
-            const double pv = (sy < 0 || sx < 0) ? bg : (double)row[(size_t)sx * C + ch];
-            racc = racc + wxb[k] * pv;
-        }
-        acc = acc + wyb[j] * racc;
-    }
-    const double r = rint(acc);
-    y[((size_t)b * Ho + yo) * Wo * C + v] = (unsigned char)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------------
-// cv2.resize on 8-bit images with OpenCV's OWN arithmetic (round 6; imgproc/resize.cpp, the C++ reference paths -- the kernels above
-// resample with float64 weights and one rounding, one grey level off here and there).  The host (data_generator/_image_ops.py
+// cv2.resize on 8-bit images with OpenCV's OWN arithmetic (round 6; imgproc/resize.cpp, the C++ reference paths).  The host (data_generator/_image_ops.py
 // resize_plan) or the device (csrc/ssdhip_augment.hip) builds the plan: `kind`, tap indices, and the tables as float64 values that hold
 // 11-bit fixed-point shorts / float32 area weights / ones exactly.  Per output value, rows j outer, columns k inner:
 //   COPY / NEAREST   the single tap
@@ -469,34 +379,6 @@ extern "C" int ssdhip_image_program(const void* x, int in_dtype, void* y, int ou
     }
     hipLaunchKernelGGL(pixel_program_kernel, dim3(img_blocks(pixels_per_image, 4096), n_images), dim3(256), 0, stream, x, in_dtype, y, out_dtype,
                        pixels_per_image, ops_dev, args_dev);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
-}
-
-extern "C" int ssdhip_image_resize_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* ix_dev,
-                                      const double* wx_dev, int nx, const int* iy_dev, const double* wy_dev, int ny, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !y || !ix_dev || !wx_dev || !iy_dev || !wy_dev) return SSDHIP_E_BADARG;
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || C > 4 || nx <= 0 || ny <= 0 || nx > 64 || ny > 64) return SSDHIP_E_BADARG;
-    if (nx <= 8 && Ho <= 65535 && (long long)Wo * C < 0x7fffff00LL) {
-        hipLaunchKernelGGL(resize_rows_kernel, dim3((unsigned)((Wo * C + 255) / 256), (unsigned)Ho, (unsigned)B), dim3(256), 0, stream,
-                           static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), H, W, Ho, Wo, C, ix_dev, wx_dev, nx, iy_dev, wy_dev, ny);
-        return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(resize_taps_kernel, dim3(img_blocks((long long)Ho * Wo * C, 4096), B), dim3(256), 0, stream,
-                       static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), H, W, Ho, Wo, C, ix_dev, wx_dev, nx, iy_dev, wy_dev, ny);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
-}
-
-extern "C" int ssdhip_image_resize_gather_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* ix_dev,
-                                             const double* wx_dev, int nx, const int* iy_dev, const double* wy_dev, int ny,
-                                             const void* background_dev, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !y || !ix_dev || !wx_dev || !iy_dev || !wy_dev || !background_dev) return SSDHIP_E_BADARG;
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || Ho <= 0 || Ho > 65535 || Wo <= 0 || C <= 0 || C > 4 || nx <= 0 || ny <= 0 || nx > 64 || ny > 64)
-        return SSDHIP_E_BADARG;
-    hipLaunchKernelGGL(resize_gather_kernel, dim3((unsigned)((Wo * C + 255) / 256), (unsigned)Ho, (unsigned)B), dim3(256), 0, stream,
-                       static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), H, W, Ho, Wo, C, ix_dev, wx_dev, nx, iy_dev, wy_dev, ny,
-                       static_cast<const unsigned char*>(background_dev));
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 

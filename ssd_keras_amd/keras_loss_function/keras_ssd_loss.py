@@ -19,8 +19,6 @@ class _SSDLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y_true, y_pred, neg_pos_ratio, n_neg_min, alpha):
         lib = nat.load()
-        if not hasattr(lib, 'ssdhip_loss_forward'):
-            raise nat.SsdHipError("libssdhip.so was built without the loss kernels")
         y_true = y_true.detach()
         yp = y_pred.detach()
         if y_true.dtype != torch.float32:
@@ -40,10 +38,8 @@ class _SSDLossFn(torch.autograd.Function):
         keep = torch.empty((B, N), dtype=torch.uint8, device=dev)
         ws = nat.workspaces.get(dev, 'loss', lib.ssdhip_loss_workspace_bytes(B, N, C))
         p = lambda t: ctypes.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = lib.ssdhip_loss_forward(p(y_true), p(yp), B, N, C, int(neg_pos_ratio), int(n_neg_min), float(alpha),
-                                         p(loss), p(stats), p(keep), p(ws), ws.numel(), nat.current_stream_ptr(dev))
-        nat.check(rc, 'ssdhip_loss_forward')
+        nat.launch('ssdhip_loss_forward', dev, p(y_true), p(yp), B, N, C, int(neg_pos_ratio), int(n_neg_min), float(alpha), p(loss),
+                   p(stats), p(keep), p(ws), ws.numel())
         ctx.save_for_backward(y_true, yp, keep, stats)
         ctx.alpha = float(alpha)
         ctx.in_dtype = y_pred.dtype
@@ -53,15 +49,11 @@ class _SSDLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loss, _gs, _gk):
         y_true, yp, keep, stats = ctx.saved_tensors
-        lib = nat.load()
         B, N, L = yp.shape
         grad = torch.empty_like(yp)
         go = grad_loss.detach().float().contiguous()
         p = lambda t: ctypes.c_void_p(t.data_ptr())
-        with torch.cuda.device(yp.device):
-            rc = lib.ssdhip_loss_backward(p(y_true), p(yp), p(keep), p(stats), p(go), B, N, L - 12, ctx.alpha, p(grad),
-                                          nat.current_stream_ptr(yp.device))
-        nat.check(rc, 'ssdhip_loss_backward')
+        nat.launch('ssdhip_loss_backward', yp.device, p(y_true), p(yp), p(keep), p(stats), p(go), B, N, L - 12, ctx.alpha, p(grad))
         return None, grad.to(ctx.in_dtype), None, None, None
 
 

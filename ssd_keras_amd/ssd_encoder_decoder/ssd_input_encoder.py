@@ -171,9 +171,7 @@ class SSDInputEncoder:
     def encode_to_device(self, ground_truth_labels, device=None, want_f32=True, want_f64=False, want_matches=False):
         '''Run the encoder kernels; outputs stay in HBM.  Returns (y_f32 | None, y_f64 | None, match_gt | None).'''
         import torch
-        lib = nat.load()
-        if not hasattr(lib, 'ssdhip_encode'):
-            raise nat.SsdHipError("libssdhip.so was built without the encoder")
+        nat.load()
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device())
         gt, offsets, max_g = self._pack_ground_truth(ground_truth_labels)
@@ -237,13 +235,10 @@ class SSDInputEncoder:
         need = lib.ssdhip_encode_workspace_bytes(B, N, C, int(n_gt))
         ws = nat.workspaces.get(device, 'encode', need)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(device):
-            rc = lib.ssdhip_encode(ptr(anchors), ptr(variances), ptr(gt_d), ptr(off_d), int(n_gt), int(max_gt_per_image), B, N, C,
-                                   float(self.img_height), float(self.img_width), 1 if self.matching_type == 'multi' else 0,
-                                   float(self.pos_iou_threshold), float(self.neg_iou_limit), nat.COORDS[self.coords],
-                                   int(bool(self.normalize_coords)), nat.BORDER[self.border_pixels], int(self.background_id),
-                                   ptr(y32), ptr(y64), ptr(mm), ptr(ws), ws.numel(), nat.current_stream_ptr(device))
-        nat.check(rc, 'ssdhip_encode')
+        nat.launch('ssdhip_encode', device, ptr(anchors), ptr(variances), ptr(gt_d), ptr(off_d), int(n_gt), int(max_gt_per_image), B, N,
+                   C, float(self.img_height), float(self.img_width), 1 if self.matching_type == 'multi' else 0,
+                   float(self.pos_iou_threshold), float(self.neg_iou_limit), nat.COORDS[self.coords], int(bool(self.normalize_coords)),
+                   nat.BORDER[self.border_pixels], int(self.background_id), ptr(y32), ptr(y64), ptr(mm), ptr(ws), ws.numel())
         return y32, y64, mm
 
     def __call__(self, ground_truth_labels, diagnostics=False):

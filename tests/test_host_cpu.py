@@ -15,9 +15,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def lib():
+    """The library build() writes, as `_native.load()` declares it (every export typed from SIGNATURES)."""
+    from ssd_keras_amd import _native as nat
     from ssd_keras_amd import build
-    path = build.build()
-    return ctypes.CDLL(path)
+    assert build.build() == nat.lib_path()
+    return nat.load()
 
 
 def test_library_exports_every_declared_symbol(lib):
@@ -26,10 +28,46 @@ def test_library_exports_every_declared_symbol(lib):
     assert len(names) >= 10
     for n in names:
         assert hasattr(lib, n), n
-    lib.ssdhip_abi_version.restype = ctypes.c_int
     assert lib.ssdhip_abi_version() == 1
-    lib.ssdhip_strerror.restype = ctypes.c_char_p
     assert b"workspace" in lib.ssdhip_strerror(-2)
+
+
+def _header_prototypes():
+    """{name: (return type, [parameter types])} of every prototype in include/ssdhip.h, comments and preprocessor lines stripped."""
+    src = open(os.path.join(ROOT, "include", "ssdhip.h")).read()
+    src = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", " ", src, flags=re.S | re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([^;{}]*?)\b(ssdhip_[a-z_0-9]+)\s*\(([^;{}]*)\)\s*;", src):
+        assert name not in protos, "declared twice: " + name
+        params = [" ".join(p.split()) for p in params.split(",")] if params.strip() not in ("", "void") else []
+        # drop each parameter's name: the type is what precedes it
+        protos[name] = (" ".join(ret.split()), [p if "*" in p.rsplit(" ", 1)[-1] else p.rsplit(" ", 1)[0] for p in params])
+    return protos
+
+
+def test_signature_table_matches_the_header():
+    """_native.SIGNATURES, the ctypes declaration of every export, against the C prototypes: ctypes does not notice a mismatch (a
+    `long long` or a `double` declared as c_int is silently truncated or misread), so the table is checked argument by argument."""
+    from ssd_keras_amd import _native as nat
+    scalar = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "double": ctypes.c_double,
+              "float": ctypes.c_float}
+
+    def matches(ctype, declared):
+        if "*" in ctype:
+            return declared in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(declared, ctypes._Pointer)
+        key = " ".join(w for w in ctype.split() if w != "const")
+        assert key in scalar, "no ctypes kind for C type %r" % ctype
+        return declared is scalar[key]
+
+    protos = _header_prototypes()
+    assert len(protos) >= 10
+    assert sorted(nat.SIGNATURES) == sorted(protos)
+    for name, (ret, params) in protos.items():
+        declared_ret, declared_args = nat.SIGNATURES[name]
+        assert matches(ret, declared_ret), "%s returns %s, declared %s" % (name, ret, declared_ret)
+        assert len(declared_args) == len(params), "%s takes %d arguments, declared %d" % (name, len(params), len(declared_args))
+        for i, (ctype, declared) in enumerate(zip(params, declared_args)):
+            assert matches(ctype, declared), "%s argument %d is %s, declared %s" % (name, i, ctype, declared)
 
 
 def test_integration_doc_names_every_export():
@@ -41,8 +79,6 @@ def test_integration_doc_names_every_export():
 
 
 def test_workspace_sizes(lib):
-    for fn in (lib.ssdhip_decode_workspace_bytes, lib.ssdhip_encode_workspace_bytes, lib.ssdhip_loss_workspace_bytes):
-        fn.restype = ctypes.c_size_t
     d = lib.ssdhip_decode_workspace_bytes(32, 8732, 21, 200, 400, 0, 0)
     assert 32 * 8732 * (16 + 20 * 8) <= d < 2 * 32 * 8732 * (16 + 20 * 8)
     d64 = lib.ssdhip_decode_workspace_bytes(32, 8732, 21, 200, 400, 0, 1)              # float64 predictions: its own, larger layout
@@ -243,10 +279,7 @@ def test_evaluator_ground_truth_packing():
 
 def test_entry_points_reject_bad_arguments_before_launching(lib):
     """Argument validation happens on the host, ahead of any launch: callable without a GPU."""
-    vp, ci = ctypes.c_void_p, ctypes.c_int
     conv = lib.ssdhip_conv2d_nhwc_bf16
-    conv.restype = ci
-    conv.argtypes = [vp] * 4 + [ci] * 10 + [vp]
     dummy = ctypes.create_string_buffer(64)
     a = ctypes.addressof(dummy)
     a += (-a) % 16                                                    # a 16-byte aligned, non-null fake pointer (never dereferenced)
@@ -262,12 +295,8 @@ def test_entry_points_reject_bad_arguments_before_launching(lib):
                 dict(H=2, W=2, pad=0)):
         assert call(**bad) == -1, bad
     same = lib.ssdhip_conv2d_same_nhwc_bf16
-    same.restype = ci
-    same.argtypes = [vp] * 4 + [ci] * 8 + [vp]
     assert same(a, a, None, a, 1, 8, 8, 64, 48, 3, 1, 1, None) == -1
     loss = lib.ssdhip_loss_forward
-    loss.restype = ci
-    loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, vp]
     assert loss(a, a, 2, 10, 6, 3, 0, 1.0, a, a, a, a, 16, None) == -2                      # SSDHIP_E_WORKSPACE: too small
     assert loss(a, a, 2, 10, 1, 3, 0, 1.0, a, a, a, a, 1 << 20, None) == -1                 # C < 2
 
