@@ -634,6 +634,18 @@ int ssdhip_image_resize_gather_cv_u8(const void* x, void* y, int B, int H, int W
  * Identity tables with pre / post set are an exact integer translation. */
 int ssdhip_image_warp_affine_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* geo_dev, const int* xtab_dev,
                                 const int* ytab_dev, const void* background_dev, void* stream);
+/* Ragged batches: B uint8 images of different sizes concatenated in one device buffer; table [B][4] int64 = byte offset (a multiple of
+ * 4; the package aligns to 256), H, W, C with C in {1, 3, 4}.
+ * ssdhip_image_resize_gather_ragged_u8: ssdhip_image_resize_gather_cv_u8 with image b read through its table entry and ConvertTo3Channels
+ *   (data_generator/object_detection_2d_photometric_ops.py:88-107) folded into the read: C = 1 replicated, C = 4 alpha dropped;
+ *   y [B][Ho][Wo][3]; tap indices address image b's own rows / columns (clamped into it), -1 reads background [B][3].
+ * ssdhip_image_program_ragged_u8: ssdhip_image_program (uint8 -> uint8) on a ragged batch of C = 3 images, image i runs ops[i]; y has x's
+ *   layout; max_pixels = the largest H W of the batch. */
+int ssdhip_image_resize_gather_ragged_u8(const void* x, const long long* table_dev, void* y, int B, int Ho, int Wo, const int* plan_dev,
+                                         const int* ix_dev, const double* wx_dev, int nx, const int* iy_dev, const double* wy_dev, int ny,
+                                         const void* background_dev, void* stream);
+int ssdhip_image_program_ragged_u8(const void* x, const long long* table_dev, void* y, int B, long long max_pixels, const int* ops_dev,
+                                   const double* args_dev, void* stream);
 int ssdhip_image_hist_u8(const void* x, long long n_pixels, int C, int channel, unsigned int* hist_dev, void* stream);
 int ssdhip_image_lut_u8(const void* x, void* y, long long n_values, int C, int channel_mask, const void* table_dev, void* stream);
 
@@ -740,6 +752,14 @@ int ssdhip_ssd_augment_decide_stream(const ssdhip_augment_params* params, const 
                                      const unsigned int* mt_state, const double* labels, const int* n_labels, int* programs_ops,
                                      double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
                                      unsigned int* mt_state_out, void* stream);
+/* The two decision exports for a ragged batch (table_dev [B][4] int64 as ssdhip_image_resize_gather_ragged_u8's): image b's (H, W) come
+ * from its table entry instead of params->img_height / img_width (which must still be positive).  Same outputs as the uniform forms. */
+int ssdhip_ssd_augment_decide_stream_ragged(const ssdhip_augment_params* params, const ssdhip_augment_photo* photo, int B,
+                                            const long long* table_dev, const unsigned int* mt_state, const double* labels,
+                                            const int* n_labels, int* programs_ops, double* programs_args, int* geometry,
+                                            double* labels_out, int* n_labels_out, unsigned int* mt_state_out, void* stream);
+int ssdhip_augment_plans_ragged(const int* geometry_dev, const long long* table_dev, int B, int out_h, int out_w, int n_taps, int* plan_dev,
+                                int* ix_dev, double* wx_dev, int* iy_dev, double* wy_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,8 @@ SIGNATURES = {
     "ssdhip_image_resize_cv_u8": (_I, [_P, _P] + [_I] * 8 + [_P, _P, _I, _P, _P, _I, _P]),
     "ssdhip_image_resize_gather_cv_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 3 + [_I, _P, _P, _I, _P, _P]),
     "ssdhip_image_warp_affine_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 5),
+    "ssdhip_image_resize_gather_ragged_u8": (_I, [_P, _P, _P] + [_I] * 3 + [_P] * 3 + [_I, _P, _P, _I, _P, _P]),
+    "ssdhip_image_program_ragged_u8": (_I, [_P, _P, _P, _I, _LL] + [_P] * 3),
     "ssdhip_image_hist_u8": (_I, [_P, _LL, _I, _I, _P, _P]),
     "ssdhip_image_lut_u8": (_I, [_P, _P, _LL, _I, _I, _P, _P]),
     "ssdhip_conv3x3_image_nhwc_bf16": (_I, [_P] * 4 + [_I] * 7 + [_P]),
@@ -153,6 +155,8 @@ SIGNATURES = {
     "ssdhip_augment_plans": (_I, [_P] + [_I] * 6 + [_P] * 6),
     "ssdhip_ssd_augment_decide": (_I, [_PARAMS, _I] + [_P] * 8),
     "ssdhip_ssd_augment_decide_stream": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 10),
+    "ssdhip_ssd_augment_decide_stream_ragged": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 11),
+    "ssdhip_augment_plans_ragged": (_I, [_P, _P] + [_I] * 4 + [_P] * 6),
 }
 
 
@@ -1678,6 +1682,54 @@ def image_resize_gather_cv_u8(images, out_h, out_w, plans, ix, wx, iy, wy, backg
     return out
 
 
+def image_resize_gather_ragged_u8(data, table, out_h, out_w, plans, ix, wx, iy, wy, background):
+    """ssdhip_image_resize_gather_ragged_u8: a ragged batch (data: CUDA uint8 buffer, table (B, 4) int64 CUDA tensor = byte offset, H, W, C;
+    _image_ops.pack_ragged) -> the (B, out_h, out_w, 3) uint8 batch, ConvertTo3Channels folded in.  plans (B, 4) int32, tables ix / wx
+    (B, out_w, nx), iy / wy (B, out_h, ny) (index -1 = background), background (B, 3) uint8, as image_resize_gather_cv_u8's."""
+    torch = _torch()
+    require_cuda(data, "data")
+    require_cuda(table, "table")
+    if data.dtype != torch.uint8 or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4:
+        raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
+    b, dev = int(table.shape[0]), data.device
+    plans = to_device(plans, device=dev, dtype=torch.int32).contiguous()
+    ix = to_device(ix, device=dev, dtype=torch.int32).contiguous()
+    wx = to_device(wx, device=dev, dtype=torch.float64).contiguous()
+    iy = to_device(iy, device=dev, dtype=torch.int32).contiguous()
+    wy = to_device(wy, device=dev, dtype=torch.float64).contiguous()
+    bg = to_device(background, device=dev, dtype=torch.uint8).contiguous()
+    pad = lambda t: torch.cat([t, torch.zeros_like(t)], dim=2)
+    if ix.shape[2] < 2:
+        ix, wx = pad(ix), pad(wx)
+    if iy.shape[2] < 2:
+        iy, wy = pad(iy), pad(wy)
+    if (ix.shape != wx.shape or iy.shape != wy.shape or tuple(ix.shape[:2]) != (b, out_w) or tuple(iy.shape[:2]) != (b, out_h)
+            or tuple(bg.shape) != (b, 3) or tuple(plans.shape) != (b, 4)):
+        raise SsdHipError("plans must be (B, 4), tap tables (B, out_w, nx) / (B, out_h, ny), background (B, 3)")
+    out = torch.empty((b, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    launch("ssdhip_image_resize_gather_ragged_u8", dev, _ptr(data), _ptr(table), _ptr(out), b, int(out_h), int(out_w), _ptr(plans), _ptr(ix),
+           _ptr(wx), int(ix.shape[2]), _ptr(iy), _ptr(wy), int(iy.shape[2]), _ptr(bg))
+    return out
+
+
+def image_program_ragged_u8(data, table, max_pixels, ops, args):
+    """ssdhip_image_program_ragged_u8: per-image uint8 -> uint8 programs on a ragged batch of 3-channel images (data, table as
+    image_resize_gather_ragged_u8's); ops (B, 16) int32, args (B, 16) float64.  Returns a buffer with data's layout."""
+    torch = _torch()
+    require_cuda(data, "data")
+    require_cuda(table, "table")
+    if data.dtype != torch.uint8 or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4:
+        raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
+    b, dev = int(table.shape[0]), data.device
+    ops = to_device(ops, device=dev, dtype=torch.int32).contiguous()
+    args = to_device(args, device=dev, dtype=torch.float64).contiguous()
+    if tuple(ops.shape) != (b, IMG_PROG) or tuple(args.shape) != (b, IMG_PROG):
+        raise SsdHipError("ops / args must be (%d, %d)" % (b, IMG_PROG))
+    out = torch.empty_like(data)
+    launch("ssdhip_image_program_ragged_u8", dev, _ptr(data), _ptr(table), _ptr(out), b, int(max_pixels), _ptr(ops), _ptr(args))
+    return out
+
+
 def image_warp_affine_u8(images, out_h, out_w, geo, xtab, ytab, background):
     """ssdhip_image_warp_affine_u8 (cv2.warpAffine, INTER_LINEAR, BORDER_CONSTANT, 8-bit; csrc/ssdhip_warp.hip): images (B, H, W, C)
     CUDA uint8; geo (B, 5) int32 [flip, pre_dx, pre_dy, post_dx, post_dy]; per-image tables xtab (B, out_w, 2), ytab (B, out_h, 2) int32
@@ -1771,6 +1823,20 @@ def ssd_augment_decide(params, mt_states, labels, n_labels, device):
 
 
 def ssd_augment_decide_stream(params, photo, mt_state, labels, n_labels, device):
+    """See _decide_stream (the uniform batch: params' img_height / img_width are every image's size)."""
+    return _decide_stream(params, photo, mt_state, labels, n_labels, device, None)
+
+
+def ssd_augment_decide_stream_ragged(params, photo, mt_state, labels, n_labels, table):
+    """`ssdhip_ssd_augment_decide_stream_ragged`: as ssd_augment_decide_stream, image b's (H, W) from `table` (B, 4) int64 CUDA tensor
+    (pack_ragged's: byte offset, H, W, C); params' img_height / img_width are the batch's largest."""
+    if tuple(table.shape) != (int(labels.shape[0]), 4) or table.dtype != _torch().int64:
+        raise SsdHipError("ssd_augment_decide_stream_ragged: table (B, 4) int64")
+    require_cuda(table, "table")
+    return _decide_stream(params, photo, mt_state, labels, n_labels, table.device, table)
+
+
+def _decide_stream(params, photo, mt_state, labels, n_labels, device, table):
     """`ssdhip_ssd_augment_decide_stream`: the whole batch on ONE generator stream, photometric decisions included (round 6).  params as
     ssd_augment_decide; photo = dict(prob, lower, upper: four values each for brightness / contrast / saturation / hue, swap_prob);
     mt_state (625,) uint32 (np.random.get_state(): the 624 key words + the position), labels (B, 64, 5) float64, n_labels (B,) int32.
@@ -1805,9 +1871,12 @@ def ssd_augment_decide_stream(params, photo, mt_state, labels, n_labels, device)
     dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
     base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
     vp = ctypes.c_void_p
-    launch("ssdhip_ssd_augment_decide_stream", device, ctypes.byref(q), ctypes.byref(ph), B, vp(base_in + nl), vp(base_in),
-           vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args), vp(base_out + o_geo), vp(base_out), vp(base_out + o_n),
-           vp(base_out + o_mt))
+    outs = (vp(base_in + nl), vp(base_in), vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args), vp(base_out + o_geo),
+            vp(base_out), vp(base_out + o_n), vp(base_out + o_mt))
+    if table is None:
+        launch("ssdhip_ssd_augment_decide_stream", device, ctypes.byref(q), ctypes.byref(ph), B, *outs)
+    else:
+        launch("ssdhip_ssd_augment_decide_stream_ragged", device, ctypes.byref(q), ctypes.byref(ph), B, _ptr(table), *outs)
     geo_dev = dev_out[o_geo:o_geo + B * 48].view(torch.int32).view(B, 12)
     ops_dev = dev_out[o_ops:o_ops + B * IMG_PROG * 4].view(torch.int32).view(B, IMG_PROG)
     args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG)
@@ -1831,5 +1900,22 @@ def augment_plans(geo_dev, H, W, out_h, out_w, n_taps):
     iy = torch.empty((B, out_h, n_taps), dtype=torch.int32, device=dev)
     wy = torch.empty((B, out_h, n_taps), dtype=torch.float64, device=dev)
     launch("ssdhip_augment_plans", dev, _ptr(geo_dev), B, int(H), int(W), int(out_h), int(out_w), int(n_taps), _ptr(plans), _ptr(ix),
+           _ptr(wx), _ptr(iy), _ptr(wy))
+    return plans, ix, wx, iy, wy
+
+
+def augment_plans_ragged(geo_dev, table, out_h, out_w, n_taps):
+    """`ssdhip_augment_plans_ragged`: augment_plans for a ragged batch, image b's size from `table` (B, 4) int64 CUDA tensor."""
+    torch = _torch()
+    B, dev = int(geo_dev.shape[0]), geo_dev.device
+    require_cuda(table, "table")
+    if tuple(table.shape) != (B, 4) or table.dtype != torch.int64:
+        raise SsdHipError("augment_plans_ragged: table (B, 4) int64")
+    plans = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ix = torch.empty((B, out_w, n_taps), dtype=torch.int32, device=dev)
+    wx = torch.empty((B, out_w, n_taps), dtype=torch.float64, device=dev)
+    iy = torch.empty((B, out_h, n_taps), dtype=torch.int32, device=dev)
+    wy = torch.empty((B, out_h, n_taps), dtype=torch.float64, device=dev)
+    launch("ssdhip_augment_plans_ragged", dev, _ptr(geo_dev), _ptr(table), B, int(out_h), int(out_w), int(n_taps), _ptr(plans), _ptr(ix),
            _ptr(wx), _ptr(iy), _ptr(wy))
     return plans, ix, wx, iy, wy

@@ -115,8 +115,9 @@ __device__ __forceinline__ int aug_position(Mt& s, int lane, int extent, int siz
 }
 
 // The geometric decisions of ONE image (SSDExpand, SSDRandomCrop, RandomFlip, ResizeRandomInterp + the label arithmetic) by one wave on
-// the generator state `s`: what SSDDataAugmentation.__call__ does behind the photometric part (:208-280).
-__device__ __forceinline__ void aug_decide_image(const AugParams& p, Mt& s, const int lane, const int b, const double* __restrict__ lab_in,
+// the generator state `s`: what SSDDataAugmentation.__call__ does behind the photometric part (:208-280).  (H0, W0): the image's size.
+__device__ __forceinline__ void aug_decide_image(const AugParams& p, Mt& s, const int lane, const int b, const int H0, const int W0,
+                                                 const double* __restrict__ lab_in,
                                                  const int* __restrict__ n_in, int* __restrict__ geo, double* __restrict__ lab_out,
                                                  int* __restrict__ n_out) {
     const int n = n_in[b];
@@ -126,7 +127,7 @@ __device__ __forceinline__ void aug_decide_image(const AugParams& p, Mt& s, cons
         const double* r = lab_in + ((size_t)b * AUG_MAXG + lane) * 5;
         cls = r[0]; x0 = r[1]; y0 = r[2]; x1 = r[3]; y1 = r[4];
     }
-    int H = p.H, W = p.W;
+    int H = H0, W = W0;
     int g[12] = {0, 0, 0, H, W, 0, 0, 0, H, W, 0, 0};
 
     // ---- SSDExpand: RandomPatch(prob), one trial, no validator: the image on a canvas of 1 .. 4 times its size ----------------------
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(64) void ssd_augment_decide_kernel(AugParams p, con
     s.pos = (int)mt_in[(size_t)b * 625 + 624];
     s.base = -1; s.win = 0u;
     __syncthreads();
-    aug_decide_image(p, s, lane, b, lab_in, n_in, geo, lab_out, n_out);
+    aug_decide_image(p, s, lane, b, p.H, p.W, lab_in, n_in, geo, lab_out, n_out);
     if (lane == 0) mt_out[(size_t)b * 625 + 624] = (u32)s.pos;
     __syncthreads();
     for (int i = lane; i < 624; i += 64) mt_out[(size_t)b * 625 + i] = key[i];
@@ -235,10 +236,22 @@ __global__ __launch_bounds__(64) void ssd_augment_decide_kernel(AugParams p, con
 struct AugPhoto {                                         // RandomBrightness / Contrast / Saturation / Hue: prob, uniform(lo, hi); swap: prob 0
     double prob[4], lo[4], hi[4], swap_prob;
 };
-constexpr int AUG_PROG = 16;                              // steps of a program (include/ssdhip.h: SSDHIP_IMG_PROG)
+constexpr int AUG_PROG = 16;
+// The size of image b: the batch's (uniform) or the image's own from the ragged table [B][4] int64 = byte offset, H, W, C.
+struct UniformHW {
+    int H, W;
+    __device__ __forceinline__ int h(int) const { return H; }
+    __device__ __forceinline__ int w(int) const { return W; }
+};
+struct RaggedHW {
+    const long long* table;
+    __device__ __forceinline__ int h(int b) const { return (int)table[(size_t)b * 4 + 1]; }
+    __device__ __forceinline__ int w(int b) const { return (int)table[(size_t)b * 4 + 2]; }
+};                              // steps of a program (include/ssdhip.h: SSDHIP_IMG_PROG)
 enum { OP_END = 0, OP_TO_F32 = 1, OP_TO_U8 = 2, OP_BRIGHTNESS = 3, OP_CONTRAST = 4, OP_SATURATION = 5, OP_HUE = 6, OP_RGB2HSV = 7, OP_HSV2RGB = 8 };
 
-__global__ __launch_bounds__(64) void ssd_augment_stream_kernel(AugParams p, AugPhoto ph, int B, const u32* __restrict__ mt_in,
+template <class HW>
+__global__ __launch_bounds__(64) void ssd_augment_stream_kernel(AugParams p, AugPhoto ph, HW hw, int B, const u32* __restrict__ mt_in,
                                                                 const double* __restrict__ lab_in, const int* __restrict__ n_in,
                                                                 int* __restrict__ prog_ops, double* __restrict__ prog_args,
                                                                 int* __restrict__ geo, double* __restrict__ lab_out, int* __restrict__ n_out,
@@ -275,7 +288,7 @@ __global__ __launch_bounds__(64) void ssd_augment_stream_kernel(AugParams p, Aug
         if (lane == 0)
             for (int i = 0; i < AUG_PROG; ++i) { prog_ops[(size_t)b * AUG_PROG + i] = ops[i]; prog_args[(size_t)b * AUG_PROG + i] = args[i]; }
         // ---- the geometric half on the same stream ------------------------------------------------------------------------------------
-        aug_decide_image(p, s, lane, b, lab_in, n_in, geo, lab_out, n_out);
+        aug_decide_image(p, s, lane, b, hw.h(b), hw.w(b), lab_in, n_in, geo, lab_out, n_out);
     }
     if (lane == 0) mt_out[624] = (u32)s.pos;
     __syncthreads();
@@ -338,13 +351,15 @@ __device__ __forceinline__ AugPlan aug_plan_of(int Hc, int Wc, int out_h, int ou
 }
 
 // grid (blocks over positions, 2 axes, B); axis 0 = columns (x), 1 = rows (y); plan [B][4] = kind, area, taps per column, taps per row
-__global__ __launch_bounds__(128) void aug_plan_kernel(const int* __restrict__ geo, int H, int W, int out_h, int out_w, int n_taps,
+template <class HW>
+__global__ __launch_bounds__(128) void aug_plan_kernel(const int* __restrict__ geo, HW hw, int out_h, int out_w, int n_taps,
                                                        int* __restrict__ plan, int* __restrict__ ix, double* __restrict__ wx,
                                                        int* __restrict__ iy, double* __restrict__ wy) {
     const int b = (int)blockIdx.z, axis = (int)blockIdx.y;
     const int n_dst = axis == 0 ? out_w : out_h;
     const int i = (int)blockIdx.x * 128 + (int)threadIdx.x;
     const int* g = geo + (size_t)b * 12;
+    const int H = hw.h(b), W = hw.w(b);
     const int Hc = g[8], Wc = g[9];
     const AugPlan q = aug_plan_of(Hc, Wc, out_h, out_w, g[11], n_taps);
     if (axis == 0 && i == 0) { plan[b * 4] = q.kind; plan[b * 4 + 1] = q.area; plan[b * 4 + 2] = q.tx; plan[b * 4 + 3] = q.ty; }
@@ -481,8 +496,33 @@ extern "C" int ssdhip_ssd_augment_decide_stream(const ssdhip_augment_params* q, 
         ph.prob[i] = photo->prob[i]; ph.lo[i] = photo->lower[i]; ph.hi[i] = photo->upper[i];
     }
     ph.swap_prob = 0.0;
-    hipLaunchKernelGGL(ssd_augment_stream_kernel, dim3(1), dim3(64), 0, stream, p, ph, B, mt_state, labels, n_labels, programs_ops,
-                       programs_args, geometry, labels_out, n_labels_out, mt_state_out);
+    hipLaunchKernelGGL(ssd_augment_stream_kernel<UniformHW>, dim3(1), dim3(64), 0, stream, p, ph, UniformHW{p.H, p.W}, B, mt_state, labels,
+                       n_labels, programs_ops, programs_args, geometry, labels_out, n_labels_out, mt_state_out);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// The same walk over a ragged batch: image b's (H, W) from table_dev [B][4] int64 (byte offset, H, W, C) instead of params->img_height /
+// img_width (which must still be positive: the largest H and W of the batch).  Same outputs.
+extern "C" int ssdhip_ssd_augment_decide_stream_ragged(const ssdhip_augment_params* q, const ssdhip_augment_photo* photo, int B,
+                                                       const long long* table_dev, const unsigned int* mt_state, const double* labels,
+                                                       const int* n_labels, int* programs_ops, double* programs_args, int* geometry,
+                                                       double* labels_out, int* n_labels_out, unsigned int* mt_state_out, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!q || !photo || B <= 0 || !table_dev || !mt_state || !labels || !n_labels || !programs_ops || !programs_args || !geometry ||
+        !labels_out || !n_labels_out || !mt_state_out)
+        return SSDHIP_E_BADARG;
+    if (photo->swap_prob != 0.0) return SSDHIP_E_BADARG;
+    AugParams p;
+    const int rc = aug_params_from(q, p);
+    if (rc != SSDHIP_OK) return rc;
+    AugPhoto ph;
+    for (int i = 0; i < 4; ++i) {
+        if (!(photo->prob[i] >= 0.0 && photo->prob[i] <= 1.0)) return SSDHIP_E_BADARG;
+        ph.prob[i] = photo->prob[i]; ph.lo[i] = photo->lower[i]; ph.hi[i] = photo->upper[i];
+    }
+    ph.swap_prob = 0.0;
+    hipLaunchKernelGGL(ssd_augment_stream_kernel<RaggedHW>, dim3(1), dim3(64), 0, stream, p, ph, RaggedHW{table_dev}, B, mt_state, labels,
+                       n_labels, programs_ops, programs_args, geometry, labels_out, n_labels_out, mt_state_out);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 
@@ -523,7 +563,22 @@ extern "C" int ssdhip_augment_plans(const int* geometry_dev, int B, int H, int W
         return SSDHIP_E_BADARG;
     if (n_taps < 8 || n_taps > 64) return SSDHIP_E_BADARG;                       // Lanczos-4 needs eight
     const int n = out_h > out_w ? out_h : out_w;
-    hipLaunchKernelGGL(aug_plan_kernel, dim3((unsigned)((n + 127) / 128), 2, (unsigned)B), dim3(128), 0, stream, geometry_dev, H, W, out_h,
-                       out_w, n_taps, plan_dev, ix_dev, wx_dev, iy_dev, wy_dev);
+    hipLaunchKernelGGL(aug_plan_kernel<UniformHW>, dim3((unsigned)((n + 127) / 128), 2, (unsigned)B), dim3(128), 0, stream, geometry_dev,
+                       UniformHW{H, W}, out_h, out_w, n_taps, plan_dev, ix_dev, wx_dev, iy_dev, wy_dev);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// ssdhip_augment_plans for a ragged batch: image b's canvas bounds from table_dev [B][4] int64 (byte offset, H, W, C); the plans index
+// each image's own rows / columns (ssdhip_image_resize_gather_ragged_u8).
+extern "C" int ssdhip_augment_plans_ragged(const int* geometry_dev, const long long* table_dev, int B, int out_h, int out_w, int n_taps,
+                                           int* plan_dev, int* ix_dev, double* wx_dev, int* iy_dev, double* wy_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!geometry_dev || !table_dev || !plan_dev || !ix_dev || !wx_dev || !iy_dev || !wy_dev || B <= 0 || B > 65535 || out_h <= 0 ||
+        out_w <= 0)
+        return SSDHIP_E_BADARG;
+    if (n_taps < 8 || n_taps > 64) return SSDHIP_E_BADARG;
+    const int n = out_h > out_w ? out_h : out_w;
+    hipLaunchKernelGGL(aug_plan_kernel<RaggedHW>, dim3((unsigned)((n + 127) / 128), 2, (unsigned)B), dim3(128), 0, stream, geometry_dev,
+                       RaggedHW{table_dev}, out_h, out_w, n_taps, plan_dev, ix_dev, wx_dev, iy_dev, wy_dev);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }

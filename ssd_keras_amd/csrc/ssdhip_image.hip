@@ -204,11 +204,27 @@ __global__ __launch_bounds__(256) void pixel_program_kernel(const void* __restri
     }
 }
 
+// How a batch's images are laid out: image `img` starts `offset(img)` bytes into the buffer and has `count(img)` pixels.  Uniform: the
+// (B, H, W, 3) tensor.  Ragged: B images of different sizes in one buffer, table [B][4] int64 = byte offset, H, W, C (the offsets 256-byte
+// aligned by the host, so every image starts on a dword).
+struct UniformImages {
+    long long pixels;
+    __device__ __forceinline__ long long offset(int img) const { return (long long)img * pixels * 3; }
+    __device__ __forceinline__ long long count(int) const { return pixels; }
+};
+struct RaggedImages {
+    const long long* table;
+    __device__ __forceinline__ long long offset(int img) const { return table[(size_t)img * 4]; }
+    __device__ __forceinline__ long long count(int img) const { return table[(size_t)img * 4 + 1] * table[(size_t)img * 4 + 2]; }
+};
+
 // The uint8 -> uint8 form (the photometric distortions of a whole batch): FOUR pixels = 12 bytes = three dwords per thread and trip, so
 // a wave moves 768 contiguous bytes per load / store instruction instead of 64 single bytes at a 3-byte stride; every program step is
 // decoded once for the four pixels; OpenCV's two 8-bit HSV division tables sit in LDS (built once per workgroup) instead of two integer
-// divisions per pixel.  Same arithmetic, same results as pixel_program_kernel.  pixels % 4 == 0 (the host checks; else the generic kernel).
-__global__ __launch_bounds__(256) void pixel_program_u8x4_kernel(const unsigned int* __restrict__ x, unsigned int* __restrict__ y, long long pixels,
+// divisions per pixel.  Same arithmetic, same results as pixel_program_kernel.  The last count % 4 pixels of an image (ragged batches
+// only: the uniform form is launched for pixels % 4 == 0) take one work item each, byte by byte.
+template <class Imgs>
+__global__ __launch_bounds__(256) void pixel_program_u8x4_kernel(const unsigned char* __restrict__ x, unsigned char* __restrict__ y, Imgs imgs,
                                                                  const int* __restrict__ ops, const double* __restrict__ args) {
     __shared__ int sdiv[256], hdiv[256];
     sdiv[threadIdx.x] = img_div_table(255 << 12, (int)threadIdx.x, 1);
@@ -217,10 +233,25 @@ __global__ __launch_bounds__(256) void pixel_program_u8x4_kernel(const unsigned 
     const int img = blockIdx.y;
     const int* op = ops + (size_t)img * IMG_PROG;
     const double* arg = args + (size_t)img * IMG_PROG;
-    const long long groups = pixels / 4;
-    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long long)gridDim.x * 256) {
-        const size_t e = ((size_t)img * groups + g) * 3;                 // dword index of the group's 12 bytes
-        const unsigned int w0 = x[e], w1 = x[e + 1], w2 = x[e + 2];
+    const long long pixels = imgs.count(img), off = imgs.offset(img);
+    const unsigned int* xw = reinterpret_cast<const unsigned int*>(x + off);
+    unsigned int* yw = reinterpret_cast<unsigned int*>(y + off);
+    const long long groups = pixels / 4, items = groups + (pixels - groups * 4);
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < items; g += (long long)gridDim.x * 256) {
+        if (g >= groups) {                                               // the tail: one pixel
+            const size_t e = (size_t)(groups * 4 + (g - groups)) * 3;
+            double px[1][3] = {{(double)x[off + e], (double)x[off + e + 1], (double)x[off + e + 2]}};
+            int tag = IMG_U8;
+            for (int k = 0; k < IMG_PROG; ++k) {
+                const int o = op[k];
+                if (o == OP_END) break;
+                img_apply<1>(px, tag, o, arg[k], sdiv, hdiv);
+            }
+            y[off + e] = (unsigned char)px[0][0]; y[off + e + 1] = (unsigned char)px[0][1]; y[off + e + 2] = (unsigned char)px[0][2];
+            continue;
+        }
+        const size_t e = (size_t)g * 3;                                  // dword index of the group's 12 bytes
+        const unsigned int w0 = xw[e], w1 = xw[e + 1], w2 = xw[e + 2];
         double px[4][3];
         px[0][0] = w0 & 255u; px[0][1] = (w0 >> 8) & 255u; px[0][2] = (w0 >> 16) & 255u;
         px[1][0] = w0 >> 24; px[1][1] = w1 & 255u; px[1][2] = (w1 >> 8) & 255u;
@@ -237,9 +268,9 @@ __global__ __launch_bounds__(256) void pixel_program_u8x4_kernel(const unsigned 
         for (int n = 0; n < 4; ++n)
 #pragma unroll
             for (int q = 0; q < 3; ++q) b[n * 3 + q] = (unsigned int)(unsigned char)px[n][q];
-        y[e] = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
-        y[e + 1] = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
-        y[e + 2] = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+        yw[e] = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+        yw[e + 1] = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+        yw[e + 2] = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
     }
 }
 
@@ -310,12 +341,44 @@ __global__ __launch_bounds__(256) void resize_cv_kernel(const unsigned char* __r
     y[((size_t)b * Ho + yo) * Wo * C + v] = cv_resample(kind, area, nx, ny, wx + (size_t)xo * nx, wy + (size_t)yo * ny, px);
 }
 
+// Where the gather reads image b's channel ch: `at(sy, sx)` = the source value at row sy, column sx.  Uniform: the (B, H, W, C) tensor.
+// Ragged: the table [B][4] of RaggedImages, output channel ch read from source channel ch (C = 3, 4: alpha never read) or 0 (C = 1, grey
+// replicated) -- ConvertTo3Channels folded into the read; indices clamped into the image (a plan built for other sizes cannot leave it).
+struct UniformGatherSrc {
+    const unsigned char* x;
+    int H, W, C;
+    struct View {
+        const unsigned char* p;
+        int W, C;
+        __device__ __forceinline__ int at(int sy, int sx) const { return (int)p[((size_t)sy * W + sx) * C]; }
+    };
+    __device__ __forceinline__ View view(int b, int ch) const { return View{x + (size_t)b * H * W * C + ch, W, C}; }
+};
+struct RaggedGatherSrc {
+    const unsigned char* x;
+    const long long* table;
+    struct View {
+        const unsigned char* p;
+        int H, W, C;
+        __device__ __forceinline__ int at(int sy, int sx) const {
+            sy = sy < H ? sy : H - 1; sx = sx < W ? sx : W - 1;
+            return (int)p[((size_t)sy * W + sx) * C];
+        }
+    };
+    __device__ __forceinline__ View view(int b, int ch) const {
+        const long long* t = table + (size_t)b * 4;
+        const int c = (int)t[3];
+        return View{x + t[0] + (c == 1 ? 0 : ch), (int)t[1], (int)t[2], c};
+    }
+};
+
 // every image its own plan (the augmentation chain's gather launch): plan [B][4] = kind, area, taps per column, taps per row (<= nx, ny =
 // the tables' strides); ix / wx [B][Wo][nx], iy / wy [B][Ho][ny]; index -1 = the expansion canvas -> background [B][C]
-__global__ __launch_bounds__(256) void resize_gather_cv_kernel(const unsigned char* __restrict__ x, unsigned char* __restrict__ y, int H,
-                                                               int W, int Ho, int Wo, int C, const int* __restrict__ plan,
-                                                               const int* __restrict__ ix, const double* __restrict__ wx, int nx,
-                                                               const int* __restrict__ iy, const double* __restrict__ wy, int ny,
+template <class Src>
+__global__ __launch_bounds__(256) void resize_gather_cv_kernel(Src src, unsigned char* __restrict__ y, int Ho, int Wo, int C,
+                                                               const int* __restrict__ plan, const int* __restrict__ ix,
+                                                               const double* __restrict__ wx, int nx, const int* __restrict__ iy,
+                                                               const double* __restrict__ wy, int ny,
                                                                const unsigned char* __restrict__ background) {
     const int v = (int)blockIdx.x * 256 + (int)threadIdx.x, yo = (int)blockIdx.y, b = (int)blockIdx.z;
     if (v >= Wo * C) return;
@@ -324,10 +387,10 @@ __global__ __launch_bounds__(256) void resize_gather_cv_kernel(const unsigned ch
     const int bg = (int)background[b * C + ch];
     const int* ixb = ix + ((size_t)b * Wo + xo) * nx;
     const int* iyb = iy + ((size_t)b * Ho + yo) * ny;
-    const unsigned char* src = x + (size_t)b * H * W * C;
+    const typename Src::View img = src.view(b, ch);
     auto px = [&](int j, int k) -> int {
         const int sy = iyb[j], sx = ixb[k];
-        return (sy < 0 || sx < 0) ? bg : (int)src[((size_t)sy * W + sx) * C + ch];
+        return (sy < 0 || sx < 0) ? bg : img.at(sy, sx);
     };
     y[((size_t)b * Ho + yo) * Wo * C + v] = cv_resample(kind, area, tx < nx ? tx : nx, ty < ny ? ty : ny, wx + ((size_t)b * Wo + xo) * nx,
                                                         wy + ((size_t)b * Ho + yo) * ny, px);
@@ -373,8 +436,9 @@ extern "C" int ssdhip_image_program(const void* x, int in_dtype, void* y, int ou
     if (!x || !y || !ops_dev || !args_dev || n_images <= 0 || n_images > 65535 || pixels_per_image <= 0) return SSDHIP_E_BADARG;
     if (in_dtype < IMG_U8 || in_dtype > IMG_F64 || out_dtype < IMG_U8 || out_dtype > IMG_F64) return SSDHIP_E_BADARG;
     if (in_dtype == IMG_U8 && out_dtype == IMG_U8 && pixels_per_image % 4 == 0 && !(((uintptr_t)x | (uintptr_t)y) & 3)) {
-        hipLaunchKernelGGL(pixel_program_u8x4_kernel, dim3(img_blocks(pixels_per_image / 4, 2048), n_images), dim3(256), 0, stream,
-                           static_cast<const unsigned int*>(x), static_cast<unsigned int*>(y), pixels_per_image, ops_dev, args_dev);
+        hipLaunchKernelGGL(pixel_program_u8x4_kernel<UniformImages>, dim3(img_blocks(pixels_per_image / 4, 2048), n_images), dim3(256), 0,
+                           stream, static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), UniformImages{pixels_per_image},
+                           ops_dev, args_dev);
         return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
     }
     hipLaunchKernelGGL(pixel_program_kernel, dim3(img_blocks(pixels_per_image, 4096), n_images), dim3(256), 0, stream, x, in_dtype, y, out_dtype,
@@ -404,9 +468,37 @@ extern "C" int ssdhip_image_resize_gather_cv_u8(const void* x, void* y, int B, i
     if (!x || !y || !plan_dev || !ix_dev || !wx_dev || !iy_dev || !wy_dev || !background_dev) return SSDHIP_E_BADARG;
     if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || Ho <= 0 || Ho > 65535 || Wo <= 0 || C <= 0 || C > 4 || nx < 2 || ny < 2 || nx > 64 || ny > 64)
         return SSDHIP_E_BADARG;
-    hipLaunchKernelGGL(resize_gather_cv_kernel, dim3((unsigned)((Wo * C + 255) / 256), (unsigned)Ho, (unsigned)B), dim3(256), 0, stream,
-                       static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), H, W, Ho, Wo, C, plan_dev, ix_dev, wx_dev, nx,
-                       iy_dev, wy_dev, ny, static_cast<const unsigned char*>(background_dev));
+    hipLaunchKernelGGL(resize_gather_cv_kernel<UniformGatherSrc>, dim3((unsigned)((Wo * C + 255) / 256), (unsigned)Ho, (unsigned)B), dim3(256),
+                       0, stream, UniformGatherSrc{static_cast<const unsigned char*>(x), H, W, C}, static_cast<unsigned char*>(y), Ho, Wo, C,
+                       plan_dev, ix_dev, wx_dev, nx, iy_dev, wy_dev, ny, static_cast<const unsigned char*>(background_dev));
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// ---- ragged batches: B uint8 images of different sizes in one buffer, table [B][4] int64 = byte offset, H, W, C ----------------------
+// The gather of ssdhip_image_resize_gather_cv_u8 with each image read through its table entry and ConvertTo3Channels folded into the read
+// (C = 1 replicated, C = 4 alpha dropped): y [B][Ho][Wo][3].  The tables' indices address each image's own rows / columns.
+extern "C" int ssdhip_image_resize_gather_ragged_u8(const void* x, const long long* table_dev, void* y, int B, int Ho, int Wo,
+                                                    const int* plan_dev, const int* ix_dev, const double* wx_dev, int nx, const int* iy_dev,
+                                                    const double* wy_dev, int ny, const void* background_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!x || !table_dev || !y || !plan_dev || !ix_dev || !wx_dev || !iy_dev || !wy_dev || !background_dev) return SSDHIP_E_BADARG;
+    if (B <= 0 || B > 65535 || Ho <= 0 || Ho > 65535 || Wo <= 0 || Wo > (1 << 24) || nx < 2 || ny < 2 || nx > 64 || ny > 64)
+        return SSDHIP_E_BADARG;
+    hipLaunchKernelGGL(resize_gather_cv_kernel<RaggedGatherSrc>, dim3((unsigned)((Wo * 3 + 255) / 256), (unsigned)Ho, (unsigned)B), dim3(256),
+                       0, stream, RaggedGatherSrc{static_cast<const unsigned char*>(x), table_dev}, static_cast<unsigned char*>(y), Ho, Wo,
+                       3, plan_dev, ix_dev, wx_dev, nx, iy_dev, wy_dev, ny, static_cast<const unsigned char*>(background_dev));
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// The photometric programs of ssdhip_image_program (uint8 -> uint8) on a ragged batch of 3-channel images, one program per image, ONE
+// launch: y has x's layout (the same table); max_pixels = the largest H W of the batch (sizes the grid).
+extern "C" int ssdhip_image_program_ragged_u8(const void* x, const long long* table_dev, void* y, int B, long long max_pixels,
+                                              const int* ops_dev, const double* args_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!x || !table_dev || !y || !ops_dev || !args_dev || B <= 0 || B > 65535 || max_pixels <= 0) return SSDHIP_E_BADARG;
+    if (((uintptr_t)x | (uintptr_t)y) & 3) return SSDHIP_E_BADARG;
+    hipLaunchKernelGGL(pixel_program_u8x4_kernel<RaggedImages>, dim3(img_blocks((max_pixels + 3) / 4, 2048), B), dim3(256), 0, stream,
+                       static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), RaggedImages{table_dev}, ops_dev, args_dev);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 

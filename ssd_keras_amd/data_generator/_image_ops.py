@@ -161,6 +161,108 @@ def gather_batch(images, lazies):
     return nat.image_resize_gather_cv_u8(images.contiguous(), out_h, out_w, kinds, ix, wx, iy, wy, bg)
 
 
+# ---- ragged batches: images of different sizes in one device buffer ----------------------------------------------------------------
+RAGGED_ALIGN = 256                                           # byte alignment of every image in a ragged buffer
+
+
+class RaggedBatch:
+    """B uint8 images of different sizes on the device: `data` (a CUDA uint8 buffer), `table` ((B, 4) int64 CUDA tensor: byte offset into
+    `data`, H, W, C), `shapes` (the B (H, W, C) on the host) and `max_pixels` (the largest H W)."""
+
+    def __init__(self, data, table, shapes):
+        self.data, self.table, self.shapes = data, table, [tuple(int(v) for v in s) for s in shapes]
+        self.max_pixels = max(h * w for h, w, _ in self.shapes)
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def like(self, data):
+        return RaggedBatch(data, self.table, self.shapes)
+
+
+def _hwc(image):
+    shape = tuple(int(v) for v in image.shape)
+    if len(shape) == 2:
+        return shape + (1,)
+    if len(shape) == 3 and shape[2] in (1, 3, 4):
+        return shape
+    raise ValueError("a ragged batch takes (H, W) or (H, W, C) images with C in (1, 3, 4), not %s" % (shape,))
+
+
+def pack_ragged(images, device=None):
+    """A list of uint8 images (NumPy arrays or CUDA tensors, (H, W) or (H, W, C), C in 1 / 3 / 4) -> RaggedBatch.  Host images cross
+    PCIe in ONE copy: [table | image 0 | image 1 | ...], each part starting on a RAGGED_ALIGN boundary."""
+    import torch
+    if len(images) == 0:
+        raise ValueError("a ragged batch holds at least one image")
+    shapes = [_hwc(im) for im in images]
+    for im in images:
+        if (im.dtype != np.uint8) if isinstance(im, np.ndarray) else (im.dtype != torch.uint8):
+            raise TypeError("ragged batches hold uint8 images")
+    B = len(images)
+    head = -(-B * 32 // RAGGED_ALIGN) * RAGGED_ALIGN
+    offsets, pos = [], 0
+    for h, w, c in shapes:
+        offsets.append(pos)
+        pos += -(-h * w * c // RAGGED_ALIGN) * RAGGED_ALIGN
+    table = np.array([(o, h, w, c) for o, (h, w, c) in zip(offsets, shapes)], dtype=np.int64)
+    if device is None:
+        dev = next((im.device for im in images if torch.is_tensor(im) and im.is_cuda), None)
+        device = dev if dev is not None else torch.device("cuda", torch.cuda.current_device())
+    host = np.zeros((head + pos,), dtype=np.uint8)
+    host[:B * 32] = table.view(np.uint8).ravel()
+    on_device = []
+    for im, o, (h, w, c) in zip(images, offsets, shapes):
+        if isinstance(im, np.ndarray):
+            host[head + o:head + o + h * w * c] = np.ascontiguousarray(im).reshape(-1)
+        else:
+            on_device.append((im, o, h * w * c))
+    buf = torch.from_numpy(host).to(device)
+    for im, o, n in on_device:                               # device images: copied into place on the device
+        buf[head + o:head + o + n].copy_(im.reshape(-1))
+    return RaggedBatch(buf[head:], buf[:B * 32].view(torch.int64).view(B, 4), shapes)
+
+
+def gather_batch_ragged(packed, lazies):
+    """Execute the recorded geometry of a ragged batch: lazies[i] a resized GeoImage over image i (its index maps address image i's own
+    rows / columns) -> the (B, out_h, out_w, 3) uint8 batch, ONE launch; 1- and 4-channel images are read as ConvertTo3Channels makes them."""
+    sizes = {l.resized[:2] for l in lazies}
+    if len(sizes) != 1:
+        raise ValueError("every image of a batch must end in the same size")
+    if len(lazies) != len(packed):
+        raise ValueError("one lazy image per image of the batch")
+    out_h, out_w = sizes.pop()
+    plans = [l.plan() for l in lazies]
+    for (kind, area, sx, vx, sy, vy), (h, w, _) in zip(plans, packed.shapes):
+        if sx.max() >= w or sy.max() >= h:
+            raise ValueError("the recorded geometry is not of these images")
+    n = max(max(pl[2].shape[1], pl[4].shape[1]) for pl in plans)
+    n = 2 if n <= 2 else (4 if n <= 4 else (8 if n <= 8 else 16 if n <= 16 else n))
+    b = len(lazies)
+    ix, wx = np.zeros((b, out_w, n), dtype=np.int32), np.zeros((b, out_w, n), dtype=np.float64)
+    iy, wy = np.zeros((b, out_h, n), dtype=np.int32), np.zeros((b, out_h, n), dtype=np.float64)
+    kinds = np.zeros((b, 4), dtype=np.int32)                      # kind, area, taps per column, taps per row
+    for k, (kind, area, sx, vx, sy, vy) in enumerate(plans):
+        ix[k, :, :sx.shape[1]], wx[k, :, :sx.shape[1]] = sx, vx
+        iy[k, :, :sy.shape[1]], wy[k, :, :sy.shape[1]] = sy, vy
+        kinds[k] = (kind, area, sx.shape[1], sy.shape[1])
+    bg = np.array([(l.background if l.background is not None else (0, 0, 0)) for l in lazies], dtype=np.uint8)
+    return nat.image_resize_gather_ragged_u8(packed.data, packed.table, out_h, out_w, kinds, ix, wx, iy, wy, bg)
+
+
+def run_ragged(packed, programs):
+    """Per-image uint8 -> uint8 programs on a ragged batch of 3-channel images, ONE launch -> a RaggedBatch of the results."""
+    if any(c != 3 for _, _, c in packed.shapes):
+        raise ValueError("photometric programs take 3-channel images")
+    for p in programs:
+        if end_dtype(np.uint8, p) != U8:
+            raise ValueError("a ragged program must end in uint8")
+    enc = [encode(p) for p in programs]
+    out = nat.image_program_ragged_u8(packed.data, packed.table, packed.max_pixels, np.stack([e[0] for e in enc]),
+                                      np.stack([e[1] for e in enc]))
+    return packed.like(out)
+
+
 # ---- cv2.resize for 8-bit images: the tables of OpenCV's imgproc/resize.cpp (3.4 / 4.x), the arithmetic runs in csrc/ssdhip_image.hip ----
 # cv::resize on CV_8U (round 6; the first version resampled with float64 weights and one rounding, off by one grey level here and there):
 #   LINEAR / CUBIC / LANCZOS4, and AREA when an axis grows ("area_mode" bilinear): per output column / row the float32 kernel values become

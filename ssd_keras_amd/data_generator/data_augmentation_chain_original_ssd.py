@@ -148,6 +148,10 @@ class SSDDataAugmentation:
         does) takes every other decision of the chain -- expansion, the crop search with its IoU validation, flip, interpolation mode --
         and does the label arithmetic.  The global NumPy generator is left untouched."""
         import torch
+        if isinstance(images, (list, tuple)):
+            if seeds is not None:
+                raise ValueError("seeds= takes a (B, H, W, 3) CUDA batch; a list of images runs on the global np.random stream")
+            return self._augment_ragged(images, labels)
         if seeds is not None:
             return self._augment_batch_seeded(images, labels, seeds)
         if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3):
@@ -175,6 +179,77 @@ class SSDDataAugmentation:
             out_labels.append(lab)
         distorted = iop.run_batch(images, programs)
         return iop.gather_batch(distorted, lazies), out_labels
+
+    def _augment_ragged(self, images, labels):
+        """augment_batch for a LIST of (H_i, W_i, 3) uint8 images of different sizes (NumPy arrays or CUDA tensors): one upload
+        (iop.pack_ragged), then the launches of the uniform path on the ragged layout -- the decisions of the whole batch on the global
+        np.random stream (ssdhip_ssd_augment_decide_stream_ragged), the photometric programs (ssdhip_image_program_ragged_u8), the tap
+        tables (ssdhip_augment_plans_ragged) and one gather (ssdhip_image_resize_gather_ragged_u8).  Same pixels, labels and final
+        np.random state as calling the chain on image 0, 1, 2, ...; a configuration or label layout the kernel does not cover takes the
+        per-image chain's own code (host decisions, the same two pixel launches)."""
+        from .. import _native as nat
+        if len(labels) != len(images):
+            raise ValueError("one label array per image")
+        if any(len(im.shape) != 3 or int(im.shape[2]) != 3 for im in images):
+            raise TypeError("augment_batch takes a list of (H, W, 3) uint8 images")
+        for t in (self.expand, self.random_crop, self.random_flip, self.resize):
+            t.labels_format = self.labels_format
+        packed = iop.pack_ragged(list(images))
+        B = len(packed)
+        lf = self.labels_format
+        cols = [lf['class_id'], lf['xmin'], lf['ymin'], lf['xmax'], lf['ymax']]
+        arrs = [np.asarray(lab) for lab in labels]
+        h_max, w_max = max(s[0] for s in packed.shapes), max(s[1] for s in packed.shapes)
+        params, photo, state = self._seeded_params(h_max, w_max), self._photo_params(), np.random.get_state()
+        dtypes = {a.dtype for a in arrs}
+        fast = (params is not None and photo is not None and state[0] == 'MT19937' and len(dtypes) == 1
+                and next(iter(dtypes)) in (np.dtype(np.int64), np.dtype(np.float64)) and sorted(cols) == [0, 1, 2, 3, 4]
+                and all(a.ndim == 2 and a.shape[1] == 5 and a.shape[0] <= nat.AUG_MAX_BOXES for a in arrs))
+        out_h, out_w = int(self.resize.height), int(self.resize.width)
+        n_taps = max(8, int(np.ceil(float(self.expand.expand.patch_coord_generator.max_scale) * max(h_max / out_h, w_max / out_w))) + 2)
+        if not fast:
+            programs, lazies, out_labels = [], [], []
+            for (h, w, _), lab in zip(packed.shapes, arrs):
+                programs.append(self.photometric_distortions.draw())
+                img = iop.GeoImage.of(h, w)
+                for transform in (self.expand, self.random_crop, self.random_flip, self.resize):
+                    img, lab = transform(img, lab)
+                lazies.append(img)
+                out_labels.append(lab)
+            return iop.gather_batch_ragged(iop.run_ragged(packed, programs), lazies), out_labels
+        lab_in = np.zeros((B, nat.AUG_MAX_BOXES, 5), dtype=np.float64)
+        n_in = np.empty((B,), dtype=np.int32)
+        for i, a in enumerate(arrs):
+            n_in[i] = a.shape[0]
+            if a.shape[0]:
+                lab_in[i, :a.shape[0]] = a[:, cols]
+        mt = np.empty((625,), dtype=np.uint32)
+        mt[:624], mt[624] = state[1], state[2]
+        ops_dev, args_dev, geo_dev, fetch = nat.ssd_augment_decide_stream_ragged(params, photo, mt, lab_in, n_in, packed.table)
+        distorted = packed.like(nat.image_program_ragged_u8(packed.data, packed.table, packed.max_pixels, ops_dev, args_dev))
+        inv = np.argsort(cols)
+        if n_taps <= 64:
+            plans, ix, wx, iy, wy = nat.augment_plans_ragged(geo_dev, packed.table, out_h, out_w, n_taps)
+            row = np.array([int(v) for v in self.expand.expand.background], dtype=np.uint8)
+            out = nat.image_resize_gather_ragged_u8(distorted.data, packed.table, out_h, out_w, plans, ix, wx, iy, wy, np.repeat(row[None], B, 0))
+            geo, lab_out, n_out, mt_out = fetch()
+        else:                                            # (a source too large for the device-built tables: host-built geometry)
+            geo, lab_out, n_out, mt_out = fetch()
+            out = iop.gather_batch_ragged(distorted, [self._lazy_of(geo[i], h, w) for i, (h, w, _) in enumerate(packed.shapes)])
+        dt = arrs[0].dtype
+        np.random.set_state((state[0], mt_out[:624], int(mt_out[624]), state[3], state[4]))
+        return out, [np.ascontiguousarray(lab_out[i, :int(n_out[i])][:, inv]).astype(dt) for i in range(B)]
+
+    def _lazy_of(self, g, h, w):
+        """The GeoImage of one image's recorded geometry (a row of ssdhip_ssd_augment_decide*'s `geometry`)."""
+        img = iop.GeoImage.of(h, w)
+        if g[0]:
+            img = img.window(int(g[1]), int(g[2]), int(g[3]), int(g[4]), self.expand.expand.background)
+        if g[5]:
+            img = img.window(int(g[6]), int(g[7]), int(g[8]), int(g[9]), self.random_crop.random_crop.background)
+        if g[10]:
+            img = img[:, ::-1]
+        return img.resize(self.resize.height, self.resize.width, int(g[11]))
 
     def _seeded_params(self, h, w):
         """The chain's configuration as ssdhip_augment_params fields, or None when an op is not in the original-SSD configuration the

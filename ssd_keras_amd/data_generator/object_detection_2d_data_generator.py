@@ -1,0 +1,625 @@
+"""Drop-in for the reference's data_generator/object_detection_2d_data_generator.py: `DataGenerator`, the class every training and
+evaluation notebook gets its batches from, with the reference's parsers (CSV, Pascal VOC XML, MS COCO JSON), its pickled-dataset round
+trip and its `generate()` semantics -- removal of images without ground truth, inverters, degenerate-box handling, the order of the
+`returns` tuple, the reshuffle at every epoch wrap (`sklearn.utils.shuffle`, which draws from the global NumPy generator the augmentation
+chains read too).
+
+`generate()` picks how a batch is transformed from the transformation list it is given:
+  * `[SSDDataAugmentation]`: the images (any sizes) go to the device as ONE ragged batch and the whole chain runs in a few launches
+    (`SSDDataAugmentation.augment_batch` on a list of images);
+  * `[ConvertTo3Channels, Resize]`, `[ConvertTo3Channels, RandomPadFixedAR, Resize]` (the evaluation lists): the label logic and the
+    inverters are the transforms' own host code on lazy images (`_image_ops.GeoImage`), the pixels of the batch ONE gather launch over the
+    ragged batch (`_image_ops.gather_batch_ragged`, 1- and 4-channel images folded to three channels in the read);
+  * `[DataAugmentationConstantInputSize]` on images of one size: `DataAugmentationConstantInputSize.augment_batch`;
+  * anything else: the reference's per-image loop over the package's transforms.
+Every path gives the per-image loop's pixels, labels, inverters and final `np.random` state.  Images are decoded by PIL on the host, as in
+the reference.  HDF5 datasets are not supported (h5py is not a dependency of this package); their parameter and methods raise
+`DatasetError`.  The parsers' XML reader is `xml.etree.ElementTree` (the reference uses BeautifulSoup) with the same results."""
+from __future__ import annotations
+
+import csv
+import inspect
+import json
+import os
+import pickle
+import sys
+import warnings
+from collections import defaultdict
+from copy import deepcopy
+from xml.etree import ElementTree
+
+import numpy as np
+
+from .object_detection_2d_image_boxes_validation_utils import BoxFilter
+
+
+class DegenerateBatchError(Exception):
+    '''Raised when a generated batch ends up degenerate, e.g. empty.'''
+    pass
+
+
+class DatasetError(Exception):
+    '''Raised when anything is wrong with the dataset, in particular when batches are requested before a dataset was loaded.'''
+    pass
+
+
+_HDF5 = ("HDF5 datasets are not supported by this package (h5py is not one of its dependencies): parse the dataset with parse_csv / "
+         "parse_xml / parse_json or pass file lists, and use save_dataset / get_dataset to keep it.")
+
+
+def _progress(items, desc, verbose):
+    if not verbose:
+        return items
+    try:
+        from tqdm import tqdm
+    except ImportError:                                    # the progress bar is cosmetic
+        return items
+    return tqdm(items, desc=desc, file=sys.stdout)
+
+
+def _load_image(filename):
+    from PIL import Image
+    with Image.open(filename) as image:
+        return np.array(image, dtype=np.uint8)
+
+
+class DataGenerator:
+    '''Generates batches of samples and their labels indefinitely, shuffling the dataset consistently after each complete pass
+    (reference :66-1220).  See the module docstring for how batches are transformed.'''
+
+    def __init__(self,
+                 load_images_into_memory=False,
+                 hdf5_dataset_path=None,
+                 filenames=None,
+                 filenames_type='text',
+                 images_dir=None,
+                 labels=None,
+                 image_ids=None,
+                 eval_neutral=None,
+                 labels_output_format=('class_id', 'xmin', 'ymin', 'xmax', 'ymax'),
+                 verbose=True):
+        self.labels_output_format = labels_output_format
+        self.labels_format = {'class_id': labels_output_format.index('class_id'),
+                              'xmin': labels_output_format.index('xmin'),
+                              'ymin': labels_output_format.index('ymin'),
+                              'xmax': labels_output_format.index('xmax'),
+                              'ymax': labels_output_format.index('ymax')}
+        self.dataset_size = 0
+        self.load_images_into_memory = load_images_into_memory
+        self.images = None
+
+        if filenames is not None:
+            if isinstance(filenames, (list, tuple)):
+                self.filenames = filenames
+            elif isinstance(filenames, str):
+                with open(filenames, 'rb') as f:
+                    if filenames_type == 'pickle':
+                        self.filenames = pickle.load(f)
+                    elif filenames_type == 'text':
+                        self.filenames = [os.path.join(images_dir, line.strip().decode()) for line in f]
+                    else:
+                        raise ValueError("`filenames_type` can be either 'text' or 'pickle'.")
+            else:
+                raise ValueError("`filenames` must be either a Python list/tuple or a string representing a filepath (to a pickled or text "
+                                 "file). The value you passed is neither of the two.")
+            self.dataset_size = len(self.filenames)
+            self.dataset_indices = np.arange(self.dataset_size, dtype=np.int32)
+            if load_images_into_memory:
+                self.images = [_load_image(f) for f in _progress(self.filenames, 'Loading images into memory', verbose)]
+        else:
+            self.filenames = None
+
+        self.labels = self._list_or_pickle(labels, "labels")
+        self.image_ids = self._list_or_pickle(image_ids, "image_ids")
+        self.eval_neutral = self._list_or_pickle(eval_neutral, "image_ids")
+
+        self.hdf5_dataset = None
+        if hdf5_dataset_path is not None:
+            self.hdf5_dataset_path = hdf5_dataset_path
+            self.load_hdf5_dataset(verbose=verbose)
+
+    @staticmethod
+    def _list_or_pickle(value, name):
+        if value is None:
+            return None
+        if isinstance(value, str):
+            with open(value, 'rb') as f:
+                return pickle.load(f)
+        if isinstance(value, (list, tuple)):
+            return value
+        raise ValueError("`{}` must be either a Python list/tuple or a string representing the path to a pickled file containing a "
+                         "list/tuple. The value you passed is neither of the two.".format(name))
+
+    def _load_images(self, verbose):
+        self.dataset_size = len(self.filenames)
+        self.dataset_indices = np.arange(self.dataset_size, dtype=np.int32)
+        if self.load_images_into_memory:
+            self.images = [_load_image(f) for f in _progress(self.filenames, 'Loading images into memory', verbose)]
+
+    def load_hdf5_dataset(self, verbose=True):
+        '''Reference :241-285 (h5py): not supported here.'''
+        raise DatasetError(_HDF5)
+
+    def create_hdf5_dataset(self, file_path='dataset.h5', resize=False, variable_image_size=True, verbose=True):
+        '''Reference :597-740 (h5py): not supported here.'''
+        raise DatasetError(_HDF5)
+
+    # ---- parsers ---------------------------------------------------------------------------------------------------------------------
+    def parse_csv(self,
+                  images_dir,
+                  labels_filename,
+                  input_format,
+                  include_classes='all',
+                  random_sample=False,
+                  ret=False,
+                  verbose=True):
+        '''Reference :287-386: one box per CSV row (a header row first), rows sorted, grouped by image name; the image id is the name up
+        to its first dot.  `random_sample`: keep each image with that probability (one `np.random.uniform` draw per image).'''
+        self.images_dir = images_dir
+        self.labels_filename = labels_filename
+        self.input_format = input_format
+        self.include_classes = include_classes
+        if self.labels_filename is None or self.input_format is None:
+            raise ValueError("`labels_filename` and/or `input_format` have not been set yet. You need to pass them as arguments.")
+        self.filenames, self.image_ids, self.labels = [], [], []
+
+        data = []
+        with open(self.labels_filename, newline='') as csvfile:
+            csvread = csv.reader(csvfile, delimiter=',')
+            next(csvread)
+            for row in csvread:
+                if self.include_classes == 'all' or int(row[self.input_format.index('class_id')].strip()) in self.include_classes:
+                    box = [row[self.input_format.index('image_name')].strip()]
+                    for element in self.labels_output_format:
+                        box.append(int(row[self.input_format.index(element)].strip()))
+                    data.append(box)
+        data = sorted(data)
+
+        def add(current_file, current_image_id, current_labels):
+            if random_sample:
+                p = np.random.uniform(0, 1)
+                if not p >= (1 - random_sample):
+                    return
+            self.labels.append(np.stack(current_labels, axis=0))
+            self.filenames.append(os.path.join(self.images_dir, current_file))
+            self.image_ids.append(current_image_id)
+
+        current_file = data[0][0]
+        current_image_id = data[0][0].split('.')[0]
+        current_labels = []
+        for i, box in enumerate(data):
+            if box[0] != current_file:
+                add(current_file, current_image_id, current_labels)
+                current_labels = []
+                current_file = box[0]
+                current_image_id = box[0].split('.')[0]
+            current_labels.append(box[1:])
+            if i == len(data) - 1:
+                add(current_file, current_image_id, current_labels)
+
+        self._load_images(verbose)
+        if ret:
+            return self.images, self.filenames, self.labels, self.image_ids
+
+    def parse_xml(self,
+                  images_dirs,
+                  image_set_filenames,
+                  annotations_dirs=[],
+                  classes=['background',
+                           'aeroplane', 'bicycle', 'bird', 'boat',
+                           'bottle', 'bus', 'car', 'cat',
+                           'chair', 'cow', 'diningtable', 'dog',
+                           'horse', 'motorbike', 'person', 'pottedplant',
+                           'sheep', 'sofa', 'train', 'tvmonitor'],
+                  include_classes='all',
+                  exclude_truncated=False,
+                  exclude_difficult=False,
+                  ret=False,
+                  verbose=True):
+        '''Reference :388-521: Pascal VOC image sets (one image id per line) and their XML annotations; `difficult` boxes are marked in
+        `eval_neutral`.  Without annotation directories, `labels` and `eval_neutral` are None.'''
+        self.images_dirs = images_dirs
+        self.annotations_dirs = annotations_dirs
+        self.image_set_filenames = image_set_filenames
+        self.classes = classes
+        self.include_classes = include_classes
+        self.filenames, self.image_ids, self.labels, self.eval_neutral = [], [], [], []
+        if not annotations_dirs:
+            self.labels = None
+            self.eval_neutral = None
+            annotations_dirs = [None] * len(images_dirs)
+
+        for images_dir, image_set_filename, annotations_dir in zip(images_dirs, image_set_filenames, annotations_dirs):
+            with open(image_set_filename) as f:
+                image_ids = [line.strip() for line in f]
+                self.image_ids += image_ids
+            for image_id in _progress(image_ids, "Processing image set '{}'".format(os.path.basename(image_set_filename)), verbose):
+                filename = '{}'.format(image_id) + '.jpg'
+                self.filenames.append(os.path.join(images_dir, filename))
+                if annotations_dir is None:
+                    continue
+                root = ElementTree.parse(os.path.join(annotations_dir, image_id + '.xml')).getroot()
+                folder = root.find('.//folder').text
+                boxes, eval_neutr = [], []
+                for obj in root.iter('object'):
+                    class_name = obj.find('name').text
+                    class_id = self.classes.index(class_name)
+                    if (not self.include_classes == 'all') and (class_id not in self.include_classes):
+                        continue
+                    pose = obj.find('pose').text
+                    truncated = int(obj.find('truncated').text)
+                    if exclude_truncated and (truncated == 1):
+                        continue
+                    difficult = int(obj.find('difficult').text)
+                    if exclude_difficult and (difficult == 1):
+                        continue
+                    bndbox = obj.find('bndbox')
+                    item_dict = {'folder': folder, 'image_name': filename, 'image_id': image_id, 'class_name': class_name,
+                                 'class_id': class_id, 'pose': pose, 'truncated': truncated, 'difficult': difficult,
+                                 'xmin': int(bndbox.find('.//xmin').text), 'ymin': int(bndbox.find('.//ymin').text),
+                                 'xmax': int(bndbox.find('.//xmax').text), 'ymax': int(bndbox.find('.//ymax').text)}
+                    boxes.append([item_dict[item] for item in self.labels_output_format])
+                    eval_neutr.append(bool(difficult))
+                self.labels.append(boxes)
+                self.eval_neutral.append(eval_neutr)
+
+        self._load_images(verbose)
+        if ret:
+            return self.images, self.filenames, self.labels, self.image_ids, self.eval_neutral
+
+    def parse_json(self,
+                   images_dirs,
+                   annotations_filenames,
+                   ground_truth_available=False,
+                   include_classes='all',
+                   ret=False,
+                   verbose=True):
+        '''Reference :523-595: MS COCO annotation files; the 80 non-consecutive category ids become consecutive class ids 1..80
+        (`cats_to_classes`, `classes_to_cats`, `cats_to_names`, `classes_to_names`); boxes [x, y, w, h] become corners.'''
+        self.images_dirs = images_dirs
+        self.annotations_filenames = annotations_filenames
+        self.include_classes = include_classes
+        self.filenames, self.image_ids, self.labels = [], [], []
+        if not ground_truth_available:
+            self.labels = None
+
+        with open(annotations_filenames[0], 'r') as f:
+            annotations = json.load(f)
+        self.cats_to_names, self.classes_to_names, self.cats_to_classes, self.classes_to_cats = {}, ['background'], {}, {}
+        for i, cat in enumerate(annotations['categories']):
+            self.cats_to_names[cat['id']] = cat['name']
+            self.classes_to_names.append(cat['name'])
+            self.cats_to_classes[cat['id']] = i + 1
+            self.classes_to_cats[i + 1] = cat['id']
+
+        for images_dir, annotations_filename in zip(self.images_dirs, self.annotations_filenames):
+            with open(annotations_filename, 'r') as f:
+                annotations = json.load(f)
+            if ground_truth_available:
+                image_ids_to_annotations = defaultdict(list)
+                for annotation in annotations['annotations']:
+                    image_ids_to_annotations[annotation['image_id']].append(annotation)
+            for img in _progress(annotations['images'], "Processing '{}'".format(os.path.basename(annotations_filename)), verbose):
+                self.filenames.append(os.path.join(images_dir, img['file_name']))
+                self.image_ids.append(img['id'])
+                if not ground_truth_available:
+                    continue
+                boxes = []
+                for annotation in image_ids_to_annotations[img['id']]:
+                    cat_id = annotation['category_id']
+                    if (not self.include_classes == 'all') and (cat_id not in self.include_classes):
+                        continue
+                    xmin, ymin, width, height = annotation['bbox'][:4]
+                    item_dict = {'image_name': img['file_name'], 'image_id': img['id'], 'class_id': self.cats_to_classes[cat_id],
+                                 'xmin': xmin, 'ymin': ymin, 'xmax': xmin + width, 'ymax': ymin + height}
+                    boxes.append([item_dict[item] for item in self.labels_output_format])
+                self.labels.append(boxes)
+
+        self._load_images(verbose)
+        if ret:
+            return self.images, self.filenames, self.labels, self.image_ids
+
+    # ---- batches ---------------------------------------------------------------------------------------------------------------------
+    def _shuffle(self):
+        import sklearn.utils
+        objects_to_shuffle = [self.dataset_indices]
+        for obj in (self.filenames, self.labels, self.image_ids, self.eval_neutral):
+            if obj is not None:
+                objects_to_shuffle.append(obj)
+        shuffled_objects = sklearn.utils.shuffle(*objects_to_shuffle)
+        for i in range(len(objects_to_shuffle)):
+            objects_to_shuffle[i][:] = shuffled_objects[i]
+
+    @staticmethod
+    def _batch_path(transformations, images, have_labels):
+        """Which batch path a transformation list takes (see the module docstring); None = the per-image loop."""
+        from .data_augmentation_chain_constant_input_size import DataAugmentationConstantInputSize
+        from .data_augmentation_chain_original_ssd import SSDDataAugmentation
+        from .object_detection_2d_geometric_ops import Resize
+        from .object_detection_2d_patch_sampling_ops import RandomPadFixedAR
+        from .object_detection_2d_photometric_ops import ConvertTo3Channels
+        kinds = [type(t) for t in transformations]
+        if not images or any(not isinstance(im, np.ndarray) or im.dtype != np.uint8 for im in images):
+            return None
+        if any(im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] not in (1, 3, 4)) for im in images):
+            return None
+        if kinds in ([ConvertTo3Channels, Resize], [ConvertTo3Channels, RandomPadFixedAR, Resize]):
+            return 'gather'
+        if not have_labels:
+            return None
+        if kinds == [SSDDataAugmentation]:
+            return 'ssd'
+        if (kinds == [DataAugmentationConstantInputSize] and len({im.shape for im in images}) == 1 and images[0].ndim == 3
+                and images[0].shape[2] == 3):
+            return 'constant'
+        return None
+
+    def _transform_batch(self, path, transformations, images, labels, want_inverters):
+        """The batch paths: images (uint8 NumPy) and labels (arrays, or None) of the items that are transformed -> (CUDA (n, H, W, 3)
+        uint8 batch, labels or None, inverters per item)."""
+        import torch
+        from . import _image_ops as iop
+        if path == 'ssd':
+            three = [im if (im.ndim == 3 and im.shape[2] == 3) else transformations[0].photometric_distortions.convert_to_3_channels(im)
+                     for im in images]
+            out, out_labels = transformations[0].augment_batch(three, labels)
+            return out, out_labels, [[] for _ in images]
+        if path == 'constant':
+            batch = torch.from_numpy(np.stack(images)).to(torch.device('cuda', torch.cuda.current_device()))
+            out, out_labels = transformations[0].augment_batch(batch, labels)
+            return out, out_labels, [[] for _ in images]
+        # 'gather': the transforms' own host code on lazy images, then one launch for the pixels
+        lazies, out_labels, inverters = [], [], []
+        for k, im in enumerate(images):
+            img = iop.GeoImage.of(int(im.shape[0]), int(im.shape[1]))
+            lab = None if labels is None else labels[k]
+            inv = []
+            for transform in transformations:
+                takes = want_inverters and ('return_inverter' in inspect.signature(transform).parameters)
+                if lab is not None:
+                    if takes:
+                        img, lab, inverter = transform(img, lab, return_inverter=True)
+                        inv.append(inverter)
+                    else:
+                        img, lab = transform(img, lab)
+                else:
+                    if takes:
+                        img, inverter = transform(img, return_inverter=True)
+                        inv.append(inverter)
+                    else:
+                        img = transform(img)
+            lazies.append(img)
+            out_labels.append(lab)
+            inverters.append(inv[::-1])
+        out = iop.gather_batch_ragged(iop.pack_ragged(images), lazies)
+        return out, (None if labels is None else out_labels), inverters
+
+    def generate(self,
+                 batch_size=32,
+                 shuffle=True,
+                 transformations=[],
+                 label_encoder=None,
+                 returns={'processed_images', 'encoded_labels'},
+                 keep_images_without_gt=False,
+                 degenerate_box_handling='remove',
+                 device=None):
+        '''Reference :742-1157: yields lists of the `returns` in the order 'processed_images', 'encoded_labels', 'matched_anchors',
+        'processed_labels', 'filenames', 'image_ids', 'evaluation-neutral', 'inverse_transform', 'original_images', 'original_labels'.
+        `device` (not in the reference): 'processed_images' is the CUDA uint8 batch on that device, not downloaded, and 'encoded_labels'
+        come from `SSDInputEncoder.encode_to_device` (float64, on the device).'''
+        from ..ssd_encoder_decoder.ssd_input_encoder import SSDInputEncoder
+        if self.dataset_size == 0:
+            raise DatasetError("Cannot generate batches because you did not load a dataset.")
+
+        if self.labels is None:
+            if any([ret in returns for ret in ['original_labels', 'processed_labels', 'encoded_labels', 'matched_anchors', 'evaluation-neutral']]):
+                warnings.warn("Since no labels were given, none of 'original_labels', 'processed_labels', 'evaluation-neutral', 'encoded_labels', and 'matched_anchors' " +
+                              "are possible returns, but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
+        elif label_encoder is None:
+            if any([ret in returns for ret in ['encoded_labels', 'matched_anchors']]):
+                warnings.warn("Since no label encoder was given, 'encoded_labels' and 'matched_anchors' aren't possible returns, " +
+                              "but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
+        elif not isinstance(label_encoder, SSDInputEncoder):
+            if 'matched_anchors' in returns:
+                warnings.warn("`label_encoder` is not an `SSDInputEncoder` object, therefore 'matched_anchors' is not a possible return, " +
+                              "but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
+
+        if shuffle:
+            self._shuffle()
+        if degenerate_box_handling == 'remove':
+            box_filter = BoxFilter(check_overlap=False, check_min_area=False, check_degenerate=True, labels_format=self.labels_format)
+        if self.labels is not None:
+            for transform in transformations:
+                transform.labels_format = self.labels_format
+        if device is not None:
+            import torch
+            device = torch.device(device)
+
+        current = 0
+        while True:
+            batch_X, batch_y = [], []
+            if current >= self.dataset_size:
+                current = 0
+                if shuffle:
+                    self._shuffle()
+
+            batch_indices = self.dataset_indices[current:current + batch_size]
+            if self.images is not None:
+                for i in batch_indices:
+                    batch_X.append(self.images[i])
+                batch_filenames = self.filenames[current:current + batch_size] if self.filenames is not None else None
+            else:
+                batch_filenames = self.filenames[current:current + batch_size]
+                for filename in batch_filenames:
+                    batch_X.append(_load_image(filename))
+
+            batch_y = deepcopy(self.labels[current:current + batch_size]) if self.labels is not None else None
+            batch_eval_neutral = self.eval_neutral[current:current + batch_size] if self.eval_neutral is not None else None
+            batch_image_ids = self.image_ids[current:current + batch_size] if self.image_ids is not None else None
+            if 'original_images' in returns:
+                batch_original_images = deepcopy(batch_X)
+            if 'original_labels' in returns:
+                batch_original_labels = deepcopy(batch_y)
+            current += batch_size
+
+            batch_items_to_remove = []
+            batch_inverse_transforms = []
+            want_inverters = 'inverse_transform' in returns
+            path = self._batch_path(transformations, batch_X, self.labels is not None) if transformations else None
+            processed = None                                   # the batch paths' CUDA batch of the transformed items
+            if path is not None:
+                todo = []
+                for i in range(len(batch_X)):
+                    if self.labels is not None:
+                        batch_y[i] = np.array(batch_y[i])
+                        if (batch_y[i].size == 0) and not keep_images_without_gt:
+                            batch_items_to_remove.append(i)
+                            continue
+                    todo.append(i)
+                if todo:
+                    processed, out_labels, inverters = self._transform_batch(
+                        path, transformations, [batch_X[i] for i in todo], None if self.labels is None else [batch_y[i] for i in todo],
+                        want_inverters)
+                    for k, i in enumerate(todo):
+                        batch_X[i] = k                         # a row of `processed`
+                        if self.labels is not None:
+                            batch_y[i] = out_labels[k]
+                inv_of = dict(zip(todo, inverters)) if todo else {}
+                batch_inverse_transforms = [inv_of.get(i, []) for i in range(len(batch_X))]
+                for i in todo:
+                    self._check_degenerate(i, batch_y, degenerate_box_handling, box_filter if degenerate_box_handling == 'remove' else None,
+                                           keep_images_without_gt, batch_items_to_remove)
+            else:
+                for i in range(len(batch_X)):
+                    if self.labels is not None:
+                        batch_y[i] = np.array(batch_y[i])
+                        if (batch_y[i].size == 0) and not keep_images_without_gt:
+                            batch_items_to_remove.append(i)
+                            batch_inverse_transforms.append([])
+                            continue
+                    if transformations:
+                        inverse_transforms = []
+                        for transform in transformations:
+                            if self.labels is not None:
+                                if want_inverters and ('return_inverter' in inspect.signature(transform).parameters):
+                                    batch_X[i], batch_y[i], inverse_transform = transform(batch_X[i], batch_y[i], return_inverter=True)
+                                    inverse_transforms.append(inverse_transform)
+                                else:
+                                    batch_X[i], batch_y[i] = transform(batch_X[i], batch_y[i])
+                                if batch_X[i] is None:
+                                    batch_items_to_remove.append(i)
+                                    batch_inverse_transforms.append([])
+                                    continue
+                            else:
+                                if want_inverters and ('return_inverter' in inspect.signature(transform).parameters):
+                                    batch_X[i], inverse_transform = transform(batch_X[i], return_inverter=True)
+                                    inverse_transforms.append(inverse_transform)
+                                else:
+                                    batch_X[i] = transform(batch_X[i])
+                        batch_inverse_transforms.append(inverse_transforms[::-1])
+                    self._check_degenerate(i, batch_y, degenerate_box_handling, box_filter if degenerate_box_handling == 'remove' else None,
+                                           keep_images_without_gt, batch_items_to_remove)
+
+            if batch_items_to_remove:
+                for j in sorted(batch_items_to_remove, reverse=True):
+                    batch_X.pop(j)
+                    batch_filenames.pop(j)
+                    if batch_inverse_transforms:
+                        batch_inverse_transforms.pop(j)
+                    if self.labels is not None:
+                        batch_y.pop(j)
+                    if self.image_ids is not None:
+                        batch_image_ids.pop(j)
+                    if self.eval_neutral is not None:
+                        batch_eval_neutral.pop(j)
+                    if 'original_images' in returns:
+                        batch_original_images.pop(j)
+                    if 'original_labels' in returns and self.labels is not None:
+                        batch_original_labels.pop(j)
+
+            batch_X = self._assemble(batch_X, processed, device)
+            if (batch_X.numel() if device is not None else batch_X.size) == 0:
+                raise DegenerateBatchError("You produced an empty batch. This might be because the images in the batch vary " +
+                                           "in their size and/or number of channels. Note that after all transformations " +
+                                           "(if any were given) have been applied to all images in the batch, all images " +
+                                           "must be homogenous in size along all axes.")
+
+            batch_y_encoded, batch_matched_anchors = None, None
+            if not (label_encoder is None or self.labels is None):
+                if ('matched_anchors' in returns) and isinstance(label_encoder, SSDInputEncoder):
+                    batch_y_encoded, batch_matched_anchors = label_encoder(batch_y, diagnostics=True)
+                elif device is not None and isinstance(label_encoder, SSDInputEncoder):
+                    batch_y_encoded = label_encoder.encode_to_device(batch_y, device=device, want_f32=False, want_f64=True)[1]
+                else:
+                    batch_y_encoded = label_encoder(batch_y, diagnostics=False)
+
+            ret = []
+            if 'processed_images' in returns: ret.append(batch_X)
+            if 'encoded_labels' in returns: ret.append(batch_y_encoded)
+            if 'matched_anchors' in returns: ret.append(batch_matched_anchors)
+            if 'processed_labels' in returns: ret.append(batch_y)
+            if 'filenames' in returns: ret.append(batch_filenames)
+            if 'image_ids' in returns: ret.append(batch_image_ids)
+            if 'evaluation-neutral' in returns: ret.append(batch_eval_neutral)
+            if 'inverse_transform' in returns: ret.append(batch_inverse_transforms)
+            if 'original_images' in returns: ret.append(batch_original_images)
+            if 'original_labels' in returns: ret.append(batch_original_labels)
+            yield ret
+
+    def _check_degenerate(self, i, batch_y, handling, box_filter, keep_images_without_gt, batch_items_to_remove):
+        """Reference :774-795: degenerate boxes of item i after the transformations -> a warning, or BoxFilter removes them."""
+        if self.labels is None:
+            return
+        xmin, ymin = self.labels_format['xmin'], self.labels_format['ymin']
+        xmax, ymax = self.labels_format['xmax'], self.labels_format['ymax']
+        if np.any(batch_y[i][:, xmax] - batch_y[i][:, xmin] <= 0) or np.any(batch_y[i][:, ymax] - batch_y[i][:, ymin] <= 0):
+            if handling == 'warn':
+                warnings.warn("Detected degenerate ground truth bounding boxes for batch item {} with bounding boxes {}, ".format(i, batch_y[i]) +
+                              "i.e. bounding boxes where xmax <= xmin and/or ymax <= ymin. " +
+                              "This could mean that your dataset contains degenerate ground truth boxes, or that any image transformations you may apply might " +
+                              "result in degenerate ground truth boxes, or that you are parsing the ground truth in the wrong coordinate format." +
+                              "Degenerate ground truth bounding boxes may lead to NaN errors during the training.")
+            elif handling == 'remove':
+                batch_y[i] = box_filter(batch_y[i])
+                if (batch_y[i].size == 0) and not keep_images_without_gt:
+                    batch_items_to_remove.append(i)
+
+    @staticmethod
+    def _assemble(batch_X, processed, device):
+        """The batch as the reference's `np.array(batch_X)`, or as a CUDA tensor on `device`.  With a batch path, batch_X holds row
+        numbers of `processed` (the images that survived removal)."""
+        if processed is None:
+            batch = np.array(batch_X)
+            if device is None:
+                return batch
+            import torch
+            return torch.from_numpy(np.ascontiguousarray(batch)).to(device)
+        rows = list(batch_X)
+        if device is not None:
+            import torch
+            t = processed.to(device)
+            return t if rows == list(range(int(t.shape[0]))) else t[torch.as_tensor(rows, dtype=torch.long, device=t.device)]
+        host = processed.cpu().numpy()
+        return host if rows == list(range(host.shape[0])) else host[rows]
+
+    # ---- the dataset -----------------------------------------------------------------------------------------------------------------
+    def save_dataset(self,
+                     filenames_path='filenames.pkl',
+                     labels_path=None,
+                     image_ids_path=None,
+                     eval_neutral_path=None):
+        '''Reference :1159-1193: pickles the file names and, where a path is given, labels, image ids and eval_neutral.'''
+        with open(filenames_path, 'wb') as f:
+            pickle.dump(self.filenames, f)
+        for path, value in ((labels_path, self.labels), (image_ids_path, self.image_ids), (eval_neutral_path, self.eval_neutral)):
+            if path is not None:
+                with open(path, 'wb') as f:
+                    pickle.dump(value, f)
+
+    def get_dataset(self):
+        '''Returns (filenames, labels, image_ids, eval_neutral).'''
+        return self.filenames, self.labels, self.image_ids, self.eval_neutral
+
+    def get_dataset_size(self):
+        '''Returns the number of images in the dataset.'''
+        return self.dataset_size

@@ -81,14 +81,23 @@ class Evaluator:
         '''Reference :258-424: run the model over `data_generator` and collect, per class, the tuples
         `(image_id, confidence, xmin, ymin, xmax, ymax)`.  The generator must honour the reference's `generate(batch_size,
         shuffle=False, transformations=..., label_encoder=None, returns={...}, keep_images_without_gt=True,
-        degenerate_box_handling='remove')` contract; `transformations` is passed as the mode string ('resize' / 'pad') because
-        the reference's image transformation classes are not part of this package.'''
-        if data_generator_mode not in ('resize', 'pad'):
-            raise ValueError("`data_generator_mode` can be either of 'resize' or 'pad', but received '{}'.".format(data_generator_mode))
+        degenerate_box_handling='remove')` contract (data_generator/object_detection_2d_data_generator.py's `DataGenerator`);
+        `transformations` are the reference's lists (:320-330): `[ConvertTo3Channels, Resize]` for 'resize', `[ConvertTo3Channels,
+        RandomPadFixedAR, Resize]` for 'pad'.'''
         import torch
+        from ..data_generator.object_detection_2d_geometric_ops import Resize
+        from ..data_generator.object_detection_2d_patch_sampling_ops import RandomPadFixedAR
+        from ..data_generator.object_detection_2d_photometric_ops import ConvertTo3Channels
         from ..ssd_encoder_decoder.ssd_output_decoder import decode_detections
+        if data_generator_mode == 'resize':
+            transformations = [ConvertTo3Channels(), Resize(height=img_height, width=img_width, labels_format=self.gt_format)]
+        elif data_generator_mode == 'pad':
+            transformations = [ConvertTo3Channels(), RandomPadFixedAR(patch_aspect_ratio=img_width / img_height, labels_format=self.gt_format),
+                               Resize(height=img_height, width=img_width, labels_format=self.gt_format)]
+        else:
+            raise ValueError("`data_generator_mode` can be either of 'resize' or 'pad', but received '{}'.".format(data_generator_mode))
         pf = self.pred_format
-        generator = self.data_generator.generate(batch_size=batch_size, shuffle=False, transformations=data_generator_mode,
+        generator = self.data_generator.generate(batch_size=batch_size, shuffle=False, transformations=transformations,
                                                  label_encoder=None,
                                                  returns={'processed_images', 'image_ids', 'evaluation-neutral', 'inverse_transform',
                                                           'original_labels'},

@@ -5,7 +5,7 @@ of the two callers of `decode_detections` the survey names (t
 GPU: `ssd_output_decoder.decode_detections` -> libssdhip), maps the boxes back to the original images with the transformations'
 inverters and writes the MS COCO detection results JSON.  Same signature, keyword names, error text and output file as the reference;
 `data_generator` is any object honouring the reference generator's `generate(...)` / `get_dataset_size()` contract
-(data_generator/object_detection_2d_data_generator.py:873-1160 -- the generator itself is outside this package),
+(data_generator/object_detection_2d_data_generator.py:873-1160; the package's own is `data_generator.object_detection_2d_data_generator.DataGenerator`),
 and it receives the SAME transformation list the reference builds (ConvertTo3Channels [, RandomPadFixedAR], Resize: all three are
 mirrored here).  `model.predict(batch_X)` may return a NumPy array or a tensor (a torch module's `__call__` is used when it has no
 `predict`)."""
