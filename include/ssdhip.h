@@ -703,6 +703,43 @@ int ssdhip_shadow_refresh(const ssdhip_shadow_desc* table_dev, int n_weights, in
 int ssdhip_sgd_momentum_step(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* bufs_h,
                              const long long* numel_h, double lr, double momentum, double weight_decay, void* stream);
 
+/* keras.optimizers.Adam (Keras 2.x get_updates; ssd7_training.ipynb:153 and every notebook but ssd300_training's) with its scalars on
+ * the DEVICE (csrc/ssdhip_adam.hip): the bias correction changes every step, so a captured step cannot carry it in kernel arguments.
+ * A state block in plain global memory (16-byte aligned, ssdhip_adam_state_bytes(n_groups) bytes, n_groups <= SSDHIP_ADAM_MAX_GROUPS)
+ * holds the step count and per parameter group the running products beta^t and the float32 scalars of the update; every launch below
+ * is stream-ordered and reads or writes the block on the device only, so a replayed graph sees the current values.
+ * ssdhip_adam_state_init   one group's hyperparameters and the block's `iterations` (0, or a restored optimizer's step: the products
+ *                          are then rebuilt by `iterations` float64 multiplications, the tick's own sequence); call it for every group.
+ * ssdhip_adam_step         over n_tensors float32 tensors of parameter group `group`, named by HOST arrays of device pointers (parameter,
+ *                          gradient, m, v, and vhat or NULL = no amsgrad; element counts; 16-byte aligned).  tick != 0 first advances the
+ *                          block (the first call of an optimizer step ticks, the calls for its other groups do not):
+ *                              iterations += 1; b1^t *= beta_1; b2^t *= beta_2;
+ *                              lr = lr0 / (1 + decay * (iterations - 1)) when decay > 0;  lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)
+ *                          in float64, lr_t rounded once to float32.  Then per element, one IEEE float32 operation each, in this order:
+ *                              g = g + weight_decay * p (weight_decay != 0);  m = beta_1 * m + (1 - beta_1) * g;
+ *                              v = beta_2 * v + (1 - beta_2) * (g * g);  vhat = max(vhat, v) (amsgrad; vhat then replaces v below);
+ *                              p = p - lr_t * m / (sqrt(v) + epsilon)
+ *                          The tensor table travels in the kernel arguments (72 tensors per launch): no upload, no host synchronisation.
+ * ssdhip_optim_set_lr      a group's base learning rate lr0, e.g. between two replays of a captured step. */
+#define SSDHIP_ADAM_MAX_GROUPS 64
+typedef struct ssdhip_adam_group {
+    double lr, decay, beta_1, beta_2;       /* lr0 and the hyperparameters the tick reads */
+    double b1t, b2t;                        /* beta_1^iterations, beta_2^iterations as running products */
+    float lr_t, one_minus_beta_1, one_minus_beta_2, beta_1_f, beta_2_f, epsilon, weight_decay;   /* what the update reads */
+    int reserved;
+} ssdhip_adam_group;
+typedef struct ssdhip_adam_state {
+    long long iterations;
+    int n_groups, reserved;
+    ssdhip_adam_group groups[];
+} ssdhip_adam_state;
+size_t ssdhip_adam_state_bytes(int n_groups);
+int ssdhip_adam_state_init(void* state, int n_groups, int group, double lr, double beta_1, double beta_2, double epsilon, double decay,
+                           double weight_decay, long long iterations, void* stream);
+int ssdhip_adam_step(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* m_h, void* const* v_h,
+                     void* const* vhat_h, const long long* numel_h, int group, void* state, int tick, void* stream);
+int ssdhip_optim_set_lr(void* state, int group, double lr, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The decisions of the original-SSD augmentation chain for a whole batch in ONE launch (csrc/ssdhip_augment.hip): SSDExpand ->
  * SSDRandomCrop -> RandomFlip -> ResizeRandomInterp of data_generator/data_augmentation_chain_original_ssd.py:208-280 (with

@@ -152,6 +152,10 @@ SIGNATURES = {
     "ssdhip_conv2d_image_x3_nhwc_f16": (_I, [_P] * 4 + [_I] * 11 + [_F, _P]),
     "ssdhip_shadow_refresh": (_I, [_P] + [_I] * 4 + [_P]),
     "ssdhip_sgd_momentum_step": (_I, [_I] + [_P] * 4 + [_D] * 3 + [_P]),
+    "ssdhip_adam_state_bytes": (_SZ, [_I]),
+    "ssdhip_adam_state_init": (_I, [_P, _I, _I] + [_D] * 6 + [_LL, _P]),
+    "ssdhip_adam_step": (_I, [_I] + [_P] * 6 + [_I, _P, _I, _P]),
+    "ssdhip_optim_set_lr": (_I, [_P, _I, _D, _P]),
     "ssdhip_augment_plans": (_I, [_P] + [_I] * 6 + [_P] * 6),
     "ssdhip_ssd_augment_decide": (_I, [_PARAMS, _I] + [_P] * 8),
     "ssdhip_ssd_augment_decide_stream": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 10),
@@ -676,6 +680,60 @@ def sgd_table(params, grads, bufs, device):
 def sgd_momentum_step(table, lr, momentum, weight_decay=0.0):
     device, n, pp, gp, mp, nn = table
     launch("ssdhip_sgd_momentum_step", device, n, pp, gp, mp, nn, float(lr), float(momentum), float(weight_decay))
+
+
+# struct ssdhip_adam_state / ssdhip_adam_group (include/ssdhip.h), for reading a state block back on the host
+ADAM_STATE_HEAD = np.dtype([("iterations", "<i8"), ("n_groups", "<i4"), ("reserved", "<i4")])
+ADAM_GROUP = np.dtype([(n, "<f8") for n in ("lr", "decay", "beta_1", "beta_2", "b1t", "b2t")] +
+                      [(n, "<f4") for n in ("lr_t", "one_minus_beta_1", "one_minus_beta_2", "beta_1_f", "beta_2_f", "epsilon", "weight_decay")] +
+                      [("reserved", "<i4")])
+
+
+ADAM_MAX_GROUPS = 64                                   # SSDHIP_ADAM_MAX_GROUPS
+
+
+def adam_state_bytes(n_groups):
+    n = load().ssdhip_adam_state_bytes(int(n_groups))
+    if n == 0:
+        raise SsdHipError("an Adam state block holds 1 .. 64 parameter groups (got %d)" % n_groups)
+    return n
+
+
+def adam_state_init(block, n_groups, group, lr, beta_1, beta_2, epsilon, decay, weight_decay, iterations=0):
+    """One group's hyperparameters and the step count into a state block (a uint8 CUDA tensor of adam_state_bytes(n_groups))."""
+    launch("ssdhip_adam_state_init", block.device, _ptr(block), int(n_groups), int(group), float(lr), float(beta_1), float(beta_2),
+           float(epsilon), float(decay), float(weight_decay), int(iterations))
+
+
+def adam_state_read(block):
+    """(iterations, structured array of the groups) of a state block: a device-to-host copy, i.e. a synchronisation."""
+    raw = block.detach().cpu().numpy()
+    head = raw[:ADAM_STATE_HEAD.itemsize].view(ADAM_STATE_HEAD)[0]
+    groups = raw[ADAM_STATE_HEAD.itemsize:].view(ADAM_GROUP)[:int(head["n_groups"])]
+    return int(head["iterations"]), groups
+
+
+def adam_table(params, grads, ms, vs, vhats, device):
+    """The HOST table of ssdhip_adam_step, as sgd_table: parameter, gradient, m, v and (amsgrad) vhat of every tensor."""
+    torch = _torch()
+    n = len(params)
+    cols = [params, grads, ms, vs] + ([vhats] if vhats is not None else [])
+    for ts in zip(*cols):
+        for t in ts:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != ts[0].numel() or t.data_ptr() % 16 or t.device != device:
+                raise SsdHipError("adam_table: parameter, gradient and moment buffers must be dense float32 of one size on one device")
+    vp, ll = ctypes.c_void_p * n, ctypes.c_longlong * n
+    ptrs = [vp(*[t.data_ptr() for t in col]) for col in cols]
+    return (device, n) + tuple(ptrs) + ((None,) if vhats is None else ()) + (ll(*[p.numel() for p in params]),)
+
+
+def adam_step(table, block, group, tick):
+    device, n, pp, gp, mp, vp, hp, nn = table
+    launch("ssdhip_adam_step", device, n, pp, gp, mp, vp, hp, nn, int(group), _ptr(block), 1 if tick else 0)
+
+
+def optim_set_lr(block, group, lr):
+    launch("ssdhip_optim_set_lr", block.device, _ptr(block), int(group), float(lr))
 
 
 def maxpool_bwd(x, gy, kernel, stride, pad=0):

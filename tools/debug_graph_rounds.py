@@ -6,6 +6,7 @@ synchronize.  Prints per round: eager loss, replayed loss, worst relative gradie
   DBG_ZERO_WS=1     re-zero every libssdhip workspace before each replay        SSDHIP_NO_OWN_WGRAD / _DGRAD = 1
   DBG_FUSED_SGD=1   ssd_keras_amd.optimizers.SGD (one launch)                   DBG_OPT_IN_GRAPH=1   the optimizer step is captured too
                                                                                 (round 6: the whole step as ONE graph)
+  DBG_ADAM=1        ssd_keras_amd.optimizers.Adam instead of SGD (its scalars live on the device: the replays advance them)
 """
 import os
 import sys
@@ -39,7 +40,11 @@ if E("DBG_FUSED_SGD", "0") == "1":
     from ssd_keras_amd.optimizers import SGD as _SGD
 else:
     _SGD = torch.optim.SGD
-opt = _SGD(model.parameters(), lr=float(E("DBG_LR", "1e-7")), momentum=0.9)
+if E("DBG_ADAM", "0") == "1":                         # ssd_keras_amd.optimizers.Adam (tick + one update launch) instead of SGD
+    from ssd_keras_amd.optimizers import Adam as _Adam
+    opt = _Adam(model.parameters(), lr=float(E("DBG_LR", "1e-7")), epsilon=1e-8)
+else:
+    opt = _SGD(model.parameters(), lr=float(E("DBG_LR", "1e-7")), momentum=0.9)
 OPT_IN_GRAPH = E("DBG_OPT_IN_GRAPH", "0") == "1"
 enc = SSDInputEncoder(matching_type='multi', pos_iou_threshold=0.5, neg_iou_limit=0.5, **cfg)
 gt = syn.make_ground_truth(B, cfg["n_classes"], 300, 300, max_boxes=8, seed=7)
@@ -146,4 +151,6 @@ with torch.cuda.device(dev):
         if E("DBG_SYNC", "1") == "1":
             torch.cuda.synchronize()
         out.append("%.4f/%.4f/%.3g" % (le, lg, worst))
-print("ROUNDS", " ".join("%s=%s" % (k, v) for k, v in sorted(os.environ.items()) if k.startswith("DBG_") or k.startswith("SSDHIP_NO")), "|", "  ".join(out))
+extra = " ADAM_ITERATIONS=%d" % opt.iterations if E("DBG_ADAM", "0") == "1" else ""      # the DEVICE's step count behind the replays
+print("ROUNDS", " ".join("%s=%s" % (k, v) for k, v in sorted(os.environ.items()) if k.startswith("DBG_") or k.startswith("SSDHIP_NO")) + extra,
+      "|", "  ".join(out))
