@@ -740,6 +740,48 @@ int ssdhip_adam_step(int n_tensors, void* const* params_h, const void* const* gr
                      void* const* vhat_h, const long long* numel_h, int group, void* state, int tick, void* stream);
 int ssdhip_optim_set_lr(void* state, int group, double lr, void* stream);
 
+/* keras.optimizers.SGD(lr, momentum, decay, nesterov) (ssd300_training.ipynb:169, under its LearningRateScheduler) with its scalars on the
+ * DEVICE, as Adam's above (csrc/ssdhip_optim.hip): ssdhip_sgd_momentum_step carries `lr` in its kernel arguments, so a captured launch
+ * replays the rate of its capture.  A state block in plain global memory (16-byte aligned, ssdhip_sgd_state_bytes(n_groups) bytes,
+ * n_groups <= SSDHIP_ADAM_MAX_GROUPS) holds the step count and per parameter group lr0, decay and momentum in float64 and the float32
+ * scalars the update reads; every launch below is stream-ordered and touches the block on the device only.
+ * ssdhip_sgd_state_init   one group's hyperparameters and the block's `iterations` (0, or a restored optimizer's step); call it for
+ *                         every group.
+ * ssdhip_sgd_set_lr       a group's base learning rate lr0, e.g. between two replays of a captured step.
+ * ssdhip_sgd_step         over n_tensors float32 tensors of parameter group `group`, named by HOST arrays of device pointers (parameter,
+ *                         gradient, buffer -- zeros before the first step -- and element count; 16-byte aligned).  tick != 0 first
+ *                         advances the block (the first call of an optimizer step ticks, the calls for its other groups do not):
+ *                             iterations += 1;  lr = lr0 / (1 + decay * (iterations - 1)) when decay > 0  (float64; Keras reads the
+ *                             count before it increments it);  lr_t = lr rounded once to float32.
+ *                         Then per element, one IEEE float32 operation each, in this order:
+ *                             g = g + weight_decay * p (weight_decay != 0)
+ *                           rule 0 (torch.optim.SGD; the buffer is `momentum_buffer`):
+ *                             buf = momentum * buf + g;  p = p - lr_t * buf
+ *                             nesterov != 0:  d = g + momentum * buf (the new buf);  p = p - lr_t * d
+ *                           rule 1 (Keras 2.x SGD.get_updates; the buffer is the velocity):
+ *                             v = momentum * v - lr_t * g;  p = p + v
+ *                             nesterov != 0:  p = (p + momentum * v) - lr_t * g (the new v)
+ *                         rule 0 without Nesterov and decay is ssdhip_sgd_momentum_step's arithmetic on the same float32 scalars: the
+ *                         results are bit-identical.  The two rules agree (in real numbers) only while lr_t stays constant: a velocity
+ *                         keeps the rate it was built under, a momentum buffer is rescaled as a whole by the new one.  The tensor table
+ *                         travels in the kernel arguments (80 tensors per launch): no upload, no host synchronisation. */
+typedef struct ssdhip_sgd_group {
+    double lr, decay, momentum;             /* lr0 and the hyperparameters the tick reads */
+    float lr_t, momentum_f, weight_decay;   /* what the update reads */
+    int reserved;
+} ssdhip_sgd_group;
+typedef struct ssdhip_sgd_state {
+    long long iterations;
+    int n_groups, reserved;
+    ssdhip_sgd_group groups[];
+} ssdhip_sgd_state;
+size_t ssdhip_sgd_state_bytes(int n_groups);
+int ssdhip_sgd_state_init(void* state, int n_groups, int group, double lr, double momentum, double decay, double weight_decay,
+                          long long iterations, void* stream);
+int ssdhip_sgd_set_lr(void* state, int group, double lr, void* stream);
+int ssdhip_sgd_step(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* bufs_h, const long long* numel_h,
+                    int group, void* state, int rule, int nesterov, int tick, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The decisions of the original-SSD augmentation chain for a whole batch in ONE launch (csrc/ssdhip_augment.hip): SSDExpand ->
  * SSDRandomCrop -> RandomFlip -> ResizeRandomInterp of data_generator/data_augmentation_chain_original_ssd.py:208-280 (with

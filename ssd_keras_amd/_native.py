@@ -156,6 +156,10 @@ SIGNATURES = {
     "ssdhip_adam_state_init": (_I, [_P, _I, _I] + [_D] * 6 + [_LL, _P]),
     "ssdhip_adam_step": (_I, [_I] + [_P] * 6 + [_I, _P, _I, _P]),
     "ssdhip_optim_set_lr": (_I, [_P, _I, _D, _P]),
+    "ssdhip_sgd_state_bytes": (_SZ, [_I]),
+    "ssdhip_sgd_state_init": (_I, [_P, _I, _I] + [_D] * 4 + [_LL, _P]),
+    "ssdhip_sgd_set_lr": (_I, [_P, _I, _D, _P]),
+    "ssdhip_sgd_step": (_I, [_I] + [_P] * 4 + [_I, _P, _I, _I, _I, _P]),
     "ssdhip_augment_plans": (_I, [_P] + [_I] * 6 + [_P] * 6),
     "ssdhip_ssd_augment_decide": (_I, [_PARAMS, _I] + [_P] * 8),
     "ssdhip_ssd_augment_decide_stream": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 10),
@@ -734,6 +738,43 @@ def adam_step(table, block, group, tick):
 
 def optim_set_lr(block, group, lr):
     launch("ssdhip_optim_set_lr", block.device, _ptr(block), int(group), float(lr))
+
+
+# struct ssdhip_sgd_state / ssdhip_sgd_group (include/ssdhip.h); the table of ssdhip_sgd_step is sgd_table's
+SGD_STATE_HEAD = ADAM_STATE_HEAD
+SGD_GROUP = np.dtype([(n, "<f8") for n in ("lr", "decay", "momentum")] + [(n, "<f4") for n in ("lr_t", "momentum_f", "weight_decay")] +
+                     [("reserved", "<i4")])
+SGD_RULES = {"torch": 0, "keras": 1}                   # ssdhip_sgd_step's `rule`
+
+
+def sgd_state_bytes(n_groups):
+    n = load().ssdhip_sgd_state_bytes(int(n_groups))
+    if n == 0:
+        raise SsdHipError("an SGD state block holds 1 .. 64 parameter groups (got %d)" % n_groups)
+    return n
+
+
+def sgd_state_init(block, n_groups, group, lr, momentum, decay, weight_decay, iterations=0):
+    """One group's hyperparameters and the step count into a state block (a uint8 CUDA tensor of sgd_state_bytes(n_groups))."""
+    launch("ssdhip_sgd_state_init", block.device, _ptr(block), int(n_groups), int(group), float(lr), float(momentum), float(decay),
+           float(weight_decay), int(iterations))
+
+
+def sgd_state_read(block):
+    """(iterations, structured array of the groups) of a state block: a device-to-host copy, i.e. a synchronisation."""
+    raw = block.detach().cpu().numpy()
+    head = raw[:SGD_STATE_HEAD.itemsize].view(SGD_STATE_HEAD)[0]
+    groups = raw[SGD_STATE_HEAD.itemsize:].view(SGD_GROUP)[:int(head["n_groups"])]
+    return int(head["iterations"]), groups
+
+
+def sgd_set_lr(block, group, lr):
+    launch("ssdhip_sgd_set_lr", block.device, _ptr(block), int(group), float(lr))
+
+
+def sgd_step(table, block, group, rule, nesterov, tick):
+    device, n, pp, gp, mp, nn = table
+    launch("ssdhip_sgd_step", device, n, pp, gp, mp, nn, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0)
 
 
 def maxpool_bwd(x, gy, kernel, stride, pad=0):

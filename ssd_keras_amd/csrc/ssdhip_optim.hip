@@ -13,7 +13,14 @@
 //   shadow_refresh_kernel   grid = tiles of 32 x 32 (Cout x Cin) filter taps over every weight tensor + a tail for the 1-D tensors
 //                           (biases, L2Normalization's gamma): float32 master -> bf16 through LDS, both layouts written as 64-byte runs.
 //   sgd_momentum_kernel     torch.optim.SGD's update (buf = momentum buf + g [+ wd p]; p -= lr buf; the first step's buf = g), every
-//                           parameter in one launch, float32.
+//                           parameter in one launch, float32.  `lr` is a kernel argument: a captured launch replays it.
+//   sgd_tick_kernel / sgd_step_kernel<RULE, NESTEROV>
+//                           the same launch shape with its scalars in a state block on the DEVICE, as Adam's (ssdhip_adam.hip): a
+//                           one-workgroup tick advances `iterations` and rounds lr_t = lr0 / (1 + decay (iterations - 1)) once to float32,
+//                           the update reads lr_t, momentum and weight_decay from the block -- a captured step follows ssdhip_sgd_set_lr
+//                           between replays (ssd300_training.ipynb's LearningRateScheduler).  RULE 0: torch's buffer, RULE 1: Keras 2.x
+//                           SGD.get_updates' velocity (v = momentum v - lr g; p += v), each with and without Nesterov.  20 bytes per
+//                           parameter, as sgd_momentum_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -203,6 +210,102 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(const SgdArgs a, floa
     }
 }
 
+__global__ __launch_bounds__(64) void sgd_init_kernel(ssdhip_sgd_state* st, int n_groups, int group, double lr, double momentum,
+                                                      double decay, double weight_decay, long long iterations) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    st->iterations = iterations;                           // (every group's call rewrites the same count)
+    st->n_groups = n_groups;
+    st->reserved = 0;
+    ssdhip_sgd_group& s = st->groups[group];
+    s.lr = lr;
+    s.decay = decay;
+    s.momentum = momentum;
+    s.lr_t = 0.f;                                          // (the tick in front of every update writes it)
+    s.momentum_f = (float)momentum;
+    s.weight_decay = (float)weight_decay;
+    s.reserved = 0;
+}
+
+__global__ __launch_bounds__(64) void sgd_set_lr_kernel(ssdhip_sgd_state* st, int group, double lr) {
+    if (threadIdx.x == 0 && blockIdx.x == 0 && group < st->n_groups) st->groups[group].lr = lr;
+}
+
+// One workgroup, one thread per parameter group.
+__global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void sgd_tick_kernel(ssdhip_sgd_state* st) {
+    const int g = threadIdx.x;
+    const long long t = st->iterations + 1;
+    const int n_groups = st->n_groups;
+    __syncthreads();                                       // every thread has read the old count
+    if (g == 0) st->iterations = t;
+    if (g >= n_groups) return;
+    ssdhip_sgd_group& s = st->groups[g];
+    double lr = s.lr;
+    if (s.decay > 0.0) lr = lr / (1.0 + s.decay * (double)(t - 1));   // Keras reads `iterations` before it increments it
+    s.lr_t = (float)lr;
+}
+
+// One element of the update; `m` is the momentum buffer (RULE 0) or the velocity (RULE 1).  One IEEE float32 operation per line part,
+// in the order of include/ssdhip.h; RULE 0 without Nesterov is sgd_momentum_kernel's sequence.
+template <int RULE, bool NESTEROV>
+__device__ __forceinline__ void sgd_update(float& p, float g, float& m, float lr, float momentum, float weight_decay) {
+    if (weight_decay != 0.f) g = g + weight_decay * p;
+    if (RULE == 0) {
+        m = momentum * m + g;
+        if (NESTEROV) {
+            const float d = g + momentum * m;
+            p = p - lr * d;
+        } else {
+            p = p - lr * m;
+        }
+    } else {
+        const float lg = lr * g;
+        m = momentum * m - lg;
+        if (NESTEROV)
+            p = (p + momentum * m) - lg;
+        else
+            p = p + m;
+    }
+}
+
+template <int RULE, bool NESTEROV>
+__global__ __launch_bounds__(256) void sgd_step_kernel(const SgdArgs a, const ssdhip_sgd_state* __restrict__ st, int group) {
+    const int tid = threadIdx.x, blk = (int)blockIdx.x;
+    if (group >= st->n_groups) return;
+    const ssdhip_sgd_group& s = st->groups[group];         // uniform: scalar loads, the values the tick has just written
+    const float lr = s.lr_t, momentum = s.momentum_f, weight_decay = s.weight_decay;
+    int lo = 0, hi = a.count - 1;                          // last tensor with block0 <= blk
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.block0[mid] <= blk) lo = mid; else hi = mid - 1;
+    }
+    float* p = a.p[lo];
+    const float* g = a.g[lo];
+    float* m = a.m[lo];
+    const long long n = a.n[lo];
+    const long long base = (long long)(blk - a.block0[lo]) * 4096;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const long long i = base + (long long)u * 1024 + tid * 4;
+        if (i + 3 < n) {
+            const float4 pv = *reinterpret_cast<const float4*>(p + i), gv = *reinterpret_cast<const float4*>(g + i);
+            const float4 mv = *reinterpret_cast<const float4*>(m + i);
+            float gg[4] = {gv.x, gv.y, gv.z, gv.w}, pp[4] = {pv.x, pv.y, pv.z, pv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sgd_update<RULE, NESTEROV>(pp[q], gg[q], mm[q], lr, momentum, weight_decay);
+            *reinterpret_cast<float4*>(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+            *reinterpret_cast<float4*>(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+        } else {
+            for (long long j = i; j < n && j < i + 4; ++j) {
+                float pq = p[j], mq = m[j];
+                sgd_update<RULE, NESTEROV>(pq, g[j], mq, lr, momentum, weight_decay);
+                m[j] = mq;
+                p[j] = pq;
+            }
+        }
+    }
+}
+static_assert(sizeof(SgdArgs) + sizeof(void*) + 2 * sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
+
 }  // namespace ssdhip
 
 using namespace ssdhip;
@@ -243,6 +346,73 @@ extern "C" int ssdhip_sgd_momentum_step(int n_tensors, void* const* params_h, co
             if (blocks > 0x7fffffffLL) return SSDHIP_E_BADARG;
         }
         hipLaunchKernelGGL(sgd_momentum_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, (float)lr, (float)momentum, (float)weight_decay);
+        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
+    }
+    return SSDHIP_OK;
+}
+
+extern "C" size_t ssdhip_sgd_state_bytes(int n_groups) {
+    if (n_groups <= 0 || n_groups > SSDHIP_ADAM_MAX_GROUPS) return 0;
+    return sizeof(ssdhip_sgd_state) + (size_t)n_groups * sizeof(ssdhip_sgd_group);
+}
+
+extern "C" int ssdhip_sgd_state_init(void* state, int n_groups, int group, double lr, double momentum, double decay, double weight_decay,
+                                     long long iterations, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!state || ((uintptr_t)state & 15) || n_groups <= 0 || n_groups > SSDHIP_ADAM_MAX_GROUPS || group < 0 || group >= n_groups)
+        return SSDHIP_E_BADARG;
+    if (!(lr >= 0.0) || !(momentum >= 0.0) || !(decay >= 0.0) || !(weight_decay >= 0.0) || iterations < 0) return SSDHIP_E_BADARG;
+    hipLaunchKernelGGL(sgd_init_kernel, dim3(1), dim3(64), 0, stream, static_cast<ssdhip_sgd_state*>(state), n_groups, group, lr,
+                       momentum, decay, weight_decay, iterations);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_sgd_set_lr(void* state, int group, double lr, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!state || ((uintptr_t)state & 15) || group < 0 || group >= SSDHIP_ADAM_MAX_GROUPS || !(lr >= 0.0)) return SSDHIP_E_BADARG;
+    hipLaunchKernelGGL(sgd_set_lr_kernel, dim3(1), dim3(64), 0, stream, static_cast<ssdhip_sgd_state*>(state), group, lr);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_sgd_step(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* bufs_h,
+                               const long long* numel_h, int group, void* state, int rule, int nesterov, int tick, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n_tensors <= 0 || !params_h || !grads_h || !bufs_h || !numel_h || !state || ((uintptr_t)state & 15) || group < 0
+        || group >= SSDHIP_ADAM_MAX_GROUPS || rule < 0 || rule > 1)
+        return SSDHIP_E_BADARG;
+    for (int k = 0; k < n_tensors; ++k) {
+        if (!params_h[k] || !grads_h[k] || !bufs_h[k] || numel_h[k] <= 0) return SSDHIP_E_BADARG;
+        if (((uintptr_t)params_h[k] | (uintptr_t)grads_h[k] | (uintptr_t)bufs_h[k]) & 15) return SSDHIP_E_BADARG;
+        if ((numel_h[k] + 4095) / 4096 > 0x3fffffffLL) return SSDHIP_E_BADARG;
+    }
+    ssdhip_sgd_state* st = static_cast<ssdhip_sgd_state*>(state);
+    if (tick) {
+        hipLaunchKernelGGL(sgd_tick_kernel, dim3(1), dim3(SSDHIP_ADAM_MAX_GROUPS), 0, stream, st);
+        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
+    }
+    for (int k0 = 0; k0 < n_tensors; k0 += SGD_CHUNK) {
+        SgdArgs a;
+        a.count = n_tensors - k0 < SGD_CHUNK ? n_tensors - k0 : SGD_CHUNK;
+        long long blocks = 0;
+        for (int k = 0; k < SGD_CHUNK; ++k) {
+            const int src = k < a.count ? k0 + k : k0;     // (unused slots repeat the first tensor: never selected)
+            a.p[k] = static_cast<float*>(params_h[src]);
+            a.g[k] = static_cast<const float*>(grads_h[src]);
+            a.m[k] = static_cast<float*>(bufs_h[src]);
+            a.n[k] = numel_h[src];
+            a.block0[k] = (int)blocks;
+            if (k < a.count) blocks += (numel_h[src] + 4095) / 4096;
+            if (blocks > 0x7fffffffLL) return SSDHIP_E_BADARG;
+        }
+        const dim3 grid((unsigned)blocks), wg(256);
+        if (rule == 0 && !nesterov)
+            hipLaunchKernelGGL((sgd_step_kernel<0, false>), grid, wg, 0, stream, a, st, group);
+        else if (rule == 0)
+            hipLaunchKernelGGL((sgd_step_kernel<0, true>), grid, wg, 0, stream, a, st, group);
+        else if (!nesterov)
+            hipLaunchKernelGGL((sgd_step_kernel<1, false>), grid, wg, 0, stream, a, st, group);
+        else
+            hipLaunchKernelGGL((sgd_step_kernel<1, true>), grid, wg, 0, stream, a, st, group);
         if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
     }
     return SSDHIP_OK;

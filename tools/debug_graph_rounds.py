@@ -7,6 +7,9 @@ synchronize.  Prints per round: eager loss, replayed loss, worst relative gradie
   DBG_FUSED_SGD=1   ssd_keras_amd.optimizers.SGD (one launch)                   DBG_OPT_IN_GRAPH=1   the optimizer step is captured too
                                                                                 (round 6: the whole step as ONE graph)
   DBG_ADAM=1        ssd_keras_amd.optimizers.Adam instead of SGD (its scalars live on the device: the replays advance them)
+  DBG_RULE=keras    with DBG_FUSED_SGD=1: the velocity form of the update (default: torch's momentum buffer)
+  DBG_SET_LR=R:LR   before round R (0-based) the learning rate becomes LR -- `set_lr` of the package's optimizers, which a captured
+                    step follows (the state block on the device), `param_groups` for the framework's
 """
 import os
 import sys
@@ -44,7 +47,9 @@ if E("DBG_ADAM", "0") == "1":                         # ssd_keras_amd.optimizers
     from ssd_keras_amd.optimizers import Adam as _Adam
     opt = _Adam(model.parameters(), lr=float(E("DBG_LR", "1e-7")), epsilon=1e-8)
 else:
-    opt = _SGD(model.parameters(), lr=float(E("DBG_LR", "1e-7")), momentum=0.9)
+    opt = _SGD(model.parameters(), lr=float(E("DBG_LR", "1e-7")), momentum=0.9,
+               **({"rule": E("DBG_RULE")} if E("DBG_RULE") and E("DBG_FUSED_SGD", "0") == "1" else {}))
+SET_LR = (int(E("DBG_SET_LR").split(":")[0]), float(E("DBG_SET_LR").split(":")[1])) if E("DBG_SET_LR") else None
 OPT_IN_GRAPH = E("DBG_OPT_IN_GRAPH", "0") == "1"
 enc = SSDInputEncoder(matching_type='multi', pos_iou_threshold=0.5, neg_iou_limit=0.5, **cfg)
 gt = syn.make_ground_truth(B, cfg["n_classes"], 300, 300, max_boxes=8, seed=7)
@@ -108,6 +113,12 @@ with torch.cuda.device(dev):
     graph_grads = [p.grad for p in watched]
     graph_trace = list(TRACE)
     for rnd in range(int(E("DBG_ROUNDS", "6"))):
+        if SET_LR is not None and rnd == SET_LR[0]:
+            if hasattr(opt, "set_lr"):
+                opt.set_lr(SET_LR[1])
+            else:
+                for grp in opt.param_groups:
+                    grp["lr"] = SET_LR[1]
         le, eager_grads = float("nan"), None
         if E("DBG_EAGER_BETWEEN", "1") == "1":
             for p in watched:
@@ -152,5 +163,7 @@ with torch.cuda.device(dev):
             torch.cuda.synchronize()
         out.append("%.4f/%.4f/%.3g" % (le, lg, worst))
 extra = " ADAM_ITERATIONS=%d" % opt.iterations if E("DBG_ADAM", "0") == "1" else ""      # the DEVICE's step count behind the replays
+if E("DBG_ADAM", "0") != "1" and hasattr(opt, "iterations"):
+    extra = " SGD_ITERATIONS=%d" % opt.iterations
 print("ROUNDS", " ".join("%s=%s" % (k, v) for k, v in sorted(os.environ.items()) if k.startswith("DBG_") or k.startswith("SSDHIP_NO")) + extra,
       "|", "  ".join(out))

@@ -12,11 +12,11 @@ clock).  Per variant: median / min / max over the rounds, the spread (max - min)
                                                                        --repeat=3: the list three times (0.95 / 1.26 GB of state, far
                                                                        beyond the 256 MB Infinity Cache: neither kernel is helped by it)
     python tools/time_adam_step.py --merge-kernel-stats STATS.csv OUT.json [REPEAT]
-                                                                       (no GPU) adam_step_kernel's and sgd_momentum_kernel's time per
+                                                                       (no GPU) adam_step_kernel's and sgd_step_kernel's time per
                                                                        launch from that trace into OUT.json: bytes/s = algorithmic bytes
                                                                        (28 / 20 per parameter) over KERNEL time, and the two conditions
 Conditions: (a) and (b) not slower than the faster form of (c) beyond the spread of the variants compared; adam_step_kernel's bytes/s not
-below sgd_momentum_kernel's beyond the relative standard deviation of the two kernels' durations in the trace.
+below sgd_step_kernel's beyond the relative standard deviation of the two kernels' durations in the trace.
 """
 import csv
 import json
@@ -30,18 +30,18 @@ N_PARAMS = 26285486                                           # SSD300, 20 class
 def merge_kernel_stats(stats_csv, out_json, repeat=1):
     res = json.load(open(out_json))
     rows = {}
-    n_launch = {"adam_step_kernel": -(-71 * repeat // 72), "sgd_momentum_kernel": -(-71 * repeat // 80)}      # tensors per launch
+    n_launch = {"adam_step_kernel": -(-71 * repeat // 72), "sgd_step_kernel": -(-71 * repeat // 80)}      # tensors per launch
     for r in csv.DictReader(open(stats_csv)):
-        for key in ("adam_step_kernel", "sgd_momentum_kernel", "adam_tick_kernel"):
+        for key in ("adam_step_kernel", "sgd_step_kernel", "adam_tick_kernel"):
             if key in r["Name"]:
                 rows[key] = {"calls": int(r["Calls"]), "average_us": float(r["AverageNs"]) / 1e3, "min_us": float(r["MinNs"]) / 1e3,
                              "max_us": float(r["MaxNs"]) / 1e3, "rel_stddev": float(r["StdDev"]) / float(r["AverageNs"])}
     n = res["parameters"] * repeat
-    for key, per_param in (("adam_step_kernel", 28), ("sgd_momentum_kernel", 20)):
+    for key, per_param in (("adam_step_kernel", 28), ("sgd_step_kernel", 20)):
         rows[key]["launches_per_step"] = n_launch[key]
         rows[key]["bytes_per_s"] = round(per_param * n / (rows[key]["average_us"] * n_launch[key] * 1e-6))
     if repeat != 1:                                           # the same kernels on the list repeated: footprints far beyond the L3
-        rows["kernel_ratio"] = round(rows["adam_step_kernel"]["bytes_per_s"] / rows["sgd_momentum_kernel"]["bytes_per_s"], 4)
+        rows["kernel_ratio"] = round(rows["adam_step_kernel"]["bytes_per_s"] / rows["sgd_step_kernel"]["bytes_per_s"], 4)
         res["kernels_list_x%d" % repeat] = rows
         json.dump(res, open(out_json, "w"), indent=1)
         print(json.dumps({"kernels_list_x%d" % repeat: rows}))
@@ -51,13 +51,13 @@ def merge_kernel_stats(stats_csv, out_json, repeat=1):
     torch_best = min((k for k in v if k.startswith("c_")), key=lambda k: v[k]["ms_median"])
     ours = max(("a_adam_eager", "b_adam_graph"), key=lambda k: v[k]["ms_median"])
     tol_1 = max(v[ours]["spread"], v[torch_best]["spread"])
-    tol_2 = max(rows["adam_step_kernel"]["rel_stddev"], rows["sgd_momentum_kernel"]["rel_stddev"])
+    tol_2 = max(rows["adam_step_kernel"]["rel_stddev"], rows["sgd_step_kernel"]["rel_stddev"])
     res["conditions"] = {
         "adam_eager_and_graph_not_slower_than_torch_adam": bool(v[ours]["ms_median"] <= v[torch_best]["ms_median"] * (1.0 + tol_1)),
         "compared": [ours, torch_best], "spread_allowed": round(tol_1, 4),
         "adam_kernel_bytes_per_s_not_below_sgd_kernel": bool(rows["adam_step_kernel"]["bytes_per_s"]
-                                                             >= rows["sgd_momentum_kernel"]["bytes_per_s"] * (1.0 - tol_2)),
-        "kernel_ratio": round(rows["adam_step_kernel"]["bytes_per_s"] / rows["sgd_momentum_kernel"]["bytes_per_s"], 4),
+                                                             >= rows["sgd_step_kernel"]["bytes_per_s"] * (1.0 - tol_2)),
+        "kernel_ratio": round(rows["adam_step_kernel"]["bytes_per_s"] / rows["sgd_step_kernel"]["bytes_per_s"], 4),
         "kernel_spread_allowed": round(tol_2, 4)}
     json.dump(res, open(out_json, "w"), indent=1)
     print(json.dumps({"kernels": rows, "conditions": res["conditions"]}))
