@@ -151,6 +151,13 @@ __device__ __forceinline__ u32 c64_load_u16(u32 voff, i32x4 rsrc, u32 soff) {
     return v;
 }
 
+// the same for four bytes (the offset is a multiple of 4 in every lane that is in range)
+__device__ __forceinline__ u32 c64_load_u32(u32 voff, i32x4 rsrc, u32 soff) {
+    u32 v;
+    asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+    return v;
+}
+
 __device__ __forceinline__ i32x4 c64_rsrc(const void* base, int num_records) {
     const unsigned long long a = (unsigned long long)(uintptr_t)base;
     i32x4 r;
@@ -232,8 +239,9 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
     // ---- FRONT: the producer wave.  The halo of a tile is conv1_1 of the (HR + 2) x (HC + 2) x 3 input patch around it: K = 27
     //      (padded to 32, k = kh * 9 + kw * 3 + ci as in conv3x3_cin3_kernel -- same operands, same MFMA, hence the same bf16 values
     //      the separate kernel would have written to memory), 64 channels x 180 halo pixels = 24 v_mfma_f32_32x32x16_bf16 per tile
-    //      against the 288 of the four multiplying waves.  Per tile: 12 two-byte global loads per lane (requested a tile ahead),
-    //      the patch into LDS, per 32 halo pixels 16 two-byte gathers -> B operand, 4 MFMAs, bias + ReLU + rounding (halo pixels
+    //      against the 288 of the four multiplying waves.  Per tile: 6 four-byte global loads per lane (requested a tile ahead; 12 two-byte
+    //      ones for an odd W), the patch into LDS, per 32 halo pixels 11 dword reads + 8 v_perm_b32 -> B operand (two-byte form: 16 two-byte
+    //      gathers), 4 MFMAs, bias + ReLU + rounding (halo pixels
     //      outside the image become ZERO: they are conv1_2's padding, not conv1_1 of padding), 8-byte stores into the 144-byte halo
     //      rows.  Two halo buffers: tile i + 1's halo is produced while tile i is multiplied. ----------------------------------
     if constexpr (FRONT) {
@@ -268,16 +276,6 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
                 for (int e = 0; e < 4; ++e)
                     b1v[cb][4 * g + e] = p.b1 ? __uint_as_float((u32)p.b1[cb * 32 + 8 * g + 4 * khalf + e] << 16) : 0.f;
         // the lane's halo pixel in each block of 32: patch offset of its top-left tap, halo-row offset, (hr, hc)
-        // gather offsets (bytes into the patch) of the lane's 16 k values relative to its pixel: k -> (kh, r = kw * 3 + ci)
-        u32 kofs[2][8];
-#pragma unroll
-        for (int st = 0; st < 2; ++st)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int k = (2 * st + khalf) * 8 + j;
-                kofs[st][j] = (u32)(((k / 9) * PROW + (k % 9)) * 2);          // k = 27 .. 31 read row kh = 3 (x zero weights)
-            }
-        // the lane's halo pixel in each block of 32: patch offset of its top-left tap, halo-row offset, (hr, hc)
         u32 pbase[MYB], hdst[MYB], hcoord[MYB];
 #pragma unroll
         for (int blk = 0; blk < MYB; ++blk) {
@@ -287,20 +285,83 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
             hdst[blk] = (u32)(hpc * 144 + 8 * khalf);
             hcoord[blk] = (u32)((hr << 8) | hc | (hp < HPX ? 0 : 0x10000));
         }
-        // raw-load slots: element n = 64 i + lane of the patch = (pr, pc, ci); two-byte buffer loads, an out-of-range offset reads 0
         const i32x4 r3 = c64_rsrc(p.x3, p.B * p.H * p.W * 6);
-        u32 rrel[NRAW], rco[NRAW];
+        // Two forms of the data movement (image -> registers -> patch -> B fragments); the MFMAs and the epilogue are shared.
+        // WIDE: everything in dwords.  A patch row is PROW * 2 contiguous bytes of the image and starts on a dword when the image does and
+        // W is even (tile origins are even columns) -- 300, 512 and every other size the models use.  Then the patch is NDW dwords: NRAWW
+        // 4-byte loads and stores per lane, and a fragment comes from aligned dword reads + v_perm_b32 (below).  In dwords the image border
+        // is still clean: the two columns left of a border tile are 12 bytes, and W - pw is even.
+        // Otherwise (odd W: every other image row starts on a half dword; a misaligned x3) the two-byte form: 12 two-byte loads and stores
+        // per lane, 8 two-byte gathers per fragment.  It is kept, not replaced by per-row shifts in the wide form, because no model runs
+        // it -- a per-row shift would put a second, row-dependent selector set into the path that matters to serve one that does not.
+        auto run = [&](auto widec) {
+        constexpr bool WIDE = decltype(widec)::value;
+        constexpr int ROWB = PROW * 2, NDW = PATCH / 2, DPR = PROW / 2, NRAWW = (NDW + 63) / 64;
+        constexpr int NR = WIDE ? NRAWW : NRAW;
+        static_assert(PROW % 2 == 0 && NRAWW * 64 * 4 <= C64_PATCH1 && (HR + 1) * ROWB + (HC - 1) * 6 + 32 <= C64_PATCH1,
+                      "dword patch rows; every raw slot and every fragment read stay inside the producer's patch copy");
+        // two-byte form: gather offsets (bytes into the patch) of the lane's 16 k values relative to its pixel: k -> (kh, r = kw * 3 + ci)
+        [[maybe_unused]] u32 kofs[2][8];
+        // WIDE: the lane's fragment g = 2 st + khalf is k = 8 g .. 8 g + 7 of the pixel's three 9-element rows (k = 9 kh + r):
+        //   g0 = row 0 [0..7] | g1 = row 0 [8], row 1 [0..6] | g2 = row 1 [7..8], row 2 [0..5] | g3 = row 2 [6..8], zeros
+        // (the zeros meet zero weights; the two-byte form reads the next patch row there).  With R[kh][m] the dwords from the pixel's row start
+        // rounded DOWN to a dword (sb = 2 bytes of shift for odd halo columns, 0 for even ones), every fragment dword is
+        // v_perm_b32(X[m + 1], X[m], selector) of two neighbouring reads X, with per-LANE addresses and selectors so both lane halves run one
+        // instruction stream:  st 0: X[0] at fadr[0], X[1..4] at fadr[1];  st 1: X[0..1] at fadr[2], X[2..5] at fadr[3]
+        //   khalf 0: g0 = R0[0], R0[1..4]             g2 = R1[3..4], R2[0..3]
+        //   khalf 1: g1 = R0[4], R1[0..3]             g3 = R2[3..4], R2[4..] (only R2[4] is selected, the rest is zeroed by the selector)
+        // 11 dword reads per block instead of 32 two-byte ones.
+        [[maybe_unused]] u32 fadr[MYB][4], fsel[MYB][5];
+        if constexpr (WIDE) {
 #pragma unroll
-        for (int i = 0; i < NRAW; ++i) {
-            const int n = 64 * i + lane, nn = n < PATCH ? n : 0;
-            const int pr = nn / PROW, rem = nn - pr * PROW, pc = rem / 3;
-            rrel[i] = n < PATCH ? (u32)(((pr * p.W) * 3 + rem) * 2) : OOB;
-            rco[i] = (u32)((pr << 8) | pc);
+            for (int blk = 0; blk < MYB; ++blk) {
+                const u32 sb = pbase[blk] & 2u, a0 = pbase[blk] - sb;
+                const u32 fun0 = 0x03020100u + sb * 0x01010101u, fun2 = fun0 + 0x02020202u;   // bytes sb .. sb + 3 / sb + 2 .. sb + 5 of {X[m + 1], X[m]}
+                const u32 one = sb | ((sb + 1u) << 8);                                        // the half word at byte sb of X[m]
+                if (khalf == 0) {
+                    fadr[blk][0] = a0; fadr[blk][1] = a0 + 4; fadr[blk][2] = a0 + ROWB + 12; fadr[blk][3] = a0 + 2 * ROWB;
+                    fsel[blk][0] = fun0; fsel[blk][1] = fun0; fsel[blk][2] = fun2; fsel[blk][3] = fun0; fsel[blk][4] = fun0;
+                } else {
+                    fadr[blk][0] = a0 + 16; fadr[blk][1] = a0 + ROWB; fadr[blk][2] = a0 + 2 * ROWB + 12; fadr[blk][3] = a0 + 2 * ROWB + 16;
+                    fsel[blk][0] = one | ((one + 0x0404u) << 16);      // row 0 [8] from X[0], row 1 [0] from X[1]
+                    fsel[blk][1] = fun2;
+                    fsel[blk][2] = fun0;
+                    fsel[blk][3] = one | 0x0c0c0000u;                  // row 2 [8], then zero (selector byte 0x0c)
+                    fsel[blk][4] = 0x0c0c0c0cu;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int k = (2 * st + khalf) * 8 + j;
+                    kofs[st][j] = (u32)(((k / 9) * PROW + (k % 9)) * 2);          // k = 27 .. 31 read row kh = 3 (x zero weights)
+                }
         }
+        // raw-load slots: slot n = 64 i + lane of the patch = element (pr, pc, ci) / WIDE: dword (pr, c4), which holds parts of the pixels
+        // pcs .. pce; buffer loads, an out-of-range offset reads 0
+        u32 rrel[NR], rco[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int n = 64 * i + lane;
+            if constexpr (WIDE) {
+                const int nn = n < NDW ? n : 0;
+                const int pr = nn / DPR, c4 = nn - pr * DPR;
+                rrel[i] = n < NDW ? (u32)((pr * p.W) * 6 + c4 * 4) : OOB;
+                rco[i] = (u32)((pr << 16) | (((2 * c4) / 3) << 8) | ((2 * c4 + 1) / 3));
+            } else {
+                const int nn = n < PATCH ? n : 0;
+                const int pr = nn / PROW, rem = nn - pr * PROW, pc = rem / 3;
+                rrel[i] = n < PATCH ? (u32)(((pr * p.W) * 3 + rem) * 2) : OOB;
+                rco[i] = (u32)((pr << 16) | (pc << 8) | pc);
+            }
+        }
+        auto load = [&](u32 voff, u32 soff) { return WIDE ? c64_load_u32(voff, r3, soff) : c64_load_u16(voff, r3, soff); };
         // (asm loads + a hand-counted wait in front of the patch stores a tile later: with the builtin hipcc converted / paired the
         //  16-bit values right behind the loads and waited for them there -- one exposed memory round trip per tile, the largest
         //  single item of this wave's 6 500 cycles per tile in the in-kernel timers of profiles/r04p1_*)
-        auto request = [&](int tile, u32 (&raw)[NRAW]) {
+        auto request = [&](int tile, u32 (&raw)[NR]) {
             int b, h0, w0;
             tile_origin(tile, b, h0, w0);
             const int ph = h0 - 2, pw = w0 - 2;                               // image position of patch element (0, 0)
@@ -308,43 +369,64 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
             if (inside) {                                                     // the tile's position is a scalar offset
                 const u32 soff = (u32)((((b * p.H + ph) * p.W + pw) * 3) * 2);
 #pragma unroll
-                for (int i = 0; i < NRAW; ++i) raw[i] = c64_load_u16(rrel[i], r3, soff);
+                for (int i = 0; i < NR; ++i) raw[i] = load(rrel[i], soff);
             } else {
                 const int base = ((b * p.H + ph) * p.W + pw) * 6;             // may be negative: only added to offsets of in-image elements
 #pragma unroll
-                for (int i = 0; i < NRAW; ++i) {
-                    const int pr = (int)(rco[i] >> 8) & 0xff, pc = (int)rco[i] & 0xff;
-                    const bool ok = rrel[i] != OOB && (unsigned)(ph + pr) < (unsigned)p.H && (unsigned)(pw + pc) < (unsigned)p.W;
-                    raw[i] = c64_load_u16(ok ? (u32)(base + (int)rrel[i]) : OOB, r3, 0u);
+                for (int i = 0; i < NR; ++i) {
+                    const int pr = (int)(rco[i] >> 16), pcs = (int)(rco[i] >> 8) & 0xff, pce = (int)rco[i] & 0xff;
+                    const bool ok = rrel[i] != OOB && (unsigned)(ph + pr) < (unsigned)p.H && (unsigned)(pw + pcs) < (unsigned)p.W &&
+                                    (unsigned)(pw + pce) < (unsigned)p.W;
+                    raw[i] = load(ok ? (u32)(base + (int)rrel[i]) : OOB, 0u);
                 }
             }
         };
         C64_PROF_DECL
-        // every request is exactly NRAW loads and this wave issues no other VMEM operation: `newer` = a younger request is in flight
-        auto landed = [&](u32 (&raw)[NRAW], bool newer) {
-            if (newer) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NRAW) : "memory");
+        // every request is exactly NR loads and this wave issues no other VMEM operation: `newer` = a younger request is in flight
+        auto landed = [&](u32 (&raw)[NR], bool newer) {
+            if (newer) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NR) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-            for (int i = 0; i < NRAW; ++i) asm volatile("" : "+v"(raw[i]));
+            for (int i = 0; i < NR; ++i) asm volatile("" : "+v"(raw[i]));
         };
         // Gathers of ALL the wave's blocks first, then all their MFMAs, then the epilogues: the LDS and matrix-pipe latencies of one block
         // are covered by the other's work (the pipe is shared with the SIMD's multiplying wave, whose MFMAs run back to back).
-        auto produce = [&](int tile, const u32 (&raw)[NRAW], int buf) {
+        auto produce = [&](int tile, const u32 (&raw)[NR], int buf) {
             int b, h0, w0;
             tile_origin(tile, b, h0, w0);
-#pragma unroll
-            for (int i = 0; i < NRAW; ++i) reinterpret_cast<unsigned short*>(patch)[64 * i + lane] = (unsigned short)raw[i];   // slots beyond the patch hold 0
             unsigned char* hb = lds + H_OFF + buf * HB;
             bf16x8 bfr[MYB][2];
+            if constexpr (WIDE) {
 #pragma unroll
-            for (int blk = 0; blk < MYB; ++blk)
+                for (int i = 0; i < NR; ++i) reinterpret_cast<u32*>(patch)[64 * i + lane] = raw[i];      // slots beyond the patch hold 0: the spare row stays zero
 #pragma unroll
-                for (int st = 0; st < 2; ++st) {
-                    union { bf16x8 v; unsigned short u[8]; } t;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) t.u[j] = *reinterpret_cast<const unsigned short*>(patch + pbase[blk] + kofs[st][j]);
-                    bfr[blk][st] = t.v;
+                for (int blk = 0; blk < MYB; ++blk) {
+                    const u32* q0 = reinterpret_cast<const u32*>(patch + fadr[blk][0]);
+                    const u32* q1 = reinterpret_cast<const u32*>(patch + fadr[blk][1]);
+                    const u32* q2 = reinterpret_cast<const u32*>(patch + fadr[blk][2]);
+                    const u32* q3 = reinterpret_cast<const u32*>(patch + fadr[blk][3]);
+                    const u32 s0 = q0[0], s1 = q1[0], s2 = q1[1], s3 = q1[2], s4 = q1[3];
+                    const u32 t0 = q2[0], t1 = q2[1], t2 = q3[0], t3 = q3[1], t4 = q3[2], t5 = q3[3];
+                    const c64_u32x4 f0 = {__builtin_amdgcn_perm(s1, s0, fsel[blk][0]), __builtin_amdgcn_perm(s2, s1, fsel[blk][1]),
+                                          __builtin_amdgcn_perm(s3, s2, fsel[blk][1]), __builtin_amdgcn_perm(s4, s3, fsel[blk][1])};
+                    const c64_u32x4 f1 = {__builtin_amdgcn_perm(t1, t0, fsel[blk][2]), __builtin_amdgcn_perm(t3, t2, fsel[blk][3]),
+                                          __builtin_amdgcn_perm(t4, t3, fsel[blk][4]), __builtin_amdgcn_perm(t5, t4, fsel[blk][4])};
+                    bfr[blk][0] = __builtin_bit_cast(bf16x8, f0);
+                    bfr[blk][1] = __builtin_bit_cast(bf16x8, f1);
                 }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NR; ++i) reinterpret_cast<unsigned short*>(patch)[64 * i + lane] = (unsigned short)raw[i];   // slots beyond the patch hold 0
+#pragma unroll
+                for (int blk = 0; blk < MYB; ++blk)
+#pragma unroll
+                    for (int st = 0; st < 2; ++st) {
+                        union { bf16x8 v; unsigned short u[8]; } t;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) t.u[j] = *reinterpret_cast<const unsigned short*>(patch + pbase[blk] + kofs[st][j]);
+                        bfr[blk][st] = t.v;
+                    }
+            }
             // The matrix pipe of this SIMD is shared with its multiplying wave, whose MFMAs are always ready and which wins the issue
             // arbitration (older wave; raised priority): this wave's eight MFMAs used to sit out the multiplier's whole K loop (in-kernel
             // timers, r04p5: 3 200 cycles in this section, the multipliers then waiting 1 000 at the barrier for the epilogue below).
@@ -396,7 +478,7 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
         };
         // Two register sets used alternately (the tile loop is unrolled by two by hand): the set requested in step i is stored into the
         // patch in step i + 1 and never copied, so the only wait for it sits in front of those stores, a whole tile after the request.
-        u32 raw_a[NRAW], raw_b[NRAW];
+        u32 raw_a[NR], raw_b[NR];
         request(first, raw_a);
         landed(raw_a, false);
         produce(first, raw_a, 0);
@@ -404,7 +486,7 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                    // halo of the first tile (+ the multipliers' weights) in place
         int buf = 0;
-        auto step = [&](int tile, u32 (&cur)[NRAW], u32 (&nxt)[NRAW]) {
+        auto step = [&](int tile, u32 (&cur)[NR], u32 (&nxt)[NR]) {
             const bool req = !(SSDHIP_C64_ABLATE & 8) && tile + 2 * stride < p.tiles;                       // 8: idle producers
             if (req) request(tile + 2 * stride, nxt);
             C64_PROF_MARK(0)
@@ -426,6 +508,9 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
             step(tile + stride, raw_b, raw_a);
         }
         if (wave == 4) { C64_PROF_FLUSH(16) }
+        };
+        if (!(p.W & 1) && !((uintptr_t)p.x3 & 3)) run(std::true_type{});
+        else run(std::false_type{});
         return;
       }
     }
