@@ -593,6 +593,20 @@ int ssdhip_conv1_block_nhwc_bf16(const void* x3, const void* w1, const void* b1,
 int ssdhip_conv3x3_cin3_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W,
                                   int Cin, int Cout, int relu, void* stream);
 
+/* A block of SSD7 -- Conv2D(kernel, padding='same') -> BatchNormalization(axis=3) in inference mode -> ELU(alpha=1) [-> MaxPooling2D(2, 2)
+ * 'valid' if pool != 0] (models/keras_ssd7.py:277-309) -- as one launch (csrc/ssdhip_convbn.hip).  x [B, H, W, Cin] bf16, y [B, H, W, Cout]
+ * bf16 or, pooled, [B, H / 2, W / 2, Cout] (the last row / column of an odd map feeds nothing).  Per output value, in float32:
+ * v = fmaf(acc, scale[c], shift[c]); e = v > 0 ? v : expm1f(v); with pool the maximum of the window's four e; one rounding to bf16.
+ * scale, shift [Cout] float32: scale = gamma / sqrt(running_var + eps), shift = beta + (conv_bias - running_mean) scale -- the kernel adds
+ * no other bias.  Geometries: kernel 3 with (Cin, Cout) one of (32, 48), (48, 64), (64, 64), (64, 48), (48, 48), (48, 32); kernel 5 with
+ * Cin 3, Cout 32.  SSDHIP_E_BADARG for any other, and ssdhip_conv_bn_elu_pack_bytes returns 0 for it.
+ * w_packed (16-byte aligned) holds ssdhip_conv_bn_elu_pack_bytes bytes of bf16, zero where not named:
+ *   kernel 3: [kh][kw][32 ceil(Cout / 32)][Cin + 8], element (kh, kw, co, ci) = filter[co][ci][kh][kw] for co < Cout, ci < Cin;
+ *   kernel 5: [kh][32][16], element (kh, co, 3 kw + ci) = filter[co][ci][kh][kw]. */
+size_t ssdhip_conv_bn_elu_pack_bytes(int Cin, int Cout, int kernel);
+int ssdhip_conv_bn_elu_nhwc_bf16(const void* x, const void* w_packed, const float* scale, const float* shift, void* y, int B, int H, int W,
+                                 int Cin, int Cout, int kernel, int pool, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Image half of the training-time augmentation (csrc/ssdhip_image.hip): what the reference does per image on the host
  * through OpenCV (data_generator/object_detection_2d_photometric_ops.py:23-480, object_detection_2d_geometric_ops.py:27-148), for a

@@ -139,6 +139,8 @@ SIGNATURES = {
     "ssdhip_conv3x3_halo_group_nhwc_bf16": (_I, [_I] + [_P] * 9 + [_I, _I, _P]),
     "ssdhip_conv1_block_nhwc_bf16": (_I, [_P] * 6 + [_I] * 7 + [_P]),
     "ssdhip_conv3x3_cin3_nhwc_bf16": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "ssdhip_conv_bn_elu_pack_bytes": (_SZ, [_I] * 3),
+    "ssdhip_conv_bn_elu_nhwc_bf16": (_I, [_P] * 5 + [_I] * 7 + [_P]),
     "ssdhip_image_program": (_I, [_P, _I, _P, _I, _I, _LL] + [_P] * 3),
     "ssdhip_image_resize_cv_u8": (_I, [_P, _P] + [_I] * 8 + [_P, _P, _I, _P, _P, _I, _P]),
     "ssdhip_image_resize_gather_cv_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 3 + [_I, _P, _P, _I, _P, _P]),
@@ -1500,6 +1502,58 @@ def conv3x3_cin3(x, weight, bias, relu=True):
     y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
     launch("ssdhip_conv3x3_cin3_nhwc_bf16", x.device, _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), b, h, w, cin, cout, int(bool(relu)))
     return y
+
+
+def conv_bn_elu_pack(weight, out=None):
+    """Filters (Cout, Cin, k, k) of one of SSD7's blocks -> the bf16 image `conv_bn_elu` keeps resident (include/ssdhip.h,
+    ssdhip_conv_bn_elu_nhwc_bf16: [kh][kw][Cout rounded up to 32][Cin + 8] for k = 3, [kh][32][16] with k = 3 kw + ci for the 5 x 5
+    first layer; zero elsewhere), rounded to bf16 once.  Runs when the weights change, not per step; `out`: refresh that tensor in place."""
+    torch = _torch()
+    if not weight.is_cuda or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
+        raise SsdHipError("weight must be a (Cout, Cin, k, k) CUDA tensor")
+    cout, cin, k, _ = weight.shape
+    nbytes = int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(k)))
+    if nbytes == 0:
+        raise SsdHipError("conv_bn_elu: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, k))
+    wb = weight.detach().to(torch.bfloat16)
+    if k == 3:
+        packed = wb.new_zeros((3, 3, -(-cout // 32) * 32, cin + 8))
+        packed[:, :, :cout, :cin] = wb.permute(2, 3, 0, 1)
+    else:
+        packed = wb.new_zeros((k, cout, 16))
+        packed[:, :, :3 * k] = wb.permute(2, 0, 3, 1).reshape(k, cout, 3 * k)
+    assert packed.numel() * 2 == nbytes
+    if out is None:
+        return packed
+    out.copy_(packed)
+    return out
+
+
+def conv_bn_elu(x, packed, scale, shift, kernel, pool, out=None):
+    """Conv2D(kernel, 'same') -> BatchNormalization (inference) -> ELU [-> MaxPooling2D(2, 2) 'valid'] in one launch
+    (csrc/ssdhip_convbn.hip).  x (B, Cin, H, W) bf16 with NHWC memory; packed: `conv_bn_elu_pack` of the filters; scale, shift:
+    float32 (Cout,) tables, y = elu(conv(x) * scale + shift).  Returns (B, Cout, H, W) -- pooled (B, Cout, H // 2, W // 2) -- bf16
+    with NHWC memory (`out`: written there).  Raises for a geometry the kernel does not cover."""
+    torch = _torch()
+    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4:
+        raise SsdHipError("x must be a 4-D bfloat16 CUDA tensor")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    b, cin, h, w = x.shape
+    cout = scale.numel()
+    if (scale.dtype != torch.float32 or shift.dtype != torch.float32 or shift.numel() != cout or not scale.is_contiguous()
+            or not shift.is_contiguous() or not packed.is_contiguous() or packed.dtype != torch.bfloat16
+            or packed.numel() * 2 != int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(kernel)))):
+        raise SsdHipError("conv_bn_elu: float32 (Cout,) tables and the packed filters of this geometry (Cin = %d, Cout = %d, k = %d)"
+                          % (cin, cout, kernel))
+    ho, wo = (h // 2, w // 2) if pool else (h, w)
+    if out is None:
+        out = torch.empty((b, ho, wo, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    elif tuple(out.shape) != (b, cout, ho, wo) or out.dtype != torch.bfloat16 or not out.permute(0, 2, 3, 1).is_contiguous():
+        raise SsdHipError("conv_bn_elu: `out` must be a (%d, %d, %d, %d) bf16 tensor with NHWC memory" % (b, cout, ho, wo))
+    launch("ssdhip_conv_bn_elu_nhwc_bf16", x.device, _ptr(x), _ptr(packed), _ptr(scale), _ptr(shift), _ptr(out), b, h, w, cin, cout,
+           int(kernel), int(bool(pool)))
+    return out
 
 
 def conv1_block(x, w1, b1, weight, bias, relu=True, pool=False):

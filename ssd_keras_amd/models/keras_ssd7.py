@@ -6,9 +6,11 @@ Seven conv + BatchNorm(eps 1e-3, Keras momentum 0.99) + ELU blocks with 2x2 'val
 from __future__ import annotations
 
 import numpy as np
+import torch
 from torch import nn
 import torch.nn.functional as F
 
+from .. import _native as nat
 from ._common import SSDModel, he_normal_, make_priorboxes, pool_out, resolve_anchor_config
 
 
@@ -32,8 +34,74 @@ class SSD7(SSDModel):
                                           ['anchors4', 'anchors5', 'anchors6', 'anchors7'])
         he_normal_(self)
 
+    def fused_blocks(self, enable=True):
+        """Opt in to (or, with False, out of) running every Conv2D -> BatchNormalization -> ELU [-> MaxPooling2D] block of a bf16 model
+        in eval mode under no_grad as ONE libssdhip launch (csrc/ssdhip_convbn.hip): the block's map is rounded to bf16 once instead of
+        three times and is never written and read back between the convolution, the normalisation, the activation and the pool.  Off by
+        default: the default bf16 path stays bit-identical to the framework's.  A model in train() mode (batch statistics) and every
+        other dtype / device keep the default path whatever the switch says.  Returns the model."""
+        self.__dict__["_fused_blocks"] = bool(enable)
+        return self
+
+    def _fused_blocks_on(self, x):
+        return (self.__dict__.get("_fused_blocks", False) and not self.training and self._fused(x)
+                and self.convs[0].weight.dtype == torch.bfloat16 and self.img_channels == 3)
+
+    def _block_sources(self, i):
+        conv, bn = self.convs[i], self.bns[i]
+        return (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+
+    def _block_key(self, i):
+        return tuple((t.data_ptr(), t._version) for t in self._block_sources(i))
+
+    def _block_tables(self, i):
+        """(packed filters, scale, shift) of block i for `nat.conv_bn_elu`, cached; rebuilt IN THEIR OWN STORAGE (a captured HIP graph
+        keeps reading it) when the convolution's or the BatchNorm's tensors changed -- an in-place update (optimizer step,
+        load_state_dict, load_keras_weights) bumps `_version`, a replaced storage changes `data_ptr()`.  The tables are computed on
+        the host in float64 and rounded once: scale = gamma / sqrt(running_var + eps), shift = beta + (conv_bias - running_mean) scale."""
+        cache = self.__dict__.setdefault("_block_cache", {})
+        key = self._block_key(i)
+        hit = cache.get(i)
+        if hit is not None and hit[0] == key and hit[1].device == self.convs[i].weight.device:
+            return hit[1:]
+        w, b, gamma, beta, mean, var = (t.detach() for t in self._block_sources(i))
+        f64 = lambda t: t.double().cpu()
+        scale = f64(gamma) / torch.sqrt(f64(var) + self.bns[i].eps)
+        shift = f64(beta) + (f64(b) - f64(mean)) * scale
+        tables = torch.stack([scale, shift]).float().to(w.device)
+        if hit is not None and hit[1].device == w.device:
+            nat.conv_bn_elu_pack(w, out=hit[1])
+            hit[2].copy_(tables[0])
+            hit[3].copy_(tables[1])
+            hit = (key,) + tuple(hit[1:])
+        else:
+            hit = (key, nat.conv_bn_elu_pack(w), tables[0].contiguous(), tables[1].contiguous())
+        cache[i] = hit
+        return hit[1:]
+
+    def _derived_weights_key(self):
+        key = super()._derived_weights_key()
+        if self.__dict__.get("_block_cache"):
+            key += tuple(self._block_key(i) for i in range(7))
+        return key
+
+    def _refresh_derived_weights(self):
+        super()._refresh_derived_weights()
+        for i in list(self.__dict__.get("_block_cache", {})):
+            self._block_tables(i)
+
     def features(self, x):
         feats = []
+        if self._fused_blocks_on(x):
+            # blocks 1-3 with their pool in the launch; blocks 4-7 feed the predictor heads with their full maps, then the pooling pass
+            for i in range(7):
+                packed, scale, shift = self._block_tables(i)
+                x = nat.conv_bn_elu(x, packed, scale, shift, 5 if i == 0 else 3, pool=i < 3)
+                if i >= 3:
+                    feats.append(x)
+                    if i < 6:
+                        x = self.max_pool(x, 2, 2)
+            return feats
         for i in range(7):
             x = F.elu(self.bns[i](self.convs[i](x)))
             if i >= 3:
