@@ -21,14 +21,9 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
 
 namespace ssdhip {
-
-typedef unsigned short bf16_t;
-typedef __bf16 cc_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float cc_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 cc_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float cc_f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CC_MAX_LAYERS = 8;
 constexpr int CC_THREADS = 512;
@@ -54,13 +49,6 @@ struct ChainParams {
     int n_layers, zero_off;      // zero_off: LDS offset of a row of zeros (padding taps)
     ChainLayerDev L[CC_MAX_LAYERS];
 };
-
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ u32 cc_pack2(float a, float b) {
-    const cc_f32x2 v = {a, b};
-    return __builtin_bit_cast(u32, __builtin_convertvector(v, cc_bf16x2));
-}
-#endif
 
 template <int CC_RING>
 __global__ __launch_bounds__(CC_THREADS) void conv_chain_kernel(ChainParams p) {
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(CC_THREADS) void conv_chain_kernel(ChainParams p) {
             const int ho = live ? pix / l.Wout : 0, wo = live ? pix - ho * l.Wout : 0;
             const int hi0 = ho * l.stride - l.pad, wi0 = wo * l.stride - l.pad;
             const uint4* wsrc = l.wp + (size_t)nb * kt * 64 + lane;
-            cc_f32x16 acc, acc1;                          // even / odd K-steps: two dependency chains through the matrix pipe instead of one
+            f32x16 acc, acc1;                          // even / odd K-steps: two dependency chains through the matrix pipe instead of one
 #pragma unroll
             for (int v = 0; v < 16; ++v) { acc[v] = 0.f; acc1[v] = 0.f; }
             uint4 ring[CC_RING];
@@ -134,8 +122,8 @@ __global__ __launch_bounds__(CC_THREADS) void conv_chain_kernel(ChainParams p) {
                     const int kn = kb + CC_RING + j;
                     ring[SB + j] = wsrc[(size_t)(kn < kt ? kn : kt - 1) * 64];
                     __builtin_amdgcn_sched_barrier(0);    // the refill is issued HERE, eight steps ahead of its use, not batched at the block's end
-                    if (j & 1) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cc_bf16x8, a), __builtin_bit_cast(cc_bf16x8, bq[HB][j]), acc1, 0, 0, 0);
-                    else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cc_bf16x8, a), __builtin_bit_cast(cc_bf16x8, bq[HB][j]), acc, 0, 0, 0);
+                    if (j & 1) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq[HB][j]), acc1, 0, 0, 0);
+                    else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq[HB][j]), acc, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
@@ -178,7 +166,7 @@ __global__ __launch_bounds__(CC_THREADS) void conv_chain_kernel(ChainParams p) {
                         if (l.bias) v += __uint_as_float((u32)l.bias[c + e] << 16);
                         o[e] = l.relu ? (v <= 0.f ? 0.f : v) : v;
                     }
-                    const uint2 pk = make_uint2(cc_pack2(o[0], o[1]), cc_pack2(o[2], o[3]));
+                    const uint2 pk = make_uint2(pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3]));
                     *reinterpret_cast<uint2*>(lds + l.out_off + pix * out_stride + c * 2) = pk;
                     if (l.y) *reinterpret_cast<uint2*>(l.y + ((size_t)b * npix + pix) * l.Cout + c) = pk;
                 }
@@ -199,7 +187,6 @@ __global__ __launch_bounds__(CC_THREADS) void conv_chain_kernel(ChainParams p) {
 // waves per SIMD: 32 ring + 64 pixel-operand + 48 accumulator registers).  Replaces six launches of 22-102 us each on the
 // reference-precision step's critical path.
 // ======================================================================================
-typedef _Float16 cc_f16x8 __attribute__((ext_vector_type(8)));
 [[maybe_unused]] constexpr int CX_PF = 4;                                 // K-steps of a block (one tap x 64 channels)
 // K-steps of filter (hi, lo) twins a wave keeps in flight (CX_RING: 4 or 8 -- one or two blocks); 8 measured 3 % slower than 4
 // (104.4 against 101.2 us, same file): SSDHIP_CHAIN_X3_RING=4|8 selects at launch
@@ -252,7 +239,7 @@ __global__ __launch_bounds__(CC_THREADS) void conv_chain_x3_kernel(ChainX3Params
             const int ho = live ? pix / l.Wout : 0, wo = live ? pix - ho * l.Wout : 0;
             const int hi0 = ho * l.stride - l.pad, wi0 = wo * l.stride - l.pad;
             const uint4* wsrc = l.wp + (size_t)nb * kt * 128 + lane;
-            cc_f32x16 a_hh, a_hl, a_lh;
+            f32x16 a_hh, a_hl, a_lh;
 #pragma unroll
             for (int v = 0; v < 16; ++v) { a_hh[v] = 0.f; a_hl[v] = 0.f; a_lh[v] = 0.f; }
             uint4 rh[CX_RING], rl[CX_RING];
@@ -300,9 +287,9 @@ __global__ __launch_bounds__(CC_THREADS) void conv_chain_x3_kernel(ChainX3Params
                     rh[SB + j] = wsrc[o];
                     rl[SB + j] = wsrc[o + 64];
                     __builtin_amdgcn_sched_barrier(0);
-                    a_hh = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cc_f16x8, wh), __builtin_bit_cast(cc_f16x8, bh[HB][j]), a_hh, 0, 0, 0);
-                    a_hl = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cc_f16x8, wh), __builtin_bit_cast(cc_f16x8, bl[HB][j]), a_hl, 0, 0, 0);
-                    a_lh = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cc_f16x8, wl), __builtin_bit_cast(cc_f16x8, bh[HB][j]), a_lh, 0, 0, 0);
+                    a_hh = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh), __builtin_bit_cast(f16x8, bh[HB][j]), a_hh, 0, 0, 0);
+                    a_hl = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wh), __builtin_bit_cast(f16x8, bl[HB][j]), a_hl, 0, 0, 0);
+                    a_lh = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wl), __builtin_bit_cast(f16x8, bh[HB][j]), a_lh, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };

@@ -23,12 +23,10 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
+#include "ssdhip_tile.h"
 
 namespace ssdhip {
-
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __attribute__((aligned(64))) const unsigned int g_zero_block[16] = {0};
 
@@ -57,12 +55,6 @@ struct ConvParams {
     const float* bias32;
     float oscale;
 };
-
-__device__ __forceinline__ u32 f2bf_rn(float f) {
-    const u32 u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 __device__ __forceinline__ void glds16(const void* src, unsigned char* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -202,7 +194,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_igemm_kernel(ConvParams 
                 for (int q = 0; q < 4; ++q) {
                     float v = acc[ci][pi][4 * g + q] + bv[q];
                     if (p.relu) v = v > 0.f ? v : (v != v ? v : 0.f);
-                    o[q] = f2bf_rn(v);
+                    o[q] = bf16_bits(v);
                 }
                 const int chunk = ci * 4 + g;          // 16-byte chunk of the pixel row; this lane fills half of it
                 *reinterpret_cast<uint2*>(stage + px * ROWB + ((chunk ^ (px & (4 * CI - 1))) << 4) + khalf * 8) =
@@ -257,13 +249,6 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // ONE K loop over 3 C channels: slices [0, n) multiply x hi by w hi, [n, 2n) x hi by w lo, [2n, 3n) x lo by w hi (the filters are
 // packed [w hi | w lo | w hi] on the host, x is read through the slice map j -> j < n ? j : j - n).  The epilogue scales, adds the
 // float32 bias, applies the activation on float32 values and splits the result again (or leaves it float32 for the graph glue).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ u32 x3_split2(float a, float b, u32& lo_out) {
-    const _Float16 ha = (_Float16)a, hb = (_Float16)b;
-    const _Float16 la = (_Float16)(a - (float)ha), lb = (_Float16)(b - (float)hb);
-    lo_out = (u32)__builtin_bit_cast(unsigned short, la) | ((u32)__builtin_bit_cast(unsigned short, lb) << 16);
-    return (u32)__builtin_bit_cast(unsigned short, ha) | ((u32)__builtin_bit_cast(unsigned short, hb) << 16);
-}
 
 template <int BC, bool POOL, bool SK = false, bool X3 = false>
 __device__ __forceinline__ void conv_igemm4_body(const ConvParams& p, unsigned char* lds, const int id_) {
@@ -504,7 +489,7 @@ __device__ __forceinline__ void conv_igemm4_body(const ConvParams& p, unsigned c
                         *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + (size_t)pix[pi] * p.Cout + ch) = make_float4(v[0], v[1], v[2], v[3]);
                     } else {
                         u32 l0, l1;
-                        const u32 h0 = x3_split2(v[0], v[1], l0), h1 = x3_split2(v[2], v[3], l1);
+                        const u32 h0 = split2_f16(v[0], v[1], l0), h1 = split2_f16(v[2], v[3], l1);
                         bf16_t* row = p.y + (size_t)pix[pi] * (2 * p.Cout) + ch;
                         *reinterpret_cast<uint2*>(row) = make_uint2(h0, h1);
                         *reinterpret_cast<uint2*>(row + p.Cout) = make_uint2(l0, l1);
@@ -543,7 +528,7 @@ __device__ __forceinline__ void conv_igemm4_body(const ConvParams& p, unsigned c
                     if (has_right) v = right > v ? right : v;
                     v += bv[q];
                     if (p.relu) v = v > 0.f ? v : (v != v ? v : 0.f);
-                    o[q] = f2bf_rn(v);
+                    o[q] = bf16_bits(v);
                 }
                 if (!(r31 & 1)) {
                     const int px = r31 >> 1, chunk = ci * 4 + g;
@@ -604,7 +589,7 @@ __device__ __forceinline__ void conv_igemm4_body(const ConvParams& p, unsigned c
                 for (int q = 0; q < 4; ++q) {
                     float v = acc[ci][pi][4 * g + q] + bv[q];
                     if (p.relu) v = v > 0.f ? v : (v != v ? v : 0.f);
-                    o[q] = f2bf_rn(v);
+                    o[q] = bf16_bits(v);
                 }
                 const int chunk = ci * 4 + g;
                 *reinterpret_cast<uint2*>(stage + px * ROWB + ((chunk ^ (px & (4 * CI - 1))) << 4) + khalf * 8) =
@@ -683,7 +668,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     for (int e = 0; e < 8; ++e) {
         float v = a[e] + (bias ? __uint_as_float((u32)bias[co + e] << 16) : 0.f);
         if (relu) v = v > 0.f ? v : (v != v ? v : 0.f);
-        o[e] = f2bf_rn(v);
+        o[e] = bf16_bits(v);
     }
     *reinterpret_cast<uint4*>(y + i * 8) = make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16));
 }
@@ -732,28 +717,7 @@ __global__ __launch_bounds__(CONV_THREADS, 2) void conv_igemm4_group_kernel(Conv
 //   * LDS rows are 64 bytes (32 channels); 16-byte chunk c of row r sits at position c ^ ((r >> 2) & 3), which keeps
 //     both the lane-linear LDS-DMA image and the ds_read_b128 fragment reads free of bank conflicts.
 // =================================================================================================================
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
 #if defined(__HIP_DEVICE_COMPILE__)
-// one wave-wide 1 KiB LDS-DMA load: lane L writes 16 bytes at lds_dst + 16 L from base(rsrc) + soff + voff (zeros if voff is
-// out of range).  M0 is saved and restored inside the statement (hipcc does not model it around asm).
-__device__ __forceinline__ void bload_lds16(u32 voff, i32x4 rsrc, u32 lds_dst, u32 soff) {
-    u32 keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst), "s"(soff) : "memory");
-}
-
-__device__ __forceinline__ i32x4 make_rsrc(const void* base, long offset_bytes, int num_records) {
-    const unsigned long long a = (unsigned long long)(uintptr_t)base + (unsigned long long)offset_bytes;
-    i32x4 r;
-    r.x = (int)(u32)a;
-    r.y = (int)((u32)(a >> 32) & 0xffffu);             // stride 0, no swizzle
-    r.z = num_records;
-    r.w = 0x00020000;
-    return r;
-}
-
 template <int BC, int NS>
 __device__ __forceinline__ void conv_igemm5_body(const ConvParams& p, unsigned char* lds) {
     constexpr int CI = BC / 64;
@@ -775,8 +739,8 @@ __device__ __forceinline__ void conv_igemm5_body(const ConvParams& p, unsigned c
     const int csteps = Cin / BK, T = KK * csteps;
 
     const int neg = (half * dil * p.W + half * dil) * Cin * 2;
-    const i32x4 rx = make_rsrc(p.x, -(long)neg, p.Min * Cin * 2 + 2 * neg);
-    const i32x4 rw = make_rsrc(p.w, 0, p.Cout * KK * Cin * 2);
+    const i32x4 rx = tile_rsrc(p.x, -(long)neg, p.Min * Cin * 2 + 2 * neg);
+    const i32x4 rw = tile_rsrc(p.w, p.Cout * KK * Cin * 2);
     const u32 lds0 = (u32)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
 
     // ---- per-thread load descriptors: a 1 KiB piece = 16 rows x 64 bytes; lane L -> row L >> 2, position L & 3 ------
@@ -843,9 +807,9 @@ __device__ __forceinline__ void conv_igemm5_body(const ConvParams& p, unsigned c
         const u32 tapbit = 1u << t;
         const u32 xb = lds0 + stage * STG + wave * 1024, wb = xb + XBYTES;
 #pragma unroll
-        for (int i = 0; i < XP; ++i) bload_lds16((xok[i] & tapbit) ? xoff[i] : OOB, rx, xb + i * 4096, soff_x);
+        for (int i = 0; i < XP; ++i) tile_dma16_soff((xok[i] & tapbit) ? xoff[i] : OOB, rx, xb + i * 4096, soff_x);
 #pragma unroll
-        for (int i = 0; i < WP; ++i) bload_lds16(woff[i], rw, wb + i * 4096, soff_w);
+        for (int i = 0; i < WP; ++i) tile_dma16_soff(woff[i], rw, wb + i * 4096, soff_w);
         if (++n_kw == KS) { n_kw = 0; if (++n_kh == KS) { n_kh = 0; ++n_cs; } }
     };
 
@@ -920,7 +884,7 @@ __device__ __forceinline__ void conv_igemm5_body(const ConvParams& p, unsigned c
                 for (int q = 0; q < 4; ++q) {
                     float v = acc[ci][pi][4 * g + q] + bv[q];
                     if (p.relu) v = v > 0.f ? v : (v != v ? v : 0.f);
-                    o[q] = f2bf_rn(v);
+                    o[q] = bf16_bits(v);
                 }
                 const int chunk = ci * 4 + g;
                 *reinterpret_cast<uint2*>(stage + px * ROWB + ((chunk ^ (px & (4 * CI - 1))) << 4) + khalf * 8) =
@@ -1091,7 +1055,7 @@ __global__ __launch_bounds__(C1_BP) void conv3x3_cin3_kernel(const bf16_t* __res
                 for (int q = 0; q < 4; ++q) {
                     float v = acc[ci][pi][4 * g + q] + bv[q];
                     if (relu) v = v > 0.f ? v : (v != v ? v : 0.f);
-                    o[q] = f2bf_rn(v);
+                    o[q] = bf16_bits(v);
                 }
                 *reinterpret_cast<uint2*>(stage + r31 * 128 + (((ci * 4 + g) ^ (r31 & 7)) << 4) + khalf * 8) =
                     make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));

@@ -32,17 +32,14 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
+#include "ssdhip_tile.h"
 
 #ifndef SSDHIP_C64_ABLATE
 #define SSDHIP_C64_ABLATE 0      // profiling builds only (tools/prof_build.sh): 1 no global stores, 2 no epilogue, 4 no fragment reads (wrong results)
 #endif
 
 namespace ssdhip {
-
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // In-kernel phase timers of the Cin = 64 kernels, profiling build only (tools/prof_build.sh): shader cycles of wave 0 (multiplier) and
 // wave 4 (loader / first producer) per phase, summed over tiles and workgroups; read back with ssdhip_profile_read_c64.
@@ -93,21 +90,7 @@ struct C64Params {
     bf16_t* y2;                  // KEEP (training, round 6): the full-resolution activation [B, H, W, Cout] beside the pooled y
 };
 
-__device__ __forceinline__ u32 c64_f2bf_rn(float f) {
-    const u32 u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 #if defined(__HIP_DEVICE_COMPILE__)
-typedef __bf16 c64_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float c64_f32x2 __attribute__((ext_vector_type(2)));
-// two float32 -> packed bf16, round to nearest even: one v_cvt_pk_bf16_f32 (the integer formulation of ssdhip_conv.hip costs
-// ~6 VALU operations per value, and with one wave per SIMD every epilogue instruction is MFMA idle time)
-__device__ __forceinline__ u32 c64_pack2(float a, float b) {
-    const c64_f32x2 v = {a, b};
-    return __builtin_bit_cast(u32, __builtin_convertvector(v, c64_bf16x2));
-}
 // max(v, v of lane ^ 1) in ONE VALU instruction (DPP quad_perm [1,0,3,2] on the first operand).  The s_nop covers the
 // VALU-write -> DPP-read hazard, which hipcc does not pad inside an asm statement; the operand always comes from a VALU op.
 __device__ __forceinline__ float c64_max_with_lane_xor1(float v) {
@@ -115,13 +98,6 @@ __device__ __forceinline__ float c64_max_with_lane_xor1(float v) {
     asm("s_nop 1\n\tv_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v));
     return r;
 }
-typedef short c64_s16x2 __attribute__((ext_vector_type(2)));
-typedef u32 c64_u32x2 __attribute__((ext_vector_type(2)));
-// v_pk_max_i16 on two packed bf16 values (see the epilogue)
-__device__ __forceinline__ u32 c64_pkmax_i16(u32 a, u32 b) {
-    return __builtin_bit_cast(u32, __builtin_elementwise_max(__builtin_bit_cast(c64_s16x2, a), __builtin_bit_cast(c64_s16x2, b)));
-}
-typedef u32 c64_u32x4 __attribute__((ext_vector_type(4)));
 // The epilogue's stores.  In the accumulator layout the lane (pixel, khalf) holds channels 8 g + 4 khalf + (0 .. 3) of the wave's 32 as
 // (lo[g], hi[g]) for g = 0 .. 3: 8-byte runs.  v_permlane32_swap trades them between the two lanes of a pixel (lane, lane + 32) so that
 // the khalf = 0 lane ends up with all 16 bytes of g = 0 / 2 and the khalf = 1 lane with those of g = 1 / 3: two 16-byte stores per
@@ -132,18 +108,9 @@ __device__ __forceinline__ void c64_store_runs(const u32 (&lo)[4], const u32 (&h
     for (int pr = 0; pr < 2; ++pr) {
         const auto sl = __builtin_amdgcn_permlane32_swap(lo[2 * pr], lo[2 * pr + 1], false, false);
         const auto sh = __builtin_amdgcn_permlane32_swap(hi[2 * pr], hi[2 * pr + 1], false, false);
-        if (!(SSDHIP_C64_ABLATE & 1)) __builtin_amdgcn_raw_buffer_store_b128(c64_u32x4{sl[0], sh[0], sl[1], sh[1]}, ry, voff + pr * 32, soff, 0);
+        if (!(SSDHIP_C64_ABLATE & 1)) __builtin_amdgcn_raw_buffer_store_b128(u32x4{sl[0], sh[0], sl[1], sh[1]}, ry, voff + pr * 32, soff, 0);
     }
 }
-__device__ __forceinline__ float c64_relu(float v) { return v <= 0.f ? 0.f : v; }     // NaN stays NaN, -0 -> +0 (as ssdhip_conv.hip)
-
-// one wave-wide 1 KiB LDS-DMA load (see ssdhip_conv.hip: inline asm so hipcc does not drain vmcnt before aliasing ds_reads)
-__device__ __forceinline__ void c64_bload(u32 voff, i32x4 rsrc, u32 lds_dst, u32 soff = 0) {
-    u32 keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst), "s"(soff) : "memory");
-}
-
 // one two-byte buffer load (zero-extended), not tracked by hipcc's wait-count insertion: the caller counts vmcnt
 __device__ __forceinline__ u32 c64_load_u16(u32 voff, i32x4 rsrc, u32 soff) {
     u32 v;
@@ -156,16 +123,6 @@ __device__ __forceinline__ u32 c64_load_u32(u32 voff, i32x4 rsrc, u32 soff) {
     u32 v;
     asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
     return v;
-}
-
-__device__ __forceinline__ i32x4 c64_rsrc(const void* base, int num_records) {
-    const unsigned long long a = (unsigned long long)(uintptr_t)base;
-    i32x4 r;
-    r.x = (int)(u32)a;
-    r.y = (int)((u32)(a >> 32) & 0xffffu);
-    r.z = num_records;
-    r.w = 0x00020000;
-    return r;
 }
 
 // FRONT: the 64-channel input map is never read from memory -- it is conv1_1 (3 -> 64 channels, models/keras_ssd300.py:274) of the
@@ -212,8 +169,8 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
     // activations: descriptor base one image row + one pixel BEFORE x, so the halo origin of any tile is a non-negative scalar
     // offset; gfx950 range-checks voffset + soffset, hence the widened num_records (valid lanes still only touch bytes of x)
     const int xneg = (p.W + 1) * 128;
-    const i32x4 rx = c64_rsrc(reinterpret_cast<const unsigned char*>(p.x) - xneg, p.x_bytes + 2 * xneg);
-    const i32x4 rw = c64_rsrc(p.w, p.w_bytes);
+    const i32x4 rx = tile_rsrc(reinterpret_cast<const unsigned char*>(p.x) - xneg, p.x_bytes + 2 * xneg);
+    const i32x4 rw = tile_rsrc(p.w, p.w_bytes);
 
     // ---- resident weights: tap t -> [64 co rows][128 B], 16-byte chunk c of row r at position c ^ ((r >> 1) & 7) ----------
     if (!WREG && wave < 4) {
@@ -225,7 +182,7 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
                 const int piece = i * 4 + wave;
                 const int row = piece * 8 + (lane >> 3);
                 const int j = pos ^ ((row >> 1) & 7);
-                c64_bload((u32)((co0 + row) * 1152 + t * 128 + j * 16), rw, lds0 + W_OFF + t * 8192 + piece * 1024);
+                tile_dma16_soff((u32)((co0 + row) * 1152 + t * 128 + j * 16), rw, lds0 + W_OFF + t * 8192 + piece * 1024, 0u);   // (soffset 0 in an SGPR)
             }
     }
 
@@ -285,7 +242,7 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
             hdst[blk] = (u32)(hpc * 144 + 8 * khalf);
             hcoord[blk] = (u32)((hr << 8) | hc | (hp < HPX ? 0 : 0x10000));
         }
-        const i32x4 r3 = c64_rsrc(p.x3, p.B * p.H * p.W * 6);
+        const i32x4 r3 = tile_rsrc(p.x3, p.B * p.H * p.W * 6);
         // Two forms of the data movement (image -> registers -> patch -> B fragments); the MFMAs and the epilogue are shared.
         // WIDE: everything in dwords.  A patch row is PROW * 2 contiguous bytes of the image and starts on a dword when the image does and
         // W is even (tile origins are even columns) -- 300, 512 and every other size the models use.  Then the patch is NDW dwords: NRAWW
@@ -407,9 +364,9 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
                     const u32* q3 = reinterpret_cast<const u32*>(patch + fadr[blk][3]);
                     const u32 s0 = q0[0], s1 = q1[0], s2 = q1[1], s3 = q1[2], s4 = q1[3];
                     const u32 t0 = q2[0], t1 = q2[1], t2 = q3[0], t3 = q3[1], t4 = q3[2], t5 = q3[3];
-                    const c64_u32x4 f0 = {__builtin_amdgcn_perm(s1, s0, fsel[blk][0]), __builtin_amdgcn_perm(s2, s1, fsel[blk][1]),
+                    const u32x4 f0 = {__builtin_amdgcn_perm(s1, s0, fsel[blk][0]), __builtin_amdgcn_perm(s2, s1, fsel[blk][1]),
                                           __builtin_amdgcn_perm(s3, s2, fsel[blk][1]), __builtin_amdgcn_perm(s4, s3, fsel[blk][1])};
-                    const c64_u32x4 f1 = {__builtin_amdgcn_perm(t1, t0, fsel[blk][2]), __builtin_amdgcn_perm(t3, t2, fsel[blk][3]),
+                    const u32x4 f1 = {__builtin_amdgcn_perm(t1, t0, fsel[blk][2]), __builtin_amdgcn_perm(t3, t2, fsel[blk][3]),
                                           __builtin_amdgcn_perm(t4, t3, fsel[blk][4]), __builtin_amdgcn_perm(t5, t4, fsel[blk][4])};
                     bfr[blk][0] = __builtin_bit_cast(bf16x8, f0);
                     bfr[blk][1] = __builtin_bit_cast(bf16x8, f1);
@@ -466,7 +423,7 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
                             float o[4];
 #pragma unroll
                             for (int e = 0; e < 4; ++e) o[e] = a1[blk][cb][4 * g + e] + b1v[cb][4 * g + e];
-                            u32 lo = c64_pkmax_i16(c64_pack2(o[0], o[1]), 0u), hi = c64_pkmax_i16(c64_pack2(o[2], o[3]), 0u);
+                            u32 lo = pkmax_i16(pack2_bf16(o[0], o[1]), 0u), hi = pkmax_i16(pack2_bf16(o[2], o[3]), 0u);
                             if constexpr (EDGE) { lo &= keep; hi &= keep; }
                             if (live) *reinterpret_cast<uint2*>(hb + hdst[blk] + (cb * 32 + 8 * g) * 2) = make_uint2(lo, hi);
                         }
@@ -547,14 +504,14 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
             if (h0 >= 1 && w0 >= 1 && h0 + 2 * RP + 1 <= p.H && w0 + CC + 1 <= p.W) {
                 const u32 soff = (u32)(((b * p.H + h0 - 1) * p.W + (w0 - 1)) * 128 + xneg);
 #pragma unroll
-                for (int k = 0; k < NPW; ++k) c64_bload(rel[k], rx, dst + k * C64_NLOAD * 1024, soff);
+                for (int k = 0; k < NPW; ++k) tile_dma16_soff(rel[k], rx, dst + k * C64_NLOAD * 1024, soff);
             } else {
 #pragma unroll
                 for (int k = 0; k < NPW; ++k) {
                     const int h = h0 - 1 + (hrc[k] >> 16), w = w0 - 1 + ((hrc[k] >> 4) & 0xfff);
                     const bool ok = hrc[k] >= 0 && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W;
                     const u32 voff = ok ? (u32)(((b * p.H + h) * p.W + w) * 128 + (hrc[k] & 15) * 16 + xneg) : OOB;
-                    c64_bload(voff, rx, dst + k * C64_NLOAD * 1024);
+                    tile_dma16_soff(voff, rx, dst + k * C64_NLOAD * 1024, 0u);   // (soffset 0 in an SGPR, as above)
                 }
             }
         };
@@ -690,7 +647,7 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
         //      store -- and with one wave per SIMD all of it was MFMA idle time (in-kernel timers, profiles/r04p1_*: 1 700 - 2 400 of
         //      a tile's 4 600 - 5 200 cycles).  L2 merges the partial lines; a tile writes 16 KB per ~3 000 cycles, nowhere near a
         //      store-path limit.  Per 4 values: 2 packed bias adds, 2 packed conversions, 2 v_pk_max_i16 (ReLU on the rounded pair:
-        //      for bf16 bit patterns integer order is numeric order and -0 / negative values become +0, as c64_relu; +NaN stays NaN).
+        //      for bf16 bit patterns integer order is numeric order and -0 / negative values become +0, as relu_nan; +NaN stays NaN).
         //      The store address is image base (descriptor) + tile origin (scalar) + a per-lane constant; pixels outside the map get
         //      an out-of-range offset, which the buffer unit drops -- no branches. ------------------------------------------------
         int b, h0, w0;
@@ -711,8 +668,8 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
                     u32 lo[4], hi[4];
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        lo[g] = c64_pkmax_i16(c64_pack2(acc[pi][4 * g] + bv[4 * g], acc[pi][4 * g + 1] + bv[4 * g + 1]), floor16);
-                        hi[g] = c64_pkmax_i16(c64_pack2(acc[pi][4 * g + 2] + bv[4 * g + 2], acc[pi][4 * g + 3] + bv[4 * g + 3]), floor16);
+                        lo[g] = pkmax_i16(pack2_bf16(acc[pi][4 * g] + bv[4 * g], acc[pi][4 * g + 1] + bv[4 * g + 1]), floor16);
+                        hi[g] = pkmax_i16(pack2_bf16(acc[pi][4 * g + 2] + bv[4 * g + 2], acc[pi][4 * g + 3] + bv[4 * g + 3]), floor16);
                     }
                     c64_store_runs(lo, hi, ry2, voff2, sbase2);
                 }
@@ -747,8 +704,8 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
                         }
                         o[e] = v + bv[4 * g + e];
                     }
-                    lo[g] = c64_pkmax_i16(c64_pack2(o[0], o[1]), floor16);
-                    hi[g] = c64_pkmax_i16(c64_pack2(o[2], o[3]), floor16);
+                    lo[g] = pkmax_i16(pack2_bf16(o[0], o[1]), floor16);
+                    hi[g] = pkmax_i16(pack2_bf16(o[2], o[3]), floor16);
                 }
                 c64_store_runs(lo, hi, ry, voff, sbase);
             };
@@ -765,8 +722,8 @@ __device__ __forceinline__ void conv64_body(const C64Params& p, unsigned char* l
                 u32 lo[4], hi[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    lo[g] = c64_pkmax_i16(c64_pack2(acc[pi][4 * g] + bv[4 * g], acc[pi][4 * g + 1] + bv[4 * g + 1]), floor16);
-                    hi[g] = c64_pkmax_i16(c64_pack2(acc[pi][4 * g + 2] + bv[4 * g + 2], acc[pi][4 * g + 3] + bv[4 * g + 3]), floor16);
+                    lo[g] = pkmax_i16(pack2_bf16(acc[pi][4 * g] + bv[4 * g], acc[pi][4 * g + 1] + bv[4 * g + 1]), floor16);
+                    hi[g] = pkmax_i16(pack2_bf16(acc[pi][4 * g + 2] + bv[4 * g + 2], acc[pi][4 * g + 3] + bv[4 * g + 3]), floor16);
                 }
                 c64_store_runs(lo, hi, ry, voff, sbase);
             }

@@ -26,15 +26,10 @@
 #include <stdint.h>
 
 #include "ssdhip.h"
+#include "ssdhip_bf16.h"
 
 namespace ssdhip {
 namespace {
-
-typedef __bf16 cbn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cbn_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float cbn_f32x2 __attribute__((ext_vector_type(2)));
-typedef float cbn_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int cbn_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CBN_THREADS = 256;                         // four waves: wave i owns rows 2 i, 2 i + 1 of a tile
 constexpr int CBN_TH = 8, CBN_TW = 32;                   // output tile
@@ -50,11 +45,6 @@ struct CbnParams {
     int HT, WT, tiles;           // tile grid per image, tiles = B HT WT
 };
 
-__device__ __forceinline__ unsigned cbn_pack2(float a, float b) {    // two float32 -> packed bf16, round to nearest even
-    const cbn_f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, cbn_bf16x2));
-}
-
 __device__ __forceinline__ float cbn_max(float a, float b) { return (a > b || a != a) ? a : b; }    // NaN wins, as in max_pool2d
 
 __device__ __forceinline__ void cbn_tile_origin(const CbnParams& p, int tile, int& b, int& h0, int& w0) {
@@ -66,7 +56,7 @@ __device__ __forceinline__ void cbn_tile_origin(const CbnParams& p, int tile, in
 
 // acc[r][nt]: rows h, h + 1 of image b, column w = the lane's (lane & 31), channel (v & 3) + 8 (v >> 2) + 4 (lane >> 5) of tile nt.
 template <int COUT, bool POOL>
-__device__ __forceinline__ void cbn_epilogue(const cbn_f32x16 (&acc)[2][(COUT + 31) / 32], const float* tab, const CbnParams& p, int b, int h,
+__device__ __forceinline__ void cbn_epilogue(const f32x16 (&acc)[2][(COUT + 31) / 32], const float* tab, const CbnParams& p, int b, int h,
                                              int w, int lane) {
     constexpr int NT = (COUT + 31) / 32;
     const int khalf = lane >> 5;
@@ -96,13 +86,13 @@ __device__ __forceinline__ void cbn_epilogue(const cbn_f32x16 (&acc)[2][(COUT + 
                 const int ph = h >> 1, pw = w >> 1;
                 if (!(lane & 1) && ph < p.Ho && pw < p.Wo)
                     *reinterpret_cast<uint2*>(p.y + (((size_t)b * p.Ho + ph) * p.Wo + pw) * (COUT * 2) + c * 2) =
-                        make_uint2(cbn_pack2(m[0], m[1]), cbn_pack2(m[2], m[3]));
+                        make_uint2(pack2_bf16(m[0], m[1]), pack2_bf16(m[2], m[3]));
             } else {
 #pragma unroll
                 for (int r = 0; r < 2; ++r)
                     if (h + r < p.H && w < p.W)
                         *reinterpret_cast<uint2*>(p.y + (((size_t)b * p.H + h + r) * p.W + w) * (COUT * 2) + c * 2) =
-                            make_uint2(cbn_pack2(e[r][0], e[r][1]), cbn_pack2(e[r][2], e[r][3]));
+                            make_uint2(pack2_bf16(e[r][0], e[r][1]), pack2_bf16(e[r][2], e[r][3]));
             }
         }
 }
@@ -141,30 +131,30 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
     if (tile >= p.tiles) return;
 
     // the 16-byte chunks of a tile's halo, dealt to the threads: chunk n = pixel n / CH (row hr, column hc), channels 8 (n % CH) ...
-    auto fetch = [&](int t, cbn_u32x4 (&r)[NLD]) {
+    auto fetch = [&](int t, u32x4 (&r)[NLD]) {
         int b, h0, w0;
         cbn_tile_origin(p, t, b, h0, w0);
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int n = tid + CBN_THREADS * i, px = n / CH, c = n - px * CH, hr = px / HC, hc = px - hr * HC;
             const int h = h0 - 1 + hr, w = w0 - 1 + hc;
-            r[i] = cbn_u32x4{0u, 0u, 0u, 0u};            // outside the image: the layer's zero padding
+            r[i] = u32x4{0u, 0u, 0u, 0u};            // outside the image: the layer's zero padding
             if (n < NCHUNK && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W)
-                r[i] = *reinterpret_cast<const cbn_u32x4*>(p.x + (((size_t)b * p.H + h) * p.W + w) * (CIN * 2) + c * 16);
+                r[i] = *reinterpret_cast<const u32x4*>(p.x + (((size_t)b * p.H + h) * p.W + w) * (CIN * 2) + c * 16);
         }
     };
-    auto stash = [&](const cbn_u32x4 (&r)[NLD]) {
+    auto stash = [&](const u32x4 (&r)[NLD]) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int n = tid + CBN_THREADS * i, px = n / CH, c = n - px * CH;
-            if (n < NCHUNK) *reinterpret_cast<cbn_u32x4*>(hl + px * PS + c * 16) = r[i];
+            if (n < NCHUNK) *reinterpret_cast<u32x4*>(hl + px * PS + c * 16) = r[i];
         }
     };
 
-    cbn_u32x4 raw[NLD];
+    u32x4 raw[NLD];
     fetch(tile, raw);
     for (int i = tid; i < G::WBYTES / 16; i += CBN_THREADS)              // the resident filters: the packed image as it is
-        reinterpret_cast<cbn_u32x4*>(wl)[i] = reinterpret_cast<const cbn_u32x4*>(p.w)[i];
+        reinterpret_cast<u32x4*>(wl)[i] = reinterpret_cast<const u32x4*>(p.w)[i];
     cbn_load_tables(tab, p, COUT, tid);
 
     const unsigned char* bptr = hl + ((2 * wave) * HC + r31) * PS + khalf * 16;
@@ -174,7 +164,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
         __syncthreads();                                 // this tile's halo (first pass: filters and tables too) is in LDS
         if (tile + stride < p.tiles) fetch(tile + stride, raw);          // in flight during the MFMAs
 
-        cbn_f32x16 acc[2][NT];
+        f32x16 acc[2][NT];
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -186,11 +176,11 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
 #pragma unroll
             for (int kk = 0; kk < KS; ++kk) {
                 const int boff = ((t / 3) * HC + (t % 3)) * PS + kk * 32;
-                const cbn_bf16x8 b0 = *reinterpret_cast<const cbn_bf16x8*>(bptr + boff);
-                const cbn_bf16x8 b1 = *reinterpret_cast<const cbn_bf16x8*>(bptr + boff + HC * PS);
+                const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(bptr + boff);
+                const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(bptr + boff + HC * PS);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
-                    const cbn_bf16x8 a = *reinterpret_cast<const cbn_bf16x8*>(aptr + (t * NT + nt) * 32 * PS + kk * 32);
+                    const bf16x8 a = *reinterpret_cast<const bf16x8*>(aptr + (t * NT + nt) * 32 * PS + kk * 32);
                     acc[0][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b0, acc[0][nt], 0, 0, 0);
                     acc[1][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b1, acc[1][nt], 0, 0, 0);
                 }
@@ -242,9 +232,9 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p)
 
     unsigned short raw[CBN5_NLD];
     fetch(tile, raw);
-    cbn_bf16x8 a[5];
+    bf16x8 a[5];
 #pragma unroll
-    for (int kh = 0; kh < 5; ++kh) a[kh] = *reinterpret_cast<const cbn_bf16x8*>(p.w + ((kh * 32 + r31) * 16 + khalf * 8) * 2);
+    for (int kh = 0; kh < 5; ++kh) a[kh] = *reinterpret_cast<const bf16x8*>(p.w + ((kh * 32 + r31) * 16 + khalf * 8) * 2);
     cbn_load_tables(tab, p, 32, tid);
     if (tid < CBN5_HR * 2) *reinterpret_cast<unsigned*>(hl + (tid >> 1) * CBN5_RS + CBN5_ROW * 2 + (tid & 1) * 4) = 0u;
 
@@ -258,7 +248,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p)
         __syncthreads();
         if (tile + stride < p.tiles) fetch(tile + stride, raw);
 
-        cbn_f32x16 acc[2][1];
+        f32x16 acc[2][1];
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -269,11 +259,11 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p)
             for (int r = 0; r < 2; ++r) {
                 const unsigned* q = reinterpret_cast<const unsigned*>(bptr + (r + kh) * CBN5_RS);
                 const unsigned d[5] = {q[0], q[1], q[2], q[3], q[4]};
-                cbn_u32x4 f;
+                u32x4 f;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) f[i] = (unsigned)(((((unsigned long long)d[i + 1]) << 32) | d[i]) >> shift);
                 f[3] &= last;
-                acc[r][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kh], __builtin_bit_cast(cbn_bf16x8, f), acc[r][0], 0, 0, 0);
+                acc[r][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kh], __builtin_bit_cast(bf16x8, f), acc[r][0], 0, 0, 0);
             }
         int b, h0, w0;
         cbn_tile_origin(p, tile, b, h0, w0);

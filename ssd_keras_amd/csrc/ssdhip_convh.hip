@@ -42,6 +42,8 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
+#include "ssdhip_tile.h"
 
 namespace ssdhip {
 
@@ -59,11 +61,6 @@ __device__ unsigned long long g_profh[16];
 #define CH_PROF_TILE
 #define CH_PROF_FLUSH(base)
 #endif
-
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CH_THREADS = 512;
 constexpr int CH_BN = 256;                               // positions per tile
@@ -113,41 +110,10 @@ struct ConvHParams {
 };
 
 #if defined(__HIP_DEVICE_COMPILE__)
-typedef __bf16 ch_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ch_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32 ch_pack2(float a, float b) {           // v_cvt_pk_bf16_f32: round to nearest even
-    const ch_f32x2 v = {a, b};
-    return __builtin_bit_cast(u32, __builtin_convertvector(v, ch_bf16x2));
-}
-__device__ __forceinline__ float ch_relu(float v) { return v <= 0.f ? 0.f : v; }       // NaN stays NaN, -0 -> +0
-// Two bf16 values at once as signed 16-bit integers (v_pk_max_i16).  On ROUNDED activations this is the whole activation step:
-// max(x, 0) sends every value with the sign bit set (negative numbers, -0) to +0 and leaves the others (+NaN included) alone -- the
-// same bits as "v <= 0 ? 0 : v" before the rounding, because rounding to bf16 is monotonic and keeps the sign; max(x, 0x8000) is the
-// identity (no activation).  And on NON-NEGATIVE bf16 values integer order is numeric order, so it is also the pooling maximum.
-typedef short ch_s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u32 ch_pkmax_i16(u32 a, u32 b) {
-    return __builtin_bit_cast(u32, __builtin_elementwise_max(__builtin_bit_cast(ch_s16x2, a), __builtin_bit_cast(ch_s16x2, b)));
-}
-
-// one wave-wide 1 KiB LDS-DMA load: lane L writes 16 bytes at lds_dst + 16 L from base(rsrc) + soff + voff (zeros if the offset
-// is out of range).  M0 is saved and restored inside the statement (hipcc does not model it around asm).
-__device__ __forceinline__ void ch_bload(u32 voff, i32x4 rsrc, u32 lds_dst, u32 soff) {
-    u32 keep;
-    // wave-uniform by construction; the explicit readfirstlane keeps them in SGPRs when hipcc has folded a common factor of the
-    // expression into a vector register (an "s" constraint does not insert one by itself)
-    lds_dst = (u32)__builtin_amdgcn_readfirstlane((int)lds_dst);
-    soff = (u32)__builtin_amdgcn_readfirstlane((int)soff);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst), "s"(soff) : "memory");
-}
-__device__ __forceinline__ i32x4 ch_rsrc(const void* base, int num_records) {
-    const unsigned long long a = (unsigned long long)(uintptr_t)base;
-    i32x4 r;
-    r.x = (int)(u32)a;
-    r.y = (int)((u32)(a >> 32) & 0xffffu);
-    r.z = num_records;
-    r.w = 0x00020000;
-    return r;
+// tile_dma16_soff with lds_dst and soff forced into SGPRs: both are wave-uniform by construction here, but hipcc folds a common factor
+// of their expressions into a vector register, and an "s" constraint does not insert a readfirstlane by itself (ssdhip_tile.h)
+__device__ __forceinline__ void ch_dma16(u32 voff, i32x4 rsrc, u32 lds_dst, u32 soff) {
+    tile_dma16_soff(voff, rsrc, wave_uniform(lds_dst), wave_uniform(soff));
 }
 // MODE bits -- 64: the second wave of every SIMD (waves 4..7) reads its fragments two slots later; 8: ... issues its requests two
 // slots later; 128: persistent workgroups (one per CU) that walk over tiles and request the next tile's first slab and weights during
@@ -161,17 +127,10 @@ __device__ __forceinline__ i32x4 ch_rsrc(const void* base, int num_records) {
 // SMALL: the map may be narrower than 7 pixels (the epilogue then steps its positions with a loop instead of one select).
 // threshold_backward's keep rule on two bf16 activations at once: all ones where the value is NOT <= 0 (positive, or NaN), zero elsewhere
 __device__ __forceinline__ u32 ch_keep2(u32 m) {
-    const ch_s16x2 h = __builtin_bit_cast(ch_s16x2, m);
-    const ch_s16x2 a = h & (short)0x7fff;
-    const ch_s16x2 k = (h > (short)0) | (a > (short)0x7f80);
+    const s16x2 h = __builtin_bit_cast(s16x2, m);
+    const s16x2 a = h & (short)0x7fff;
+    const s16x2 k = (h > (short)0) | (a > (short)0x7f80);
     return __builtin_bit_cast(u32, k);
-}
-typedef _Float16 ch_f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ u32 ch_split2(float a, float b, u32& lo_out) {        // two float32 -> packed float16 hi parts, lo parts
-    const _Float16 ha = (_Float16)a, hb = (_Float16)b;
-    const _Float16 la = (_Float16)(a - (float)ha), lb = (_Float16)(b - (float)hb);
-    lo_out = (u32)__builtin_bit_cast(unsigned short, la) | ((u32)__builtin_bit_cast(unsigned short, lb) << 16);
-    return (u32)__builtin_bit_cast(unsigned short, ha) | ((u32)__builtin_bit_cast(unsigned short, hb) << 16);
 }
 
 // NWV = waves per workgroup.  8 (2 x 4, each 64 channels x 64 positions, two waves per SIMD) is the round-2 layout.  4 (round 4: 2 x 2,
@@ -232,22 +191,21 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
     const int csteps = Cin >> 6;
     const int XC = X3 ? p.xC : Cin;                       // channels of an x row
     const u32 lds0 = (u32)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    const i32x4 rx = ch_rsrc(p.x, p.x_bytes);
-    const i32x4 rw = ch_rsrc(p.w, p.w_bytes);
+    const i32x4 rx = tile_rsrc(p.x, p.x_bytes);
+    const i32x4 rw = tile_rsrc(p.w, p.w_bytes);
     // Outputs leave through a buffer descriptor: a lane that has nothing to store gets an out-of-range offset (dropped by the
     // buffer unit), so every wave issues EXACTLY NST store instructions per tile -- the K loop's first waits after an epilogue
     // count on that (see `post` in step()).
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    typedef unsigned int ch_u32x4 __attribute__((ext_vector_type(4)));
     auto store16 = [&](const uint4 v, const bool ok, const u32 elem) {     // elem: index of the first of the 8 channels (y is below 2 GB)
         if constexpr (!(MODE & 256)) {
-            const ch_u32x4 d = {v.x, v.y, v.z, v.w};
+            const u32x4 d = {v.x, v.y, v.z, v.w};
             __builtin_amdgcn_raw_buffer_store_b128(d, ry, ok ? elem * 2u : OOB, 0, 0);
         }
     };
     auto store16_at = [&](const uint4 v, const u32 byte_off) {            // byte_off: OOB for a lane that has nothing to store
         if constexpr (!(MODE & 256)) {
-            const ch_u32x4 d = {v.x, v.y, v.z, v.w};
+            const u32x4 d = {v.x, v.y, v.z, v.w};
             __builtin_amdgcn_raw_buffer_store_b128(d, ry, byte_off, 0, 0);
         }
     };
@@ -332,7 +290,7 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
     // the weights of tap `tap` of slice `cs` of channel tile `co` into ring stage `stage` (all wave-uniform): this wave's piece i
     auto issue_w_piece = [&](const int co, const int cs, const int tap, const int stage, const int i) {
         const u32 soff = (u32)(((co * 9 + tap) * Cin + cs * 64) * 2);
-        ch_bload(woff[i], rw, lds0 + stage * CH_WST + (i * NWV + wave) * 1024, soff);
+        ch_dma16(woff[i], rw, lds0 + stage * CH_WST + (i * NWV + wave) * 1024, soff);
     };
 
     // ---- fragment addressing -----------------------------------------------------------------------------------------------
@@ -379,7 +337,7 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
     auto mfma_one = [&](auto setc, auto ic) {             // MFMA i of a step: k16 block i / (2 NPI), accumulator (ci, pi) = ((i / NPI) & 1, i % NPI)
         constexpr int S = decltype(setc)::value, i = decltype(ic)::value, kk = i / (2 * NPI), ci = (i / NPI) & 1, pi = i % NPI;
         if constexpr (X3)
-            acc[ci][pi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ch_f16x8, fa[S][kk][ci]), __builtin_bit_cast(ch_f16x8, fb[S][kk][pi]),
+            acc[ci][pi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[S][kk][ci]), __builtin_bit_cast(f16x8, fb[S][kk][pi]),
                                                                  acc[ci][pi], 0, 0, 0);
         else
             acc[ci][pi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[S][kk][ci], fb[S][kk][pi], acc[ci][pi], 0, 0, 0);
@@ -388,7 +346,7 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
 
     // ---- prologue of the workgroup's first tile: slab of slice 0, weights of steps 0 .. D-1 ------------------------------------
 #pragma unroll
-    for (int k = 0; k < NXO; ++k) ch_bload(xoff[k], rx, lds0 + SLAB0 + xdst(k), 0u);
+    for (int k = 0; k < NXO; ++k) ch_dma16(xoff[k], rx, lds0 + SLAB0 + xdst(k), 0u);
 #pragma unroll
     for (int d = 0; d < D; ++d)
 #pragma unroll
@@ -442,7 +400,7 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
         };
         auto req_x = [&](const int u) {                    // piece TAP WPK + u of the next slice's slab (TAP < SPW)
             if (!nomore)
-                ch_bload(xoff[TAP * WPK + u], rx, lds0 + SLAB0 + ((cs + 1) & 1) * SLB + xdst(TAP * WPK + u),
+                ch_dma16(xoff[TAP * WPK + u], rx, lds0 + SLAB0 + ((cs + 1) & 1) * SLB + xdst(TAP * WPK + u),
                          nxt ? 0u : (u32)(((X3 && cs + 1 >= p.nx) ? cs + 1 - p.nx : cs + 1) * 128));
         };
         auto slot = [&](auto ic) {
@@ -598,14 +556,14 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
             }
         if constexpr (!X3) {
         // ---- bf16 epilogue (round 4: the instruction diet of DESIGN 8 item 2).  Per 4 values: 2 v_pk_add_f32 (bias), 2
-        //      v_cvt_pk_bf16_f32, 2 v_pk_max_i16 (the activation on the rounded pair, see ch_pkmax_i16) -- instead of four compare +
+        //      v_cvt_pk_bf16_f32, 2 v_pk_max_i16 (the activation on the rounded pair, see pkmax_i16) -- instead of four compare +
         //      select pairs with their VCC hazard states; the store offsets of the 1-D form are computed once per tile, branch-free.
         const u32 floor16 = p.relu ? 0u : 0x80008000u;
         auto pack4 = [&](const int ci, const int pi, const int g, u32& p0, u32& p1) {
             const float s0 = acc[ci][pi][4 * g + 0] + bv[ci][4 * g + 0], s1 = acc[ci][pi][4 * g + 1] + bv[ci][4 * g + 1];
             const float s2 = acc[ci][pi][4 * g + 2] + bv[ci][4 * g + 2], s3 = acc[ci][pi][4 * g + 3] + bv[ci][4 * g + 3];
-            p0 = ch_pkmax_i16(ch_pack2(s0, s1), floor16);
-            p1 = ch_pkmax_i16(ch_pack2(s2, s3), floor16);
+            p0 = pkmax_i16(pack2_bf16(s0, s1), floor16);
+            p1 = pkmax_i16(pack2_bf16(s2, s3), floor16);
         };
         // DIRECT: a lane holds channels ci 32 + 8 g + 4 khalf + (0 .. 3) of its position as (lo[g], hi[g]); v_permlane32_swap between the
         // two lanes of a position (lane, lane + 32) leaves the khalf = 0 lane with the 16 bytes of g = 0 / 2 and the khalf = 1 lane with
@@ -641,9 +599,9 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
                         u32 a0, a1, b0, b1;
                         pack4(ci, 0, g, a0, a1);
                         pack4(ci, 1, g, b0, b1);
-                        u32 v0 = ch_pkmax_i16(a0, b0 & mrow1) & mcol, v1 = ch_pkmax_i16(a1, b1 & mrow1) & mcol;
-                        lo[g] = ch_pkmax_i16(v0, (u32)__builtin_amdgcn_update_dpp(0, (int)v0, 0xB1, 0xf, 0xf, false));
-                        hi[g] = ch_pkmax_i16(v1, (u32)__builtin_amdgcn_update_dpp(0, (int)v1, 0xB1, 0xf, 0xf, false));
+                        u32 v0 = pkmax_i16(a0, b0 & mrow1) & mcol, v1 = pkmax_i16(a1, b1 & mrow1) & mcol;
+                        lo[g] = pkmax_i16(v0, (u32)__builtin_amdgcn_update_dpp(0, (int)v0, 0xB1, 0xf, 0xf, false));
+                        hi[g] = pkmax_i16(v1, (u32)__builtin_amdgcn_update_dpp(0, (int)v1, 0xB1, 0xf, 0xf, false));
                     } else {
                         float o[4];
 #pragma unroll
@@ -655,8 +613,8 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
                             if (has_right) v = right > v ? right : v;
                             o[e] = v + bv[ci][4 * g + e];
                         }
-                        lo[g] = ch_pack2(o[0], o[1]);
-                        hi[g] = ch_pack2(o[2], o[3]);
+                        lo[g] = pack2_bf16(o[0], o[1]);
+                        hi[g] = pack2_bf16(o[2], o[3]);
                     }
                 }
                 store_runs(lo, hi, off + ci * 64);
@@ -686,9 +644,9 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
                         u32 a0, a1, b0, b1;
                         pack4(ci, 2 * ph, g, a0, a1);
                         pack4(ci, 2 * ph + 1, g, b0, b1);
-                        u32 v0 = ch_pkmax_i16(a0, b0 & mrow1) & mcol, v1 = ch_pkmax_i16(a1, b1 & mrow1) & mcol;
-                        v0 = ch_pkmax_i16(v0, (u32)__builtin_amdgcn_update_dpp(0, (int)v0, 0xB1, 0xf, 0xf, false));
-                        v1 = ch_pkmax_i16(v1, (u32)__builtin_amdgcn_update_dpp(0, (int)v1, 0xB1, 0xf, 0xf, false));
+                        u32 v0 = pkmax_i16(a0, b0 & mrow1) & mcol, v1 = pkmax_i16(a1, b1 & mrow1) & mcol;
+                        v0 = pkmax_i16(v0, (u32)__builtin_amdgcn_update_dpp(0, (int)v0, 0xB1, 0xf, 0xf, false));
+                        v1 = pkmax_i16(v1, (u32)__builtin_amdgcn_update_dpp(0, (int)v1, 0xB1, 0xf, 0xf, false));
                         if (!(r31 & 1)) {
                             const int px = r31 >> 1, chunk = ci * 4 + g;
                             *reinterpret_cast<uint2*>(pstage + px * 128 + ((chunk ^ (px & 7)) << 4) + khalf * 8) = make_uint2(v0, v1);
@@ -713,7 +671,7 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
                         if (!(r31 & 1)) {
                             const int px = r31 >> 1, chunk = ci * 4 + g;
                             *reinterpret_cast<uint2*>(pstage + px * 128 + ((chunk ^ (px & 7)) << 4) + khalf * 8) =
-                                make_uint2(ch_pack2(o[0], o[1]), ch_pack2(o[2], o[3]));
+                                make_uint2(pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3]));
                         }
                     }
             }
@@ -763,7 +721,7 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
                     for (int j = 0; j < 4; ++j) {
                         const int px = j * 8 + (lane >> 3);
                         const uint4 v = *reinterpret_cast<const uint4*>(stage + px * 128 + ((c ^ (px & 7)) << 4));
-                        const ch_u32x4 d = {v.x, v.y, v.z, v.w};
+                        const u32x4 d = {v.x, v.y, v.z, v.w};
                         __builtin_amdgcn_raw_buffer_store_b128(d, ryf, so[j], 0, 0);
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -872,7 +830,7 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
             }
             // MSK: the activation at the lane's eight store addresses, requested before the packing and the LDS round trip below
             // (an address that stores nothing reads zeros); the loads are the compiler's, it waits for them where they are used
-            [[maybe_unused]] ch_u32x4 mk[NPI][4];
+            [[maybe_unused]] u32x4 mk[NPI][4];
             [[maybe_unused]] float bs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // MSK: sums of the lane's eight channels over its eight positions
             [[maybe_unused]] float4 bold0 = make_float4(0.f, 0.f, 0.f, 0.f), bold1 = bold0;  // what the wave's earlier tiles left in its row
             [[maybe_unused]] float* brow = nullptr;
@@ -967,12 +925,12 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
                         u32 p0, p1;
                         if constexpr (X3) {
                             u32 l0, l1;
-                            const u32 h0_ = ch_split2(o[0], o[1], l0), h1_ = ch_split2(o[2], o[3], l1);
+                            const u32 h0_ = split2_f16(o[0], o[1], l0), h1_ = split2_f16(o[2], o[3], l1);
                             p0 = part ? l0 : h0_;
                             p1 = part ? l1 : h1_;
                         } else {
-                            p0 = ch_pack2(o[0], o[1]);
-                            p1 = ch_pack2(o[2], o[3]);
+                            p0 = pack2_bf16(o[0], o[1]);
+                            p1 = pack2_bf16(o[2], o[3]);
                         }
                         *reinterpret_cast<uint2*>(stage + px * 128 + ((chunk ^ (px & 7)) << 4) + khalf * 8) = make_uint2(p0, p1);
                     }
@@ -1022,12 +980,12 @@ __device__ __forceinline__ void convh_body(const ConvHParams& p, unsigned char* 
                         u32 p0, p1;
                         if constexpr (X3) {
                             u32 l0, l1;
-                            const u32 h0_ = ch_split2(o[0], o[1], l0), h1_ = ch_split2(o[2], o[3], l1);
+                            const u32 h0_ = split2_f16(o[0], o[1], l0), h1_ = split2_f16(o[2], o[3], l1);
                             p0 = part ? l0 : h0_;
                             p1 = part ? l1 : h1_;
                         } else {
-                            p0 = ch_pack2(o[0], o[1]);
-                            p1 = ch_pack2(o[2], o[3]);
+                            p0 = pack2_bf16(o[0], o[1]);
+                            p1 = pack2_bf16(o[2], o[3]);
                         }
                         *reinterpret_cast<uint2*>(stage + r31 * 128 + ((chunk ^ (r31 & 7)) << 4) + khalf * 8) = make_uint2(p0, p1);
                     }

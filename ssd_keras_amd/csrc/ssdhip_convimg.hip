@@ -22,13 +22,10 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
+#include "ssdhip_tile.h"
 
 namespace ssdhip {
-
-typedef unsigned short bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CI_THREADS = 512;
 constexpr int CI_PX = 384;                               // pixels of a tile (12 blocks of 32)
@@ -79,49 +76,12 @@ struct ConvImgParams {
     float oscale;
 };
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __bf16 ci_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ci_f32x2 __attribute__((ext_vector_type(2)));
-typedef short ci_s16x2 __attribute__((ext_vector_type(2)));
-typedef u32 ci_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32 ci_pack2(float a, float b) {
-    const ci_f32x2 v = {a, b};
-    return __builtin_bit_cast(u32, __builtin_convertvector(v, ci_bf16x2));
-}
-__device__ __forceinline__ u32 ci_pkmax_i16(u32 a, u32 b) {
-    return __builtin_bit_cast(u32, __builtin_elementwise_max(__builtin_bit_cast(ci_s16x2, a), __builtin_bit_cast(ci_s16x2, b)));
-}
-// one wave-wide 1 KiB LDS-DMA load: lane L writes 16 bytes at lds_dst + 16 L from base(rsrc) + voff (zeros if out of range)
-__device__ __forceinline__ void ci_bload(u32 voff, i32x4 rsrc, u32 lds_dst) {
-    u32 keep;
-    lds_dst = (u32)__builtin_amdgcn_readfirstlane((int)lds_dst);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ i32x4 ci_rsrc(const void* base, u32 num_records) {
-    const unsigned long long a = (unsigned long long)(uintptr_t)base;
-    i32x4 r;
-    r.x = (int)(u32)a;
-    r.y = (int)((u32)(a >> 32) & 0xffffu);
-    r.z = (int)num_records;
-    r.w = 0x00020000;
-    return r;
-}
-#endif
-
 // BM: output channels of a tile.  128: a wave owns 64 channels (two 32-channel MFMA blocks) x 96 pixels.  64: a wave owns ONE block x 96
 // pixels -- twice the tiles (conv5_x: 32 images x 8 = 256 instead of 128 for 256 CUs) for 1.33 KB of LDS reads per MFMA instead of 0.83.
 // KS: filter size, 3 (nine taps per 64-channel slice, any dilation / stride / padding: a tap is an address) or 1 (round 6: fc7, conv6_1 --
 // ONE step per slice; the implicit-GEMM form moved 2.5 x the bytes per FLOP of a 3x3 layer from L2 into LDS and ran fc7 at a quarter of the
 // peak).  NPB: 32-pixel MFMA blocks of a wave, 3 (output maps up to 384 pixels) or 1 (up to 128: the strided conv6_2, 19 x 19 -> 10 x 10,
 // would idle in three quarters of a 384-pixel tile).
-typedef _Float16 ci_f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ u32 ci_split2(float a, float b, u32& lo_out) {          // hi = fl16(v), lo = fl16(v - hi), two values per word
-    const _Float16 ha = (_Float16)a, hb = (_Float16)b;
-    const _Float16 la = (_Float16)(a - (float)ha), lb = (_Float16)(b - (float)hb);
-    lo_out = (u32)__builtin_bit_cast(unsigned short, la) | ((u32)__builtin_bit_cast(unsigned short, lb) << 16);
-    return (u32)__builtin_bit_cast(unsigned short, ha) | ((u32)__builtin_bit_cast(unsigned short, hb) << 16);
-}
 
 template <int BM, int KS, int NPB, bool X3 = false>
 __global__ __launch_bounds__(CI_THREADS, 1) void conv_image_kernel(ConvImgParams p) {
@@ -169,8 +129,8 @@ __global__ __launch_bounds__(CI_THREADS, 1) void conv_image_kernel(ConvImgParams
         else reinterpret_cast<float*>(lds + CI_BIAS)[tid - 128] = p.bias ? __uint_as_float((u32)p.bias[co0 + tid - 128] << 16) : 0.f;
     }
     const int XC = X3 ? p.xC : p.Cin;                    // channels of an x row
-    const i32x4 rx = ci_rsrc(p.x + ((size_t)b * HW + px0) * XC, (u32)((size_t)npx * XC * 2));
-    const i32x4 rw = ci_rsrc(p.w + (size_t)co0 * NT * p.Cin, (u32)((size_t)BM * NT * p.Cin * 2));
+    const i32x4 rx = tile_rsrc(p.x + ((size_t)b * HW + px0) * XC, (u32)((size_t)npx * XC * 2));
+    const i32x4 rw = tile_rsrc(p.w + (size_t)co0 * NT * p.Cin, (u32)((size_t)BM * NT * p.Cin * 2));
 
     // ---- request plan.  Every wave issues exactly NFP + 1 LDS-DMA pieces per step, in this order: [NFP filter pieces of step i + 2 | one slab
     //      piece of the next slice]; a request that has nothing to fetch goes out of range into the dump area.  So `s_waitcnt vmcnt(NFP + 2)`
@@ -194,14 +154,17 @@ __global__ __launch_bounds__(CI_THREADS, 1) void conv_image_kernel(ConvImgParams
         const bool ok = (slice < n_slices) & (px < npx) & (c < 8);
         const bool any = (slice < n_slices) & (piece * 64 < 9 * npx);         // wave-uniform: the piece holds at least one slot of the map
         const int xs = (X3 && slice >= p.xslices) ? slice - p.xslices : slice;      // X3: the x slice this K slice multiplies (hi, hi, lo)
-        ci_bload(ok ? (u32)((px * XC + xs * 64) * 2 + c * 16) : OOB, rx, any ? lds0 + buf * CI_SLAB + piece * 1024 : lds0 + CI_DUMP);
+        // (wave_uniform: the destination is uniform by construction, but an "s" operand does not get a readfirstlane by itself; ssdhip_tile.h)
+        tile_dma16(ok ? (u32)((px * XC + xs * 64) * 2 + c * 16) : OOB, rx,
+                   wave_uniform(any ? lds0 + buf * CI_SLAB + piece * 1024 : lds0 + CI_DUMP));
     };
     // filters of step `wstep` = (slice, tap) into ring stage `stage`
     auto issue_filter_piece = [&](const int i, const int wstep, const int stage) {
         const bool wok = wstep < n_steps;
         const int ws = wstep / NT, wt = wstep - NT * ws;
         const u32 wo = (u32)((wt * p.Cin + ws * 64) * 2);
-        ci_bload(wok ? wrel[i] + wo : OOB, rw, wok ? lds0 + CI_W0 + stage * CI_WST + (NFP * wave + i) * 1024 : lds0 + CI_DUMP);
+        tile_dma16(wok ? wrel[i] + wo : OOB, rw,
+                   wave_uniform(wok ? lds0 + CI_W0 + stage * CI_WST + (NFP * wave + i) * 1024 : lds0 + CI_DUMP));
     };
     auto issue_filters = [&](const int wstep, const int stage) {
 #pragma unroll
@@ -286,7 +249,7 @@ __global__ __launch_bounds__(CI_THREADS, 1) void conv_image_kernel(ConvImgParams
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int pi = 0; pi < NPB; ++pi) {
-                    if constexpr (X3) acc[0][pi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ci_f16x8, fa[kk & 1][0]), __builtin_bit_cast(ci_f16x8, fb[kk & 1][pi]), acc[0][pi], 0, 0, 0);
+                    if constexpr (X3) acc[0][pi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[kk & 1][0]), __builtin_bit_cast(f16x8, fb[kk & 1][pi]), acc[0][pi], 0, 0, 0);
                     else acc[0][pi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk & 1][0], fb[kk & 1][pi], acc[0][pi], 0, 0, 0);
                 }
                 // the step's requests go out a few at a time BETWEEN MFMA blocks: an LDS-DMA instruction holds its wave
@@ -313,7 +276,7 @@ __global__ __launch_bounds__(CI_THREADS, 1) void conv_image_kernel(ConvImgParams
                 if constexpr (NCB == 2) {
 #pragma unroll
                     for (int pi = 0; pi < NPB; ++pi) {
-                        if constexpr (X3) acc[1][pi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ci_f16x8, fa[kk & 1][1]), __builtin_bit_cast(ci_f16x8, fb[kk & 1][pi]), acc[1][pi], 0, 0, 0);
+                        if constexpr (X3) acc[1][pi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[kk & 1][1]), __builtin_bit_cast(f16x8, fb[kk & 1][pi]), acc[1][pi], 0, 0, 0);
                         else acc[1][pi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[kk & 1][1], fb[kk & 1][pi], acc[1][pi], 0, 0, 0);
                     }
                 }
@@ -357,7 +320,7 @@ __global__ __launch_bounds__(CI_THREADS, 1) void conv_image_kernel(ConvImgParams
                         *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + pix * p.Cout + co0 + chl) = make_float4(v[0], v[1], v[2], v[3]);
                     } else {
                         u32 l0, l1;
-                        const u32 h0 = ci_split2(v[0], v[1], l0), h1 = ci_split2(v[2], v[3], l1);
+                        const u32 h0 = split2_f16(v[0], v[1], l0), h1 = split2_f16(v[2], v[3], l1);
                         bf16_t* row = p.y + pix * (2 * p.Cout) + co0 + chl;
                         *reinterpret_cast<uint2*>(row) = make_uint2(h0, h1);
                         *reinterpret_cast<uint2*>(row + p.Cout) = make_uint2(l0, l1);
@@ -386,14 +349,14 @@ __global__ __launch_bounds__(CI_THREADS, 1) void conv_image_kernel(ConvImgParams
             u32 lo[4], hi[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                lo[g] = ci_pkmax_i16(ci_pack2(acc[ci][pi][4 * g] + bv[4 * g], acc[ci][pi][4 * g + 1] + bv[4 * g + 1]), floor16);
-                hi[g] = ci_pkmax_i16(ci_pack2(acc[ci][pi][4 * g + 2] + bv[4 * g + 2], acc[ci][pi][4 * g + 3] + bv[4 * g + 3]), floor16);
+                lo[g] = pkmax_i16(pack2_bf16(acc[ci][pi][4 * g] + bv[4 * g], acc[ci][pi][4 * g + 1] + bv[4 * g + 1]), floor16);
+                hi[g] = pkmax_i16(pack2_bf16(acc[ci][pi][4 * g + 2] + bv[4 * g + 2], acc[ci][pi][4 * g + 3] + bv[4 * g + 3]), floor16);
             }
 #pragma unroll
             for (int pr = 0; pr < 2; ++pr) {
                 const auto sl = __builtin_amdgcn_permlane32_swap(lo[2 * pr], lo[2 * pr + 1], false, false);
                 const auto sh = __builtin_amdgcn_permlane32_swap(hi[2 * pr], hi[2 * pr + 1], false, false);
-                __builtin_amdgcn_raw_buffer_store_b128(ci_u32x4{sl[0], sh[0], sl[1], sh[1]}, ry, voff + pr * 32, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{sl[0], sh[0], sl[1], sh[1]}, ry, voff + pr * 32, 0, 0);
             }
         }
     }

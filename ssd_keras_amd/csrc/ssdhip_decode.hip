@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void scan_kernel(const float* __restrict__ y, 
     if (!((uintptr_t)y & 15) && !(((size_t)p.N * p.L) & 3) && !((TA * p.L) & 3) && total_bytes < 0x7fffff00ull && !(TA & 63) && !p.no_dma) {
         const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
         const u32 lds0 = (u32)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem_raw;
-        const tile_i32x4 rs = tile_rsrc(y, (u32)total_bytes);
+        const i32x4 rs = tile_rsrc(y, (u32)total_bytes);
         const u32 off = (u32)(((size_t)b * p.N + a0) * (size_t)p.L * sizeof(float));
         const int nch = (na * p.L + 3) >> 2;                       // the last chunk may run into the next rows (or read zeros past the end)
         for (int q0 = wave * 64; q0 < nch; q0 += TA) {
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256) void scan_heads_kernel(HeadParams hp, const fl
     int l, a0, na;
     head_tile_of(hp, (int)blockIdx.x, l, a0, na);
     float* rows = reinterpret_cast<float*>(smem_raw);
-    hbf16_t* cl = reinterpret_cast<hbf16_t*>(smem_raw + (size_t)hp.TA * p.L * sizeof(float));
+    bf16_t* cl = reinterpret_cast<bf16_t*>(smem_raw + (size_t)hp.TA * p.L * sizeof(float));
     int* wave_cnt = reinterpret_cast<int*>(smem_raw + (head_tile_lds(hp.TA, p.C) + 15) / 16 * 16);
     head_build_rows(hp, anchors_var, l, b, a0, na, rows, cl, threadIdx.x, blockDim.x);
     scan_tile_body(rows, wave_cnt, p, b, hp.anchor_off[l] + a0, na, boxes, cand, cand_count, cls_out);
@@ -698,7 +698,6 @@ __device__ __forceinline__ void block_bitonic_desc_regs(u64 (&v)[PER], u64* xch)
 // offset register (the step rides in the scalar soffset; past-the-end slots come back as 0 from the buffer unit's range check
 // and are mapped to the "consumed" key ~0).  The record count goes through an opaque scalar so that the loads are not hoisted
 // out of the round loop (the list is loop invariant; hoisting would keep 2 * KC registers alive through the NMS phases).
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 template <int T, int KP>
 __device__ __forceinline__ void load_keys_cached(const u64* keys, int n, int tid, int first, u64 (&kc)[KP]) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -707,7 +706,7 @@ __device__ __forceinline__ void load_keys_cached(const u64* keys, int n, int tid
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u64*>(keys), 0, nn * 8, 0x00020000);
 #pragma unroll
     for (int u = 0; u < KP; ++u) {
-        const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, tid * 8, (first + u) * T * 8, 0);
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, tid * 8, (first + u) * T * 8, 0);
         const u64 key = ((u64)v.y << 32) | v.x;
         kc[u] = key ? key : ~0ull;
     }

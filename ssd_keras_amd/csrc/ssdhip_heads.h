@@ -8,25 +8,17 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
 #include "ssdhip_tile.h"
 
 namespace ssdhip {
 
-typedef unsigned short hbf16_t;
-
-__device__ __forceinline__ float h_bf2f(u32 h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ u32 h_f2bf(float f) {          // round to nearest even, NaN stays NaN (as c10::BFloat16)
-    const u32 u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 constexpr int MAX_PRED_LAYERS = 8;
 struct HeadParams {
-    const hbf16_t* conf[MAX_PRED_LAYERS];
-    const hbf16_t* loc[MAX_PRED_LAYERS];
-    const hbf16_t* conf_bias[MAX_PRED_LAYERS];    // [n_boxes*C] or null
-    const hbf16_t* loc_bias[MAX_PRED_LAYERS];     // [n_boxes*4] or null
+    const bf16_t* conf[MAX_PRED_LAYERS];
+    const bf16_t* loc[MAX_PRED_LAYERS];
+    const bf16_t* conf_bias[MAX_PRED_LAYERS];    // [n_boxes*C] or null
+    const bf16_t* loc_bias[MAX_PRED_LAYERS];     // [n_boxes*4] or null
     int n_anchors[MAX_PRED_LAYERS];
     int n_boxes[MAX_PRED_LAYERS];
     int conf_stride[MAX_PRED_LAYERS];             // elements between consecutive pixels of the conf / loc source
@@ -42,7 +34,7 @@ struct HeadParams {
 // LDS bytes of one tile: [TA][C+12] float rows + the logits' staging area -- [TA][C] + [TA][4] bf16, or (packed heads, round 5) the
 // tile's whole pixel rows as LDS-DMA leaves them: up to TA / n_boxes + 2 rows of 16-byte chunks, the last load's idle lanes, the biases
 __host__ __device__ inline size_t head_stage_bytes(int TA, int C) {
-    return (size_t)TA * (C + 4) * sizeof(hbf16_t) + (size_t)16 * TA + (size_t)64 * (C + 4) + 1024;
+    return (size_t)TA * (C + 4) * sizeof(bf16_t) + (size_t)16 * TA + (size_t)64 * (C + 4) + 1024;
 }
 __host__ __device__ inline size_t head_tile_lds(int TA, int C) { return (size_t)TA * (C + 12) * sizeof(float) + head_stage_bytes(TA, C); }
 
@@ -57,9 +49,9 @@ __device__ __forceinline__ void head_tile_of(const HeadParams& hp, int tile_id, 
 // Builds rows[a][0..C+11] = [softmax(conf + bias) | loc + bias | anchor | variances] for anchors a0..a0+na-1 of layer l, image b.
 // `rows`: [TA][C+12] float in LDS, `cl`: [TA][C] + [TA][4] bf16 staging in LDS.  Ends with a __syncthreads().
 __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const float* __restrict__ anchors_var, int l, int b, int a0, int na,
-                                                float* rows, hbf16_t* cl, int tid, int nthreads) {
+                                                float* rows, bf16_t* cl, int tid, int nthreads) {
     const int TA = hp.TA, C = hp.C, L = C + 12;
-    hbf16_t* ll = cl + (size_t)TA * C;
+    bf16_t* ll = cl + (size_t)TA * C;
     const int nb = hp.n_boxes[l];
     if (hp.src_f32) {
         // float32 head outputs (bias already added by the convolution): the values go straight into the float32 rows -- the same index
@@ -133,14 +125,14 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
         if (dma) {
             unsigned char* st = reinterpret_cast<unsigned char*>(cl);
             const u32 lds0 = (u32)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)st;
-            const tile_i32x4 rs = tile_rsrc(hp.conf[l], (u32)src_bytes);
+            const i32x4 rs = tile_rsrc(hp.conf[l], (u32)src_bytes);
             const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
             const u32 row0 = (u32)(((size_t)b * npix_l + pix0) * (size_t)stride * 2);
             for (int q0 = wave * 64; q0 < nchunks; q0 += nthreads) {
                 const int q = q0 + lane, r = q / cpr, j = q - r * cpr;
                 tile_dma16(q < nchunks ? row0 + (u32)r * (u32)(stride * 2) + (u32)j * 16u : TILE_OOB, rs, lds0 + (u32)q0 * 16u);
             }
-            hbf16_t* bs = reinterpret_cast<hbf16_t*>(st + dma_area);                     // [nb C] conf bias | [nb 4] loc bias
+            bf16_t* bs = reinterpret_cast<bf16_t*>(st + dma_area);                     // [nb C] conf bias | [nb 4] loc bias
             const bool has_cb = hp.conf_bias[l] != nullptr, has_lb = hp.loc_bias[l] != nullptr;
             if (has_cb) for (int i = tid; i < nb * C; i += nthreads) bs[i] = hp.conf_bias[l][i];
             if (has_lb) for (int i = tid; i < nb * 4; i += nthreads) bs[nb * C + i] = hp.loc_bias[l][i];
@@ -154,9 +146,9 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
             __syncthreads();
             for (int a = tid; a < na; a += nthreads) {
                 const int ga = a0 + a, pix = ga / nb, box = ga - pix * nb;
-                const hbf16_t* prow = reinterpret_cast<const hbf16_t*>(st + (size_t)(pix - pix0) * pitch);
-                const hbf16_t* src = prow + box * C;
-                const hbf16_t* cb = bs + box * C;
+                const bf16_t* prow = reinterpret_cast<const bf16_t*>(st + (size_t)(pix - pix0) * pitch);
+                const bf16_t* src = prow + box * C;
+                const bf16_t* cb = bs + box * C;
                 float* r = rows + (size_t)a * L;
                 float mx = -INFINITY;
                 int c = 0;
@@ -164,16 +156,16 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
                     float v[4];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
-                        const float x = h_bf2f(src[c + u]);
+                        const float x = bf16_float(src[c + u]);
                         // the PyTorch path rounds conv + bias to bf16 before the float32 softmax: keep that rounding
-                        v[u] = has_cb ? h_bf2f(h_f2bf(x + h_bf2f(cb[c + u]))) : x;
+                        v[u] = has_cb ? bf16_float(bf16_bits(x + bf16_float(cb[c + u]))) : x;
                     }
 #pragma unroll
                     for (int u = 0; u < 4; ++u) { r[c + u] = v[u]; mx = fmaxf(mx, v[u]); }
                 }
                 for (; c < C; ++c) {
-                    const float x = h_bf2f(src[c]);
-                    const float v = has_cb ? h_bf2f(h_f2bf(x + h_bf2f(cb[c]))) : x;
+                    const float x = bf16_float(src[c]);
+                    const float v = has_cb ? bf16_float(bf16_bits(x + bf16_float(cb[c]))) : x;
                     r[c] = v;
                     mx = fmaxf(mx, v);
                 }
@@ -196,10 +188,10 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
                     for (int u = 0; u < 4; ++u) r[c + u] = e[u] / sum;
                 }
                 for (; c < C; ++c) r[c] = r[c] / sum;
-                const hbf16_t* lsrc = prow + nb * C + box * 4;
-                const hbf16_t* lb = bs + nb * C + box * 4;
+                const bf16_t* lsrc = prow + nb * C + box * 4;
+                const bf16_t* lb = bs + nb * C + box * 4;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) r[C + k] = has_lb ? h_bf2f(h_f2bf(h_bf2f(lsrc[k]) + h_bf2f(lb[k]))) : h_bf2f(lsrc[k]);
+                for (int k = 0; k < 4; ++k) r[C + k] = has_lb ? bf16_float(bf16_bits(bf16_float(lsrc[k]) + bf16_float(lb[k]))) : bf16_float(lsrc[k]);
                 if (av16 && a == tid) {
                     r[C + 4] = av0.x; r[C + 5] = av0.y; r[C + 6] = av0.z; r[C + 7] = av0.w;
                     r[C + 8] = av1.x; r[C + 9] = av1.y; r[C + 10] = av1.z; r[C + 11] = av1.w;
@@ -213,8 +205,8 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
         }
     }
     if (hp.conf_stride[l] == nb * C && hp.loc_stride[l] == nb * 4) {                    // dense heads: contiguous spans
-        const hbf16_t* csrc = hp.conf[l] + ((size_t)b * hp.n_anchors[l] + a0) * C;
-        const hbf16_t* lsrc = hp.loc[l] + ((size_t)b * hp.n_anchors[l] + a0) * 4;
+        const bf16_t* csrc = hp.conf[l] + ((size_t)b * hp.n_anchors[l] + a0) * C;
+        const bf16_t* lsrc = hp.loc[l] + ((size_t)b * hp.n_anchors[l] + a0) * 4;
         for (int i = tid; i < na * C; i += nthreads) cl[i] = csrc[i];
         for (int i = tid; i < na * 4; i += nthreads) ll[i] = lsrc[i];
     } else {                                                                            // heads packed into one wider conv output
@@ -227,7 +219,7 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
             int c = tid % C;
             const int ga0 = a0 + tid / C;
             int pix = ga0 / nb, box = ga0 - pix * nb;
-            const hbf16_t* src = hp.conf[l] + px0 * hp.conf_stride[l];
+            const bf16_t* src = hp.conf[l] + px0 * hp.conf_stride[l];
             const int cs = hp.conf_stride[l];
             const int q0 = step_a / nb, r0 = step_a - q0 * nb, q1 = (step_a + 1) / nb, r1 = step_a + 1 - q1 * nb;   // anchors -> (pixels, boxes)
             for (int i = tid; i < na * C; i += nthreads) {
@@ -245,7 +237,7 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
             const int k = tid & 3;
             const int ga0 = a0 + (tid >> 2);
             int pix = ga0 / nb, box = ga0 - pix * nb;
-            const hbf16_t* src = hp.loc[l] + px0 * hp.loc_stride[l];
+            const bf16_t* src = hp.loc[l] + px0 * hp.loc_stride[l];
             const int ls = hp.loc_stride[l];
             const int q0 = step_a / nb, r0 = step_a - q0 * nb;
             for (int i = tid; i < na * 4; i += nthreads) {
@@ -260,19 +252,19 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
     for (int a = tid; a < na; a += nthreads) {
         const int box = (a0 + a) % nb;                        // (one division per row)
         float* r = rows + (size_t)a * L;
-        const hbf16_t* cb = hp.conf_bias[l] ? hp.conf_bias[l] + box * C : nullptr;
+        const bf16_t* cb = hp.conf_bias[l] ? hp.conf_bias[l] + box * C : nullptr;
         float mx = -INFINITY;
         for (int c = 0; c < C; ++c) {
             // the PyTorch path rounds conv + bias to bf16 before the float32 softmax: keep that rounding
-            const float v = cb ? h_bf2f(h_f2bf(h_bf2f(cl[a * C + c]) + h_bf2f(cb[c]))) : h_bf2f(cl[a * C + c]);
+            const float v = cb ? bf16_float(bf16_bits(bf16_float(cl[a * C + c]) + bf16_float(cb[c]))) : bf16_float(cl[a * C + c]);
             r[c] = v;
             mx = fmaxf(mx, v);
         }
         float sum = 0.f;
         for (int c = 0; c < C; ++c) { const float e = expf(r[c] - mx); r[c] = e; sum += e; }
         for (int c = 0; c < C; ++c) r[c] = r[c] / sum;
-        const hbf16_t* lb = hp.loc_bias[l] ? hp.loc_bias[l] + box * 4 : nullptr;
-        for (int k = 0; k < 4; ++k) r[C + k] = lb ? h_bf2f(h_f2bf(h_bf2f(ll[a * 4 + k]) + h_bf2f(lb[k]))) : h_bf2f(ll[a * 4 + k]);
+        const bf16_t* lb = hp.loc_bias[l] ? hp.loc_bias[l] + box * 4 : nullptr;
+        for (int k = 0; k < 4; ++k) r[C + k] = lb ? bf16_float(bf16_bits(bf16_float(ll[a * 4 + k]) + bf16_float(lb[k]))) : bf16_float(ll[a * 4 + k]);
         const float* av = anchors_var + (size_t)(hp.anchor_off[l] + a0 + a) * 8;
         for (int k = 0; k < 8; ++k) r[C + 4 + k] = av[k];
     }
@@ -298,10 +290,10 @@ static inline int head_fill_params(HeadParams& hp, int n_layers, const void* con
     int off = 0, tiles = 0;
     for (int l = 0; l < MAX_PRED_LAYERS; ++l) {
         const bool on = l < n_layers;
-        hp.conf[l] = on ? static_cast<const hbf16_t*>(conf_h[l]) : nullptr;
-        hp.loc[l] = on ? static_cast<const hbf16_t*>(loc_h[l]) : nullptr;
-        hp.conf_bias[l] = (on && conf_bias_h) ? static_cast<const hbf16_t*>(conf_bias_h[l]) : nullptr;
-        hp.loc_bias[l] = (on && loc_bias_h) ? static_cast<const hbf16_t*>(loc_bias_h[l]) : nullptr;
+        hp.conf[l] = on ? static_cast<const bf16_t*>(conf_h[l]) : nullptr;
+        hp.loc[l] = on ? static_cast<const bf16_t*>(loc_h[l]) : nullptr;
+        hp.conf_bias[l] = (on && conf_bias_h) ? static_cast<const bf16_t*>(conf_bias_h[l]) : nullptr;
+        hp.loc_bias[l] = (on && loc_bias_h) ? static_cast<const bf16_t*>(loc_bias_h[l]) : nullptr;
         hp.n_anchors[l] = on ? n_anchors_h[l] : 0;
         hp.n_boxes[l] = on ? n_boxes_h[l] : 1;
         hp.conf_stride[l] = on ? (conf_stride_h ? conf_stride_h[l] : n_boxes_h[l] * C) : 0;

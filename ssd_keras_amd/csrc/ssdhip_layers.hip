@@ -15,22 +15,15 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
 #include "ssdhip_heads.h"
 
 namespace ssdhip {
 
-typedef unsigned short bf16_t;
-
-__device__ __forceinline__ float bf2f(u32 h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ u32 f2bf(float f) {            // round to nearest even, NaN stays NaN (as c10::BFloat16)
-    const u32 u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 // two bf16 lanes of one dword: out = act(x + b)
 __device__ __forceinline__ u32 bias_act2(u32 x, u32 b, bool relu) {
-    u32 lo = f2bf(bf2f(x & 0xffffu) + bf2f(b & 0xffffu));
-    u32 hi = f2bf(bf2f(x >> 16) + bf2f(b >> 16));
+    u32 lo = bf16_bits(bf16_float(x & 0xffffu) + bf16_float(b & 0xffffu));
+    u32 hi = bf16_bits(bf16_float(x >> 16) + bf16_float(b >> 16));
     if (relu) {                                            // clamp_min(0) on the rounded value; NaN passes through
         if ((lo & 0x8000u) && (lo & 0x7fffu) <= 0x7f80u) lo = 0;
         if ((hi & 0x8000u) && (hi & 0x7fffu) <= 0x7f80u) hi = 0;
@@ -42,7 +35,7 @@ __device__ __forceinline__ uint4 bias_act8(uint4 x, uint4 b, bool relu) {
 }
 // max of two bf16 as torch's max_pool2d takes it (NaN propagates)
 __device__ __forceinline__ u32 bfmax1(u32 a, u32 b) {
-    const float fa = bf2f(a), fb = bf2f(b);
+    const float fa = bf16_float(a), fb = bf16_float(b);
     return (fa > fb || fa != fa) ? a : b;
 }
 __device__ __forceinline__ u32 bfmax2(u32 a, u32 b) { return bfmax1(a & 0xffffu, b & 0xffffu) | (bfmax1(a >> 16, b >> 16) << 16); }
@@ -125,7 +118,6 @@ __global__ __launch_bounds__(256) void bias_act_maxpool_kernel(const uint4* __re
 // +0 where the compare-based maximum keeps the first one; equal as numbers.)  The map is applied once per element on the way into
 // LDS and inverted once per output.
 constexpr int POOL3_THREADS = 1024;
-typedef short l_s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short l_u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u32 l_ordered2(u32 v) {
     const u32 mag = v & 0x7fff7fffu;
@@ -133,15 +125,12 @@ __device__ __forceinline__ u32 l_ordered2(u32 v) {
     const l_u16x2 over = __builtin_elementwise_sub_sat(__builtin_bit_cast(l_u16x2, mag), __builtin_bit_cast(l_u16x2, 0x7f807f80u));
     const l_u16x2 one = __builtin_elementwise_min(over, __builtin_bit_cast(l_u16x2, 0x00010001u));
     v &= ~(__builtin_bit_cast(u32, one) << 15);            // NaNs become positive
-    const u32 neg = __builtin_bit_cast(u32, __builtin_bit_cast(l_s16x2, v) >> 15);   // 0xffff in a negative half
+    const u32 neg = __builtin_bit_cast(u32, __builtin_bit_cast(s16x2, v) >> 15);   // 0xffff in a negative half
     return v ^ (neg & 0x7fff7fffu);
 }
 __device__ __forceinline__ u32 l_unordered2(u32 t) {
-    const u32 neg = __builtin_bit_cast(u32, __builtin_bit_cast(l_s16x2, t) >> 15);
+    const u32 neg = __builtin_bit_cast(u32, __builtin_bit_cast(s16x2, t) >> 15);
     return t ^ (neg & 0x7fff7fffu);
-}
-__device__ __forceinline__ u32 l_pkmax_i16(u32 a, u32 b) {
-    return __builtin_bit_cast(u32, __builtin_elementwise_max(__builtin_bit_cast(l_s16x2, a), __builtin_bit_cast(l_s16x2, b)));
 }
 __global__ __launch_bounds__(POOL3_THREADS) void pool3x3s1_slab_kernel(const uint4* __restrict__ x, uint4* __restrict__ y, int H, int W,
                                                                        u32 cvec, u32 slabs) {
@@ -165,7 +154,7 @@ __global__ __launch_bounds__(POOL3_THREADS) void pool3x3s1_slab_kernel(const uin
                 const int hi = h + dh, wi = w + dw;
                 const bool in = (hi >= 0) & (hi < H) & (wi >= 0) & (wi < W);
                 const uint4 v = pool3_tile[(in ? hi * W + wi : px) * 8 + c];               // outside the map: the centre again (no effect)
-                best = make_uint4(l_pkmax_i16(v.x, best.x), l_pkmax_i16(v.y, best.y), l_pkmax_i16(v.z, best.z), l_pkmax_i16(v.w, best.w));
+                best = make_uint4(pkmax_i16(v.x, best.x), pkmax_i16(v.y, best.y), pkmax_i16(v.z, best.z), pkmax_i16(v.w, best.w));
             }
         y[base + (size_t)px * cvec + (u32)c] = make_uint4(l_unordered2(best.x), l_unordered2(best.y), l_unordered2(best.z), l_unordered2(best.w));
     }
@@ -186,7 +175,7 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const uint4* __restrict__ x
             const uint4 v = row[j];
             const u32 w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { const float a = bf2f(w[q] & 0xffffu), c = bf2f(w[q] >> 16); ss += a * a; ss += c * c; }
+            for (int q = 0; q < 4; ++q) { const float a = bf16_float(w[q] & 0xffffu), c = bf16_float(w[q] >> 16); ss += a * a; ss += c * c; }
         }
         for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
         const float inv = rsqrtf(fmaxf(ss, 1e-12f));
@@ -197,7 +186,7 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const uint4* __restrict__ x
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float g0 = gamma[j * 8 + q * 2], g1 = gamma[j * 8 + q * 2 + 1];
-                o[q] = f2bf((bf2f(w[q] & 0xffffu) * inv) * g0) | (f2bf((bf2f(w[q] >> 16) * inv) * g1) << 16);
+                o[q] = bf16_bits((bf16_float(w[q] & 0xffffu) * inv) * g0) | (bf16_bits((bf16_float(w[q] >> 16) * inv) * g1) << 16);
             }
             y[(size_t)px * cvec + j] = make_uint4(o[0], o[1], o[2], o[3]);
         }
@@ -242,7 +231,7 @@ __global__ __launch_bounds__(256) void pool2_l2norm_kernel(const uint4* __restri
             const u32 w4[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
             float acc = 0.f;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) { const float a = bf2f(w4[t] & 0xffffu), c = bf2f(w4[t] >> 16); acc += a * a; acc += c * c; }
+            for (int t = 0; t < 4; ++t) { const float a = bf16_float(w4[t] & 0xffffu), c = bf16_float(w4[t] >> 16); acc += a * a; acc += c * c; }
             ss[q] = acc;
         }
         for (int off = 32; off > 0; off >>= 1) {
@@ -257,7 +246,7 @@ __global__ __launch_bounds__(256) void pool2_l2norm_kernel(const uint4* __restri
             u32 r[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-                r[t] = f2bf((bf2f(w4[t] & 0xffffu) * inv) * g[2 * t]) | (f2bf((bf2f(w4[t] >> 16) * inv) * g[2 * t + 1]) << 16);
+                r[t] = bf16_bits((bf16_float(w4[t] & 0xffffu) * inv) * g[2 * t]) | (bf16_bits((bf16_float(w4[t] >> 16) * inv) * g[2 * t + 1]) << 16);
             const int h = 2 * ho + (q >> 1), w = 2 * wo + (q & 1);
             y_norm[((size_t)(b * H + h) * W + w) * 64 + lane] = make_uint4(r[0], r[1], r[2], r[3]);
         }
@@ -278,7 +267,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const float* __restrict
             const int sc = pp.swap[c];
             float t = v[sc] - pp.mean[sc];
             if (pp.has_scale) t = t / pp.scale[sc];
-            out[(size_t)px * Cin + c] = (bf16_t)f2bf(t);
+            out[(size_t)px * Cin + c] = (bf16_t)bf16_bits(t);
         }
     }
 }
@@ -297,7 +286,7 @@ __global__ __launch_bounds__(256) void preprocess3_kernel(const float4* __restri
                 const int sc = pp.swap[ch];
                 float t = (sc == 0 ? v[px * 3] : sc == 1 ? v[px * 3 + 1] : v[px * 3 + 2]) - pp.mean[sc];
                 if (pp.has_scale) t = t / pp.scale[sc];
-                o[px * 3 + ch] = f2bf(t);
+                o[px * 3 + ch] = bf16_bits(t);
             }
         out[(size_t)q * 3] = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
         out[(size_t)q * 3 + 1] = make_uint2(o[4] | (o[5] << 16), o[6] | (o[7] << 16));
@@ -317,7 +306,7 @@ __global__ __launch_bounds__(256) void head_kernel(HeadParams hp, const float* _
     int l, a0, na;
     head_tile_of(hp, (int)blockIdx.x, l, a0, na);
     float* rows = reinterpret_cast<float*>(smem_raw);                                   // [TA][L]
-    hbf16_t* cl = reinterpret_cast<hbf16_t*>(smem_raw + (size_t)hp.TA * L * sizeof(float));
+    bf16_t* cl = reinterpret_cast<bf16_t*>(smem_raw + (size_t)hp.TA * L * sizeof(float));
     head_build_rows(hp, anchors_var, l, b, a0, na, rows, cl, tid, 256);
     float* dst = y + ((size_t)b * hp.N + hp.anchor_off[l] + a0) * L;
     for (int i = tid; i < na * L; i += 256) dst[i] = rows[i];
@@ -365,8 +354,8 @@ __global__ __launch_bounds__(HG_TILE) void head_grad_kernel(HeadGradParams hp, c
         float dot = 0.f;
         for (int c = 0; c < C; ++c) dot += gr[c] * pr[c];
         bf16_t* row = reinterpret_cast<bf16_t*>(stage + (size_t)pix * rowb);
-        for (int c = 0; c < C; ++c) row[box * C + c] = (bf16_t)f2bf(pr[c] * (gr[c] - dot));
-        for (int k = 0; k < 4; ++k) row[nb * C + box * 4 + k] = (bf16_t)f2bf(gr[C + k]);
+        for (int c = 0; c < C; ++c) row[box * C + c] = (bf16_t)bf16_bits(pr[c] * (gr[c] - dot));
+        for (int k = 0; k < 4; ++k) row[nb * C + box * 4 + k] = (bf16_t)bf16_bits(gr[C + k]);
     }
     __syncthreads();
     const size_t npix_l = (size_t)(hp.n_anchors[l] / nb);
@@ -469,13 +458,6 @@ namespace ssdhip {
 //                     K = 27 is no GEMM: 5 GFLOP of vector work against 0.7 GB of output; MIOpen's float32 path for a 3-channel
 //                     NHWC input is its naive kernel (5.2 ms at batch 32, r03w).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 l_split2(float a, float b, u32& lo_out) {
-    const _Float16 ha = (_Float16)a, hb = (_Float16)b;
-    const _Float16 la = (_Float16)(a - (float)ha), lb = (_Float16)(b - (float)hb);
-    lo_out = (u32)__builtin_bit_cast(unsigned short, la) | ((u32)__builtin_bit_cast(unsigned short, lb) << 16);
-    return (u32)__builtin_bit_cast(unsigned short, ha) | ((u32)__builtin_bit_cast(unsigned short, hb) << 16);
-}
-
 // one thread per 8 channels of a pixel; cvec = C / 8
 __global__ __launch_bounds__(256) void x3_split_kernel(const float4* __restrict__ x, uint4* __restrict__ y, u32 n_pixels, u32 cvec) {
     const u32 total = n_pixels * cvec;
@@ -483,7 +465,7 @@ __global__ __launch_bounds__(256) void x3_split_kernel(const float4* __restrict_
         const u32 px = i / cvec, cg = i - px * cvec;
         const float4 a = x[(size_t)i * 2], b = x[(size_t)i * 2 + 1];
         u32 l0, l1, l2, l3;
-        const u32 h0 = l_split2(a.x, a.y, l0), h1 = l_split2(a.z, a.w, l1), h2 = l_split2(b.x, b.y, l2), h3 = l_split2(b.z, b.w, l3);
+        const u32 h0 = split2_f16(a.x, a.y, l0), h1 = split2_f16(a.z, a.w, l1), h2 = split2_f16(b.x, b.y, l2), h3 = split2_f16(b.z, b.w, l3);
         y[(size_t)px * (2 * cvec) + cg] = make_uint4(h0, h1, h2, h3);
         y[(size_t)px * (2 * cvec) + cvec + cg] = make_uint4(l0, l1, l2, l3);
     }
@@ -569,12 +551,11 @@ __global__ __launch_bounds__(256, 4) void conv1_1_x3_kernel(const float* __restr
             hq[u] = (int)((px / (u32)W) % (u32)H);
         }
         // packed float32 FMAs (v_pk_fma_f32: two channels per instruction): the kernel's VALU work is 864 FMAs per thread and tile
-        typedef float c11_f2 __attribute__((ext_vector_type(2)));
-        c11_f2 acc[C11_PX][4];
+        f32x2 acc[C11_PX][4];
 #pragma unroll
         for (int u = 0; u < C11_PX; ++u)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[u][e] = (c11_f2){0.f, 0.f};
+            for (int e = 0; e < 4; ++e) acc[u][e] = (f32x2){0.f, 0.f};
 #pragma unroll 1
         for (int kh = 0; kh < 3; ++kh) {                  // not unrolled: one filter row's 72 values in flight at a time
             // the quad's six input pixels of this filter row (local pixels pl * 4 - 1 .. pl * 4 + 4 -> run offsets pl * 12 .. + 17)
@@ -595,10 +576,10 @@ __global__ __launch_bounds__(256, 4) void conv1_1_x3_kernel(const float* __restr
                 for (int ci = 0; ci < 3; ++ci) {
                     const float4 w0 = *reinterpret_cast<const float4*>(wt + ((kh * 3 + kw) * 3 + ci) * 64);
                     const float4 w1 = *reinterpret_cast<const float4*>(wt + ((kh * 3 + kw) * 3 + ci) * 64 + 4);
-                    const c11_f2 wr[4] = {{w0.x, w0.y}, {w0.z, w0.w}, {w1.x, w1.y}, {w1.z, w1.w}};
+                    const f32x2 wr[4] = {{w0.x, w0.y}, {w0.z, w0.w}, {w1.x, w1.y}, {w1.z, w1.w}};
 #pragma unroll
                     for (int u = 0; u < C11_PX; ++u) {
-                        const c11_f2 vv = {v[u][ci], v[u][ci]};
+                        const f32x2 vv = {v[u][ci], v[u][ci]};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) acc[u][e] = __builtin_elementwise_fma(vv, wr[e], acc[u][e]);
                     }
@@ -615,7 +596,7 @@ __global__ __launch_bounds__(256, 4) void conv1_1_x3_kernel(const float* __restr
                 o[e] = relu ? (t > 0.f ? t : (t != t ? t : 0.f)) : t;
             }
             u32 l0, l1, l2, l3;
-            const u32 h0 = l_split2(o[0], o[1], l0), h1 = l_split2(o[2], o[3], l1), h2 = l_split2(o[4], o[5], l2), h3 = l_split2(o[6], o[7], l3);
+            const u32 h0 = split2_f16(o[0], o[1], l0), h1 = split2_f16(o[2], o[3], l1), h2 = split2_f16(o[4], o[5], l2), h3 = split2_f16(o[6], o[7], l3);
             y[(size_t)(px0 + u) * 16 + cg] = make_uint4(h0, h1, h2, h3);
             y[(size_t)(px0 + u) * 16 + 8 + cg] = make_uint4(l0, l1, l2, l3);
         }
@@ -655,7 +636,7 @@ __global__ __launch_bounds__(256) void x3_l2norm_kernel(const uint4* __restrict_
                 o[2 * q + 1] = (b * inv) * gamma[j * 8 + 2 * q + 1];
             }
             u32 l0, l1, l2, l3;
-            const u32 h0 = l_split2(o[0], o[1], l0), h1 = l_split2(o[2], o[3], l1), h2 = l_split2(o[4], o[5], l2), h3 = l_split2(o[6], o[7], l3);
+            const u32 h0 = split2_f16(o[0], o[1], l0), h1 = split2_f16(o[2], o[3], l1), h2 = split2_f16(o[4], o[5], l2), h3 = split2_f16(o[6], o[7], l3);
             y[(size_t)px * (2 * cvec) + j] = make_uint4(h0, h1, h2, h3);
             y[(size_t)px * (2 * cvec) + cvec + j] = make_uint4(l0, l1, l2, l3);
         }

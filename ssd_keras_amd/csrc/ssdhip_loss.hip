@@ -522,7 +522,7 @@ static bool stream_big_lds(const void* fn, int which, size_t lds) {     // the >
 }
 
 // the wave's next tile -> stage `lds_dst`: G loads per array, always (a short last tile of an image and the lanes past its end write zeros)
-__device__ __forceinline__ void stream_issue(int t, int tiles64, int N, int L, int G, tile_i32x4 rt, tile_i32x4 rp, u32 lds_dst, int lane) {
+__device__ __forceinline__ void stream_issue(int t, int tiles64, int N, int L, int G, i32x4 rt, i32x4 rp, u32 lds_dst, int lane) {
     const int b = t / tiles64, a0 = (t - b * tiles64) * 64;
     const int na = min(64, N - a0);
     const u32 tile_off = (u32)(((size_t)b * N + a0) * (size_t)L * 4);
@@ -549,7 +549,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void anchor_stream_kernel(const float
     unsigned char* mine = smem_raw + (size_t)wave * 2 * stage;
     const u32 lds0 = (u32)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem_raw + (u32)wave * 2u * stage;
     const u32 total_bytes = (u32)((size_t)B * N * (size_t)L * 4);
-    const tile_i32x4 rt = tile_rsrc(y_true, total_bytes), rp = tile_rsrc(y_pred, total_bytes);
+    const i32x4 rt = tile_rsrc(y_true, total_bytes), rp = tile_rsrc(y_pred, total_bytes);
     const int WT = B * tiles64, W = gridDim.x * nw, gw = blockIdx.x * nw + wave;
     for (int i = tid; i < L1_BINS; i += blockDim.x) hist[i] = 0u;
     __syncthreads();
@@ -631,8 +631,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void backward_stream_kernel(const flo
     unsigned char* mine = smem_raw + (size_t)wave * 2 * stage;
     const u32 lds0 = (u32)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem_raw + (u32)wave * 2u * stage;
     const u32 total_bytes = (u32)((size_t)B * N * (size_t)L * 4);
-    const tile_i32x4 rt = tile_rsrc(y_true, total_bytes), rp = tile_rsrc(y_pred, total_bytes), rk = tile_rsrc(keep, (u32)((size_t)B * N));
-    const tile_i32x4 rg = tile_rsrc(grad_out, (u32)B * 4u);
+    const i32x4 rt = tile_rsrc(y_true, total_bytes), rp = tile_rsrc(y_pred, total_bytes), rk = tile_rsrc(keep, (u32)((size_t)B * N));
+    const i32x4 rg = tile_rsrc(grad_out, (u32)B * 4u);
     const int WT = B * tiles64, W = gridDim.x * nw, gw = blockIdx.x * nw + wave;
     // No load of hipcc's own may follow the first DMA load: its s_waitcnt would drain ours with it (hipcc counts only what it issued).
     // stats[0] is read -- and waited for, the empty asm pins that -- up here; grad_out[b] comes with the tile.

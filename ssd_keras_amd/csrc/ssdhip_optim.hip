@@ -26,14 +26,9 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
 
 namespace ssdhip {
-
-__device__ __forceinline__ unsigned short opt_f2b(float f) {          // round to nearest even, NaN stays NaN (as c10::BFloat16)
-    const u32 u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 
 constexpr int SH_T = 32;                                  // tile edge (output x input channels)
 constexpr int SH_MAXKK = 16;                              // taps of a filter: 1 x 1, 3 x 3, 4 x 4 (SSD512's conv10_2)
@@ -54,7 +49,7 @@ __global__ __launch_bounds__(256) void shadow_refresh_kernel(const ssdhip_shadow
         __syncthreads();
         const ssdhip_shadow_desc d = tab[sh_which];
         const int i = (blk - d.tile0) * 256 + tid;
-        if (i < d.O) static_cast<unsigned short*>(d.cl)[i] = opt_f2b(static_cast<const float*>(d.src)[i]);
+        if (i < d.O) static_cast<unsigned short*>(d.cl)[i] = bf16_bits<bf16_t>(static_cast<const float*>(d.src)[i]);
         return;
     }
     if (tid == 0) {
@@ -90,7 +85,7 @@ __global__ __launch_bounds__(256) void shadow_refresh_kernel(const ssdhip_shadow
             }
 #pragma unroll
             for (int u = 0; u < SH_U; ++u)
-                if (at[u] >= 0) tile[at[u]] = opt_f2b(v[u]);
+                if (at[u] >= 0) tile[at[u]] = bf16_bits<bf16_t>(v[u]);
         }
     } else {
         // master [O][I][kk] float32: the tile's row o is the contiguous run [i0 .. i0 + ni) x kk
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(256) void shadow_refresh_kernel(const ssdhip_shadow
             }
 #pragma unroll
             for (int u = 0; u < SH_U; ++u)
-                if (at[u] >= 0) tile[at[u]] = opt_f2b(v[u]);
+                if (at[u] >= 0) tile[at[u]] = bf16_bits<bf16_t>(v[u]);
         }
     }
     __syncthreads();

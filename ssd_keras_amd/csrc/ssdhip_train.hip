@@ -18,15 +18,9 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
 
 namespace ssdhip {
-
-__device__ __forceinline__ float tb2f(u32 h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ u32 tf2b(float f) {             // round to nearest even, NaN stays NaN (as c10::BFloat16)
-    const u32 u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 // gy, y, out: [n_pixels][C] bf16 as uint4 (8 channels); partial: [gridDim.x][C] float32.  cvec = C / 8 divides 256.
 // MASK = false: no activation behind the layer (the packed predictor heads): channel sums of gy only, nothing written to `out`.
@@ -48,11 +42,11 @@ __global__ __launch_bounds__(256) void relu_bwd_bias_kernel(const uint4* __restr
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             // threshold_backward(grad, y, 0): zero where y <= 0 (a NaN activation lets the gradient through)
-            const u32 lo = (MASK && tb2f(vw[q] & 0xffffu) <= 0.f) ? 0u : (gw[q] & 0xffffu);
-            const u32 hi = (MASK && tb2f(vw[q] >> 16) <= 0.f) ? 0u : (gw[q] >> 16);
+            const u32 lo = (MASK && bf16_float(vw[q] & 0xffffu) <= 0.f) ? 0u : (gw[q] & 0xffffu);
+            const u32 hi = (MASK && bf16_float(vw[q] >> 16) <= 0.f) ? 0u : (gw[q] >> 16);
             o[q] = lo | (hi << 16);
-            acc[2 * q] += tb2f(lo);
-            acc[2 * q + 1] += tb2f(hi);
+            acc[2 * q] += bf16_float(lo);
+            acc[2 * q + 1] += bf16_float(hi);
         }
         if (MASK) out[i] = make_uint4(o[0], o[1], o[2], o[3]);
     }
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const uint4* __restric
                         const int pos = hi * W + wi;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            const float a = tb2f(vw[q] & 0xffffu), c = tb2f(vw[q] >> 16);
+                            const float a = bf16_float(vw[q] & 0xffffu), c = bf16_float(vw[q] >> 16);
                             if (a > best[2 * q] || a != a) { best[2 * q] = a; arg[2 * q] = pos; }          // max_pool2d: first maximum, NaN wins
                             if (c > best[2 * q + 1] || c != c) { best[2 * q + 1] = c; arg[2 * q + 1] = pos; }
                         }
@@ -109,12 +103,12 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const uint4* __restric
                 const int me = h * W + w;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    if (arg[2 * q] == me) acc[2 * q] += tb2f(gw[q] & 0xffffu);
-                    if (arg[2 * q + 1] == me) acc[2 * q + 1] += tb2f(gw[q] >> 16);
+                    if (arg[2 * q] == me) acc[2 * q] += bf16_float(gw[q] & 0xffffu);
+                    if (arg[2 * q + 1] == me) acc[2 * q + 1] += bf16_float(gw[q] >> 16);
                 }
             }
-        gx[i] = make_uint4(tf2b(acc[0]) | (tf2b(acc[1]) << 16), tf2b(acc[2]) | (tf2b(acc[3]) << 16), tf2b(acc[4]) | (tf2b(acc[5]) << 16),
-                           tf2b(acc[6]) | (tf2b(acc[7]) << 16));
+        gx[i] = make_uint4(bf16_bits(acc[0]) | (bf16_bits(acc[1]) << 16), bf16_bits(acc[2]) | (bf16_bits(acc[3]) << 16), bf16_bits(acc[4]) | (bf16_bits(acc[5]) << 16),
+                           bf16_bits(acc[6]) | (bf16_bits(acc[7]) << 16));
     }
 }
 
@@ -160,17 +154,17 @@ __global__ __launch_bounds__(256) void maxpool3s1_bwd_kernel(const uint4* __rest
                             const int r = dh + eh + 2, c = dw + ew + 2;
                             const uint4 v = nb[r][c];
                             const u32 wd = q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w;
-                            const float a = tb2f(wd & 0xffffu), cc = tb2f(wd >> 16);
+                            const float a = bf16_float(wd & 0xffffu), cc = bf16_float(wd >> 16);
                             const bool ok = okr[r] && okc[c];
                             if (ok && (a > best0 || a != a)) { best0 = a; arg0 = (eh + 1) * 3 + (ew + 1); }
                             if (ok && (cc > best1 || cc != cc)) { best1 = cc; arg1 = (eh + 1) * 3 + (ew + 1); }
                         }
-                    if (arg0 == me) acc[2 * q] += tb2f(gw[q] & 0xffffu);
-                    if (arg1 == me) acc[2 * q + 1] += tb2f(gw[q] >> 16);
+                    if (arg0 == me) acc[2 * q] += bf16_float(gw[q] & 0xffffu);
+                    if (arg1 == me) acc[2 * q + 1] += bf16_float(gw[q] >> 16);
                 }
             }
-        gx[i] = make_uint4(tf2b(acc[0]) | (tf2b(acc[1]) << 16), tf2b(acc[2]) | (tf2b(acc[3]) << 16), tf2b(acc[4]) | (tf2b(acc[5]) << 16),
-                           tf2b(acc[6]) | (tf2b(acc[7]) << 16));
+        gx[i] = make_uint4(bf16_bits(acc[0]) | (bf16_bits(acc[1]) << 16), bf16_bits(acc[2]) | (bf16_bits(acc[3]) << 16), bf16_bits(acc[4]) | (bf16_bits(acc[5]) << 16),
+                           bf16_bits(acc[6]) | (bf16_bits(acc[7]) << 16));
     }
 }
 
@@ -202,7 +196,7 @@ __global__ __launch_bounds__(256) void maxpool3s1_bwd_img_kernel(const uint4* __
 #pragma unroll
             for (int e = 0; e < 9; ++e) {
                 const u32 wd = q == 0 ? v[e].x : q == 1 ? v[e].y : q == 2 ? v[e].z : v[e].w;
-                const float a = tb2f(wd & 0xffffu), c = tb2f(wd >> 16);
+                const float a = bf16_float(wd & 0xffffu), c = bf16_float(wd >> 16);
                 if (ok[e] && (a > best0 || a != a)) { best0 = a; arg0 = (u32)e; }          // max_pool2d: first maximum, NaN wins
                 if (ok[e] && (c > best1 || c != c)) { best1 = c; arg1 = (u32)e; }
             }
@@ -227,12 +221,12 @@ __global__ __launch_bounds__(256) void maxpool3s1_bwd_img_kernel(const uint4* __
                 const u32 me = (u32)((1 - dh) * 3 + (1 - dw));
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    if (((c >> (8 * q)) & 15u) == me) acc[2 * q] += tb2f(gw[q] & 0xffffu);
-                    if (((c >> (8 * q + 4)) & 15u) == me) acc[2 * q + 1] += tb2f(gw[q] >> 16);
+                    if (((c >> (8 * q)) & 15u) == me) acc[2 * q] += bf16_float(gw[q] & 0xffffu);
+                    if (((c >> (8 * q + 4)) & 15u) == me) acc[2 * q + 1] += bf16_float(gw[q] >> 16);
                 }
             }
-        gx[(img + (size_t)px) * cvec + cg] = make_uint4(tf2b(acc[0]) | (tf2b(acc[1]) << 16), tf2b(acc[2]) | (tf2b(acc[3]) << 16),
-                                                         tf2b(acc[4]) | (tf2b(acc[5]) << 16), tf2b(acc[6]) | (tf2b(acc[7]) << 16));
+        gx[(img + (size_t)px) * cvec + cg] = make_uint4(bf16_bits(acc[0]) | (bf16_bits(acc[1]) << 16), bf16_bits(acc[2]) | (bf16_bits(acc[3]) << 16),
+                                                         bf16_bits(acc[4]) | (bf16_bits(acc[5]) << 16), bf16_bits(acc[6]) | (bf16_bits(acc[7]) << 16));
     }
 }
 
@@ -265,11 +259,11 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const uint4* __restri
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const u32 w = q == 0 ? v[k].x : q == 1 ? v[k].y : q == 2 ? v[k].z : v[k].w;
-                const float a = tb2f(w & 0xffffu), c = tb2f(w >> 16);
+                const float a = bf16_float(w & 0xffffu), c = bf16_float(w >> 16);
                 if (ok[k] && (a > best0 || a != a)) { best0 = a; arg0 = k; }          // max_pool2d: first maximum, NaN wins
                 if (ok[k] && (c > best1 || c != c)) { best1 = c; arg1 = k; }
             }
-            const u32 glo = tf2b(0.f + tb2f(gw[q] & 0xffffu)), ghi = tf2b(0.f + tb2f(gw[q] >> 16));
+            const u32 glo = bf16_bits(0.f + bf16_float(gw[q] & 0xffffu)), ghi = bf16_bits(0.f + bf16_float(gw[q] >> 16));
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k][q] = (arg0 == k ? glo : 0u) | ((arg1 == k ? ghi : 0u) << 16);
         }
@@ -317,20 +311,20 @@ __global__ __launch_bounds__(256) void maxpool2_relu_bwd_bias_kernel(const uint4
                             : k == 1 ? (q == 0 ? v[1].x : q == 1 ? v[1].y : q == 2 ? v[1].z : v[1].w)
                             : k == 2 ? (q == 0 ? v[2].x : q == 1 ? v[2].y : q == 2 ? v[2].z : v[2].w)
                                      : (q == 0 ? v[3].x : q == 1 ? v[3].y : q == 2 ? v[3].z : v[3].w);
-                const float a = tb2f(w & 0xffffu), c = tb2f(w >> 16);
+                const float a = bf16_float(w & 0xffffu), c = bf16_float(w >> 16);
                 if (ok[k] && (a > best0 || a != a)) { best0 = a; arg0 = k; }          // max_pool2d: first maximum, NaN wins
                 if (ok[k] && (c > best1 || c != c)) { best1 = c; arg1 = k; }
             }
             // maxpool_bwd_kernel's value (0 + g, rounded: -0 becomes +0) where the pixel is the window's arg-max, then the ReLU mask
-            const u32 glo = tf2b(0.f + tb2f(gw[q] & 0xffffu)), ghi = tf2b(0.f + tb2f(gw[q] >> 16));
+            const u32 glo = bf16_bits(0.f + bf16_float(gw[q] & 0xffffu)), ghi = bf16_bits(0.f + bf16_float(gw[q] >> 16));
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const u32 w = k == 0 ? (q == 0 ? v[0].x : q == 1 ? v[0].y : q == 2 ? v[0].z : v[0].w)
                             : k == 1 ? (q == 0 ? v[1].x : q == 1 ? v[1].y : q == 2 ? v[1].z : v[1].w)
                             : k == 2 ? (q == 0 ? v[2].x : q == 1 ? v[2].y : q == 2 ? v[2].z : v[2].w)
                                      : (q == 0 ? v[3].x : q == 1 ? v[3].y : q == 2 ? v[3].z : v[3].w);
-                const u32 lo = (arg0 != k || tb2f(w & 0xffffu) <= 0.f) ? 0u : glo;
-                const u32 hi = (arg1 != k || tb2f(w >> 16) <= 0.f) ? 0u : ghi;
+                const u32 lo = (arg0 != k || bf16_float(w & 0xffffu) <= 0.f) ? 0u : glo;
+                const u32 hi = (arg1 != k || bf16_float(w >> 16) <= 0.f) ? 0u : ghi;
                 o[k][q] = lo | (hi << 16);
             }
         }
@@ -339,7 +333,7 @@ __global__ __launch_bounds__(256) void maxpool2_relu_bwd_bias_kernel(const uint4
             if (ok[k]) {
                 out[pos[k]] = make_uint4(o[k][0], o[k][1], o[k][2], o[k][3]);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) { acc[2 * q] += tb2f(o[k][q] & 0xffffu); acc[2 * q + 1] += tb2f(o[k][q] >> 16); }
+                for (int q = 0; q < 4; ++q) { acc[2 * q] += bf16_float(o[k][q] & 0xffffu); acc[2 * q + 1] += bf16_float(o[k][q] >> 16); }
             }
         }
     }
@@ -364,8 +358,6 @@ __global__ __launch_bounds__(256) void maxpool2_relu_bwd_bias_kernel(const uint4
 // the tile's im2col patch [k = (kh 3 + kw) 3 + ci][pixel], and four waves accumulate D[64 channels][32 k] with
 // v_mfma_f32_32x32x16_bf16 over the pixels (K).  Reads gy + y + x once, writes per-workgroup partial sums (added in order by the caller).
 // ---------------------------------------------------------------------------------------------------------------
-typedef __bf16 tr_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float tr_f32x16 __attribute__((ext_vector_type(16)));
 constexpr int C11B_PITCH = 144;                              // bytes per LDS row: 64 pixels + padding, 16-byte aligned
 
 __global__ __launch_bounds__(256) void conv1_1_bwd_kernel(const uint4* __restrict__ gy, const uint4* __restrict__ y,
@@ -378,7 +370,7 @@ __global__ __launch_bounds__(256) void conv1_1_bwd_kernel(const uint4* __restric
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cg = tid & 7, pp = tid >> 3;                   // 8 channels x one PAIR of pixels per thread
     float bacc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    tr_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     for (int i = tid; i < 32 * C11B_PITCH / 4; i += 256) reinterpret_cast<u32*>(pT)[i] = 0u;
@@ -412,11 +404,11 @@ __global__ __launch_bounds__(256) void conv1_1_bwd_kernel(const uint4* __restric
             const u32 gw[4] = {g[e].x, g[e].y, g[e].z, g[e].w}, vw[4] = {a[e].x, a[e].y, a[e].z, a[e].w};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const u32 lo = (tb2f(vw[q] & 0xffffu) <= 0.f) ? 0u : (gw[q] & 0xffffu);
-                const u32 hi = (tb2f(vw[q] >> 16) <= 0.f) ? 0u : (gw[q] >> 16);
+                const u32 lo = (bf16_float(vw[q] & 0xffffu) <= 0.f) ? 0u : (gw[q] & 0xffffu);
+                const u32 hi = (bf16_float(vw[q] >> 16) <= 0.f) ? 0u : (gw[q] >> 16);
                 m[e][q] = lo | (hi << 16);
-                bacc[2 * q] += tb2f(lo);
-                bacc[2 * q + 1] += tb2f(hi);
+                bacc[2 * q] += bf16_float(lo);
+                bacc[2 * q + 1] += bf16_float(hi);
             }
         }
 #pragma unroll
@@ -437,8 +429,8 @@ __global__ __launch_bounds__(256) void conv1_1_bwd_kernel(const uint4* __restric
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int px0 = (pxhalf * 2 + ks) * 16 + (lane >> 5) * 8;
-            const tr_bf16x8 fa = *reinterpret_cast<const tr_bf16x8*>(gT + (cohalf * 32 + (lane & 31)) * C11B_PITCH + px0 * 2);
-            const tr_bf16x8 fb = *reinterpret_cast<const tr_bf16x8*>(pT + (lane & 31) * C11B_PITCH + px0 * 2);
+            const bf16x8 fa = *reinterpret_cast<const bf16x8*>(gT + (cohalf * 32 + (lane & 31)) * C11B_PITCH + px0 * 2);
+            const bf16x8 fb = *reinterpret_cast<const bf16x8*>(pT + (lane & 31) * C11B_PITCH + px0 * 2);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc, 0, 0, 0);
         }
         __syncthreads();                                      // the next tile overwrites gT / pT / xs
@@ -559,7 +551,7 @@ __device__ __forceinline__ void l2_load(const void* base, size_t vec, float (&v)
         const uint4 r = reinterpret_cast<const uint4*>(base)[vec];
         const u32 w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { v[2 * q] = tb2f(w[q] & 0xffffu); v[2 * q + 1] = tb2f(w[q] >> 16); }
+        for (int q = 0; q < 4; ++q) { v[2 * q] = bf16_float(w[q] & 0xffffu); v[2 * q + 1] = bf16_float(w[q] >> 16); }
     } else {
         const float4 r = reinterpret_cast<const float4*>(base)[vec];
         v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
@@ -569,8 +561,8 @@ __device__ __forceinline__ void l2_load(const void* base, size_t vec, float (&v)
 template <bool BF16>
 __device__ __forceinline__ void l2_store(void* base, size_t vec, const float (&v)[8]) {
     if constexpr (BF16)
-        reinterpret_cast<uint4*>(base)[vec] = make_uint4(tf2b(v[0]) | (tf2b(v[1]) << 16), tf2b(v[2]) | (tf2b(v[3]) << 16),
-                                                         tf2b(v[4]) | (tf2b(v[5]) << 16), tf2b(v[6]) | (tf2b(v[7]) << 16));
+        reinterpret_cast<uint4*>(base)[vec] = make_uint4(bf16_bits(v[0]) | (bf16_bits(v[1]) << 16), bf16_bits(v[2]) | (bf16_bits(v[3]) << 16),
+                                                         bf16_bits(v[4]) | (bf16_bits(v[5]) << 16), bf16_bits(v[6]) | (bf16_bits(v[7]) << 16));
     else
         reinterpret_cast<float4*>(base)[vec] = make_float4(v[0], v[1], v[2], v[3]);
 }

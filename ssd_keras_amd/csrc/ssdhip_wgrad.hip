@@ -36,16 +36,12 @@
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
+#include "ssdhip_bf16.h"
+#include "ssdhip_tile.h"
 
 namespace ssdhip {
 
-typedef unsigned short bf16_t;
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
-typedef int wg_i32x4 __attribute__((ext_vector_type(4)));
 typedef short wg_s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int wg_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int wg_u32x4 __attribute__((ext_vector_type(4)));
 
 struct WgParams {
     const bf16_t* x;             // [B, H, W, Cin]
@@ -66,25 +62,10 @@ constexpr int WG_THREADS = 512;
 constexpr int wg_lds_bytes(int cos, int rb) { return 2 * (64 * rb + 32) * 64 + 4 * 1024 + cos * 4 * 64 * 64; }
 
 #if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ void wg_bload(u32 voff, wg_i32x4 rsrc, u32 lds_dst) {     // one 1 KiB LDS-DMA piece (see ch_bload)
-    u32 keep;
-    lds_dst = (u32)__builtin_amdgcn_readfirstlane((int)lds_dst);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ wg_i32x4 wg_rsrc(const void* base, int num_records) {
-    const unsigned long long a = (unsigned long long)(uintptr_t)base;
-    wg_i32x4 r;
-    r.x = (int)(u32)a;
-    r.y = (int)((u32)(a >> 32) & 0xffffu);
-    r.z = num_records;
-    r.w = 0x00020000;
-    return r;
-}
 typedef __attribute__((address_space(3))) unsigned char wg_lds_byte;
-__device__ __forceinline__ wg_u32x2 wg_tr_read(wg_lds_byte* lds, u32 off) {   // ds_read_b64_tr_b16 at byte `off` of the workgroup's LDS array
+__device__ __forceinline__ u32x2 wg_tr_read(wg_lds_byte* lds, u32 off) {   // ds_read_b64_tr_b16 at byte `off` of the workgroup's LDS array
     const wg_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wg_s16x4*)(lds + off));
-    return __builtin_bit_cast(wg_u32x2, v);
+    return __builtin_bit_cast(u32x2, v);
 }
 
 // position tracker of one request piece: the lane's position advances by 64 per block
@@ -125,7 +106,7 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgParams p) {
     int nst = p.n_blocks - sa;
     nst = nst > p.blocks_per_split ? p.blocks_per_split : nst;          // blocks of this workgroup (may be <= 0: it then writes zeros)
 
-    const wg_i32x4 rx = wg_rsrc(p.x, p.x_bytes), rdy = wg_rsrc(p.dy, p.dy_bytes);
+    const i32x4 rx = tile_rsrc(p.x, p.x_bytes), rdy = tile_rsrc(p.dy, p.dy_bytes);
 
     // ---- request pieces: lane L of a piece fetches 16 bytes of position (block 64 + rg 16 + L / 4), channels sub 32 + (L & 3) 8 ----------
     const int xsub = wave & 1, xrg = wave >> 1;          // this wave's X piece of a block
@@ -174,15 +155,18 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgParams p) {
     int xslot = 0, dslot = 0;                            // ring slots of the NEXT X block / dY block to request
     auto req_x = [&]() {
         const u32 off = track_off(tx, p.Cin, xc);
-        wg_bload(off, rx, lds0 + XR + xsub * XSUB + (xslot * 64 + xrg * 16) * 64);
-        if (guard) wg_bload(xslot == 0 ? off : WG_OOB, rx, lds0 + (xslot == 0 ? XR + xsub * XSUB + (R + xrg * 16) * 64 : DUMP + wave * 1024));
+        // (wave_uniform: the destinations are uniform by construction, but an "s" operand does not get a readfirstlane by itself; ssdhip_tile.h)
+        tile_dma16(off, rx, wave_uniform(lds0 + XR + xsub * XSUB + (xslot * 64 + xrg * 16) * 64));
+        if (guard)
+            tile_dma16(xslot == 0 ? off : WG_OOB, rx, wave_uniform(lds0 + (xslot == 0 ? XR + xsub * XSUB + (R + xrg * 16) * 64 : DUMP + wave * 1024)));
         track_step(tx);
         xslot = xslot + 1 == RB ? 0 : xslot + 1;
     };
     auto req_dy = [&]() {
 #pragma unroll
         for (int u = 0; u < NDY; ++u) {
-            wg_bload(track_off(tdy[u], p.Cout, co0 + dsub[u] * 32 + (lane & 3) * 8), rdy, lds0 + DYB + dsub[u] * DSUB + (dslot * 64 + drg[u] * 16) * 64);
+            tile_dma16(track_off(tdy[u], p.Cout, co0 + dsub[u] * 32 + (lane & 3) * 8), rdy,
+                       wave_uniform(lds0 + DYB + dsub[u] * DSUB + (dslot * 64 + drg[u] * 16) * 64));
             track_step(tdy[u]);
         }
         dslot = (dslot + 1) & 3;
@@ -199,7 +183,7 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgParams p) {
     const u32 a_lane = (u32)(DYB + wm * 2 * DSUB) + lp * 64 + cbyte;          // + cb DSUB + (slot 64 + kk 16) 64 (+ 512 for the second read)
     const u32 x_lane = (u32)(XR + wn * XSUB) + lp * 64 + cbyte;               // + ring row 64 + kw 64 (+ 512)
 
-    wg_f32x16 acc[2][5];                                 // [32-channel block of the wave's 64 output channels][tap of the group]
+    f32x16 acc[2][5];                                 // [32-channel block of the wave's 64 output channels][tap of the group]
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -207,8 +191,8 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgParams p) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) acc[cb][t][v] = 0.f;
 
-    wg_u32x4 fa[2][2];                                   // [set][cb]: dY^T fragments (32 channels x 16 positions) of this K-step and the next
-    wg_u32x4 fx[5];                                      // X fragments of the group's taps: ONE set -- a tap's registers are refilled for
+    u32x4 fa[2][2];                                   // [set][cb]: dY^T fragments (32 channels x 16 positions) of this K-step and the next
+    u32x4 fx[5];                                      // X fragments of the group's taps: ONE set -- a tap's registers are refilled for
                                                          // the next K-step as soon as its two MFMAs have issued
     // ring row of position (64 (block) - W1 - 1) of the CURRENT block, i.e. of tap (0, 0) of the block's first position
     int ubase = 64 * p.HB - DIL * (W1 + 1);              // >= 0 because 64 HB >= DIL (W1 + 1)
@@ -219,8 +203,8 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgParams p) {
         if constexpr (ABL & 2) { asm volatile("" : "+v"(fa[S][0]), "+v"(fa[S][1]) : "v"(a0)); return; }
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
-            const wg_u32x2 lo = wg_tr_read(ldsp, a0 + cb * DSUB), hi = wg_tr_read(ldsp, a0 + cb * DSUB + 512);
-            fa[S][cb] = wg_u32x4{lo.x, lo.y, hi.x, hi.y};
+            const u32x2 lo = wg_tr_read(ldsp, a0 + cb * DSUB), hi = wg_tr_read(ldsp, a0 + cb * DSUB + 512);
+            fa[S][cb] = u32x4{lo.x, lo.y, hi.x, hi.y};
         }
     };
     // the address of filter row kh of K-step (ub, kk): the row's first ring row is wrapped in SCALAR arithmetic; the lanes' rows (+ lp <= 7,
@@ -232,8 +216,8 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgParams p) {
     };
     auto read_tap = [&](const int slot, const u32 a, const int kw) {
         if constexpr (ABL & 2) { asm volatile("" : "+v"(fx[slot]) : "v"(a)); return; }
-        const wg_u32x2 lo = wg_tr_read(ldsp, a + kw * DIL * 64), hi = wg_tr_read(ldsp, a + kw * DIL * 64 + 512);
-        fx[slot] = wg_u32x4{lo.x, lo.y, hi.x, hi.y};
+        const u32x2 lo = wg_tr_read(ldsp, a + kw * DIL * 64), hi = wg_tr_read(ldsp, a + kw * DIL * 64 + 512);
+        fx[slot] = u32x4{lo.x, lo.y, hi.x, hi.y};
     };
     auto mfma_tap = [&](auto setc, const int slot) {
         constexpr int S = decltype(setc)::value;
@@ -242,7 +226,7 @@ __global__ __launch_bounds__(WG_THREADS) void conv_wgrad_kernel(WgParams p) {
             if constexpr (ABL & 8) {                      // (keeps the operands alive: a VALU operation instead of the MFMA)
                 acc[cb][slot][0] = __uint_as_float(__float_as_uint(acc[cb][slot][0]) ^ (fx[slot].x & fx[slot].w & fa[S][cb].x & fa[S][cb].w & 1u));
             } else {
-                acc[cb][slot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wg_bf16x8, fa[S][cb]), __builtin_bit_cast(wg_bf16x8, fx[slot]),
+                acc[cb][slot] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[S][cb]), __builtin_bit_cast(bf16x8, fx[slot]),
                                                                         acc[cb][slot], 0, 0, 0);
             }
         }
@@ -409,14 +393,14 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(Wg1Params p) {
     const int s0 = split * p.steps_per_split, s1 = min(p.n_steps, s0 + p.steps_per_split);
     const int cg = tid & 15, pp0 = tid >> 4;                 // 8 channels x the pixel pairs pp0 and pp0 + 16
     const int cohalf = wave & 1, cihalf = wave >> 1;
-    wg_f32x16 acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
-    wg_u32x4 ra[4], rb[4];                                   // [unit u][pixel e]: unit u = pair pp0 + 16 u
+    u32x4 ra[4], rb[4];                                   // [unit u][pixel e]: unit u = pair pp0 + 16 u
     auto request = [&](int step) {
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -424,8 +408,8 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(Wg1Params p) {
             for (int e = 0; e < 2; ++e) {
                 const long long px = (long long)step * 64 + 2 * (pp0 + 16 * u) + e;
                 const bool ok = px < p.P;
-                ra[2 * u + e] = ok ? *reinterpret_cast<const wg_u32x4*>(p.dy + px * p.Cout + co0 + cg * 8) : wg_u32x4{0u, 0u, 0u, 0u};
-                rb[2 * u + e] = ok ? *reinterpret_cast<const wg_u32x4*>(p.x + px * p.Cin + ci0 + cg * 8) : wg_u32x4{0u, 0u, 0u, 0u};
+                ra[2 * u + e] = ok ? *reinterpret_cast<const u32x4*>(p.dy + px * p.Cout + co0 + cg * 8) : u32x4{0u, 0u, 0u, 0u};
+                rb[2 * u + e] = ok ? *reinterpret_cast<const u32x4*>(p.x + px * p.Cin + ci0 + cg * 8) : u32x4{0u, 0u, 0u, 0u};
             }
     };
     auto stage = [&]() {
@@ -453,12 +437,12 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_kernel(Wg1Params p) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int chunk = 2 * ks + (lane >> 5);           // pixels 8 chunk .. + 7
-            wg_bf16x8 fa[2], fb[2];
+            bf16x8 fa[2], fb[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int ra_ = cohalf * 64 + i * 32 + (lane & 31), rb_ = cihalf * 64 + i * 32 + (lane & 31);
-                fa[i] = *reinterpret_cast<const wg_bf16x8*>(aT + ra_ * WG1_PITCH + ((chunk ^ ((ra_ >> 3) & 7)) << 4));
-                fb[i] = *reinterpret_cast<const wg_bf16x8*>(bT + rb_ * WG1_PITCH + ((chunk ^ ((rb_ >> 3) & 7)) << 4));
+                fa[i] = *reinterpret_cast<const bf16x8*>(aT + ra_ * WG1_PITCH + ((chunk ^ ((ra_ >> 3) & 7)) << 4));
+                fb[i] = *reinterpret_cast<const bf16x8*>(bT + rb_ * WG1_PITCH + ((chunk ^ ((rb_ >> 3) & 7)) << 4));
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -512,7 +496,7 @@ __global__ __launch_bounds__(256) void conv_taps_wgrad_kernel(WgTParams p) {
     const int s0 = split * p.steps_per_split, s1 = min(p.n_steps, s0 + p.steps_per_split);
     const int cg = tid & 15, pp0 = tid >> 4;
     const int cohalf = wave & 1, cihalf = wave >> 1;
-    wg_f32x16 acc[3][2][2];
+    f32x16 acc[3][2][2];
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -521,7 +505,7 @@ __global__ __launch_bounds__(256) void conv_taps_wgrad_kernel(WgTParams p) {
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[t][i][j][v] = 0.f;
-    wg_u32x4 ra[4], rb[3][4];
+    u32x4 ra[4], rb[3][4];
     const u32 howo = (u32)(p.Ho * p.Wo);
     auto request = [&](int step) {
 #pragma unroll
@@ -531,15 +515,15 @@ __global__ __launch_bounds__(256) void conv_taps_wgrad_kernel(WgTParams p) {
                 const u32 px = (u32)step * 64u + 2u * (u32)(pp0 + 16 * u) + (u32)e;
                 const bool ok = px < (u32)p.P;
                 const u32 b = px / howo, r = px - b * howo, ho = r / (u32)p.Wo, wo = r - ho * (u32)p.Wo;
-                ra[2 * u + e] = ok ? *reinterpret_cast<const wg_u32x4*>(p.dy + (size_t)px * p.Cout + co0 + cg * 8) : wg_u32x4{0u, 0u, 0u, 0u};
+                ra[2 * u + e] = ok ? *reinterpret_cast<const u32x4*>(p.dy + (size_t)px * p.Cout + co0 + cg * 8) : u32x4{0u, 0u, 0u, 0u};
                 const int hi = (int)ho * p.stride + kh * p.dil - p.pad;
                 const bool okh = ok && hi >= 0 && hi < p.H;
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
                     const int wi = (int)wo * p.stride + t * p.dil - p.pad;
                     const bool okx = okh && wi >= 0 && wi < p.W;
-                    rb[t][2 * u + e] = okx ? *reinterpret_cast<const wg_u32x4*>(p.x + (((size_t)b * p.H + hi) * p.W + wi) * p.Cin + ci0 + cg * 8)
-                                           : wg_u32x4{0u, 0u, 0u, 0u};
+                    rb[t][2 * u + e] = okx ? *reinterpret_cast<const u32x4*>(p.x + (((size_t)b * p.H + hi) * p.W + wi) * p.Cin + ci0 + cg * 8)
+                                           : u32x4{0u, 0u, 0u, 0u};
                 }
             }
     };
@@ -570,19 +554,19 @@ __global__ __launch_bounds__(256) void conv_taps_wgrad_kernel(WgTParams p) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int chunk = 2 * ks + (lane >> 5);
-            wg_bf16x8 fa[2];
+            bf16x8 fa[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int ra_ = cohalf * 64 + i * 32 + (lane & 31);
-                fa[i] = *reinterpret_cast<const wg_bf16x8*>(aT + ra_ * WG1_PITCH + ((chunk ^ ((ra_ >> 3) & 7)) << 4));
+                fa[i] = *reinterpret_cast<const bf16x8*>(aT + ra_ * WG1_PITCH + ((chunk ^ ((ra_ >> 3) & 7)) << 4));
             }
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                wg_bf16x8 fb[2];
+                bf16x8 fb[2];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int rb_ = cihalf * 64 + j * 32 + (lane & 31);
-                    fb[j] = *reinterpret_cast<const wg_bf16x8*>(bT[t] + rb_ * WG1_PITCH + ((chunk ^ ((rb_ >> 3) & 7)) << 4));
+                    fb[j] = *reinterpret_cast<const bf16x8*>(bT[t] + rb_ * WG1_PITCH + ((chunk ^ ((rb_ >> 3) & 7)) << 4));
                 }
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
