@@ -1,17 +1,15 @@
 """Shared machinery of the SSD model builders (reference models/keras_ssd300.py:200-457 and twins).
 
 The convolutional stack of a bf16 model runs on libssdhip's MFMA kernels (csrc/ssdhip_convh / conv64 / conv /
-convimg / chain .hip), dispatched here per layer shape (`SSDModel._pick`), with the graph glue in
-csrc/ssdhip_layers.hip and, for training, autograd functions over the same kernels (+ csrc/ssdhip_wgrad /
-ssdhip_train .hip); the framework's own convolution (MIOpen) only runs float32 models and the few layer
+convimg / chain .hip), dispatched here per layer shape (`SSDModel._pick` over the candidates `_conv_select` lists), with the graph glue in
+csrc/ssdhip_layers.hip and, for training, the autograd functions of `_train_fns` over the same kernels (+ csrc/ssdhip_wgrad /
+ssdhip_train .hip) and the bf16 weight copies of `_shadow`; the framework's own convolution (MIOpen) only runs float32 models and the few layer
 geometries no kernel here covers.  Around it this module adds what the reference's graph does: in-graph input
 normalisation, NHWC-ordered head reshapes so the anchor axis factorises exactly like Keras'
 `Reshape((-1, n_classes))`, the resident anchor constant, softmax, the `(B, N, C+12)` prediction layout and the
 optional decode layer.
 """
 from __future__ import annotations
-
-import os
 
 import numpy as np
 import torch
@@ -20,11 +18,17 @@ import torch.nn.functional as F
 
 from .. import _native as nat
 from ..anchor_math import n_boxes_for
-from ..optimizers import _bump_versions
 from ..keras_layers.keras_layer_AnchorBoxes import AnchorBoxes
 from ..keras_layers.keras_layer_DecodeDetections import DecodeDetections
 from ..keras_layers.keras_layer_DecodeDetectionsFast import DecodeDetectionsFast
 from ..keras_layers.keras_layer_L2Normalization import L2Normalization
+from . import _conv_select as sel
+from . import _shadow
+from ._graphed import GraphedInference
+from ._heads import PredictorHeads
+from ._train_fns import (_AssembleTrainFn, _ConvBiasActFn, _ConvBiasActPoolFn, _MaxPoolFn, _PackedHeadFn, _ReluLink,  # noqa: F401
+                         _conv_input_weight_grads)
+
 
 
 def conv_out(n, k, s=1, p=0, d=1):
@@ -80,380 +84,7 @@ def resolve_anchor_config(n_predictor_layers, min_scale, max_scale, scales, aspe
     return list(scales), ars, n_boxes, steps, offsets
 
 
-class _ReluLink:
-    """Training step, two ReLU convolutions in a row where the upper one is the lower one's ONLY consumer (conv2_1 -> conv2_2, conv3_1 ->
-    conv3_2 -> conv3_3, conv4_1 -> conv4_2 -> conv4_3): the upper layer's data gradient can leave its kernel already masked by its
-    input > 0 -- which is the lower layer's threshold_backward -- so the lower layer skips its pass over (dL/dy, y).  The link is how the
-    two autograd nodes agree: the upper node's backward sets `masked` only when its kernel really applied the mask, the lower node's
-    backward (which autograd runs after it) consumes the flag and falls back to its own mask otherwise."""
-    __slots__ = ("masked", "partial")
-
-    def __init__(self):
-        self.masked = False
-        self.partial = None      # the masked gradient's channel sums by workgroup ([rows, C] float32): the lower layer's bias-gradient partials
-
-
-class _ConvBiasActFn(torch.autograd.Function):
-    """A convolution layer of the TRAINING step with libssdhip's MFMA kernel in the forward pass (convolution + bias + ReLU, one
-    kernel, bf16 NHWC -- the same kernels the inference path runs) and libssdhip's data / weight gradients behind it
-    (`_conv_input_weight_grads`: since round 6 every layer of SSD300 / SSD512 except a 4 x 4 or grouped convolution; the framework's
-    convolution_backward is the fallback for what the kernels do not cover).  `run` is the libssdhip thunk picked for this layer
-    shape: (x_bf16, w_bf16, b_bf16) -> y."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, run, stride, padding, dilation, relu, wb=None, bb=None, wt=None, link_in=None, link_out=None):
-        xb = x.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        if wb is None:                                   # no bf16 shadow of the parameters at hand: cast here
-            wb = weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-            bb = bias.detach().to(torch.bfloat16) if bias is not None else None
-        y = run(xb, wb, bb)
-        # (wt: the data gradient's filters, built with the shadows -- None: built in backward; saved like the others so that autograd's
-        #  version check covers it when the shadows are refreshed between this forward and its backward)
-        ctx.save_for_backward(xb, wb, y if relu else None, wt)
-        ctx.conf = (stride, padding, dilation, relu, weight.dtype, None if bias is None else bias.dtype, x.dtype)
-        # link_in: x is the ReLU output of a layer that feeds nothing else (_ReluLink); link_out: the same towards this layer's consumer
-        ctx.links = (link_in, link_out if relu else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        xb, wb, y, wt = ctx.saved_tensors
-        stride, padding, dilation, relu, wdt, bdt, xdt = ctx.conf
-        gy = gy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        want_gb = bdt is not None and ctx.needs_input_grad[2]
-        partial = None
-        import os
-        if (relu and not ctx.needs_input_grad[0] and gy.is_cuda and tuple(wb.shape) == (64, 3, 3, 3) and stride == (1, 1)
-                and padding == (1, 1) and dilation == (1, 1) and os.environ.get("SSDHIP_NO_CONV1_1_BWD", "0") != "1"):
-            # the first layer: no data gradient, so the masked gradient is only ever summed -- ReLU mask, bias gradient and weight gradient
-            # in ONE pass that writes nothing but partial sums (csrc/ssdhip_train.hip, conv1_1_bwd_kernel)
-            gw, gb = nat.conv1_1_backward(gy, y, xb)
-            return None, gw.to(wdt), (gb.to(bdt) if want_gb else None), None, None, None, None, None, None, None, None, None, None
-        link_in, link_out = ctx.links
-        if relu:
-            premasked = link_out is not None and link_out.masked
-            if link_out is not None:
-                partial, link_out.partial = link_out.partial, None
-                link_out.masked = False                  # consumed: the consumer's next backward sets it again
-            fused = None
-            if premasked:
-                # dL/dy arrived masked by y > 0 from the consumer's data-gradient kernel (_ReluLink), its channel sums beside it
-                if want_gb and partial is None:
-                    partial = nat.channel_sums_partial(gy)
-            else:
-                # ReLU mask and the per-workgroup channel sums of the bias gradient in ONE libssdhip pass (csrc/ssdhip_train.hip); the rows
-                # are added by the weight gradient's reduction launch where that is ours, by one framework reduction otherwise
-                fused = nat.relu_bwd_bias(gy, y, reduce=False)
-                if fused is not None:
-                    gy, partial = fused
-                else:
-                    gy = torch.ops.aten.threshold_backward(gy, y, 0)
-        gx, gw, gb = _conv_input_weight_grads(gy, xb, wb, stride, padding, dilation, ctx.needs_input_grad[0], wt,
-                                              partial if want_gb else None, link_in)
-        if want_gb:
-            if gb is None:
-                gb = nat.row_sums(partial) if partial is not None else gy.sum(dim=(0, 2, 3), dtype=torch.float32)
-            gb = gb.to(bdt)
-        else:
-            gb = None
-        return (gx.to(xdt) if gx is not None else None), gw.to(wdt), gb, None, None, None, None, None, None, None, None, None, None
-
-
-def _conv_input_weight_grads(gy, xb, wb, stride, padding, dilation, need_x, wt=None, bias_partial=None, link_in=None):
-    """dL/dx, dL/dw [and dL/db] of a convolution from the (masked) dL/dy.  Data gradient: a stride-1 'same' layer through the forward's
-    MFMA kernel on the transposed, tap-flipped filters; a strided or 'valid' 3 x 3 layer the same way behind an embedding launch (round
-    6).  Weight gradient: the position-grid kernel (3 x 3 'same', incl. fc6's dilation 6), the pixel GEMM (1 x 1), the tap-gathered pixel
-    GEMM (any other 3 x 3) -- csrc/ssdhip_wgrad.hip.  What none of them covers goes to aten.convolution_backward (MIOpen).
-    bias_partial: per-workgroup channel sums of gy ([rows, Cout] float32); the third result is their ordered sum when the weight
-    gradient's reduction launch could add them on the side, None otherwise (the caller reduces them itself).
-    link_in (_ReluLink): xb is the ReLU output of a layer that feeds nothing else -- where the slab kernel runs the data gradient it
-    writes dL/dx masked by xb > 0 and sets the link (the layer below then skips its own mask pass)."""
-    gx = None
-    k = wb.shape[2]
-    same = (stride == (1, 1) and k % 2 == 1 and padding == (dilation[0] * (k // 2),) * 2 and dilation[0] == dilation[1]
-            and wb.shape[0] % 64 == 0 and wb.shape[1] % 64 == 0 and k in (1, 3))
-    import os
-    own_taps = os.environ.get("SSDHIP_NO_TAPS_BWD", "0") != "1"
-    # (round 6) a strided or 'valid' 3 x 3 layer (conv6_2 / conv7_2: stride 2 behind ZeroPadding2D; conv8_2 / conv9_2: no padding):
-    # dX[r] = sum_k dY[(r + pad - k) / s] w[k] is the 3 x 3 'same' convolution of Z -- zeros with dY at (1 - pad + s i) -- with the same
-    # transposed, tap-flipped filters: one embedding launch (csrc/ssdhip_train.hip), then the branch below as for a 'same' layer
-    embedded = (need_x and not same and own_taps and k == 3 and dilation == (1, 1) and stride[0] == stride[1] and padding[0] == padding[1]
-                and padding[0] in (0, 1) and wb.shape[0] % 64 == 0 and wb.shape[1] % 64 == 0 and gy.is_cuda
-                and os.environ.get("SSDHIP_NO_OWN_DGRAD", "0") != "1")
-    if embedded:
-        gy_full, gy = gy, nat.embed_strided(gy, xb.shape[2], xb.shape[3], stride[0], 1 - padding[0])
-    if need_x and (same or embedded) and os.environ.get("SSDHIP_NO_OWN_DGRAD", "0") != "1":
-        # the data gradient of a stride-1 'same' convolution IS a 'same' convolution of dL/dy with the filters transposed
-        # (Cin <-> Cout) and their taps flipped: the forward's MFMA kernel runs it, no bias, no activation
-        if wt is None:                                   # (the shadow set hands the transposed filters over: csrc/ssdhip_optim.hip)
-            wt = wb.flip(2, 3).permute(1, 0, 2, 3).contiguous(memory_format=torch.channels_last)
-        # (the deep 3x3 layers through the slab kernel, csrc/ssdhip_convh.hip: bit-identical and faster, r02o)
-        halo = (k == 3 and dilation[0] == 1 and wt.shape[0] % 128 == 0 and wt.shape[1] % 128 == 0
-                and os.environ.get("SSDHIP_NO_HALO", "0") != "1")
-        # (small maps -- conv5_x, fc6 with its dilation -- through the image-resident kernel, csrc/ssdhip_convimg.hip, where it fills the chip)
-        image = (k == 3 and gy.shape[2] * gy.shape[3] <= 384 and gy.shape[0] * (wt.shape[0] // 64) >= 128
-                 and nat.conv3x3_image_supported(gy, wt, dilation[0]) and os.environ.get("SSDHIP_NO_IMAGE", "0") != "1")
-        # (a 64-channel dL/dy -- conv1_2 -- through the resident-filter kernel of the Cin = 64 layers, csrc/ssdhip_conv64.hip: the same bits as
-        #  the implicit-GEMM kernel in half its time, 430 -> 215 us at 300 x 300 / batch 32)
-        c64 = (k == 3 and dilation[0] == 1 and wt.shape[1] == 64 and wt.shape[0] % 64 == 0 and os.environ.get("SSDHIP_NO_C64_DGRAD", "0") != "1")
-        # (round 6: the 1 x 1 layers on small maps -- fc7, conv6_1 -- through the same kernel's one-step-per-slice form)
-        image1 = (k == 1 and gy.shape[2] * gy.shape[3] <= 384 and gy.shape[0] * (wt.shape[0] // 64) >= 128
-                  and nat.conv2d_image_supported(gy, wt) and os.environ.get("SSDHIP_IMAGE2", "1") != "0"
-                  and os.environ.get("SSDHIP_NO_IMAGE", "0") != "1")
-        masked = None
-        if (link_in is not None and halo and same and not image and gy.dtype == torch.bfloat16 and xb.dtype == torch.bfloat16
-                and os.environ.get("SSDHIP_NO_MASKED_DGRAD", "0") != "1"):
-            masked = nat.conv3x3_halo_masked(gy, wt, xb, sums=os.environ.get("SSDHIP_NO_MASKED_SUMS", "0") != "1")
-        if masked is not None:
-            gx, link_in.partial = masked if isinstance(masked, tuple) else (masked, None)
-            link_in.masked = True
-        elif image:
-            gx = nat.conv3x3_image(gy, wt, None, dilation=dilation[0], relu=False)
-        elif image1:
-            gx = nat.conv2d_image(gy, wt, None, relu=False)
-        elif c64:
-            gx = nat.conv3x3_c64(gy, wt, None, relu=False, pool=False)
-        else:
-            gx = nat.conv2d_same(gy, wt, None, dilation=dilation[0], relu=False, variant=7 if halo else None)
-    if embedded:
-        gy = gy_full
-    gw, gb = None, None
-    if (k == 3 and stride == (1, 1) and padding == (1, 1) and dilation == (1, 1) and os.environ.get("SSDHIP_NO_OWN_WGRAD", "0") != "1"):
-        # the weight gradient through libssdhip's MFMA kernel (csrc/ssdhip_wgrad.hip; float32, fixed summation order); None: geometry
-        # not covered (3 input channels, predictor heads whose channel counts are not multiples of 64)
-        if xb.shape[1] % 64 == 0 and gy.shape[1] % 64 == 0:
-            got = nat.conv3x3_wgrad(xb, gy, bias_partial=bias_partial)
-            if got is not None and bias_partial is not None:
-                gw, gb = got
-            else:
-                gw = got
-    if (gw is None and k == 1 and stride == (1, 1) and padding == (0, 0) and gy.is_cuda and xb.shape[1] % 128 == 0 and gy.shape[1] % 128 == 0
-            and os.environ.get("SSDHIP_NO_OWN_WGRAD", "0") != "1"):
-        # the 1 x 1 layers (fc7, conv6_1 ... conv9_1): the weight gradient is a GEMM over the pixels (csrc/ssdhip_wgrad.hip,
-        # conv1x1_wgrad_kernel; float32, fixed summation order), the bias partials ride in its reduction launch
-        got = nat.conv1x1_wgrad(xb, gy, bias_partial=bias_partial)
-        if got is not None and bias_partial is not None:
-            gw, gb = got
-        else:
-            gw = got
-    if (gw is None and k == 3 and own_taps and gy.is_cuda and stride[0] == stride[1] and padding[0] == padding[1] and dilation[0] == dilation[1]
-            and xb.shape[1] % 128 == 0 and gy.shape[1] % 128 == 0 and os.environ.get("SSDHIP_NO_OWN_WGRAD", "0") != "1"):
-        # (round 6) the other 3 x 3 layers -- fc6's dilation, the strided and the 'valid' extras -- through the tap-gathered pixel GEMM
-        # (csrc/ssdhip_wgrad.hip, conv_taps_wgrad_kernel): with it the training step holds no framework convolution
-        got = nat.conv3x3_taps_wgrad(xb, gy, stride[0], padding[0], dilation[0], bias_partial=bias_partial)
-        if got is not None and bias_partial is not None:
-            gw, gb = got
-        else:
-            gw = got
-    masks = [need_x and gx is None, gw is None, False]
-    if masks[0] or masks[1]:
-        gx_m, gw_m, _ = torch.ops.aten.convolution_backward(gy, xb, wb, None, list(stride), list(padding), list(dilation), False, [0, 0],
-                                                            1, masks)
-        if gx is None and need_x:
-            gx = gx_m
-        if gw is None:
-            gw = gw_m
-    return gx, gw, gb
-
-
-class _ConvBiasActPoolFn(torch.autograd.Function):
-    """Conv2D(relu) -> MaxPooling2D(2, 2, 'same') of the TRAINING step (pool1 .. pool3) as one autograd node: forward = the layer's
-    MFMA kernel + the one-pass pooling kernel (conv1_2 -> pool1: ONE launch that writes both maps, round 6); backward = max-pool gradient, ReLU mask and bias gradient in ONE pass over the
-    full-resolution map (csrc/ssdhip_train.hip, maxpool2_relu_bwd_bias_kernel) -- the unmasked full-resolution gradient is never
-    written -- then the convolution's gradients as in _ConvBiasActFn."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, run, stride, padding, dilation, wb=None, bb=None, wt=None, link_in=None):
-        xb = x.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        if wb is None:
-            wb = weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-            bb = bias.detach().to(torch.bfloat16) if bias is not None else None
-        ctx.link_in = link_in
-        import os
-        if (xb.shape[1] == 64 and wb.shape[2:] == (3, 3) and stride == (1, 1) and padding == (1, 1) and dilation == (1, 1)
-                and wb.shape[0] % 64 == 0 and xb.is_cuda and os.environ.get("SSDHIP_NO_POOL_KEEP", "0") != "1"):
-            # round 6: conv1_2 -> pool1 as ONE launch that writes the activation AND the pooled map (csrc/ssdhip_conv64.hip, KEEP): the
-            # pooling pass read the 368 MB map back (~95 us of the step)
-            y, p = nat.conv3x3_c64_pool_keep(xb, wb, bb, relu=True)
-        else:
-            # fourth session: conv2_2 -> pool2 and conv3_3 -> pool3 the same way on the slab kernel (csrc/ssdhip_convh.hip, KEEP)
-            kept = None
-            if (xb.shape[1] % 128 == 0 and wb.shape[0] % 128 == 0 and wb.shape[2:] == (3, 3) and stride == (1, 1) and padding == (1, 1)
-                    and dilation == (1, 1) and xb.is_cuda and os.environ.get("SSDHIP_NO_POOL_KEEP", "0") != "1"
-                    and os.environ.get("SSDHIP_NO_HALO", "0") != "1" and os.environ.get("SSDHIP_NO_HALO_POOL_KEEP", "0") != "1"):
-                kept = nat.conv3x3_halo_pool_keep(xb, wb, bb, relu=True)
-            if kept is not None:
-                y, p = kept
-            else:
-                y = run(xb, wb, bb)
-                p = nat.bias_act_maxpool(y, None, 2, 2, 0, True, relu=False)
-        ctx.save_for_backward(xb, wb, y, wt)
-        ctx.conf = (stride, padding, dilation, weight.dtype, None if bias is None else bias.dtype, x.dtype)
-        return p
-
-    @staticmethod
-    def backward(ctx, gp):
-        xb, wb, y, wt = ctx.saved_tensors
-        stride, padding, dilation, wdt, bdt, xdt = ctx.conf
-        gp = gp.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        fused = nat.maxpool2_relu_bwd_bias(y, gp, reduce=False)
-        if fused is None:
-            raise RuntimeError("channel count not supported by the fused pooling backward (the forward checks it)")
-        gy, partial = fused
-        want_gb = bdt is not None and ctx.needs_input_grad[2]
-        gx, gw, gb = _conv_input_weight_grads(gy, xb, wb, stride, padding, dilation, ctx.needs_input_grad[0], wt,
-                                              partial if want_gb else None, ctx.link_in)
-        if want_gb:
-            gb = (gb if gb is not None else nat.row_sums(partial)).to(bdt)
-        else:
-            gb = None
-        return (gx.to(xdt) if gx is not None else None), gw.to(wdt), gb, None, None, None, None, None, None, None, None
-
-
-class _PackedHeadFn(torch.autograd.Function):
-    """The two predictor heads of one source map in the TRAINING step as one libssdhip node (round 4): conf and loc filters packed along
-    Cout (zero rows up to a multiple of 128), forward = the slab kernel (no activation), data gradient = the slab kernel on the flipped /
-    transposed pack, weight gradient = ssdhip_conv3x3_wgrad on the packed gradient, bias gradient = one reduction -- instead of two
-    framework convolutions forward and four backward per map (MIOpen: 1.7 ms of a 12.7 ms step, profiles/r04za).  Returns the packed
-    (B, Cp, H, W) bf16 map; the caller slices conf / loc out of it (reference: models/keras_ssd300.py:322-335)."""
-
-    @staticmethod
-    def forward(ctx, x, wc, bc, wl, bl, pw, pb, pwt):
-        """pw / pb / pwt: the packed bf16 filters [conf | loc | zero rows], biases and transposed / flipped filters of this source map,
-        kept up to date with the parameters by the model's shadow set (SSDModel._packed_head_shadow): nothing is concatenated here."""
-        xb = x.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        y = nat.conv3x3_halo(xb, pw, pb, relu=False, pool=False)
-        ctx.save_for_backward(xb, pw, pwt)
-        ctx.conf = (wc.shape[0], wl.shape[0], wc.dtype, bc.dtype, x.dtype)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        xb, w, wt = ctx.saved_tensors
-        nc, nl, wdt, bdt, xdt = ctx.conf
-        gyb = gy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = nat.conv2d_same(gyb, wt, None, dilation=1, relu=False, variant=7).to(xdt)
-        partial = nat.channel_sums_partial(gyb)              # per-workgroup channel sums; the weight gradient's reduction launch adds them
-        got = nat.conv3x3_wgrad(xb, gyb, bias_partial=partial)
-        if got is None:
-            raise RuntimeError("packed predictor head: weight-gradient geometry not covered")
-        gw, gb = got if partial is not None else (got, gyb.float().sum(dim=(0, 2, 3)))
-        return (gx, gw[:nc].to(wdt), gb[:nc].to(bdt), gw[nc:nc + nl].to(wdt), gb[nc:nc + nl].to(bdt), None, None, None)
-
-
-class _AssembleTrainFn(torch.autograd.Function):
-    """Reshape + Concatenate + softmax + AnchorBoxes + Concatenate of the TRAINING step (models/keras_ssd300.py:363-419) as one autograd
-    node over the packed head maps: forward = ssdhip_assemble_predictions_strided_bf16 (the inference path's one-launch assembly),
-    backward = ssdhip_assemble_predictions_backward_bf16 (softmax backward and the scatter into the packed layout, one launch) --
-    instead of six slices, three concatenations, a softmax and an index_select forward and their ~15 kernels backward."""
-
-    @staticmethod
-    def forward(ctx, anchors, n_classes, n_boxes, *ys):
-        pred = nat.assemble_predictions([y.detach() for y in ys], [None] * len(ys), [None] * len(ys), [None] * len(ys), list(n_boxes),
-                                        anchors, n_classes)
-        ctx.save_for_backward(pred)
-        ctx.conf = (n_classes, tuple(n_boxes), tuple(tuple(y.shape) for y in ys))
-        return pred
-
-    @staticmethod
-    def backward(ctx, g):
-        (pred,) = ctx.saved_tensors
-        n_classes, n_boxes, shapes = ctx.conf
-        grads = nat.assemble_predictions_backward(g.float(), pred, shapes, n_boxes, n_classes)
-        return (None, None, None) + tuple(grads)
-
-
-class _MaxPoolFn(torch.autograd.Function):
-    """max_pool2d of a bf16 NHWC map in the training step: libssdhip forward (one pass) and backward (gather, deterministic)."""
-
-    @staticmethod
-    def forward(ctx, x, kernel, stride, pad, ceil_mode):
-        y = nat.bias_act_maxpool(x, None, kernel, stride, pad, ceil_mode, relu=False)
-        ctx.save_for_backward(x)
-        ctx.conf = (kernel, stride, pad)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        kernel, stride, pad = ctx.conf
-        return nat.maxpool_bwd(x, gy.to(torch.bfloat16), kernel, stride, pad), None, None, None, None
-
-
-class GraphedInference:
-    """`model(images)` (forward + DecodeDetections) of a fixed input shape as a HIP graph.
-
-    The graph reads the tensor handed to the constructor (`static_in`) and writes `static_out`: calling the object with another
-    tensor copies it into `static_in` first (one device copy); the returned tensor is overwritten by the next call.  Capture happens
-    after `warmup` eager steps on the capture stream, so the per-shape kernel autotune, the workspaces and the side stream of the
-    predictor heads exist before anything is recorded (allocations, host -> device copies and timing syncs are illegal inside a
-    capture).  Inference only (no_grad)."""
-
-    def __init__(self, model, images, warmup=3, fn=None):
-        if not images.is_cuda:
-            raise ValueError("HIP graphs need a CUDA/HIP tensor")
-        run = fn if fn is not None else model            # fn: another callable of the model on the same input (model.head_outputs)
-        self.model = model
-        self.static_in = images
-        dev = images.device
-        self.stream = torch.cuda.Stream(device=dev)
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
-        had = model.__dict__.get("_head_overlap")
-        model.__dict__["_head_overlap"] = os.environ.get("SSDHIP_GRAPH_HEAD_OVERLAP", "4")   # two streams inside the graph: explicit dependencies, no allocator subtleties
-        try:
-            with torch.cuda.stream(self.stream), torch.no_grad():
-                for _ in range(max(1, warmup)):
-                    run(self.static_in)
-            torch.cuda.current_stream(dev).wait_stream(self.stream)
-            torch.cuda.synchronize(dev)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="relaxed"):
-                self.static_out = run(self.static_in)
-        finally:
-            model.__dict__["_head_overlap"] = had
-        # (see __call__: an OLDER graph of a model must not be replayed on a foreign stream once a newer one exists)
-        self._epoch = model.__dict__.get("_graph_epoch", 0) + 1
-        model.__dict__["_graph_epoch"] = self._epoch
-
-        # What the recorded kernels read besides `static_in`: the parameters' own storage (in-place updates -- optimizer steps,
-        # load_state_dict, load_keras_weights -- are seen by the next replay) and the PACKED head filters, separate tensors built from
-        # the conf / loc weights, and the other tensors DERIVED from parameters (the fragment-packed conv7_1 ... conv9_2 filters of
-        # SSD300's one-launch tail, the float32 copy of L2Normalization's gamma in a bf16 model): all of them are refreshed in place
-        # when the parameter they come from changed (`_refresh_derived_weights`, keyed on `_derived_weights_key`).  A parameter
-        # whose storage was REPLACED (`conv.weight = nn.Parameter(...)`, `param.data = t`) is something the graph cannot follow.
-        self._param_ptrs = tuple(p.data_ptr() for p in model.parameters())
-        self._derived_key = model._derived_weights_key()
-
-    def __call__(self, images=None):
-        if images is not None and images.data_ptr() != self.static_in.data_ptr():
-            if tuple(images.shape) != tuple(self.static_in.shape) or images.dtype != self.static_in.dtype:
-                raise ValueError("this graph was captured for images of shape %s / %s, got %s / %s" % (
-                    tuple(self.static_in.shape), self.static_in.dtype, tuple(images.shape), images.dtype))
-            self.static_in.copy_(images, non_blocking=True)
-        if tuple(p.data_ptr() for p in self.model.parameters()) != self._param_ptrs:
-            raise RuntimeError("a parameter's storage was replaced after the graph was captured: call model.graphed(...) again")
-        key = self.model._derived_weights_key()
-        if key != self._derived_key:
-            self.model._refresh_derived_weights()
-            self._derived_key = key
-        cur = torch.cuda.current_stream(self.static_in.device)
-        if self.model.__dict__.get("_graph_epoch", 0) != self._epoch and cur.cuda_stream != self.stream.cuda_stream:
-            # Another graph of this model was captured after this one.  On ROCm 7.2 replaying the OLDER of two such graphs on a stream
-            # other than its capture stream segfaults inside hipGraphLaunch (tools/debug_two_graphs.py: 2 graphs + foreign stream
-            # crashes, 1 graph or the capture stream does not; profiles/r06zq_two_steps_in_flight_negative.txt) -- so it is replayed
-            # on its capture stream, ordered behind and in front of the caller's stream.
-            self.stream.wait_stream(cur)
-            with torch.cuda.stream(self.stream):
-                self.graph.replay()
-            cur.wait_stream(self.stream)
-            return self.static_out
-        self.graph.replay()
-        return self.static_out
-
-
-class SSDModel(nn.Module):
+class SSDModel(PredictorHeads, nn.Module):
     """Base class: subclasses define `features(x) -> list of predictor feature maps` plus
     `conf_heads`, `loc_heads` (ModuleLists) and `priorboxes` (ModuleList of AnchorBoxes)."""
 
@@ -497,74 +128,12 @@ class SSDModel(nn.Module):
     # igemm, miopen.
     _conv_choice = {}
 
-    @staticmethod
-    def _igemm_ok(conv, x):
-        k = conv.kernel_size[0]
-        return (k in (1, 3) and conv.kernel_size[1] == k and conv.stride == (1, 1) and conv.groups == 1
-                and conv.dilation[0] == conv.dilation[1] and conv.padding == (conv.dilation[0] * (k // 2),) * 2
-                and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and conv.bias is not None)
-
-    @staticmethod
-    def _igemm_general_ok(conv, x):
-        """Strided / partially padded 3x3 and 1x1 layers (conv6_2 ... conv9_2) for nat.conv2d."""
-        k = conv.kernel_size[0]
-        return (k in (1, 3) and conv.kernel_size[1] == k and conv.stride[0] == conv.stride[1] and 1 <= conv.stride[0] <= 4
-                and conv.groups == 1 and conv.dilation[0] == conv.dilation[1] and isinstance(conv.padding, tuple)
-                and conv.padding[0] == conv.padding[1] and 0 <= conv.padding[0] <= conv.dilation[0] * (k // 2)
-                and conv.padding_mode == 'zeros' and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
-                and conv.bias is not None)
-
-    @staticmethod
-    def _few_tiles(m_pixels, cout):
-        """Fewer 128 x 128 output tiles than a third of the CUs: the layer's one-pass kernels leave most of the chip idle while a few
-        workgroups walk their whole K loop (the SSD extra layers behind fc7)."""
-        return -(-m_pixels // 128) * -(-cout // 128) <= 100
-
-    @staticmethod
-    def _splitk_measured_regime(x):
-        """Where the split-K form was measured inside the graphed step (profiles/r03p_*: the SSD300 / SSD512 extra layers behind fc7 at
-        batch 32: maps of at most 19 x 19 ... 32 x 32 pixels, a batch that fills the K ranges): only there is it taken without a timing
-        run.  Everywhere else (small batches, where `_few_tiles` also covers conv3_x ... fc7) it is an ordinary autotune candidate."""
-        return x.shape[0] >= 16 and x.shape[2] * x.shape[3] <= 32 * 32
-
-    @staticmethod
-    def _halo_ok(conv, x):
-        """csrc/ssdhip_convh.hip: 3x3, dilation 1, Cin and Cout multiples of 128 (maps up to 94 wide on the padded position grid,
-        wider ones and the pooled form on 2-D tiles)."""
-        import os
-        return (conv.kernel_size == (3, 3) and conv.dilation == (1, 1) and conv.in_channels % 128 == 0
-                and conv.out_channels % 128 == 0 and os.environ.get("SSDHIP_NO_HALO", "0") != "1")
-
-    @staticmethod
-    def _image_ok(conv, x):
-        """csrc/ssdhip_convimg.hip: 3x3 'same' with any dilation, the whole map of an image (at most 384 pixels) resident in LDS, one
-        tile per (image, 128 output channels) -- offered where that gives at least half a chip's worth of tiles."""
-        import os
-        return (conv.kernel_size == (3, 3) and x.shape[2] * x.shape[3] <= 384 and conv.in_channels % 64 == 0
-                and conv.out_channels % 64 == 0 and 1 <= conv.dilation[0] <= 16
-                and x.shape[0] * (conv.out_channels // 64) >= 128 and os.environ.get("SSDHIP_NO_IMAGE", "0") != "1")
-
-    @staticmethod
-    def _image2_ok(conv, x):
-        """Round 6, csrc/ssdhip_convimg.hip's general form: 1 x 1 layers (fc7, conv6_1: one step per 64-channel slice of the resident
-        image) and strided / partially padded 3 x 3 layers (conv6_2) on maps of at most 384 pixels, where one image x 64 output channels
-        per tile gives at least half a chip's worth of tiles."""
-        import os
-        k = conv.kernel_size[0]
-        if (os.environ.get("SSDHIP_IMAGE2", "1") == "0" or os.environ.get("SSDHIP_NO_IMAGE", "0") == "1" or conv.kernel_size[1] != k
-                or conv.stride[0] != conv.stride[1] or conv.dilation[0] != conv.dilation[1] or not isinstance(conv.padding, tuple)
-                or conv.padding[0] != conv.padding[1] or conv.groups != 1 or conv.padding_mode != 'zeros'):
-            return False
-        return (x.shape[0] * (conv.out_channels // 64) >= 128
-                and nat.conv2d_image_supported(x, conv.weight, conv.stride[0], conv.padding[0], conv.dilation[0]))
-
     def _pick(self, key, candidates):
         """candidates: {name: thunk}; returns the name of the fastest (timed once per key with events)."""
-        import os
-        mode = os.environ.get("SSDHIP_CONV", "auto")
+        mode = sel.switch("CONV")
         if mode in candidates:
             return mode
-        prefer = os.environ.get("SSDHIP_PREFER")              # A/B aid: this candidate wherever it is offered, the autotune elsewhere
+        prefer = sel.switch("PREFER")              # A/B aid: this candidate wherever it is offered, the autotune elsewhere
         if prefer and prefer in candidates:
             return prefer
         if mode == "igemm" and "igemm" not in candidates:
@@ -633,76 +202,20 @@ class SSDModel(nn.Module):
         """Conv2D(activation='relu' | None).  link_in / link_out (_ReluLink, training step only; see `relu_link`): x is the ReLU output of a
         layer that feeds nothing but this one / this layer's output feeds exactly one layer, which holds the same link as its link_in."""
         if self._fused(x, conv):
-            import os
-            k = conv.kernel_size[0]
-            if (conv.in_channels == 3 and conv.out_channels == 64 and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-                    and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.bias is not None):
+            g = sel.geometry_of(conv, x)
+            if sel.first_layer(g):
                 return nat.conv3x3_cin3(x, conv.weight, conv.bias, relu=relu)
             cands = {"miopen": lambda: nat.bias_act(self._conv_nobias(conv, x), conv.bias, relu=relu)}
-            if self._igemm_ok(conv, x):
-                cands["igemm"] = lambda: nat.conv2d_same(x, conv.weight, conv.bias, dilation=conv.dilation[0], relu=relu)
-                # the three-stage / 32-channel-slice / 3-workgroups-per-CU variant wins on the shallow-K layers (Cin = 64)
-                cands["igemm6"] = lambda: nat.conv2d_same(x, conv.weight, conv.bias, dilation=conv.dilation[0], relu=relu, variant=6)
-                if x.shape[0] * x.shape[2] * x.shape[3] <= 128 * 128:          # at most one workgroup per CU: the deepest ring too
-                    cands["igemm5"] = lambda: nat.conv2d_same(x, conv.weight, conv.bias, dilation=conv.dilation[0], relu=relu, variant=5)
-                if self._few_tiles(x.shape[0] * x.shape[2] * x.shape[3], conv.out_channels):
-                    # the split-K form: the K ranges of a tile side by side on otherwise idle CUs
-                    cands["splitk"] = lambda: nat.conv2d(x, conv.weight, conv.bias, stride=1, padding=conv.padding[0],
-                                                         dilation=conv.dilation[0], relu=relu, variant=8)
-                if conv.in_channels == 64 and k == 3 and conv.dilation[0] == 1:
-                    cands["c64"] = lambda: nat.conv3x3_c64(x, conv.weight, conv.bias, relu=relu, pool=False)
-                if self._halo_ok(conv, x):
-                    cands["halo"] = lambda: nat.conv2d_same(x, conv.weight, conv.bias, dilation=1, relu=relu, variant=7)
-                if self._image_ok(conv, x):
-                    # one image per tile, the dilated taps as per-lane LDS addresses (csrc/ssdhip_convimg.hip): fc6
-                    cands["image"] = lambda: nat.conv3x3_image(x, conv.weight, conv.bias, dilation=conv.dilation[0], relu=relu)
-                if k == 1 and self._image2_ok(conv, x):
-                    # round 6: a 1 x 1 layer with the image's 64-channel slices resident in LDS, one step per slice (fc7 41 -> ~17 us,
-                    # conv6_1 23 -> ~10 us: the implicit-GEMM tiles move 2.5 x the bytes per FLOP from L2).  Taken without a timing
-                    # run, like the split-K form below: a back-to-back burst of these kernels is L2-warm and host-paced.
-                    cands["image"] = lambda: nat.conv2d_image(x, conv.weight, conv.bias, relu=relu)
-                    if (os.environ.get("SSDHIP_CONV", "auto") in ("auto", "auto_miopen") and not os.environ.get("SSDHIP_PREFER")
-                            and x.shape[0] >= 16):
-                        return cands["image"]()
-                if k == 1 and os.environ.get("SSDHIP_GEMM_1X1", "0") == "1":
-                    # a 1 x 1 layer on NHWC memory IS a plain GEMM ([B H W, Cin] x [Cin, Cout] + bias, ReLU).  Opt-in: the library's
-                    # (hipBLASLt through torch, bias / activation in its epilogue) was measured on fc7 and conv6_1 inside the step and is
-                    # no faster than the implicit-GEMM kernels (profiles/r05zd_library_gemm_for_1x1_layers_ab.txt: 2.119 / 2.112 / 2.119 ms)
-                    cands["gemm"] = lambda: self._gemm_1x1(conv, x, relu)
-            elif self._igemm_general_ok(conv, x):
-                # the extra layers: small maps, one workgroup per CU at most -- the deeper LDS rings (loads three / two steps ahead)
-                # hide the L2 latency that the two-stage kernel exposes on every K-step
-                ho = (x.shape[2] + 2 * conv.padding[0] - conv.dilation[0] * (k - 1) - 1) // conv.stride[0] + 1
-                wo = (x.shape[3] + 2 * conv.padding[0] - conv.dilation[0] * (k - 1) - 1) // conv.stride[0] + 1
-                names = (("igemm", None), ("igemm5", 5), ("igemm6", 6))
-                if self._few_tiles(x.shape[0] * ho * wo, conv.out_channels):
-                    names += (("splitk", 8),)
-                for nm, v in names:
-                    cands[nm] = lambda v=v: nat.conv2d(x, conv.weight, conv.bias, stride=conv.stride[0], padding=conv.padding[0],
-                                                       dilation=conv.dilation[0], relu=relu, variant=v)
-                if (self._halo_ok(conv, x) and conv.stride[0] in (1, 2) and conv.padding[0] in (0, 1) and x.shape[3] <= 94
-                        and x.shape[2] + 2 * conv.padding[0] >= 3 and x.shape[3] + 2 * conv.padding[0] >= 3):
-                    # the slab kernel keeps the strided / cropped positions of the stride-1 'same' result: redundant FLOPs, but
-                    # these layers cost the latency of their K loop, not arithmetic
-                    cands["halo"] = lambda: nat.conv2d(x, conv.weight, conv.bias, stride=conv.stride[0], padding=conv.padding[0],
-                                                       dilation=1, relu=relu, variant=7)
-                if self._image2_ok(conv, x):
-                    # round 6: conv6_2 (19 x 19 -> 10 x 10, stride 2) with the image resident in LDS, the strided taps as addresses, one
-                    # (image, 64 channels) tile of 128 pixels per workgroup: 256 tiles at batch 32 instead of a split-K launch + its reduction
-                    cands["image"] = lambda: nat.conv2d_image(x, conv.weight, conv.bias, stride=conv.stride[0], padding=conv.padding[0],
-                                                              dilation=conv.dilation[0], relu=relu)
-                    if (os.environ.get("SSDHIP_CONV", "auto") in ("auto", "auto_miopen") and not os.environ.get("SSDHIP_PREFER")
-                            and x.shape[0] >= 16):
-                        return cands["image"]()
-            import os
-            if ("splitk" in cands and self._splitk_measured_regime(x) and os.environ.get("SSDHIP_NO_SPLITK", "0") != "1"
-                    and os.environ.get("SSDHIP_CONV", "auto") in ("auto", "auto_miopen") and not os.environ.get("SSDHIP_PREFER")):
-                # The few-tile layers take the split-K form without a timing run: a back-to-back microbenchmark of these 5-30 us
-                # kernels is host-bound and L2-warm and says nothing about them inside the step, where the form was measured
-                # (r03p, graphed step, two A/B pairs: 2.435 -> 2.353 and 2.455 -> 2.378 ms; chain of extra layers 178 -> 138 us)
-                return cands["splitk"]()
-            name = (self._pick(("act", tuple(x.shape), conv.out_channels, k, conv.dilation[0], relu, conv.stride[0], conv.padding[0]), cands)
-                    if len(cands) > 1 else "miopen")
+            for name, fn in sel.candidates(g, relu, sel.INFERENCE).items():
+                cands[name] = lambda fn=fn: fn(x, conv.weight, conv.bias)
+            if sel.igemm(g) and g.k == 1 and sel.on("GEMM_1X1"):
+                # a 1 x 1 layer on NHWC memory IS a plain GEMM ([B H W, Cin] x [Cin, Cout] + bias, ReLU).  Opt-in: the library's
+                # (hipBLASLt through torch, bias / activation in its epilogue) was measured on fc7 and conv6_1 inside the step and is
+                # no faster than the implicit-GEMM kernels (profiles/r05zd_library_gemm_for_1x1_layers_ab.txt: 2.119 / 2.112 / 2.119 ms)
+                cands["gemm"] = lambda: self._gemm_1x1(conv, x, relu)
+            if len(cands) == 1:
+                return cands["miopen"]()
+            name = sel.untimed_choice(g, relu) or self._pick(sel.act_key(g, relu), cands)
             return cands[name]()
         if self._fused_train(x, conv):
             run, _name = self._train_thunk(conv, x, relu)
@@ -719,113 +232,20 @@ class SSDModel(nn.Module):
         return (self.fused_training and x.is_cuda and torch.is_grad_enabled() and conv.bias is not None and conv.groups == 1
                 and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)))
 
-    @staticmethod
-    def _own_dgrad_ok(conv):
-        """The data gradient of this layer runs on libssdhip's forward kernels with transposed / flipped filters (see
-        _conv_input_weight_grads): stride 1, 'same', k in (1, 3), channel counts multiples of 64."""
-        k = conv.kernel_size[0]
-        if conv.groups != 1 or conv.kernel_size[1] != k or conv.in_channels % 64 or conv.out_channels % 64:
-            return False
-        if (k == 3 and conv.dilation == (1, 1) and conv.stride[0] == conv.stride[1] and conv.padding[0] == conv.padding[1]
-                and conv.padding[0] in (0, 1) and isinstance(conv.padding, tuple)):
-            return True                                  # (round 6) strided / 'valid' 3 x 3: embedding launch + the 'same' kernel
-        return (conv.stride == (1, 1) and k in (1, 3) and conv.dilation[0] == conv.dilation[1]
-                and conv.padding == (conv.dilation[0] * (k // 2),) * 2)
-
-    def _shadow_build(self, device):
-        """bf16 copies of every convolution's float32 master weights in the layouts the MFMA kernels read (csrc/ssdhip_optim.hip):
-        channels_last filters, their transposed / tap-flipped twin where the layer's data gradient runs on our kernels, the bias; the
-        conf and loc heads of a source map as ROWS OF ONE packed tensor ([conf | loc | zero rows up to a multiple of 128]: what
-        _PackedHeadFn multiplies), so that nothing is concatenated, flipped or re-laid-out per step."""
-        convs = [m for m in self.modules() if isinstance(m, nn.Conv2d) and m.bias is not None]
-        index = {id(c): i for i, c in enumerate(convs)}
-        cl, tr, bias, tr_arg = [None] * len(convs), [None] * len(convs), [None] * len(convs), [(0, 0)] * len(convs)
-        packs = {}
-        heads = list(zip(getattr(self, "conf_heads", []), getattr(self, "loc_heads", [])))
-        with torch.no_grad():
-            for l, (ch, lh) in enumerate(heads):
-                same = lambda c: (isinstance(c, nn.Conv2d) and c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1)
-                                  and c.dilation == (1, 1) and c.groups == 1 and c.bias is not None and id(c) in index)
-                if not (same(ch) and same(lh) and ch.in_channels == lh.in_channels and ch.in_channels % 128 == 0):
-                    continue
-                nc, nl, cin = ch.out_channels, lh.out_channels, ch.in_channels
-                cp = -(-(nc + nl) // 128) * 128
-                pw = torch.zeros((cp, cin, 3, 3), dtype=torch.bfloat16, device=device).contiguous(memory_format=torch.channels_last)
-                pwt = torch.zeros((cin, cp, 3, 3), dtype=torch.bfloat16, device=device).contiguous(memory_format=torch.channels_last)
-                pb = torch.zeros((cp,), dtype=torch.bfloat16, device=device)
-                packs[l] = (pw, pb, pwt, nc, nl)
-                for conv, lo, n in ((ch, 0, nc), (lh, nc, nl)):
-                    i = index[id(conv)]
-                    cl[i], bias[i], tr[i], tr_arg[i] = pw[lo:lo + n], pb[lo:lo + n], pwt, (cp, lo)
-            for i, c in enumerate(convs):
-                if cl[i] is not None:
-                    continue
-                cl[i] = torch.empty(tuple(c.weight.shape), dtype=torch.bfloat16, device=device).contiguous(memory_format=torch.channels_last)
-                if cl[i].dim() == 4 and not cl[i].permute(0, 2, 3, 1).is_contiguous():          # size-1 dims can leave odd strides behind
-                    cl[i] = torch.empty(tuple(c.weight.permute(0, 2, 3, 1).shape), dtype=torch.bfloat16, device=device).permute(0, 3, 1, 2)
-                bias[i] = torch.empty((c.out_channels,), dtype=torch.bfloat16, device=device)
-                if self._own_dgrad_ok(c):
-                    o, ci, kh, kw = c.weight.shape
-                    tr[i] = torch.empty((ci, kh, kw, o), dtype=torch.bfloat16, device=device).permute(0, 3, 1, 2)   # (I, O, kh, kw) channels_last
-                    tr_arg[i] = (o, 0)
-        dests, seen = [], set()                                   # every tensor the refresh launch writes, once (views share a counter)
-        for t in cl + tr + bias + [u for pk in packs.values() for u in pk[:3]]:
-            if t is None:
-                continue
-            base = t._base if t._base is not None else t
-            if id(base) not in seen:
-                seen.add(id(base))
-                dests.append(base)
-        return {"device": device, "convs": convs, "index": index, "cl": cl, "tr": tr, "bias": bias, "tr_arg": tr_arg, "packs": packs,
-                "key": None, "table": None, "table_key": None, "dests": tuple(dests)}
-
-    def _shadow_state_fresh(self, conv):
-        """The shadow state with every bf16 copy up to date (ONE launch over all parameters when any of them changed: the optimizer's
-        in-place update bumps `_version`)."""
-        st = self.__dict__.get("_shadow_state")
-        if st is None or st["device"] != conv.weight.device:
-            st = self._shadow_build(conv.weight.device)
-            self.__dict__["_shadow_state"] = st
-        # Inside raw_predictions the check runs once per forward pass (`_shadow_fresh`); a direct call of features() / conv_act()
-        # checks every time.  The key holds the Parameter OBJECT, its storage and its version: an optimizer step bumps the version,
-        # `param.data = t` changes the storage, `conv.weight = nn.Parameter(...)` the object.
-        if not (self.__dict__.get("_in_forward", False) and self.__dict__.get("_shadow_fresh", False)):
-            src = [c.weight for c in st["convs"]] + [c.bias for c in st["convs"]]
-            key = tuple((id(t), t.data_ptr(), t._version) for t in src)
-            if key != st["key"]:
-                tkey = tuple((id(t), t.data_ptr(), tuple(t.stride())) for t in src)
-                if st["table"] is None or st["table_key"] != tkey:             # the table holds raw pointers: rebuilt when a storage moved
-                    w = [(c.weight.detach(), st["cl"][i], st["tr"][i], st["tr_arg"][i][0], st["tr_arg"][i][1]) for i, c in enumerate(st["convs"])]
-                    v = [(c.bias.detach().contiguous(), st["bias"][i]) for i, c in enumerate(st["convs"])]
-                    if any(b.data_ptr() != c.bias.data_ptr() for (b, _), c in zip(v, st["convs"])):
-                        raise RuntimeError("a convolution bias is not a contiguous tensor")
-                    st["table"] = nat.shadow_table(w, v, st["device"])
-                    st["table_key"] = tkey
-                nat.shadow_refresh(st["table"])
-                # the kernel rewrote the shadows in place behind autograd's back: their version counters move as an in-place tensor
-                # op's would, so a backward whose forward saved the OLD filters raises instead of multiplying the new ones (ADVICE r5)
-                _bump_versions(st["dests"])
-                # Inside a stream capture the refresh is only RECORDED (it runs at every replay): the shadows are not fresh for the next
-                # eager call, which must refresh them itself (tests/test_train_graph_gpu.py: the first eager step after a capture
-                # multiplied the previous step's filters, 1.3e-3 off on the loss).
-                if not torch.cuda.is_current_stream_capturing():
-                    st["key"] = key
-            self.__dict__["_shadow_fresh"] = True
-        return st
 
     def _bf16_shadow(self, conv, with_transposed=False):
         """bf16 copies of a convolution's float32 master weight (channels_last) and bias for the libssdhip kernels [+ the transposed,
         tap-flipped filters of its data gradient, or None]; (None, None[, None]) for a convolution the shadow set does not hold."""
         if conv.weight.dtype == torch.bfloat16:
             return (conv.weight.detach(), conv.bias.detach(), None) if with_transposed else (conv.weight.detach(), conv.bias.detach())
-        st = self._shadow_state_fresh(conv)
-        i = st["index"].get(id(conv))
+        st = _shadow.fresh(self, conv.weight.device)
+        i = st.index.get(id(conv))
         if i is None:
             return (None, None, None) if with_transposed else (None, None)
         if with_transposed:
-            packed = st["tr_arg"][i][0] != conv.out_channels               # a head's rows live in its source map's packed tensor
-            return st["cl"][i], st["bias"][i], (None if packed else st["tr"][i])
-        return st["cl"][i], st["bias"][i]
+            packed = st.tr_arg[i][0] != conv.out_channels                  # a head's rows live in its source map's packed tensor
+            return st.cl[i], st.bias[i], (None if packed else st.tr[i])
+        return st.cl[i], st.bias[i]
 
     def _packed_head_shadow(self, l):
         """(packed filters (Cp, Cin, 3, 3) bf16 channels_last, packed bias (Cp,), transposed / flipped (Cin, Cp, 3, 3), n_conf, n_loc) of
@@ -833,39 +253,19 @@ class SSDModel(nn.Module):
         ch = self.conf_heads[l]
         if ch.weight.dtype == torch.bfloat16:
             return None
-        return self._shadow_state_fresh(ch)["packs"].get(l)
+        return _shadow.fresh(self, ch.weight.device).packs.get(l)
 
     def _train_thunk(self, conv, x, relu):
         """The libssdhip kernel for this layer as `(x_bf16, w_bf16, b_bf16) -> y`, or (None, None).  The variant is the one the
         per-shape autotune keeps (same keys as the inference path)."""
-        k = conv.kernel_size[0]
-        d = conv.dilation[0]
-        if (conv.in_channels == 3 and conv.out_channels == 64 and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-                and conv.padding == (1, 1) and conv.dilation == (1, 1)):
+        g = sel.geometry_of(conv, x)
+        if sel.first_layer(g):
             return (lambda xb, wb, bb: nat.conv3x3_cin3(xb, wb, bb, relu=relu)), "cin3"
-        if self._igemm_ok(conv, x):
-            cands = {"igemm": lambda xb, wb, bb: nat.conv2d_same(xb, wb, bb, dilation=d, relu=relu),
-                     "igemm6": lambda xb, wb, bb: nat.conv2d_same(xb, wb, bb, dilation=d, relu=relu, variant=6)}
-            if conv.in_channels == 64 and k == 3 and d == 1:
-                cands["c64"] = lambda xb, wb, bb: nat.conv3x3_c64(xb, wb, bb, relu=relu, pool=False)
-            if self._halo_ok(conv, x):
-                cands["halo"] = lambda xb, wb, bb: nat.conv2d_same(xb, wb, bb, dilation=1, relu=relu, variant=7)
-            if self._image_ok(conv, x):
-                cands["image"] = lambda xb, wb, bb: nat.conv3x3_image(xb, wb, bb, dilation=d, relu=relu)
-            if k == 1 and self._image2_ok(conv, x):
-                cands["image"] = lambda xb, wb, bb: nat.conv2d_image(xb, wb, bb, relu=relu)
-        elif self._igemm_general_ok(conv, x):
-            cands = {nm: (lambda xb, wb, bb, v=v: nat.conv2d(xb, wb, bb, stride=conv.stride[0], padding=conv.padding[0], dilation=d,
-                                                            relu=relu, variant=v))
-                     for nm, v in (("igemm", None), ("igemm5", 5), ("igemm6", 6))}
-            if self._image2_ok(conv, x):
-                cands["image"] = lambda xb, wb, bb: nat.conv2d_image(xb, wb, bb, stride=conv.stride[0], padding=conv.padding[0], dilation=d,
-                                                                     relu=relu)
-        else:
+        cands = sel.candidates(g, relu, sel.TRAINING)
+        if not cands:
             return None, None
-        import os
-        key = ("act", tuple(x.shape), conv.out_channels, k, d, relu, conv.stride[0], conv.padding[0])
-        forced = os.environ.get("SSDHIP_CONV", "auto")
+        key = sel.act_key(g, relu)
+        forced = sel.switch("CONV")
         if len(cands) == 1:
             name = "igemm"
         elif forced in cands:
@@ -889,38 +289,18 @@ class SSDModel(nn.Module):
         autograd -- the inference paths take no links."""
         return _ReluLink() if torch.is_grad_enabled() else None
 
+
     def conv_act_pool(self, conv, x, kernel, stride, pad=0, ceil_mode=False, link_in=None):
         if self._fused(x, conv):
             cands = {"miopen": lambda: nat.bias_act_maxpool(self._conv_nobias(conv, x), conv.bias, kernel, stride, pad, ceil_mode,
                                                             relu=True)}
-            if self._igemm_ok(conv, x):
-                cands["igemm"] = lambda: nat.bias_act_maxpool(
-                    nat.conv2d_same(x, conv.weight, conv.bias, dilation=conv.dilation[0], relu=True), None, kernel, stride, pad,
-                    ceil_mode, relu=False)
-                cands["igemm6"] = lambda: nat.bias_act_maxpool(
-                    nat.conv2d_same(x, conv.weight, conv.bias, dilation=conv.dilation[0], relu=True, variant=6), None, kernel, stride,
-                    pad, ceil_mode, relu=False)
-                if self._halo_ok(conv, x):               # the slab kernel + a separate pooling pass can beat the fused epilogue
-                    cands["halo"] = lambda: nat.bias_act_maxpool(
-                        nat.conv2d_same(x, conv.weight, conv.bias, dilation=1, relu=True, variant=7), None, kernel, stride, pad,
-                        ceil_mode, relu=False)
-                if self._image_ok(conv, x):              # conv5_3 -> pool5: the image-resident kernel + the pooling pass
-                    cands["image"] = lambda: nat.bias_act_maxpool(
-                        nat.conv3x3_image(x, conv.weight, conv.bias, dilation=conv.dilation[0], relu=True), None, kernel, stride, pad,
-                        ceil_mode, relu=False)
-                if (kernel == 2 and stride == 2 and pad == 0 and (ceil_mode or x.shape[2] % 2 == 0) and (ceil_mode or x.shape[3] % 2 == 0)):
-                    # pooling fused into the convolution's epilogue: the full-resolution activation is never written
-                    cands["igemm_pool"] = lambda: nat.conv2d_same_pool2(x, conv.weight, conv.bias, dilation=conv.dilation[0], relu=True)
-                    if self._halo_ok(conv, x):
-                        cands["halo_pool"] = lambda: nat.conv3x3_halo(x, conv.weight, conv.bias, relu=True, pool=True)
-                    if conv.in_channels == 64 and conv.kernel_size == (3, 3) and conv.dilation[0] == 1:
-                        cands["c64_pool"] = lambda: nat.conv3x3_c64(x, conv.weight, conv.bias, relu=True, pool=True)
+            for name, fn in sel.pooled_candidates(sel.geometry_of(conv, x), kernel, stride, pad, ceil_mode).items():
+                cands[name] = lambda fn=fn: fn(x, conv.weight, conv.bias)
             name = (self._pick(("pool", tuple(x.shape), conv.out_channels, conv.kernel_size[0], conv.dilation[0], kernel, stride, pad),
                                cands) if len(cands) > 1 else "miopen")
             return cands[name]()
-        import os
         if (kernel == 2 and stride == 2 and pad == 0 and ceil_mode and self._fused_train(x, conv) and conv.out_channels % 8 == 0
-                and 256 % (conv.out_channels // 8) == 0 and os.environ.get("SSDHIP_NO_FUSED_POOL_BWD", "0") != "1"):
+                and 256 % (conv.out_channels // 8) == 0 and not sel.on("NO_FUSED_POOL_BWD")):
             run, _name = self._train_thunk(conv, x, True)
             if run is not None:
                 wb, bb, wt = self._bf16_shadow(conv, with_transposed=True)
@@ -933,8 +313,7 @@ class SSDModel(nn.Module):
         per shape against the two-kernel form."""
         same3 = lambda c: (c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1)
                            and c.groups == 1 and c.bias is not None)
-        import os
-        if (os.environ.get("SSDHIP_NO_CONV1_BLOCK", "0") != "1" and os.environ.get("SSDHIP_CONV", "auto") in ("auto", "auto_miopen")
+        if (not sel.on("NO_CONV1_BLOCK") and sel.switch("CONV") in ("auto", "auto_miopen")
                 and self._fused(x, c1) and self._fused(x, c2) and same3(c1) and same3(c2)
                 and c1.in_channels == 3 and c1.out_channels == 64
                 and c2.in_channels == 64 and c2.out_channels % 64 == 0):
@@ -950,9 +329,8 @@ class SSDModel(nn.Module):
     def max_pool(self, x, kernel, stride, pad=0, ceil_mode=False):
         if self._fused(x) and x.shape[1] % 8 == 0:
             return nat.bias_act_maxpool(x, None, kernel, stride, pad, ceil_mode, relu=False)
-        import os
         if (self.fused_training and x.is_cuda and x.dtype == torch.bfloat16 and torch.is_grad_enabled() and x.shape[1] % 8 == 0
-                and x.requires_grad and os.environ.get("SSDHIP_NO_OWN_POOL", "0") != "1"):
+                and x.requires_grad and not sel.on("NO_OWN_POOL")):
             return _MaxPoolFn.apply(x, kernel, stride, pad, ceil_mode)
         return F.max_pool2d(x, kernel, stride, pad, ceil_mode=ceil_mode)
 
@@ -969,7 +347,7 @@ class SSDModel(nn.Module):
                                   list(self.swap_channels) if self.swap_channels else None)
         if (nhwc and self.fused_training and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and torch.is_grad_enabled()
                 and not x.requires_grad and self.img_channels <= 4 and torch.is_autocast_enabled()
-                and torch.get_autocast_dtype("cuda") == torch.bfloat16 and os.environ.get("SSDHIP_NO_TRAIN_PREPROCESS", "0") != "1"):
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16 and not sel.on("NO_TRAIN_PREPROCESS")):
             # the training step under bf16 autocast: the first convolution casts its input to bf16 anyway, and the images need no
             # gradient -- the same one-launch kernel instead of a subtraction, an index_select and two layout / dtype copies
             return nat.preprocess(x, self.subtract_mean, self.divide_by_stddev,
@@ -1074,8 +452,7 @@ class SSDModel(nn.Module):
                 return self.decoder.forward_from_heads(*head_args)          # y_pred is never materialised
             pred = nat.assemble_predictions(*head_args)
             return self.decoder(pred) if (decode and self.decoder is not None) else pred
-        import os
-        if (torch.is_grad_enabled() and not decode and os.environ.get("SSDHIP_NO_TRAIN_ASSEMBLY", "0") != "1" and len(feats) <= 8
+        if (torch.is_grad_enabled() and not decode and not sel.on("NO_TRAIN_ASSEMBLY") and len(feats) <= 8
                 and all(self._packed_train_head_ok(f, ch, lh) for f, ch, lh in zip(feats, self.conf_heads, self.loc_heads))
                 and self._train_assembly_fits(len(feats))):
             # every source map's heads are one packed libssdhip node: the assembly and its backward are one launch each (the backward
@@ -1103,223 +480,6 @@ class SSDModel(nn.Module):
         anchors = self.anchors_and_variances(sizes, conf.device)
         pred = torch.cat([conf, loc, anchors.unsqueeze(0).expand(b, -1, -1)], dim=2)   # 'predictions' (:419)
         return self.decoder(pred) if (decode and self.decoder is not None) else pred
-
-    def _split_heads(self, x):
-        """Fused bf16 inference only: the predictor heads of the trunk's two source maps (conv4_3, fc7: ~85 % of the head FLOPs) do not
-        depend on the extra layers -- a chain of eight small convolutions that leaves most CUs idle -- so the two can share the chip
-        on two HIP streams.  Mode 3 is what the HIP-graph step uses (GraphedInference; the eager path stays on one stream unless
-        SSDHIP_HEAD_OVERLAP says otherwise): the two trunk heads as a grouped slab launch capped at 160 of the 256 CUs on the second
-        stream beside the chain, then the four small heads (1.4 % / 0.7 % of a step in round 2; no measurable difference since the
-        extra layers are split-K launches: profiles/r03zd_two_stream_heads_and_producer_priority_remeasured.txt).  Modes 1 | 2 are the older forms with the implicit-GEMM heads (1: the heads on the second stream; 2: the chain on
-        a high-priority second stream): ~190 us of kernels run side by side but slow each other down by as much -- those heads fill
-        every CU (r02p: 2.831 off / 2.832 / 2.815 ms).  Returns (feature maps, packed head outputs), or None for the one-stream path."""
-        import os
-        mode = os.environ.get("SSDHIP_HEAD_OVERLAP") or self.__dict__.get("_head_overlap") or "0"
-        if (mode == "0" or not hasattr(self, "trunk_features") or not x.is_cuda
-                or torch.is_grad_enabled() or not self.fused_inference or x.dtype != torch.bfloat16
-                or len(self.conf_heads) > 8 + 2):
-            return None
-        if not all(conv.weight.dtype == torch.bfloat16 for conv in self.conf_heads):
-            return None
-        early = self.trunk_features(x)
-        n_early = len(early)
-        if not all(self._fused_head_ok(f, ch) and self._packed_head_ok(ch, lh, f)
-                   for f, ch, lh in zip(early, self.conf_heads, self.loc_heads)):
-            raise RuntimeError("predictor heads of the trunk do not qualify for the packed kernel")
-        if mode in ("3", "4") and not self._halo_heads_ok(early):
-            mode = "1"
-        main = torch.cuda.current_stream(x.device)
-        side = self.__dict__.get("_side_stream")
-        if side is None or side.device != x.device:
-            # An ORDINARY stream since round 6 (rounds 2-5: priority -1, "served first when both streams have workgroups pending" --
-            # schedule 4 has no such moment: the capped launch leaves the chain its CUs).  Same box, 6 x 60 steps alternating: 2.0068 ms
-            # (ordinary) vs 2.0072 ms (high priority); but once a process has USED a high-priority stream, every later HIP graph with
-            # parallel branches replays slower on this runtime -- the reference-precision step 6.5 -> 7.6-7.9 ms, slower than its eager
-            # form, which is what bench.py's second graph measured in rounds 5-6 (profiles/r06z_graphs_after_a_high_priority_stream.txt).
-            side = torch.cuda.Stream(device=x.device, priority=int(os.environ.get("SSDHIP_SIDE_PRIORITY", "0")))
-            self.__dict__["_side_stream"] = side
-
-        def check_rest(rest):
-            if not all(self._fused_head_ok(f, ch) and self._packed_head_ok(ch, lh, f)
-                       for f, ch, lh in zip(rest, self.conf_heads[n_early:], self.loc_heads[n_early:])):
-                raise RuntimeError("predictor heads of the extra layers do not qualify for the packed kernel")
-
-        # No record_stream anywhere: every tensor the other stream touches outlives the join in program order, and a block of the
-        # side stream's pool is only reused after that stream has waited for the current one again.
-        if mode == "4" and hasattr(self, "extra_features_front") and hasattr(self, "extra_features_tail"):
-            # Round 4: the tail of the extra layers is ONE launch on one CU per image (csrc/ssdhip_chain.hip: 32 CUs, ~55 us), so the
-            # balance moved: first the front of the extra layers (conv6_1, conv6_2: split-K launches that want the whole chip), THEN
-            # the two trunk heads on the second stream capped so that one CU per image stays free, beside the tail and the small heads
-            front = self.extra_features_front(early[1])
-            # Round 6: conv6_2 exists BEFORE the fork, so its head rides in the capped launch with the two trunk heads instead of leading
-            # the small launch behind the chain.  In units of 72 K-steps the capped launch is then 112 fc7 items x 2 + 192 conv4_3 items
-            # + 32 conv6_2 items = 448 = exactly two per workgroup at 224 workgroups in the kernel's snake order (at 216 sixteen
-            # workgroups draw an fc7 item AND a conv6_2 item: 132 us instead of 102), and 224 + the chain's 32 = the chip's 256 CUs.
-            # Same box, alternating, 3 x 30 steps: 1.935 -> 1.926 ms per step (profiles/r06y_ab_head_split.txt).
-            n_big = n_early + 1 if (os.environ.get("SSDHIP_HEAD_SPLIT", "3") == "3" and self._halo_heads_ok([front])
-                                    and self._fused_head_ok(front, self.conf_heads[n_early])
-                                    and self._packed_head_ok(self.conf_heads[n_early], self.loc_heads[n_early], front)) else n_early
-            big_maps = list(early) + ([front] if n_big > n_early else [])
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                big = nat.conv3x3_halo_group(big_maps, [self._packed_head_weight(l, 128) for l in range(n_big)], None, relu=False,
-                                             max_workgroups=int(os.environ.get("SSDHIP_HEAD_WGS", "224" if n_big > n_early else "216")))
-            rest = self.extra_features_tail(front)
-            check_rest(rest)
-            later = rest[n_big - n_early:]                    # the maps whose heads are still to come
-            if not later:
-                small = []
-            elif self._halo_heads_ok(later):
-                small = nat.conv3x3_halo_group(list(later), [self._packed_head_weight(n_big + l, 128) for l in range(len(later))], None,
-                                               relu=False)
-            else:
-                small = nat.conv2d_same_group(list(later), [self._packed_head_weight(n_big + l) for l in range(len(later))], None,
-                                              relu=False)
-            main.wait_stream(side)
-            return early + rest, big + small
-        if mode in ("3", "4"):
-            # the two trunk heads as a grouped slab launch capped at HALF the CUs (persistent workgroups, one per CU) on the second
-            # stream, the latency-bound chain of extra layers on the current one in the other half, then the four small heads
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                big = nat.conv3x3_halo_group(list(early), [self._packed_head_weight(l, 128) for l in range(n_early)], None, relu=False,
-                                             max_workgroups=int(os.environ.get("SSDHIP_HEAD_WGS", "128")))
-            rest = self.extra_features(early[1])
-            check_rest(rest)
-            if self._halo_heads_ok(rest):
-                small = nat.conv3x3_halo_group(list(rest), [self._packed_head_weight(n_early + l, 128) for l in range(len(rest))], None,
-                                               relu=False)
-            else:                                            # extra maps the slab kernel does not cover: the implicit-GEMM group
-                small = nat.conv2d_same_group(list(rest), [self._packed_head_weight(n_early + l) for l in range(len(rest))], None,
-                                              relu=False)
-            main.wait_stream(side)
-            return early + rest, big + small
-        if mode == "2":
-            # the latency-bound chain (extra layers + their small heads) on the high-priority stream, the two big heads on the current
-            # one: the chain's few workgroups no longer queue behind ~600 head workgroups at every one of its eight launches
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                rest = self.extra_features(early[1])
-                check_rest(rest)
-                small = nat.conv2d_same_group(list(rest), [self._packed_head_weight(n_early + l) for l in range(len(rest))], None,
-                                              relu=False)
-            big = nat.conv2d_same_group(list(early), [self._packed_head_weight(l) for l in range(n_early)], None, relu=False)
-            main.wait_stream(side)
-            return early + rest, big + small
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            big = nat.conv2d_same_group(list(early), [self._packed_head_weight(l) for l in range(n_early)], None, relu=False)
-        rest = self.extra_features(early[1])
-        check_rest(rest)
-        small = nat.conv2d_same_group(list(rest), [self._packed_head_weight(n_early + l) for l in range(len(rest))], None, relu=False)
-        main.wait_stream(side)
-        return early + rest, big + small
-
-    def _train_assembly_fits(self, n_maps):
-        """The one-launch assembly backward runs for this model's packed heads (LDS need from libssdhip's own formula, cached)."""
-        packs = [self._packed_head_shadow(l) for l in range(n_maps)]
-        if any(pk is None for pk in packs):
-            return False
-        key = (self.n_classes, tuple(int(pb.n_boxes) for pb in self.priorboxes[:n_maps]), tuple(int(pk[0].shape[0]) for pk in packs))
-        memo = self.__dict__.setdefault("_assembly_fits", {})
-        if key not in memo:
-            memo[key] = nat.assemble_backward_supported(key[0], key[1], key[2])
-        return memo[key]
-
-    def _packed_train_head_ok(self, f, ch, lh):
-        """Training step, bf16 autocast on the GPU, 3x3 'same' heads on a map the slab / weight-gradient kernels cover."""
-        import os
-        return (self._fused_train(f, ch) and lh.bias is not None and self._packed_head_ok(ch, lh, f) and f.shape[1] % 128 == 0
-                and f.shape[3] <= 190 and os.environ.get("SSDHIP_NO_OWN_HEADS", "0") != "1"
-                and ch in self.conf_heads and self._packed_head_shadow(list(self.conf_heads).index(ch)) is not None)
-
-    def _heads_grouped(self, feats):
-        outs = nat.conv2d_same_group(list(feats), [self._packed_head_weight(l) for l in range(len(feats))], None, relu=False)
-        return outs, [None] * len(outs)
-
-    def _heads_halo_grouped(self, feats):
-        """All packed heads through the slab kernel in one launch of persistent workgroups (csrc/ssdhip_convh.hip): filters padded to a
-        multiple of 128 output channels; the deepest head (fc7's: 144 K-steps) is dispatched first."""
-        outs = nat.conv3x3_halo_group(list(feats), [self._packed_head_weight(l, 128) for l in range(len(feats))], None, relu=False)
-        return outs, [None] * len(outs)
-
-    def _heads_halo_mixed(self, feats):
-        """Round 6, fourth session (SSD512: its conv4_3 map is 64 wide, two columns more than the grouped slab launch's LDS layout takes,
-        and ALL seven heads fell back to the implicit-GEMM group -- 223 us of a 3.0 ms step): the maps wider than 62 each through the
-        single-problem slab entry (which tiles them as it sees fit: 16 x 16-pixel tiles, one round of 256 workgroups at batch 16), the
-        others as the grouped slab launch."""
-        wide = [l for l, f in enumerate(feats) if f.shape[3] > 62]
-        rest = [l for l in range(len(feats)) if l not in wide]
-        outs = [None] * len(feats)
-        for l in wide:
-            outs[l] = nat.conv3x3_halo(feats[l], self._packed_head_weight(l, 128), None, relu=False, pool=False)
-        if rest:
-            got = nat.conv3x3_halo_group([feats[l] for l in rest], [self._packed_head_weight(l, 128) for l in rest], None, relu=False)
-            for l, y in zip(rest, got):
-                outs[l] = y
-        return outs, [None] * len(outs)
-
-    def _halo_heads_mixed_ok(self, feats):
-        import os
-        rest = [f for f in feats if f.shape[3] <= 62]
-        return (os.environ.get("SSDHIP_NO_HALO", "0") != "1" and os.environ.get("SSDHIP_NO_HALO_MIXED", "0") != "1"
-                and len(rest) <= 8 and len(rest) < len(feats)
-                and all(f.shape[1] % 128 == 0 for f in feats))
-
-    def _halo_heads_ok(self, feats):
-        import os
-        return (os.environ.get("SSDHIP_NO_HALO", "0") != "1" and len(feats) <= 8
-                and all(f.shape[1] % 128 == 0 and f.shape[3] <= 62 for f in feats))
-
-    def _heads_per_layer(self, feats):
-        """Per layer the two heads run either as two MIOpen convolutions or PACKED into one libssdhip implicit-GEMM launch
-        (conf and loc filters concatenated along Cout, zero-padded to 64 channels): timed once per shape, faster kept."""
-        confs, locs = [], []
-        for l, (f, ch, lh) in enumerate(zip(feats, self.conf_heads, self.loc_heads)):
-            cands = {"miopen": lambda f=f, ch=ch, lh=lh: (self._conv_nobias(ch, f), self._conv_nobias(lh, f))}
-            if self._packed_head_ok(ch, lh, f):
-                cands["igemm"] = lambda f=f, l=l: (nat.conv2d_same(f, self._packed_head_weight(l), None, dilation=1, relu=False), None)
-            name = self._pick(("head", l, tuple(f.shape), ch.out_channels, lh.out_channels), cands) if len(cands) > 1 else "miopen"
-            c, lo = cands[name]()
-            confs.append(c)
-            locs.append(lo)
-        return confs, locs
-
-    @staticmethod
-    def _packed_head_ok(ch, lh, f):
-        same = lambda c: (c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1)
-        return same(ch) and same(lh) and ch.in_channels % 64 == 0 and ch.in_channels == lh.in_channels
-
-    def _packed_head_weight(self, l, multiple=64):
-        """[conf filters | loc filters | zero rows up to a multiple of `multiple`] of predictor layer l as one (Cout, Cin, 3, 3) bf16
-        weight in channels_last memory; rebuilt when either head's weight tensor changes (in-place updates bump `_version`)."""
-        ch, lh = self.conf_heads[l], self.loc_heads[l]
-        key = (ch.weight._version, lh.weight._version, ch.weight.data_ptr(), lh.weight.data_ptr())
-        hit = self._packed_heads.get((l, multiple))
-        n = ch.out_channels + lh.out_channels
-        if hit is not None and hit[0] != key and hit[1].device == ch.weight.device and hit[1].dtype == ch.weight.dtype:
-            # refreshed IN PLACE: a captured HIP graph (GraphedInference) keeps reading this storage
-            with torch.no_grad():
-                hit[1][:ch.out_channels].copy_(ch.weight)
-                hit[1][ch.out_channels:n].copy_(lh.weight)
-            hit = (key, hit[1])
-            self._packed_heads[(l, multiple)] = hit
-        elif hit is None or hit[0] != key:
-            pad = (-n) % multiple
-            with torch.no_grad():
-                w = torch.cat([ch.weight, lh.weight] + ([ch.weight.new_zeros((pad,) + tuple(ch.weight.shape[1:]))] if pad else []), dim=0)
-                w = w.contiguous(memory_format=torch.channels_last)
-            hit = (key, w)
-            self._packed_heads[(l, multiple)] = hit
-        return hit[1]
-
-    def _head_weights_key(self):
-        return tuple((c.weight._version, c.weight.data_ptr()) for heads in (self.conf_heads, self.loc_heads) for c in heads)
-
-    def _refresh_packed_heads(self):
-        """Rebuild every cached packed head filter IN ITS OWN STORAGE (a captured HIP graph keeps reading that storage)."""
-        for (l, multiple) in list(self._packed_heads):
-            self._packed_head_weight(l, multiple)
 
     def _derived_weights_key(self):
         """Versions of every parameter some cached, derived tensor was built from (what a captured graph cannot follow by itself)."""

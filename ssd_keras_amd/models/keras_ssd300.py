@@ -18,6 +18,7 @@ from torch import nn
 from .. import _native as nat
 
 from ..keras_layers.keras_layer_L2Normalization import L2Normalization
+from ._conv_select import on
 from ._common import SSDModel, conv_out, he_normal_, make_priorboxes, pool_out, resolve_anchor_config
 
 
@@ -40,7 +41,7 @@ class _VGGBase(SSDModel):
         ca, cap = self.conv_act, self.conv_act_pool
         x = self.conv1_block_pool(self.conv1_1, self.conv1_2, x)                # conv1_1 -> conv1_2 -> pool1 ('same' pooling pads bottom/right)
         # (training step: each pair of consecutive ReLU layers shares a link -- the upper layer's data gradient leaves its kernel masked
-        #  by the lower layer's activation, which is that layer's ReLU backward: models/_common.py, _ReluLink; None under no_grad)
+        #  by the lower layer's activation, which is that layer's ReLU backward: models/_train_fns.py, _ReluLink; None under no_grad)
         l2, l31, l32, l41, l42 = (self.relu_link() for _ in range(5))
         x = cap(self.conv2_2, ca(self.conv2_1, x, link_out=l2), 2, 2, ceil_mode=True, link_in=l2)
         x = cap(self.conv3_3, ca(self.conv3_2, ca(self.conv3_1, x, link_out=l31), link_in=l31, link_out=l32), 2, 2, ceil_mode=True, link_in=l32)
@@ -61,12 +62,10 @@ class _VGGBase(SSDModel):
     def _trunk(self, x):
         """[conv4_3_norm, fc7].  Fused bf16 inference (round 6): pool4 and conv4_3_norm are ONE pass over the conv4_3 map
         (csrc/ssdhip_layers.hip, pool2_l2norm_kernel: 15.9 + 21 -> ~24 us at batch 32, bit-identical to the two passes)."""
-        import os
         conv4_3 = self._vgg_to_conv4_3(x)
         norm = self.conv4_3_norm
         if (self._fused(conv4_3) and conv4_3.shape[1] == 512 and norm.fused_inference and norm.gamma is not None
-                and not torch.is_grad_enabled() and os.environ.get("SSDHIP_NO_POOL_NORM", "0") != "1"):
-            from .. import _native as nat
+                and not torch.is_grad_enabled() and not on("NO_POOL_NORM")):
             pooled, normed = nat.pool2_l2_normalize(conv4_3, norm.gamma_float32())
             return [normed, self._vgg_from_pool4(pooled)]
         return [norm(conv4_3), self._vgg_from_conv4_3(conv4_3)]
@@ -129,8 +128,7 @@ class SSD300(_VGGBase):
         """conv7_1 ... conv9_2 (reference models/keras_ssd300.py:304-313) as ONE launch, one workgroup per image, the intermediate maps in
         LDS (csrc/ssdhip_chain.hip) on the fused bf16 inference path; None -> the caller runs the six layers one by one.  The filters are
         re-packed in MFMA fragment order once per set of weights (keyed on the parameters' versions)."""
-        import os
-        if not _refresh_only and (not self._fused(conv6_2) or os.environ.get("SSDHIP_NO_CHAIN", "0") == "1"):
+        if not _refresh_only and (not self._fused(conv6_2) or on("NO_CHAIN")):
             return None
         convs = self._tail_convs()
         key = self._tail_chain_key() + (str(conv6_2.device),)

@@ -19,6 +19,14 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import hdf5_lite
+from .keras_ssd7 import SSD7
+
+try:
+    import h5py
+except ImportError:
+    h5py = None
+
 
 def _conv(c):
     items = [(c.weight, lambda a: np.transpose(a, (3, 2, 0, 1)), lambda t: np.transpose(t, (2, 3, 1, 0)))]
@@ -34,7 +42,6 @@ def _bn(b):
 
 def keras_layer_map(model):
     """Keras layer name -> [(tensor, keras->torch, torch->keras), ...] for every weighted layer of an SSD300 / SSD512 / SSD7."""
-    from .keras_ssd7 import SSD7
     m = {}
     if isinstance(model, SSD7):
         for i in range(7):
@@ -74,7 +81,6 @@ def _chunked_attr(attrs, name):
 def _read_h5_lite(path):
     """The same walk over a Keras weight file with this package's own HDF5 reader (models/hdf5_lite.py: the "old style" subset
     h5py's default libver writes; no HDF5 library needed)."""
-    from . import hdf5_lite
     f = hdf5_lite.File(path)
     g = f["model_weights"] if "model_weights" in f else f.root
     out = {}
@@ -87,9 +93,7 @@ def _read_h5_lite(path):
 
 
 def _read_h5(path):
-    try:
-        import h5py
-    except ImportError:                                          # the usual case where this package runs: its own reader
+    if h5py is None:                                             # the usual case where this package runs: its own reader
         return _read_h5_lite(path)
     out = {}
     with h5py.File(path, "r") as f:
@@ -121,7 +125,6 @@ def save_keras_weights_h5(source, path, backend="tensorflow", keras_version="2.2
     `keras_version`; one group per layer with the attribute `weight_names` = ["<layer>/kernel:0", "<layer>/bias:0", ...] and the arrays
     as datasets under those paths -- through this package's HDF5 writer (models/hdf5_lite.py; no h5py).  Weight names follow Keras 2:
     Conv2D kernel / bias, BatchNormalization gamma / beta / moving_mean / moving_variance, L2Normalization gamma."""
-    from . import hdf5_lite
     weights = source if isinstance(source, dict) else export_keras_weights(source)
     conv, bn = ("kernel:0", "bias:0"), ("gamma:0", "beta:0", "moving_mean:0", "moving_variance:0")
     groups = {}

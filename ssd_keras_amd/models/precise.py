@@ -26,6 +26,7 @@ decoded detections in the inference modes) computed here.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -50,11 +51,9 @@ class PreciseForward:
         self._calibrating = None                          # dict while `calibrate` records the layers' largest magnitudes
         self._calibrated = False
         self._headroom = 4.0
-        import os as _os
-        self._framework_calibration = _os.environ.get("SSDHIP_X3_FRAMEWORK_CALIBRATION", "0") == "1"   # rounds 3-5: MIOpen float32 walk
+        self._framework_calibration = os.environ.get("SSDHIP_X3_FRAMEWORK_CALIBRATION", "0") == "1"   # rounds 3-5: MIOpen float32 walk
         self.check_finite = check_finite
         self._last_heads = None
-        import os
         self._torch_assembly = os.environ.get("SSDHIP_X3_TORCH_ASSEMBLY", "0") == "1"    # the round-4 assembly in framework ops (A/B)
         # The two side streams of __call__ are PICKED: which hardware queues a process's streams share depends on how many were created
         # before, and a pair that shares one with the default stream (or with each other) loses the overlap -- 6.9 ms against 7.4 ms
@@ -123,7 +122,6 @@ class PreciseForward:
     PROBE = 2.0 ** 14                                     # calibration probe: the layer's output divided by this cannot leave float16
 
     def _divisor(self, amax):
-        import math
         if not math.isfinite(amax) or amax <= 65504.0 / self._headroom:
             return 1.0
         return 2.0 ** math.ceil(math.log2(amax / self.LIMIT))
@@ -137,7 +135,6 @@ class PreciseForward:
             # NHWC convolutions from its naive kernel, 85-450 ms per layer -- the first call of model.precise() took 25 s.)
             x2, s_in = self._as_pair(act)
             w, oscale, _b = self._conv_filters(conv)
-            import math
             probe = self.PROBE
             for _ in range(6):                            # (a probe that overflows all the same is repeated with its square: 2^28, 2^56, ...)
                 b_try = (conv.bias.detach().float() / probe).contiguous() if conv.bias is not None else None
@@ -342,7 +339,6 @@ class PreciseForward:
         with a 2^14 divisor, then run for real (`conv`): two forwards' worth of kernels, no framework convolution (round 6; the float32
         framework walk of rounds 3-5 -- SSDHIP_X3_FRAMEWORK_CALIBRATION=1 -- took 25 s on MIOpen's naive NHWC kernels).  Returns
         {layer name: (largest magnitude, divisor)}."""
-        import math
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("calibrate outside a stream capture")
         self._headroom = float(headroom)

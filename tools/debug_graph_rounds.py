@@ -74,8 +74,8 @@ def shadow_error():
     st = model.__dict__.get("_shadow_state")
     if st is None:
         return float("nan")
-    src = [c.weight for c in st["convs"]] + [c.bias for c in st["convs"]]
-    return max(float((d.float() - t.detach().to(torch.bfloat16).float()).abs().max()) for d, t in zip(st["dst"], src))
+    src = [c.weight for c in st.convs] + [c.bias for c in st.convs]
+    return max(float((d.float() - t.detach().to(torch.bfloat16).float()).abs().max()) for d, t in zip(st.cl + st.bias, src))
 
 
 def fwd_bwd():

@@ -1,4 +1,4 @@
-"""GPU check of models/_common._ConvBiasActFn on single layers: output and gradients vs a float32 PyTorch reference of the same op."""
+"""GPU check of models/_train_fns._ConvBiasActFn on single layers: output and gradients vs a float32 PyTorch reference of the same op."""
 import os
 import sys
 
