@@ -607,6 +607,30 @@ size_t ssdhip_conv_bn_elu_pack_bytes(int Cin, int Cout, int kernel);
 int ssdhip_conv_bn_elu_nhwc_bf16(const void* x, const void* w_packed, const float* scale, const float* shift, void* y, int B, int H, int W,
                                  int Cin, int Cout, int kernel, int pool, void* stream);
 
+/* The same block in the TRAINING step, everything behind its convolution (csrc/ssdhip_bntrain.hip): BatchNormalization with BATCH
+ * statistics -> ELU(alpha=1) [-> MaxPooling2D(2, 2) 'valid'], forward and backward.  y [B, H, W, C] bf16 is the convolution's output,
+ * C one of 32, 48, 64 and M = B H W >= 2; SSDHIP_E_BADARG otherwise.  gamma, beta [C]: bf16 if param_bf16 != 0, else float32; the
+ * running buffers likewise by running_bf16 (both NULL: no update).  Every sum has an order fixed by the shape: results are
+ * bit-reproducible.  n_slots = ssdhip_bn_elu_train_blocks(M, C) (0: shape not covered); partial: float32 scratch of 3 n_slots C values.
+ *
+ * forward   mean, invstd [C] float32 out: the batch mean and 1 / sqrt(biased variance + eps); tables [2 C] float32 out:
+ *           scale = gamma invstd, shift = beta - mean scale.  running = (1 - momentum) running + momentum stat in place, with the unbiased
+ *           variance M2 / (M - 1), rounded once to the buffer's dtype.  Per value v = fmaf(y, scale, shift); e = v > 0 ? v : expm1f(v).
+ *           full [B, H, W, C] and / or pooled [B, H / 2, W / 2, C] bf16 out (at least one; pooled needs H, W >= 2): pooled is the
+ *           maximum of the window's four float32 e, rounded once.  An odd last row / column feeds no window but counts in the statistics.
+ * backward  g_full / g_pooled: the gradients of those maps (at least one).  g_e = g_full + [position wins its window] g_pooled; the
+ *           winner is the first of (0,0), (0,1), (1,0), (1,1) with the largest s y, s the sign of gamma ((0,0) for gamma = 0).
+ *           dv = g_e (v > 0 ? 1 : expf(v)); dbeta = sum dv, dgamma = sum dv xhat with xhat = (y - mean) invstd, float32 [C] out;
+ *           dy [B, H, W, C] bf16 out = gamma invstd (dv - dbeta / M - xhat dgamma / M).  partial: 2 n_slots C values. */
+int ssdhip_bn_elu_train_blocks(long long positions, int C);
+int ssdhip_bn_elu_train_fwd_nhwc_bf16(const void* y, const void* gamma, const void* beta, int param_bf16, void* running_mean,
+                                      void* running_var, int running_bf16, double momentum, double eps, void* full, void* pooled,
+                                      float* mean, float* invstd, float* tables, float* partial, int B, int H, int W, int C,
+                                      int n_slots, void* stream);
+int ssdhip_bn_elu_train_bwd_nhwc_bf16(const void* y, const float* mean, const float* invstd, const void* gamma, const void* beta,
+                                      int param_bf16, const void* g_full, const void* g_pooled, void* dy, float* dgamma,
+                                      float* dbeta, float* partial, int B, int H, int W, int C, int n_slots, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Image half of the training-time augmentation (csrc/ssdhip_image.hip): what the reference does per image on the host
  * through OpenCV (data_generator/object_detection_2d_photometric_ops.py:23-480, object_detection_2d_geometric_ops.py:27-148), for a

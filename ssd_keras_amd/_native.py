@@ -141,6 +141,9 @@ SIGNATURES = {
     "ssdhip_conv3x3_cin3_nhwc_bf16": (_I, [_P] * 4 + [_I] * 6 + [_P]),
     "ssdhip_conv_bn_elu_pack_bytes": (_SZ, [_I] * 3),
     "ssdhip_conv_bn_elu_nhwc_bf16": (_I, [_P] * 5 + [_I] * 7 + [_P]),
+    "ssdhip_bn_elu_train_blocks": (_I, [_LL, _I]),
+    "ssdhip_bn_elu_train_fwd_nhwc_bf16": (_I, [_P] * 3 + [_I, _P, _P, _I, _D, _D] + [_P] * 6 + [_I] * 5 + [_P]),
+    "ssdhip_bn_elu_train_bwd_nhwc_bf16": (_I, [_P] * 5 + [_I] + [_P] * 6 + [_I] * 5 + [_P]),
     "ssdhip_image_program": (_I, [_P, _I, _P, _I, _I, _LL] + [_P] * 3),
     "ssdhip_image_resize_cv_u8": (_I, [_P, _P] + [_I] * 8 + [_P, _P, _I, _P, _P, _I, _P]),
     "ssdhip_image_resize_gather_cv_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 3 + [_I, _P, _P, _I, _P, _P]),
@@ -1554,6 +1557,94 @@ def conv_bn_elu(x, packed, scale, shift, kernel, pool, out=None):
     launch("ssdhip_conv_bn_elu_nhwc_bf16", x.device, _ptr(x), _ptr(packed), _ptr(scale), _ptr(shift), _ptr(out), b, h, w, cin, cout,
            int(kernel), int(bool(pool)))
     return out
+
+
+def _bn_train_map(t, name):
+    """A (B, C, H, W) bf16 CUDA tensor whose memory is NHWC already, for the BatchNorm training kernels: (b, h, w, c).  Nothing is copied:
+    these calls run inside autograd nodes and captured steps, where a silent layout copy would hide a mistake upstream."""
+    torch = _torch()
+    if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 4:
+        raise SsdHipError("bn_elu_train: %s must be a 4-D bfloat16 CUDA tensor" % name)
+    if not t.permute(0, 2, 3, 1).is_contiguous():
+        raise SsdHipError("bn_elu_train: %s must have NHWC (channels_last) memory" % name)
+    b, c, h, w = t.shape
+    return b, h, w, c
+
+
+def _bn_train_vectors(c, device, **named):
+    """The per-channel vectors of one call: contiguous (C,) CUDA tensors on the map's device; returns whether they are bf16."""
+    torch = _torch()
+    dtypes = set()
+    for name, t in named.items():
+        if (not t.is_cuda or t.device != device or t.dim() != 1 or t.numel() != c or not t.is_contiguous()
+                or t.dtype not in (torch.float32, torch.bfloat16)):
+            raise SsdHipError("bn_elu_train: %s must be a contiguous (%d,) float32 or bfloat16 tensor on %s" % (name, c, device))
+        dtypes.add(t.dtype)
+    if len(dtypes) > 1:
+        raise SsdHipError("bn_elu_train: %s must share one dtype" % " and ".join(named))
+    return int(dtypes.pop() == torch.bfloat16)
+
+
+def bn_elu_train_blocks(positions, c):
+    """Partial slots of the BatchNorm training kernels for a map of `positions` = B H W pixels and c channels; 0: shape not covered
+    (c not 32, 48 or 64, or fewer than two positions)."""
+    return int(load().ssdhip_bn_elu_train_blocks(int(positions), int(c)))
+
+
+def bn_elu_train_forward(y, gamma, beta, running_mean, running_var, momentum, eps, pool, keep_full):
+    """BatchNormalization with BATCH statistics -> ELU [-> MaxPooling2D(2, 2) 'valid'] behind a convolution of the training step
+    (csrc/ssdhip_bntrain.hip; include/ssdhip.h, ssdhip_bn_elu_train_fwd_nhwc_bf16).  y (B, C, H, W) bf16 with NHWC memory, the
+    convolution's output; gamma, beta (C,) float32 or bf16; running_mean / running_var (C,) float32 or bf16, updated IN PLACE by
+    nn.BatchNorm2d's rule (None, None: no update).  pool: return the pooled map; keep_full: return the full map (without pool it always
+    is).  Returns (full | None, pooled | None, mean, invstd), the last two float32 (C,): what the backward needs."""
+    torch = _torch()
+    b, h, w, c = _bn_train_map(y, "y")
+    nb = bn_elu_train_blocks(b * h * w, c)
+    if nb == 0:
+        raise SsdHipError("bn_elu_train: no kernel for C = %d with B H W = %d (C in 32, 48, 64; at least two positions)" % (c, b * h * w))
+    if pool and (h < 2 or w < 2):
+        raise SsdHipError("bn_elu_train: a %d x %d map has no 2 x 2 window to pool" % (h, w))
+    param_bf16 = _bn_train_vectors(c, y.device, gamma=gamma, beta=beta)
+    if (running_mean is None) != (running_var is None):
+        raise SsdHipError("bn_elu_train: running_mean and running_var come together")
+    running_bf16 = 0 if running_mean is None else _bn_train_vectors(c, y.device, running_mean=running_mean, running_var=running_var)
+    dev = y.device
+    full = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=dev).permute(0, 3, 1, 2) if (keep_full or not pool) else None
+    pooled = torch.empty((b, h // 2, w // 2, c), dtype=torch.bfloat16, device=dev).permute(0, 3, 1, 2) if pool else None
+    stats = torch.empty((4, c), dtype=torch.float32, device=dev)              # mean | invstd | scale | shift
+    partial = torch.empty((nb, 3, c), dtype=torch.float32, device=dev)
+    launch("ssdhip_bn_elu_train_fwd_nhwc_bf16", dev, _ptr(y), _ptr(gamma), _ptr(beta), param_bf16, _ptr(running_mean), _ptr(running_var),
+           running_bf16, float(momentum), float(eps), _ptr(full), _ptr(pooled), _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]),
+           _ptr(partial), b, h, w, c, nb)
+    return full, pooled, stats[0], stats[1]
+
+
+def bn_elu_train_backward(y, mean, invstd, gamma, beta, g_full, g_pooled):
+    """Backward of `bn_elu_train_forward` (ssdhip_bn_elu_train_bwd_nhwc_bf16): y, gamma, beta as given to it, mean / invstd as it
+    returned them, g_full / g_pooled the gradients of the maps it returned (bf16, NHWC memory; None for a map that was not returned
+    or fed nothing).  beta is needed because v = y scale + shift is recomputed, not stored.  Returns (dy bf16 like y, dgamma, dbeta
+    float32 (C,))."""
+    torch = _torch()
+    b, h, w, c = _bn_train_map(y, "y")
+    nb = bn_elu_train_blocks(b * h * w, c)
+    if nb == 0:
+        raise SsdHipError("bn_elu_train: no kernel for C = %d with B H W = %d (C in 32, 48, 64; at least two positions)" % (c, b * h * w))
+    if g_full is None and g_pooled is None:
+        raise SsdHipError("bn_elu_train: the backward needs the gradient of the full map, of the pooled map or both")
+    if g_full is not None and _bn_train_map(g_full, "g_full") != (b, h, w, c):
+        raise SsdHipError("bn_elu_train: g_full must have y's shape")
+    if g_pooled is not None and (h < 2 or w < 2 or _bn_train_map(g_pooled, "g_pooled") != (b, h // 2, w // 2, c)):
+        raise SsdHipError("bn_elu_train: g_pooled must be the gradient of y's 2 x 2 'valid' pooled map")
+    param_bf16 = _bn_train_vectors(c, y.device, gamma=gamma, beta=beta)
+    if _bn_train_vectors(c, y.device, mean=mean, invstd=invstd) != 0:
+        raise SsdHipError("bn_elu_train: mean and invstd are float32")
+    dev = y.device
+    dy = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=dev).permute(0, 3, 1, 2)
+    grads = torch.empty((2, c), dtype=torch.float32, device=dev)              # dgamma | dbeta
+    partial = torch.empty((nb, 2, c), dtype=torch.float32, device=dev)
+    launch("ssdhip_bn_elu_train_bwd_nhwc_bf16", dev, _ptr(y), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), param_bf16, _ptr(g_full),
+           _ptr(g_pooled), _ptr(dy), _ptr(grads[0]), _ptr(grads[1]), _ptr(partial), b, h, w, c, nb)
+    return dy, grads[0], grads[1]
 
 
 def conv1_block(x, w1, b1, weight, bias, relu=True, pool=False):

@@ -1,6 +1,7 @@
 """The training step's autograd functions over the libssdhip kernels (csrc/ssdhip_train.hip, ssdhip_wgrad.hip and the forward
-kernels of the inference path): one node per convolution layer [+ pooling], per pair of predictor heads, for the prediction assembly and
-for a max-pool.  `SSDModel` (models/_common.py) applies them; which forward kernel a layer runs is `_conv_select`'s choice."""
+kernels of the inference path): one node per convolution layer [+ pooling], per pair of predictor heads, for the prediction assembly,
+for a max-pool and for what follows a convolution in a block of SSD7 (batch-statistics BatchNorm + ELU [+ pool],
+csrc/ssdhip_bntrain.hip).  `SSDModel` (models/_common.py) applies them; which forward kernel a layer runs is `_conv_select`'s choice."""
 import torch
 
 from .. import _native as nat
@@ -276,3 +277,40 @@ class _MaxPoolFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         kernel, stride, pad = ctx.conf
         return nat.maxpool_bwd(x, gy.to(torch.bfloat16), kernel, stride, pad), None, None, None, None
+
+
+def _nhwc(t):
+    """t as a bf16 tensor whose memory is NHWC (a no-op for what the framework's channels_last convolutions return)."""
+    t = t.to(torch.bfloat16)
+    if not t.permute(0, 2, 3, 1).is_contiguous():
+        t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    return t
+
+
+class _BnEluPoolFn(torch.autograd.Function):
+    """BatchNormalization (batch statistics, moving-average update) -> ELU [-> MaxPooling2D(2, 2) 'valid'] behind a convolution of SSD7's
+    training step as one autograd node (csrc/ssdhip_bntrain.hip): three libssdhip launches forward, three backward, instead of the
+    framework's batch_norm, elu and max_pool2d and their backward kernels.  Saves the convolution's output y, mean, invstd, gamma and
+    beta -- no ELU output or mask: v is recomputed from y.  Returns (full | None, pooled | None, running_mean, running_var); the
+    buffers are updated in place (marked dirty, so they are outputs) and take no gradient."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, running_mean, running_var, momentum, eps, pool, keep_full):
+        y = _nhwc(y.detach())
+        full, pooled, mean, invstd = nat.bn_elu_train_forward(y, gamma.detach(), beta.detach(), running_mean, running_var, momentum, eps,
+                                                              pool, keep_full)
+        ctx.mark_dirty(running_mean, running_var)
+        ctx.mark_non_differentiable(running_mean, running_var)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(y, mean, invstd, gamma, beta)
+        return full, pooled, running_mean, running_var
+
+    @staticmethod
+    def backward(ctx, g_full, g_pooled, _g_mean, _g_var):
+        y, mean, invstd, gamma, beta = ctx.saved_tensors
+        if g_full is None and g_pooled is None:
+            return (None,) * 9
+        dy, dgamma, dbeta = nat.bn_elu_train_backward(y, mean, invstd, gamma.detach(), beta.detach(),
+                                                      None if g_full is None else _nhwc(g_full),
+                                                      None if g_pooled is None else _nhwc(g_pooled))
+        return dy, dgamma.to(gamma.dtype), dbeta.to(beta.dtype), None, None, None, None, None, None

@@ -11,6 +11,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from .. import _native as nat
+from ._train_fns import _BnEluPoolFn
 from ._common import SSDModel, he_normal_, make_priorboxes, pool_out, resolve_anchor_config
 
 
@@ -34,18 +35,52 @@ class SSD7(SSDModel):
                                           ['anchors4', 'anchors5', 'anchors6', 'anchors7'])
         he_normal_(self)
 
-    def fused_blocks(self, enable=True):
+    def fused_blocks(self, enable=True, training=False):
         """Opt in to (or, with False, out of) running every Conv2D -> BatchNormalization -> ELU [-> MaxPooling2D] block of a bf16 model
         in eval mode under no_grad as ONE libssdhip launch (csrc/ssdhip_convbn.hip): the block's map is rounded to bf16 once instead of
         three times and is never written and read back between the convolution, the normalisation, the activation and the pool.  Off by
         default: the default bf16 path stays bit-identical to the framework's.  A model in train() mode (batch statistics) and every
-        other dtype / device keep the default path whatever the switch says.  Returns the model."""
+        other dtype / device keep the default path whatever the switch says -- unless `training=True` asks for the training path too:
+        a bf16 CUDA model in train() mode then runs what lies between a block's convolution and the next one's -- batch statistics, the
+        running-statistics update, the normalisation, ELU and the pool, and their backward -- as libssdhip launches with one autograd
+        node per block (csrc/ssdhip_bntrain.hip, models/_train_fns.py: _BnEluPoolFn); the convolutions stay the framework's.  A block
+        whose shape those kernels do not cover keeps the default chain.  Returns the model."""
         self.__dict__["_fused_blocks"] = bool(enable)
+        self.__dict__["_fused_blocks_training"] = bool(enable) and bool(training)
         return self
+
+    # The blocks the training path takes when it is switched on (a set, so that a measurement can take one out: DESIGN.md 4.4,
+    # "SSD7 training", has the per-block numbers behind it).
+    TRAIN_BLOCKS = frozenset(range(7))
 
     def _fused_blocks_on(self, x):
         return (self.__dict__.get("_fused_blocks", False) and not self.training and self._fused(x)
                 and self.convs[0].weight.dtype == torch.bfloat16 and self.img_channels == 3)
+
+    def _train_blocks_on(self, x):
+        return (self.__dict__.get("_fused_blocks_training", False) and self.training and x.is_cuda and x.dtype == torch.bfloat16
+                and self.convs[0].weight.dtype == torch.bfloat16)
+
+    def _train_block(self, i, x):
+        """Block i of the training path: (the map for the next block, the map for the predictor heads or None); None where the kernels
+        do not cover the block (the caller runs the default chain, which raises for a single value per channel as the framework does)."""
+        bn = self.bns[i]
+        pool, keep = i < 6, i >= 3
+        b, _, h, w = x.shape
+        if (i not in self.TRAIN_BLOCKS or not bn.track_running_stats or bn.momentum is None or not bn.affine
+                or bn.weight.dtype != bn.bias.dtype or bn.running_mean.dtype != bn.running_var.dtype
+                or nat.bn_elu_train_blocks(b * h * w, bn.num_features) == 0 or (pool and (h < 2 or w < 2))):
+            return None
+        y = self.convs[i](x)
+        bn.num_batches_tracked.add_(1)
+        args = (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, pool, keep)
+        if torch.is_grad_enabled():
+            full, pooled = _BnEluPoolFn.apply(y, *args)[:2]
+        else:
+            if not y.permute(0, 2, 3, 1).is_contiguous():
+                y = y.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+            full, pooled = nat.bn_elu_train_forward(y, *args)[:2]
+        return (pooled if pool else full), (full if keep else None)
 
     def _block_sources(self, i):
         conv, bn = self.convs[i], self.bns[i]
@@ -102,7 +137,14 @@ class SSD7(SSDModel):
                     if i < 6:
                         x = self.max_pool(x, 2, 2)
             return feats
+        train_blocks = self._train_blocks_on(x)
         for i in range(7):
+            done = self._train_block(i, x) if train_blocks else None
+            if done is not None:
+                x, feat = done
+                if feat is not None:
+                    feats.append(feat)
+                continue
             x = F.elu(self.bns[i](self.convs[i](x)))
             if i >= 3:
                 feats.append(x)
