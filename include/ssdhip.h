@@ -631,6 +631,39 @@ int ssdhip_bn_elu_train_bwd_nhwc_bf16(const void* y, const float* mean, const fl
                                       int param_bf16, const void* g_full, const void* g_pooled, void* dy, float* dgamma,
                                       float* dbeta, float* partial, int B, int H, int W, int C, int n_slots, void* stream);
 
+/* The CONVOLUTIONS of SSD7's training step (csrc/ssdhip_convbn.hip, csrc/ssdhip_wgrad7.hip).  Geometries everywhere: those of
+ * ssdhip_conv_bn_elu_nhwc_bf16; SSDHIP_E_BADARG for any other, with nothing launched and every output untouched.
+ *
+ * ssdhip_conv_same_bias_nhwc_bf16   Conv2D(kernel, 'same') + bias on the kernels of ssdhip_conv_bn_elu_nhwc_bf16 with a plain epilogue:
+ *     y [B, H, W, Cout] bf16 = bf16_rne(acc + float(bias[c])), acc the float32 MFMA accumulator: one float32 add, one rounding.
+ *     w_packed: the image of ssdhip_conv_bn_elu_pack_bytes.  bias [Cout] bf16 -- the layer's own parameter, widened in the kernel -- or
+ *     NULL.  The data gradient of a 3 x 3 layer is this entry on dL/dy (Cin and Cout swapped) with the packed image of
+ *     filter.flip(2, 3).transpose(0, 1) and no bias.
+ *
+ * ssdhip_ssd7_pack_filters   ONE launch that writes the packed images of up to 8 layers from their bf16 filters: for layer i the
+ *     forward image fwd[i] and, where flipped[i] is not NULL (kernel 3 only), the image of the data gradient's filters.  Every byte of
+ *     every image is written, padding rows and columns included.  weights[i]: (Cout[i], Cin[i], k, k) bf16 read through the four element
+ *     strides strides[4 i ..] (any memory order); the arrays are host arrays, read while enqueuing (the table travels in the kernel
+ *     arguments).  Enqueue-only and capturable; the buffers are the caller's.
+ *
+ * ssdhip_ssd7_conv_wgrad_nhwc_bf16   dw[co][kh][kw][ci] = sum_{b,h,w} dy[b,h,w,co] x[b, h + kh - p, w + kw - p, ci] and
+ *     db[co] = sum dy[b,h,w,co] (db may be NULL), x [B, H, W, Cin], dy [B, H, W, Cout] bf16, float32 accumulation on the MFMA.  The
+ *     sum is split over 8 x 32 position tiles: split s of plan[0] owns plan[1] consecutive tiles (the last one plan[3]) of plan[2],
+ *     writes one float32 partial into the workspace, and a second launch adds the splits in index order in float32 and writes dw and
+ *     db once: bit-reproducible, no atomics, no memset.  out_bf16 = 0: float32 outputs; else bf16, one rounding.  dw_strides: the four
+ *     element strides of dw as a (Cout, Cin, kh, kw) tensor (a host array), or NULL for dense [Cout][k][k][Cin].  The plan is host
+ *     arithmetic: the most splits for which the partials, written and read back, do not exceed the operand bytes, at most 256 and at
+ *     most one per tile.  workspace: 16-byte aligned, ssdhip_ssd7_conv_wgrad_workspace_bytes bytes (0: geometry not covered); a smaller
+ *     one is SSDHIP_E_BADARG. */
+int ssdhip_conv_same_bias_nhwc_bf16(const void* x, const void* w_packed, const void* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                                    int kernel, void* stream);
+int ssdhip_ssd7_pack_filters(int n_layers, const void* const* weights, void* const* fwd, void* const* flipped, const int* Cin,
+                             const int* Cout, const int* kernel, const long long* strides, void* stream);
+int ssdhip_ssd7_conv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kernel, int* plan);
+size_t ssdhip_ssd7_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kernel);
+int ssdhip_ssd7_conv_wgrad_nhwc_bf16(const void* x, const void* dy, void* dw, void* db, int B, int H, int W, int Cin, int Cout, int kernel,
+                                     int out_bf16, const long long* dw_strides, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Image half of the training-time augmentation (csrc/ssdhip_image.hip): what the reference does per image on the host
  * through OpenCV (data_generator/object_detection_2d_photometric_ops.py:23-480, object_detection_2d_geometric_ops.py:27-148), for a

@@ -52,6 +52,7 @@ class _AugPhoto(ctypes.Structure):                   # struct ssdhip_augment_pho
 # tests/test_host_cpu.py checks it against the header's prototypes.
 _I, _LL, _SZ, _D, _F, _P = ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_double, ctypes.c_float, ctypes.c_void_p
 _INTP, _PARAMS, _PHOTO = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_AugParams), ctypes.POINTER(_AugPhoto)
+_LLP = ctypes.POINTER(ctypes.c_longlong)
 SIGNATURES = {
     "ssdhip_abi_version": (_I, []),
     "ssdhip_strerror": (ctypes.c_char_p, [_I]),
@@ -144,6 +145,11 @@ SIGNATURES = {
     "ssdhip_bn_elu_train_blocks": (_I, [_LL, _I]),
     "ssdhip_bn_elu_train_fwd_nhwc_bf16": (_I, [_P] * 3 + [_I, _P, _P, _I, _D, _D] + [_P] * 6 + [_I] * 5 + [_P]),
     "ssdhip_bn_elu_train_bwd_nhwc_bf16": (_I, [_P] * 5 + [_I] + [_P] * 6 + [_I] * 5 + [_P]),
+    "ssdhip_conv_same_bias_nhwc_bf16": (_I, [_P] * 4 + [_I] * 6 + [_P]),
+    "ssdhip_ssd7_pack_filters": (_I, [_I] + [_P] * 3 + [_INTP] * 3 + [_LLP, _P]),
+    "ssdhip_ssd7_conv_wgrad_plan": (_I, [_I] * 6 + [_INTP]),
+    "ssdhip_ssd7_conv_wgrad_workspace_bytes": (_SZ, [_I] * 6),
+    "ssdhip_ssd7_conv_wgrad_nhwc_bf16": (_I, [_P] * 4 + [_I] * 7 + [_LLP, _P, _SZ, _P]),
     "ssdhip_image_program": (_I, [_P, _I, _P, _I, _I, _LL] + [_P] * 3),
     "ssdhip_image_resize_cv_u8": (_I, [_P, _P] + [_I] * 8 + [_P, _P, _I, _P, _P, _I, _P]),
     "ssdhip_image_resize_gather_cv_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 3 + [_I, _P, _P, _I, _P, _P]),
@@ -1557,6 +1563,126 @@ def conv_bn_elu(x, packed, scale, shift, kernel, pool, out=None):
     launch("ssdhip_conv_bn_elu_nhwc_bf16", x.device, _ptr(x), _ptr(packed), _ptr(scale), _ptr(shift), _ptr(out), b, h, w, cin, cout,
            int(kernel), int(bool(pool)))
     return out
+
+
+def _ssd7_map(t, name):
+    """A (B, C, H, W) bf16 CUDA tensor whose memory is NHWC already (nothing is copied: these calls run inside autograd nodes and
+    captured steps); returns (b, h, w, c)."""
+    torch = _torch()
+    if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 4:
+        raise SsdHipError("ssd7 convolution: %s must be a 4-D bfloat16 CUDA tensor" % name)
+    if not t.permute(0, 2, 3, 1).is_contiguous():
+        raise SsdHipError("ssd7 convolution: %s must have NHWC (channels_last) memory" % name)
+    b, c, h, w = t.shape
+    return b, h, w, c
+
+
+def ssd7_conv_geometry(cin, cout, kernel):
+    """Whether (Cin, Cout, kernel) is one of SSD7's seven convolutions -- what `ssd7_conv_bias` and `ssd7_conv_wgrad` cover."""
+    return int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(kernel))) != 0
+
+
+def ssd7_conv_bias(x, packed, bias, cout, kernel, out=None):
+    """Conv2D(kernel, 'same') + bias of SSD7's training step on the kernels of `conv_bn_elu` with a plain epilogue
+    (ssdhip_conv_same_bias_nhwc_bf16): y = bf16(acc + float(bias)).  x (B, Cin, H, W) bf16 with NHWC memory; packed: the filter image
+    (`conv_bn_elu_pack` / `ssd7_pack_filters`); bias (Cout,) bf16 or None.  The data gradient of a 3 x 3 layer is this call on dL/dy
+    with the flipped image and no bias.  Returns (B, Cout, H, W) bf16 with NHWC memory."""
+    torch = _torch()
+    b, h, w, cin = _ssd7_map(x, "x")
+    nbytes = int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(kernel)))
+    if nbytes == 0:
+        raise SsdHipError("ssd7_conv_bias: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, kernel))
+    if not packed.is_cuda or packed.dtype != torch.bfloat16 or not packed.is_contiguous() or packed.numel() * 2 != nbytes:
+        raise SsdHipError("ssd7_conv_bias: `packed` must be the %d-byte bf16 filter image of this geometry" % nbytes)
+    if bias is not None and (not bias.is_cuda or bias.dtype != torch.bfloat16 or bias.numel() != cout or not bias.is_contiguous()):
+        raise SsdHipError("ssd7_conv_bias: bias must be a contiguous (%d,) bfloat16 CUDA tensor" % cout)
+    if out is None:
+        out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    elif _ssd7_map(out, "out") != (b, h, w, cout):
+        raise SsdHipError("ssd7_conv_bias: `out` must be a (%d, %d, %d, %d) bf16 tensor with NHWC memory" % (b, cout, h, w))
+    launch("ssdhip_conv_same_bias_nhwc_bf16", x.device, _ptr(x), _ptr(packed), _ptr(bias), _ptr(out), b, h, w, cin, int(cout), int(kernel))
+    return out
+
+
+def ssd7_pack_images(weights):
+    """Empty filter images for `ssd7_pack_filters`: (forward images, flipped images) of the (Cout, Cin, k, k) weights; the flipped image
+    of a 5 x 5 layer is None (the first layer has no data gradient)."""
+    torch = _torch()
+    fwd, flipped = [], []
+    for wt in weights:
+        cout, cin, k, _ = wt.shape
+        n = int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(k)))
+        if n == 0:
+            raise SsdHipError("ssd7_pack_images: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, k))
+        fwd.append(torch.empty((n // 2,), dtype=torch.bfloat16, device=wt.device))
+        nt = int(load().ssdhip_conv_bn_elu_pack_bytes(int(cout), int(cin), int(k))) if k == 3 else 0
+        flipped.append(torch.empty((nt // 2,), dtype=torch.bfloat16, device=wt.device) if nt else None)
+    return fwd, flipped
+
+
+def ssd7_pack_filters(weights, fwd, flipped):
+    """ONE launch that writes every byte of the filter images of up to eight layers from their bf16 weights (ssdhip_ssd7_pack_filters;
+    any memory order: the weights' element strides travel in the kernel arguments): `fwd[i]` = `conv_bn_elu_pack(weights[i])` and,
+    where `flipped[i]` is not None, `conv_bn_elu_pack(weights[i].flip(2, 3).transpose(0, 1))`, the data gradient's filters.  Enqueue
+    only, capturable; this is what runs once per training step."""
+    torch = _torch()
+    n = len(weights)
+    if n == 0 or len(fwd) != n or len(flipped) != n:
+        raise SsdHipError("ssd7_pack_filters: one forward and one flipped image (or None) per weight")
+    dev = weights[0].device
+    for wt, f, t in zip(weights, fwd, flipped):
+        if not wt.is_cuda or wt.dtype != torch.bfloat16 or wt.dim() != 4 or wt.shape[2] != wt.shape[3] or wt.device != dev:
+            raise SsdHipError("ssd7_pack_filters: the weights are (Cout, Cin, k, k) bfloat16 tensors on one GPU")
+        cout, cin, k, _ = wt.shape
+        need = (int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(k))),
+                int(load().ssdhip_conv_bn_elu_pack_bytes(int(cout), int(cin), int(k))) if k == 3 else 0)
+        for img, nbytes in ((f, need[0]), (t, need[1])):
+            if img is not None and (nbytes == 0 or not img.is_cuda or img.device != dev or img.dtype != torch.bfloat16
+                                    or not img.is_contiguous() or img.numel() * 2 != nbytes):
+                raise SsdHipError("ssd7_pack_filters: an image does not fit its layer (Cin = %d, Cout = %d, k = %d)" % (cin, cout, k))
+        if f is None:
+            raise SsdHipError("ssd7_pack_filters: every layer needs its forward image")
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in ts])
+    ints = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+    strides = (ctypes.c_longlong * (4 * n))(*[int(v) for wt in weights for v in wt.stride()])
+    launch("ssdhip_ssd7_pack_filters", dev, n, ptrs(weights), ptrs(fwd), ptrs(flipped), ints(wt.shape[1] for wt in weights),
+           ints(wt.shape[0] for wt in weights), ints(wt.shape[2] for wt in weights), strides)
+
+
+def ssd7_conv_wgrad_plan(b, h, w, cin, cout, kernel):
+    """How `ssd7_conv_wgrad` splits its sum over the 8 x 32 position tiles (host arithmetic, ssdhip_ssd7_conv_wgrad_plan):
+    (splits, tiles per split, tiles, tiles of the last split), or None for a geometry the kernel does not cover."""
+    plan = (ctypes.c_int * 4)()
+    if load().ssdhip_ssd7_conv_wgrad_plan(int(b), int(h), int(w), int(cin), int(cout), int(kernel), plan) != 0:
+        return None
+    return tuple(plan)
+
+
+def ssd7_conv_wgrad(x, dy, kernel, like=None):
+    """dL/dw and dL/db of one of SSD7's convolutions (csrc/ssdhip_wgrad7.hip): x (B, Cin, H, W) and dy (B, Cout, H, W) bf16 with NHWC
+    memory.  `like`: a (Cout, Cin, k, k) float32 or bfloat16 tensor -- the outputs take its dtype (bf16: one rounding) and dw its
+    element strides, so that the parameter's gradient needs no framework op; None: float32, dw dense [Cout][k][k][Cin] (channels_last).
+    Splits added in index order: bit-reproducible.  Returns (dw (Cout, Cin, k, k), db (Cout,))."""
+    torch = _torch()
+    b, h, w, cin = _ssd7_map(x, "x")
+    if _ssd7_map(dy, "dy")[:3] != (b, h, w) or dy.device != x.device:
+        raise SsdHipError("ssd7_conv_wgrad: dy must cover x's positions")
+    cout, k, dev = dy.shape[1], int(kernel), x.device
+    need = int(load().ssdhip_ssd7_conv_wgrad_workspace_bytes(b, h, w, cin, cout, k))
+    if need == 0:
+        raise SsdHipError("ssd7_conv_wgrad: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, k))
+    if like is None:
+        dw = torch.empty((cout, k, k, cin), dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+    else:
+        if tuple(like.shape) != (cout, cin, k, k) or like.dtype not in (torch.float32, torch.bfloat16):
+            raise SsdHipError("ssd7_conv_wgrad: `like` must be a (%d, %d, %d, %d) float32 or bfloat16 tensor" % (cout, cin, k, k))
+        dw = torch.empty_strided(like.shape, like.stride(), dtype=like.dtype, device=dev)
+    db = torch.empty((cout,), dtype=dw.dtype, device=dev)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    strides = (ctypes.c_longlong * 4)(*[int(v) for v in dw.stride()])
+    launch("ssdhip_ssd7_conv_wgrad_nhwc_bf16", dev, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), b, h, w, cin, cout, k,
+           int(dw.dtype == torch.bfloat16), strides, _ptr(ws), need)
+    return dw, db
 
 
 def _bn_train_map(t, name):

@@ -34,12 +34,17 @@ namespace {
 constexpr int CBN_THREADS = 256;                         // four waves: wave i owns rows 2 i, 2 i + 1 of a tile
 constexpr int CBN_TH = 8, CBN_TW = 32;                   // output tile
 constexpr int CBN_TAB = 512;                             // LDS: scale[64] | shift[64] float32
+// Epilogue modes.  CBN_BN_ELU: the block of the inference path (below).  CBN_BIAS: the plain convolution of the TRAINING step and its
+// data gradient -- y = bf16(acc + float(bias[c])), one float32 add and one rounding, full-size map only; the bias is the layer's own
+// bf16 parameter, widened here (tab[c]; zeros for a NULL bias, which is what the data gradient passes).
+constexpr int CBN_BN_ELU = 0, CBN_BIAS = 1;
 
 struct CbnParams {
     const unsigned char* x;      // [B, H, W, Cin] bf16
     const unsigned char* w;      // packed filters (ssdhip_conv_bn_elu_pack_bytes)
     const float* scale;          // [Cout]
     const float* shift;          // [Cout]
+    const bf16_t* bias;          // CBN_BIAS: [Cout] bf16 or NULL (no bias)
     unsigned char* y;            // [B, H, W, Cout] or pooled [B, H / 2, W / 2, Cout] bf16
     int B, H, W, Ho, Wo;
     int HT, WT, tiles;           // tile grid per image, tiles = B HT WT
@@ -55,7 +60,7 @@ __device__ __forceinline__ void cbn_tile_origin(const CbnParams& p, int tile, in
 }
 
 // acc[r][nt]: rows h, h + 1 of image b, column w = the lane's (lane & 31), channel (v & 3) + 8 (v >> 2) + 4 (lane >> 5) of tile nt.
-template <int COUT, bool POOL>
+template <int COUT, bool POOL, int EPI>
 __device__ __forceinline__ void cbn_epilogue(const f32x16 (&acc)[2][(COUT + 31) / 32], const float* tab, const CbnParams& p, int b, int h,
                                              int w, int lane) {
     constexpr int NT = (COUT + 31) / 32;
@@ -73,8 +78,12 @@ __device__ __forceinline__ void cbn_epilogue(const f32x16 (&acc)[2][(COUT + 31) 
             for (int r = 0; r < 2; ++r)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float v = fmaf(acc[r][nt][4 * g + i], s[i], t[i]);
-                    e[r][i] = v > 0.f ? v : expm1f(v);
+                    if constexpr (EPI == CBN_BIAS) {
+                        e[r][i] = acc[r][nt][4 * g + i] + s[i];
+                    } else {
+                        const float v = fmaf(acc[r][nt][4 * g + i], s[i], t[i]);
+                        e[r][i] = v > 0.f ? v : expm1f(v);
+                    }
                 }
             if constexpr (POOL) {
                 float m[4];
@@ -97,10 +106,16 @@ __device__ __forceinline__ void cbn_epilogue(const f32x16 (&acc)[2][(COUT + 31) 
         }
 }
 
+template <int EPI>
 __device__ __forceinline__ void cbn_load_tables(float* tab, const CbnParams& p, int cout, int tid) {
     if (tid < 64) {
-        tab[tid] = tid < cout ? p.scale[tid] : 0.f;
-        tab[64 + tid] = tid < cout ? p.shift[tid] : 0.f;
+        if constexpr (EPI == CBN_BIAS) {
+            tab[tid] = (tid < cout && p.bias) ? bf16_float(p.bias[tid]) : 0.f;
+            tab[64 + tid] = 0.f;
+        } else {
+            tab[tid] = tid < cout ? p.scale[tid] : 0.f;
+            tab[64 + tid] = tid < cout ? p.shift[tid] : 0.f;
+        }
     }
 }
 
@@ -116,7 +131,7 @@ struct Cbn3 {
     static_assert(LDS <= 160 * 1024 && CIN % 16 == 0, "LDS budget; whole MFMA steps");
 };
 
-template <int CIN, int COUT, bool POOL>
+template <int CIN, int COUT, bool POOL, int EPI>
 __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p) {
     using G = Cbn3<CIN, COUT>;
     constexpr int NT = G::NT, PS = G::PS, KS = G::KS, CH = G::CH, HC = G::HC, NCHUNK = G::NCHUNK, NLD = G::NLD;
@@ -155,7 +170,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
     fetch(tile, raw);
     for (int i = tid; i < G::WBYTES / 16; i += CBN_THREADS)              // the resident filters: the packed image as it is
         reinterpret_cast<u32x4*>(wl)[i] = reinterpret_cast<const u32x4*>(p.w)[i];
-    cbn_load_tables(tab, p, COUT, tid);
+    cbn_load_tables<EPI>(tab, p, COUT, tid);
 
     const unsigned char* bptr = hl + ((2 * wave) * HC + r31) * PS + khalf * 16;
     const unsigned char* aptr = wl + r31 * PS + khalf * 16;
@@ -187,7 +202,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
             }
         int b, h0, w0;
         cbn_tile_origin(p, tile, b, h0, w0);
-        cbn_epilogue<COUT, POOL>(acc, tab, p, b, h0 + 2 * wave, w0 + r31, lane);
+        cbn_epilogue<COUT, POOL, EPI>(acc, tab, p, b, h0 + 2 * wave, w0 + r31, lane);
         __syncthreads();                                 // every wave is done with the halo before the next one overwrites it
     }
 }
@@ -198,7 +213,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
 constexpr int CBN5_HR = CBN_TH + 4, CBN5_HC = CBN_TW + 4, CBN5_ROW = CBN5_HC * 3, CBN5_RS = 224, CBN5_NEL = CBN5_HR * CBN5_ROW;
 constexpr int CBN5_NLD = (CBN5_NEL + CBN_THREADS - 1) / CBN_THREADS;
 
-template <bool POOL>
+template <bool POOL, int EPI>
 __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p) {
     __shared__ __attribute__((aligned(16))) unsigned char cbn_lds[CBN_TAB + CBN5_HR * CBN5_RS];
     float* tab = reinterpret_cast<float*>(cbn_lds);
@@ -235,7 +250,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p)
     bf16x8 a[5];
 #pragma unroll
     for (int kh = 0; kh < 5; ++kh) a[kh] = *reinterpret_cast<const bf16x8*>(p.w + ((kh * 32 + r31) * 16 + khalf * 8) * 2);
-    cbn_load_tables(tab, p, 32, tid);
+    cbn_load_tables<EPI>(tab, p, 32, tid);
     if (tid < CBN5_HR * 2) *reinterpret_cast<unsigned*>(hl + (tid >> 1) * CBN5_RS + CBN5_ROW * 2 + (tid & 1) * 4) = 0u;
 
     // the lane's operand of kernel row kh: 16 bytes at 6 bytes a column, i.e. on a half-dword boundary for odd columns -- five aligned
@@ -267,7 +282,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p)
             }
         int b, h0, w0;
         cbn_tile_origin(p, tile, b, h0, w0);
-        cbn_epilogue<32, POOL>(acc, tab, p, b, h0 + 2 * wave, w0 + r31, lane);
+        cbn_epilogue<32, POOL, EPI>(acc, tab, p, b, h0 + 2 * wave, w0 + r31, lane);
         __syncthreads();
     }
 }
@@ -282,10 +297,10 @@ int cbn_cu_count() {
     return n;
 }
 
-template <int CIN, int COUT, bool POOL>
+template <int CIN, int COUT, bool POOL, int EPI = CBN_BN_ELU>
 int cbn_launch3(const CbnParams& p, hipStream_t stream) {
     using G = Cbn3<CIN, COUT>;
-    auto fn = convbn3_kernel<CIN, COUT, POOL>;
+    auto fn = convbn3_kernel<CIN, COUT, POOL, EPI>;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
     if (attr != hipSuccess) return SSDHIP_E_LAUNCH;
     int per_cu = (160 * 1024) / G::LDS;                  // workgroups that fit a CU's LDS; two keep a CU busy across the barriers
@@ -301,6 +316,49 @@ int cbn_launch3(const CbnParams& p, int pool, hipStream_t stream) {
     return pool ? cbn_launch3<CIN, COUT, true>(p, stream) : cbn_launch3<CIN, COUT, false>(p, stream);
 }
 
+// ---- filter images, refreshed on the device ----------------------------------------------------------------------------------------
+// One launch writes EVERY byte of every image of a table of layers (padding rows and columns included: nothing relies on an earlier
+// fill) from the bf16 parameters, read through their four element strides: the forward image of ssdhip_conv_bn_elu_pack_bytes and, for
+// the 3 x 3 layers, the image of the data gradient's filters, w.flip(2, 3).transpose(0, 1) -- (Cin, Cout) swapped, taps flipped.
+constexpr int CBN_PACK_MAX = 8;
+struct CbnPackLayer {
+    const bf16_t* w;
+    bf16_t* fwd;
+    bf16_t* flip;                // NULL: not wanted (always for the 5 x 5 layer, which has no data gradient)
+    long long s[4];              // element strides of (Cout, Cin, kh, kw)
+    int cin, cout, kernel;
+};
+struct CbnPackTable {
+    CbnPackLayer layer[CBN_PACK_MAX];
+};
+
+// elements of the image of a (rows = Cout, cols = Cin) 3 x 3 layer
+__host__ __device__ inline int cbn_image3_elems(int cin, int cout) { return 9 * ((cout + 31) / 32) * 32 * (cin + 8); }
+
+__global__ __launch_bounds__(256) void cbn_pack_kernel(const CbnPackTable t) {
+    const CbnPackLayer& L = t.layer[blockIdx.y >> 1];
+    const bool flip = blockIdx.y & 1;
+    bf16_t* out = flip ? L.flip : L.fwd;
+    if (!out || !L.w) return;
+    const int step = (int)(gridDim.x * blockDim.x);
+    if (L.kernel == 5) {                                 // [kh][32][16], k = 3 kw + ci, k = 15 zero
+        for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < 5 * 32 * 16; i += step) {
+            const int k = i & 15, co = (i >> 4) & 31, kh = i >> 9;
+            out[i] = k < 15 ? L.w[co * L.s[0] + (k % 3) * L.s[1] + kh * L.s[2] + (k / 3) * L.s[3]] : (bf16_t)0;
+        }
+        return;
+    }
+    // the image's rows / columns: forward (Cout, Cin); flipped (Cin, Cout), element (kh, kw, r, c) = w[c][r][2 - kh][2 - kw]
+    const int rows = flip ? L.cin : L.cout, cols = flip ? L.cout : L.cin, rp = (rows + 31) / 32 * 32, cp = cols + 8;
+    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < 9 * rp * cp; i += step) {
+        const int c = i % cp, q = i / cp, r = q % rp, tap = q / rp, kh = tap / 3, kw = tap - 3 * kh;
+        bf16_t v = 0;
+        if (r < rows && c < cols)
+            v = flip ? L.w[c * L.s[0] + r * L.s[1] + (2 - kh) * L.s[2] + (2 - kw) * L.s[3]] : L.w[r * L.s[0] + c * L.s[1] + kh * L.s[2] + kw * L.s[3]];
+        out[i] = v;
+    }
+}
+
 }  // namespace
 }  // namespace ssdhip
 
@@ -313,17 +371,21 @@ extern "C" size_t ssdhip_conv_bn_elu_pack_bytes(int Cin, int Cout, int kernel) {
     return ok ? (size_t)9 * ((Cout + 31) / 32) * 32 * (Cin * 2 + 16) : 0;
 }
 
-extern "C" int ssdhip_conv_bn_elu_nhwc_bf16(const void* x, const void* w_packed, const float* scale, const float* shift, void* y, int B, int H,
-                                            int W, int Cin, int Cout, int kernel, int pool, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !w_packed || !scale || !shift || !y || B <= 0 || H <= 0 || W <= 0) return SSDHIP_E_BADARG;
+namespace ssdhip {
+namespace {
+// Both epilogues: the checks every launch shares, then the geometry's instantiation (scale / shift: CBN_BN_ELU; bias: CBN_BIAS).
+int cbn_run(int epi, const void* x, const void* w_packed, const float* scale, const float* shift, const void* bias, void* y, int B, int H, int W,
+            int Cin, int Cout, int kernel, int pool, hipStream_t stream) {
+    if (!x || !w_packed || !y || B <= 0 || H <= 0 || W <= 0) return SSDHIP_E_BADARG;
+    if (epi == CBN_BN_ELU && (!scale || !shift)) return SSDHIP_E_BADARG;
     if (ssdhip_conv_bn_elu_pack_bytes(Cin, Cout, kernel) == 0) return SSDHIP_E_BADARG;
     if (pool && (H < 2 || W < 2)) return SSDHIP_E_BADARG;
-    if ((((uintptr_t)w_packed | (uintptr_t)y) & 15) || ((uintptr_t)x & (kernel == 3 ? 15 : 1)) || (((uintptr_t)scale | (uintptr_t)shift) & 3))
+    if ((((uintptr_t)w_packed | (uintptr_t)y) & 15) || ((uintptr_t)x & (kernel == 3 ? 15 : 1)) || (((uintptr_t)scale | (uintptr_t)shift) & 3) ||
+        ((uintptr_t)bias & 1))
         return SSDHIP_E_BADARG;
     CbnParams p;
     p.x = static_cast<const unsigned char*>(x); p.w = static_cast<const unsigned char*>(w_packed);
-    p.scale = scale; p.shift = shift; p.y = static_cast<unsigned char*>(y);
+    p.scale = scale; p.shift = shift; p.bias = static_cast<const bf16_t*>(bias); p.y = static_cast<unsigned char*>(y);
     p.B = B; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;
     p.HT = (H + CBN_TH - 1) / CBN_TH; p.WT = (W + CBN_TW - 1) / CBN_TW;
     const long long tiles = (long long)B * p.HT * p.WT;
@@ -332,11 +394,59 @@ extern "C" int ssdhip_conv_bn_elu_nhwc_bf16(const void* x, const void* w_packed,
     if (kernel == 5) {
         const long long cap = (long long)cbn_cu_count() * 4;
         const int grid = (int)(tiles < cap ? tiles : cap);
-        if (pool) hipLaunchKernelGGL(convbn5_kernel<true>, dim3(grid), dim3(CBN_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL(convbn5_kernel<false>, dim3(grid), dim3(CBN_THREADS), 0, stream, p);
+        if (epi == CBN_BIAS) hipLaunchKernelGGL((convbn5_kernel<false, CBN_BIAS>), dim3(grid), dim3(CBN_THREADS), 0, stream, p);
+        else if (pool) hipLaunchKernelGGL((convbn5_kernel<true, CBN_BN_ELU>), dim3(grid), dim3(CBN_THREADS), 0, stream, p);
+        else hipLaunchKernelGGL((convbn5_kernel<false, CBN_BN_ELU>), dim3(grid), dim3(CBN_THREADS), 0, stream, p);
         return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    }
+    if (epi == CBN_BIAS) {
+        if (Cin == 32) return cbn_launch3<32, 48, false, CBN_BIAS>(p, stream);
+        if (Cin == 48)
+            return Cout == 64 ? cbn_launch3<48, 64, false, CBN_BIAS>(p, stream)
+                              : Cout == 48 ? cbn_launch3<48, 48, false, CBN_BIAS>(p, stream) : cbn_launch3<48, 32, false, CBN_BIAS>(p, stream);
+        return Cout == 64 ? cbn_launch3<64, 64, false, CBN_BIAS>(p, stream) : cbn_launch3<64, 48, false, CBN_BIAS>(p, stream);
     }
     if (Cin == 32) return cbn_launch3<32, 48>(p, pool, stream);
     if (Cin == 48) return Cout == 64 ? cbn_launch3<48, 64>(p, pool, stream) : Cout == 48 ? cbn_launch3<48, 48>(p, pool, stream) : cbn_launch3<48, 32>(p, pool, stream);
     return Cout == 64 ? cbn_launch3<64, 64>(p, pool, stream) : cbn_launch3<64, 48>(p, pool, stream);
+}
+}  // namespace
+}  // namespace ssdhip
+
+extern "C" int ssdhip_conv_bn_elu_nhwc_bf16(const void* x, const void* w_packed, const float* scale, const float* shift, void* y, int B, int H,
+                                            int W, int Cin, int Cout, int kernel, int pool, void* stream_) {
+    return cbn_run(CBN_BN_ELU, x, w_packed, scale, shift, nullptr, y, B, H, W, Cin, Cout, kernel, pool, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int ssdhip_conv_same_bias_nhwc_bf16(const void* x, const void* w_packed, const void* bias, void* y, int B, int H, int W, int Cin,
+                                               int Cout, int kernel, void* stream_) {
+    return cbn_run(CBN_BIAS, x, w_packed, nullptr, nullptr, bias, y, B, H, W, Cin, Cout, kernel, 0, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int ssdhip_ssd7_pack_filters(int n_layers, const void* const* weights, void* const* fwd, void* const* flipped, const int* Cin,
+                                        const int* Cout, const int* kernel, const long long* strides, void* stream_) {
+    if (n_layers <= 0 || n_layers > CBN_PACK_MAX || !weights || !fwd || !flipped || !Cin || !Cout || !kernel || !strides) return SSDHIP_E_BADARG;
+    CbnPackTable t = {};
+    int most = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        CbnPackLayer& L = t.layer[i];
+        if (!weights[i] || !fwd[i] || ssdhip_conv_bn_elu_pack_bytes(Cin[i], Cout[i], kernel[i]) == 0) return SSDHIP_E_BADARG;
+        if (kernel[i] == 5 && flipped[i]) return SSDHIP_E_BADARG;       // the first layer has no data gradient
+        if (((uintptr_t)weights[i] | (uintptr_t)fwd[i] | (uintptr_t)flipped[i]) & 1) return SSDHIP_E_BADARG;
+        long long reach = 0;                              // the farthest element the strides address: a sanity bound, not the tensor's size
+        const int dims[4] = {Cout[i], Cin[i], kernel[i], kernel[i]};
+        for (int d = 0; d < 4; ++d) {
+            if (strides[4 * i + d] < 0) return SSDHIP_E_BADARG;
+            reach += strides[4 * i + d] * (dims[d] - 1);
+            L.s[d] = strides[4 * i + d];
+        }
+        if (reach > 0x3fffffffLL) return SSDHIP_E_BADARG;
+        L.w = static_cast<const bf16_t*>(weights[i]); L.fwd = static_cast<bf16_t*>(fwd[i]); L.flip = static_cast<bf16_t*>(flipped[i]);
+        L.cin = Cin[i]; L.cout = Cout[i]; L.kernel = kernel[i];
+        const int n = kernel[i] == 5 ? 5 * 32 * 16 : cbn_image3_elems(Cin[i] > Cout[i] ? Cin[i] : Cout[i], Cin[i] > Cout[i] ? Cin[i] : Cout[i]);
+        most = n > most ? n : most;
+    }
+    const int bx = (most + 256 * 4 - 1) / (256 * 4);      // about four elements a thread in the largest image
+    hipLaunchKernelGGL(cbn_pack_kernel, dim3(bx, 2 * n_layers), dim3(256), 0, static_cast<hipStream_t>(stream_), t);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }

@@ -1,7 +1,7 @@
 """The training step's autograd functions over the libssdhip kernels (csrc/ssdhip_train.hip, ssdhip_wgrad.hip and the forward
 kernels of the inference path): one node per convolution layer [+ pooling], per pair of predictor heads, for the prediction assembly,
-for a max-pool and for what follows a convolution in a block of SSD7 (batch-statistics BatchNorm + ELU [+ pool],
-csrc/ssdhip_bntrain.hip).  `SSDModel` (models/_common.py) applies them; which forward kernel a layer runs is `_conv_select`'s choice."""
+for a max-pool, for what follows a convolution in a block of SSD7 (batch-statistics BatchNorm + ELU [+ pool],
+csrc/ssdhip_bntrain.hip) and for that convolution itself (csrc/ssdhip_convbn.hip, ssdhip_wgrad7.hip).  `SSDModel` (models/_common.py) applies them; which forward kernel a layer runs is `_conv_select`'s choice."""
 import torch
 
 from .. import _native as nat
@@ -314,3 +314,39 @@ class _BnEluPoolFn(torch.autograd.Function):
                                                       None if g_full is None else _nhwc(g_full),
                                                       None if g_pooled is None else _nhwc(g_pooled))
         return dy, dgamma.to(gamma.dtype), dbeta.to(beta.dtype), None, None, None, None, None, None
+
+
+class _Ssd7ConvFn(torch.autograd.Function):
+    """A trunk convolution of SSD7's training step as one autograd node over libssdhip: forward = the block's MFMA kernel with the plain
+    epilogue (convolution + bias, csrc/ssdhip_convbn.hip); backward = the same kernel on dL/dy with the transposed, tap-flipped filter
+    image where the input needs a gradient (the 5 x 5 first layer's never does), and the weight / bias gradient of
+    csrc/ssdhip_wgrad7.hip, written in the parameters' own dtype and memory order -- no framework op on either side.
+    `image` / `flipped`: the layer's packed filters, refreshed by the model once per step (`nat.ssd7_pack_filters`); they are the
+    model's buffers, not saved tensors.  Saves x -- the previous block's output, alive anyway -- and nothing derived; of the weight it
+    keeps the parameter itself (no copy), for the gradient's layout and for this check: `flipped` is rewritten by every forward, so the
+    data gradient is only right while the weights are the ones this forward saw.  Gradient accumulation over unchanged weights is
+    fine; a backward that runs after an in-place weight update raises instead of using the newer filters."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, image, flipped):
+        x = _nhwc(x.detach())
+        ctx.save_for_backward(x)
+        ctx.flipped, ctx.weight, ctx.version = flipped, weight, weight._version
+        return nat.ssd7_conv_bias(x, image, bias.detach(), weight.shape[0], weight.shape[2])
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        weight = ctx.weight
+        gy = _nhwc(gy)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            if ctx.flipped is None:
+                raise RuntimeError("_Ssd7ConvFn: the first layer has no data gradient (its input must not require one)")
+            if weight._version != ctx.version:
+                raise RuntimeError("_Ssd7ConvFn: the weights changed in place between this forward and its backward; the data "
+                                   "gradient's filter image follows the newest forward")
+            gx = nat.ssd7_conv_bias(gy, ctx.flipped, None, x.shape[1], weight.shape[2])
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gw, gb = nat.ssd7_conv_wgrad(x, gy, weight.shape[2], like=weight)
+        return gx, (gw if ctx.needs_input_grad[1] else None), (gb if ctx.needs_input_grad[2] else None), None, None

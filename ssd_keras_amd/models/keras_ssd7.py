@@ -11,7 +11,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from .. import _native as nat
-from ._train_fns import _BnEluPoolFn
+from ._train_fns import _BnEluPoolFn, _Ssd7ConvFn
 from ._common import SSDModel, he_normal_, make_priorboxes, pool_out, resolve_anchor_config
 
 
@@ -35,7 +35,7 @@ class SSD7(SSDModel):
                                           ['anchors4', 'anchors5', 'anchors6', 'anchors7'])
         he_normal_(self)
 
-    def fused_blocks(self, enable=True, training=False):
+    def fused_blocks(self, enable=True, training=False, convolutions=False):
         """Opt in to (or, with False, out of) running every Conv2D -> BatchNormalization -> ELU [-> MaxPooling2D] block of a bf16 model
         in eval mode under no_grad as ONE libssdhip launch (csrc/ssdhip_convbn.hip): the block's map is rounded to bf16 once instead of
         three times and is never written and read back between the convolution, the normalisation, the activation and the pool.  Off by
@@ -44,14 +44,25 @@ class SSD7(SSDModel):
         a bf16 CUDA model in train() mode then runs what lies between a block's convolution and the next one's -- batch statistics, the
         running-statistics update, the normalisation, ELU and the pool, and their backward -- as libssdhip launches with one autograd
         node per block (csrc/ssdhip_bntrain.hip, models/_train_fns.py: _BnEluPoolFn); the convolutions stay the framework's.  A block
-        whose shape those kernels do not cover keeps the default chain.  Returns the model."""
+        whose shape those kernels do not cover keeps the default chain.
+        `convolutions=True` (with `training=True`; off by default, and every call without it behaves as before) moves the seven trunk
+        convolutions of that training path to libssdhip as well: one launch at the top of `features` rebuilds the packed filter images
+        from the current parameters, then each block in TRAIN_CONVS runs `_Ssd7ConvFn` -- forward on the inference path's MFMA kernels
+        with a bias epilogue, data gradient on the same kernels with the flipped image, weight / bias gradient in
+        csrc/ssdhip_wgrad7.hip -- followed by `_BnEluPoolFn`.  The `nn.Conv2d` modules in `self.convs` are NOT called on this route
+        (their parameters are read directly), so forward hooks registered on them do not fire.  Returns the model."""
         self.__dict__["_fused_blocks"] = bool(enable)
         self.__dict__["_fused_blocks_training"] = bool(enable) and bool(training)
+        self.__dict__["_fused_blocks_convs"] = bool(enable) and bool(training) and bool(convolutions)
         return self
 
     # The blocks the training path takes when it is switched on (a set, so that a measurement can take one out: DESIGN.md 4.4,
     # "SSD7 training", has the per-block numbers behind it).
     TRAIN_BLOCKS = frozenset(range(7))
+    # ... and the blocks whose convolution runs in libssdhip under `convolutions=True`: those whose forward, data gradient and weight
+    # gradient together beat the framework's, summed over batch 8 and 32 (same section: the per-layer timings).  Blocks 4-7 -- maps of
+    # 37 x 37 and below -- do not, and keep the framework's convolution.
+    TRAIN_CONVS = frozenset((0, 1, 2))
 
     def _fused_blocks_on(self, x):
         return (self.__dict__.get("_fused_blocks", False) and not self.training and self._fused(x)
@@ -61,9 +72,30 @@ class SSD7(SSDModel):
         return (self.__dict__.get("_fused_blocks_training", False) and self.training and x.is_cuda and x.dtype == torch.bfloat16
                 and self.convs[0].weight.dtype == torch.bfloat16)
 
-    def _train_block(self, i, x):
+    def _train_conv_images(self):
+        """{layer: (forward image, flipped image or None)} of the convolutions `convolutions=True` runs, or None when the route is off:
+        the model's own buffers (allocated once per device, so a captured step keeps reading them), REWRITTEN from the current
+        parameters by one launch here -- `features` calls this once per step."""
+        if not self.__dict__.get("_fused_blocks_convs", False):
+            return None
+        dev = self.convs[0].weight.device
+        hit = self.__dict__.get("_conv_images")
+        if hit is None or hit[0] != dev or hit[1] != self.TRAIN_CONVS:
+            layers = [i for i in sorted(self.TRAIN_CONVS)
+                      if self.convs[i].bias is not None and self.convs[i].weight.dtype == self.convs[i].bias.dtype == torch.bfloat16
+                      and nat.ssd7_conv_geometry(self.convs[i].in_channels, self.convs[i].out_channels, self.convs[i].kernel_size[0])]
+            hit = (dev, self.TRAIN_CONVS, layers) + nat.ssd7_pack_images([self.convs[i].weight for i in layers])
+            self.__dict__["_conv_images"] = hit
+        _, _, layers, fwd, flipped = hit
+        if not layers:
+            return {}
+        nat.ssd7_pack_filters([self.convs[i].weight.detach() for i in layers], fwd, flipped)
+        return {i: (fwd[n], flipped[n]) for n, i in enumerate(layers)}
+
+    def _train_block(self, i, x, images=None):
         """Block i of the training path: (the map for the next block, the map for the predictor heads or None); None where the kernels
-        do not cover the block (the caller runs the default chain, which raises for a single value per channel as the framework does)."""
+        do not cover the block (the caller runs the default chain, which raises for a single value per channel as the framework does).
+        images: `_train_conv_images()` -- a layer found there runs its convolution in libssdhip too."""
         bn = self.bns[i]
         pool, keep = i < 6, i >= 3
         b, _, h, w = x.shape
@@ -71,7 +103,15 @@ class SSD7(SSDModel):
                 or bn.weight.dtype != bn.bias.dtype or bn.running_mean.dtype != bn.running_var.dtype
                 or nat.bn_elu_train_blocks(b * h * w, bn.num_features) == 0 or (pool and (h < 2 or w < 2))):
             return None
-        y = self.convs[i](x)
+        conv = self.convs[i]
+        image, flipped = images.get(i, (None, None)) if images else (None, None)
+        if image is None or (flipped is None and x.requires_grad):
+            y = conv(x)
+        elif torch.is_grad_enabled():
+            y = _Ssd7ConvFn.apply(x, conv.weight, conv.bias, image, flipped)
+        else:
+            y = nat.ssd7_conv_bias(x if x.permute(0, 2, 3, 1).is_contiguous() else x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2),
+                                   image, conv.bias.detach(), conv.out_channels, conv.kernel_size[0])
         bn.num_batches_tracked.add_(1)
         args = (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, pool, keep)
         if torch.is_grad_enabled():
@@ -138,8 +178,9 @@ class SSD7(SSDModel):
                         x = self.max_pool(x, 2, 2)
             return feats
         train_blocks = self._train_blocks_on(x)
+        images = self._train_conv_images() if train_blocks else None
         for i in range(7):
-            done = self._train_block(i, x) if train_blocks else None
+            done = self._train_block(i, x, images) if train_blocks else None
             if done is not None:
                 x, feat = done
                 if feat is not None:
