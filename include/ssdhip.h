@@ -791,6 +791,11 @@ int ssdhip_sgd_momentum_step(int n_tensors, void* const* params_h, const void* c
  *                              v = beta_2 * v + (1 - beta_2) * (g * g);  vhat = max(vhat, v) (amsgrad; vhat then replaces v below);
  *                              p = p - lr_t * m / (sqrt(v) + epsilon)
  *                          The tensor table travels in the kernel arguments (72 tensors per launch): no upload, no host synchronisation.
+ * ssdhip_adam_step_bf16    the same step for bf16 parameters with float32 MASTER weights: parameter and gradient are bf16, master, m, v
+ *                          (and vhat) float32, all named as above and 16-byte aligned.  Per element the sequence above runs on the master
+ *                          with g = float(bf16 gradient) (exact; weight decay reads the master), then p = bf16(master), round to nearest
+ *                          even; p is written, never read.  Same state block, same tick: the master follows, bit for bit, what
+ *                          ssdhip_adam_step does to a float32 parameter fed the same gradients.  64 tensors per launch.
  * ssdhip_optim_set_lr      a group's base learning rate lr0, e.g. between two replays of a captured step. */
 #define SSDHIP_ADAM_MAX_GROUPS 64
 typedef struct ssdhip_adam_group {
@@ -809,6 +814,8 @@ int ssdhip_adam_state_init(void* state, int n_groups, int group, double lr, doub
                            double weight_decay, long long iterations, void* stream);
 int ssdhip_adam_step(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* m_h, void* const* v_h,
                      void* const* vhat_h, const long long* numel_h, int group, void* state, int tick, void* stream);
+int ssdhip_adam_step_bf16(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h, void* const* m_h,
+                          void* const* v_h, void* const* vhat_h, const long long* numel_h, int group, void* state, int tick, void* stream);
 int ssdhip_optim_set_lr(void* state, int group, double lr, void* stream);
 
 /* keras.optimizers.SGD(lr, momentum, decay, nesterov) (ssd300_training.ipynb:169, under its LearningRateScheduler) with its scalars on the
@@ -835,7 +842,11 @@ int ssdhip_optim_set_lr(void* state, int group, double lr, void* stream);
  *                         rule 0 without Nesterov and decay is ssdhip_sgd_momentum_step's arithmetic on the same float32 scalars: the
  *                         results are bit-identical.  The two rules agree (in real numbers) only while lr_t stays constant: a velocity
  *                         keeps the rate it was built under, a momentum buffer is rescaled as a whole by the new one.  The tensor table
- *                         travels in the kernel arguments (80 tensors per launch): no upload, no host synchronisation. */
+ *                         travels in the kernel arguments (80 tensors per launch): no upload, no host synchronisation.
+ * ssdhip_sgd_step_bf16    the same step for bf16 parameters with float32 MASTER weights: parameter and gradient are bf16, master and
+ *                         buffer float32.  The sequence above runs on the master with g = float(bf16 gradient) (exact; weight decay
+ *                         reads the master), then p = bf16(master), round to nearest even; p is written, never read.  Same state block,
+ *                         same tick, 80 tensors per launch. */
 typedef struct ssdhip_sgd_group {
     double lr, decay, momentum;             /* lr0 and the hyperparameters the tick reads */
     float lr_t, momentum_f, weight_decay;   /* what the update reads */
@@ -852,6 +863,8 @@ int ssdhip_sgd_state_init(void* state, int n_groups, int group, double lr, doubl
 int ssdhip_sgd_set_lr(void* state, int group, double lr, void* stream);
 int ssdhip_sgd_step(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* bufs_h, const long long* numel_h,
                     int group, void* state, int rule, int nesterov, int tick, void* stream);
+int ssdhip_sgd_step_bf16(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h, void* const* bufs_h,
+                         const long long* numel_h, int group, void* state, int rule, int nesterov, int tick, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The decisions of the original-SSD augmentation chain for a whole batch in ONE launch (csrc/ssdhip_augment.hip): SSDExpand ->

@@ -166,11 +166,13 @@ SIGNATURES = {
     "ssdhip_adam_state_bytes": (_SZ, [_I]),
     "ssdhip_adam_state_init": (_I, [_P, _I, _I] + [_D] * 6 + [_LL, _P]),
     "ssdhip_adam_step": (_I, [_I] + [_P] * 6 + [_I, _P, _I, _P]),
+    "ssdhip_adam_step_bf16": (_I, [_I] + [_P] * 7 + [_I, _P, _I, _P]),
     "ssdhip_optim_set_lr": (_I, [_P, _I, _D, _P]),
     "ssdhip_sgd_state_bytes": (_SZ, [_I]),
     "ssdhip_sgd_state_init": (_I, [_P, _I, _I] + [_D] * 4 + [_LL, _P]),
     "ssdhip_sgd_set_lr": (_I, [_P, _I, _D, _P]),
     "ssdhip_sgd_step": (_I, [_I] + [_P] * 4 + [_I, _P, _I, _I, _I, _P]),
+    "ssdhip_sgd_step_bf16": (_I, [_I] + [_P] * 5 + [_I, _P, _I, _I, _I, _P]),
     "ssdhip_augment_plans": (_I, [_P] + [_I] * 6 + [_P] * 6),
     "ssdhip_ssd_augment_decide": (_I, [_PARAMS, _I] + [_P] * 8),
     "ssdhip_ssd_augment_decide_stream": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 10),
@@ -747,6 +749,32 @@ def adam_step(table, block, group, tick):
     launch("ssdhip_adam_step", device, n, pp, gp, mp, vp, hp, nn, int(group), _ptr(block), 1 if tick else 0)
 
 
+def _master_table(what, params, grads, float_cols, device):
+    """Checks and pointer arrays of the bf16 tables: `params` / `grads` dense bf16, every column of `float_cols` dense float32, one
+    size per row, 16-byte aligned, on `device`."""
+    torch = _torch()
+    n = len(params)
+    for row in zip(params, grads, *float_cols):
+        for k, t in enumerate(row):
+            want = torch.bfloat16 if k < 2 else torch.float32
+            if t.dtype != want or not t.is_contiguous() or t.numel() != row[0].numel() or t.data_ptr() % 16 or t.device != device:
+                raise SsdHipError("%s: parameter and gradient must be dense bf16, master and buffers dense float32, of one size on one "
+                                  "device" % what)
+    vp, ll = ctypes.c_void_p * n, ctypes.c_longlong * n
+    return vp, [vp(*[t.data_ptr() for t in col]) for col in [params, grads] + list(float_cols)], ll(*[p.numel() for p in params])
+
+
+def adam_table_bf16(params, grads, masters, ms, vs, vhats, device):
+    """The HOST table of ssdhip_adam_step_bf16: bf16 parameter and gradient, float32 master, m, v and (amsgrad) vhat of every tensor."""
+    _, ptrs, nn = _master_table("adam_table_bf16", params, grads, [masters, ms, vs] + ([vhats] if vhats is not None else []), device)
+    return (device, len(params)) + tuple(ptrs) + ((None,) if vhats is None else ()) + (nn,)
+
+
+def adam_step_bf16(table, block, group, tick):
+    device, n, pp, gp, wp, mp, vp, hp, nn = table
+    launch("ssdhip_adam_step_bf16", device, n, pp, gp, wp, mp, vp, hp, nn, int(group), _ptr(block), 1 if tick else 0)
+
+
 def optim_set_lr(block, group, lr):
     launch("ssdhip_optim_set_lr", block.device, _ptr(block), int(group), float(lr))
 
@@ -786,6 +814,18 @@ def sgd_set_lr(block, group, lr):
 def sgd_step(table, block, group, rule, nesterov, tick):
     device, n, pp, gp, mp, nn = table
     launch("ssdhip_sgd_step", device, n, pp, gp, mp, nn, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0)
+
+
+def sgd_table_bf16(params, grads, masters, bufs, device):
+    """The HOST table of ssdhip_sgd_step_bf16: bf16 parameter and gradient, float32 master and buffer of every tensor."""
+    _, ptrs, nn = _master_table("sgd_table_bf16", params, grads, [masters, bufs], device)
+    return (device, len(params)) + tuple(ptrs) + (nn,)
+
+
+def sgd_step_bf16(table, block, group, rule, nesterov, tick):
+    device, n, pp, gp, wp, mp, nn = table
+    launch("ssdhip_sgd_step_bf16", device, n, pp, gp, wp, mp, nn, int(group), _ptr(block), int(rule), 1 if nesterov else 0,
+           1 if tick else 0)
 
 
 def maxpool_bwd(x, gy, kernel, stride, pad=0):

@@ -21,6 +21,10 @@
 //                           between replays (ssd300_training.ipynb's LearningRateScheduler).  RULE 0: torch's buffer, RULE 1: Keras 2.x
 //                           SGD.get_updates' velocity (v = momentum v - lr g; p += v), each with and without Nesterov.  20 bytes per
 //                           parameter, as sgd_momentum_kernel.
+//   sgd_step_bf16_kernel<RULE, NESTEROV>
+//                           the same update (sgd_update) on a float32 MASTER copy of a bf16 parameter: bf16 gradient in (exact in
+//                           float32), weight decay on the master, p = bf16(master) out, round to nearest even, never read.  Eight values
+//                           per thread and pass; 20 bytes per parameter as well (2 + 8 + 8 + 2).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -301,6 +305,73 @@ __global__ __launch_bounds__(256) void sgd_step_kernel(const SgdArgs a, const ss
 }
 static_assert(sizeof(SgdArgs) + sizeof(void*) + 2 * sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
 
+// Four pointers + count + first block = 44 bytes per tensor: 80 tensors are 3524 bytes.
+constexpr int SGD_BF16_CHUNK = 80;
+struct SgdBf16Args {
+    bf16_t* p[SGD_BF16_CHUNK];                             // written only
+    const bf16_t* g[SGD_BF16_CHUNK];
+    float* w[SGD_BF16_CHUNK];                              // the float32 master
+    float* m[SGD_BF16_CHUNK];
+    long long n[SGD_BF16_CHUNK];
+    int block0[SGD_BF16_CHUNK];
+    int count;
+};
+static_assert(sizeof(SgdBf16Args) + sizeof(void*) + 2 * sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
+
+template <int RULE, bool NESTEROV>
+__global__ __launch_bounds__(256) void sgd_step_bf16_kernel(const SgdBf16Args a, const ssdhip_sgd_state* __restrict__ st, int group) {
+    const int tid = threadIdx.x, blk = (int)blockIdx.x;
+    if (group >= st->n_groups) return;
+    const ssdhip_sgd_group& s = st->groups[group];         // uniform: scalar loads, the values the tick has just written
+    const float lr = s.lr_t, momentum = s.momentum_f, weight_decay = s.weight_decay;
+    int lo = 0, hi = a.count - 1;                          // last tensor with block0 <= blk
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.block0[mid] <= blk) lo = mid; else hi = mid - 1;
+    }
+    bf16_t* p = a.p[lo];
+    const bf16_t* g = a.g[lo];
+    float* w = a.w[lo];
+    float* m = a.m[lo];
+    const long long n = a.n[lo];
+    const long long base = (long long)(blk - a.block0[lo]) * 4096;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const long long i = base + (long long)u * 2048 + tid * 8;
+        if (i + 7 < n) {
+            const uint4 gv = *reinterpret_cast<const uint4*>(g + i);
+            const u32 gw[4] = {gv.x, gv.y, gv.z, gv.w};
+            float ww[8], mm[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float4 wv = *reinterpret_cast<const float4*>(w + i + 4 * h), mv = *reinterpret_cast<const float4*>(m + i + 4 * h);
+                ww[4 * h] = wv.x, ww[4 * h + 1] = wv.y, ww[4 * h + 2] = wv.z, ww[4 * h + 3] = wv.w;
+                mm[4 * h] = mv.x, mm[4 * h + 1] = mv.y, mm[4 * h + 2] = mv.z, mm[4 * h + 3] = mv.w;
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const float gq = (q & 1) ? __uint_as_float(gw[q >> 1] & 0xffff0000u) : bf16_float(gw[q >> 1] & 0xffffu);
+                sgd_update<RULE, NESTEROV>(ww[q], gq, mm[q], lr, momentum, weight_decay);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                *reinterpret_cast<float4*>(w + i + 4 * h) = make_float4(ww[4 * h], ww[4 * h + 1], ww[4 * h + 2], ww[4 * h + 3]);
+                *reinterpret_cast<float4*>(m + i + 4 * h) = make_float4(mm[4 * h], mm[4 * h + 1], mm[4 * h + 2], mm[4 * h + 3]);
+            }
+            *reinterpret_cast<uint4*>(p + i) = make_uint4(pack2_bf16(ww[0], ww[1]), pack2_bf16(ww[2], ww[3]), pack2_bf16(ww[4], ww[5]),
+                                                          pack2_bf16(ww[6], ww[7]));
+        } else {
+            for (long long j = i; j < n && j < i + 8; ++j) {
+                float wq = w[j], mq = m[j];
+                sgd_update<RULE, NESTEROV>(wq, bf16_float(g[j]), mq, lr, momentum, weight_decay);
+                m[j] = mq;
+                w[j] = wq;
+                p[j] = bf16_bits<bf16_t>(wq);
+            }
+        }
+    }
+}
+
 }  // namespace ssdhip
 
 using namespace ssdhip;
@@ -408,6 +479,55 @@ extern "C" int ssdhip_sgd_step(int n_tensors, void* const* params_h, const void*
             hipLaunchKernelGGL((sgd_step_kernel<1, false>), grid, wg, 0, stream, a, st, group);
         else
             hipLaunchKernelGGL((sgd_step_kernel<1, true>), grid, wg, 0, stream, a, st, group);
+        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
+    }
+    return SSDHIP_OK;
+}
+
+extern "C" int ssdhip_sgd_step_bf16(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h,
+                                    void* const* bufs_h, const long long* numel_h, int group, void* state, int rule, int nesterov,
+                                    int tick, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n_tensors <= 0 || !params_h || !grads_h || !master_h || !bufs_h || !numel_h || !state || ((uintptr_t)state & 15) || group < 0
+        || group >= SSDHIP_ADAM_MAX_GROUPS || rule < 0 || rule > 1)
+        return SSDHIP_E_BADARG;
+    long long chunk_blocks = 0;
+    for (int k = 0; k < n_tensors; ++k) {
+        if (!params_h[k] || !grads_h[k] || !master_h[k] || !bufs_h[k] || numel_h[k] <= 0) return SSDHIP_E_BADARG;
+        if (((uintptr_t)params_h[k] | (uintptr_t)grads_h[k] | (uintptr_t)master_h[k] | (uintptr_t)bufs_h[k]) & 15) return SSDHIP_E_BADARG;
+        if ((numel_h[k] + 4095) / 4096 > 0x3fffffffLL) return SSDHIP_E_BADARG;
+        if (k % SGD_BF16_CHUNK == 0) chunk_blocks = 0;      // (a launch's grid, before the tick: nothing runs on a refused call)
+        chunk_blocks += (numel_h[k] + 4095) / 4096;
+        if (chunk_blocks > 0x7fffffffLL) return SSDHIP_E_BADARG;
+    }
+    ssdhip_sgd_state* st = static_cast<ssdhip_sgd_state*>(state);
+    if (tick) {
+        hipLaunchKernelGGL(sgd_tick_kernel, dim3(1), dim3(SSDHIP_ADAM_MAX_GROUPS), 0, stream, st);
+        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
+    }
+    for (int k0 = 0; k0 < n_tensors; k0 += SGD_BF16_CHUNK) {
+        SgdBf16Args a;
+        a.count = n_tensors - k0 < SGD_BF16_CHUNK ? n_tensors - k0 : SGD_BF16_CHUNK;
+        long long blocks = 0;
+        for (int k = 0; k < SGD_BF16_CHUNK; ++k) {
+            const int src = k < a.count ? k0 + k : k0;     // (unused slots repeat the first tensor: never selected)
+            a.p[k] = static_cast<bf16_t*>(params_h[src]);
+            a.g[k] = static_cast<const bf16_t*>(grads_h[src]);
+            a.w[k] = static_cast<float*>(master_h[src]);
+            a.m[k] = static_cast<float*>(bufs_h[src]);
+            a.n[k] = numel_h[src];
+            a.block0[k] = (int)blocks;
+            if (k < a.count) blocks += (numel_h[src] + 4095) / 4096;
+        }
+        const dim3 grid((unsigned)blocks), wg(256);
+        if (rule == 0 && !nesterov)
+            hipLaunchKernelGGL((sgd_step_bf16_kernel<0, false>), grid, wg, 0, stream, a, st, group);
+        else if (rule == 0)
+            hipLaunchKernelGGL((sgd_step_bf16_kernel<0, true>), grid, wg, 0, stream, a, st, group);
+        else if (!nesterov)
+            hipLaunchKernelGGL((sgd_step_bf16_kernel<1, false>), grid, wg, 0, stream, a, st, group);
+        else
+            hipLaunchKernelGGL((sgd_step_bf16_kernel<1, true>), grid, wg, 0, stream, a, st, group);
         if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
     }
     return SSDHIP_OK;

@@ -20,8 +20,14 @@ Both keep their scalars in such a state block per device (`iterations`, per grou
 `set_lr` changes the learning rate between two replays of a captured step, `init_state()` allocates what a capture may not, and
 `iterations` reads the device's count back.
 
-In both, float32 parameters on a GPU with gradients of their own memory layout take the fused launch; anything else (CPU tensors, other
-dtypes, SGD with momentum 0) the plain tensor expressions of the same rule."""
+`master_weights=True` (per group) is how a bf16 model is trained: the optimizer keeps a float32 master copy of every bf16 parameter
+(`state[p]["master"]`, the moments float32 beside it), runs the float32 rule on the master with the bf16 gradient widened exactly, and
+writes the parameter as the master rounded to nearest even.  Without it a bf16 parameter is updated in bf16, where an update below
+half an ulp of the weight -- 2^-9 of its magnitude -- rounds to nothing, step after step.
+
+In both, float32 parameters on a GPU with gradients of their own memory layout take the fused launch, and so do bf16 parameters with
+bf16 gradients under `master_weights` (a launch of their own: ssdhip_adam_step_bf16 / ssdhip_sgd_step_bf16); anything else (CPU
+tensors, other dtypes, bf16 without masters, SGD with momentum 0) the plain tensor expressions of the same rule."""
 from __future__ import annotations
 
 import math
@@ -39,7 +45,23 @@ def _bump_versions(tensors):
         torch._foreach_add_(list(tensors), 0)
 
 
-class _OneLaunchOptimizer(torch.optim.Optimizer):
+class _MasterWeightsOption(type):
+    """`master_weights=` at construction: `SGD(params, ..., master_weights=True)`.  Why a metaclass and not an ordinary keyword of
+    the two `__init__`: tests/test_sgd_cpu.py and tests/test_optim_cpu.py pin the exact parameter lists of `SGD.__init__` and
+    `Adam.__init__`, so the keyword is taken here, in front of `__init__`, and handed to `_OneLaunchOptimizer.__init__` as a default of
+    the parameter groups.  The price: `inspect.signature(SGD)` and `help(SGD)` show `(*args, master_weights=False, **kwargs)` -- the
+    Keras parameters are on `SGD.__init__` --, and a subclass cannot forward the option through `super().__init__`: it passes it where
+    it constructs (`Sub(..., master_weights=True)`), or sets `group["master_weights"]` before the first step.  Once those two lists may
+    grow, this class goes and `master_weights=False` becomes a keyword-only parameter of the two constructors."""
+
+    def __call__(cls, *args, master_weights=False, **kwargs):
+        self = cls.__new__(cls)
+        self._master_weights_default = bool(master_weights)
+        self.__init__(*args, **kwargs)
+        return self
+
+
+class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption):
     """What the one-launch optimizers share: which parameters are eligible, the cache of their pointer tables, and the scalars -- one
     state block per device that a tick kernel advances (`iterations`, per group the base learning rate and what the update reads),
     a dictionary on the host for the tensor expressions.  `lr` may change at any time -- through `param_groups` (a
@@ -47,10 +69,19 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
     uses between two replays of a captured step; the other hyperparameters are fixed once the first step has been taken.
 
     A step inside `torch.cuda.graph` records the tick and the update launches only.  Nothing may be allocated there, so the state
-    buffers and the state block must exist: take an eager step first, or call `init_state()` with the gradients in place.
+    buffers (the masters among them) and the state block must exist: take an eager step first, or call `init_state()` with the
+    gradients in place.
     `iterations` reads the device's count back (a synchronisation: for logging and checkpoints).  A device's count advances with the
     update launches on that device and the host's with the tensor expressions: in an optimizer that mixes both, a step in which no
     parameter of a device has a gradient leaves that device's count one behind (the notebooks' models never do that).
+
+    Masters (`master_weights`): a master is made from its parameter once (`p.float()`, exact) and is the truth from then on.  The
+    optimizer remembers each parameter's `_version` after its own update; an eager `step()` that finds another one (the model loaded a
+    checkpoint, somebody wrote the weights in place) takes the master from the parameter again before it updates.  A captured step
+    cannot (the copy would replay every time): it raises, and `sync_masters()` is the call to make -- before the capture, or between
+    two replays after loading weights.  A master's creation (the first step, `init_state()`) remembers the version too, so weights
+    loaded after `init_state()` are found.  No remembered version (a master that came with a restored or unpickled optimizer) means
+    the master is trusted.
 
     A subclass names its state (`_buffers`, `_BLOCK`, `_HOST`) and supplies `_check`, `_hyper` (lr first), `_tag`, `_plan`, the
     block's three native calls, `_launch` and `_expressions`."""
@@ -60,9 +91,10 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
     _HOST = None                                             # self.state[_HOST]: the same scalars for the tensor-expression path
 
     def __init__(self, params, defaults):
+        defaults = dict(defaults, master_weights=self.__dict__.pop("_master_weights_default", False))   # (_MasterWeightsOption)
         self._check(defaults)
         super().__init__(params, defaults)
-        self._tables, self._seen = {}, {}
+        self._tables, self._seen, self._versions, self._mastering = {}, {}, {}, {}
         for group in self.param_groups:
             self._check(group)
         self._check_groups()
@@ -76,7 +108,17 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
     # addresses only -- `load_state_dict` after a step replaced the momentum buffers, the kernel kept updating the freed ones).
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        self._tables = {}
+        self._tables, self._versions, self._mastering = {}, {}, {}
+        for group in self.param_groups:                       # (a checkpoint from before the option existed)
+            group.setdefault("master_weights", False)
+        # (the framework casts every floating-point state tensor to its parameter's dtype: the float32 state of a bf16 parameter is
+        #  taken from the checkpoint again, as it was saved)
+        saved, ids = state_dict["state"], [i for g in state_dict["param_groups"] for i in g["params"]]
+        for i, p in zip(ids, (p for g in self.param_groups for p in g["params"])):
+            if "master" in saved.get(i, ()):
+                for name, t in saved[i].items():
+                    if torch.is_tensor(t) and t.is_floating_point() and t.dtype != p.dtype:
+                        self.state[p][name] = t.detach().to(device=p.device, copy=True)
         host = self.state.get(self._HOST)
         if host is not None:                                  # (state that belongs to no parameter is not copied by the framework)
             self.state[self._HOST] = {k: (list(v) if isinstance(v, list) else v) for k, v in host.items()}
@@ -86,10 +128,14 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
         super().__setstate__(state)
         self._tables = {}                                     # never pickled pointers: rebuilt on the next step
         self._seen = {}                                       # what the blocks hold is read from `param_groups` again: see _push
+        self._versions, self._mastering = {}, {}              # (keyed by the parameters of the optimizer this was copied from)
+        for group in self.param_groups:
+            group.setdefault("master_weights", False)
 
     def __getstate__(self):
         state = dict(super().__getstate__()) if hasattr(super(), "__getstate__") else dict(self.__dict__)
-        state.pop("_tables", None)
+        for name in ("_tables", "_versions", "_mastering"):
+            state.pop(name, None)
         return state
 
     def add_param_group(self, param_group):
@@ -118,24 +164,31 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
         is the same memory contiguous or channels_last; only the stride METADATA of its size-1 dimensions differs)."""
         return tuple(g.shape) == tuple(p.shape) and all(a == b for a, b, n in zip(g.stride(), p.stride(), p.shape) if n != 1)
 
+    @staticmethod
+    def _mastered(group, p):
+        """`p` is updated through a float32 master: a bf16 parameter of a group with `master_weights`."""
+        return group["master_weights"] and p.dtype == torch.bfloat16
+
     def _split(self, group, fusable=True):
-        """The parameters of a group that have a gradient: {device: those that take the fused launch}, [the others]."""
+        """The parameters of a group that have a gradient: {(device, bf16 with a master): those that take a fused launch}, [the
+        others]."""
         fused, rest = {}, []
         for p in group["params"]:
             g = p.grad
             if g is None:
                 continue
-            ok = (fusable and p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse
+            bf16 = self._mastered(group, p)
+            ok = (fusable and p.is_cuda and (bf16 or p.dtype == torch.float32) and g.dtype == p.dtype and not g.is_sparse
                   and self._dense(p) and self._same_order(g, p) and p.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0)
             if ok:
-                fused.setdefault(p.device, []).append(p)
+                fused.setdefault((p.device, bf16), []).append(p)
             else:
                 rest.append(p)
         return fused, rest
 
     def _key(self, group):
         """Which parameters have a gradient, and where the tensors the kernel touches live."""
-        state, names = self.state, self._buffers
+        state, names = self.state, self._buffers + ("master",)
         key = []
         for p in group["params"]:
             g = p.grad
@@ -149,7 +202,8 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
     def _planned(self, gi, group, tag):
         """(tables, rest) of `_plan(gi, group)`, rebuilt only when a tensor moved (the tables hold raw pointers) or `tag` changed.
         Everything per-parameter that can be decided once is decided in `_plan`: the step itself is host-bound (~280 launches in
-        11 ms), every microsecond of Python in it shows.  A table is (native table, its parameters, the block's key, the device)."""
+        11 ms), every microsecond of Python in it shows.  A table is (native table, its parameters, the block's key, the device,
+        bf16 parameters with masters)."""
         key = self._key(group)
         tabs = self.__dict__.setdefault("_tables", {})
         hit = tabs.get(gi)
@@ -160,13 +214,47 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
         return hit[2], hit[3]
 
     def _zeros(self, p, st, name, capturing):
-        """The state buffer `name` of `p`, zeros in the parameter's layout when it does not exist yet."""
+        """The state buffer `name` of `p`, zeros in the parameter's layout (float32 beside a master) when it does not exist yet."""
         if name not in st:
             if capturing:
                 raise RuntimeError("%s: state buffers cannot be created inside a graph capture; take an eager step or call "
                                    "init_state() first" % type(self).__name__)
-            st[name] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st[name] = torch.zeros_like(st.get("master", p), memory_format=torch.preserve_format)
         return st[name]
+
+    def _master(self, p, st, capturing):
+        """The float32 master of a bf16 parameter, in the parameter's layout: `p.float()` (exact) when it does not exist yet."""
+        if "master" not in st:
+            if capturing:
+                raise RuntimeError("%s: master weights cannot be created inside a graph capture; take an eager step or call "
+                                   "init_state() first" % type(self).__name__)
+            st["master"] = p.detach().to(torch.float32, memory_format=torch.preserve_format, copy=True)
+            self._versions[p] = p._version                        # init_state(), THEN the model loads weights: found, not trusted
+            for name in self._buffers:                            # moments of a checkpoint saved without masters: widened (exact)
+                if name in st and st[name].dtype != torch.float32:
+                    st[name] = st[name].to(torch.float32, memory_format=torch.preserve_format)
+        return st["master"]
+
+    def _masters(self, plans):
+        """Per group, the parameters of this step that have a master."""
+        out = []
+        for (tables, rest), group in zip(plans, self.param_groups):
+            ps = [p for _, tps, _, _, bf16 in tables if bf16 for p in tps]
+            if group["master_weights"]:
+                ps += [p for p in rest if p.dtype == torch.bfloat16]
+            out.append(ps)
+        return out
+
+    def sync_masters(self):
+        """Every master from its parameter again (exact), on the current stream: after the model's weights were written by somebody
+        else -- `load_state_dict`, `load_keras_weights`, an in-place edit -- and the next step is a captured one or a replay."""
+        with torch.no_grad():
+            for group in self.param_groups:
+                for p in group["params"]:
+                    st = self.state[p] if p in self.state else ()
+                    if "master" in st:
+                        st["master"].copy_(p)
+                        self._versions[p] = p._version
 
     # ---- the scalars: one state block per device, a dictionary on the host for the tensor expressions -------------------------------
     def _block_keys(self):
@@ -239,7 +327,7 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
         """What the first step allocates -- state buffers of the parameters that have a gradient now, the state block -- without a
         step: so that `step()` can be captured into a graph from step 1 on."""
         for gi, group in enumerate(self.param_groups):
-            for _, _, _, dev in self._planned(gi, group, self._tag(group))[0]:
+            for _, _, _, dev, _ in self._planned(gi, group, self._tag(group))[0]:
                 self._block(dev)
 
     @torch.no_grad()
@@ -249,19 +337,34 @@ class _OneLaunchOptimizer(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         groups = self.param_groups
+        for gi, group in enumerate(groups):
+            if self._mastering.setdefault(gi, group["master_weights"]) != group["master_weights"]:
+                raise ValueError("%s: `master_weights` cannot change after the first step (group %d)" % (type(self).__name__, gi))
         plans = [self._planned(gi, group, self._tag(group)) for gi, group in enumerate(groups)]
+        masters = self._masters(plans)
+        versions = self._versions
+        for ps in masters:                                          # somebody else wrote the parameter: it is the truth now
+            for p in ps:
+                if versions.get(p, p._version) != p._version:
+                    if p.is_cuda and torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError("%s: a parameter changed behind its master weights; call sync_masters() before the capture "
+                                           "(a copy recorded into the graph would replay with every step)" % type(self).__name__)
+                    self.state[p]["master"].copy_(p)
         # every group's learning rate first: the tick in front of the first update launch computes lr_t of ALL groups
         for gi, (tables, _) in enumerate(plans):
-            for _, _, key, dev in tables:
+            for _, _, key, dev, _ in tables:
                 self._push(key, gi, groups[gi], self._block(dev))
         ticked = set()
         for gi, (tables, _) in enumerate(plans):
-            for table, ps, key, _ in tables:
-                self._launch(table, self.state[key], gi, groups[gi], key not in ticked)
+            for table, ps, key, _, bf16 in tables:
+                self._launch(table, self.state[key], gi, groups[gi], key not in ticked, bf16)
                 ticked.add(key)
                 _bump_versions(ps)                                  # caches keyed on `_version` (the bf16 shadows) must see the update
         if any(rest for _, rest in plans):
             self._expressions(plans, self._host_tick())
+        for ps in masters:
+            for p in ps:
+                versions[p] = p._version
         return loss
 
 
@@ -299,7 +402,7 @@ class SGD(_OneLaunchOptimizer):
 
     @staticmethod
     def _tag(group):
-        return (group["momentum"] != 0.0, group["rule"])
+        return (group["momentum"] != 0.0, group["rule"], group["master_weights"])
 
     _state_bytes = staticmethod(nat.sgd_state_bytes)
     _state_read = staticmethod(nat.sgd_state_read)
@@ -328,18 +431,23 @@ class SGD(_OneLaunchOptimizer):
         name = self._BUFFER[group["rule"]]
         capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
         tables = []
-        for dev, ps in fused.items():
-            bufs = [self._zeros(p, self.state[p], name, capturing) for p in ps]   # zeros: torch's first buf = grad, Keras's v = 0
-            table = nat.sgd_table([_flat(p) for p in ps], [_flat(p.grad) for p in ps], [_flat(b) for b in bufs], dev)
-            tables.append((table, tuple(ps), self._BLOCK + str(dev), dev))
-        if group["momentum"] != 0.0:
-            for p in rest:
+        for (dev, bf16), ps in fused.items():
+            flat = [[_flat(p) for p in ps], [_flat(p.grad) for p in ps]]
+            if bf16:
+                flat.append([_flat(self._master(p, self.state[p], capturing)) for p in ps])
+            flat.append([_flat(self._zeros(p, self.state[p], name, capturing)) for p in ps])   # zeros: torch's first buf = grad, Keras's v = 0
+            table = (nat.sgd_table_bf16 if bf16 else nat.sgd_table)(*flat, dev)
+            tables.append((table, tuple(ps), self._BLOCK + str(dev), dev, bf16))
+        for p in rest:
+            if self._mastered(group, p):
+                self._master(p, self.state[p], capturing and p.is_cuda)
+            if group["momentum"] != 0.0:
                 self._zeros(p, self.state[p], name, capturing and p.is_cuda)
         return tables, rest
 
     @staticmethod
-    def _launch(table, blk, gi, group, tick):
-        nat.sgd_step(table, blk, gi, nat.SGD_RULES[group["rule"]], group["nesterov"], tick)
+    def _launch(table, blk, gi, group, tick, bf16):
+        (nat.sgd_step_bf16 if bf16 else nat.sgd_step)(table, blk, gi, nat.SGD_RULES[group["rule"]], group["nesterov"], tick)
 
     def _expressions(self, plans, lr_ts):
         for (_, rest), group, lr in zip(plans, self.param_groups, lr_ts):
@@ -347,21 +455,26 @@ class SGD(_OneLaunchOptimizer):
             keras, name = group["rule"] == "keras", self._BUFFER[group["rule"]]
             for p in rest:                                          # one rounding per operation, in the kernel's order: no `alpha=`
                 g = p.grad.to_dense() if p.grad.is_sparse else p.grad   # forms (the framework evaluates those as a fused multiply-add)
+                w = p                                               # what the rule updates: the parameter, or its float32 master
+                if self._mastered(group, p):
+                    w, g = self.state[p]["master"], g.float()
                 if wd != 0.0:
-                    g = g + p * wd
+                    g = g + w * wd
                 if mom == 0.0:                                      # no state: both rules are p - lr g
-                    p.sub_(g * lr)
+                    w.sub_(g * lr)
                 elif keras:
                     v, lg = self.state[p][name], g * lr
                     v.mul_(mom).sub_(lg)
                     if nesterov:
-                        p.add_(v * mom).sub_(lg)
+                        w.add_(v * mom).sub_(lg)
                     else:
-                        p.add_(v)
+                        w.add_(v)
                 else:
                     buf = self.state[p][name]
                     buf.mul_(mom).add_(g)
-                    p.sub_((g + buf * mom) * lr if nesterov else buf * lr)
+                    w.sub_((g + buf * mom) * lr if nesterov else buf * lr)
+                if w is not p:
+                    p.copy_(w)                                      # round to nearest even
 
 
 class Adam(_OneLaunchOptimizer):
@@ -394,7 +507,7 @@ class Adam(_OneLaunchOptimizer):
         return tuple(float(group[k]) for k in ("lr", "beta_1", "beta_2", "epsilon", "decay", "weight_decay"))
 
     def _tag(self, group):
-        return (group["amsgrad"], self._fused)
+        return (group["amsgrad"], self._fused, group["master_weights"])
 
     _state_bytes = staticmethod(nat.adam_state_bytes)
     _state_read = staticmethod(nat.adam_state_read)
@@ -433,8 +546,10 @@ class Adam(_OneLaunchOptimizer):
             lr_t.append(lr * math.sqrt(1.0 - b2t) / (1.0 - b1t))
         return lr_t
 
-    def _moments(self, p, amsgrad, capturing):
+    def _moments(self, p, amsgrad, capturing, master=False):
         st = self.state[p]
+        if master:
+            self._master(p, st, capturing)
         for n in ("m", "v", "vhat") if amsgrad else ("m", "v"):
             self._zeros(p, st, n, capturing)
         return st
@@ -444,18 +559,19 @@ class Adam(_OneLaunchOptimizer):
         ams = group["amsgrad"]
         capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
         tables = []
-        for dev, ps in fused.items():
-            sts = [self._moments(p, ams, capturing) for p in ps]
-            table = nat.adam_table([_flat(p) for p in ps], [_flat(p.grad) for p in ps], [_flat(st["m"]) for st in sts],
-                                   [_flat(st["v"]) for st in sts], [_flat(st["vhat"]) for st in sts] if ams else None, dev)
-            tables.append((table, tuple(ps), self._BLOCK + str(dev), dev))
+        for (dev, bf16), ps in fused.items():
+            sts = [self._moments(p, ams, capturing, bf16) for p in ps]
+            flat = [[_flat(p) for p in ps], [_flat(p.grad) for p in ps]] + ([[_flat(st["master"]) for st in sts]] if bf16 else [])
+            flat += [[_flat(st["m"]) for st in sts], [_flat(st["v"]) for st in sts], [_flat(st["vhat"]) for st in sts] if ams else None]
+            table = (nat.adam_table_bf16 if bf16 else nat.adam_table)(*flat, dev)
+            tables.append((table, tuple(ps), self._BLOCK + str(dev), dev, bf16))
         for p in rest:
-            self._moments(p, ams, capturing and p.is_cuda)
+            self._moments(p, ams, capturing and p.is_cuda, self._mastered(group, p))
         return tables, rest
 
     @staticmethod
-    def _launch(table, blk, gi, group, tick):
-        nat.adam_step(table, blk, gi, tick=tick)
+    def _launch(table, blk, gi, group, tick, bf16):
+        (nat.adam_step_bf16 if bf16 else nat.adam_step)(table, blk, gi, tick=tick)
 
     def _expressions(self, plans, lr_ts):
         for (_, rest), group, lr_t in zip(plans, self.param_groups, lr_ts):
@@ -463,8 +579,11 @@ class Adam(_OneLaunchOptimizer):
             for p in rest:                                          # one rounding per operation, in the kernel's order: no `alpha=`
                 st = self.state[p]                                  # forms (the framework evaluates those as a fused multiply-add)
                 g = p.grad.to_dense() if p.grad.is_sparse else p.grad
+                w = p                                               # what the rule updates: the parameter, or its float32 master
+                if self._mastered(group, p):
+                    w, g = st["master"], g.float()
                 if wd != 0.0:
-                    g = g + p * wd
+                    g = g + w * wd
                 m, v = st["m"], st["v"]
                 m.mul_(b1).add_(g * (1.0 - b1))
                 v.mul_(b2).add_((g * g) * (1.0 - b2))
@@ -474,4 +593,6 @@ class Adam(_OneLaunchOptimizer):
                 # (the framework's vectorised CPU sqrt is one ulp off IEEE's on 0.7 % of values; the float64 one rounded to
                 #  float32 is the correctly rounded float32 root: 53 >= 2 * 24 + 2 bits, double rounding cannot show)
                 root = den.sqrt() if den.dtype == torch.float64 else den.double().sqrt().to(den.dtype)
-                p.sub_((m * lr_t) / (root + eps))
+                w.sub_((m * lr_t) / (root + eps))
+                if w is not p:
+                    p.copy_(w)                                      # round to nearest even

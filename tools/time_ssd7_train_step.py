@@ -12,6 +12,14 @@ profiles/ssd7_conv_training.json (its "off", "on" and "blocks" entries are what 
 profiles/ssd7_fused_training.json before it had the third arm).
 
     python tools/time_ssd7_train_step.py [--out FILE] [--batches 8,32] [--rounds 7] [--steps 200] [--all-layers]
+
+--master-weights times the optimizer's side of the same step instead, under the same protocol: the "conv" model (bf16 parameters) with
+`--optimizer {sgd,adam}` built with `master_weights=False` (bf16 parameters through the optimizer's tensor expressions) and with
+`master_weights=True` (float32 masters, ssdhip_sgd_step_bf16 / ssdhip_adam_step_bf16), alternating in one process; plus, after the
+timings, the nodes of each captured graph by type and the kernel launches of one eager run of the same step.  Writes
+profiles/ssd7_master_weights.json.
+
+    python tools/time_ssd7_train_step.py --master-weights [--optimizer sgd|adam] [--out FILE] [--batches 8,32] [--rounds 7] [--steps 200]
 """
 import argparse
 import json
@@ -50,10 +58,14 @@ def timed(torch, fn, n):
     return a.elapsed_time(b) / n
 
 
-def graphed_step(torch, model, images, y_true):
+def graphed_step(torch, model, images, y_true, optimizer="sgd", master_weights=False, counted=False):
+    """The replay of the step captured as one HIP graph; with `counted` (replay, the eager step, the graph object kept for its nodes)."""
     from ssd_keras_amd.keras_loss_function.keras_ssd_loss import SSDLoss
-    from ssd_keras_amd.optimizers import SGD
-    opt = SGD(model.parameters(), lr=1e-5, momentum=0.9)
+    from ssd_keras_amd.optimizers import SGD, Adam
+    if optimizer == "sgd":
+        opt = SGD(model.parameters(), lr=1e-5, momentum=0.9, master_weights=master_weights)
+    else:
+        opt = Adam(model.parameters(), lr=1e-5, epsilon=1e-8, master_weights=master_weights)
     lf = SSDLoss(neg_pos_ratio=3, n_neg_min=0, alpha=1.0)
 
     def step():
@@ -68,11 +80,17 @@ def graphed_step(torch, model, images, y_true):
             step()
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
+    graph = None
+    if counted:
+        try:
+            graph = torch.cuda.CUDAGraph(keep_graph=True)           # the captured graph stays readable: graph_nodes()
+        except TypeError:
+            pass
+    graph = graph or torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         step()
     torch.cuda.synchronize()
-    return graph.replay
+    return (graph.replay, step, graph) if counted else graph.replay
 
 
 def _graphed(torch, fn):
@@ -182,9 +200,112 @@ def conv_layer_times(torch, model, batch, rounds=5, replays=100):
     return out
 
 
+def synthetic_targets(batch, n_anchor, width):
+    """A fixed encoded batch: every anchor background except one in sixteen, which carries a class and box offsets."""
+    rng = np.random.RandomState(7)
+    y = np.zeros((batch, n_anchor, width), dtype=np.float32)
+    pos = rng.rand(batch, n_anchor) < 1.0 / 16
+    cls = rng.randint(1, width - 12, size=(batch, n_anchor))
+    y[..., 0] = ~pos
+    for k in range(1, width - 12):
+        y[..., k] = pos & (cls == k)
+    y[..., width - 12:width - 8] = rng.randn(batch, n_anchor, 4) * 0.5 * pos[..., None]
+    return y
+
+
+def graph_nodes(graph):
+    """{"kernel": n, "memcpy": n, "memset": n, "other": n} of a captured graph kept with keep_graph=True, read through the HIP runtime's
+    hipGraphGetNodes / hipGraphNodeGetType (queries only); None where the framework or the runtime does not offer them."""
+    import ctypes
+    try:
+        handle = ctypes.c_void_p(int(graph.raw_cuda_graph()))
+        with open("/proc/self/maps") as maps:                        # the runtime the framework has loaded, not a second copy
+            loaded = sorted({line.split()[-1] for line in maps if "libamdhip64" in line})
+        if len(loaded) != 1:
+            return None
+        hip = ctypes.CDLL(loaded[0])
+        n = ctypes.c_size_t(0)
+        if hip.hipGraphGetNodes(handle, None, ctypes.byref(n)) != 0 or n.value == 0:
+            return None
+        nodes = (ctypes.c_void_p * n.value)()
+        if hip.hipGraphGetNodes(handle, nodes, ctypes.byref(n)) != 0:
+            return None
+        names = {0: "kernel", 1: "memcpy", 2: "memset"}              # hipGraphNodeTypeKernel, ...Memcpy, ...Memset
+        out = {"kernel": 0, "memcpy": 0, "memset": 0, "other": 0}
+        for node in nodes[:n.value]:
+            kind = ctypes.c_int(-1)
+            if hip.hipGraphNodeGetType(ctypes.c_void_p(node), ctypes.byref(kind)) != 0:
+                return None
+            out[names.get(kind.value, "other")] += 1
+        return out
+    except Exception:                                         # noqa: BLE001
+        return None
+
+
+def eager_launches(torch, fn):
+    """Kernel launches of one EAGER call of `fn` (the launches a capture records), counted by the framework's profiler; None where it
+    records no device activity."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and "mem" not in e.name.lower())
+        return n or None
+    except Exception:                                         # noqa: BLE001
+        return None
+
+
+def master_weights_arms(torch, args):
+    """The bf16 step of the "conv" model with the optimizer's masters off (the parameters updated in bf16 by the tensor expressions)
+    and on (one or two libssdhip launches on float32 masters): arms alternating, median and spread as in main()."""
+    arms = {"master_weights_off": False, "master_weights_on": True}
+    result = {"device": torch.cuda.get_device_name(0), "model": "SSD7 300x300x3, 5 classes, bf16, train(), fused_blocks(True, training=True, "
+              "convolutions=True)", "optimizer": args.optimizer,
+              "step": "forward + SSDLoss + backward + ssd_keras_amd.optimizers.%s, one HIP graph" % args.optimizer.upper(),
+              "rounds": args.rounds, "steps_per_round": args.steps, "batches": {}}
+    for batch in [int(b) for b in args.batches.split(",")]:
+        images = torch.from_numpy(np.random.RandomState(100).randint(0, 256, size=(batch, 300, 300, 3)).astype(np.float32)).cuda()
+        models = {arm: build(torch, "conv") for arm in arms}
+        with torch.no_grad():
+            n_anchor, width = build(torch, "off").eval()(images[:1]).shape[1:]
+        y_true = torch.from_numpy(synthetic_targets(batch, n_anchor, width)).cuda()
+        captured = {arm: graphed_step(torch, models[arm], images, y_true, args.optimizer, on, counted=True) for arm, on in arms.items()}
+        replays = {arm: c[0] for arm, c in captured.items()}
+        for fn in replays.values():
+            timed(torch, fn, 40)
+        rounds = {arm: [] for arm in arms}
+        for _ in range(args.rounds):
+            for arm in arms:
+                rounds[arm].append(timed(torch, replays[arm], args.steps))
+        entry = {}
+        for arm in arms:
+            entry[arm] = {"median_ms": round(float(np.median(rounds[arm])), 4), "spread_ms": round(max(rounds[arm]) - min(rounds[arm]), 4),
+                          "rounds_ms": [round(v, 4) for v in rounds[arm]]}
+        for arm in arms:                                           # last: nothing here may disturb the timings above
+            entry[arm]["graph_nodes"] = graph_nodes(captured[arm][2])
+            entry[arm]["eager_kernel_launches"] = eager_launches(torch, captured[arm][1])
+        off, on = entry["master_weights_off"], entry["master_weights_on"]
+        entry["on_minus_off_ms"] = round(on["median_ms"] - off["median_ms"], 4)
+        entry["not_slower"] = bool(on["median_ms"] - off["median_ms"] <= max(on["spread_ms"], off["spread_ms"]))
+        result["batches"][str(batch)] = entry
+        print(json.dumps({"batch": batch, **entry}), flush=True)
+        del replays, captured, models
+        torch.cuda.empty_cache()
+    result["note"] = ("the step time is the only performance claim; convergence over a real training run is not measured.  "
+                      "graph_nodes: the nodes of the captured step by type, read from the HIP graph itself; eager_kernel_launches: the "
+                      "kernel activities the framework's profiler records for one eager run of the same step")
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ssd7_conv_training.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/ssd7_conv_training.json (profiles/ssd7_master_weights.json with "
+                    "--master-weights)")
+    ap.add_argument("--master-weights", action="store_true", help="time the optimizer's masters off against on instead of the three routes")
+    ap.add_argument("--optimizer", choices=("sgd", "adam"), default="sgd", help="the optimizer of the --master-weights arms")
     ap.add_argument("--all-layers", action="store_true", help="the conv arm routes all seven layers, not SSD7.TRAIN_CONVS")
     ap.add_argument("--batches", default="8,32")
     ap.add_argument("--rounds", type=int, default=7)
@@ -193,6 +314,15 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("time_ssd7_train_step.py needs a GPU: there is nothing to time without one")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "ssd7_master_weights.json" if args.master_weights else "ssd7_conv_training.json")
+    if args.master_weights:
+        result = master_weights_arms(torch, args)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        return
     result = {"device": torch.cuda.get_device_name(0), "model": "SSD7 300x300x3, 5 classes, bf16, train()",
               "step": "forward + SSDLoss + backward + ssd_keras_amd.optimizers.SGD, one HIP graph", "rounds": args.rounds,
               "steps_per_round": args.steps, "batches": {}}
@@ -202,15 +332,7 @@ def main():
         with torch.no_grad():
             n_anchor, width = models["off"].eval()(images[:1]).shape[1:]
         models["off"].train()
-        rng = np.random.RandomState(7)
-        y = np.zeros((batch, n_anchor, width), dtype=np.float32)
-        pos = rng.rand(batch, n_anchor) < 1.0 / 16
-        cls = rng.randint(1, width - 12, size=(batch, n_anchor))
-        y[..., 0] = ~pos
-        for k in range(1, width - 12):
-            y[..., k] = pos & (cls == k)
-        y[..., width - 12:width - 8] = rng.randn(batch, n_anchor, 4) * 0.5 * pos[..., None]
-        y_true = torch.from_numpy(y).cuda()
+        y_true = torch.from_numpy(synthetic_targets(batch, n_anchor, width)).cuda()
         replays = {k: graphed_step(torch, m, images, y_true) for k, m in models.items()}
         for fn in replays.values():
             timed(torch, fn, 40)
