@@ -664,6 +664,36 @@ size_t ssdhip_ssd7_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int 
 int ssdhip_ssd7_conv_wgrad_nhwc_bf16(const void* x, const void* dy, void* dw, void* db, int B, int H, int W, int Cin, int Cout, int kernel,
                                      int out_bf16, const long long* dw_strides, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The PREDICTOR HEADS of SSD7's training step (csrc/ssdhip_heads7.hip): the conf and loc heads of a source map -- Conv2D(3 x 3, 'same')
+ * on Cin in {64, 48, 32} channels -- as one convolution with the filters [conf | loc | zero rows] up to Cp = 48 output channels.  Forward
+ * and data gradient are ssdhip_conv_same_bias_nhwc_bf16 with (Cin, 48) and (48, Cin).  SSDHIP_E_BADARG for anything else, with nothing
+ * launched and every output untouched.
+ *
+ * ssdhip_ssd7_pack_heads   ONE launch that writes, for each of up to 8 maps, fwd[i] (the image of ssdhip_conv_bn_elu_pack_bytes(Cin[i],
+ *     48, 3) of the concatenated filters), flipped[i] (the image of (48, Cin[i], 3) of their flip(2, 3).transpose(0, 1)) and bias[i]
+ *     ([48] bf16: conf bias | loc bias | zeros).  Every byte is written.  conf_w[i] (n_conf[i], Cin[i], 3, 3) and loc_w[i] (n_loc[i],
+ *     Cin[i], 3, 3) bf16 are read through the element strides strides[8 i ..] (conf's four, then loc's four); conf_b[i], loc_b[i] are
+ *     dense bf16.  n_conf[i] + n_loc[i] <= 48.  The arrays are host arrays, read while enqueuing; enqueue-only and capturable.
+ *
+ * ssdhip_ssd7_head_wgrad_nhwc_bf16   dw[co][kh][kw][ci] = sum_{b,h,w} dy[b,h,w,co] x[b, h + kh - 1, w + kw - 1, ci] and db[co] = sum
+ *     dy[b,h,w,co] of the packed convolution, x [B, H, W, Cin], dy [B, H, W, Cp = 48] bf16 (W <= 256), float32 accumulation on the MFMA;
+ *     packed rows [0, n_conf) go to dw_conf / db_conf, the next n_loc to dw_loc / db_loc, the padding rows nowhere.  The batch is one
+ *     list of plan[7] = B (H + 2)(W + 2) positions on the zero-padded grid, walked in plan[2] chunks of plan[4] positions: split s of
+ *     plan[0] owns plan[1] consecutive chunks (the last one plan[3]), plan[5] = 3 workgroups per split take one kernel row each and
+ *     plan[6] step parities write partials of their own -- plan[0] plan[6] float32 partial tiles [48][3][3][Cin] + [48] in the
+ *     workspace.  A second launch adds them in index order in float32 and writes the four outputs once: bit-reproducible, no atomics,
+ *     no memset.  out_bf16 = 0: float32 outputs; else bf16, one rounding.  dw_conf_strides / dw_loc_strides: the four element strides
+ *     of that output as a (n, Cin, kh, kw) tensor (host arrays), or NULL for dense [n][3][3][Cin].  The plan is host arithmetic on the
+ *     shape.  workspace: 16-byte aligned, ssdhip_ssd7_head_wgrad_workspace_bytes bytes (0: shape not covered). */
+int ssdhip_ssd7_pack_heads(int n_maps, const void* const* conf_w, const void* const* loc_w, const void* const* conf_b,
+                           const void* const* loc_b, void* const* fwd, void* const* flipped, void* const* bias, const int* Cin,
+                           const int* n_conf, const int* n_loc, const long long* strides, void* stream);
+int ssdhip_ssd7_head_wgrad_plan(int B, int H, int W, int Cin, int Cp, int* plan);
+size_t ssdhip_ssd7_head_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cp);
+int ssdhip_ssd7_head_wgrad_nhwc_bf16(const void* x, const void* dy, void* dw_conf, void* db_conf, void* dw_loc, void* db_loc, int B, int H,
+                                     int W, int Cin, int Cp, int n_conf, int n_loc, int out_bf16, const long long* dw_conf_strides,
+                                     const long long* dw_loc_strides, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Image half of the training-time augmentation (csrc/ssdhip_image.hip): what the reference does per image on the host
  * through OpenCV (data_generator/object_detection_2d_photometric_ops.py:23-480, object_detection_2d_geometric_ops.py:27-148), for a

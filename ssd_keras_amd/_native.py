@@ -150,6 +150,10 @@ SIGNATURES = {
     "ssdhip_ssd7_conv_wgrad_plan": (_I, [_I] * 6 + [_INTP]),
     "ssdhip_ssd7_conv_wgrad_workspace_bytes": (_SZ, [_I] * 6),
     "ssdhip_ssd7_conv_wgrad_nhwc_bf16": (_I, [_P] * 4 + [_I] * 7 + [_LLP, _P, _SZ, _P]),
+    "ssdhip_ssd7_pack_heads": (_I, [_I] + [_P] * 7 + [_INTP] * 3 + [_LLP, _P]),
+    "ssdhip_ssd7_head_wgrad_plan": (_I, [_I] * 5 + [_INTP]),
+    "ssdhip_ssd7_head_wgrad_workspace_bytes": (_SZ, [_I] * 5),
+    "ssdhip_ssd7_head_wgrad_nhwc_bf16": (_I, [_P] * 6 + [_I] * 8 + [_LLP, _LLP, _P, _SZ, _P]),
     "ssdhip_image_program": (_I, [_P, _I, _P, _I, _I, _LL] + [_P] * 3),
     "ssdhip_image_resize_cv_u8": (_I, [_P, _P] + [_I] * 8 + [_P, _P, _I, _P, _P, _I, _P]),
     "ssdhip_image_resize_gather_cv_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 3 + [_I, _P, _P, _I, _P, _P]),
@@ -1723,6 +1727,105 @@ def ssd7_conv_wgrad(x, dy, kernel, like=None):
     launch("ssdhip_ssd7_conv_wgrad_nhwc_bf16", dev, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), b, h, w, cin, cout, k,
            int(dw.dtype == torch.bfloat16), strides, _ptr(ws), need)
     return dw, db
+
+
+SSD7_HEAD_CP = 48                                    # packed output channels of a source map's two heads (csrc/ssdhip_heads7.hip)
+
+
+def ssd7_head_geometry(cin, n_conf, n_loc):
+    """Whether the two heads of a `cin`-channel map pack into the 48-channel convolution of `ssd7_pack_heads` / `ssd7_head_wgrad`."""
+    return int(cin) in (64, 48, 32) and n_conf > 0 and n_loc > 0 and n_conf + n_loc <= SSD7_HEAD_CP
+
+
+def _ssd7_head_params(conf_w, loc_w, what):
+    torch = _torch()
+    for wt in (conf_w, loc_w):
+        if (wt.dim() != 4 or tuple(wt.shape[2:]) != (3, 3) or wt.shape[1] != conf_w.shape[1] or wt.device != conf_w.device
+                or wt.dtype != conf_w.dtype):
+            raise SsdHipError("%s: the heads' filters are (n, Cin, 3, 3) tensors of one dtype on one device" % what)
+    if not ssd7_head_geometry(conf_w.shape[1], conf_w.shape[0], loc_w.shape[0]):
+        raise SsdHipError("%s: no kernel for Cin = %d with %d + %d output channels" % (what, conf_w.shape[1], conf_w.shape[0], loc_w.shape[0]))
+    return torch
+
+
+def ssd7_head_images(conf_ws, loc_ws):
+    """Empty buffers for `ssd7_pack_heads`: (forward images, flipped images, packed biases), one of each per source map."""
+    fwd, flipped, bias = [], [], []
+    for cw, lw in zip(conf_ws, loc_ws):
+        torch = _ssd7_head_params(cw, lw, "ssd7_head_images")
+        cin = int(cw.shape[1])
+        new = lambda n: torch.empty((n,), dtype=torch.bfloat16, device=cw.device)
+        fwd.append(new(int(load().ssdhip_conv_bn_elu_pack_bytes(cin, SSD7_HEAD_CP, 3)) // 2))
+        flipped.append(new(int(load().ssdhip_conv_bn_elu_pack_bytes(SSD7_HEAD_CP, cin, 3)) // 2))
+        bias.append(new(SSD7_HEAD_CP))
+    return fwd, flipped, bias
+
+
+def ssd7_pack_heads(conf_ws, loc_ws, conf_bs, loc_bs, fwd, flipped, bias):
+    """ONE launch that writes every byte of the packed heads of up to eight source maps from their bf16 parameters
+    (ssdhip_ssd7_pack_heads; any memory order of the filters: their element strides travel in the kernel arguments).  With
+    w = cat([conf_w, loc_w, zero rows up to 48]): `fwd[i]` = `conv_bn_elu_pack(w)`, `flipped[i]` = `conv_bn_elu_pack(w.flip(2, 3)
+    .transpose(0, 1))`, `bias[i]` = [conf_b | loc_b | zeros].  Enqueue only, capturable; this is what runs once per training step."""
+    n = len(conf_ws)
+    if n == 0 or n > 8 or any(len(v) != n for v in (loc_ws, conf_bs, loc_bs, fwd, flipped, bias)):
+        raise SsdHipError("ssd7_pack_heads: one to eight maps, and one entry per map in every list")
+    dev = conf_ws[0].device
+    for cw, lw, cb, lb, f, t, pb in zip(conf_ws, loc_ws, conf_bs, loc_bs, fwd, flipped, bias):
+        torch = _ssd7_head_params(cw, lw, "ssd7_pack_heads")
+        cin = int(cw.shape[1])
+        if not cw.is_cuda or cw.dtype != torch.bfloat16 or cw.device != dev:
+            raise SsdHipError("ssd7_pack_heads: the filters are bfloat16 tensors on one GPU")
+        for b_, wt in ((cb, cw), (lb, lw)):
+            if b_.dtype != torch.bfloat16 or b_.device != dev or tuple(b_.shape) != (wt.shape[0],) or not b_.is_contiguous():
+                raise SsdHipError("ssd7_pack_heads: a head's bias is a contiguous (n,) bfloat16 tensor beside its filters")
+        need = (int(load().ssdhip_conv_bn_elu_pack_bytes(cin, SSD7_HEAD_CP, 3)), int(load().ssdhip_conv_bn_elu_pack_bytes(SSD7_HEAD_CP, cin, 3)),
+                2 * SSD7_HEAD_CP)
+        for img, nbytes in zip((f, t, pb), need):
+            if (img is None or not img.is_cuda or img.device != dev or img.dtype != torch.bfloat16 or not img.is_contiguous()
+                    or img.numel() * 2 != nbytes):
+                raise SsdHipError("ssd7_pack_heads: a buffer does not fit its map (Cin = %d): see ssd7_head_images" % cin)
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+    ints = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+    strides = (ctypes.c_longlong * (8 * n))(*[int(v) for cw, lw in zip(conf_ws, loc_ws) for v in tuple(cw.stride()) + tuple(lw.stride())])
+    launch("ssdhip_ssd7_pack_heads", dev, n, ptrs(conf_ws), ptrs(loc_ws), ptrs(conf_bs), ptrs(loc_bs), ptrs(fwd), ptrs(flipped), ptrs(bias),
+           ints(cw.shape[1] for cw in conf_ws), ints(cw.shape[0] for cw in conf_ws), ints(lw.shape[0] for lw in loc_ws), strides)
+
+
+def ssd7_head_wgrad_plan(b, h, w, cin, cp=SSD7_HEAD_CP):
+    """How `ssd7_head_wgrad` walks the B (H + 2)(W + 2) positions of the zero-padded list (host arithmetic, ssdhip_ssd7_head_wgrad_plan):
+    (splits, chunks per split, chunks, chunks of the last split, positions per chunk, kernel-row groups, step parities with a partial
+    of their own, positions), or None for a shape the kernel does not cover."""
+    plan = (ctypes.c_int * 8)()
+    if load().ssdhip_ssd7_head_wgrad_plan(int(b), int(h), int(w), int(cin), int(cp), plan) != 0:
+        return None
+    return tuple(plan)
+
+
+def ssd7_head_wgrad(x, dy, like_conf, like_loc):
+    """The parameter gradients of a source map's two heads (csrc/ssdhip_heads7.hip): x (B, Cin, H, W) and the packed dL/dy (B, 48, H, W),
+    bf16 with NHWC memory.  `like_conf` (n_conf, Cin, 3, 3) and `like_loc` (n_loc, Cin, 3, 3), float32 or bfloat16 (both the same): the
+    outputs take their dtype (bf16: one rounding) and dw their element strides, so that the parameters' gradients need no framework op.
+    Partial sums added in an order fixed by the shape: bit-reproducible.  Returns (dw_conf, db_conf, dw_loc, db_loc)."""
+    torch = _ssd7_head_params(like_conf, like_loc, "ssd7_head_wgrad")
+    b, h, w, cin = _ssd7_map(x, "x")
+    if _ssd7_map(dy, "dy") != (b, h, w, SSD7_HEAD_CP) or dy.device != x.device:
+        raise SsdHipError("ssd7_head_wgrad: dy must be the packed (B, %d, H, W) gradient over x's positions" % SSD7_HEAD_CP)
+    if like_conf.shape[1] != cin or like_conf.dtype not in (torch.float32, torch.bfloat16):
+        raise SsdHipError("ssd7_head_wgrad: the filters are float32 or bfloat16 and have x's %d input channels" % cin)
+    dev = x.device
+    need = int(load().ssdhip_ssd7_head_wgrad_workspace_bytes(b, h, w, cin, SSD7_HEAD_CP))
+    if need == 0:
+        raise SsdHipError("ssd7_head_wgrad: no kernel for a %d x %d map of %d channels" % (h, w, cin))
+    outs = []
+    for like in (like_conf, like_loc):
+        outs.append(torch.empty_strided(like.shape, like.stride(), dtype=like.dtype, device=dev))
+        outs.append(torch.empty((like.shape[0],), dtype=like.dtype, device=dev))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    sc = (ctypes.c_longlong * 4)(*[int(v) for v in outs[0].stride()])
+    sl = (ctypes.c_longlong * 4)(*[int(v) for v in outs[2].stride()])
+    launch("ssdhip_ssd7_head_wgrad_nhwc_bf16", dev, _ptr(x), _ptr(dy), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), b, h, w,
+           cin, SSD7_HEAD_CP, int(like_conf.shape[0]), int(like_loc.shape[0]), int(like_conf.dtype == torch.bfloat16), sc, sl, _ptr(ws), need)
+    return tuple(outs)
 
 
 def _bn_train_map(t, name):

@@ -429,6 +429,9 @@ class SSDModel(PredictorHeads, nn.Module):
         feats = self.features(xin)
         b = x.shape[0]
         sizes = [(f.shape[2], f.shape[3]) for f in feats]
+        own = self._model_head_route(feats, sizes, decode)
+        if own is not None:
+            return own
         if all(self._fused_head_ok(f, ch) for f, ch in zip(feats, self.conf_heads)):
             # heads without bias; bias, Reshape, softmax, anchors and the concatenations are one libssdhip pass (:363-419)
             packable = all(self._packed_head_ok(ch, lh, f) for f, ch, lh in zip(feats, self.conf_heads, self.loc_heads))
@@ -480,6 +483,11 @@ class SSDModel(PredictorHeads, nn.Module):
         anchors = self.anchors_and_variances(sizes, conf.device)
         pred = torch.cat([conf, loc, anchors.unsqueeze(0).expand(b, -1, -1)], dim=2)   # 'predictions' (:419)
         return self.decoder(pred) if (decode and self.decoder is not None) else pred
+
+    def _model_head_route(self, feats, sizes, decode):
+        """A model's own way from the source maps to the predictions, tried ahead of the generic head paths: the prediction tensor, or
+        None -- always, here -- for "take the generic path" (SSD7 overrides it for `fused_blocks(..., heads=True)`)."""
+        return None
 
     def _derived_weights_key(self):
         """Versions of every parameter some cached, derived tensor was built from (what a captured graph cannot follow by itself)."""

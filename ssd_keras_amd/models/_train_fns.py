@@ -1,7 +1,8 @@
 """The training step's autograd functions over the libssdhip kernels (csrc/ssdhip_train.hip, ssdhip_wgrad.hip and the forward
 kernels of the inference path): one node per convolution layer [+ pooling], per pair of predictor heads, for the prediction assembly,
 for a max-pool, for what follows a convolution in a block of SSD7 (batch-statistics BatchNorm + ELU [+ pool],
-csrc/ssdhip_bntrain.hip) and for that convolution itself (csrc/ssdhip_convbn.hip, ssdhip_wgrad7.hip).  `SSDModel` (models/_common.py) applies them; which forward kernel a layer runs is `_conv_select`'s choice."""
+csrc/ssdhip_bntrain.hip), for that convolution itself (csrc/ssdhip_convbn.hip, ssdhip_wgrad7.hip) and for the pair of predictor heads
+of one of SSD7's source maps (csrc/ssdhip_heads7.hip).  `SSDModel` (models/_common.py) applies them; which forward kernel a layer runs is `_conv_select`'s choice."""
 import torch
 
 from .. import _native as nat
@@ -350,3 +351,38 @@ class _Ssd7ConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             gw, gb = nat.ssd7_conv_wgrad(x, gy, weight.shape[2], like=weight)
         return gx, (gw if ctx.needs_input_grad[1] else None), (gb if ctx.needs_input_grad[2] else None), None, None
+
+
+class _Ssd7HeadFn(torch.autograd.Function):
+    """The two predictor heads of one source map of SSD7's training step as one autograd node over libssdhip (csrc/ssdhip_heads7.hip):
+    the filters [conf | loc | zero rows] up to 48 output channels run as ONE convolution.  Forward = the blocks' MFMA kernel with the
+    plain epilogue on the packed image and the packed bias; data gradient = the same kernel on dL/dy with the flipped image; parameter
+    gradients = `nat.ssd7_head_wgrad`, which writes the four gradients in the parameters' own dtype and memory order and drops the
+    padding rows -- no framework op on either side.  Returns the packed (B, 48, h, w) bf16 map with NHWC memory, which
+    `_AssembleTrainFn` consumes.
+    `image` / `flipped` / `packed_bias`: the model's buffers, rewritten from the current parameters once per step
+    (`nat.ssd7_pack_heads`); they are not saved tensors.  As in `_Ssd7ConvFn`, a backward that runs after an in-place change of either
+    filter raises instead of using the newer flipped image."""
+
+    @staticmethod
+    def forward(ctx, x, conf_w, conf_b, loc_w, loc_b, image, flipped, packed_bias):
+        x = _nhwc(x.detach())
+        ctx.save_for_backward(x)
+        ctx.flipped, ctx.filters, ctx.versions = flipped, (conf_w, loc_w), (conf_w._version, loc_w._version)
+        return nat.ssd7_conv_bias(x, image, packed_bias, nat.SSD7_HEAD_CP, 3)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        conf_w, loc_w = ctx.filters
+        gy = _nhwc(gy)
+        gx = None
+        if ctx.needs_input_grad[0]:
+            if (conf_w._version, loc_w._version) != ctx.versions:
+                raise RuntimeError("_Ssd7HeadFn: the weights changed in place between this forward and its backward; the data "
+                                   "gradient's filter image follows the newest forward")
+            gx = nat.ssd7_conv_bias(gy, ctx.flipped, None, x.shape[1], 3)
+        grads = (None,) * 4
+        if any(ctx.needs_input_grad[1:5]):
+            grads = tuple(g if need else None for g, need in zip(nat.ssd7_head_wgrad(x, gy, conf_w, loc_w), ctx.needs_input_grad[1:5]))
+        return (gx,) + grads + (None, None, None)

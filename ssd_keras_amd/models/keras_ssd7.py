@@ -11,7 +11,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from .. import _native as nat
-from ._train_fns import _BnEluPoolFn, _Ssd7ConvFn
+from ._train_fns import _AssembleTrainFn, _BnEluPoolFn, _Ssd7ConvFn, _Ssd7HeadFn
 from ._common import SSDModel, he_normal_, make_priorboxes, pool_out, resolve_anchor_config
 
 
@@ -35,7 +35,7 @@ class SSD7(SSDModel):
                                           ['anchors4', 'anchors5', 'anchors6', 'anchors7'])
         he_normal_(self)
 
-    def fused_blocks(self, enable=True, training=False, convolutions=False):
+    def fused_blocks(self, enable=True, training=False, convolutions=False, heads=False):
         """Opt in to (or, with False, out of) running every Conv2D -> BatchNormalization -> ELU [-> MaxPooling2D] block of a bf16 model
         in eval mode under no_grad as ONE libssdhip launch (csrc/ssdhip_convbn.hip): the block's map is rounded to bf16 once instead of
         three times and is never written and read back between the convolution, the normalisation, the activation and the pool.  Off by
@@ -50,10 +50,20 @@ class SSD7(SSDModel):
         from the current parameters, then each block in TRAIN_CONVS runs `_Ssd7ConvFn` -- forward on the inference path's MFMA kernels
         with a bias epilogue, data gradient on the same kernels with the flipped image, weight / bias gradient in
         csrc/ssdhip_wgrad7.hip -- followed by `_BnEluPoolFn`.  The `nn.Conv2d` modules in `self.convs` are NOT called on this route
-        (their parameters are read directly), so forward hooks registered on them do not fire.  Returns the model."""
+        (their parameters are read directly), so forward hooks registered on them do not fire.
+        `heads=True` (with `training=True`; off by default, independent of `convolutions`, and every call without it behaves as before)
+        moves what lies behind the trunk in that training path to libssdhip: one launch rebuilds the packed images and biases of the four
+        source maps' heads from the current parameters, each map's conf and loc heads run as ONE 48-channel convolution under
+        `_Ssd7HeadFn` (forward and data gradient on the blocks' MFMA kernels, parameter gradients in csrc/ssdhip_heads7.hip), and
+        `_AssembleTrainFn` builds the prediction tensor from the four packed maps in one launch (one more backward) -- instead of
+        eight framework convolutions, their permutes, reshapes, concatenations and the softmax.  All four maps or none: the route needs
+        3 x 3 'same' heads with bias, bf16 weights and biases, n_boxes (n_classes + 4) <= 48 and source maps of 64, 48 or 32 channels on
+        every map; anything else keeps the framework's heads.  The `nn.Conv2d` modules in `self.conf_heads` / `self.loc_heads` are NOT
+        called on this route, so forward hooks registered on them do not fire.  Returns the model."""
         self.__dict__["_fused_blocks"] = bool(enable)
         self.__dict__["_fused_blocks_training"] = bool(enable) and bool(training)
         self.__dict__["_fused_blocks_convs"] = bool(enable) and bool(training) and bool(convolutions)
+        self.__dict__["_fused_blocks_heads"] = bool(enable) and bool(training) and bool(heads)
         return self
 
     # The blocks the training path takes when it is switched on (a set, so that a measurement can take one out: DESIGN.md 4.4,
@@ -121,6 +131,47 @@ class SSD7(SSDModel):
                 y = y.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
             full, pooled = nat.bn_elu_train_forward(y, *args)[:2]
         return (pooled if pool else full), (full if keep else None)
+
+    def _train_heads_covered(self, feats):
+        """Whether `heads=True` takes all four source maps (the conditions of `fused_blocks`' docstring, and the one-launch assembly
+        backward fitting its LDS: the kernel's own formula)."""
+        same = lambda c: (c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1
+                          and c.bias is not None and c.weight.dtype == c.bias.dtype == torch.bfloat16 and c.weight.is_cuda)
+        if not 0 < len(feats) == len(self.conf_heads) == len(self.loc_heads) <= 8:
+            return False
+        for f, ch, lh, pb in zip(feats, self.conf_heads, self.loc_heads, self.priorboxes):
+            if not (same(ch) and same(lh) and f.is_cuda and f.dtype == torch.bfloat16 and ch.in_channels == lh.in_channels == f.shape[1]
+                    and ch.out_channels == pb.n_boxes * self.n_classes and lh.out_channels == pb.n_boxes * 4
+                    and nat.ssd7_head_geometry(f.shape[1], ch.out_channels, lh.out_channels)
+                    and nat.ssd7_head_wgrad_plan(f.shape[0], f.shape[2], f.shape[3], f.shape[1]) is not None):
+                return False
+        key = (self.n_classes, tuple(int(pb.n_boxes) for pb in self.priorboxes))
+        memo = self.__dict__.setdefault("_head_assembly_fits", {})
+        if key not in memo:
+            memo[key] = nat.assemble_backward_supported(key[0], key[1], (nat.SSD7_HEAD_CP,) * len(key[1]))
+        return memo[key]
+
+    def _model_head_route(self, feats, sizes, decode):
+        """`heads=True`: the packed heads of the four source maps and the prediction assembly as libssdhip autograd nodes; None -- the
+        generic head path -- when the switch is off, outside a training step under autograd, or for heads the kernels do not cover.
+        The packed images and biases are the model's own buffers (allocated once per device, so a captured step keeps reading them),
+        REWRITTEN from the current parameters by one launch here, once per step."""
+        if (not self.__dict__.get("_fused_blocks_heads", False) or decode or not self.training or not torch.is_grad_enabled()
+                or not self._train_heads_covered(feats)):
+            return None
+        conf_w, loc_w = [ch.weight for ch in self.conf_heads], [lh.weight for lh in self.loc_heads]
+        dev = conf_w[0].device
+        hit = self.__dict__.get("_head_images")
+        if hit is None or hit[0] != dev:
+            hit = (dev,) + nat.ssd7_head_images(conf_w, loc_w)
+            self.__dict__["_head_images"] = hit
+        _, fwd, flipped, bias = hit
+        nat.ssd7_pack_heads([t.detach() for t in conf_w], [t.detach() for t in loc_w], [ch.bias.detach() for ch in self.conf_heads],
+                            [lh.bias.detach() for lh in self.loc_heads], fwd, flipped, bias)
+        ys = [_Ssd7HeadFn.apply(f, ch.weight, ch.bias, lh.weight, lh.bias, fwd[l], flipped[l], bias[l])
+              for l, (f, ch, lh) in enumerate(zip(feats, self.conf_heads, self.loc_heads))]
+        anchors = self.anchors_and_variances(sizes, dev)
+        return _AssembleTrainFn.apply(anchors, self.n_classes, [pb.n_boxes for pb in self.priorboxes], *ys)
 
     def _block_sources(self, i):
         conv, bn = self.convs[i], self.bns[i]

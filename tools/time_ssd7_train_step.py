@@ -20,6 +20,13 @@ timings, the nodes of each captured graph by type and the kernel launches of one
 profiles/ssd7_master_weights.json.
 
     python tools/time_ssd7_train_step.py --master-weights [--optimizer sgd|adam] [--out FILE] [--batches 8,32] [--rounds 7] [--steps 200]
+
+--heads times `fused_blocks(True, training=True, convolutions=True, heads=True)` against its parent route, the same call without
+`heads`, both with SGD(master_weights=True), under the same protocol; plus, per source map and pass of the predictor heads and for
+the prediction assembly, the framework's calls against the libssdhip call (the weight gradient in both of libssdhip's forms), and
+the nodes of each captured graph.  Writes profiles/ssd7_head_training.json.
+
+    python tools/time_ssd7_train_step.py --heads [--out FILE] [--batches 8,32] [--rounds 7] [--steps 200]
 """
 import argparse
 import json
@@ -300,11 +307,137 @@ def master_weights_arms(torch, args):
     return result
 
 
+def _alternating(torch, fns, rounds, replays):
+    """{name: (median us, spread us)} of the calls in `fns`, each captured into a HIP graph of its own: `rounds` rounds of `replays`
+    replays each, alternating."""
+    graphs = {name: _graphed(torch, fn) for name, fn in fns.items()}
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, replay in graphs.items():
+            times[name].append(1e3 * timed(torch, replay, replays))
+    return {name: (float(np.median(ts)), max(ts) - min(ts)) for name, ts in times.items()}
+
+
+def head_times(torch, model, batch, rounds=5, replays=100):
+    """us per source map and pass of the predictor heads -- forward, data gradient, parameter gradients -- the framework's calls (two
+    convolutions; for the data gradient also their sum) against the one libssdhip call on the packed head, each captured into a HIP
+    graph of its own, rounds alternating; median and spread (max - min).  The weight gradient is timed in both of libssdhip's forms:
+    `libssdhip_us` is ssdhip_ssd7_head_wgrad (the padded position list), `tile_form_us` is ssdhip_ssd7_conv_wgrad on the same packed
+    operands (8 x 32 position tiles; it returns the packed rows, not the four parameter gradients).  Last row: the prediction assembly,
+    forward + backward, the framework's permute / reshape / cat / softmax / cat chain against `_AssembleTrainFn`."""
+    import torch.nn.functional as F
+    from ssd_keras_amd import _native as nat
+    from ssd_keras_amd.models._train_fns import _AssembleTrainFn
+    aten = torch.ops.aten
+    out = []
+    g = torch.Generator(device="cuda").manual_seed(5)
+    conf_w, loc_w = [c.weight.detach() for c in model.conf_heads], [c.weight.detach() for c in model.loc_heads]
+    conf_b, loc_b = [c.bias.detach() for c in model.conf_heads], [c.bias.detach() for c in model.loc_heads]
+    fwd, flipped, bias = nat.ssd7_head_images(conf_w, loc_w)
+    nat.ssd7_pack_heads(conf_w, loc_w, conf_b, loc_b, fwd, flipped, bias)
+    sizes = [tuple(int(v) for v in s) for s in model.predictor_sizes()]
+    rand = lambda n, h, w, c: torch.randn((n, h, w, c), device="cuda", generator=g).to(torch.bfloat16).permute(0, 3, 1, 2)
+    for l, (h, w) in enumerate(sizes):
+        wc, wl, bc, bl = conf_w[l], loc_w[l], conf_b[l], loc_b[l]
+        nc, nl, cin = wc.shape[0], wl.shape[0], wc.shape[1]
+        x, dy = rand(batch, h, w, cin), rand(batch, h, w, nat.SSD7_HEAD_CP)
+        dyc, dyl = dy[:, :nc].contiguous(memory_format=torch.channels_last), dy[:, nc:nc + nl].contiguous(memory_format=torch.channels_last)
+        back = lambda d, wt, mask: aten.convolution_backward(d, x, wt, [wt.shape[0]], [1, 1], [1, 1], [1, 1], False, [0, 0], 1, mask)
+        passes = {
+            "forward": {"framework": lambda: (F.conv2d(x, wc, bc, padding=1), F.conv2d(x, wl, bl, padding=1)),
+                        "libssdhip": lambda: nat.ssd7_conv_bias(x, fwd[l], bias[l], nat.SSD7_HEAD_CP, 3)},
+            "dgrad": {"framework": lambda: back(dyc, wc, [True, False, False])[0] + back(dyl, wl, [True, False, False])[0],
+                      "libssdhip": lambda: nat.ssd7_conv_bias(dy, flipped[l], None, cin, 3)},
+            "wgrad": {"framework": lambda: (back(dyc, wc, [False, True, True]), back(dyl, wl, [False, True, True])),
+                      "libssdhip": lambda: nat.ssd7_head_wgrad(x, dy, wc, wl),
+                      "tile_form": lambda: nat.ssd7_conv_wgrad(x, dy, 3)}}
+        row = {"map": l + 4, "x": [batch, h, w, cin], "packed": [nc, nl, nat.SSD7_HEAD_CP],
+               "wgrad_plan": list(nat.ssd7_head_wgrad_plan(batch, h, w, cin)), "tile_form_plan": list(nat.ssd7_conv_wgrad_plan(batch, h, w, cin, 48, 3))}
+        for name, fns in passes.items():
+            got = _alternating(torch, fns, rounds, replays)
+            row[name] = {k + "_us": round(v[0], 1) for k, v in got.items()}
+            row[name].update({k + "_spread_us": round(v[1], 1) for k, v in got.items()})
+            row[name]["adopt"] = bool(got["framework"][0] - got["libssdhip"][0] > max(got["framework"][1], got["libssdhip"][1]))
+        row["framework_sum_us"] = round(sum(row[p]["framework_us"] for p in passes), 1)
+        row["libssdhip_sum_us"] = round(sum(row[p]["libssdhip_us"] for p in passes), 1)
+        out.append(row)
+    # the assembly: forward + backward from the head maps to dL/d(head maps), the upstream gradient fixed
+    n_boxes = [int(pb.n_boxes) for pb in model.priorboxes]
+    ncls = model.n_classes
+    anchors = model.anchors_and_variances(sizes, torch.device("cuda", torch.cuda.current_device()))
+    ys = [rand(batch, h, w, nat.SSD7_HEAD_CP).requires_grad_(True) for h, w in sizes]
+    confs = [rand(batch, h, w, nb * ncls).requires_grad_(True) for (h, w), nb in zip(sizes, n_boxes)]
+    locs = [rand(batch, h, w, nb * 4).requires_grad_(True) for (h, w), nb in zip(sizes, n_boxes)]
+    up = torch.randn((batch, anchors.shape[0], ncls + 12), device="cuda", generator=g)
+
+    def chain():
+        c = torch.softmax(torch.cat([t.permute(0, 2, 3, 1).reshape(batch, -1, ncls) for t in confs], dim=1).float(), dim=-1)
+        lo = torch.cat([t.permute(0, 2, 3, 1).reshape(batch, -1, 4) for t in locs], dim=1).float()
+        pred = torch.cat([c, lo, anchors.unsqueeze(0).expand(batch, -1, -1)], dim=2)
+        return torch.autograd.grad([pred], confs + locs, [up])
+
+    def own():
+        return torch.autograd.grad([_AssembleTrainFn.apply(anchors, ncls, n_boxes, *ys)], ys, [up])
+
+    got = _alternating(torch, {"framework": chain, "libssdhip": own}, rounds, replays)
+    row = {"map": "assembly", "anchors": int(anchors.shape[0])}
+    row.update({k + "_us": round(v[0], 1) for k, v in got.items()})
+    row.update({k + "_spread_us": round(v[1], 1) for k, v in got.items()})
+    row["adopt"] = bool(got["framework"][0] - got["libssdhip"][0] > max(got["framework"][1], got["libssdhip"][1]))
+    out.append(row)
+    return out
+
+
+def heads_arms(torch, args):
+    """The bf16 step with SGD(master_weights=True) on the parent route (`training=True, convolutions=True`) and with `heads=True` on top
+    of it: arms alternating, median and spread as in main(); then the per-map, per-pass table and the nodes of each captured graph."""
+    arms = {"parent": False, "heads": True}
+    result = {"device": torch.cuda.get_device_name(0), "model": "SSD7 300x300x3, 5 classes, bf16, train(), fused_blocks(True, training=True, "
+              "convolutions=True[, heads=True])",
+              "step": "forward + SSDLoss + backward + ssd_keras_amd.optimizers.SGD(master_weights=True), one HIP graph",
+              "rounds": args.rounds, "steps_per_round": args.steps, "batches": {}}
+    for batch in [int(b) for b in args.batches.split(",")]:
+        images = torch.from_numpy(np.random.RandomState(100).randint(0, 256, size=(batch, 300, 300, 3)).astype(np.float32)).cuda()
+        models = {arm: build(torch, "conv").fused_blocks(True, training=True, convolutions=True, heads=on) for arm, on in arms.items()}
+        with torch.no_grad():
+            n_anchor, width = build(torch, "off").eval()(images[:1]).shape[1:]
+        y_true = torch.from_numpy(synthetic_targets(batch, n_anchor, width)).cuda()
+        captured = {arm: graphed_step(torch, models[arm], images, y_true, "sgd", True, counted=True) for arm in arms}
+        replays = {arm: c[0] for arm, c in captured.items()}
+        for fn in replays.values():
+            timed(torch, fn, 40)
+        rounds = {arm: [] for arm in arms}
+        for _ in range(args.rounds):
+            for arm in arms:
+                rounds[arm].append(timed(torch, replays[arm], args.steps))
+        entry = {}
+        for arm in arms:
+            entry[arm] = {"median_ms": round(float(np.median(rounds[arm])), 4), "spread_ms": round(max(rounds[arm]) - min(rounds[arm]), 4),
+                          "rounds_ms": [round(v, 4) for v in rounds[arm]]}
+        for arm in arms:                                           # last: nothing here may disturb the timings above
+            entry[arm]["graph_nodes"] = graph_nodes(captured[arm][2])
+            entry[arm]["eager_kernel_launches"] = eager_launches(torch, captured[arm][1])
+        parent, heads = entry["parent"], entry["heads"]
+        entry["heads_minus_parent_ms"] = round(heads["median_ms"] - parent["median_ms"], 4)
+        entry["faster"] = bool(parent["median_ms"] - heads["median_ms"] > parent["spread_ms"] + heads["spread_ms"])
+        entry["head_maps"] = head_times(torch, models["heads"], batch)
+        result["batches"][str(batch)] = entry
+        print(json.dumps({"batch": batch, **entry}), flush=True)
+        del replays, captured, models
+        torch.cuda.empty_cache()
+    result["note"] = ("faster: the medians differ by more than the sum of the two arms' spreads (the rule behind SSD7.TRAIN_CONVS).  "
+                      "graph_nodes: the nodes of the captured step by type, read from the HIP graph itself; eager_kernel_launches: the "
+                      "kernel activities the framework's profiler records for one eager run of the same step")
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default: profiles/ssd7_conv_training.json (profiles/ssd7_master_weights.json with "
                     "--master-weights)")
     ap.add_argument("--master-weights", action="store_true", help="time the optimizer's masters off against on instead of the three routes")
+    ap.add_argument("--heads", action="store_true", help="time heads=True against the parent route (training=True, convolutions=True), "
+                    "both with SGD(master_weights=True), instead of the three routes")
     ap.add_argument("--optimizer", choices=("sgd", "adam"), default="sgd", help="the optimizer of the --master-weights arms")
     ap.add_argument("--all-layers", action="store_true", help="the conv arm routes all seven layers, not SSD7.TRAIN_CONVS")
     ap.add_argument("--batches", default="8,32")
@@ -315,9 +448,10 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("time_ssd7_train_step.py needs a GPU: there is nothing to time without one")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "ssd7_master_weights.json" if args.master_weights else "ssd7_conv_training.json")
-    if args.master_weights:
-        result = master_weights_arms(torch, args)
+        args.out = os.path.join(ROOT, "profiles", "ssd7_head_training.json" if args.heads else
+                                "ssd7_master_weights.json" if args.master_weights else "ssd7_conv_training.json")
+    if args.heads or args.master_weights:
+        result = heads_arms(torch, args) if args.heads else master_weights_arms(torch, args)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1)
