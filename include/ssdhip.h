@@ -345,7 +345,8 @@ int ssdhip_maxpool_bwd_nhwc_bf16(const void* x, const void* gy, void* gx, int B,
 /* The same when a layer's two heads were computed by ONE wider convolution (conf and loc filters concatenated along Cout,
  * padded to the MFMA kernel's 64-channel granularity): conf_h[l] / loc_h[l] point at the first conf / loc channel of pixel 0 and
  * conf_stride_h[l] / loc_stride_h[l] give the number of bf16 elements between consecutive pixels (>= n_boxes*C / n_boxes*4;
- * NULL arrays = dense heads as above). */
+ * NULL arrays = dense heads as above).  At most 8 layers; 2 <= C <= 242 (ssdhip_head_tile_anchors: beyond, even the smallest tile
+ * outgrows a launch's LDS and the call returns SSDHIP_E_BADARG). */
 int ssdhip_assemble_predictions_strided_bf16(int n_layers, const void* const* conf_h, const void* const* loc_h,
                                              const void* const* conf_bias_h, const void* const* loc_bias_h,
                                              const int* n_anchors_h, const int* n_boxes_h,
@@ -461,6 +462,10 @@ int ssdhip_decode_from_heads(int n_layers, const void* const* conf_h, const void
                              int semantics, int coords, int normalize_coords, double img_height, double img_width,
                              int border_pixels, void* out, int out_dtype, int out_rows, int* out_count,
                              int* out_anchor_idx, void* ws, size_t ws_bytes, void* stream);
+/* Host arithmetic, no launch: the anchors per tile (256, 128, 64 or 32: the largest whose rows and staging fit 60 KB of LDS) the
+ * assembly entries (for_decode == 0) or the decode-from-heads entries (for_decode != 0) use for C classes; 0 where they refuse the
+ * class count -- C outside 2..1024, an assembly tile beyond the 64 KB a launch takes, a decode tile of fewer than 64 rows. */
+int ssdhip_head_tile_anchors(int C, int for_decode);
 
 /* The same convolution followed by MaxPooling2D(pool_size 2, strides 2, padding 'same') in ONE kernel (conv1_2 -> pool1,
  * conv2_2 -> pool2, conv3_3 -> pool3 of models/keras_ssd300.py:274-290): the 2x2 maximum is taken on the float32 accumulators,

@@ -118,6 +118,7 @@ SIGNATURES = {
     "ssdhip_assemble_predictions_strided_f32": (_I, [_I] + [_P] * 7 + [_I] * 3 + [_P, _P]),
     "ssdhip_decode_from_heads_f32": (_I, [_I] + [_P] * 7 + [_I] * 3 + [_D, _D] + [_I] * 6 + [_D, _D, _I, _P, _I, _I] + [_P] * 3 + [_SZ, _P]),
     "ssdhip_decode_from_heads": (_I, [_I] + [_P] * 9 + [_I] * 3 + [_D, _D] + [_I] * 6 + [_D, _D, _I, _P, _I, _I] + [_P] * 3 + [_SZ, _P]),
+    "ssdhip_head_tile_anchors": (_I, [_I, _I]),
     "ssdhip_conv2d_same_pool2_nhwc_bf16": (_I, [_P] * 4 + [_I] * 8 + [_P]),
     "ssdhip_conv2d_same_group_nhwc_bf16": (_I, [_I] + [_P] * 11 + [_I, _P]),
     "ssdhip_conv3x3_c64_nhwc_bf16": (_I, [_P] * 4 + [_I] * 8 + [_P]),

@@ -1652,7 +1652,7 @@ static int decode_from_heads_any(int src_f32, int n_layers, const void* const* c
     HeadParams hp;
     HeadSource src;
     src.hp = &hp; src.anchors_var = anchors_var; src.tiles = 0;
-    size_t tile_lds = 60 * 1024;
+    size_t tile_lds = HEAD_TILE_BUDGET;
 #if defined(SSDHIP_PROFILE)
     if (const char* e = getenv("SSDHIP_HEADS_LDS_KB")) { const int v = atoi(e); if (v >= 8 && v <= 120) tile_lds = (size_t)v * 1024; }   // tile sweep
 #endif

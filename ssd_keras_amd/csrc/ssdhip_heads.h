@@ -38,6 +38,23 @@ __host__ __device__ inline size_t head_stage_bytes(int TA, int C) {
 }
 __host__ __device__ inline size_t head_tile_lds(int TA, int C) { return (size_t)TA * (C + 12) * sizeof(float) + head_stage_bytes(TA, C); }
 
+// Anchors per tile: the largest of 256, 128, 64, 32 whose head_tile_lds fits max_lds bytes (32 even where it does not).
+static inline int head_tile_anchors(int C, size_t max_lds) {
+    int TA = 256;
+    while (TA > 32 && head_tile_lds(TA, C) > max_lds) TA >>= 1;
+    return TA;
+}
+// The tile budget of every entry, and the dynamic LDS a launch gets without an opt-in.
+constexpr size_t HEAD_TILE_BUDGET = 60 * 1024, HEAD_LAUNCH_LDS = 64 * 1024;
+// What ssdhip_head_tile_anchors exports: the tile of the assembly (for_decode == 0: head_kernel, 256 threads) or decode-from-heads
+// (scan_heads_kernel, one thread per row: at least one wave of rows) entries for C classes, 0 where they refuse the class count.
+static inline int head_entry_tile_anchors(int C, int for_decode) {
+    if (C < 2 || C > 1024) return 0;
+    const int TA = head_tile_anchors(C, HEAD_TILE_BUDGET);
+    if (for_decode) return TA >= 64 ? TA : 0;
+    return head_tile_lds(TA, C) <= HEAD_LAUNCH_LDS ? TA : 0;
+}
+
 // Which layer / anchors the tile `tile_id` of the launch covers.
 __device__ __forceinline__ void head_tile_of(const HeadParams& hp, int tile_id, int& l, int& a0, int& na) {
     l = 0;
@@ -46,6 +63,10 @@ __device__ __forceinline__ void head_tile_of(const HeadParams& hp, int tile_id, 
     na = min(hp.TA, hp.n_anchors[l] - a0);
 }
 
+// head_sum: the softmax denominator is accumulated in double and rounded once.  A float32 running sum rounds at every class, and on a
+// row whose classes share one logit (bf16 logits often do) every rounding errs the same way: 80 equal terms next to one large one
+// put a probability of 0.68 off by 2.0e-6 at 81 classes and 0.95 off by 2.3e-6 at 62 (tests/test_decode_from_heads_gpu.py, planted
+// rows), beyond the 2e-6 bar of the assembled probabilities.  In double the terms add exactly; what is left is expf and two roundings.
 // Builds rows[a][0..C+11] = [softmax(conf + bias) | loc + bias | anchor | variances] for anchors a0..a0+na-1 of layer l, image b.
 // `rows`: [TA][C+12] float in LDS, `cl`: [TA][C] + [TA][4] bf16 staging in LDS.  Ends with a __syncthreads().
 __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const float* __restrict__ anchors_var, int l, int b, int a0, int na,
@@ -98,8 +119,9 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
             float* r = rows + (size_t)a * L;
             float mx = -INFINITY;
             for (int c = 0; c < C; ++c) mx = fmaxf(mx, r[c]);
-            float sum = 0.f;
-            for (int c = 0; c < C; ++c) { const float e = expf(r[c] - mx); r[c] = e; sum += e; }
+            double acc = 0.0;                                   // (head_sum: why the sum is not a float)
+            for (int c = 0; c < C; ++c) { const float e = expf(r[c] - mx); r[c] = e; acc += (double)e; }
+            const float sum = (float)acc;
             for (int c = 0; c < C; ++c) r[c] = r[c] / sum;
             const float* av = anchors_var + (size_t)(hp.anchor_off[l] + a0 + a) * 8;
             for (int k = 0; k < 8; ++k) r[C + 4 + k] = av[k];
@@ -169,17 +191,18 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
                     r[c] = v;
                     mx = fmaxf(mx, v);
                 }
-                float sum = 0.f;
+                double acc = 0.0;                               // (head_sum)
                 for (c = 0; c + 4 <= C; c += 4) {
                     float e[4];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) e[u] = r[c + u];
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) { e[u] = expf(e[u] - mx); sum += e[u]; }
+                    for (int u = 0; u < 4; ++u) { e[u] = expf(e[u] - mx); acc += (double)e[u]; }
 #pragma unroll
                     for (int u = 0; u < 4; ++u) r[c + u] = e[u];
                 }
-                for (; c < C; ++c) { const float e = expf(r[c] - mx); r[c] = e; sum += e; }
+                for (; c < C; ++c) { const float e = expf(r[c] - mx); r[c] = e; acc += (double)e; }
+                const float sum = (float)acc;
                 for (c = 0; c + 4 <= C; c += 4) {
                     float e[4];
 #pragma unroll
@@ -260,8 +283,9 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
             r[c] = v;
             mx = fmaxf(mx, v);
         }
-        float sum = 0.f;
-        for (int c = 0; c < C; ++c) { const float e = expf(r[c] - mx); r[c] = e; sum += e; }
+        double acc = 0.0;                                       // (head_sum)
+        for (int c = 0; c < C; ++c) { const float e = expf(r[c] - mx); r[c] = e; acc += (double)e; }
+        const float sum = (float)acc;
         for (int c = 0; c < C; ++c) r[c] = r[c] / sum;
         const bf16_t* lb = hp.loc_bias[l] ? hp.loc_bias[l] + box * 4 : nullptr;
         for (int k = 0; k < 4; ++k) r[C + k] = lb ? bf16_float(bf16_bits(bf16_float(ll[a * 4 + k]) + bf16_float(lb[k]))) : bf16_float(ll[a * 4 + k]);
@@ -279,8 +303,7 @@ static inline int head_fill_params(HeadParams& hp, int n_layers, const void* con
                                    size_t max_lds, int* tiles_out, int src_f32 = 0) {
     if (n_layers <= 0 || n_layers > MAX_PRED_LAYERS || !conf_h || !loc_h || !n_anchors_h || !n_boxes_h || N <= 0 || C < 2 || C > 1024)
         return SSDHIP_E_BADARG;
-    int TA = 256;
-    while (TA > 32 && head_tile_lds(TA, C) > max_lds) TA >>= 1;
+    const int TA = head_tile_anchors(C, max_lds);
     hp.n_layers = n_layers; hp.N = N; hp.C = C; hp.TA = TA; hp.src_f32 = src_f32 ? 1 : 0;
     { const char* e = getenv("SSDHIP_HEADS_DMA"); hp.row_dma = !(e && e[0] == '0'); }
     if (src_f32 && (conf_bias_h || loc_bias_h)) {

@@ -780,6 +780,8 @@ extern "C" int ssdhip_preprocess_nhwc_f32_to_bf16(const float* images, void* out
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 
+extern "C" int ssdhip_head_tile_anchors(int C, int for_decode) { return head_entry_tile_anchors(C, for_decode); }
+
 extern "C" int ssdhip_assemble_predictions_strided_bf16(int n_layers, const void* const* conf_h, const void* const* loc_h,
                                                         const void* const* conf_bias_h, const void* const* loc_bias_h,
                                                         const int* n_anchors_h, const int* n_boxes_h,
@@ -788,10 +790,11 @@ extern "C" int ssdhip_assemble_predictions_strided_bf16(int n_layers, const void
                                                         void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!anchors_var || !y_pred || B <= 0) return SSDHIP_E_BADARG;
+    if (!head_entry_tile_anchors(C, 0)) return SSDHIP_E_BADARG;      // the smallest tile's rows exceed what a launch takes (C >= 243)
     HeadParams hp;
     int tiles = 0;
     const int rc = head_fill_params(hp, n_layers, conf_h, loc_h, conf_bias_h, loc_bias_h, n_anchors_h, n_boxes_h, conf_stride_h,
-                                    loc_stride_h, N, C, 60 * 1024, &tiles);
+                                    loc_stride_h, N, C, HEAD_TILE_BUDGET, &tiles);
     if (rc != SSDHIP_OK) return rc;
     hipLaunchKernelGGL(head_kernel, dim3(tiles, B), dim3(256), head_tile_lds(hp.TA, C), stream, hp, anchors_var, y_pred);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
@@ -805,10 +808,11 @@ extern "C" int ssdhip_assemble_predictions_strided_f32(int n_layers, const void*
                                                        float* y_pred, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!anchors_var || !y_pred || B <= 0) return SSDHIP_E_BADARG;
+    if (!head_entry_tile_anchors(C, 0)) return SSDHIP_E_BADARG;      // the smallest tile's rows exceed what a launch takes (C >= 243)
     HeadParams hp;
     int tiles = 0;
     const int rc = head_fill_params(hp, n_layers, conf_h, loc_h, nullptr, nullptr, n_anchors_h, n_boxes_h, conf_stride_h, loc_stride_h,
-                                    N, C, 60 * 1024, &tiles, 1);
+                                    N, C, HEAD_TILE_BUDGET, &tiles, 1);
     if (rc != SSDHIP_OK) return rc;
     hipLaunchKernelGGL(head_kernel, dim3(tiles, B), dim3(256), head_tile_lds(hp.TA, C), stream, hp, anchors_var, y_pred);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
