@@ -901,6 +901,39 @@ int ssdhip_sgd_step(int n_tensors, void* const* params_h, const void* const* gra
 int ssdhip_sgd_step_bf16(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h, void* const* bufs_h,
                          const long long* numel_h, int group, void* state, int rule, int nesterov, int tick, void* stream);
 
+/* What a training LOOP whose step is a replayed HIP graph needs on the device (csrc/ssdhip_fit.hip; ssd_keras_amd/training.py): the loss
+ * Keras reports -- mean(compute_loss) + l2 * sum over the conv kernels of sum(w^2) -- summed over an epoch with no host read per step.
+ * ssdhip_sumsq_partials    sum of squares over a table of dense tensors named by HOST arrays (device pointers, element counts; the table
+ *                          travels in the kernel arguments, 128 tensors per launch, longer tables take more launches).  dtype:
+ *                          SSDHIP_SUMSQ_F32 or SSDHIP_SUMSQ_BF16 for the whole table; pointers need their element's alignment only.
+ *                          Every tensor is cut into chunks of SSDHIP_SUMSQ_CHUNK elements (the last one short); chunk c of the table,
+ *                          counted tensor after tensor, is one workgroup and writes partials[c], one float32, exactly once.  n_partials
+ *                          must equal the table's chunk count: sum over tensors of ceil(numel / SSDHIP_SUMSQ_CHUNK).  Order of additions
+ *                          inside a chunk, with V = 4 (float32) or 8 (bf16): element e belongs to lane (e / V) % 256 as that lane's value
+ *                          (e / (256 V)) V + e % V, values past the tensor's end are +0; per lane acc = acc + x * x from 0 over its 32
+ *                          values (float32, one rounding per operation); per wave of 64 lanes v[l] = v[l] + v[l + s] for s = 32 .. 1;
+ *                          then ((w0 + w1) + w2) + w3 over the four waves.  No atomics, nothing to zero beforehand.
+ * ssdhip_fit_meter_reset   writes every byte of a state block: sum 0, seen 0, steps 0, first_bad -1, last 0.
+ * ssdhip_fit_meter_update  one step into the block, one workgroup.  loss [B] float32 (SSDLoss.compute_loss), partials [n_partials] (may be
+ *                          none: NULL, 0):  m = float32(sum_i float64(loss[i]) / B);  q = float32(sum_j float64(partials[j]));  both sums
+ *                          in index order;  batch_loss = m + l2 * q (two float32 operations);  sum += float64(batch_loss) * B;  seen += B;
+ *                          steps += 1;  last = batch_loss;  first_bad = steps - 1 if batch_loss is not finite and first_bad < 0.
+ * The block is plain global memory, 16-byte aligned, ssdhip_fit_meter_state_bytes() bytes; every launch is stream-ordered. */
+#define SSDHIP_SUMSQ_CHUNK 8192
+#define SSDHIP_SUMSQ_F32 0
+#define SSDHIP_SUMSQ_BF16 1
+typedef struct ssdhip_fit_meter_state {
+    double sum;                             /* sum over the steps of float64(batch_loss) * B */
+    long long seen, steps, first_bad;       /* samples, steps, index of the first step with a non-finite batch_loss or -1 */
+    float last;                             /* the latest batch_loss */
+    int reserved[3];
+} ssdhip_fit_meter_state;
+int ssdhip_sumsq_partials(int n_tensors, const void* const* tensors_h, const long long* numel_h, int dtype, float* partials,
+                          long long n_partials, void* stream);
+size_t ssdhip_fit_meter_state_bytes(void);
+int ssdhip_fit_meter_reset(void* state, void* stream);
+int ssdhip_fit_meter_update(const float* loss, int B, const float* partials, long long n_partials, float l2, void* state, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The decisions of the original-SSD augmentation chain for a whole batch in ONE launch (csrc/ssdhip_augment.hip): SSDExpand ->
  * SSDRandomCrop -> RandomFlip -> ResizeRandomInterp of data_generator/data_augmentation_chain_original_ssd.py:208-280 (with

@@ -178,6 +178,10 @@ SIGNATURES = {
     "ssdhip_sgd_set_lr": (_I, [_P, _I, _D, _P]),
     "ssdhip_sgd_step": (_I, [_I] + [_P] * 4 + [_I, _P, _I, _I, _I, _P]),
     "ssdhip_sgd_step_bf16": (_I, [_I] + [_P] * 5 + [_I, _P, _I, _I, _I, _P]),
+    "ssdhip_sumsq_partials": (_I, [_I, _P, _LLP, _I, _P, _LL, _P]),
+    "ssdhip_fit_meter_state_bytes": (_SZ, []),
+    "ssdhip_fit_meter_reset": (_I, [_P, _P]),
+    "ssdhip_fit_meter_update": (_I, [_P, _I, _P, _LL, _F, _P, _P]),
     "ssdhip_augment_plans": (_I, [_P] + [_I] * 6 + [_P] * 6),
     "ssdhip_ssd_augment_decide": (_I, [_PARAMS, _I] + [_P] * 8),
     "ssdhip_ssd_augment_decide_stream": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 10),
@@ -831,6 +835,75 @@ def sgd_step_bf16(table, block, group, rule, nesterov, tick):
     device, n, pp, gp, wp, mp, nn = table
     launch("ssdhip_sgd_step_bf16", device, n, pp, gp, wp, mp, nn, int(group), _ptr(block), int(rule), 1 if nesterov else 0,
            1 if tick else 0)
+
+
+# ---- the training loop's device side (csrc/ssdhip_fit.hip) -----------------------------------------------------------------------
+SUMSQ_CHUNK = 8192                                     # SSDHIP_SUMSQ_CHUNK
+SUMSQ_F32, SUMSQ_BF16 = 0, 1                           # SSDHIP_SUMSQ_F32 / SSDHIP_SUMSQ_BF16
+# struct ssdhip_fit_meter_state (include/ssdhip.h)
+FIT_METER_STATE = np.dtype([("sum", "<f8"), ("seen", "<i8"), ("steps", "<i8"), ("first_bad", "<i8"), ("last", "<f4"),
+                            ("reserved", "<i4", (3,))])
+
+
+def sumsq_chunks(numels):
+    """Partials of ssdhip_sumsq_partials for tensors of these element counts: one per chunk of SUMSQ_CHUNK, a tensor's last one short."""
+    return sum(-(-int(n) // SUMSQ_CHUNK) for n in numels)
+
+
+def sumsq_table(tensors, device):
+    """The HOST table of ssdhip_sumsq_partials over dense tensors, all float32 or all bf16 (views into larger buffers are fine: only
+    the element's own alignment is needed).  It travels in the kernel arguments.  Returns (device, n, pointers, counts, dtype flag,
+    number of partials); the caller keeps the tensors alive."""
+    torch = _torch()
+    n = len(tensors)
+    dtypes = {t.dtype for t in tensors}
+    if n and dtypes not in ({torch.float32}, {torch.bfloat16}):
+        raise SsdHipError("sumsq_table: the tensors must be all float32 or all bfloat16")
+    for t in tensors:
+        if not t.is_cuda or t.device != device:
+            raise SsdHipError("sumsq_table: every tensor must live on %s: ssd_keras_amd has no CPU path" % (device,))
+        if not (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))):
+            raise SsdHipError("sumsq_table: the tensors must be dense")
+    flag = SUMSQ_BF16 if dtypes == {torch.bfloat16} else SUMSQ_F32
+    vp, ll = ctypes.c_void_p * n, ctypes.c_longlong * n
+    numels = [t.numel() for t in tensors]
+    return device, n, vp(*[t.data_ptr() for t in tensors]), ll(*numels), flag, sumsq_chunks(numels)
+
+
+def sumsq_partials(table, partials):
+    """One float32 partial per chunk of the table's tensors into `partials` (float32, exactly the table's chunk count)."""
+    device, n, ptrs, numels, flag, chunks = table
+    torch = _torch()
+    if partials.dtype != torch.float32 or not partials.is_contiguous() or partials.device != device:
+        raise SsdHipError("sumsq_partials: `partials` must be a contiguous float32 tensor on the tensors' device")
+    launch("ssdhip_sumsq_partials", device, n, ptrs, numels, flag, _ptr(partials), partials.numel())
+
+
+def fit_meter_state_bytes():
+    return int(load().ssdhip_fit_meter_state_bytes())
+
+
+def fit_meter_reset(block):
+    launch("ssdhip_fit_meter_reset", block.device, _ptr(block))
+
+
+def fit_meter_update(block, loss, partials, l2):
+    """One step's loss (float32 (B,)) and the penalty's partials (float32, or None) into the meter's state block."""
+    torch = _torch()
+    require_cuda(loss, "loss")
+    if loss.dtype != torch.float32 or loss.dim() != 1:
+        raise SsdHipError("fit_meter_update: loss must be a float32 (batch,) tensor")
+    if partials is not None and (partials.dtype != torch.float32 or not partials.is_contiguous() or partials.device != loss.device):
+        raise SsdHipError("fit_meter_update: partials must be a contiguous float32 tensor on the loss's device")
+    launch("ssdhip_fit_meter_update", loss.device, _ptr(loss), int(loss.numel()), _ptr(partials),
+           int(partials.numel()) if partials is not None else 0, float(l2), _ptr(block))
+
+
+def fit_meter_parse(raw):
+    """A state block's bytes (a uint8 NumPy array) as {"sum", "seen", "steps", "first_bad", "last"}."""
+    st = np.asarray(raw, dtype=np.uint8)[:FIT_METER_STATE.itemsize].view(FIT_METER_STATE)[0]
+    return {"sum": float(st["sum"]), "seen": int(st["seen"]), "steps": int(st["steps"]), "first_bad": int(st["first_bad"]),
+            "last": np.float32(st["last"])}
 
 
 def maxpool_bwd(x, gy, kernel, stride, pad=0):

@@ -256,6 +256,17 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
                         st["master"].copy_(p)
                         self._versions[p] = p._version
 
+    def mark_replayed(self):
+        """After replays of a captured `step()`, which run no Python: the host's share of an eager step -- the `_version` of every
+        parameter that has a gradient bumped once (caches keyed on it, the models' derived tensors among them, must see the update)
+        and, for the parameters with a master, remembered as this optimizer's own write."""
+        ps = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        if ps:
+            _bump_versions(ps)
+        for p in ps:
+            if p in self._versions:
+                self._versions[p] = p._version
+
     # ---- the scalars: one state block per device, a dictionary on the host for the tensor expressions -------------------------------
     def _block_keys(self):
         return [k for k in self.state if isinstance(k, str) and k.startswith(self._BLOCK)]
