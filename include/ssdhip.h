@@ -225,6 +225,34 @@ int ssdhip_match_predictions_multi(const float* pred, const int* pred_segment, c
                                    int* false_pos, int* cum_true_pos, int* cum_false_pos, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * COCO bbox evaluation: the COCOeval(cocoGt, cocoDt, 'bbox') cell of ssd300_evaluation_COCO.ipynb (evaluate() and accumulate();
+ * csrc/ssdhip_cocoeval.hip, protocol restated in tests/np_cocoeval.py).  A pair is (category slot k, image index i), pair index
+ * k * n_images + i; boxes are [x, y, w, h] float64; every array below is a device array.
+ *
+ * ssdhip_coco_match: the detections (det_pair, det_box [n_det,4], det_score) and the ground truth (gt_pair, gt_box [n_gt,4], gt_area,
+ * gt_crowd uint8) in input order.  Outputs: det_order [n_det] -- the detections pair by pair, inside a pair by descending score,
+ * equal scores in input order (argsort(-score, kind='mergesort')) -- and det_offsets [n_pairs+1], its CSR; gt_order [n_gt] (pair by
+ * pair, input order) and gt_offsets [n_pairs+1]; det_match [A*T, n_det] at the positions of det_order, for the first
+ * min(count, max_det) detections of each pair (the rest is not written): (g + 1) << 1 | ignore, g the matched ground truth's position
+ * in its pair (0: unmatched); gt_ignore [A, n_gt] at the positions of gt_order; pair_npig [n_pairs, A] non-ignored ground truth.
+ * iou_thrs [T], area_rng [A,2]; T <= 32, A <= 8.
+ *
+ * ssdhip_coco_accumulate: from those arrays precision [T,R,K,A,M], recall [T,K,A,M] and scores [T,R,K,A,M] float64, -1 where a
+ * (category, area range) has no non-ignored ground truth; every element is written.  max_dets [M] ascending, max_det = its last value
+ * (the cut ssdhip_coco_match applied), rec_thrs [R] non-decreasing; M <= 8, R <= 1024. */
+size_t ssdhip_coco_match_workspace_bytes(int n_det, int n_gt, int T, int A);
+int ssdhip_coco_match(const int* det_pair, const double* det_box, const double* det_score, int n_det, const int* gt_pair,
+                      const double* gt_box, const double* gt_area, const unsigned char* gt_crowd, int n_gt, int n_pairs,
+                      const double* iou_thrs, int T, const double* area_rng, int A, int max_det, int* det_order, int* det_offsets,
+                      int* gt_order, int* gt_offsets, int* det_match, unsigned char* gt_ignore, int* pair_npig, void* ws,
+                      size_t ws_bytes, void* stream);
+size_t ssdhip_coco_accumulate_workspace_bytes(int n_det, int K);
+int ssdhip_coco_accumulate(const int* det_pair, const double* det_score, const int* det_order, const int* det_offsets, int n_det,
+                           const int* det_match, const int* pair_npig, int n_images, int K, int T, int A, const int* max_dets, int M,
+                           int max_det, const double* rec_thrs, int R, double* precision, double* recall, double* scores, void* ws,
+                           size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Graph glue between the convolutions (bf16 activations, NHWC = torch channels_last; C % 8 == 0; pointers
  * 16-byte aligned).  Each call is ONE pass over the tensor where the framework path runs 2-7 elementwise kernels.
  *

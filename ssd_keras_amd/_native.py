@@ -76,6 +76,10 @@ SIGNATURES = {
     "ssdhip_match_predictions_workspace_bytes": (_SZ, [_I, _I]),
     "ssdhip_match_predictions": (_I, [_P, _P, _I] + [_P] * 3 + [_I, _I, _D, _I] + [_P] * 6 + [_SZ, _P]),
     "ssdhip_match_predictions_multi": (_I, [_P] * 3 + [_I] + [_P] * 3 + [_I, _I, _P, _I, _D, _I] + [_P] * 6 + [_SZ, _P]),
+    "ssdhip_coco_match_workspace_bytes": (_SZ, [_I] * 4),
+    "ssdhip_coco_match": (_I, [_P] * 3 + [_I] + [_P] * 4 + [_I, _I, _P, _I, _P, _I, _I] + [_P] * 8 + [_SZ, _P]),
+    "ssdhip_coco_accumulate_workspace_bytes": (_SZ, [_I, _I]),
+    "ssdhip_coco_accumulate": (_I, [_P] * 4 + [_I, _P, _P] + [_I] * 4 + [_P, _I, _I, _P, _I] + [_P] * 4 + [_SZ, _P]),
     "ssdhip_bias_act_nhwc_bf16": (_I, [_P] * 3 + [_LL, _I, _I, _P]),
     "ssdhip_bias_act_maxpool_nhwc_bf16": (_I, [_P] * 3 + [_I] * 10 + [_P]),
     "ssdhip_l2_normalize_nhwc_bf16": (_I, [_P] * 3 + [_LL, _I, _P]),
@@ -2165,6 +2169,74 @@ def match_predictions_all(pred, pred_segment, pred_class, class_start, gt_boxes,
            float(matching_iou_threshold), BORDER[border_pixels], *[ctypes.c_void_p(out[i].data_ptr()) for i in range(5)], _ptr(ws),
            ws.numel())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# COCO bbox evaluation (csrc/ssdhip_cocoeval.hip)
+# ------------------------------------------------------------------------------------------------
+COCO_MAX_T, COCO_MAX_A, COCO_MAX_M, COCO_MAX_R = 32, 8, 8, 1024
+
+
+def coco_match(det_pair, det_box, det_score, gt_pair, gt_box, gt_area, gt_crowd, n_pairs, iou_thrs, area_rng, max_det):
+    """COCOeval.evaluate() on the device (ssdhip_coco_match).  NumPy arrays in input order: det_pair (n_det,) pair index of each
+    detection, det_box (n_det, 4) [x, y, w, h], det_score; gt_pair, gt_box, gt_area, gt_crowd; iou_thrs (T,), area_rng (A, 2).
+    Returns a dict of CUDA tensors: the uploaded inputs and det_order, det_offsets, gt_order, gt_offsets, det_match (A*T, n_det) int32,
+    gt_ignore (A, n_gt) uint8, pair_npig (n_pairs, A) int32 (layouts: include/ssdhip.h)."""
+    torch = _torch()
+    lib = load()
+    if not torch.cuda.is_available():
+        raise SsdHipError("COCO evaluation needs a GPU: ssd_keras_amd has no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n_det, n_gt = int(len(det_pair)), int(len(gt_pair))
+    T, A = int(len(iou_thrs)), int(len(area_rng))
+
+    def up(a, dtype, shape):
+        a = np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(shape))
+        if a.shape[0] == 0:                                          # a valid pointer for an empty side
+            a = np.zeros((1,) + tuple(a.shape[1:]), dtype=dtype)
+        return torch.from_numpy(a).to(dev)
+
+    r = dict(n_det=n_det, n_gt=n_gt, n_pairs=int(n_pairs), T=T, A=A, max_det=int(max_det))
+    r["det_pair"], r["det_box"], r["det_score"] = up(det_pair, np.int32, (-1,)), up(det_box, np.float64, (-1, 4)), up(det_score, np.float64, (-1,))
+    r["gt_pair"], r["gt_box"], r["gt_area"] = up(gt_pair, np.int32, (-1,)), up(gt_box, np.float64, (-1, 4)), up(gt_area, np.float64, (-1,))
+    r["gt_crowd"] = up(gt_crowd, np.uint8, (-1,))
+    r["iou_thrs"], r["area_rng"] = up(iou_thrs, np.float64, (-1,)), up(area_rng, np.float64, (-1, 2))
+    r["det_order"] = torch.empty((max(n_det, 1),), dtype=torch.int32, device=dev)
+    r["det_offsets"] = torch.empty((n_pairs + 1,), dtype=torch.int32, device=dev)
+    r["gt_order"] = torch.empty((max(n_gt, 1),), dtype=torch.int32, device=dev)
+    r["gt_offsets"] = torch.empty((n_pairs + 1,), dtype=torch.int32, device=dev)
+    r["det_match"] = torch.empty((A * T, max(n_det, 1)), dtype=torch.int32, device=dev)
+    r["gt_ignore"] = torch.empty((A, max(n_gt, 1)), dtype=torch.uint8, device=dev)
+    r["pair_npig"] = torch.empty((n_pairs, A), dtype=torch.int32, device=dev)
+    need = lib.ssdhip_coco_match_workspace_bytes(n_det, n_gt, T, A)
+    if need == 0:
+        raise SsdHipError("unsupported COCO evaluation shape: %d thresholds, %d area ranges" % (T, A))
+    ws = workspaces.get(dev, "coco_eval", need)
+    launch("ssdhip_coco_match", dev, _ptr(r["det_pair"]), _ptr(r["det_box"]), _ptr(r["det_score"]), n_det, _ptr(r["gt_pair"]),
+           _ptr(r["gt_box"]), _ptr(r["gt_area"]), _ptr(r["gt_crowd"]), n_gt, int(n_pairs), _ptr(r["iou_thrs"]), T, _ptr(r["area_rng"]), A,
+           int(max_det), _ptr(r["det_order"]), _ptr(r["det_offsets"]), _ptr(r["gt_order"]), _ptr(r["gt_offsets"]), _ptr(r["det_match"]),
+           _ptr(r["gt_ignore"]), _ptr(r["pair_npig"]), _ptr(ws), ws.numel())
+    return r
+
+
+def coco_accumulate(r, n_images, K, max_dets, rec_thrs):
+    """COCOeval.accumulate() on the device (ssdhip_coco_accumulate) from coco_match's dict.  Returns CUDA float64 tensors
+    precision (T, R, K, A, M), recall (T, K, A, M), scores (T, R, K, A, M)."""
+    torch = _torch()
+    lib = load()
+    dev = r["det_order"].device
+    T, A, M, R = r["T"], r["A"], int(len(max_dets)), int(len(rec_thrs))
+    md = torch.from_numpy(np.ascontiguousarray(np.asarray(max_dets, dtype=np.int32))).to(dev)
+    rt = torch.from_numpy(np.ascontiguousarray(np.asarray(rec_thrs, dtype=np.float64))).to(dev)
+    precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+    scores = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+    need = lib.ssdhip_coco_accumulate_workspace_bytes(r["n_det"], int(K))
+    ws = workspaces.get(dev, "coco_eval", need)
+    launch("ssdhip_coco_accumulate", dev, _ptr(r["det_pair"]), _ptr(r["det_score"]), _ptr(r["det_order"]), _ptr(r["det_offsets"]), r["n_det"],
+           _ptr(r["det_match"]), _ptr(r["pair_npig"]), int(n_images), int(K), T, A, _ptr(md), M, r["max_det"], _ptr(rt), R,
+           _ptr(precision), _ptr(recall), _ptr(scores), _ptr(ws), ws.numel())
+    return precision, recall, scores
 
 
 def box_filter(boxes, box_image, image_hw, check_overlap, check_min_area, check_degenerate, criterion, lower, upper, min_area,
