@@ -693,40 +693,111 @@ def shadow_refresh(table):
     launch("ssdhip_shadow_refresh", dev_tab.device, _ptr(dev_tab), n_w, n_tiles, n_v, n_vb)
 
 
-def sgd_table(params, grads, bufs, device):
-    """The HOST table of ssdhip_sgd_momentum_step over dense float32 tensors (parameter, gradient, momentum buffer of one memory
-    layout each): ctypes arrays of device pointers and element counts.  It travels in the kernel arguments -- nothing is uploaded."""
+def _optim_table(what, device, bf16, cols):
+    """The HOST table of an optimizer step (csrc/ssdhip_optim_step.h): ctypes arrays of device pointers, one per column in the
+    kernel's order, and of element counts.  It travels in the kernel arguments -- nothing is uploaded.  Parameter and gradient (the
+    first two columns) are dense float32, or with `bf16` dense bf16 beside a float32 master; every further column is dense float32;
+    one size per row, 16-byte aligned, on `device`.  A column that is None (no amsgrad) stays None."""
     torch = _torch()
-    n = len(params)
-    for p, g, m in zip(params, grads, bufs):
-        for t in (p, g, m):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.data_ptr() % 16 or t.device != device:
-                raise SsdHipError("sgd_table: parameter, gradient and momentum buffer must be dense float32 of one size on one device")
+    present = [c for c in cols if c is not None]
+    for row in zip(*present):
+        for k, t in enumerate(row):
+            want = torch.bfloat16 if bf16 and k < 2 else torch.float32
+            if t.dtype != want or not t.is_contiguous() or t.numel() != row[0].numel() or t.data_ptr() % 16 or t.device != device:
+                raise SsdHipError("%s: %s, of one size on one device" % (what, (
+                    "parameter and gradient must be dense bf16, master and buffers dense float32" if bf16 else
+                    "parameter, gradient and state buffers must be dense float32")))
+    n = len(cols[0])
     vp, ll = ctypes.c_void_p * n, ctypes.c_longlong * n
-    return (device, n, vp(*[p.data_ptr() for p in params]), vp(*[g.data_ptr() for g in grads]), vp(*[m.data_ptr() for m in bufs]),
-            ll(*[p.numel() for p in params]))
+    return ((device, n) + tuple(None if c is None else vp(*[t.data_ptr() for t in c]) for c in cols)
+            + (ll(*[p.numel() for p in cols[0]]),))
+
+
+def _optim_step(name, table, *args):
+    launch(name, table[0], *table[1:], *args)
+
+
+def sgd_table(params, grads, bufs, device):
+    """The table of ssdhip_sgd_momentum_step and ssdhip_sgd_step: parameter, gradient and momentum buffer (or velocity)."""
+    return _optim_table("sgd_table", device, False, [params, grads, bufs])
+
+
+def sgd_table_bf16(params, grads, masters, bufs, device):
+    """The table of ssdhip_sgd_step_bf16: bf16 parameter and gradient, float32 master and buffer of every tensor."""
+    return _optim_table("sgd_table_bf16", device, True, [params, grads, masters, bufs])
+
+
+def adam_table(params, grads, ms, vs, vhats, device):
+    """The table of ssdhip_adam_step: parameter, gradient, m, v and (amsgrad, else None) vhat of every tensor."""
+    return _optim_table("adam_table", device, False, [params, grads, ms, vs, vhats])
+
+
+def adam_table_bf16(params, grads, masters, ms, vs, vhats, device):
+    """The table of ssdhip_adam_step_bf16: bf16 parameter and gradient, float32 master, m, v and (amsgrad) vhat of every tensor."""
+    return _optim_table("adam_table_bf16", device, True, [params, grads, masters, ms, vs, vhats])
 
 
 def sgd_momentum_step(table, lr, momentum, weight_decay=0.0):
-    device, n, pp, gp, mp, nn = table
-    launch("ssdhip_sgd_momentum_step", device, n, pp, gp, mp, nn, float(lr), float(momentum), float(weight_decay))
+    _optim_step("ssdhip_sgd_momentum_step", table, float(lr), float(momentum), float(weight_decay))
 
 
-# struct ssdhip_adam_state / ssdhip_adam_group (include/ssdhip.h), for reading a state block back on the host
-ADAM_STATE_HEAD = np.dtype([("iterations", "<i8"), ("n_groups", "<i4"), ("reserved", "<i4")])
+def sgd_step(table, block, group, rule, nesterov, tick):
+    _optim_step("ssdhip_sgd_step", table, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0)
+
+
+def sgd_step_bf16(table, block, group, rule, nesterov, tick):
+    _optim_step("ssdhip_sgd_step_bf16", table, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0)
+
+
+def adam_step(table, block, group, tick):
+    _optim_step("ssdhip_adam_step", table, int(group), _ptr(block), 1 if tick else 0)
+
+
+def adam_step_bf16(table, block, group, tick):
+    _optim_step("ssdhip_adam_step_bf16", table, int(group), _ptr(block), 1 if tick else 0)
+
+
+# struct ssdhip_adam_state / ssdhip_adam_group and ssdhip_sgd_state / ssdhip_sgd_group (include/ssdhip.h), for reading a state block
+# back on the host: one head, the groups behind it
+ADAM_STATE_HEAD = SGD_STATE_HEAD = np.dtype([("iterations", "<i8"), ("n_groups", "<i4"), ("reserved", "<i4")])
 ADAM_GROUP = np.dtype([(n, "<f8") for n in ("lr", "decay", "beta_1", "beta_2", "b1t", "b2t")] +
                       [(n, "<f4") for n in ("lr_t", "one_minus_beta_1", "one_minus_beta_2", "beta_1_f", "beta_2_f", "epsilon", "weight_decay")] +
                       [("reserved", "<i4")])
-
-
+SGD_GROUP = np.dtype([(n, "<f8") for n in ("lr", "decay", "momentum")] + [(n, "<f4") for n in ("lr_t", "momentum_f", "weight_decay")] +
+                     [("reserved", "<i4")])
+SGD_RULES = {"torch": 0, "keras": 1}                   # ssdhip_sgd_step's `rule`
 ADAM_MAX_GROUPS = 64                                   # SSDHIP_ADAM_MAX_GROUPS
 
 
-def adam_state_bytes(n_groups):
-    n = load().ssdhip_adam_state_bytes(int(n_groups))
+def _state_bytes(export, optimizer, n_groups):
+    n = getattr(load(), export)(int(n_groups))
     if n == 0:
-        raise SsdHipError("an Adam state block holds 1 .. 64 parameter groups (got %d)" % n_groups)
+        raise SsdHipError("an %s state block holds 1 .. 64 parameter groups (got %d)" % (optimizer, n_groups))
     return n
+
+
+def _state_read(block, group_dtype):
+    """(iterations, structured array of the groups) of a state block: a device-to-host copy, i.e. a synchronisation."""
+    raw = block.detach().cpu().numpy()
+    head = raw[:ADAM_STATE_HEAD.itemsize].view(ADAM_STATE_HEAD)[0]
+    groups = raw[ADAM_STATE_HEAD.itemsize:].view(group_dtype)[:int(head["n_groups"])]
+    return int(head["iterations"]), groups
+
+
+def adam_state_bytes(n_groups):
+    return _state_bytes("ssdhip_adam_state_bytes", "Adam", n_groups)
+
+
+def sgd_state_bytes(n_groups):
+    return _state_bytes("ssdhip_sgd_state_bytes", "SGD", n_groups)
+
+
+def adam_state_read(block):
+    return _state_read(block, ADAM_GROUP)
+
+
+def sgd_state_read(block):
+    return _state_read(block, SGD_GROUP)
 
 
 def adam_state_init(block, n_groups, group, lr, beta_1, beta_2, epsilon, decay, weight_decay, iterations=0):
@@ -735,110 +806,18 @@ def adam_state_init(block, n_groups, group, lr, beta_1, beta_2, epsilon, decay, 
            float(epsilon), float(decay), float(weight_decay), int(iterations))
 
 
-def adam_state_read(block):
-    """(iterations, structured array of the groups) of a state block: a device-to-host copy, i.e. a synchronisation."""
-    raw = block.detach().cpu().numpy()
-    head = raw[:ADAM_STATE_HEAD.itemsize].view(ADAM_STATE_HEAD)[0]
-    groups = raw[ADAM_STATE_HEAD.itemsize:].view(ADAM_GROUP)[:int(head["n_groups"])]
-    return int(head["iterations"]), groups
-
-
-def adam_table(params, grads, ms, vs, vhats, device):
-    """The HOST table of ssdhip_adam_step, as sgd_table: parameter, gradient, m, v and (amsgrad) vhat of every tensor."""
-    torch = _torch()
-    n = len(params)
-    cols = [params, grads, ms, vs] + ([vhats] if vhats is not None else [])
-    for ts in zip(*cols):
-        for t in ts:
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != ts[0].numel() or t.data_ptr() % 16 or t.device != device:
-                raise SsdHipError("adam_table: parameter, gradient and moment buffers must be dense float32 of one size on one device")
-    vp, ll = ctypes.c_void_p * n, ctypes.c_longlong * n
-    ptrs = [vp(*[t.data_ptr() for t in col]) for col in cols]
-    return (device, n) + tuple(ptrs) + ((None,) if vhats is None else ()) + (ll(*[p.numel() for p in params]),)
-
-
-def adam_step(table, block, group, tick):
-    device, n, pp, gp, mp, vp, hp, nn = table
-    launch("ssdhip_adam_step", device, n, pp, gp, mp, vp, hp, nn, int(group), _ptr(block), 1 if tick else 0)
-
-
-def _master_table(what, params, grads, float_cols, device):
-    """Checks and pointer arrays of the bf16 tables: `params` / `grads` dense bf16, every column of `float_cols` dense float32, one
-    size per row, 16-byte aligned, on `device`."""
-    torch = _torch()
-    n = len(params)
-    for row in zip(params, grads, *float_cols):
-        for k, t in enumerate(row):
-            want = torch.bfloat16 if k < 2 else torch.float32
-            if t.dtype != want or not t.is_contiguous() or t.numel() != row[0].numel() or t.data_ptr() % 16 or t.device != device:
-                raise SsdHipError("%s: parameter and gradient must be dense bf16, master and buffers dense float32, of one size on one "
-                                  "device" % what)
-    vp, ll = ctypes.c_void_p * n, ctypes.c_longlong * n
-    return vp, [vp(*[t.data_ptr() for t in col]) for col in [params, grads] + list(float_cols)], ll(*[p.numel() for p in params])
-
-
-def adam_table_bf16(params, grads, masters, ms, vs, vhats, device):
-    """The HOST table of ssdhip_adam_step_bf16: bf16 parameter and gradient, float32 master, m, v and (amsgrad) vhat of every tensor."""
-    _, ptrs, nn = _master_table("adam_table_bf16", params, grads, [masters, ms, vs] + ([vhats] if vhats is not None else []), device)
-    return (device, len(params)) + tuple(ptrs) + ((None,) if vhats is None else ()) + (nn,)
-
-
-def adam_step_bf16(table, block, group, tick):
-    device, n, pp, gp, wp, mp, vp, hp, nn = table
-    launch("ssdhip_adam_step_bf16", device, n, pp, gp, wp, mp, vp, hp, nn, int(group), _ptr(block), 1 if tick else 0)
-
-
-def optim_set_lr(block, group, lr):
-    launch("ssdhip_optim_set_lr", block.device, _ptr(block), int(group), float(lr))
-
-
-# struct ssdhip_sgd_state / ssdhip_sgd_group (include/ssdhip.h); the table of ssdhip_sgd_step is sgd_table's
-SGD_STATE_HEAD = ADAM_STATE_HEAD
-SGD_GROUP = np.dtype([(n, "<f8") for n in ("lr", "decay", "momentum")] + [(n, "<f4") for n in ("lr_t", "momentum_f", "weight_decay")] +
-                     [("reserved", "<i4")])
-SGD_RULES = {"torch": 0, "keras": 1}                   # ssdhip_sgd_step's `rule`
-
-
-def sgd_state_bytes(n_groups):
-    n = load().ssdhip_sgd_state_bytes(int(n_groups))
-    if n == 0:
-        raise SsdHipError("an SGD state block holds 1 .. 64 parameter groups (got %d)" % n_groups)
-    return n
-
-
 def sgd_state_init(block, n_groups, group, lr, momentum, decay, weight_decay, iterations=0):
     """One group's hyperparameters and the step count into a state block (a uint8 CUDA tensor of sgd_state_bytes(n_groups))."""
     launch("ssdhip_sgd_state_init", block.device, _ptr(block), int(n_groups), int(group), float(lr), float(momentum), float(decay),
            float(weight_decay), int(iterations))
 
 
-def sgd_state_read(block):
-    """(iterations, structured array of the groups) of a state block: a device-to-host copy, i.e. a synchronisation."""
-    raw = block.detach().cpu().numpy()
-    head = raw[:SGD_STATE_HEAD.itemsize].view(SGD_STATE_HEAD)[0]
-    groups = raw[SGD_STATE_HEAD.itemsize:].view(SGD_GROUP)[:int(head["n_groups"])]
-    return int(head["iterations"]), groups
+def optim_set_lr(block, group, lr):
+    launch("ssdhip_optim_set_lr", block.device, _ptr(block), int(group), float(lr))
 
 
 def sgd_set_lr(block, group, lr):
     launch("ssdhip_sgd_set_lr", block.device, _ptr(block), int(group), float(lr))
-
-
-def sgd_step(table, block, group, rule, nesterov, tick):
-    device, n, pp, gp, mp, nn = table
-    launch("ssdhip_sgd_step", device, n, pp, gp, mp, nn, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0)
-
-
-def sgd_table_bf16(params, grads, masters, bufs, device):
-    """The HOST table of ssdhip_sgd_step_bf16: bf16 parameter and gradient, float32 master and buffer of every tensor."""
-    _, ptrs, nn = _master_table("sgd_table_bf16", params, grads, [masters, bufs], device)
-    return (device, len(params)) + tuple(ptrs) + (nn,)
-
-
-def sgd_step_bf16(table, block, group, rule, nesterov, tick):
-    device, n, pp, gp, wp, mp, nn = table
-    launch("ssdhip_sgd_step_bf16", device, n, pp, gp, wp, mp, nn, int(group), _ptr(block), int(rule), 1 if nesterov else 0,
-           1 if tick else 0)
 
 
 # ---- the training loop's device side (csrc/ssdhip_fit.hip) -----------------------------------------------------------------------

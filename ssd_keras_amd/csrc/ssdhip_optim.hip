@@ -12,25 +12,28 @@
 //
 //   shadow_refresh_kernel   grid = tiles of 32 x 32 (Cout x Cin) filter taps over every weight tensor + a tail for the 1-D tensors
 //                           (biases, L2Normalization's gamma): float32 master -> bf16 through LDS, both layouts written as 64-byte runs.
-//   sgd_momentum_kernel     torch.optim.SGD's update (buf = momentum buf + g [+ wd p]; p -= lr buf; the first step's buf = g), every
-//                           parameter in one launch, float32.  `lr` is a kernel argument: a captured launch replays it.
+//   SgdRule<RULE, NESTEROV> one element of the SGD update.  RULE 0: torch.optim.SGD's buffer (buf = momentum buf + g [+ wd p]; p -= lr buf;
+//                           the first step's buf = g), RULE 1: Keras 2.x SGD.get_updates' velocity (v = momentum v - lr g; p += v), each
+//                           with and without Nesterov.  The three step kernels below are this rule in the ONE update body every
+//                           optimizer kernel shares (optim_step, ssdhip_optim_step.h: the tensor table in the kernel arguments, 4096
+//                           values per block, vector passes with a scalar tail); they differ in where the scalars come from and in the
+//                           parameter's type.  20 bytes per parameter in all three.
+//   sgd_momentum_kernel     SgdRule<0, false> over every float32 parameter in one launch.  `lr`, `momentum` and `weight_decay` are kernel
+//                           arguments: a captured launch replays them.
 //   sgd_tick_kernel / sgd_step_kernel<RULE, NESTEROV>
-//                           the same launch shape with its scalars in a state block on the DEVICE, as Adam's (ssdhip_adam.hip): a
-//                           one-workgroup tick advances `iterations` and rounds lr_t = lr0 / (1 + decay (iterations - 1)) once to float32,
-//                           the update reads lr_t, momentum and weight_decay from the block -- a captured step follows ssdhip_sgd_set_lr
-//                           between replays (ssd300_training.ipynb's LearningRateScheduler).  RULE 0: torch's buffer, RULE 1: Keras 2.x
-//                           SGD.get_updates' velocity (v = momentum v - lr g; p += v), each with and without Nesterov.  20 bytes per
-//                           parameter, as sgd_momentum_kernel.
+//                           the scalars in a state block on the DEVICE, as Adam's (ssdhip_adam.hip): a one-workgroup tick advances
+//                           `iterations` and rounds lr_t = lr0 / (1 + decay (iterations - 1)) once to float32, the update reads lr_t,
+//                           momentum and weight_decay from the block -- a captured step follows ssdhip_sgd_set_lr between replays
+//                           (ssd300_training.ipynb's LearningRateScheduler).
 //   sgd_step_bf16_kernel<RULE, NESTEROV>
-//                           the same update (sgd_update) on a float32 MASTER copy of a bf16 parameter: bf16 gradient in (exact in
-//                           float32), weight decay on the master, p = bf16(master) out, round to nearest even, never read.  Eight values
-//                           per thread and pass; 20 bytes per parameter as well (2 + 8 + 8 + 2).
+//                           the same on a float32 MASTER copy of a bf16 parameter (optim_step's BF16 form: 2 + 8 + 8 + 2 bytes).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ssdhip.h"
 #include "ssdhip_math.h"
 #include "ssdhip_bf16.h"
+#include "ssdhip_optim_step.h"
 
 namespace ssdhip {
 
@@ -155,58 +158,42 @@ __global__ __launch_bounds__(256) void shadow_refresh_kernel(const ssdhip_shadow
     }
 }
 
-// torch.optim.SGD (momentum, dampening 0, no Nesterov): four values per thread and step, up to SGD_CHUNK tensors per launch.  The
-// tensor table travels in the KERNEL ARGUMENTS: gradients are new tensors every step (zero_grad(set_to_none=True)), and a device-side
-// table would have to be re-uploaded -- a pageable host-to-device copy that blocks the host until the whole backward pass has drained
-// (measured: the step 0.3-0.5 ms SLOWER than with the framework's optimizer although the kernels took 250 us less).
-constexpr int SGD_CHUNK = 80;
-struct SgdArgs {
-    float* p[SGD_CHUNK];
-    const float* g[SGD_CHUNK];
-    float* m[SGD_CHUNK];
-    long long n[SGD_CHUNK];
-    int block0[SGD_CHUNK];                                 // first block of each tensor (4096 values per block)
-    int count;
-};
-
-__global__ __launch_bounds__(256) void sgd_momentum_kernel(const SgdArgs a, float lr, float momentum, float weight_decay) {
-    const int tid = threadIdx.x, blk = (int)blockIdx.x;
-    int lo = 0, hi = a.count - 1;                          // last tensor with block0 <= blk (uniform: scalar loads of the arguments)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.block0[mid] <= blk) lo = mid; else hi = mid - 1;
-    }
-    float* p = a.p[lo];
-    const float* g = a.g[lo];
-    float* m = a.m[lo];
-    const long long n = a.n[lo];
-    const long long base = (long long)(blk - a.block0[lo]) * 4096;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const long long i = base + (long long)u * 1024 + tid * 4;
-        if (i + 3 < n) {
-            const float4 pv = *reinterpret_cast<const float4*>(p + i), gv = *reinterpret_cast<const float4*>(g + i);
-            const float4 mv = *reinterpret_cast<const float4*>(m + i);
-            float gg[4] = {gv.x, gv.y, gv.z, gv.w}, pp[4] = {pv.x, pv.y, pv.z, pv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float gq = gg[q];
-                if (weight_decay != 0.f) gq = gq + weight_decay * pp[q];
-                mm[q] = momentum * mm[q] + gq;
-                pp[q] = pp[q] - lr * mm[q];
+// One element of the update; `m` is the momentum buffer (RULE 0) or the velocity (RULE 1).  One IEEE float32 operation per line part,
+// in the order of include/ssdhip.h; RULE 0 without Nesterov is torch.optim.SGD's (momentum, dampening 0), sgd_momentum_kernel's.
+template <int RULE, bool NESTEROV>
+struct SgdRule {
+    static constexpr int NBUF = 1;
+    struct Scalars { float lr, momentum, weight_decay; };
+    static __device__ __forceinline__ void update(float& p, float g, float* m, const Scalars& c) {
+        if (c.weight_decay != 0.f) g = g + c.weight_decay * p;
+        if (RULE == 0) {
+            m[0] = c.momentum * m[0] + g;
+            if (NESTEROV) {
+                const float d = g + c.momentum * m[0];
+                p = p - c.lr * d;
+            } else {
+                p = p - c.lr * m[0];
             }
-            *reinterpret_cast<float4*>(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-            *reinterpret_cast<float4*>(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
         } else {
-            for (long long j = i; j < n && j < i + 4; ++j) {
-                float gq = g[j];
-                if (weight_decay != 0.f) gq = gq + weight_decay * p[j];
-                const float mq = momentum * m[j] + gq;
-                m[j] = mq;
-                p[j] = p[j] - lr * mq;
-            }
+            const float lg = c.lr * g;
+            m[0] = c.momentum * m[0] - lg;
+            if (NESTEROV)
+                p = (p + c.momentum * m[0]) - lg;
+            else
+                p = p + m[0];
         }
     }
+};
+
+// 80 tensors per launch: three pointers (four with a master) + count + first block = 36 (44) bytes per tensor, 3524 bytes at most.
+constexpr int SGD_CHUNK = 80;
+typedef OptimTable<3, SGD_CHUNK> SgdArgs;                  // p, g, buffer
+typedef OptimTable<4, SGD_CHUNK> SgdBf16Args;              // p (written only), g, master, buffer
+static_assert(sizeof(SgdBf16Args) + sizeof(void*) + 2 * sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
+static_assert(sizeof(SgdArgs) + 3 * sizeof(float) <= 4096, "the tensor table must fit the kernel arguments");
+
+__global__ __launch_bounds__(256) void sgd_momentum_kernel(const SgdArgs a, float lr, float momentum, float weight_decay) {
+    optim_step<SgdRule<0, false>, false>(a, {lr, momentum, weight_decay});
 }
 
 __global__ __launch_bounds__(64) void sgd_init_kernel(ssdhip_sgd_state* st, int n_groups, int group, double lr, double momentum,
@@ -225,10 +212,6 @@ __global__ __launch_bounds__(64) void sgd_init_kernel(ssdhip_sgd_state* st, int 
     s.reserved = 0;
 }
 
-__global__ __launch_bounds__(64) void sgd_set_lr_kernel(ssdhip_sgd_state* st, int group, double lr) {
-    if (threadIdx.x == 0 && blockIdx.x == 0 && group < st->n_groups) st->groups[group].lr = lr;
-}
-
 // One workgroup, one thread per parameter group.
 __global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void sgd_tick_kernel(ssdhip_sgd_state* st) {
     const int g = threadIdx.x;
@@ -243,133 +226,19 @@ __global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void sgd_tick_kernel(ssdhip
     s.lr_t = (float)lr;
 }
 
-// One element of the update; `m` is the momentum buffer (RULE 0) or the velocity (RULE 1).  One IEEE float32 operation per line part,
-// in the order of include/ssdhip.h; RULE 0 without Nesterov is sgd_momentum_kernel's sequence.
-template <int RULE, bool NESTEROV>
-__device__ __forceinline__ void sgd_update(float& p, float g, float& m, float lr, float momentum, float weight_decay) {
-    if (weight_decay != 0.f) g = g + weight_decay * p;
-    if (RULE == 0) {
-        m = momentum * m + g;
-        if (NESTEROV) {
-            const float d = g + momentum * m;
-            p = p - lr * d;
-        } else {
-            p = p - lr * m;
-        }
-    } else {
-        const float lg = lr * g;
-        m = momentum * m - lg;
-        if (NESTEROV)
-            p = (p + momentum * m) - lg;
-        else
-            p = p + m;
-    }
-}
-
+// The state-block forms: the group's scalars are the values the tick has just written (uniform: scalar loads).
 template <int RULE, bool NESTEROV>
 __global__ __launch_bounds__(256) void sgd_step_kernel(const SgdArgs a, const ssdhip_sgd_state* __restrict__ st, int group) {
-    const int tid = threadIdx.x, blk = (int)blockIdx.x;
     if (group >= st->n_groups) return;
-    const ssdhip_sgd_group& s = st->groups[group];         // uniform: scalar loads, the values the tick has just written
-    const float lr = s.lr_t, momentum = s.momentum_f, weight_decay = s.weight_decay;
-    int lo = 0, hi = a.count - 1;                          // last tensor with block0 <= blk
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.block0[mid] <= blk) lo = mid; else hi = mid - 1;
-    }
-    float* p = a.p[lo];
-    const float* g = a.g[lo];
-    float* m = a.m[lo];
-    const long long n = a.n[lo];
-    const long long base = (long long)(blk - a.block0[lo]) * 4096;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const long long i = base + (long long)u * 1024 + tid * 4;
-        if (i + 3 < n) {
-            const float4 pv = *reinterpret_cast<const float4*>(p + i), gv = *reinterpret_cast<const float4*>(g + i);
-            const float4 mv = *reinterpret_cast<const float4*>(m + i);
-            float gg[4] = {gv.x, gv.y, gv.z, gv.w}, pp[4] = {pv.x, pv.y, pv.z, pv.w}, mm[4] = {mv.x, mv.y, mv.z, mv.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sgd_update<RULE, NESTEROV>(pp[q], gg[q], mm[q], lr, momentum, weight_decay);
-            *reinterpret_cast<float4*>(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-            *reinterpret_cast<float4*>(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        } else {
-            for (long long j = i; j < n && j < i + 4; ++j) {
-                float pq = p[j], mq = m[j];
-                sgd_update<RULE, NESTEROV>(pq, g[j], mq, lr, momentum, weight_decay);
-                m[j] = mq;
-                p[j] = pq;
-            }
-        }
-    }
+    const ssdhip_sgd_group& s = st->groups[group];
+    optim_step<SgdRule<RULE, NESTEROV>, false>(a, {s.lr_t, s.momentum_f, s.weight_decay});
 }
-static_assert(sizeof(SgdArgs) + sizeof(void*) + 2 * sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
-
-// Four pointers + count + first block = 44 bytes per tensor: 80 tensors are 3524 bytes.
-constexpr int SGD_BF16_CHUNK = 80;
-struct SgdBf16Args {
-    bf16_t* p[SGD_BF16_CHUNK];                             // written only
-    const bf16_t* g[SGD_BF16_CHUNK];
-    float* w[SGD_BF16_CHUNK];                              // the float32 master
-    float* m[SGD_BF16_CHUNK];
-    long long n[SGD_BF16_CHUNK];
-    int block0[SGD_BF16_CHUNK];
-    int count;
-};
-static_assert(sizeof(SgdBf16Args) + sizeof(void*) + 2 * sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
 
 template <int RULE, bool NESTEROV>
 __global__ __launch_bounds__(256) void sgd_step_bf16_kernel(const SgdBf16Args a, const ssdhip_sgd_state* __restrict__ st, int group) {
-    const int tid = threadIdx.x, blk = (int)blockIdx.x;
     if (group >= st->n_groups) return;
-    const ssdhip_sgd_group& s = st->groups[group];         // uniform: scalar loads, the values the tick has just written
-    const float lr = s.lr_t, momentum = s.momentum_f, weight_decay = s.weight_decay;
-    int lo = 0, hi = a.count - 1;                          // last tensor with block0 <= blk
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.block0[mid] <= blk) lo = mid; else hi = mid - 1;
-    }
-    bf16_t* p = a.p[lo];
-    const bf16_t* g = a.g[lo];
-    float* w = a.w[lo];
-    float* m = a.m[lo];
-    const long long n = a.n[lo];
-    const long long base = (long long)(blk - a.block0[lo]) * 4096;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const long long i = base + (long long)u * 2048 + tid * 8;
-        if (i + 7 < n) {
-            const uint4 gv = *reinterpret_cast<const uint4*>(g + i);
-            const u32 gw[4] = {gv.x, gv.y, gv.z, gv.w};
-            float ww[8], mm[8];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float4 wv = *reinterpret_cast<const float4*>(w + i + 4 * h), mv = *reinterpret_cast<const float4*>(m + i + 4 * h);
-                ww[4 * h] = wv.x, ww[4 * h + 1] = wv.y, ww[4 * h + 2] = wv.z, ww[4 * h + 3] = wv.w;
-                mm[4 * h] = mv.x, mm[4 * h + 1] = mv.y, mm[4 * h + 2] = mv.z, mm[4 * h + 3] = mv.w;
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float gq = (q & 1) ? __uint_as_float(gw[q >> 1] & 0xffff0000u) : bf16_float(gw[q >> 1] & 0xffffu);
-                sgd_update<RULE, NESTEROV>(ww[q], gq, mm[q], lr, momentum, weight_decay);
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                *reinterpret_cast<float4*>(w + i + 4 * h) = make_float4(ww[4 * h], ww[4 * h + 1], ww[4 * h + 2], ww[4 * h + 3]);
-                *reinterpret_cast<float4*>(m + i + 4 * h) = make_float4(mm[4 * h], mm[4 * h + 1], mm[4 * h + 2], mm[4 * h + 3]);
-            }
-            *reinterpret_cast<uint4*>(p + i) = make_uint4(pack2_bf16(ww[0], ww[1]), pack2_bf16(ww[2], ww[3]), pack2_bf16(ww[4], ww[5]),
-                                                          pack2_bf16(ww[6], ww[7]));
-        } else {
-            for (long long j = i; j < n && j < i + 8; ++j) {
-                float wq = w[j], mq = m[j];
-                sgd_update<RULE, NESTEROV>(wq, bf16_float(g[j]), mq, lr, momentum, weight_decay);
-                m[j] = mq;
-                w[j] = wq;
-                p[j] = bf16_bits<bf16_t>(wq);
-            }
-        }
-    }
+    const ssdhip_sgd_group& s = st->groups[group];
+    optim_step<SgdRule<RULE, NESTEROV>, true>(a, {s.lr_t, s.momentum_f, s.weight_decay});
 }
 
 }  // namespace ssdhip
@@ -390,31 +259,8 @@ extern "C" int ssdhip_shadow_refresh(const ssdhip_shadow_desc* table_dev, int n_
 
 extern "C" int ssdhip_sgd_momentum_step(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* bufs_h,
                                         const long long* numel_h, double lr, double momentum, double weight_decay, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n_tensors <= 0 || !params_h || !grads_h || !bufs_h || !numel_h) return SSDHIP_E_BADARG;
-    for (int k = 0; k < n_tensors; ++k) {
-        if (!params_h[k] || !grads_h[k] || !bufs_h[k] || numel_h[k] <= 0) return SSDHIP_E_BADARG;
-        if (((uintptr_t)params_h[k] | (uintptr_t)grads_h[k] | (uintptr_t)bufs_h[k]) & 15) return SSDHIP_E_BADARG;
-        if ((numel_h[k] + 4095) / 4096 > 0x3fffffffLL) return SSDHIP_E_BADARG;
-    }
-    for (int k0 = 0; k0 < n_tensors; k0 += SGD_CHUNK) {
-        SgdArgs a;
-        a.count = n_tensors - k0 < SGD_CHUNK ? n_tensors - k0 : SGD_CHUNK;
-        long long blocks = 0;
-        for (int k = 0; k < SGD_CHUNK; ++k) {
-            const int src = k < a.count ? k0 + k : k0;     // (unused slots repeat the first tensor: never selected)
-            a.p[k] = static_cast<float*>(params_h[src]);
-            a.g[k] = static_cast<const float*>(grads_h[src]);
-            a.m[k] = static_cast<float*>(bufs_h[src]);
-            a.n[k] = numel_h[src];
-            a.block0[k] = (int)blocks;
-            if (k < a.count) blocks += (numel_h[src] + 4095) / 4096;
-            if (blocks > 0x7fffffffLL) return SSDHIP_E_BADARG;
-        }
-        hipLaunchKernelGGL(sgd_momentum_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, (float)lr, (float)momentum, (float)weight_decay);
-        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
-    }
-    return SSDHIP_OK;
+    return optim_launch<SGD_CHUNK>(static_cast<hipStream_t>(stream_), n_tensors, {params_h, grads_h, bufs_h}, numel_h, [] { return true; },
+                                   sgd_momentum_kernel, (float)lr, (float)momentum, (float)weight_decay);
 }
 
 extern "C" size_t ssdhip_sgd_state_bytes(int n_groups) {
@@ -434,101 +280,22 @@ extern "C" int ssdhip_sgd_state_init(void* state, int n_groups, int group, doubl
 }
 
 extern "C" int ssdhip_sgd_set_lr(void* state, int group, double lr, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!state || ((uintptr_t)state & 15) || group < 0 || group >= SSDHIP_ADAM_MAX_GROUPS || !(lr >= 0.0)) return SSDHIP_E_BADARG;
-    hipLaunchKernelGGL(sgd_set_lr_kernel, dim3(1), dim3(64), 0, stream, static_cast<ssdhip_sgd_state*>(state), group, lr);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    return optim_set_lr<ssdhip_sgd_state>(state, group, lr, stream_);
 }
+
+#define SGD_PICK(K, rule, nesterov) ((rule) ? ((nesterov) ? K<1, true> : K<1, false>) : ((nesterov) ? K<0, true> : K<0, false>))
 
 extern "C" int ssdhip_sgd_step(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* bufs_h,
                                const long long* numel_h, int group, void* state, int rule, int nesterov, int tick, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n_tensors <= 0 || !params_h || !grads_h || !bufs_h || !numel_h || !state || ((uintptr_t)state & 15) || group < 0
-        || group >= SSDHIP_ADAM_MAX_GROUPS || rule < 0 || rule > 1)
-        return SSDHIP_E_BADARG;
-    for (int k = 0; k < n_tensors; ++k) {
-        if (!params_h[k] || !grads_h[k] || !bufs_h[k] || numel_h[k] <= 0) return SSDHIP_E_BADARG;
-        if (((uintptr_t)params_h[k] | (uintptr_t)grads_h[k] | (uintptr_t)bufs_h[k]) & 15) return SSDHIP_E_BADARG;
-        if ((numel_h[k] + 4095) / 4096 > 0x3fffffffLL) return SSDHIP_E_BADARG;
-    }
-    ssdhip_sgd_state* st = static_cast<ssdhip_sgd_state*>(state);
-    if (tick) {
-        hipLaunchKernelGGL(sgd_tick_kernel, dim3(1), dim3(SSDHIP_ADAM_MAX_GROUPS), 0, stream, st);
-        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
-    }
-    for (int k0 = 0; k0 < n_tensors; k0 += SGD_CHUNK) {
-        SgdArgs a;
-        a.count = n_tensors - k0 < SGD_CHUNK ? n_tensors - k0 : SGD_CHUNK;
-        long long blocks = 0;
-        for (int k = 0; k < SGD_CHUNK; ++k) {
-            const int src = k < a.count ? k0 + k : k0;     // (unused slots repeat the first tensor: never selected)
-            a.p[k] = static_cast<float*>(params_h[src]);
-            a.g[k] = static_cast<const float*>(grads_h[src]);
-            a.m[k] = static_cast<float*>(bufs_h[src]);
-            a.n[k] = numel_h[src];
-            a.block0[k] = (int)blocks;
-            if (k < a.count) blocks += (numel_h[src] + 4095) / 4096;
-            if (blocks > 0x7fffffffLL) return SSDHIP_E_BADARG;
-        }
-        const dim3 grid((unsigned)blocks), wg(256);
-        if (rule == 0 && !nesterov)
-            hipLaunchKernelGGL((sgd_step_kernel<0, false>), grid, wg, 0, stream, a, st, group);
-        else if (rule == 0)
-            hipLaunchKernelGGL((sgd_step_kernel<0, true>), grid, wg, 0, stream, a, st, group);
-        else if (!nesterov)
-            hipLaunchKernelGGL((sgd_step_kernel<1, false>), grid, wg, 0, stream, a, st, group);
-        else
-            hipLaunchKernelGGL((sgd_step_kernel<1, true>), grid, wg, 0, stream, a, st, group);
-        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
-    }
-    return SSDHIP_OK;
+    if (rule < 0 || rule > 1) return SSDHIP_E_BADARG;
+    return optim_state_step<SGD_CHUNK>(n_tensors, {params_h, grads_h, bufs_h}, numel_h, group, state, tick, stream_, sgd_tick_kernel,
+                                       SGD_PICK(sgd_step_kernel, rule, nesterov));
 }
 
 extern "C" int ssdhip_sgd_step_bf16(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h,
                                     void* const* bufs_h, const long long* numel_h, int group, void* state, int rule, int nesterov,
                                     int tick, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (n_tensors <= 0 || !params_h || !grads_h || !master_h || !bufs_h || !numel_h || !state || ((uintptr_t)state & 15) || group < 0
-        || group >= SSDHIP_ADAM_MAX_GROUPS || rule < 0 || rule > 1)
-        return SSDHIP_E_BADARG;
-    long long chunk_blocks = 0;
-    for (int k = 0; k < n_tensors; ++k) {
-        if (!params_h[k] || !grads_h[k] || !master_h[k] || !bufs_h[k] || numel_h[k] <= 0) return SSDHIP_E_BADARG;
-        if (((uintptr_t)params_h[k] | (uintptr_t)grads_h[k] | (uintptr_t)master_h[k] | (uintptr_t)bufs_h[k]) & 15) return SSDHIP_E_BADARG;
-        if ((numel_h[k] + 4095) / 4096 > 0x3fffffffLL) return SSDHIP_E_BADARG;
-        if (k % SGD_BF16_CHUNK == 0) chunk_blocks = 0;      // (a launch's grid, before the tick: nothing runs on a refused call)
-        chunk_blocks += (numel_h[k] + 4095) / 4096;
-        if (chunk_blocks > 0x7fffffffLL) return SSDHIP_E_BADARG;
-    }
-    ssdhip_sgd_state* st = static_cast<ssdhip_sgd_state*>(state);
-    if (tick) {
-        hipLaunchKernelGGL(sgd_tick_kernel, dim3(1), dim3(SSDHIP_ADAM_MAX_GROUPS), 0, stream, st);
-        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
-    }
-    for (int k0 = 0; k0 < n_tensors; k0 += SGD_BF16_CHUNK) {
-        SgdBf16Args a;
-        a.count = n_tensors - k0 < SGD_BF16_CHUNK ? n_tensors - k0 : SGD_BF16_CHUNK;
-        long long blocks = 0;
-        for (int k = 0; k < SGD_BF16_CHUNK; ++k) {
-            const int src = k < a.count ? k0 + k : k0;     // (unused slots repeat the first tensor: never selected)
-            a.p[k] = static_cast<bf16_t*>(params_h[src]);
-            a.g[k] = static_cast<const bf16_t*>(grads_h[src]);
-            a.w[k] = static_cast<float*>(master_h[src]);
-            a.m[k] = static_cast<float*>(bufs_h[src]);
-            a.n[k] = numel_h[src];
-            a.block0[k] = (int)blocks;
-            if (k < a.count) blocks += (numel_h[src] + 4095) / 4096;
-        }
-        const dim3 grid((unsigned)blocks), wg(256);
-        if (rule == 0 && !nesterov)
-            hipLaunchKernelGGL((sgd_step_bf16_kernel<0, false>), grid, wg, 0, stream, a, st, group);
-        else if (rule == 0)
-            hipLaunchKernelGGL((sgd_step_bf16_kernel<0, true>), grid, wg, 0, stream, a, st, group);
-        else if (!nesterov)
-            hipLaunchKernelGGL((sgd_step_bf16_kernel<1, false>), grid, wg, 0, stream, a, st, group);
-        else
-            hipLaunchKernelGGL((sgd_step_bf16_kernel<1, true>), grid, wg, 0, stream, a, st, group);
-        if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
-    }
-    return SSDHIP_OK;
+    if (rule < 0 || rule > 1) return SSDHIP_E_BADARG;
+    return optim_state_step<SGD_CHUNK>(n_tensors, {params_h, grads_h, master_h, bufs_h}, numel_h, group, state, tick, stream_,
+                                       sgd_tick_kernel, SGD_PICK(sgd_step_bf16_kernel, rule, nesterov));
 }

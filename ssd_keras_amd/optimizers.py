@@ -27,7 +27,8 @@ half an ulp of the weight -- 2^-9 of its magnitude -- rounds to nothing, step af
 
 In both, float32 parameters on a GPU with gradients of their own memory layout take the fused launch, and so do bf16 parameters with
 bf16 gradients under `master_weights` (a launch of their own: ssdhip_adam_step_bf16 / ssdhip_sgd_step_bf16); anything else (CPU
-tensors, other dtypes, bf16 without masters, SGD with momentum 0) the plain tensor expressions of the same rule."""
+tensors, other dtypes, bf16 without masters, SGD with momentum 0) the plain tensor expressions of the same rule.  All four launches
+are ONE update body and one host launcher (csrc/ssdhip_optim_step.h) with the optimizer's rule in it, planned in one place here."""
 from __future__ import annotations
 
 import math
@@ -83,8 +84,9 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
     loaded after `init_state()` are found.  No remembered version (a master that came with a restored or unpickled optimizer) means
     the master is trusted.
 
-    A subclass names its state (`_buffers`, `_BLOCK`, `_HOST`) and supplies `_check`, `_hyper` (lr first), `_tag`, `_plan`, the
-    block's three native calls, `_launch` and `_expressions`."""
+    A subclass names its state (`_buffers`, `_BLOCK`, `_HOST`), says which buffers a group's parameters have (`_group_buffers`) and
+    whether it can take the fused launch (`_fusable`), and supplies `_check`, `_hyper` (lr first), `_tag`, the block's three native
+    calls, `_table`, `_launch` and `_expressions`."""
 
     _buffers = ()                                            # names of the per-parameter state tensors the kernel touches
     _BLOCK = None                                            # self.state[_BLOCK + device]: the device's state block, a uint8 tensor
@@ -212,6 +214,25 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
             hit = (self._key(group), tag) + plan
             tabs[gi] = hit
         return hit[2], hit[3]
+
+    def _plan(self, gi, group):
+        """Per (device, bf16 with a master) one native table over the group's parameters that take the fused launch -- columns:
+        parameter, gradient, the master if there is one, `_group_buffers(group)` -- and the rest for the tensor expressions; creates
+        the masters and the state buffers that are missing (zeros: torch's first buf = grad, Keras's v = 0, Adam's moments)."""
+        fused, rest = self._split(group, fusable=self._fusable(group))
+        names = self._group_buffers(group)
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+        def state(p, master, capturing):                     # (the master first: the buffers are made in its dtype)
+            return ([self._master(p, self.state[p], capturing)] if master else []) + [self._zeros(p, self.state[p], n, capturing) for n in names]
+
+        tables = []
+        for (dev, bf16), ps in fused.items():
+            rows = [[p, p.grad] + state(p, bf16, capturing) for p in ps]
+            tables.append((self._table([[_flat(t) for t in col] for col in zip(*rows)], dev, bf16), tuple(ps), self._BLOCK + str(dev), dev, bf16))
+        for p in rest:
+            state(p, self._mastered(group, p), capturing and p.is_cuda)
+        return tables, rest
 
     def _zeros(self, p, st, name, capturing):
         """The state buffer `name` of `p`, zeros in the parameter's layout (float32 beside a master) when it does not exist yet."""
@@ -437,24 +458,14 @@ class SGD(_OneLaunchOptimizer):
             lr_t.append(lr)
         return lr_t
 
-    def _plan(self, gi, group):
-        fused, rest = self._split(group, fusable=group["momentum"] != 0.0)
-        name = self._BUFFER[group["rule"]]
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-        tables = []
-        for (dev, bf16), ps in fused.items():
-            flat = [[_flat(p) for p in ps], [_flat(p.grad) for p in ps]]
-            if bf16:
-                flat.append([_flat(self._master(p, self.state[p], capturing)) for p in ps])
-            flat.append([_flat(self._zeros(p, self.state[p], name, capturing)) for p in ps])   # zeros: torch's first buf = grad, Keras's v = 0
-            table = (nat.sgd_table_bf16 if bf16 else nat.sgd_table)(*flat, dev)
-            tables.append((table, tuple(ps), self._BLOCK + str(dev), dev, bf16))
-        for p in rest:
-            if self._mastered(group, p):
-                self._master(p, self.state[p], capturing and p.is_cuda)
-            if group["momentum"] != 0.0:
-                self._zeros(p, self.state[p], name, capturing and p.is_cuda)
-        return tables, rest
+    def _group_buffers(self, group):                         # (momentum 0 keeps no state: both rules are p - lr g)
+        return (self._BUFFER[group["rule"]],) if group["momentum"] != 0.0 else ()
+
+    _fusable = staticmethod(lambda group: group["momentum"] != 0.0)
+
+    @staticmethod
+    def _table(cols, dev, bf16):
+        return (nat.sgd_table_bf16 if bf16 else nat.sgd_table)(*cols, dev)
 
     @staticmethod
     def _launch(table, blk, gi, group, tick, bf16):
@@ -557,28 +568,16 @@ class Adam(_OneLaunchOptimizer):
             lr_t.append(lr * math.sqrt(1.0 - b2t) / (1.0 - b1t))
         return lr_t
 
-    def _moments(self, p, amsgrad, capturing, master=False):
-        st = self.state[p]
-        if master:
-            self._master(p, st, capturing)
-        for n in ("m", "v", "vhat") if amsgrad else ("m", "v"):
-            self._zeros(p, st, n, capturing)
-        return st
+    @staticmethod
+    def _group_buffers(group):
+        return ("m", "v", "vhat") if group["amsgrad"] else ("m", "v")
 
-    def _plan(self, gi, group):
-        fused, rest = self._split(group, fusable=self._fused)
-        ams = group["amsgrad"]
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-        tables = []
-        for (dev, bf16), ps in fused.items():
-            sts = [self._moments(p, ams, capturing, bf16) for p in ps]
-            flat = [[_flat(p) for p in ps], [_flat(p.grad) for p in ps]] + ([[_flat(st["master"]) for st in sts]] if bf16 else [])
-            flat += [[_flat(st["m"]) for st in sts], [_flat(st["v"]) for st in sts], [_flat(st["vhat"]) for st in sts] if ams else None]
-            table = (nat.adam_table_bf16 if bf16 else nat.adam_table)(*flat, dev)
-            tables.append((table, tuple(ps), self._BLOCK + str(dev), dev, bf16))
-        for p in rest:
-            self._moments(p, ams, capturing and p.is_cuda, self._mastered(group, p))
-        return tables, rest
+    def _fusable(self, group):
+        return self._fused
+
+    @staticmethod
+    def _table(cols, dev, bf16):                             # (no amsgrad: no vhat column)
+        return (nat.adam_table_bf16 if bf16 else nat.adam_table)(*cols, *[None] * ((6 if bf16 else 5) - len(cols)), dev)
 
     @staticmethod
     def _launch(table, blk, gi, group, tick, bf16):

@@ -301,6 +301,61 @@ def test_entry_points_reject_bad_arguments_before_launching(lib):
     assert loss(a, a, 2, 10, 1, 3, 0, 1.0, a, a, a, a, 1 << 20, None) == -1                 # C < 2
 
 
+def test_optimizer_steps_refuse_bad_arguments_before_anything_runs(lib):
+    """The five optimizer step exports share one host launcher (csrc/ssdhip_optim_step.h) that makes EVERY check before the first
+    launch: a refused call returns SSDHIP_E_BADARG (-1) and neither the tick nor an earlier chunk has run.  The addresses are made
+    up (16-byte aligned, never dereferenced), so this runs only where no launch can succeed: there an accepted call -- and a check
+    that is missing, or that comes after the tick -- ends as SSDHIP_E_LAUNCH (-3).  Three tensors of 0x3fffffff * 4096 values are
+    each within the per-tensor limit and together over the grid's."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("made-up device addresses: only where no launch can succeed")
+    N, BIG = 3, 0x3fffffff * 4096
+    VP, LL = ctypes.c_void_p * N, ctypes.c_longlong * N
+    STATE = 1 << 24
+    # name: (columns, takes group / state / tick, takes a rule, the last column is the optional vhat)
+    exports = {"ssdhip_sgd_momentum_step": (3, False, False, False), "ssdhip_sgd_step": (3, True, True, False),
+               "ssdhip_sgd_step_bf16": (4, True, True, False), "ssdhip_adam_step": (5, True, False, True),
+               "ssdhip_adam_step_bf16": (6, True, False, True)}
+
+    def columns(ncol):
+        return [[(1 << 20) + 4096 * (c * N + k) for k in range(N)] for c in range(ncol)]
+
+    for name, (ncol, has_state, has_rule, has_vhat) in exports.items():
+        for tick in ((0, 1) if has_state else (0,)):
+            for vhat in ((True, False) if has_vhat else (True,)):
+
+                def call(n=N, cols=None, numel=(8,) * N, group=0, state=STATE, rule=0):
+                    cols = columns(ncol) if cols is None else cols
+                    if not vhat:
+                        cols = cols[:-1] + [None]
+                    tail = (group, state) + ((rule, 0) if has_rule else ()) + (tick,) if has_state else (0.1, 0.9, 0.0)
+                    return getattr(lib, name)(n, *[c if c is None else VP(*c) for c in cols],
+                                              None if numel is None else LL(*numel), *tail, None)
+
+                what = (name, tick, vhat)
+                assert call() == -3, what                                        # valid but for the device: it got as far as a launch
+                assert call(numel=(BIG,) * N) == -1, what                         # one launch's grid
+                assert call(numel=(BIG + 1, 8, 8)) == -1, what                    # one tensor's blocks
+                assert call(n=0) == -1 and call(n=-1) == -1 and call(numel=None) == -1, what
+                assert call(numel=(8, 0, 8)) == -1 and call(numel=(8, 8, -4)) == -1, what
+                for c in range(ncol - (0 if vhat else 1)):
+                    for k in range(N):
+                        for bad in (4, None):                                     # an address 4 past alignment, a null row
+                            cols = columns(ncol)
+                            cols[c][k] = None if bad is None else cols[c][k] + bad
+                            assert call(cols=cols) == -1, what + (c, k, bad)
+                    if not (has_vhat and c == ncol - 1):                          # (a null vhat column is a call without amsgrad)
+                        cols = columns(ncol)
+                        cols[c] = None
+                        assert call(cols=cols) == -1, what + (c,)
+                if has_state:
+                    assert call(group=64) == -1 and call(group=-1) == -1, what
+                    assert call(state=None) == -1 and call(state=STATE + 4) == -1, what
+                if has_rule:
+                    assert call(rule=2) == -1 and call(rule=-1) == -1, what
+
+
 def test_autotune_keeps_the_fastest_candidate_and_probes_slow_ones_once(monkeypatch):
     """SSDModel._pick (models/_common.py): best of two bursts per candidate.  MIOpen competes only under SSDHIP_CONV=auto_miopen
     (it goes last and is dropped after one probe call when that alone is slower than three calls of the best so far); by default

@@ -307,7 +307,8 @@ def test_a_capture_after_init_state_and_a_late_write_is_refused():
 
 
 def test_c_abi_refuses_bad_arguments_and_touches_nothing():
-    """Direct calls of the two exports: a null pointer, a misaligned master, numel = 0 and group = 64 return SSDHIP_E_BADARG (-1), and
+    """Direct calls of the two bf16 exports and, on float32 tensors, of ssdhip_adam_step, ssdhip_sgd_step and ssdhip_sgd_momentum_step
+    (one host launcher behind all five): a null pointer, a misaligned master, numel = 0 and group = 64 return SSDHIP_E_BADARG (-1), and
     the buffers -- filled with a sentinel -- and the state block are what they were: nothing was launched, not even the tick."""
     import torch
     from ssd_keras_amd import _native as nat
@@ -315,6 +316,7 @@ def test_c_abi_refuses_bad_arguments_and_touches_nothing():
     n = 40
     p, g = torch.full((n,), 3.0, device="cuda", dtype=torch.bfloat16), torch.full((n,), 3.0, device="cuda", dtype=torch.bfloat16)
     floats = [torch.full((n + 4,), 3.0, device="cuda") for _ in range(4)]                  # master, m, v, vhat
+    fp, fg = torch.full((n + 4,), 3.0, device="cuda"), torch.full((n + 4,), 3.0, device="cuda")   # a float32 parameter and its gradient
     adam_blk = torch.zeros((nat.adam_state_bytes(1),), dtype=torch.uint8, device="cuda")
     nat.adam_state_init(adam_blk, 1, 0, 1e-2, 0.9, 0.999, 1e-8, 0.0, 0.0)
     sgd_blk = torch.zeros((nat.sgd_state_bytes(1),), dtype=torch.uint8, device="cuda")
@@ -348,9 +350,39 @@ def test_c_abi_refuses_bad_arguments_and_touches_nothing():
         sgd(1, one(p), one(g), one(w), one(m), cnt, 0, None, 0, 0, 1, None),
         sgd(0, one(p), one(g), one(w), one(m), cnt, 0, sb, 0, 0, 1, None),
     ]
+    adam, sgd, mom = lib.ssdhip_adam_step, lib.ssdhip_sgd_step, lib.ssdhip_sgd_momentum_step
+    refused += [
+        adam(1, null, one(fg), one(m), one(v), None, cnt, 0, ab, 1, None),
+        adam(1, one(fp), one(fg), null, one(v), None, cnt, 0, ab, 1, None),
+        adam(1, one(fp), one(fg), one(m), one(v), null, cnt, 0, ab, 1, None),
+        adam(1, one(fp, 4), one(fg), one(m), one(v), None, cnt, 0, ab, 1, None),              # a parameter at 4 bytes past 16
+        adam(1, one(fp), one(fg), one(m), one(v), one(vh, 4), cnt, 0, ab, 1, None),
+        adam(1, one(fp), one(fg), one(m), one(v), None, zero, 0, ab, 1, None),
+        adam(1, one(fp), one(fg), one(m), one(v), None, cnt, 64, ab, 1, None),
+        adam(1, one(fp), one(fg), one(m), one(v), None, cnt, 0, None, 1, None),
+        adam(1, one(fp), one(fg), None, one(v), None, cnt, 0, ab, 1, None),
+        adam(0, one(fp), one(fg), one(m), one(v), None, cnt, 0, ab, 1, None),
+        sgd(1, null, one(fg), one(m), cnt, 0, sb, 0, 0, 1, None),
+        sgd(1, one(fp), one(fg), null, cnt, 0, sb, 0, 0, 1, None),
+        sgd(1, one(fp), one(fg, 4), one(m), cnt, 0, sb, 0, 0, 1, None),
+        sgd(1, one(fp), one(fg), one(m, 8), cnt, 0, sb, 0, 0, 1, None),
+        sgd(1, one(fp), one(fg), one(m), zero, 0, sb, 0, 0, 1, None),
+        sgd(1, one(fp), one(fg), one(m), cnt, 64, sb, 0, 0, 1, None),
+        sgd(1, one(fp), one(fg), one(m), cnt, 0, sb, 2, 0, 1, None),                          # no such rule
+        sgd(1, one(fp), one(fg), one(m), cnt, 0, None, 0, 0, 1, None),
+        sgd(1, one(fp), None, one(m), cnt, 0, sb, 0, 0, 1, None),
+        sgd(0, one(fp), one(fg), one(m), cnt, 0, sb, 0, 0, 1, None),
+        mom(1, null, one(fg), one(m), cnt, 0.1, 0.9, 0.0, None),
+        mom(1, one(fp), one(fg), null, cnt, 0.1, 0.9, 0.0, None),
+        mom(1, one(fp), one(fg), one(m, 4), cnt, 0.1, 0.9, 0.0, None),
+        mom(1, one(fp, 4), one(fg), one(m), cnt, 0.1, 0.9, 0.0, None),
+        mom(1, one(fp), one(fg), one(m), zero, 0.1, 0.9, 0.0, None),
+        mom(1, one(fp), one(fg), one(m), None, 0.1, 0.9, 0.0, None),
+        mom(0, one(fp), one(fg), one(m), cnt, 0.1, 0.9, 0.0, None),
+    ]
     assert refused == [E] * len(refused), refused
     torch.cuda.synchronize()
-    assert all(bool((t == 3.0).all()) for t in [p, g] + floats)
+    assert all(bool((t == 3.0).all()) for t in [p, g, fp, fg] + floats)
     assert int(nat.adam_state_read(adam_blk)[0]) == 0 and int(nat.sgd_state_read(sgd_blk)[0]) == 0           # no tick either
     assert torch.equal(adam_blk, blocks[0]) and torch.equal(sgd_blk, blocks[1])
 

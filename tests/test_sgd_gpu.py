@@ -54,9 +54,11 @@ def _same_bits(opt, ps, ts, name, where):
 
 def test_default_sgd_is_the_legacy_export_bit_for_bit():
     """The yardstick: SGD with default arguments (rule 'torch', no Nesterov, no decay) goes through the tick and the state block, and
-    over five steps its parameters and momentum buffers equal, bit for bit, those of `nat.sgd_momentum_step` -- the parent's
-    kernel, untouched -- driven directly on clones with the same gradients.  Two groups (weight decay in one), every shape of the
-    module, 150 small tensors."""
+    over five steps its parameters and momentum buffers equal, bit for bit, those of `nat.sgd_momentum_step` -- the legacy export
+    -- driven directly on clones with the same gradients.  Both kernels are one update body (csrc/ssdhip_optim_step.h), so that
+    comparison alone would prove nothing: the legacy export's clones and buffers are also held, bit for bit, to the NumPy
+    restatement (rule 'torch', no Nesterov, no decay).  Two groups (weight decay in one), every shape of the module, 150 small
+    tensors."""
     import torch
     from ssd_keras_amd import _native as nat
     from ssd_keras_amd.optimizers import SGD
@@ -66,6 +68,8 @@ def test_default_sgd_is_the_legacy_export_bit_for_bit():
     opt = SGD([{"params": ps[:k], "weight_decay": 1e-3}, {"params": ps[k:]}], lr=1e-2, momentum=0.9)
     twins = [p.detach().clone(memory_format=torch.preserve_format) for p in ps]
     bufs = [torch.zeros_like(t, memory_format=torch.preserve_format) for t in twins]
+    refs = [np_sgd.SGD(lr=1e-2, momentum=0.9, weight_decay=1e-3), np_sgd.SGD(lr=1e-2, momentum=0.9)]
+    ts = [np_sgd.fresh(_memory(t)) for t in twins]
     gen = torch.Generator(device="cuda").manual_seed(5)
     for step in range(5):
         grads = [_grad_like(torch, p, gen) for p in ps]
@@ -76,6 +80,12 @@ def test_default_sgd_is_the_legacy_export_bit_for_bit():
             table = nat.sgd_table([_flat(t) for t in twins[sl]], [_flat(g) for g in grads[sl]], [_flat(b) for b in bufs[sl]], dev)
             nat.sgd_momentum_step(table, 1e-2, 0.9, wd)
         torch.cuda.synchronize()
+        refs[0].step(ts[:k], [_memory(g) for g in grads[:k]])
+        refs[1].step(ts[k:], [_memory(g) for g in grads[k:]])
+        for i, (t, b, r) in enumerate(zip(twins, bufs, ts)):
+            for what, got in (("p", _memory(t)), ("buf", _memory(b))):
+                assert np.array_equal(got.view(np.int32), r[what].view(np.int32)), "legacy export: %s of tensor %d, step %d" % (
+                    what, i, step + 1)
         for i, (p, t, b) in enumerate(zip(ps, twins, bufs)):
             assert torch.equal(_flat(p).view(torch.int32), _flat(t).view(torch.int32)), "p of tensor %d, step %d" % (i, step + 1)
             assert torch.equal(_flat(opt.state[p]["momentum_buffer"]).view(torch.int32), _flat(b).view(torch.int32)), (i, step + 1)
