@@ -240,12 +240,24 @@ def current_stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def launch(name, device, *args):
-    """Enqueue export `name` on `device`'s current stream (its last argument) and raise if it reports an error."""
+def _launch(name, device, args, declines=False):
     torch = _torch()
     with torch.cuda.device(device):
         rc = getattr(load(), name)(*args, current_stream_ptr(device))
+    if declines and rc == -1:                             # SSDHIP_E_BADARG: not this kernel's geometry
+        return None
     check(rc, name)
+    return True
+
+
+def launch(name, device, *args):
+    """Enqueue export `name` on `device`'s current stream (its last argument) and raise if it reports an error."""
+    _launch(name, device, args)
+
+
+def _launch_or_none(name, device, *args):
+    """`launch` for the exports whose SSDHIP_E_BADARG means "not my geometry": None then (the caller takes another path), else True."""
+    return _launch(name, device, args, declines=True)
 
 
 class _Workspaces:
@@ -343,6 +355,42 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _filter_nhwc(weight, ok=True, message=None):
+    """The (Cout, Cin, k, k) filters in channels_last memory ([Cout, k, k, Cin] physical), copied where they are not.  `ok`: the
+    caller's dtype / shape check, `message` its error."""
+    if not ok:
+        raise SsdHipError(message)
+    return weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
+def _empty_nhwc(b, h, w, c, dtype, device):
+    """An uninitialised (B, C, H, W) map whose memory is NHWC."""
+    return _torch().empty((b, h, w, c), dtype=dtype, device=device).permute(0, 3, 1, 2)
+
+
+def _conv_out_size(n, k, s, p, d=1):
+    """Output size of a convolution along one axis (torch.nn.Conv2d: floor); < 1: the filter does not fit the padded map."""
+    return (n + 2 * p - d * (k - 1) - 1) // s + 1
+
+
+def _bias_partial_rows(bias_partial, cout, device):
+    """(db, rows) of a weight-gradient call: the float32 [Cout] bias gradient its reduction launch fills from `bias_partial`
+    [rows, Cout], or (None, 0) without one."""
+    if bias_partial is None:
+        return None, 0
+    torch = _torch()
+    if (bias_partial.dtype != torch.float32 or bias_partial.dim() != 2 or bias_partial.shape[1] != cout or not bias_partial.is_contiguous()):
+        raise SsdHipError("bias_partial must be a contiguous float32 [rows, Cout] tensor")
+    return torch.empty((cout,), dtype=torch.float32, device=device), int(bias_partial.shape[0])
+
+
+def _host_arrays(n):
+    """(parr, iarr): builders of the HOST argument arrays of an n-problem launch -- device pointers of tensors (None: null), ints."""
+    parr = lambda ts: (ctypes.c_void_p * n)(*[(t.data_ptr() if t is not None else None) for t in ts])
+    iarr = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+    return parr, iarr
+
+
 def bias_act(x, bias, relu=True, inplace=True):
     """act(x + bias[c]) on an NHWC-memory bf16 feature map (B, C, H, W); in place by default."""
     torch = _torch()
@@ -366,7 +414,7 @@ def bias_act_maxpool(x, bias, kernel, stride, pad=0, ceil_mode=False, relu=True)
     torch = _torch()
     x, (b, h, w, c) = _nhwc_bf16(x, "x")
     ho, wo = pool_out_size(h, kernel, stride, pad, ceil_mode), pool_out_size(w, kernel, stride, pad, ceil_mode)
-    y = torch.empty((b, ho, wo, c), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, ho, wo, c, torch.bfloat16, x.device)
     launch("ssdhip_bias_act_maxpool_nhwc_bf16", x.device, _ptr(x), _ptr(bias), _ptr(y), b, h, w, c, int(kernel), int(stride), int(pad), ho,
            wo, int(bool(relu)))
     return y
@@ -387,7 +435,7 @@ def pool2_l2_normalize(x, gamma):
     torch = _torch()
     x, (b, h, w, c) = _nhwc_bf16(x, "x")
     g = gamma.detach().float().contiguous()
-    pooled = torch.empty((b, (h + 1) // 2, (w + 1) // 2, c), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    pooled = _empty_nhwc(b, (h + 1) // 2, (w + 1) // 2, c, torch.bfloat16, x.device)
     normed = torch.empty_like(x)
     launch("ssdhip_pool2_l2_normalize_nhwc_bf16", x.device, _ptr(x), _ptr(g), _ptr(pooled), _ptr(normed), b, h, w, c)
     return pooled, normed
@@ -470,7 +518,7 @@ def _head_sources(confs, locs, conf_biases, loc_biases, n_boxes, anchors_var, n_
     nl = len(confs)
     keep = []
     cp, lp, cbp, lbp, na, cs, ls = [], [], [], [], [], [], []
-    nhwc = lambda t: t if t.permute(0, 2, 3, 1).is_contiguous() else t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    nhwc = _filter_nhwc                                      # (the head maps: the same layout rule as the filters)
     f32 = confs[0].dtype == torch.float32                    # the reference-precision path: float32 packed heads, bias already added
     esz = 4 if f32 else 2
     for i in range(nl):
@@ -905,10 +953,8 @@ def conv2d_same(x, weight, bias, dilation=1, relu=True, variant=None):
     torch = _torch()
     x, (b, h, w, cin) = _nhwc_bf16(x, "x")
     cout, cin_w, kh, kw = weight.shape
-    if weight.dtype != torch.bfloat16 or cin_w != cin or kh != kw:
-        raise SsdHipError("weight must be bfloat16 (Cout, %d, k, k)" % cin)
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight, weight.dtype == torch.bfloat16 and cin_w == cin and kh == kw, "weight must be bfloat16 (Cout, %d, k, k)" % cin)
+    y = _empty_nhwc(b, h, w, cout, torch.bfloat16, x.device)
     args = (_ptr(x), _ptr(wt), _ptr(bias), _ptr(y), b, h, w, cin, cout, int(kh), int(dilation), int(bool(relu)))
     if variant is None:
         launch("ssdhip_conv2d_same_nhwc_bf16", x.device, *args)
@@ -932,11 +978,10 @@ def conv3x3_halo(x, weight, bias, relu=True, pool=False):
     torch = _torch()
     x, (b, h, w, cin) = _nhwc_bf16(x, "x")
     cout, cin_w, kh, kw = weight.shape
-    if weight.dtype != torch.bfloat16 or cin_w != cin or kh != 3 or kw != 3:
-        raise SsdHipError("weight must be bfloat16 (Cout, %d, 3, 3)" % cin)
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight, weight.dtype == torch.bfloat16 and cin_w == cin and kh == 3 and kw == 3,
+                      "weight must be bfloat16 (Cout, %d, 3, 3)" % cin)
     ho, wo = ((h + 1) // 2, (w + 1) // 2) if pool else (h, w)
-    y = torch.empty((b, ho, wo, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, ho, wo, cout, torch.bfloat16, x.device)
     launch("ssdhip_conv3x3_halo_nhwc_bf16", x.device, _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), b, h, w, cin, cout, int(bool(relu)),
            int(bool(pool)))
     return y
@@ -958,20 +1003,18 @@ def conv3x3_halo_masked(x, weight, mask, sums=False):
     mask, mshape = _nhwc_bf16(mask, "mask")
     if mshape != (b, h, w, cout):
         raise SsdHipError("mask must have the output's shape %s, got %s" % ((b, h, w, cout), mshape))
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight)
+    y = _empty_nhwc(b, h, w, cout, torch.bfloat16, x.device)
     partial, rows = None, 0
-    with torch.cuda.device(x.device):
-        if sums:
+    if sums:
+        with torch.cuda.device(x.device):                 # (the rows follow the device's CU count)
             rows = lib.ssdhip_conv3x3_halo_masked_bias_rows(b, h, w, cout)
-            if rows <= 0:
-                return None
-            partial = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
-        rc = lib.ssdhip_conv3x3_halo_masked_nhwc_bf16(_ptr(x), _ptr(wt), _ptr(mask), _ptr(y), _ptr(partial), rows, b, h, w, cin, cout,
-                                                      current_stream_ptr(x.device))
-    if rc == -1:                                          # SSDHIP_E_BADARG: not the slab kernel's geometry
+        if rows <= 0:
+            return None
+        partial = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
+    if _launch_or_none("ssdhip_conv3x3_halo_masked_nhwc_bf16", x.device, _ptr(x), _ptr(wt), _ptr(mask), _ptr(y), _ptr(partial), rows, b, h, w,
+                       cin, cout) is None:
         return None
-    check(rc, "ssdhip_conv3x3_halo_masked_nhwc_bf16")
     return (y, partial) if sums else y
 
 
@@ -988,10 +1031,9 @@ def conv3x3_image(x, weight, bias, dilation=1, relu=True):
     torch = _torch()
     x, (b, h, w, cin) = _nhwc_bf16(x, "x")
     cout, cin_w, kh, kw = weight.shape
-    if weight.dtype != torch.bfloat16 or cin_w != cin or kh != 3 or kw != 3:
-        raise SsdHipError("weight must be bfloat16 (Cout, %d, 3, 3)" % cin)
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight, weight.dtype == torch.bfloat16 and cin_w == cin and kh == 3 and kw == 3,
+                      "weight must be bfloat16 (Cout, %d, 3, 3)" % cin)
+    y = _empty_nhwc(b, h, w, cout, torch.bfloat16, x.device)
     launch("ssdhip_conv3x3_image_nhwc_bf16", x.device, _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), b, h, w, cin, cout, int(dilation),
            int(bool(relu)))
     return y
@@ -1008,8 +1050,7 @@ def conv2d_image_supported(x, weight, stride=1, padding=0, dilation=1):
         return False
     if not (1 <= s <= 4 and 1 <= d <= 16 and 0 <= p <= d * (k // 2)) or h + 2 * p < d * (k - 1) + 1 or w + 2 * p < d * (k - 1) + 1:
         return False
-    ho, wo = (h + 2 * p - d * (k - 1) - 1) // s + 1, (w + 2 * p - d * (k - 1) - 1) // s + 1
-    return 1 <= ho * wo <= 384
+    return 1 <= _conv_out_size(h, k, s, p, d) * _conv_out_size(w, k, s, p, d) <= 384
 
 
 def conv2d_image(x, weight, bias, stride=1, padding=0, dilation=1, relu=True):
@@ -1018,14 +1059,13 @@ def conv2d_image(x, weight, bias, stride=1, padding=0, dilation=1, relu=True):
     torch = _torch()
     x, (b, h, w, cin) = _nhwc_bf16(x, "x")
     cout, cin_w, kh, kw = weight.shape
-    if weight.dtype != torch.bfloat16 or cin_w != cin or kh != kw or kh not in (1, 3):
-        raise SsdHipError("weight must be bfloat16 (Cout, %d, k, k) with k in (1, 3)" % cin)
+    wt = _filter_nhwc(weight, weight.dtype == torch.bfloat16 and cin_w == cin and kh == kw and kh in (1, 3),
+                      "weight must be bfloat16 (Cout, %d, k, k) with k in (1, 3)" % cin)
     k, s, p, d = int(kh), int(stride), int(padding), int(dilation)
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    ho, wo = (h + 2 * p - d * (k - 1) - 1) // s + 1, (w + 2 * p - d * (k - 1) - 1) // s + 1
+    ho, wo = _conv_out_size(h, k, s, p, d), _conv_out_size(w, k, s, p, d)
     if ho < 1 or wo < 1:
         raise SsdHipError("the filter does not fit the padded map")
-    y = torch.empty((b, ho, wo, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, ho, wo, cout, torch.bfloat16, x.device)
     launch("ssdhip_conv2d_image_nhwc_bf16", x.device, _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), b, h, w, cin, cout, k, s, p, d,
            int(bool(relu)))
     return y
@@ -1042,7 +1082,7 @@ def conv_chain_pack(weight, out=None):
     n = int(lib.ssdhip_conv_chain_packed_bytes(kh, cin, cout))
     if n == 0:
         return None
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight)
     if out is not None and (out.numel() != n or out.dtype != torch.uint8 or out.device != weight.device):
         raise SsdHipError("conv_chain_pack: `out` does not match this filter's packed size")
     packed = out if out is not None else torch.empty((n,), dtype=torch.uint8, device=weight.device)
@@ -1050,37 +1090,34 @@ def conv_chain_pack(weight, out=None):
     return packed
 
 
+def _chain_walk(layers, b, h, w, width, dtype, device, check_layer=None):
+    """The map sizes of a chain of layers from a (b, h, w) input: (kept outputs -- (B, width * cout, Ho, Wo) maps of `dtype`, the
+    arguments both chain exports share from the layer count on), or None when a layer's output would be empty."""
+    outs, ys = [], []
+    for l in layers:
+        h, w = _conv_out_size(h, l["k"], l["stride"], l["pad"]), _conv_out_size(w, l["k"], l["stride"], l["pad"])
+        if h < 1 or w < 1:
+            return None
+        if check_layer is not None:
+            check_layer(l)
+        ys.append(_empty_nhwc(b, h, w, width * l["cout"], dtype, device) if l.get("keep", False) else None)
+    outs = [y for y in ys if y is not None]
+    parr, iarr = _host_arrays(len(layers))
+    of = lambda key: iarr(l[key] for l in layers)
+    return outs, (len(layers), parr([l["packed"] for l in layers]), parr([l.get("bias") for l in layers]), parr(ys), of("k"), of("stride"),
+                  of("pad"), of("cout"), of("relu"))
+
+
 def conv_chain(x, layers):
     """A chain of small convolutions in one launch (csrc/ssdhip_chain.hip).  x (B, C0, H, W) bfloat16 channels_last; `layers`: a list of
     dicts {packed, bias (bfloat16 or None), k, stride, pad, cout, relu, keep}; returns the list of the kept layers' outputs
     (B, Cout, Ho, Wo) channels_last, or None when the chain does not fit (the caller runs the layers one by one)."""
     torch = _torch()
-    lib = load()
     x, (b, h, w, c0) = _nhwc_bf16(x, "x")
-    n = len(layers)
-    outs, ys = [], []
-    hh, ww = h, w
-    for l in layers:
-        hh = (hh + 2 * l["pad"] - l["k"]) // l["stride"] + 1
-        ww = (ww + 2 * l["pad"] - l["k"]) // l["stride"] + 1
-        if hh < 1 or ww < 1:
-            return None
-        if l.get("keep", False):
-            y = torch.empty((b, hh, ww, l["cout"]), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
-            outs.append(y)
-            ys.append(y)
-        else:
-            ys.append(None)
-    parr = lambda ts: (ctypes.c_void_p * n)(*[(t.data_ptr() if t is not None else None) for t in ts])
-    iarr = lambda key: (ctypes.c_int * n)(*[int(l[key]) for l in layers])
-    with torch.cuda.device(x.device):
-        rc = lib.ssdhip_conv_chain_nhwc_bf16(_ptr(x), b, h, w, c0, n, parr([l["packed"] for l in layers]), parr([l.get("bias") for l in layers]),
-                                             parr(ys), iarr("k"), iarr("stride"), iarr("pad"), iarr("cout"), iarr("relu"),
-                                             current_stream_ptr(x.device))
-    if rc == -1:                                          # SSDHIP_E_BADARG: the chain does not fit this kernel
+    walk = _chain_walk(layers, b, h, w, 1, torch.bfloat16, x.device)
+    if walk is None or _launch_or_none("ssdhip_conv_chain_nhwc_bf16", x.device, _ptr(x), b, h, w, c0, *walk[1]) is None:
         return None
-    check(rc, "ssdhip_conv_chain_nhwc_bf16")
-    return outs
+    return walk[0]
 
 
 def conv_chain_x3_pack(packed_weight, out=None):
@@ -1107,37 +1144,21 @@ def conv_chain_x3(x2, layers):
     output divisor, or None), k, stride, pad, cout, relu, mul (oscale * input divisor / output divisor), keep}; returns the kept
     layers' pair maps (B, 2 Cout, Ho, Wo), or None when the chain does not fit (the caller runs the layers one by one)."""
     torch = _torch()
-    lib = load()
     if not (x2.is_cuda and x2.dtype == torch.float16 and x2.dim() == 4 and x2.shape[1] % 2 == 0 and _nhwc_ok(x2)):
         raise SsdHipError("conv_chain_x3 takes a float16 (B, 2 C, H, W) channels_last pair map")
     b, c2, h, w = x2.shape
-    n = len(layers)
-    outs, ys = [], []
-    hh, ww = h, w
-    for l in layers:
-        hh = (hh + 2 * l["pad"] - l["k"]) // l["stride"] + 1
-        ww = (ww + 2 * l["pad"] - l["k"]) // l["stride"] + 1
-        if hh < 1 or ww < 1:
-            return None
+
+    def float32_bias(l):
         if l.get("bias") is not None and (l["bias"].dtype != torch.float32 or not l["bias"].is_contiguous()):
             raise SsdHipError("conv_chain_x3: bias must be contiguous float32")
-        if l.get("keep", False):
-            y = torch.empty((b, hh, ww, 2 * l["cout"]), dtype=torch.float16, device=x2.device).permute(0, 3, 1, 2)
-            outs.append(y)
-            ys.append(y)
-        else:
-            ys.append(None)
-    parr = lambda ts: (ctypes.c_void_p * n)(*[(t.data_ptr() if t is not None else None) for t in ts])
-    iarr = lambda key: (ctypes.c_int * n)(*[int(l[key]) for l in layers])
-    farr = (ctypes.c_float * n)(*[float(l["mul"]) for l in layers])
-    with torch.cuda.device(x2.device):
-        rc = lib.ssdhip_conv_chain_x3_nhwc_f16(_ptr(x2), b, h, w, c2 // 2, n, parr([l["packed"] for l in layers]),
-                                               parr([l.get("bias") for l in layers]), parr(ys), iarr("k"), iarr("stride"), iarr("pad"),
-                                               iarr("cout"), iarr("relu"), farr, current_stream_ptr(x2.device))
-    if rc == -1:                                          # SSDHIP_E_BADARG: the chain does not fit this kernel
+
+    walk = _chain_walk(layers, b, h, w, 2, torch.float16, x2.device, float32_bias)
+    if walk is None:
         return None
-    check(rc, "ssdhip_conv_chain_x3_nhwc_f16")
-    return outs
+    farr = (ctypes.c_float * len(layers))(*[float(l["mul"]) for l in layers])
+    if _launch_or_none("ssdhip_conv_chain_x3_nhwc_f16", x2.device, _ptr(x2), b, h, w, c2 // 2, *walk[1], farr) is None:
+        return None
+    return walk[0]
 
 
 def conv3x3_wgrad(x, dy, bias_partial=None):
@@ -1158,11 +1179,9 @@ def conv3x3_wgrad(x, dy, bias_partial=None):
     ws = workspaces.get(x.device, "wgrad", need)
     dw = torch.empty((cout, 3, 3, cin), dtype=torch.float32, device=x.device)
     if bias_partial is not None:
-        if (bias_partial.dtype != torch.float32 or bias_partial.dim() != 2 or bias_partial.shape[1] != cout or not bias_partial.is_contiguous()):
-            raise SsdHipError("bias_partial must be a contiguous float32 [rows, Cout] tensor")
-        db = torch.empty((cout,), dtype=torch.float32, device=x.device)
-        launch("ssdhip_conv3x3_wgrad_bias_nhwc_bf16", x.device, _ptr(x), _ptr(dy), _ptr(dw), _ptr(bias_partial), int(bias_partial.shape[0]),
-               _ptr(db), b, h, w, cin, cout, _ptr(ws), need)
+        db, rows = _bias_partial_rows(bias_partial, cout, x.device)
+        launch("ssdhip_conv3x3_wgrad_bias_nhwc_bf16", x.device, _ptr(x), _ptr(dy), _ptr(dw), _ptr(bias_partial), rows, _ptr(db), b, h, w, cin,
+               cout, _ptr(ws), need)
         return dw.permute(0, 3, 1, 2), db
     launch("ssdhip_conv3x3_wgrad_nhwc_bf16", x.device, _ptr(x), _ptr(dy), _ptr(dw), b, h, w, cin, cout, _ptr(ws), need)
     return dw.permute(0, 3, 1, 2)
@@ -1182,14 +1201,8 @@ def conv1x1_wgrad(x, dy, bias_partial=None):
     if need == 0:
         return None
     ws = workspaces.get(x.device, "wgrad", need)
-    dw = torch.empty((cout, 1, 1, cin), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)     # channels_last strides, like the 3 x 3 form
-    db = None
-    rows = 0
-    if bias_partial is not None:
-        if (bias_partial.dtype != torch.float32 or bias_partial.dim() != 2 or bias_partial.shape[1] != cout or not bias_partial.is_contiguous()):
-            raise SsdHipError("bias_partial must be a contiguous float32 [rows, Cout] tensor")
-        db = torch.empty((cout,), dtype=torch.float32, device=x.device)
-        rows = int(bias_partial.shape[0])
+    dw = _empty_nhwc(cout, 1, 1, cin, torch.float32, x.device)     # channels_last strides, like the 3 x 3 form
+    db, rows = _bias_partial_rows(bias_partial, cout, x.device)
     launch("ssdhip_conv1x1_wgrad_bias_nhwc_bf16", x.device, _ptr(x), _ptr(dy), _ptr(dw), _ptr(bias_partial), rows, _ptr(db), b * h * w, cin,
            cout, _ptr(ws), need)
     return (dw, db) if bias_partial is not None else dw
@@ -1228,14 +1241,8 @@ def conv3x3_taps_wgrad(x, dy, stride=1, padding=1, dilation=1, bias_partial=None
     if need == 0:
         return None
     ws = workspaces.get(x.device, "wgrad", need)
-    dw = torch.empty((cout, 3, 3, cin), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)
-    db = None
-    rows = 0
-    if bias_partial is not None:
-        if (bias_partial.dtype != torch.float32 or bias_partial.dim() != 2 or bias_partial.shape[1] != cout or not bias_partial.is_contiguous()):
-            raise SsdHipError("bias_partial must be a contiguous float32 [rows, Cout] tensor")
-        db = torch.empty((cout,), dtype=torch.float32, device=x.device)
-        rows = int(bias_partial.shape[0])
+    dw = _empty_nhwc(cout, 3, 3, cin, torch.float32, x.device)
+    db, rows = _bias_partial_rows(bias_partial, cout, x.device)
     launch("ssdhip_conv3x3_taps_wgrad_bias_nhwc_bf16", x.device, _ptr(x), _ptr(dy), _ptr(dw), _ptr(bias_partial), rows, _ptr(db), *geom,
            _ptr(ws), need)
     return (dw, db) if bias_partial is not None else dw
@@ -1252,33 +1259,32 @@ def embed_strided(gy, h, w, stride, offset):
     return z
 
 
+def _group_launch(name, xs, weights, biases, only_3x3, *tail):
+    """One launch of the group export `name` over independent 'same' convolutions: the problem count, the HOST arrays x, weight, bias,
+    y, B, H, W, Cin, Cout -- where the export takes any kernel also the kernel sizes and dilations (1) -- and `tail`.  The outputs."""
+    torch = _torch()
+    ts, dims, ys = [], [], []                              # (ts keeps the NHWC copies alive until the launch is enqueued)
+    for i in range(len(xs)):
+        x, (b, h, w, cin) = _nhwc_bf16(xs[i], "x")
+        cout, cin_w, kh, kw = weights[i].shape
+        wt = _filter_nhwc(weights[i], weights[i].dtype == torch.bfloat16 and cin_w == cin and kh == kw and (kh == 3 or not only_3x3),
+                          "weight %d must be bfloat16 (Cout, %d, %s)" % (i, cin, "3, 3" if only_3x3 else "k, k"))
+        ys.append(_empty_nhwc(b, h, w, cout, torch.bfloat16, x.device))
+        ts.append((x, wt, biases[i] if biases is not None else None, ys[-1]))
+        dims.append((b, h, w, cin, cout, kh))
+    parr, iarr = _host_arrays(len(xs))
+    arrays = [parr(t[k] for t in ts) for k in range(4)] + [iarr(d[k] for d in dims) for k in range(5 if only_3x3 else 6)]
+    if not only_3x3:
+        arrays.append(iarr([1] * len(xs)))
+    launch(name, ys[0].device, len(xs), *arrays, *tail)
+    return ys
+
+
 def conv3x3_halo_group(xs, weights, biases=None, relu=False, max_workgroups=0):
     """Several independent 3x3 'same' convolutions through the slab kernel in ONE launch (persistent workgroups, deepest problem
     first): the packed predictor heads.  xs[i] (B, Cin_i, H_i, W_i) bf16 NHWC memory, weights[i] (Cout_i, Cin_i, 3, 3) bf16
     channels_last; Cin_i % 128 == 0, Cout_i % 128 == 0, W_i <= 62 -> list of outputs (bit-identical to conv2d_same)."""
-    torch = _torch()
-    n = len(xs)
-    keep, xp, wp, bp, yp, dims, ys = [], [], [], [], [], [], []
-    for i in range(n):
-        x, (b, h, w, cin) = _nhwc_bf16(xs[i], "x")
-        wt = weights[i]
-        cout, cin_w, kh, kw = wt.shape
-        if wt.dtype != torch.bfloat16 or cin_w != cin or kh != 3 or kw != 3:
-            raise SsdHipError("weight %d must be bfloat16 (Cout, %d, 3, 3)" % (i, cin))
-        if not wt.permute(0, 2, 3, 1).is_contiguous():
-            wt = wt.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-        y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
-        keep += [x, wt]
-        ys.append(y)
-        xp.append(x.data_ptr()); wp.append(wt.data_ptr()); yp.append(y.data_ptr())
-        bp.append(biases[i].data_ptr() if (biases is not None and biases[i] is not None) else 0)
-        dims.append((b, h, w, cin, cout))
-    parr = lambda v: (ctypes.c_void_p * n)(*v)
-    iarr = lambda k: (ctypes.c_int * n)(*[d[k] for d in dims])
-    dev = ys[0].device
-    launch("ssdhip_conv3x3_halo_group_nhwc_bf16", dev, n, parr(xp), parr(wp), parr(bp), parr(yp), iarr(0), iarr(1), iarr(2), iarr(3),
-           iarr(4), int(bool(relu)), int(max_workgroups))
-    return ys
+    return _group_launch("ssdhip_conv3x3_halo_group_nhwc_bf16", xs, weights, biases, True, int(bool(relu)), int(max_workgroups))
 
 
 def conv2d(x, weight, bias, stride=1, padding=0, dilation=1, relu=True, variant=None):
@@ -1287,14 +1293,11 @@ def conv2d(x, weight, bias, stride=1, padding=0, dilation=1, relu=True, variant=
     torch = _torch()
     x, (b, h, w, cin) = _nhwc_bf16(x, "x")
     cout, cin_w, kh, kw = weight.shape
-    if weight.dtype != torch.bfloat16 or cin_w != cin or kh != kw:
-        raise SsdHipError("weight must be bfloat16 (Cout, %d, k, k)" % cin)
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    span = int(dilation) * (int(kh) - 1) + 1
-    ho, wo = (h + 2 * int(padding) - span) // int(stride) + 1, (w + 2 * int(padding) - span) // int(stride) + 1
+    wt = _filter_nhwc(weight, weight.dtype == torch.bfloat16 and cin_w == cin and kh == kw, "weight must be bfloat16 (Cout, %d, k, k)" % cin)
+    ho, wo = (_conv_out_size(n, int(kh), int(stride), int(padding), int(dilation)) for n in (h, w))
     if ho < 1 or wo < 1:
         raise SsdHipError("convolution output would be empty")
-    y = torch.empty((b, ho, wo, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, ho, wo, cout, torch.bfloat16, x.device)
     if variant == 7:                                         # the slab kernel's strided / cropped form (3x3, dilation 1 only)
         if int(kh) != 3 or int(dilation) != 1:
             raise SsdHipError("variant 7 is a 3x3, dilation-1 kernel")
@@ -1328,7 +1331,7 @@ def x3_merge(y2):
     c = c2 // 2
     if not (y2.is_cuda and y2.dtype == torch.float16 and c % 8 == 0 and _nhwc_ok(y2)):
         return y2[:, :c].float() + y2[:, c:].float()
-    out = torch.empty((b, h, w, c), dtype=torch.float32, device=y2.device).permute(0, 3, 1, 2)
+    out = _empty_nhwc(b, h, w, c, torch.float32, y2.device)
     launch("ssdhip_x3_merge_nhwc", y2.device, _ptr(y2), _ptr(out), b * h * w, c)
     return out
 
@@ -1349,7 +1352,7 @@ def x3_maxpool(y2, kernel, stride, padding=0, ceil_mode=False):
             o -= 1
         return o
     ho, wo = out(h), out(w)
-    y = torch.empty((b, ho, wo, c2), dtype=torch.float16, device=y2.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, ho, wo, c2, torch.float16, y2.device)
     launch("ssdhip_x3_maxpool_nhwc", y2.device, _ptr(y2), _ptr(y), b, h, w, c2 // 2, k, s, p, ho, wo)
     return y
 
@@ -1365,7 +1368,7 @@ def x3_l2_normalize(y2, gamma, scale=1.0):
     g = gamma.detach()
     if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != c2 // 2 or g.device != y2.device:
         raise SsdHipError("gamma must be a contiguous float32 tensor of C elements on the map's device")
-    y = torch.empty((b, h, w, c2), dtype=torch.float16, device=y2.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, h, w, c2, torch.float16, y2.device)
     launch("ssdhip_x3_l2_normalize_nhwc", y2.device, _ptr(y2), _ptr(g), _ptr(y), b * h * w, c2 // 2, ctypes.c_float(float(scale)))
     return y
 
@@ -1379,7 +1382,7 @@ def conv1_1_x3(x, weight, bias, relu=True):
         raise SsdHipError("conv1_1_x3 takes float32 (B, 3, H, W) channels_last images and (64, 3, 3, 3) filters")
     wk = weight.detach().float().permute(0, 2, 3, 1).contiguous()          # (co, kh, kw, ci)
     bk = bias.detach().float().contiguous() if bias is not None else None
-    y = torch.empty((b, h, w, 128), dtype=torch.float16, device=x.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, h, w, 128, torch.float16, x.device)
     launch("ssdhip_conv1_1_x3_nhwc", x.device, _ptr(x), _ptr(wk), _ptr(bk), _ptr(y), b, h, w, int(bool(relu)))
     return y
 
@@ -1397,7 +1400,7 @@ def conv1_1_x3_pre(images, weight, bias, mean=None, divide=None, swap=None, relu
     bk = bias.detach().float().contiguous() if bias is not None else None
     f3 = lambda v: (ctypes.c_float * 3)(*[float(t) for t in v]) if v is not None else None
     i3 = (ctypes.c_int * 3)(*[int(t) for t in swap]) if swap is not None else None
-    y = torch.empty((b, h, w, 128), dtype=torch.float16, device=images.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, h, w, 128, torch.float16, images.device)
     launch("ssdhip_conv1_1_x3_pre_nhwc", images.device, _ptr(images), _ptr(wk), _ptr(bk), _ptr(y), b, h, w, int(bool(relu)), f3(mean),
            f3(divide), i3)
     return y
@@ -1412,7 +1415,7 @@ def x3_split(v):
             v = v.contiguous(memory_format=torch.channels_last)
         if _nhwc_ok(v):
             b, c, h, w = v.shape
-            out = torch.empty((b, h, w, 2 * c), dtype=torch.float16, device=v.device).permute(0, 3, 1, 2)
+            out = _empty_nhwc(b, h, w, 2 * c, torch.float16, v.device)
             launch("ssdhip_x3_split_nhwc", v.device, _ptr(v), _ptr(out), b * h * w, c)
             return out
     hi = v.to(torch.float16)
@@ -1454,8 +1457,7 @@ def conv2d_x3(x2, packed_weight, bias, oscale, stride=1, padding=0, dilation=1, 
         raise SsdHipError("packed filters must be (Cout, 3 C, k, k) channels_last for a (B, 2 C, H, W) input")
     if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
         raise SsdHipError("bias must be contiguous float32")
-    span = int(dilation) * (int(kh) - 1) + 1
-    ho, wo = (h + 2 * int(padding) - span) // int(stride) + 1, (w + 2 * int(padding) - span) // int(stride) + 1
+    ho, wo = (_conv_out_size(n, int(kh), int(stride), int(padding), int(dilation)) for n in (h, w))
     if pool:
         ho, wo = (h + 1) // 2, (w + 1) // 2
     if ho < 1 or wo < 1:
@@ -1472,7 +1474,7 @@ def conv2d_x3(x2, packed_weight, bias, oscale, stride=1, padding=0, dilation=1, 
             and (slab64 or os.environ.get("SSDHIP_X3_NO_HALO", "0") != "1") and not image_first):
         # the slab kernel (csrc/ssdhip_convh.hip): the deep 3x3 layers and the packed heads; it writes split pairs, merged here when
         # the caller wants float32
-        y2 = torch.empty((b, ho, wo, 2 * cout), dtype=torch.float16, device=x2.device).permute(0, 3, 1, 2)
+        y2 = _empty_nhwc(b, ho, wo, 2 * cout, torch.float16, x2.device)
         launch("ssdhip_conv3x3_halo_x3_nhwc_f16", x2.device, _ptr(x2), _ptr(packed_weight), _ptr(bias), _ptr(y2), b, h, w, c, cout,
                int(bool(relu)), int(bool(pool)), ctypes.c_float(float(oscale)))
         return x3_merge(y2) if out_f32 else y2
@@ -1498,10 +1500,8 @@ def conv2d_same_pool2(x, weight, bias, dilation=1, relu=True):
     torch = _torch()
     x, (b, h, w, cin) = _nhwc_bf16(x, "x")
     cout, cin_w, kh, kw = weight.shape
-    if weight.dtype != torch.bfloat16 or cin_w != cin or kh != kw:
-        raise SsdHipError("weight must be bfloat16 (Cout, %d, k, k)" % cin)
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    y = torch.empty((b, (h + 1) // 2, (w + 1) // 2, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight, weight.dtype == torch.bfloat16 and cin_w == cin and kh == kw, "weight must be bfloat16 (Cout, %d, k, k)" % cin)
+    y = _empty_nhwc(b, (h + 1) // 2, (w + 1) // 2, cout, torch.bfloat16, x.device)
     launch("ssdhip_conv2d_same_pool2_nhwc_bf16", x.device, _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), b, h, w, cin, cout, int(kh),
            int(dilation), int(bool(relu)))
     return y
@@ -1510,29 +1510,7 @@ def conv2d_same_pool2(x, weight, bias, dilation=1, relu=True):
 def conv2d_same_group(xs, weights, biases=None, relu=False):
     """Several independent 'same' convolutions (kernel 1 or 3, stride 1, dilation 1) in ONE libssdhip launch.
     xs[i] (B, Cin_i, H_i, W_i) bf16 NHWC memory, weights[i] (Cout_i, Cin_i, k, k) bf16 channels_last -> list of outputs."""
-    torch = _torch()
-    n = len(xs)
-    keep, xp, wp, bp, yp, dims, ys = [], [], [], [], [], [], []
-    for i in range(n):
-        x, (b, h, w, cin) = _nhwc_bf16(xs[i], "x")
-        wt = weights[i]
-        cout, cin_w, kh, kw = wt.shape
-        if wt.dtype != torch.bfloat16 or cin_w != cin or kh != kw:
-            raise SsdHipError("weight %d must be bfloat16 (Cout, %d, k, k)" % (i, cin))
-        if not wt.permute(0, 2, 3, 1).is_contiguous():
-            wt = wt.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-        y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
-        keep += [x, wt]
-        ys.append(y)
-        xp.append(x.data_ptr()); wp.append(wt.data_ptr()); yp.append(y.data_ptr())
-        bp.append(biases[i].data_ptr() if (biases is not None and biases[i] is not None) else 0)
-        dims.append((b, h, w, cin, cout, int(kh), 1))
-    parr = lambda v: (ctypes.c_void_p * n)(*v)
-    iarr = lambda k: (ctypes.c_int * n)(*[d[k] for d in dims])
-    dev = ys[0].device
-    launch("ssdhip_conv2d_same_group_nhwc_bf16", dev, n, parr(xp), parr(wp), parr(bp), parr(yp), iarr(0), iarr(1), iarr(2), iarr(3),
-           iarr(4), iarr(5), iarr(6), int(bool(relu)))
-    return ys
+    return _group_launch("ssdhip_conv2d_same_group_nhwc_bf16", xs, weights, biases, False, int(bool(relu)))
 
 
 _CU_COUNT = {}
@@ -1546,9 +1524,9 @@ def conv3x3_c64(x, weight, bias, relu=True, pool=False):
     cout, cin_w, kh, kw = weight.shape
     if weight.dtype != torch.bfloat16 or cin_w != cin or cin != 64 or kh != 3 or kw != 3:
         raise SsdHipError("conv3x3_c64 needs a bfloat16 (Cout, 64, 3, 3) weight and a 64-channel input")
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight)
     ho, wo = ((h + 1) // 2, (w + 1) // 2) if pool else (h, w)
-    y = torch.empty((b, ho, wo, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, ho, wo, cout, torch.bfloat16, x.device)
     key = str(x.device)
     if key not in _CU_COUNT:
         _CU_COUNT[key] = int(torch.cuda.get_device_properties(x.device).multi_processor_count)
@@ -1566,9 +1544,9 @@ def conv3x3_c64_pool_keep(x, weight, bias, relu=True):
     cout, cin_w, kh, kw = weight.shape
     if weight.dtype != torch.bfloat16 or cin_w != cin or cin != 64 or kh != 3 or kw != 3:
         raise SsdHipError("conv3x3_c64_pool_keep needs a bfloat16 (Cout, 64, 3, 3) weight and a 64-channel input")
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
-    pooled = torch.empty((b, (h + 1) // 2, (w + 1) // 2, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight)
+    y = _empty_nhwc(b, h, w, cout, torch.bfloat16, x.device)
+    pooled = _empty_nhwc(b, (h + 1) // 2, (w + 1) // 2, cout, torch.bfloat16, x.device)
     key = str(x.device)
     if key not in _CU_COUNT:
         _CU_COUNT[key] = int(torch.cuda.get_device_properties(x.device).multi_processor_count)
@@ -1587,9 +1565,9 @@ def conv3x3_halo_pool_keep(x, weight, bias, relu=True):
     if not x.is_cuda or x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or kh != 3 or kw != 3 or cin_w % 128 or cout % 128 or x.shape[1] != cin_w:
         return None
     x, (b, h, w, cin) = _nhwc_bf16(x, "x")
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
-    pooled = torch.empty((b, (h + 1) // 2, (w + 1) // 2, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight)
+    y = _empty_nhwc(b, h, w, cout, torch.bfloat16, x.device)
+    pooled = _empty_nhwc(b, (h + 1) // 2, (w + 1) // 2, cout, torch.bfloat16, x.device)
     with torch.cuda.device(x.device):
         rc = lib.ssdhip_conv3x3_halo_pool_keep_nhwc_bf16(_ptr(x), _ptr(wt), _ptr(bias), _ptr(y), _ptr(pooled), b, h, w, cin, cout, int(bool(relu)),
                                                          current_stream_ptr(x.device))
@@ -1608,8 +1586,8 @@ def conv3x3_cin3(x, weight, bias, relu=True):
         x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
     b, cin, h, w = x.shape
     cout = weight.shape[0]
-    wt = weight if weight.permute(0, 2, 3, 1).is_contiguous() else weight.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    wt = _filter_nhwc(weight)
+    y = _empty_nhwc(b, h, w, cout, torch.bfloat16, x.device)
     launch("ssdhip_conv3x3_cin3_nhwc_bf16", x.device, _ptr(x), _ptr(wt), _ptr(bias), _ptr(y), b, h, w, cin, cout, int(bool(relu)))
     return y
 
@@ -1658,7 +1636,7 @@ def conv_bn_elu(x, packed, scale, shift, kernel, pool, out=None):
                           % (cin, cout, kernel))
     ho, wo = (h // 2, w // 2) if pool else (h, w)
     if out is None:
-        out = torch.empty((b, ho, wo, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+        out = _empty_nhwc(b, ho, wo, cout, torch.bfloat16, x.device)
     elif tuple(out.shape) != (b, cout, ho, wo) or out.dtype != torch.bfloat16 or not out.permute(0, 2, 3, 1).is_contiguous():
         raise SsdHipError("conv_bn_elu: `out` must be a (%d, %d, %d, %d) bf16 tensor with NHWC memory" % (b, cout, ho, wo))
     launch("ssdhip_conv_bn_elu_nhwc_bf16", x.device, _ptr(x), _ptr(packed), _ptr(scale), _ptr(shift), _ptr(out), b, h, w, cin, cout,
@@ -1698,7 +1676,7 @@ def ssd7_conv_bias(x, packed, bias, cout, kernel, out=None):
     if bias is not None and (not bias.is_cuda or bias.dtype != torch.bfloat16 or bias.numel() != cout or not bias.is_contiguous()):
         raise SsdHipError("ssd7_conv_bias: bias must be a contiguous (%d,) bfloat16 CUDA tensor" % cout)
     if out is None:
-        out = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+        out = _empty_nhwc(b, h, w, cout, torch.bfloat16, x.device)
     elif _ssd7_map(out, "out") != (b, h, w, cout):
         raise SsdHipError("ssd7_conv_bias: `out` must be a (%d, %d, %d, %d) bf16 tensor with NHWC memory" % (b, cout, h, w))
     launch("ssdhip_conv_same_bias_nhwc_bf16", x.device, _ptr(x), _ptr(packed), _ptr(bias), _ptr(out), b, h, w, cin, int(cout), int(kernel))
@@ -1773,7 +1751,7 @@ def ssd7_conv_wgrad(x, dy, kernel, like=None):
     if need == 0:
         raise SsdHipError("ssd7_conv_wgrad: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, k))
     if like is None:
-        dw = torch.empty((cout, k, k, cin), dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+        dw = _empty_nhwc(cout, k, k, cin, torch.float32, dev)
     else:
         if tuple(like.shape) != (cout, cin, k, k) or like.dtype not in (torch.float32, torch.bfloat16):
             raise SsdHipError("ssd7_conv_wgrad: `like` must be a (%d, %d, %d, %d) float32 or bfloat16 tensor" % (cout, cin, k, k))
@@ -1935,8 +1913,8 @@ def bn_elu_train_forward(y, gamma, beta, running_mean, running_var, momentum, ep
         raise SsdHipError("bn_elu_train: running_mean and running_var come together")
     running_bf16 = 0 if running_mean is None else _bn_train_vectors(c, y.device, running_mean=running_mean, running_var=running_var)
     dev = y.device
-    full = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=dev).permute(0, 3, 1, 2) if (keep_full or not pool) else None
-    pooled = torch.empty((b, h // 2, w // 2, c), dtype=torch.bfloat16, device=dev).permute(0, 3, 1, 2) if pool else None
+    full = _empty_nhwc(b, h, w, c, torch.bfloat16, dev) if (keep_full or not pool) else None
+    pooled = _empty_nhwc(b, h // 2, w // 2, c, torch.bfloat16, dev) if pool else None
     stats = torch.empty((4, c), dtype=torch.float32, device=dev)              # mean | invstd | scale | shift
     partial = torch.empty((nb, 3, c), dtype=torch.float32, device=dev)
     launch("ssdhip_bn_elu_train_fwd_nhwc_bf16", dev, _ptr(y), _ptr(gamma), _ptr(beta), param_bf16, _ptr(running_mean), _ptr(running_var),
@@ -1965,7 +1943,7 @@ def bn_elu_train_backward(y, mean, invstd, gamma, beta, g_full, g_pooled):
     if _bn_train_vectors(c, y.device, mean=mean, invstd=invstd) != 0:
         raise SsdHipError("bn_elu_train: mean and invstd are float32")
     dev = y.device
-    dy = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=dev).permute(0, 3, 1, 2)
+    dy = _empty_nhwc(b, h, w, c, torch.bfloat16, dev)
     grads = torch.empty((2, c), dtype=torch.float32, device=dev)              # dgamma | dbeta
     partial = torch.empty((nb, 2, c), dtype=torch.float32, device=dev)
     launch("ssdhip_bn_elu_train_bwd_nhwc_bf16", dev, _ptr(y), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta), param_bf16, _ptr(g_full),
@@ -1983,13 +1961,12 @@ def conv1_block(x, w1, b1, weight, bias, relu=True, pool=False):
     if not x.permute(0, 2, 3, 1).is_contiguous():
         x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
     b, _, h, w = x.shape
-    if tuple(w1.shape) != (64, 3, 3, 3) or weight.shape[1:] != (64, 3, 3) or w1.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
-        raise SsdHipError("conv1_block needs bfloat16 (64, 3, 3, 3) and (Cout, 64, 3, 3) weights")
-    cl = lambda t: t if t.permute(0, 2, 3, 1).is_contiguous() else t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    w1c, w2c = cl(w1), cl(weight)
+    ok = tuple(w1.shape) == (64, 3, 3, 3) and weight.shape[1:] == (64, 3, 3) and w1.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+    w1c = _filter_nhwc(w1, ok, "conv1_block needs bfloat16 (64, 3, 3, 3) and (Cout, 64, 3, 3) weights")
+    w2c = _filter_nhwc(weight)
     cout = weight.shape[0]
     ho, wo = ((h + 1) // 2, (w + 1) // 2) if pool else (h, w)
-    y = torch.empty((b, ho, wo, cout), dtype=torch.bfloat16, device=x.device).permute(0, 3, 1, 2)
+    y = _empty_nhwc(b, ho, wo, cout, torch.bfloat16, x.device)
     dev = x.device
     n_cu = _CU_COUNT.get(dev.index)
     if n_cu is None:

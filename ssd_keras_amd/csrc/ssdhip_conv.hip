@@ -1077,167 +1077,162 @@ __global__ __launch_bounds__(C1_BP) void conv3x3_cin3_kernel(const bf16_t* __res
 
 using namespace ssdhip;
 
-static int conv_run(int variant, const void* x, const void* weight, const void* bias, void* y, int B, int H, int W,
-                    int Cin, int Cout, int kernel, int dilation, int relu, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || dilation <= 0 || dilation > 8) return SSDHIP_E_BADARG;
-    if (kernel != 1 && kernel != 3) return SSDHIP_E_BADARG;
-    if (Cin <= 0 || (Cin % CONV_BK) || Cout <= 0 || (Cout % 64)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 7)) return SSDHIP_E_BADARG;
-    const long long M = (long long)B * H * W;
-    if (M * (long long)(Cin > Cout ? Cin : Cout) > 0x7fffffff0LL || M > 0x7fffff00LL) return SSDHIP_E_BADARG;
-    ConvParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y);
-    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = kernel; p.dil = dilation; p.relu = relu ? 1 : 0;
-    p.M = (int)M;
-    p.Ho = p.Wo = p.WT = p.HT = p.cshift = 0;
-    p.stride = 1; p.coff = 0; p.Min = (int)M;
-    const bool wide = (Cout % 128) == 0;
-    p.n_tiles = Cout / (wide ? 128 : 64);
-    const bool small = M * Cin * 2 + 4LL * (dilation * W + dilation) * Cin < 0x7ffff000LL && (long long)Cout * kernel * kernel * Cin * 2 < 0x7ffff000LL;
-    if (variant == 4 && !small) variant = 1;  // buffer addressing needs 31-bit byte offsets
-    if ((variant == 5 || variant == 6) && !small) variant = 1;
-    if (variant == 5 || variant == 6) {       // multi-stage LDS ring: 5 = four 16 KB stages (2 WG/CU), 6 = three (3 WG/CU)
-        p.m_tiles = (int)((M + CONV_BP - 1) / CONV_BP);
-        const int grid = ((p.m_tiles + 7) / 8) * p.n_tiles * 8;
-        if (variant == 5) {
-            if (wide) hipLaunchKernelGGL((conv_igemm5_kernel<128, 4>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-            else hipLaunchKernelGGL((conv_igemm5_kernel<64, 4>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        } else {
-            if (wide) hipLaunchKernelGGL((conv_igemm5_kernel<128, 3>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-            else hipLaunchKernelGGL((conv_igemm5_kernel<64, 3>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        }
-    } else if (variant == 4) {                // v1's tile with buffer-addressed LDS-DMA and batched fragment reads
-        p.m_tiles = (int)((M + CONV_BP - 1) / CONV_BP);
-        const int grid = ((p.m_tiles + 7) / 8) * p.n_tiles * 8;
-        if (wide) hipLaunchKernelGGL(conv_igemm4_kernel<128>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL(conv_igemm4_kernel<64>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    } else {                                  // variant 1: per-lane 64-bit addressing, the fallback for tensors beyond 2 GiB
-        p.m_tiles = (int)((M + CONV_BP - 1) / CONV_BP);
-        const int grid = ((p.m_tiles + 7) / 8) * p.n_tiles * 8;
-        if (wide) hipLaunchKernelGGL(conv_igemm_kernel<128>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL(conv_igemm_kernel<64>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
+// ---- The host side of every implicit-GEMM entry: conv_geometry checks a geometry, conv_params checks the pointers and the byte
+// limits of a FORM of the kernel and fills ConvParams, conv_launch picks the channel tile.  An entry says what differs -- its form --
+// and which kernel it launches.
+//
+// All forms take the general geometry (torch.nn.Conv2d semantics): stride >= 1 and zero padding 0 <= pad <= reach = (kernel/2) *
+// dilation on every side,
+//   y[b,ho,wo,co] = act(bias[co] + sum x[b, ho*stride - pad + kh*dil, wo*stride - pad + kw*dil, ci] * w[co,kh,kw,ci]),
+//   Ho = (H + 2*pad - dil*(kernel-1) - 1) / stride + 1 (same for Wo);
+// a 'same' entry is stride = 1, pad = reach.  What differs between the forms is data (ConvForm), not code:
+//   bias_align  the bias is read 4 bf16 values at a time (8 bytes), as float32 (X3: 4) or one value at a time by the split-K
+//               reduction (2);
+//   out_limit   M max(K channels, Cout) must not exceed it: the output index of the bf16 forms (0x7fffffff0), of the X3 form's
+//               wider rows (0x3fffffff0); the pooled bf16 form has never had one (0);
+//   pool        MaxPooling2D(2, 2, 'same') fused: stride 1 and pad = reach only, tiles from conv_pool_tiles;
+//   ws          split-K: the float32 workspace (16-byte aligned like the maps); bias and activation belong to the reduction;
+//   x3          the reference-precision form: x rows hold 2 C float16 channels, the K loop walks 3 C, float32 bias, oscale > 0.
+// Buffer addressing needs 31-bit byte offsets into x (with the rows a tile's taps reach past its end) and w.  Only the plain 'same'
+// entries accept more (`beyond`): they hand such a call to variant 1, the kernel with per-lane 64-bit addresses.
+struct ConvForm {
+    int bias_align;
+    long long out_limit;
+    bool pool = false;
+    const void* ws = nullptr;
+    bool splitk = false, x3 = false;
+    int out_f32 = 0;
+    float oscale = 1.f;
+};
+static const ConvForm CONV_PLAIN = {8, 0x7fffffff0LL}, CONV_POOLED = {8, 0, true};
+
+struct ConvGeom {
+    int reach, Ho, Wo;
+    long long Min, M;                                     // input and output pixels
+};
+
+static int conv_same_pad(int kernel, int dilation) { return kernel == 3 ? dilation : 0; }   // reach of the kernels there are
+
+static bool conv_geometry(ConvGeom& g, int B, int H, int W, int Cin, int Cout, int kernel, int stride, int pad, int dilation) {
+    if (B <= 0 || H <= 0 || W <= 0 || dilation <= 0 || dilation > 8 || (kernel != 1 && kernel != 3) || stride < 1 || stride > 4) return false;
+    g.reach = (kernel / 2) * dilation;
+    if (pad < 0 || pad > g.reach || Cin <= 0 || (Cin % CONV_BK) || Cout <= 0 || (Cout % 64)) return false;
+    if (H + 2 * pad - 2 * g.reach < 1 || W + 2 * pad - 2 * g.reach < 1) return false;
+    g.Ho = (H + 2 * pad - 2 * g.reach - 1) / stride + 1; g.Wo = (W + 2 * pad - 2 * g.reach - 1) / stride + 1;
+    g.Min = (long long)B * H * W; g.M = (long long)B * g.Ho * g.Wo;
+    return true;
+}
+
+// Tiles of the pooled forms: (64 >> cshift) row pairs x (1 << cshift) columns, the shape with the smallest padded area; false: more
+// tiles than the workgroup index holds
+static bool conv_pool_tiles(ConvParams& p, int B) {
+    p.Ho = (p.H + 1) / 2; p.Wo = (p.W + 1) / 2;
+    long long best = -1;
+    for (int cs = 6; cs >= 1; --cs) {
+        const long long wt = (p.W + (1 << cs) - 1) >> cs, ht = (p.Ho + (64 >> cs) - 1) / (64 >> cs);
+        if (best < 0 || wt * ht < best) { best = wt * ht; p.cshift = cs; p.WT = (int)wt; p.HT = (int)ht; }
     }
+    const long long mt = (long long)B * p.HT * p.WT;
+    if (mt > 0x3fffffffLL / p.n_tiles) return false;
+    p.m_tiles = (int)mt;
+    return true;
+}
+
+// SSDHIP_E_BADARG or a filled `p`.  C: the channels of x (X3: of the float32 map it stands for).
+static int conv_params(ConvParams& p, const ConvForm& f, const void* x, const void* weight, const void* bias, void* y, int B, int H, int W,
+                       int C, int Cout, int kernel, int stride, int pad, int dilation, int relu, bool* beyond = nullptr) {
+    ConvGeom g;
+    if (!x || !weight || !y || !conv_geometry(g, B, H, W, C, Cout, kernel, stride, pad, dilation)) return SSDHIP_E_BADARG;
+    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)f.ws) & 15 || ((uintptr_t)bias & (f.bias_align - 1))) return SSDHIP_E_BADARG;
+    if ((f.splitk && !f.ws) || (f.x3 && !(f.oscale > 0.f)) || (f.pool && (stride != 1 || pad != g.reach))) return SSDHIP_E_BADARG;
+    const int xC = f.x3 ? 2 * C : C, Kc = f.x3 ? 3 * C : C;
+    const bool small = g.Min * xC * 2 + 4LL * (dilation * W + dilation) * xC < 0x7ffff000LL && (long long)Cout * kernel * kernel * Kc * 2 < 0x7ffff000LL;
+    if (beyond) *beyond = !small;
+    else if (!small) return SSDHIP_E_BADARG;
+    if (f.out_limit && (g.M * (Kc > Cout ? Kc : Cout) > f.out_limit || g.M > 0x7fffff00LL)) return SSDHIP_E_BADARG;
+    p = {};
+    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight);
+    p.bias = f.x3 || f.splitk ? nullptr : static_cast<const bf16_t*>(bias);
+    p.y = f.splitk ? nullptr : static_cast<bf16_t*>(y);
+    p.H = H; p.W = W; p.Cin = Kc; p.Cout = Cout; p.KS = kernel; p.dil = dilation; p.relu = relu && !f.splitk ? 1 : 0;
+    p.M = (int)g.M; p.Min = (int)g.Min;
+    p.Ho = g.Ho; p.Wo = g.Wo;
+    p.stride = stride; p.coff = g.reach - pad;
+    p.ksplit = 1; p.slab = static_cast<float*>(const_cast<void*>(f.ws));
+    p.xC = xC; p.out_f32 = f.out_f32 ? 1 : 0; p.bias32 = f.x3 ? static_cast<const float*>(bias) : nullptr; p.oscale = f.oscale;
+    p.n_tiles = Cout / ((Cout % 128) == 0 ? 128 : 64);
+    if (f.pool) return conv_pool_tiles(p, B) ? SSDHIP_OK : SSDHIP_E_BADARG;
+    p.m_tiles = (int)((g.M + CONV_BP - 1) / CONV_BP);
+    return SSDHIP_OK;
+}
+
+// workgroups of a launch: the XCD-aware tile map deals pixel tiles in eights (x K ranges of the split-K form)
+static int conv_grid(const ConvParams& p) { return ((p.m_tiles + 7) / 8) * p.n_tiles * 8 * p.ksplit; }
+
+// 128 output channels per tile where Cout is a multiple of 128, else 64
+static int conv_launch(void (*k128)(ConvParams), void (*k64)(ConvParams), const ConvParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL((p.Cout % 128) == 0 ? k128 : k64, dim3(conv_grid(p)), dim3(CONV_THREADS), 0, stream, p);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// The plain forms by kernel variant: 4 the shipped kernel (two LDS stages, buffer-addressed LDS-DMA, batched fragment reads), 5 / 6 the
+// multi-stage LDS ring of 32-channel slices (5 = four 16 KB stages, loads three steps ahead, 2 WG/CU; 6 = three, 3 WG/CU), 1 their
+// predecessor with per-lane 64-bit addressing: the fallback for tensors beyond 2 GiB, which only a 'same' call may bring.
+static int conv_run(int variant, bool same, const void* x, const void* weight, const void* bias, void* y, int B, int H, int W, int Cin,
+                    int Cout, int kernel, int stride, int pad, int dilation, int relu, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    ConvParams p;
+    bool beyond = false;
+    if (int rc = conv_params(p, CONV_PLAIN, x, weight, bias, y, B, H, W, Cin, Cout, kernel, stride, pad, dilation, relu, same ? &beyond : nullptr))
+        return rc;
+    if (beyond) variant = 1;
+    if (variant == 5) return conv_launch(conv_igemm5_kernel<128, 4>, conv_igemm5_kernel<64, 4>, p, stream);
+    if (variant == 6) return conv_launch(conv_igemm5_kernel<128, 3>, conv_igemm5_kernel<64, 3>, p, stream);
+    if (variant == 4) return conv_launch(conv_igemm4_kernel<128>, conv_igemm4_kernel<64>, p, stream);
+    return conv_launch(conv_igemm_kernel<128>, conv_igemm_kernel<64>, p, stream);
 }
 
 // y[b,h,w,co] = act(bias[co] + sum_{kh,kw,ci} x[b, h + (kh-k/2)*dil, w + (kw-k/2)*dil, ci] * w[co,kh,kw,ci]), zero padding.
 extern "C" int ssdhip_conv2d_same_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W,
                                             int Cin, int Cout, int kernel, int dilation, int relu, void* stream) {
-    return conv_run(4, x, weight, bias, y, B, H, W, Cin, Cout, kernel, dilation, relu, stream);
-}
-
-// General form: stride >= 1 and zero padding 0 <= pad <= (kernel/2)*dilation on every side (torch.nn.Conv2d semantics):
-//   y[b,ho,wo,co] = act(bias[co] + sum x[b, ho*stride - pad + kh*dil, wo*stride - pad + kw*dil, ci] * w[co,kh,kw,ci]),
-//   Ho = (H + 2*pad - dil*(kernel-1) - 1) / stride + 1 (same for Wo).
-// The SSD extra layers: conv6_2 / conv7_2 (ZeroPadding2D(1) + 3x3 stride 2, models/keras_ssd300.py:302-307) and conv8_2 /
-// conv9_2 (3x3 'valid', :310-313).  Same kernel as the 'same' convolution: only the tile prologue's pixel -> address map differs.
-static int conv_general_run(int variant, const void* x, const void* weight, const void* bias, void* y, int B, int H, int W, int Cin,
-                            int Cout, int kernel, int stride, int pad, int dilation, int relu, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || dilation <= 0 || dilation > 8) return SSDHIP_E_BADARG;
-    if ((kernel != 1 && kernel != 3) || stride < 1 || stride > 4) return SSDHIP_E_BADARG;
-    const int reach = (kernel / 2) * dilation;
-    if (pad < 0 || pad > reach) return SSDHIP_E_BADARG;
-    if (Cin <= 0 || (Cin % CONV_BK) || Cout <= 0 || (Cout % 64)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 7)) return SSDHIP_E_BADARG;
-    const int Ho = (H + 2 * pad - 2 * reach - 1) / stride + 1, Wo = (W + 2 * pad - 2 * reach - 1) / stride + 1;
-    if (H + 2 * pad - 2 * reach < 1 || W + 2 * pad - 2 * reach < 1) return SSDHIP_E_BADARG;
-    const long long Min = (long long)B * H * W, M = (long long)B * Ho * Wo;
-    if (Min * Cin * 2 + 4LL * (dilation * W + dilation) * Cin >= 0x7ffff000LL || (long long)Cout * kernel * kernel * Cin * 2 >= 0x7ffff000LL ||
-        M * Cout > 0x7fffffff0LL)
-        return SSDHIP_E_BADARG;                // buffer addressing: 31-bit byte offsets
-    ConvParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y);
-    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = kernel; p.dil = dilation; p.relu = relu ? 1 : 0;
-    p.M = (int)M; p.Min = (int)Min;
-    p.Ho = Ho; p.Wo = Wo; p.WT = p.HT = p.cshift = 0;
-    p.stride = stride; p.coff = reach - pad;
-    const bool wide = (Cout % 128) == 0;
-    p.n_tiles = Cout / (wide ? 128 : 64);
-    p.m_tiles = (int)((M + CONV_BP - 1) / CONV_BP);
-    const int grid = ((p.m_tiles + 7) / 8) * p.n_tiles * 8;
-    if (variant == 5) {                        // four-stage ring of 32-channel slices: loads three steps ahead
-        if (wide) hipLaunchKernelGGL((conv_igemm5_kernel<128, 4>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL((conv_igemm5_kernel<64, 4>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    } else if (variant == 6) {
-        if (wide) hipLaunchKernelGGL((conv_igemm5_kernel<128, 3>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL((conv_igemm5_kernel<64, 3>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    } else {
-        if (wide) hipLaunchKernelGGL(conv_igemm4_kernel<128>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL(conv_igemm4_kernel<64>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    }
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    return conv_run(4, true, x, weight, bias, y, B, H, W, Cin, Cout, kernel, 1, conv_same_pad(kernel, dilation), dilation, relu, stream);
 }
 
 // Split-K form of ssdhip_conv2d_nhwc_bf16 for layers with a handful of tiles (the SSD extra layers conv6_1 ... conv9_2,
 // models/keras_ssd300.py:301-313): `ksplit` K ranges per tile (0: chosen so that the launch has about one workgroup per CU)
 // write float32 partial tiles to the caller's workspace, a second launch adds them in order and applies bias / activation.
-static int splitk_choose(long long tiles, int T) {       // about 200 workgroups, at most 12 ranges (every range is a float32 copy of the output)
-    long long ks = (200 + tiles - 1) / tiles;
-    if (ks > T) ks = T;
-    if (ks > 12) ks = 12;
-    return ks < 1 ? 1 : (int)ks;
-}
-static bool splitk_geometry(int B, int H, int W, int Cin, int Cout, int kernel, int stride, int pad, int dilation, long long* M_out, int* T_out,
-                            long long* tiles_out) {
-    if (B <= 0 || H <= 0 || W <= 0 || dilation <= 0 || dilation > 8 || (kernel != 1 && kernel != 3) || stride < 1 || stride > 4) return false;
-    const int reach = (kernel / 2) * dilation;
-    if (pad < 0 || pad > reach || Cin <= 0 || (Cin % CONV_BK) || Cout <= 0 || (Cout % 64)) return false;
-    if (H + 2 * pad - 2 * reach < 1 || W + 2 * pad - 2 * reach < 1) return false;
-    const int Ho = (H + 2 * pad - 2 * reach - 1) / stride + 1, Wo = (W + 2 * pad - 2 * reach - 1) / stride + 1;
-    *M_out = (long long)B * Ho * Wo;
-    *T_out = kernel * kernel * (Cin / CONV_BK);
-    *tiles_out = ((*M_out + CONV_BP - 1) / CONV_BP) * (Cout / ((Cout % 128) == 0 ? 128 : 64));
-    return true;
+// K ranges of a call: about 200 workgroups, at most 12 ranges (every range is a float32 copy of the output) and at most the K steps
+static int splitk_ranges(long long M, int Cin, int Cout, int kernel, int ksplit) {
+    const int T = kernel * kernel * (Cin / CONV_BK);
+    const long long tiles = ((M + CONV_BP - 1) / CONV_BP) * (Cout / ((Cout % 128) == 0 ? 128 : 64));
+    if (ksplit <= 0) {
+        const long long ks = (200 + tiles - 1) / tiles;
+        ksplit = ks > 12 ? 12 : (ks < 1 ? 1 : (int)ks);
+    }
+    return ksplit > T ? T : ksplit;
 }
 
 extern "C" size_t ssdhip_conv2d_splitk_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kernel, int stride, int pad, int dilation,
                                                        int ksplit) {
-    long long M, tiles;
-    int T;
-    if (!splitk_geometry(B, H, W, Cin, Cout, kernel, stride, pad, dilation, &M, &T, &tiles)) return 0;
-    if (ksplit <= 0) ksplit = splitk_choose(tiles, T);
-    if (ksplit > T) ksplit = T;
-    return (size_t)ksplit * (size_t)M * (size_t)Cout * sizeof(float);
+    ConvGeom g;
+    if (!conv_geometry(g, B, H, W, Cin, Cout, kernel, stride, pad, dilation)) return 0;
+    return (size_t)splitk_ranges(g.M, Cin, Cout, kernel, ksplit) * (size_t)g.M * (size_t)Cout * sizeof(float);
 }
 
 extern "C" int ssdhip_conv2d_splitk_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W, int Cin,
                                               int Cout, int kernel, int stride, int pad, int dilation, int relu, int ksplit, void* ws,
                                               size_t ws_bytes, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    long long M, tiles;
-    int T;
-    if (!x || !weight || !y || !ws || !splitk_geometry(B, H, W, Cin, Cout, kernel, stride, pad, dilation, &M, &T, &tiles)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)ws) & 15 || ((uintptr_t)bias & 1)) return SSDHIP_E_BADARG;
-    const int reach = (kernel / 2) * dilation;
-    const long long Min = (long long)B * H * W;
-    if (Min * Cin * 2 + 4LL * (dilation * W + dilation) * Cin >= 0x7ffff000LL || (long long)Cout * kernel * kernel * Cin * 2 >= 0x7ffff000LL ||
-        M * Cout > 0x7fffffff0LL)
-        return SSDHIP_E_BADARG;                // buffer addressing: 31-bit byte offsets
-    if (ksplit <= 0) ksplit = splitk_choose(tiles, T);
-    if (ksplit > T) ksplit = T;
-    if (ws_bytes < (size_t)ksplit * (size_t)M * (size_t)Cout * sizeof(float)) return SSDHIP_E_WORKSPACE;
+    ConvForm f = {2, 0x7fffffff0LL};
+    f.splitk = true; f.ws = ws;
     ConvParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = nullptr;
-    p.y = nullptr;
-    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = kernel; p.dil = dilation; p.relu = 0;
-    p.M = (int)M; p.Min = (int)Min;
-    p.Ho = (H + 2 * pad - 2 * reach - 1) / stride + 1; p.Wo = (W + 2 * pad - 2 * reach - 1) / stride + 1; p.WT = p.HT = p.cshift = 0;
-    p.stride = stride; p.coff = reach - pad;
-    p.ksplit = ksplit; p.slab = static_cast<float*>(ws);
-    const bool wide = (Cout % 128) == 0;
-    p.n_tiles = Cout / (wide ? 128 : 64);
-    p.m_tiles = (int)((M + CONV_BP - 1) / CONV_BP);
-    const int grid = ((p.m_tiles + 7) / 8) * p.n_tiles * 8 * ksplit;
-    if (wide) hipLaunchKernelGGL(conv_igemm4_splitk_kernel<128>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL(conv_igemm4_splitk_kernel<64>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
-    const long long n8 = M * Cout / 8;
+    if (int rc = conv_params(p, f, x, weight, bias, y, B, H, W, Cin, Cout, kernel, stride, pad, dilation, relu)) return rc;
+    p.ksplit = splitk_ranges(p.M, Cin, Cout, kernel, ksplit);
+    if (ws_bytes < (size_t)p.ksplit * (size_t)p.M * (size_t)Cout * sizeof(float)) return SSDHIP_E_WORKSPACE;
+    if (int rc = conv_launch(conv_igemm4_splitk_kernel<128>, conv_igemm4_splitk_kernel<64>, p, stream)) return rc;
+    const long long n8 = (long long)p.M * Cout / 8;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, p.slab, static_cast<const bf16_t*>(bias),
-                       static_cast<bf16_t*>(y), (int)M, Cout, ksplit, relu ? 1 : 0);
+                       static_cast<bf16_t*>(y), p.M, Cout, p.ksplit, relu ? 1 : 0);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 
@@ -1248,54 +1243,19 @@ extern "C" int ssdhip_conv2d_x3_nhwc_f16(const void* x, const void* weight, cons
                                          int kernel, int stride, int pad, int dilation, int relu, int pool, int out_f32, float oscale,
                                          void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || dilation <= 0 || dilation > 8) return SSDHIP_E_BADARG;
-    if ((kernel != 1 && kernel != 3) || stride < 1 || stride > 4 || !(oscale > 0.f)) return SSDHIP_E_BADARG;
-    const int reach = (kernel / 2) * dilation;
-    if (pad < 0 || pad > reach || C <= 0 || (C % CONV_BK) || Cout <= 0 || (Cout % 64)) return SSDHIP_E_BADARG;
-    if (pool && (stride != 1 || pad != reach)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 3)) return SSDHIP_E_BADARG;
-    if (H + 2 * pad - 2 * reach < 1 || W + 2 * pad - 2 * reach < 1) return SSDHIP_E_BADARG;
-    const int Ho = (H + 2 * pad - 2 * reach - 1) / stride + 1, Wo = (W + 2 * pad - 2 * reach - 1) / stride + 1;
-    const long long Min = (long long)B * H * W, M = (long long)B * Ho * Wo;
-    if (Min * 2 * C * 2 + 4LL * (dilation * W + dilation) * 2 * C >= 0x7ffff000LL || (long long)Cout * kernel * kernel * 3 * C * 2 >= 0x7ffff000LL ||
-        M * Cout > 0x3fffffff0LL)
-        return SSDHIP_E_BADARG;                // buffer addressing: 31-bit byte offsets
+    ConvForm f = {4, 0x3fffffff0LL, pool != 0};
+    f.x3 = true; f.out_f32 = out_f32; f.oscale = oscale;
     ConvParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = nullptr;
-    p.y = static_cast<bf16_t*>(y);
-    p.H = H; p.W = W; p.Cin = 3 * C; p.Cout = Cout; p.KS = kernel; p.dil = dilation; p.relu = relu ? 1 : 0;
-    p.M = (int)M; p.Min = (int)Min;
-    p.Ho = Ho; p.Wo = Wo; p.WT = p.HT = p.cshift = 0;
-    p.stride = stride; p.coff = reach - pad;
-    p.ksplit = 1; p.slab = nullptr;
-    p.xC = 2 * C; p.out_f32 = out_f32 ? 1 : 0; p.bias32 = bias; p.oscale = oscale;
-    const bool wide = (Cout % 128) == 0;
-    p.n_tiles = Cout / (wide ? 128 : 64);
-    if (pool) {
-        p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-        long long best = -1;                  // tile shape (64 >> cs row pairs x 1 << cs columns) with the smallest padded area
-        for (int cs = 6; cs >= 1; --cs) {
-            const long long wt = (W + (1 << cs) - 1) >> cs, ht = (p.Ho + (64 >> cs) - 1) / (64 >> cs);
-            if (best < 0 || wt * ht < best) { best = wt * ht; p.cshift = cs; p.WT = (int)wt; p.HT = (int)ht; }
-        }
-        const long long mt = (long long)B * p.HT * p.WT;
-        if (mt > 0x3fffffffLL / p.n_tiles) return SSDHIP_E_BADARG;
-        p.m_tiles = (int)mt;
-        const int grid = ((p.m_tiles + 7) / 8) * p.n_tiles * 8;
-        if (wide) hipLaunchKernelGGL((conv_igemm4_x3_kernel<128, true>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL((conv_igemm4_x3_kernel<64, true>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    } else {
-        p.m_tiles = (int)((M + CONV_BP - 1) / CONV_BP);
-        const int grid = ((p.m_tiles + 7) / 8) * p.n_tiles * 8;
-        if (wide) hipLaunchKernelGGL((conv_igemm4_x3_kernel<128, false>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL((conv_igemm4_x3_kernel<64, false>), dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    }
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    if (int rc = conv_params(p, f, x, weight, bias, y, B, H, W, C, Cout, kernel, stride, pad, dilation, relu)) return rc;
+    if (pool) return conv_launch(conv_igemm4_x3_kernel<128, true>, conv_igemm4_x3_kernel<64, true>, p, stream);
+    return conv_launch(conv_igemm4_x3_kernel<128, false>, conv_igemm4_x3_kernel<64, false>, p, stream);
 }
 
+// The general form.  The SSD extra layers: conv6_2 / conv7_2 (ZeroPadding2D(1) + 3x3 stride 2, models/keras_ssd300.py:302-307) and
+// conv8_2 / conv9_2 (3x3 'valid', :310-313).  Same kernel as the 'same' convolution: only the tile prologue's pixel -> address map differs.
 extern "C" int ssdhip_conv2d_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W, int Cin,
                                        int Cout, int kernel, int stride, int pad, int dilation, int relu, void* stream) {
-    return conv_general_run(4, x, weight, bias, y, B, H, W, Cin, Cout, kernel, stride, pad, dilation, relu, stream);
+    return conv_run(4, false, x, weight, bias, y, B, H, W, Cin, Cout, kernel, stride, pad, dilation, relu, stream);
 }
 
 // The same with an explicit kernel variant: 4 the default (two LDS stages), 5 / 6 the multi-stage ring (loads three / two steps
@@ -1304,7 +1264,7 @@ extern "C" int ssdhip_conv2d_nhwc_bf16_variant(int variant, const void* x, const
                                                int W, int Cin, int Cout, int kernel, int stride, int pad, int dilation, int relu,
                                                void* stream) {
     if (variant != 4 && variant != 5 && variant != 6) return SSDHIP_E_BADARG;
-    return conv_general_run(variant, x, weight, bias, y, B, H, W, Cin, Cout, kernel, stride, pad, dilation, relu, stream);
+    return conv_run(variant, false, x, weight, bias, y, B, H, W, Cin, Cout, kernel, stride, pad, dilation, relu, stream);
 }
 
 // Profiling aid: the same with an explicit kernel variant (4: the shipped kernel; 1: its predecessor with per-lane
@@ -1318,42 +1278,17 @@ extern "C" int ssdhip_conv2d_same_nhwc_bf16_variant(int variant, const void* x, 
         return ssdhip_conv3x3_halo_nhwc_bf16(x, weight, bias, y, B, H, W, Cin, Cout, relu, 0, stream);
     }
     if (variant != 1 && variant != 4 && variant != 5 && variant != 6) return SSDHIP_E_BADARG;
-    return conv_run(variant, x, weight, bias, y, B, H, W, Cin, Cout, kernel, dilation, relu, stream);
+    return conv_run(variant, true, x, weight, bias, y, B, H, W, Cin, Cout, kernel, 1, conv_same_pad(kernel, dilation), dilation, relu, stream);
 }
 
 // Conv2D(k x k, padding='same', activation='relu') followed by MaxPooling2D(2, 2, padding='same') as ONE kernel
 // (models/keras_ssd300.py:274-283 conv1_2 -> pool1 and twins): y [B, ceil(H/2), ceil(W/2), Cout].
 extern "C" int ssdhip_conv2d_same_pool2_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W,
                                                   int Cin, int Cout, int kernel, int dilation, int relu, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || dilation <= 0 || dilation > 8) return SSDHIP_E_BADARG;
-    if (kernel != 1 && kernel != 3) return SSDHIP_E_BADARG;
-    if (Cin <= 0 || (Cin % CONV_BK) || Cout <= 0 || (Cout % 64)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 7)) return SSDHIP_E_BADARG;
-    const long long M = (long long)B * H * W;
-    if (M * Cin * 2 + 4LL * (dilation * W + dilation) * Cin >= 0x7ffff000LL || (long long)Cout * kernel * kernel * Cin * 2 >= 0x7ffff000LL)
-        return SSDHIP_E_BADARG;
     ConvParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y);
-    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = kernel; p.dil = dilation; p.relu = relu ? 1 : 0;
-    p.M = (int)M;
-    p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-    p.stride = 1; p.coff = 0; p.Min = (int)M;
-    long long best = -1;                      // tile shape (64 >> cs row pairs x 1 << cs columns) with the smallest padded area
-    for (int cs = 6; cs >= 1; --cs) {
-        const long long wt = (W + (1 << cs) - 1) >> cs, ht = (p.Ho + (64 >> cs) - 1) / (64 >> cs);
-        if (best < 0 || wt * ht < best) { best = wt * ht; p.cshift = cs; p.WT = (int)wt; p.HT = (int)ht; }
-    }
-    const bool wide = (Cout % 128) == 0;
-    p.n_tiles = Cout / (wide ? 128 : 64);
-    const long long mt = (long long)B * p.HT * p.WT;
-    if (mt > 0x3fffffffLL / p.n_tiles) return SSDHIP_E_BADARG;
-    p.m_tiles = (int)mt;
-    const int grid = ((p.m_tiles + 7) / 8) * p.n_tiles * 8;
-    if (wide) hipLaunchKernelGGL(conv_igemm4_pool_kernel<128>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL(conv_igemm4_pool_kernel<64>, dim3(grid), dim3(CONV_THREADS), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    if (int rc = conv_params(p, CONV_POOLED, x, weight, bias, y, B, H, W, Cin, Cout, kernel, 1, conv_same_pad(kernel, dilation), dilation, relu))
+        return rc;
+    return conv_launch(conv_igemm4_pool_kernel<128>, conv_igemm4_pool_kernel<64>, p, static_cast<hipStream_t>(stream_));
 }
 
 // n_problems independent 'same' convolutions (no pooling) in one launch; arrays are HOST arrays of per-problem arguments.
@@ -1365,36 +1300,21 @@ extern "C" int ssdhip_conv2d_same_group_nhwc_bf16(int n_problems, const void* co
     if (n_problems <= 0 || n_problems > CONV_MAX_GROUP || !x_h || !weight_h || !y_h || !B_h || !H_h || !W_h || !Cin_h || !Cout_h ||
         !kernel_h || !dilation_h)
         return SSDHIP_E_BADARG;
-    ConvGroup g;
+    ConvGroup g = {};
     g.n = n_problems;
     long long blocks = 0;
-    for (int k = 0; k < CONV_MAX_GROUP; ++k) {
+    for (int k = 0; k < n_problems; ++k) {
         g.first_block[k] = (int)blocks;
-        if (k >= n_problems) { g.p[k] = g.p[0]; continue; }
-        const int B = B_h[k], H = H_h[k], W = W_h[k], Cin = Cin_h[k], Cout = Cout_h[k], ks = kernel_h[k], dil = dilation_h[k];
-        const void* bias = bias_h ? bias_h[k] : nullptr;
-        if (!x_h[k] || !weight_h[k] || !y_h[k] || B <= 0 || H <= 0 || W <= 0 || dil <= 0 || dil > 8 || (ks != 1 && ks != 3))
-            return SSDHIP_E_BADARG;
-        if (Cin <= 0 || (Cin % CONV_BK) || Cout <= 0 || (Cout % 64)) return SSDHIP_E_BADARG;
-        if (((uintptr_t)x_h[k] | (uintptr_t)weight_h[k] | (uintptr_t)y_h[k]) & 15 || ((uintptr_t)bias & 7)) return SSDHIP_E_BADARG;
-        const long long M = (long long)B * H * W;
-        if (M * Cin * 2 + 4LL * (dil * W + dil) * Cin >= 0x7ffff000LL || (long long)Cout * ks * ks * Cin * 2 >= 0x7ffff000LL ||
-            M * Cout > 0x7fffffff0LL)
-            return SSDHIP_E_BADARG;
-        ConvParams& p = g.p[k];
-        p.x = static_cast<const bf16_t*>(x_h[k]); p.w = static_cast<const bf16_t*>(weight_h[k]); p.bias = static_cast<const bf16_t*>(bias);
-        p.y = static_cast<bf16_t*>(y_h[k]);
-        p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KS = ks; p.dil = dil; p.relu = relu ? 1 : 0;
-        p.M = (int)M;
-        p.Ho = p.Wo = p.WT = p.HT = p.cshift = 0;
-        p.stride = 1; p.coff = 0; p.Min = (int)M;
-        p.n_tiles = (Cout % 128 == 0) ? Cout / 128 : Cout / 64;
-        p.m_tiles = (int)((M + CONV_BP - 1) / CONV_BP);
-        blocks += (long long)((p.m_tiles + 7) / 8) * p.n_tiles * 8;
+        if (int rc = conv_params(g.p[k], CONV_PLAIN, x_h[k], weight_h[k], bias_h ? bias_h[k] : nullptr, y_h[k], B_h[k], H_h[k], W_h[k], Cin_h[k],
+                                 Cout_h[k], kernel_h[k], 1, conv_same_pad(kernel_h[k], dilation_h[k]), dilation_h[k], relu))
+            return rc;
+        blocks += conv_grid(g.p[k]);
         if (blocks > 0x3fffffffLL) return SSDHIP_E_BADARG;
     }
-    g.first_block[CONV_MAX_GROUP] = (int)blocks;
-    for (int k = n_problems; k < CONV_MAX_GROUP; ++k) g.first_block[k] = (int)blocks;
+    for (int k = n_problems; k <= CONV_MAX_GROUP; ++k) {
+        g.first_block[k] = (int)blocks;
+        if (k < CONV_MAX_GROUP) g.p[k] = g.p[0];
+    }
     hipLaunchKernelGGL(conv_igemm4_group_kernel, dim3((unsigned)blocks), dim3(CONV_THREADS), 0, stream, g);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }

@@ -747,40 +747,58 @@ __global__ __launch_bounds__(FRONT ? C64_FRONT_THREADS : C64_THREADS, 1) void co
 
 using namespace ssdhip;
 
-// pool != 0: MaxPooling2D(2, 2, 'same') fused; y is [B, ceil(H/2), ceil(W/2), Cout].  n_workgroups: persistent workgroups to
-// launch (the caller passes the CU count; 0 = 256).
-static int c64_launch(const void* x, const void* weight, const void* bias, void* y, void* y2, int B, int H, int W, int Cin, int Cout, int relu,
-                      int pool, int n_workgroups, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || Cin != 64 || Cout <= 0 || (Cout % 64)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)y2) & 15 || ((uintptr_t)bias & 1)) return SSDHIP_E_BADARG;
-    if (y2 && !pool) return SSDHIP_E_BADARG;
-    const long long xb = (long long)B * H * W * 128, wb = (long long)Cout * 1152;
-    if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || (long long)B * H * W * Cout > 0x7fffffff0LL) return SSDHIP_E_BADARG;
-    C64Params p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y);
+// ---- ONE place that checks a call of the Cin = 64 kernel and fills C64Params, with the plan of the launch: the tile shape `cs`
+// (16 x 8 or 8 x 16 pixels: the one with the fewer padded tiles), the persistent workgroups `G` (n_workgroups: the caller passes the
+// CU count; 0 = 256; a multiple of the channel slices) and the XCD mapping.  The two forms differ in their input:
+//   plain  x [B, H, W, 64] bf16 behind buffer addressing: non-null, 16-byte aligned, B H W 128 bytes within 31 bits; y2 (KEEP: the
+//          full-size map beside the pooled one, 16-byte aligned) needs pool; SSDHIP_C64_PRIO defaults to 1 (multipliers first; equal
+//          within the spread since WREG, profiles/r03zd_*);
+//   front  x = the [B, H, W, 3] image of the fused first block, read 2 bytes at a time like w1 / b1 (2-byte aligned), 6 bytes per
+//          pixel within 31 bits; SSDHIP_C64_PRIO defaults to 3 (bit 0: multipliers above the producers; bit 1: the producers' own
+//          MFMAs above everything).
+static int c64_params(C64Params& p, int& cs, int& G, bool front, const void* x, const void* w1, const void* b1, const void* weight,
+                      const void* bias, void* y, void* y2, int B, int H, int W, int Cout, int relu, int pool, int n_workgroups) {
+    if (!x || (front && !w1) || !weight || !y || B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (Cout % 64)) return SSDHIP_E_BADARG;
+    const uintptr_t a16 = (uintptr_t)weight | (uintptr_t)y | (uintptr_t)y2 | (front ? 0 : (uintptr_t)x);
+    const uintptr_t a2 = (uintptr_t)bias | (front ? (uintptr_t)x | (uintptr_t)w1 | (uintptr_t)b1 : 0);
+    if ((a16 & 15) || (a2 & 1) || (y2 && !pool)) return SSDHIP_E_BADARG;
+    const long long xb = (long long)B * H * W * (front ? 6 : 128), wb = (long long)Cout * 1152;
+    if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || (long long)B * H * W * Cout > 0x7fffffff0LL) return SSDHIP_E_BADARG;   // 31-bit byte offsets
+    p = {};
+    p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
+    p.y = static_cast<bf16_t*>(y); p.y2 = static_cast<bf16_t*>(y2);
+    if (front) { p.x3 = static_cast<const bf16_t*>(x); p.w1 = static_cast<const bf16_t*>(w1); p.b1 = static_cast<const bf16_t*>(b1); }
+    else { p.x = static_cast<const bf16_t*>(x); p.x_bytes = (int)xb; }
+    p.w_bytes = (int)wb;
     p.B = B; p.H = H; p.W = W; p.Cout = Cout; p.relu = relu ? 1 : 0;
     p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-    p.x_bytes = (int)xb; p.w_bytes = (int)wb;
-    p.x3 = nullptr; p.w1 = nullptr; p.b1 = nullptr;
-    p.y2 = static_cast<bf16_t*>(y2);
-    { const char* e = getenv("SSDHIP_C64_PRIO"); p.prio = e ? atoi(e) : 1; }   // multipliers first; equal within the spread since WREG (profiles/r03zd_*)
+    { const char* e = getenv("SSDHIP_C64_PRIO"); p.prio = e ? atoi(e) : (front ? 3 : 1); }
     p.n_slices = Cout / 64;
-    int cs_best = 4;
+    cs = 4;
     long long best = -1;
-    for (int cs = 4; cs >= 3; --cs) {                     // tile shape (16 x 8 or 8 x 16 pixels) with the fewer padded tiles
-        const long long wt = (W + (1 << cs) - 1) >> cs, ht = (p.Ho + (64 >> cs) - 1) / (64 >> cs);
-        if (best < 0 || wt * ht < best) { best = wt * ht; cs_best = cs; p.WT = (int)wt; p.HT = (int)ht; }
+    for (int c = 4; c >= 3; --c) {
+        const long long wt = (W + (1 << c) - 1) >> c, ht = (p.Ho + (64 >> c) - 1) / (64 >> c);
+        if (best < 0 || wt * ht < best) { best = wt * ht; cs = c; p.WT = (int)wt; p.HT = (int)ht; }
     }
     const long long tiles = (long long)B * p.HT * p.WT;
     if (tiles > 0x3fffffffLL) return SSDHIP_E_BADARG;
     p.tiles = (int)tiles;
-    int G = n_workgroups > 0 ? n_workgroups : 256;
+    G = n_workgroups > 0 ? n_workgroups : 256;
     if (G > 4096) G = 4096;
     G = (G / p.n_slices) * p.n_slices;
     if (G < p.n_slices) G = p.n_slices;
     { const char* e = getenv("SSDHIP_C64_XCD"); p.xcd_pairs = (p.n_slices > 1 && G % (8 * p.n_slices) == 0 && !(e && atoi(e) == 0)) ? 1 : 0; }
+    return SSDHIP_OK;
+}
+
+// pool != 0: MaxPooling2D(2, 2, 'same') fused; y is [B, ceil(H/2), ceil(W/2), Cout].
+static int c64_launch(const void* x, const void* weight, const void* bias, void* y, void* y2, int B, int H, int W, int Cin, int Cout, int relu,
+                      int pool, int n_workgroups, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    C64Params p;
+    int cs_best, G;
+    if (Cin != 64) return SSDHIP_E_BADARG;
+    if (int rc = c64_params(p, cs_best, G, false, x, nullptr, nullptr, weight, bias, y, y2, B, H, W, Cout, relu, pool, n_workgroups)) return rc;
     // (Round 4 tried these layers on EIGHT multiplying waves without a loader wave -- 16 x 16 tiles, every wave requesting a share of
     //  the halo between its MFMAs, stores and requests in one counted vmcnt queue: 8 % slower (the two waves of a SIMD meet at the same
     //  barrier every tile, so one's epilogue does not overlap the other's MFMAs; profiles/r04v_c64_eight_waves_negative.txt), and on a
@@ -822,34 +840,9 @@ extern "C" int ssdhip_conv3x3_c64_pool_keep_nhwc_bf16(const void* x, const void*
 extern "C" int ssdhip_conv1_block_nhwc_bf16(const void* x3, const void* w1, const void* b1, const void* weight, const void* bias, void* y,
                                             int B, int H, int W, int Cout, int relu, int pool, int n_workgroups, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x3 || !w1 || !weight || !y || B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (Cout % 64)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)weight | (uintptr_t)y) & 15 || (((uintptr_t)x3 | (uintptr_t)w1 | (uintptr_t)b1 | (uintptr_t)bias) & 1)) return SSDHIP_E_BADARG;
-    const long long wb = (long long)Cout * 1152;
-    if ((long long)B * H * W * 6 >= 0x7ffff000LL || wb >= 0x7ffff000LL || (long long)B * H * W * Cout > 0x7fffffff0LL) return SSDHIP_E_BADARG;   // 31-bit byte offsets
     C64Params p;
-    p.x = nullptr; p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y);
-    p.x3 = static_cast<const bf16_t*>(x3); p.w1 = static_cast<const bf16_t*>(w1); p.b1 = static_cast<const bf16_t*>(b1);
-    p.y2 = nullptr;
-    { const char* e = getenv("SSDHIP_C64_PRIO"); p.prio = e ? atoi(e) : 3; }   // bit 0: multipliers above the producers (equal since WREG, profiles/r03zd_*); bit 1: the producers' own MFMAs above everything
-    p.B = B; p.H = H; p.W = W; p.Cout = Cout; p.relu = relu ? 1 : 0;
-    p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-    p.x_bytes = 0; p.w_bytes = (int)wb;
-    p.n_slices = Cout / 64;
-    int cs_best = 4;
-    long long best = -1;
-    for (int cs = 4; cs >= 3; --cs) {                     // tile shape (16 x 8 or 8 x 16 pixels) with the fewer padded tiles
-        const long long wt = (W + (1 << cs) - 1) >> cs, ht = (p.Ho + (64 >> cs) - 1) / (64 >> cs);
-        if (best < 0 || wt * ht < best) { best = wt * ht; cs_best = cs; p.WT = (int)wt; p.HT = (int)ht; }
-    }
-    const long long tiles = (long long)B * p.HT * p.WT;
-    if (tiles > 0x3fffffffLL) return SSDHIP_E_BADARG;
-    p.tiles = (int)tiles;
-    int G = n_workgroups > 0 ? n_workgroups : 256;
-    if (G > 4096) G = 4096;
-    G = (G / p.n_slices) * p.n_slices;
-    if (G < p.n_slices) G = p.n_slices;
-    { const char* e = getenv("SSDHIP_C64_XCD"); p.xcd_pairs = (p.n_slices > 1 && G % (8 * p.n_slices) == 0 && !(e && atoi(e) == 0)) ? 1 : 0; }
+    int cs_best, G;
+    if (int rc = c64_params(p, cs_best, G, true, x3, w1, b1, weight, bias, y, nullptr, B, H, W, Cout, relu, pool, n_workgroups)) return rc;
     static const bool wreg = []() { const char* e = getenv("SSDHIP_C64_WREG"); return e ? atoi(e) != 0 : true; }();
 #define C64F_LAUNCH(CS_, POOL_) do { if (wreg) hipLaunchKernelGGL((conv64_kernel<CS_, POOL_, 2, true, true>), dim3(G), dim3(C64_FRONT_THREADS), 0, stream, p); \
                                      else hipLaunchKernelGGL((conv64_kernel<CS_, POOL_, 2, true>), dim3(G), dim3(C64_FRONT_THREADS), 0, stream, p); } while (0)

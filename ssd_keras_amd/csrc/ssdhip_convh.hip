@@ -69,22 +69,22 @@ constexpr int CH_WST = CH_BM * 128;                      // bytes of one weight 
 constexpr int ch_lds_bytes(int nw, int spw) { return nw * CH_WST + 2 * spw * 8192; }
 
 struct ConvHParams {
-    const bf16_t* x;             // [B, H, W, Cin]
-    const bf16_t* w;             // [Cout, 3, 3, Cin]
-    const bf16_t* bias;          // [Cout] or null
-    bf16_t* y;                   // [B, H, W, Cout]
-    int H, W, Cin, Cout, relu;
-    int Q, q_tiles, n_tiles;     // padded positions B (H+1)(W+1); tiles of 256 positions; tiles of 128 channels
-    int total_ids;               // workgroup ids that map to tiles: ceil(q_tiles / 8) * n_tiles * 8 (some of the last ones to none)
-    int HT, WT, Ho, Wo;          // 2-D tiles: tiles per image (q_tiles = B HT WT); pooled map size
-    int os, ooff, Hs, Ws;        // position grid only: output pixel (ho, wo) = the 'same' result at (ho os + ooff, wo os + ooff), map Hs x Ws
+    const bf16_t* x = nullptr;   // [B, H, W, Cin]
+    const bf16_t* w = nullptr;   // [Cout, 3, 3, Cin]
+    const bf16_t* bias = nullptr;  // [Cout] or null
+    bf16_t* y = nullptr;         // [B, H, W, Cout]
+    int H = 0, W = 0, Cin = 0, Cout = 0, relu = 0;
+    int Q = 0, q_tiles = 0, n_tiles = 0;  // padded positions B (H+1)(W+1); tiles of 256 positions; tiles of 128 channels
+    int total_ids = 0;           // workgroup ids that map to tiles: ceil(q_tiles / 8) * n_tiles * 8 (some of the last ones to none)
+    int HT = 0, WT = 0, Ho = 0, Wo = 0;   // 2-D tiles: tiles per image (q_tiles = B HT WT); pooled map size
+    int os = 1, ooff = 0, Hs = 0, Ws = 0; // position grid only: output pixel (ho, wo) = the 'same' result at (ho os + ooff, wo os + ooff), map Hs x Ws
                                  // (os = 1, ooff = 0, Hs = H, Ws = W: the plain 'same' convolution)
-    int x_bytes, w_bytes, y_bytes;
+    int x_bytes = 0, w_bytes = 0, y_bytes = 0;
     // reference-precision form (X3, see ssdhip_conv.hip conv_igemm4_body): x rows hold xC = 2 C float16 channels [hi | lo], the K loop
     // walks Cin = 3 C channels (slice j reads x slice j < nx ? j : j - nx), y rows hold 2 Cout float16 channels [hi | lo]; float32 bias
-    int xC, nx;
-    const float* bias32;
-    float oscale;
+    int xC = 0, nx = 0;
+    const float* bias32 = nullptr;
+    float oscale = 1.f;
     // 2-D tiles over the STACKED batch (round 6, fourth session; Hp > 0, pooled forms): the images are laid on top of each other at a
     // pitch of Hp rows (even, >= H + 1: at least one row of zeros between two images, row pairs aligned with every image's first row)
     // and the tile rows walk the stack -- HT = ceil(nB Hp / TR) rows of tiles for the whole batch instead of ceil(H / TR) per image.
@@ -1227,6 +1227,71 @@ static bool convh_plan_unpooled(ConvHParams& p, int B, int H, int W, int n_tiles
     return true;
 }
 
+// Tiling of a call whose form leaves the choice open: fills p.{HT, WT, Hp, nB, hp_magic, Q, q_tiles, n_tiles, total_ids} and geom;
+// false: sizes beyond the kernel's index range.  stack: a pooled call may tile the stacked batch.
+static bool convh_tiling(ConvHParams& p, int B, int H, int W, int Cout, int pool, bool stack, int& geom) {
+    geom = 0;
+    if (pool ? !convh_pick_2d(p, B, H, W, pool, geom, stack) : !convh_plan_unpooled(p, B, H, W, Cout / CH_BM, geom)) return false;
+    p.n_tiles = Cout / CH_BM;
+    p.total_ids = ((p.q_tiles + 7) / 8) * p.n_tiles * 8;
+    return true;
+}
+
+// ---- ONE place that checks a call of the slab kernel and fills ConvHParams: pointers, channels, the 31-bit byte offsets of buffer
+// addressing (x, the filters, the output map), the common fields and the tiling.  An entry says what differs (ConvHForm), adds the
+// fields that are its own (mask / bsum, y_full, ...) and picks the launch.
+//   bias_align  a bf16 bias is read one value at a time (2); the X3 form's is float32 (4);
+//   max_w       the forms that live on the padded position grid only: the widest map their tile of 256 positions holds rows of -- 94
+//               with the strided form's <3, 7> slabs, 62 for the group kernel's <4, 6>; 0: any width, tiling by convh_tiling;
+//   stride, pad the strided form computes the stride-1 'same' result and keeps the positions asked for: os / ooff / Hs / Ws;
+//   pool, stack MaxPooling2D(2, 2, 'same') fused; whether the tiles may walk the stacked batch;
+//   x3          the reference-precision form: C = the channels of the float32 map, x rows hold 2 C float16, the K loop walks 3 C
+//               (C == 64, conv2_1: four 64-channel slices, the last one zeros), y rows hold 2 Cout; oscale > 0.  Its output limit is on
+//               the map it writes, the bf16 forms' on the full-size map even where they write the pooled or strided one;
+//   side        further device buffers of the form, 16-byte aligned like the maps (the mask and the channel-sum table, y_full).
+struct ConvHForm {
+    int bias_align = 2;
+    int max_w = 0;
+    int stride = 1, pad = 1;
+    int pool = 0;
+    bool stack = true;
+    bool x3 = false;
+    float oscale = 1.f;
+    const void* side[2] = {nullptr, nullptr};
+};
+
+static int convh_params(ConvHParams& p, int& geom, const ConvHForm& f, const void* x, const void* weight, const void* bias, void* y, int B,
+                        int H, int W, int C, int Cout, int relu) {
+    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || (f.max_w && W > f.max_w)) return SSDHIP_E_BADARG;
+    const bool c64 = f.x3 && C == 64;
+    if (C <= 0 || ((C % 128) && !c64) || Cout <= 0 || (Cout % CH_BM) || (f.x3 && !(f.oscale > 0.f))) return SSDHIP_E_BADARG;
+    if ((f.stride != 1 && f.stride != 2) || (f.pad != 0 && f.pad != 1) || H + 2 * f.pad < 3 || W + 2 * f.pad < 3) return SSDHIP_E_BADARG;
+    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)f.side[0] | (uintptr_t)f.side[1]) & 15 || ((uintptr_t)bias & (f.bias_align - 1)))
+        return SSDHIP_E_BADARG;
+    const int Kc = !f.x3 ? C : c64 ? 256 : 3 * C, xC = f.x3 ? 2 * C : C, yC = f.x3 ? 2 * Cout : Cout;   // channels of the K loop, of an x row, of a y row
+    const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, Hs = (H + 2 * f.pad - 3) / f.stride + 1, Ws = (W + 2 * f.pad - 3) / f.stride + 1;
+    const long long xb = (long long)B * H * W * xC * 2, wb = (long long)Cout * 9 * Kc * 2, full = (long long)B * H * W * yC * 2;
+    const long long yb = f.pool ? (long long)B * Ho * Wo * yC * 2 : (long long)B * Hs * Ws * yC * 2;
+    if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || (f.x3 ? yb : full) >= 0x7ffff000LL) return SSDHIP_E_BADARG;
+    p = ConvHParams();
+    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.y = static_cast<bf16_t*>(y);
+    p.H = H; p.W = W; p.Cin = Kc; p.Cout = Cout; p.relu = relu ? 1 : 0;
+    p.Ho = Ho; p.Wo = Wo;
+    p.os = f.stride; p.ooff = 1 - f.pad; p.Hs = Hs; p.Ws = Ws;
+    p.x_bytes = (int)xb; p.w_bytes = (int)wb; p.y_bytes = (int)yb;
+    if (f.x3) { p.xC = xC; p.nx = c64 ? 2 : C / 64; p.bias32 = static_cast<const float*>(bias); p.oscale = f.oscale; }
+    else p.bias = static_cast<const bf16_t*>(bias);
+    if (!f.max_w) return convh_tiling(p, B, H, W, Cout, f.pool, f.stack, geom) ? SSDHIP_OK : SSDHIP_E_BADARG;
+    const long long Q = (long long)B * (H + 1) * (W + 1);
+    if (Q > 0x3fffff00LL) return SSDHIP_E_BADARG;
+    geom = 0;
+    p.Q = (int)Q;
+    p.q_tiles = (int)((Q + CH_BN - 1) / CH_BN);
+    p.n_tiles = Cout / CH_BM;
+    p.total_ids = ((p.q_tiles + 7) / 8) * p.n_tiles * 8;
+    return SSDHIP_OK;
+}
+
 // The tiling ssdhip_conv3x3_halo_nhwc_bf16 / ssdhip_conv3x3_halo_x3_nhwc_f16 pick for a (batch, map, pool) -- host arithmetic only, no
 // launch: plan[0] = 0 (padded position grid) | 4 (16 x 16 pixel tiles) | 5 (8 x 32), plan[1] = position tiles (x Cout / 128 = tile
 // units), plan[2] = the row pitch of the stacked batch (0: tiles per image), plan[3] = rows of tiles (per image, or of the stack).
@@ -1235,9 +1300,7 @@ extern "C" int ssdhip_conv3x3_halo_plan(int B, int H, int W, int Cout, int pool,
     if (!plan || B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (Cout % CH_BM)) return SSDHIP_E_BADARG;
     ConvHParams p;
     int geom = 0;
-    if (pool) {
-        if (!convh_pick_2d(p, B, H, W, pool, geom, true)) return SSDHIP_E_BADARG;
-    } else if (!convh_plan_unpooled(p, B, H, W, Cout / CH_BM, geom)) return SSDHIP_E_BADARG;
+    if (!convh_tiling(p, B, H, W, Cout, pool, true, geom)) return SSDHIP_E_BADARG;
     plan[0] = geom; plan[1] = p.q_tiles; plan[2] = p.Hp; plan[3] = p.HT;
     return SSDHIP_OK;
 }
@@ -1248,26 +1311,12 @@ extern "C" int ssdhip_conv3x3_halo_plan(int B, int H, int W, int Cout, int pool,
 // up to 4x redundant MFMA work, on layers whose cost is the latency of a K loop one workgroup deep, not FLOPs.
 extern "C" int ssdhip_conv3x3_halo_strided_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W,
                                                      int Cin, int Cout, int stride, int pad, int relu, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || W > 94) return SSDHIP_E_BADARG;
-    if (Cin <= 0 || (Cin % 128) || Cout <= 0 || (Cout % CH_BM) || (stride != 1 && stride != 2) || (pad != 0 && pad != 1)) return SSDHIP_E_BADARG;
-    if (H + 2 * pad < 3 || W + 2 * pad < 3) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 1)) return SSDHIP_E_BADARG;
-    const long long xb = (long long)B * H * W * Cin * 2, wb = (long long)Cout * 9 * Cin * 2, Q = (long long)B * (H + 1) * (W + 1);
-    if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || (long long)B * H * W * Cout * 2 >= 0x7ffff000LL || Q > 0x3fffff00LL) return SSDHIP_E_BADARG;
+    ConvHForm f;
+    f.max_w = 94; f.stride = stride; f.pad = pad;
     ConvHParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y);
-    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu ? 1 : 0;
-    p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2; p.HT = p.WT = 0;
-    p.os = stride; p.ooff = 1 - pad;
-    p.Hs = (H + 2 * pad - 3) / stride + 1; p.Ws = (W + 2 * pad - 3) / stride + 1;
-    p.Q = (int)Q;
-    p.q_tiles = (int)((Q + CH_BN - 1) / CH_BN);
-    p.n_tiles = Cout / CH_BM;
-    p.x_bytes = (int)xb; p.w_bytes = (int)wb; p.y_bytes = (int)((long long)B * p.Hs * p.Ws * Cout * 2);
-    p.total_ids = ((p.q_tiles + 7) / 8) * p.n_tiles * 8;
-    convh_launch<128 | 2048>(p, 0, 0, convh_cu_count(), stream);
+    int geom;
+    if (int rc = convh_params(p, geom, f, x, weight, bias, y, B, H, W, Cin, Cout, relu)) return rc;
+    convh_launch<128 | 2048>(p, 0, 0, convh_cu_count(), static_cast<hipStream_t>(stream_));
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 
@@ -1284,30 +1333,18 @@ extern "C" int ssdhip_conv3x3_halo_group_nhwc_bf16(int n_problems, const void* c
     for (int k = 0; k < n_problems; ++k) order[k] = k;
     for (int i = 1; i < n_problems; ++i)                  // deepest K loop first (stable insertion sort)
         for (int j = i; j > 0 && Cin_h[order[j]] > Cin_h[order[j - 1]]; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+    ConvHForm f;
+    f.max_w = 62;
     ConvHGroup g;
     long long ids = 0;
     for (int s = 0; s < n_problems; ++s) {
         const int k = order[s];
-        const int B = B_h[k], H = H_h[k], W = W_h[k], Cin = Cin_h[k], Cout = Cout_h[k];
-        const void* x = x_h[k]; const void* weight = weight_h[k]; const void* bias = bias_h ? bias_h[k] : nullptr; void* y = y_h[k];
-        if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || W > 62) return SSDHIP_E_BADARG;
-        if (Cin <= 0 || (Cin % 128) || Cout <= 0 || (Cout % CH_BM)) return SSDHIP_E_BADARG;
-        if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 1)) return SSDHIP_E_BADARG;
-        const long long xb = (long long)B * H * W * Cin * 2, wb = (long long)Cout * 9 * Cin * 2, Q = (long long)B * (H + 1) * (W + 1);
-        if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || (long long)B * H * W * Cout * 2 >= 0x7ffff000LL || Q > 0x3fffff00LL) return SSDHIP_E_BADARG;
-        ConvHParams& p = g.p[s];
-        p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-        p.y = static_cast<bf16_t*>(y);
-        p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu ? 1 : 0;
-        p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2; p.HT = p.WT = 0;
-        p.os = 1; p.ooff = 0; p.Hs = H; p.Ws = W;
-        p.Q = (int)Q;
-        p.q_tiles = (int)((Q + CH_BN - 1) / CH_BN);
-        p.n_tiles = Cout / CH_BM;
-        p.x_bytes = (int)xb; p.w_bytes = (int)wb; p.y_bytes = (int)((long long)B * H * W * Cout * 2);
-        p.total_ids = ((p.q_tiles + 7) / 8) * p.n_tiles * 8;
+        int geom;
+        if (int rc = convh_params(g.p[s], geom, f, x_h[k], weight_h[k], bias_h ? bias_h[k] : nullptr, y_h[k], B_h[k], H_h[k], W_h[k], Cin_h[k],
+                                  Cout_h[k], relu))
+            return rc;
         g.first_id[s] = (int)ids;
-        ids += p.total_ids;
+        ids += g.p[s].total_ids;
         if (ids > 0x3fffffffLL) return SSDHIP_E_BADARG;
     }
     for (int s = n_problems; s <= CH_MAX_GROUP; ++s) g.first_id[s] = (int)ids;
@@ -1327,32 +1364,12 @@ extern "C" int ssdhip_conv3x3_halo_group_nhwc_bf16(int n_problems, const void* c
 // [w hi | w hi | w lo | 0] against the activation slices (hi, lo, hi, lo): the same three products plus a slice of zeros.
 extern "C" int ssdhip_conv3x3_halo_x3_nhwc_f16(const void* x, const void* weight, const float* bias, void* y, int B, int H, int W, int C,
                                                int Cout, int relu, int pool, float oscale, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || !(oscale > 0.f)) return SSDHIP_E_BADARG;
-    const bool c64 = C == 64;
-    if (C <= 0 || ((C % 128) && !c64) || Cout <= 0 || (Cout % CH_BM)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 3)) return SSDHIP_E_BADARG;
-    const int Kc = c64 ? 256 : 3 * C;                   // channels the K loop walks
-    const long long xb = (long long)B * H * W * 2 * C * 2, wb = (long long)Cout * 9 * Kc * 2;
-    const int Ho = pool ? (H + 1) / 2 : H, Wo = pool ? (W + 1) / 2 : W;
-    const long long yb = (long long)B * Ho * Wo * 2 * Cout * 2;
-    if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || yb >= 0x7ffff000LL) return SSDHIP_E_BADARG;   // 31-bit byte offsets
+    ConvHForm f;
+    f.bias_align = 4; f.pool = pool; f.x3 = true; f.oscale = oscale;
     ConvHParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = nullptr;
-    p.y = static_cast<bf16_t*>(y);
-    p.H = H; p.W = W; p.Cin = Kc; p.Cout = Cout; p.relu = relu ? 1 : 0;
-    p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-    p.HT = p.WT = 0;
-    p.os = 1; p.ooff = 0; p.Hs = H; p.Ws = W;
-    p.xC = 2 * C; p.nx = c64 ? 2 : C / 64; p.bias32 = bias; p.oscale = oscale;
-    int geom = 0;
-    if (pool) {
-        if (!convh_pick_2d(p, B, H, W, pool, geom, true)) return SSDHIP_E_BADARG;
-    } else if (!convh_plan_unpooled(p, B, H, W, Cout / CH_BM, geom)) return SSDHIP_E_BADARG;
-    p.n_tiles = Cout / CH_BM;
-    p.x_bytes = (int)xb; p.w_bytes = (int)wb; p.y_bytes = (int)yb;
-    p.total_ids = ((p.q_tiles + 7) / 8) * p.n_tiles * 8;
-    convh_launch<128, true>(p, geom, pool, convh_cu_count(), stream);
+    int geom;
+    if (int rc = convh_params(p, geom, f, x, weight, bias, y, B, H, W, C, Cout, relu)) return rc;
+    convh_launch<128, true>(p, geom, pool, convh_cu_count(), static_cast<hipStream_t>(stream_));
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 
@@ -1363,27 +1380,13 @@ extern "C" int ssdhip_conv3x3_halo_x3_nhwc_f16(const void* x, const void* weight
 extern "C" int ssdhip_conv3x3_halo_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W,
                                              int Cin, int Cout, int relu, int pool, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0) return SSDHIP_E_BADARG;
-    if (Cin <= 0 || (Cin % 128) || Cout <= 0 || (Cout % CH_BM)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 1)) return SSDHIP_E_BADARG;
-    const long long xb = (long long)B * H * W * Cin * 2, wb = (long long)Cout * 9 * Cin * 2;
-    if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || (long long)B * H * W * Cout * 2 >= 0x7ffff000LL) return SSDHIP_E_BADARG;   // 31-bit byte offsets
-    ConvHParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y);
-    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu ? 1 : 0;
-    p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-    p.HT = p.WT = 0;
-    p.os = 1; p.ooff = 0; p.Hs = H; p.Ws = W;
     int mode = pool ? 1152 : 128;                         // the schedule: see the switch below
     if (const char* e = getenv("SSDHIP_CONVH_MODE")) mode = atoi(e);
-    int geom = 0;
-    if (pool) {
-        if (!convh_pick_2d(p, B, H, W, pool, geom, mode == 1152)) return SSDHIP_E_BADARG;
-    } else if (!convh_plan_unpooled(p, B, H, W, Cout / CH_BM, geom)) return SSDHIP_E_BADARG;
-    p.n_tiles = Cout / CH_BM;
-    p.x_bytes = (int)xb; p.w_bytes = (int)wb; p.y_bytes = (int)(pool ? (long long)B * p.Ho * p.Wo * Cout * 2 : (long long)B * H * W * Cout * 2);
-    p.total_ids = ((p.q_tiles + 7) / 8) * p.n_tiles * 8;
+    ConvHForm f;
+    f.pool = pool; f.stack = mode == 1152;
+    ConvHParams p;
+    int geom;
+    if (int rc = convh_params(p, geom, f, x, weight, bias, y, B, H, W, Cin, Cout, relu)) return rc;
     const int cu_count = convh_cu_count();
     // Schedules: 128 = persistent workgroups, one per CU, that request the next tile's first slab and weights during the last slice
     // of the current tile; 1152 = the same with the tolerant waits after an epilogue.  SSDHIP_CONVH_MODE selects.  (The round-2
@@ -1433,20 +1436,12 @@ extern "C" int ssdhip_profile_read_convh(unsigned long long* host_out, int reset
 }
 #endif
 
-// Tiling of a masked call: fills p.{HT, WT, Q, q_tiles, n_tiles, total_ids} and geom; false: sizes beyond the kernel's index range
-static bool convh_masked_plan(ConvHParams& p, int B, int H, int W, int Cout, int& geom) {
-    if (!convh_plan_unpooled(p, B, H, W, Cout / CH_BM, geom)) return false;
-    p.n_tiles = Cout / CH_BM;
-    p.total_ids = ((p.q_tiles + 7) / 8) * p.n_tiles * 8;
-    return true;
-}
-
 // rows of the channel-sum table a masked call fills ([rows][Cout] float32; 0: geometry not supported)
 extern "C" int ssdhip_conv3x3_halo_masked_bias_rows(int B, int H, int W, int Cout) {
     if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (Cout % CH_BM)) return 0;
     ConvHParams p;
     int geom;
-    if (!convh_masked_plan(p, B, H, W, Cout, geom)) return 0;
+    if (!convh_tiling(p, B, H, W, Cout, 0, false, geom)) return 0;
     const int grid = convh_masked_grid(p.total_ids, p.n_tiles, convh_cu_count());
     return grid > 0 ? 4 * grid / p.n_tiles : 0;
 }
@@ -1459,25 +1454,16 @@ extern "C" int ssdhip_conv3x3_halo_masked_bias_rows(int B, int H, int W, int Cou
 // written; the column sums are the channel sums of y (the bias gradient of the layer below), added in a fixed order.
 extern "C" int ssdhip_conv3x3_halo_masked_nhwc_bf16(const void* x, const void* weight, const void* mask, void* y, float* bias_partial,
                                                     int bias_rows, int B, int H, int W, int Cin, int Cout, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !mask || !y || B <= 0 || H <= 0 || W <= 0) return SSDHIP_E_BADARG;
-    if (Cin <= 0 || (Cin % 128) || Cout <= 0 || (Cout % CH_BM)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)mask | (uintptr_t)bias_partial) & 15) return SSDHIP_E_BADARG;
-    const long long xb = (long long)B * H * W * Cin * 2, wb = (long long)Cout * 9 * Cin * 2, yb = (long long)B * H * W * Cout * 2;
-    if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || yb >= 0x7ffff000LL) return SSDHIP_E_BADARG;   // 31-bit byte offsets
+    if (!mask) return SSDHIP_E_BADARG;
+    ConvHForm f;
+    f.side[0] = mask; f.side[1] = bias_partial;
     ConvHParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = nullptr;
-    p.y = static_cast<bf16_t*>(y); p.mask = static_cast<const bf16_t*>(mask); p.bsum = bias_partial;
-    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = 0;
-    p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-    p.os = 1; p.ooff = 0; p.Hs = H; p.Ws = W;
-    p.xC = 0; p.nx = 0; p.bias32 = nullptr; p.oscale = 1.f;
-    int geom = 0;
-    if (!convh_masked_plan(p, B, H, W, Cout, geom)) return SSDHIP_E_BADARG;
-    p.x_bytes = (int)xb; p.w_bytes = (int)wb; p.y_bytes = (int)yb;
+    int geom;
+    if (int rc = convh_params(p, geom, f, x, weight, nullptr, y, B, H, W, Cin, Cout, 0)) return rc;
+    p.mask = static_cast<const bf16_t*>(mask); p.bsum = bias_partial;
     const int grid = convh_masked_grid(p.total_ids, p.n_tiles, convh_cu_count());
     if (grid <= 0 || (bias_partial && bias_rows != 4 * grid / p.n_tiles)) return SSDHIP_E_BADARG;
-    convh_launch_masked(p, geom, grid, stream);
+    convh_launch_masked(p, geom, grid, static_cast<hipStream_t>(stream_));
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 
@@ -1486,25 +1472,14 @@ extern "C" int ssdhip_conv3x3_halo_masked_nhwc_bf16(const void* x, const void* w
 // pool2, conv3_3 -> pool3).  Cin % 128 == 0, Cout % 128 == 0.  Both maps bit-identical to ssdhip_conv3x3_halo_nhwc_bf16 (pool = 0 / 1).
 extern "C" int ssdhip_conv3x3_halo_pool_keep_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y_full, void* y_pooled,
                                                        int B, int H, int W, int Cin, int Cout, int relu, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y_full || !y_pooled || B <= 0 || H <= 0 || W <= 0) return SSDHIP_E_BADARG;
-    if (Cin <= 0 || (Cin % 128) || Cout <= 0 || (Cout % CH_BM)) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y_full | (uintptr_t)y_pooled) & 15 || ((uintptr_t)bias & 1)) return SSDHIP_E_BADARG;
-    const long long xb = (long long)B * H * W * Cin * 2, wb = (long long)Cout * 9 * Cin * 2, yfb = (long long)B * H * W * Cout * 2;
-    if (xb >= 0x7ffff000LL || wb >= 0x7ffff000LL || yfb >= 0x7ffff000LL) return SSDHIP_E_BADARG;   // 31-bit byte offsets
+    if (!y_full) return SSDHIP_E_BADARG;
+    ConvHForm f;
+    f.pool = 1; f.side[0] = y_full;
     ConvHParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y_pooled); p.y_full = static_cast<bf16_t*>(y_full);
-    p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu ? 1 : 0;
-    p.Ho = (H + 1) / 2; p.Wo = (W + 1) / 2;
-    p.HT = p.WT = 0;
-    p.os = 1; p.ooff = 0; p.Hs = H; p.Ws = W;
-    p.xC = 0; p.nx = 0; p.bias32 = nullptr; p.oscale = 1.f;
-    int geom = 0;
-    if (!convh_pick_2d(p, B, H, W, 1, geom, true)) return SSDHIP_E_BADARG;
-    p.n_tiles = Cout / CH_BM;
-    p.x_bytes = (int)xb; p.w_bytes = (int)wb; p.y_bytes = (int)((long long)B * p.Ho * p.Wo * Cout * 2); p.yf_bytes = (int)yfb;
-    p.total_ids = ((p.q_tiles + 7) / 8) * p.n_tiles * 8;
-    convh_launch_keep(p, geom, convh_cu_count(), stream);
+    int geom;
+    if (int rc = convh_params(p, geom, f, x, weight, bias, y_pooled, B, H, W, Cin, Cout, relu)) return rc;
+    p.y_full = static_cast<bf16_t*>(y_full); p.yf_bytes = (int)((long long)B * H * W * Cout * 2);
+    convh_launch_keep(p, geom, convh_cu_count(), static_cast<hipStream_t>(stream_));
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
+

@@ -392,60 +392,22 @@ static void ci_pick_tiles(int B, int HW, int Kc, int Cout, int ksize, int stride
     }
 }
 
-// The general entry (round 6): k x k convolution, k in {1, 3}, of maps with H W <= 384 input pixels and at most 384 output pixels, one
-// image per tile: x [B, H, W, Cin] bf16, weight [Cout, k, k, Cin] bf16, bias [Cout] bf16 or NULL, y [B, Ho, Wo, Cout] bf16 with
-// Ho = (H + 2 padding - dilation (k - 1) - 1) / stride + 1 (Wo alike); Cin % 64 == 0, Cout % 64 == 0, 1 <= dilation <= 16,
-// 1 <= stride <= 4, 0 <= padding <= dilation (k / 2).  Replaces Conv2D(Cout, (k, k), strides, padding, dilation_rate, activation) of
-// models/keras_ssd300.py:298-313 -- fc6 (3x3, dilation 6), fc7 and conv6_1 (1x1), conv6_2 (ZeroPadding2D + 3x3 stride 2 'valid') --
-// with the K order (and hence the bits) of ssdhip_conv2d_nhwc_bf16.  SSDHIP_E_BADARG for other geometries.
-extern "C" int ssdhip_conv2d_image_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W, int Cin,
-                                             int Cout, int ksize, int stride, int padding, int dilation, int relu, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return SSDHIP_E_BADARG;
-    if ((ksize != 1 && ksize != 3) || stride < 1 || stride > 4 || dilation < 1 || dilation > 16 || padding < 0 ||
-        padding > dilation * (ksize / 2))
-        return SSDHIP_E_BADARG;
-    if ((Cin % 64) || (Cout % 64) || (long long)H * W > CI_PX) return SSDHIP_E_BADARG;
-    const int Ho = (H + 2 * padding - dilation * (ksize - 1) - 1) / stride + 1, Wo = (W + 2 * padding - dilation * (ksize - 1) - 1) / stride + 1;
-    if (H + 2 * padding < dilation * (ksize - 1) + 1 || W + 2 * padding < dilation * (ksize - 1) + 1 || Ho < 1 || Wo < 1 ||
-        (long long)Ho * Wo > CI_PX)
-        return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 1)) return SSDHIP_E_BADARG;
-    if ((long long)H * W * (Cin > Cout ? Cin : Cout) * 2 >= 0x7ffff000LL || 128LL * 9 * Cin * 2 >= 0x7ffff000LL) return SSDHIP_E_BADARG;
-    ConvImgParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = static_cast<const bf16_t*>(bias);
-    p.y = static_cast<bf16_t*>(y);
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.dil = dilation; p.relu = relu ? 1 : 0;
-    p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.pad = padding;
-    p.xC = Cin; p.xslices = Cin / 64; p.out_f32 = 0; p.bias32 = nullptr; p.oscale = 1.f;
-    int bm;
-    ci_pick_tiles(B, H * W, Cin, Cout, ksize, stride, padding, Ho * Wo, bm, p.n_pxt);
-    p.n_cot = Cout / bm;
-    const dim3 grid((unsigned)(B * p.n_cot * p.n_pxt)), block(CI_THREADS);
-    p.xcd_map = (B % 8 == 0) ? 1 : 0;                    // b = xcd + 8 (j / tiles per image) covers 0 .. B - 1 exactly when B is a multiple of 8
-    // one 32-pixel block per wave; a 1 x 1 tile of that form requests 128 slab rows per slice, so a STRIDED 1 x 1 layer whose input
-    // has more pixels than that stays on the three-block form whatever its output size
-    const bool small = (Ho * Wo <= 128 && (ksize == 3 || H * W <= 128)) || p.n_pxt > 1;
-#define CI_LAUNCH(BM_, KS_, NPB_) hipLaunchKernelGGL((conv_image_kernel<BM_, KS_, NPB_>), grid, block, 0, stream, p)
-    if (ksize == 3) {
-        if (bm == 128) { if (small) CI_LAUNCH(128, 3, 1); else CI_LAUNCH(128, 3, 3); }
-        else { if (small) CI_LAUNCH(64, 3, 1); else CI_LAUNCH(64, 3, 3); }
-    } else {
-        if (bm == 128) { if (small) CI_LAUNCH(128, 1, 1); else CI_LAUNCH(128, 1, 3); }
-        else { if (small) CI_LAUNCH(64, 1, 1); else CI_LAUNCH(64, 1, 3); }
-    }
-#undef CI_LAUNCH
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
-}
+// ---- ONE place that checks a call of the image-resident kernel and fills ConvImgParams, for both precisions.  What differs is data:
+//   x3          the reference-precision form: C = the channels of the float32 map, x rows hold 2 C float16 [hi | lo], the K loop walks
+//               3 C filter channels, the bias is float32 (bias_align 4; a bf16 bias is read one value at a time: 2);
+//   chan_bytes  bytes per pixel of one channel of the wider of the two maps, for the 31-bit byte offsets of an image: 2 (bf16), 3 x 4
+//               for the X3 form (its widest rows are taken as 3 C float32);
+//   out_f32, oscale  X3: y as float32 instead of float16 pairs; the power-of-two scale of the filters undone.
+// bm: the channel tile picked, three_blocks: the tile form of the launch (ci_launch).
+struct ConvImgForm {
+    bool x3;
+    int bias_align, chan_bytes;
+    int out_f32;
+    float oscale;
+};
 
-// The reference-precision (X3) form of the same kernel (round 6; models/precise.py): x [B, H, W, 2 C] float16 = [hi | lo], weight
-// [Cout, k, k, 3 C] float16 = [w hi | w lo | w hi] (x3_pack_weight), bias float32 [Cout] or NULL, y [B, Ho, Wo, 2 Cout] float16 pairs
-// or, with out_f32, [B, Ho, Wo, Cout] float32.  One K loop over 3 C channels, float32 accumulation, the K order of
-// ssdhip_conv2d_x3_nhwc_f16 (bit-identical to it).  C % 64 == 0, Cout % 64 == 0; geometry limits as ssdhip_conv2d_image_nhwc_bf16.
-extern "C" int ssdhip_conv2d_image_x3_nhwc_f16(const void* x, const void* weight, const float* bias, void* y, int B, int H, int W, int C,
-                                               int Cout, int ksize, int stride, int padding, int dilation, int relu, int out_f32,
-                                               float oscale, void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+static int ci_params(ConvImgParams& p, int& bm, bool& three_blocks, const ConvImgForm& f, const void* x, const void* weight, const void* bias,
+                     void* y, int B, int H, int W, int C, int Cout, int ksize, int stride, int padding, int dilation, int relu) {
     if (!x || !weight || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0) return SSDHIP_E_BADARG;
     if ((ksize != 1 && ksize != 3) || stride < 1 || stride > 4 || dilation < 1 || dilation > 16 || padding < 0 ||
         padding > dilation * (ksize / 2))
@@ -455,30 +417,70 @@ extern "C" int ssdhip_conv2d_image_x3_nhwc_f16(const void* x, const void* weight
     if (H + 2 * padding < dilation * (ksize - 1) + 1 || W + 2 * padding < dilation * (ksize - 1) + 1 || Ho < 1 || Wo < 1 ||
         (long long)Ho * Wo > CI_PX)
         return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & 3)) return SSDHIP_E_BADARG;
-    if ((long long)H * W * 3 * (C > Cout ? C : Cout) * 4 >= 0x7ffff000LL || 128LL * 9 * 3 * C * 2 >= 0x7ffff000LL) return SSDHIP_E_BADARG;
-    ConvImgParams p;
-    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.bias = nullptr;
-    p.y = static_cast<bf16_t*>(y);
-    p.B = B; p.H = H; p.W = W; p.Cin = 3 * C; p.Cout = Cout; p.dil = dilation; p.relu = relu ? 1 : 0;
+    if (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15 || ((uintptr_t)bias & (f.bias_align - 1))) return SSDHIP_E_BADARG;
+    const int Kc = f.x3 ? 3 * C : C;                     // channels the K loop walks
+    if ((long long)H * W * (C > Cout ? C : Cout) * f.chan_bytes >= 0x7ffff000LL || 128LL * 9 * Kc * 2 >= 0x7ffff000LL) return SSDHIP_E_BADARG;
+    p = {};
+    p.x = static_cast<const bf16_t*>(x); p.w = static_cast<const bf16_t*>(weight); p.y = static_cast<bf16_t*>(y);
+    if (f.x3) p.bias32 = static_cast<const float*>(bias);
+    else p.bias = static_cast<const bf16_t*>(bias);
+    p.B = B; p.H = H; p.W = W; p.Cin = Kc; p.Cout = Cout; p.dil = dilation; p.relu = relu ? 1 : 0;
     p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.pad = padding;
-    p.xC = 2 * C; p.xslices = C / 64; p.out_f32 = out_f32 ? 1 : 0; p.bias32 = bias; p.oscale = oscale;
-    int bm;
-    ci_pick_tiles(B, H * W, 3 * C, Cout, ksize, stride, padding, Ho * Wo, bm, p.n_pxt);
+    p.xC = f.x3 ? 2 * C : C; p.xslices = C / 64; p.out_f32 = f.out_f32 ? 1 : 0; p.oscale = f.oscale;
+    ci_pick_tiles(B, H * W, Kc, Cout, ksize, stride, padding, Ho * Wo, bm, p.n_pxt);
     p.n_cot = Cout / bm;
-    const dim3 grid((unsigned)(B * p.n_cot * p.n_pxt)), block(CI_THREADS);
-    p.xcd_map = (B % 8 == 0) ? 1 : 0;
-    const bool small = (Ho * Wo <= 128 && (ksize == 3 || H * W <= 128)) || p.n_pxt > 1;
-#define CI_LAUNCH3(BM_, KS_, NPB_) hipLaunchKernelGGL((conv_image_kernel<BM_, KS_, NPB_, true>), grid, block, 0, stream, p)
+    p.xcd_map = (B % 8 == 0) ? 1 : 0;                    // b = xcd + 8 (j / tiles per image) covers 0 .. B - 1 exactly when B is a multiple of 8
+    // one 32-pixel block per wave; a 1 x 1 tile of that form requests 128 slab rows per slice, so a STRIDED 1 x 1 layer whose input
+    // has more pixels than that stays on the three-block form whatever its output size
+    three_blocks = !((Ho * Wo <= 128 && (ksize == 3 || H * W <= 128)) || p.n_pxt > 1);
+    return SSDHIP_OK;
+}
+
+template <bool X3>
+static int ci_launch(const ConvImgParams& p, int bm, int ksize, bool three_blocks, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const dim3 grid((unsigned)(p.B * p.n_cot * p.n_pxt)), block(CI_THREADS);
+#define CI_LAUNCH(BM_, KS_, NPB_) hipLaunchKernelGGL((conv_image_kernel<BM_, KS_, NPB_, X3>), grid, block, 0, stream, p)
     if (ksize == 3) {
-        if (bm == 128) { if (small) CI_LAUNCH3(128, 3, 1); else CI_LAUNCH3(128, 3, 3); }
-        else { if (small) CI_LAUNCH3(64, 3, 1); else CI_LAUNCH3(64, 3, 3); }
+        if (bm == 128) { if (!three_blocks) CI_LAUNCH(128, 3, 1); else CI_LAUNCH(128, 3, 3); }
+        else { if (!three_blocks) CI_LAUNCH(64, 3, 1); else CI_LAUNCH(64, 3, 3); }
     } else {
-        if (bm == 128) { if (small) CI_LAUNCH3(128, 1, 1); else CI_LAUNCH3(128, 1, 3); }
-        else { if (small) CI_LAUNCH3(64, 1, 1); else CI_LAUNCH3(64, 1, 3); }
+        if (bm == 128) { if (!three_blocks) CI_LAUNCH(128, 1, 1); else CI_LAUNCH(128, 1, 3); }
+        else { if (!three_blocks) CI_LAUNCH(64, 1, 1); else CI_LAUNCH(64, 1, 3); }
     }
-#undef CI_LAUNCH3
+#undef CI_LAUNCH
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// The general entry (round 6): k x k convolution, k in {1, 3}, of maps with H W <= 384 input pixels and at most 384 output pixels, one
+// image per tile: x [B, H, W, Cin] bf16, weight [Cout, k, k, Cin] bf16, bias [Cout] bf16 or NULL, y [B, Ho, Wo, Cout] bf16 with
+// Ho = (H + 2 padding - dilation (k - 1) - 1) / stride + 1 (Wo alike); Cin % 64 == 0, Cout % 64 == 0, 1 <= dilation <= 16,
+// 1 <= stride <= 4, 0 <= padding <= dilation (k / 2).  Replaces Conv2D(Cout, (k, k), strides, padding, dilation_rate, activation) of
+// models/keras_ssd300.py:298-313 -- fc6 (3x3, dilation 6), fc7 and conv6_1 (1x1), conv6_2 (ZeroPadding2D + 3x3 stride 2 'valid') --
+// with the K order (and hence the bits) of ssdhip_conv2d_nhwc_bf16.  SSDHIP_E_BADARG for other geometries.
+extern "C" int ssdhip_conv2d_image_nhwc_bf16(const void* x, const void* weight, const void* bias, void* y, int B, int H, int W, int Cin,
+                                             int Cout, int ksize, int stride, int padding, int dilation, int relu, void* stream) {
+    const ConvImgForm f = {false, 2, 2, 0, 1.f};
+    ConvImgParams p;
+    int bm;
+    bool three_blocks;
+    if (int rc = ci_params(p, bm, three_blocks, f, x, weight, bias, y, B, H, W, Cin, Cout, ksize, stride, padding, dilation, relu)) return rc;
+    return ci_launch<false>(p, bm, ksize, three_blocks, stream);
+}
+
+// The reference-precision (X3) form of the same kernel (round 6; models/precise.py): x [B, H, W, 2 C] float16 = [hi | lo], weight
+// [Cout, k, k, 3 C] float16 = [w hi | w lo | w hi] (x3_pack_weight), bias float32 [Cout] or NULL, y [B, Ho, Wo, 2 Cout] float16 pairs
+// or, with out_f32, [B, Ho, Wo, Cout] float32.  One K loop over 3 C channels, float32 accumulation, the K order of
+// ssdhip_conv2d_x3_nhwc_f16 (bit-identical to it).  C % 64 == 0, Cout % 64 == 0; geometry limits as ssdhip_conv2d_image_nhwc_bf16.
+extern "C" int ssdhip_conv2d_image_x3_nhwc_f16(const void* x, const void* weight, const float* bias, void* y, int B, int H, int W, int C,
+                                               int Cout, int ksize, int stride, int padding, int dilation, int relu, int out_f32,
+                                               float oscale, void* stream) {
+    const ConvImgForm f = {true, 4, 3 * 4, out_f32, oscale};
+    ConvImgParams p;
+    int bm;
+    bool three_blocks;
+    if (int rc = ci_params(p, bm, three_blocks, f, x, weight, bias, y, B, H, W, C, Cout, ksize, stride, padding, dilation, relu)) return rc;
+    return ci_launch<true>(p, bm, ksize, three_blocks, stream);
 }
 
 // 3x3 'same' convolution (padding = dilation) of maps with H W <= 384 pixels: the round-4 entry, now the general one at stride 1 and
