@@ -962,6 +962,63 @@ size_t ssdhip_fit_meter_state_bytes(void);
 int ssdhip_fit_meter_reset(void* state, void* stream);
 int ssdhip_fit_meter_update(const float* loss, int B, const float* partials, long long n_partials, float l2, void* state, void* stream);
 
+/* Gradient clipping inside a replayed optimizer step (csrc/ssdhip_fit.hip, ssdhip_optim_step.h): `clipnorm` and `clipvalue` of
+ * keras.optimizers.Optimizer, restated from Keras 2.2.4's Optimizer.get_gradients / clip_norm --
+ *     norm = sqrt(sum over ALL parameters of sum(g^2));  g = g * (clipnorm / norm) if norm >= clipnorm  (clipnorm > 0);
+ *     g = min(max(g, -clipvalue), clipvalue)  (clipvalue > 0, after clipnorm)
+ * -- with g the gradient of the PENALISED loss, here t = g + weight_decay * w (w the float32 parameter, or the float32 master of a bf16
+ * parameter): the value an optimizer step forms first.  A clip state block in plain global memory (16-byte aligned,
+ * ssdhip_clip_state_bytes() bytes) carries the settings, the step's norm, scale and skip decision, and three counters; every launch is
+ * stream-ordered and reads its scalars from the device, so a captured step replays with the norm of that replay's gradients.  A step:
+ * ssdhip_grad_sumsq_partials per tensor table, ssdhip_clip_finish, then the clipped step entries (the first one ticks).
+ * ssdhip_clip_state_init       writes every byte of a block: the settings (0 = off; skip_nonfinite 0 / 1), q 0, norm 0, scale 1, skip 0, the
+ *                              counters 0.
+ * ssdhip_grad_sumsq_partials   ssdhip_sumsq_partials' chunking and order of additions with x = t over a table of (gradient, weight)
+ *                              pairs named by HOST arrays: t = g + weight_decay * w as two float32 operations (weight_decay rounded once
+ *                              to float32, one value for the table), t = g when weight_decay == 0, when weights_h is NULL or when the
+ *                              tensor's weight is NULL.  dtype is the GRADIENTS' (SSDHIP_SUMSQ_F32 / SSDHIP_SUMSQ_BF16, bf16 widened
+ *                              exactly); weights are float32.  Pointers need their element's alignment only: 16-byte loads where the
+ *                              address allows them (an optimizer's tables always do), narrower ones and a scalar tail otherwise.  The
+ *                              table travels in the kernel arguments (128 tensors per launch, longer tables take more launches);
+ *                              partials[c] is written exactly once per chunk, n_partials must equal the table's chunk count.  No atomics,
+ *                              nothing to zero beforehand.
+ * ssdhip_clip_finish           one workgroup, over the partials of ALL tables of the step:  q = sum_j float64(partials[j]) in index order;
+ *                              norm = float32(sqrt(q));  scale = clipnorm / norm (one float32 division) if clipnorm > 0 and
+ *                              norm >= clipnorm, else 1.0f -- a NaN norm compares false and leaves the gradients as they are, an infinite
+ *                              one gives scale 0;  skip = skip_nonfinite and q is not finite;  steps += 1;  skipped += 1 if skip, else
+ *                              clipped += 1 if the comparison held.
+ * ssdhip_sgd_step_clipped, ssdhip_sgd_step_bf16_clipped, ssdhip_adam_step_clipped, ssdhip_adam_step_bf16_clipped
+ *                              the four step entries above with `clip`, the block ssdhip_clip_finish has just written.  skip != 0: the
+ *                              tick advances nothing and no update launch writes anything.  Otherwise per element, one IEEE float32
+ *                              operation each:  t = g + weight_decay * w (weight_decay != 0);  t = t * scale (clipnorm > 0: always, scale
+ *                              is 1.0f when not clipping);  t = t > clipvalue ? clipvalue : t, t = t < -clipvalue ? -clipvalue : t
+ *                              (clipvalue > 0; comparisons, so a NaN stays a NaN as in TensorFlow's minimum / maximum);  then the
+ *                              optimizer's rule on t with its own weight-decay term left out.  Same tables, same tensors per launch. */
+typedef struct ssdhip_clip_state {
+    double q;                               /* the step's sum of squares: the partials summed in float64 */
+    long long steps, clipped, skipped;      /* steps finished, of them scaled by clipnorm, of them skipped */
+    float clipnorm, clipvalue;              /* the settings, 0 = off */
+    float norm, scale;                      /* float32(sqrt(q)); what the update multiplies by */
+    int skip_nonfinite;                     /* the option: a step whose q is not finite does nothing */
+    int skip;                               /* this step's decision */
+    int reserved[2];
+} ssdhip_clip_state;
+size_t ssdhip_clip_state_bytes(void);
+int ssdhip_clip_state_init(void* state, double clipnorm, double clipvalue, int skip_nonfinite, void* stream);
+int ssdhip_grad_sumsq_partials(int n_tensors, const void* const* grads_h, const void* const* weights_h, const long long* numel_h, int dtype,
+                               double weight_decay, float* partials, long long n_partials, void* stream);
+int ssdhip_clip_finish(const float* partials, long long n_partials, void* state, void* stream);
+int ssdhip_sgd_step_clipped(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* bufs_h, const long long* numel_h,
+                            int group, void* state, int rule, int nesterov, int tick, void* clip, void* stream);
+int ssdhip_sgd_step_bf16_clipped(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h,
+                                 void* const* bufs_h, const long long* numel_h, int group, void* state, int rule, int nesterov, int tick,
+                                 void* clip, void* stream);
+int ssdhip_adam_step_clipped(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* m_h, void* const* v_h,
+                             void* const* vhat_h, const long long* numel_h, int group, void* state, int tick, void* clip, void* stream);
+int ssdhip_adam_step_bf16_clipped(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h, void* const* m_h,
+                                  void* const* v_h, void* const* vhat_h, const long long* numel_h, int group, void* state, int tick,
+                                  void* clip, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The decisions of the original-SSD augmentation chain for a whole batch in ONE launch (csrc/ssdhip_augment.hip): SSDExpand ->
  * SSDRandomCrop -> RandomFlip -> ResizeRandomInterp of data_generator/data_augmentation_chain_original_ssd.py:208-280 (with

@@ -186,6 +186,14 @@ SIGNATURES = {
     "ssdhip_fit_meter_state_bytes": (_SZ, []),
     "ssdhip_fit_meter_reset": (_I, [_P, _P]),
     "ssdhip_fit_meter_update": (_I, [_P, _I, _P, _LL, _F, _P, _P]),
+    "ssdhip_clip_state_bytes": (_SZ, []),
+    "ssdhip_clip_state_init": (_I, [_P, _D, _D, _I, _P]),
+    "ssdhip_grad_sumsq_partials": (_I, [_I, _P, _P, _LLP, _I, _D, _P, _LL, _P]),
+    "ssdhip_clip_finish": (_I, [_P, _LL, _P, _P]),
+    "ssdhip_sgd_step_clipped": (_I, [_I] + [_P] * 4 + [_I, _P, _I, _I, _I, _P, _P]),
+    "ssdhip_sgd_step_bf16_clipped": (_I, [_I] + [_P] * 5 + [_I, _P, _I, _I, _I, _P, _P]),
+    "ssdhip_adam_step_clipped": (_I, [_I] + [_P] * 6 + [_I, _P, _I, _P, _P]),
+    "ssdhip_adam_step_bf16_clipped": (_I, [_I] + [_P] * 7 + [_I, _P, _I, _P, _P]),
     "ssdhip_augment_plans": (_I, [_P] + [_I] * 6 + [_P] * 6),
     "ssdhip_ssd_augment_decide": (_I, [_PARAMS, _I] + [_P] * 8),
     "ssdhip_ssd_augment_decide_stream": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 10),
@@ -789,20 +797,29 @@ def sgd_momentum_step(table, lr, momentum, weight_decay=0.0):
     _optim_step("ssdhip_sgd_momentum_step", table, float(lr), float(momentum), float(weight_decay))
 
 
-def sgd_step(table, block, group, rule, nesterov, tick):
-    _optim_step("ssdhip_sgd_step", table, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0)
+def _clipped(name, clip):
+    """An optimizer step's export and last arguments: with a clip state block (clip_state_init, clip_finish) its clipped form."""
+    return (name, ()) if clip is None else (name + "_clipped", (_ptr(clip),))
 
 
-def sgd_step_bf16(table, block, group, rule, nesterov, tick):
-    _optim_step("ssdhip_sgd_step_bf16", table, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0)
+def sgd_step(table, block, group, rule, nesterov, tick, clip=None):
+    name, last = _clipped("ssdhip_sgd_step", clip)
+    _optim_step(name, table, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0, *last)
 
 
-def adam_step(table, block, group, tick):
-    _optim_step("ssdhip_adam_step", table, int(group), _ptr(block), 1 if tick else 0)
+def sgd_step_bf16(table, block, group, rule, nesterov, tick, clip=None):
+    name, last = _clipped("ssdhip_sgd_step_bf16", clip)
+    _optim_step(name, table, int(group), _ptr(block), int(rule), 1 if nesterov else 0, 1 if tick else 0, *last)
 
 
-def adam_step_bf16(table, block, group, tick):
-    _optim_step("ssdhip_adam_step_bf16", table, int(group), _ptr(block), 1 if tick else 0)
+def adam_step(table, block, group, tick, clip=None):
+    name, last = _clipped("ssdhip_adam_step", clip)
+    _optim_step(name, table, int(group), _ptr(block), 1 if tick else 0, *last)
+
+
+def adam_step_bf16(table, block, group, tick, clip=None):
+    name, last = _clipped("ssdhip_adam_step_bf16", clip)
+    _optim_step(name, table, int(group), _ptr(block), 1 if tick else 0, *last)
 
 
 # struct ssdhip_adam_state / ssdhip_adam_group and ssdhip_sgd_state / ssdhip_sgd_group (include/ssdhip.h), for reading a state block
@@ -928,6 +945,69 @@ def fit_meter_update(block, loss, partials, l2):
         raise SsdHipError("fit_meter_update: partials must be a contiguous float32 tensor on the loss's device")
     launch("ssdhip_fit_meter_update", loss.device, _ptr(loss), int(loss.numel()), _ptr(partials),
            int(partials.numel()) if partials is not None else 0, float(l2), _ptr(block))
+
+
+# struct ssdhip_clip_state (include/ssdhip.h)
+CLIP_STATE = np.dtype([("q", "<f8"), ("steps", "<i8"), ("clipped", "<i8"), ("skipped", "<i8"), ("clipnorm", "<f4"), ("clipvalue", "<f4"),
+                       ("norm", "<f4"), ("scale", "<f4"), ("skip_nonfinite", "<i4"), ("skip", "<i4"), ("reserved", "<i4", (2,))])
+
+
+def clip_state_bytes():
+    return int(load().ssdhip_clip_state_bytes())
+
+
+def clip_state_init(block, clipnorm, clipvalue, skip_nonfinite):
+    """The settings (0 = off) into a clip state block (a uint8 CUDA tensor of clip_state_bytes()), everything else at its start."""
+    launch("ssdhip_clip_state_init", block.device, _ptr(block), float(clipnorm), float(clipvalue), 1 if skip_nonfinite else 0)
+
+
+def clip_state_read(block):
+    """A clip state block as one CLIP_STATE record: a device-to-host copy, i.e. a synchronisation."""
+    return block.detach().cpu().numpy()[:CLIP_STATE.itemsize].view(CLIP_STATE)[0]
+
+
+def grad_sumsq_table(grads, weights, device):
+    """The HOST table of ssdhip_grad_sumsq_partials: dense gradients, all float32 or all bf16, and per gradient its float32 weight of
+    the same size or None (`weights` None: no weight column).  Returns (device, n, gradient pointers, weight pointers or None, counts,
+    dtype flag, number of partials); the caller keeps the tensors alive."""
+    torch = _torch()
+    device, n, ptrs, numels, flag, chunks = sumsq_table(list(grads), device)
+    wp = None
+    if weights is not None:
+        if len(weights) != n:
+            raise SsdHipError("grad_sumsq_table: one weight (or None) per gradient")
+        for g, w in zip(grads, weights):
+            if w is not None and (w.dtype != torch.float32 or w.device != device or w.numel() != g.numel()
+                                  or not (w.is_contiguous() or (w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last)))):
+                raise SsdHipError("grad_sumsq_table: a weight must be dense float32 of its gradient's size on %s" % (device,))
+        wp = (ctypes.c_void_p * n)(*[None if w is None else w.data_ptr() for w in weights])
+    return device, n, ptrs, wp, numels, flag, chunks
+
+
+def grad_sumsq_partials(table, weight_decay, partials):
+    """One float32 partial per chunk of sum((g + weight_decay * w)^2) into `partials` (float32, exactly the table's chunk count).
+    `table`: grad_sumsq_table's result."""
+    device, n, ptrs, wp, numels, flag, chunks = table
+    torch = _torch()
+    if partials.dtype != torch.float32 or not partials.is_contiguous() or partials.device != device:
+        raise SsdHipError("grad_sumsq_partials: `partials` must be a contiguous float32 tensor on the tensors' device")
+    launch("ssdhip_grad_sumsq_partials", device, n, ptrs, wp, numels, flag, float(weight_decay), _ptr(partials), partials.numel())
+
+
+def optim_grad_sumsq_partials(table, bf16, weight_decay, partials):
+    """The same over an optimizer step's own table (sgd_table .. adam_table_bf16): its gradient column, and as weights its parameter
+    column or with `bf16` its master column.  No new table: the step's arrays are passed as they are."""
+    device, n, numels = table[0], table[1], table[-1]
+    launch("ssdhip_grad_sumsq_partials", device, n, table[3], table[4 if bf16 else 2], numels, SUMSQ_BF16 if bf16 else SUMSQ_F32,
+           float(weight_decay), _ptr(partials), partials.numel())
+
+
+def clip_finish(block, partials):
+    """The partials of one step (every table's, float32, contiguous) into the clip state block: q, norm, scale, skip, counters."""
+    torch = _torch()
+    if partials.dtype != torch.float32 or not partials.is_contiguous() or partials.device != block.device:
+        raise SsdHipError("clip_finish: `partials` must be a contiguous float32 tensor on the block's device")
+    launch("ssdhip_clip_finish", block.device, _ptr(partials), partials.numel(), _ptr(block))
 
 
 def fit_meter_parse(raw):

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(64) void adam_init_kernel(ssdhip_adam_state* st, in
 }
 
 // One workgroup, one thread per parameter group.
-__global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void adam_tick_kernel(ssdhip_adam_state* st) {
+__device__ __forceinline__ void adam_tick(ssdhip_adam_state* st) {
     const int g = threadIdx.x;
     const long long t = st->iterations + 1;
     const int n_groups = st->n_groups;
@@ -75,6 +75,14 @@ __global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void adam_tick_kernel(ssdhi
     s.b1t = b1t;
     s.b2t = b2t;
     s.lr_t = (float)lr_t;
+}
+
+__global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void adam_tick_kernel(ssdhip_adam_state* st) { adam_tick(st); }
+
+// The tick of a clipped step: a skipped step (ssdhip_clip_finish's decision) leaves the count and the products as they are.
+__global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void adam_tick_clipped_kernel(ssdhip_adam_state* st, const ssdhip_clip_state* clip) {
+    if (clip->skip) return;
+    adam_tick(st);
 }
 
 // One element of the update on p (the parameter, or its master) and its buffers m, v and, with amsgrad, vhat: one IEEE float32 operation
@@ -124,6 +132,31 @@ __global__ __launch_bounds__(256) void adam_step_bf16_kernel(const AdamBf16Args<
     adam_step<AMSGRAD, true>(a, st, group);
 }
 
+// The clipped forms: the same two kernels with Clipped<AdamRule> as their rule, nothing at all on a skipped step.
+static_assert(sizeof(AdamArgs<true>) + 2 * sizeof(void*) + sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
+static_assert(sizeof(AdamBf16Args<true>) + 2 * sizeof(void*) + sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
+
+template <bool AMSGRAD, bool BF16, class Table>
+__device__ __forceinline__ void adam_step_clipped(const Table& a, const ssdhip_adam_state* __restrict__ st, int group,
+                                                  const ssdhip_clip_state* __restrict__ clip) {
+    if (group >= st->n_groups || clip->skip) return;
+    const ssdhip_adam_group& s = st->groups[group];
+    optim_step<Clipped<AdamRule<AMSGRAD>>, BF16>(
+        a, {{s.lr_t, s.one_minus_beta_1, s.one_minus_beta_2, s.beta_1_f, s.beta_2_f, s.epsilon, 0.f}, s.weight_decay, clip});
+}
+
+template <bool AMSGRAD>
+__global__ __launch_bounds__(256) void adam_step_clipped_kernel(const AdamArgs<AMSGRAD> a, const ssdhip_adam_state* __restrict__ st,
+                                                                int group, const ssdhip_clip_state* __restrict__ clip) {
+    adam_step_clipped<AMSGRAD, false>(a, st, group, clip);
+}
+
+template <bool AMSGRAD>
+__global__ __launch_bounds__(256) void adam_step_bf16_clipped_kernel(const AdamBf16Args<AMSGRAD> a, const ssdhip_adam_state* __restrict__ st,
+                                                                     int group, const ssdhip_clip_state* __restrict__ clip) {
+    adam_step_clipped<AMSGRAD, true>(a, st, group, clip);
+}
+
 }  // namespace ssdhip
 
 using namespace ssdhip;
@@ -168,4 +201,28 @@ extern "C" int ssdhip_adam_step_bf16(int n_tensors, void* const* params_h, const
                                                  stream_, adam_tick_kernel, adam_step_bf16_kernel<true>);
     return optim_state_step<ADAM_BF16_CHUNK>(n_tensors, {params_h, grads_h, master_h, m_h, v_h}, numel_h, group, state, tick, stream_,
                                              adam_tick_kernel, adam_step_bf16_kernel<false>);
+}
+
+extern "C" int ssdhip_adam_step_clipped(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* m_h,
+                                        void* const* v_h, void* const* vhat_h, const long long* numel_h, int group, void* state, int tick,
+                                        void* clip, void* stream_) {
+    const ssdhip_clip_state* cl = optim_clip_block(clip);
+    if (!cl) return SSDHIP_E_BADARG;
+    if (vhat_h)
+        return optim_state_step<ADAM_CHUNK>(n_tensors, {params_h, grads_h, m_h, v_h, vhat_h}, numel_h, group, state, tick, stream_,
+                                            adam_tick_clipped_kernel, adam_step_clipped_kernel<true>, cl);
+    return optim_state_step<ADAM_CHUNK>(n_tensors, {params_h, grads_h, m_h, v_h}, numel_h, group, state, tick, stream_,
+                                        adam_tick_clipped_kernel, adam_step_clipped_kernel<false>, cl);
+}
+
+extern "C" int ssdhip_adam_step_bf16_clipped(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h,
+                                             void* const* m_h, void* const* v_h, void* const* vhat_h, const long long* numel_h, int group,
+                                             void* state, int tick, void* clip, void* stream_) {
+    const ssdhip_clip_state* cl = optim_clip_block(clip);
+    if (!cl) return SSDHIP_E_BADARG;
+    if (vhat_h)
+        return optim_state_step<ADAM_BF16_CHUNK>(n_tensors, {params_h, grads_h, master_h, m_h, v_h, vhat_h}, numel_h, group, state, tick,
+                                                 stream_, adam_tick_clipped_kernel, adam_step_bf16_clipped_kernel<true>, cl);
+    return optim_state_step<ADAM_BF16_CHUNK>(n_tensors, {params_h, grads_h, master_h, m_h, v_h}, numel_h, group, state, tick, stream_,
+                                             adam_tick_clipped_kernel, adam_step_bf16_clipped_kernel<false>, cl);
 }

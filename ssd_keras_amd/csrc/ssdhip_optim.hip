@@ -213,7 +213,7 @@ __global__ __launch_bounds__(64) void sgd_init_kernel(ssdhip_sgd_state* st, int 
 }
 
 // One workgroup, one thread per parameter group.
-__global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void sgd_tick_kernel(ssdhip_sgd_state* st) {
+__device__ __forceinline__ void sgd_tick(ssdhip_sgd_state* st) {
     const int g = threadIdx.x;
     const long long t = st->iterations + 1;
     const int n_groups = st->n_groups;
@@ -224,6 +224,14 @@ __global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void sgd_tick_kernel(ssdhip
     double lr = s.lr;
     if (s.decay > 0.0) lr = lr / (1.0 + s.decay * (double)(t - 1));   // Keras reads `iterations` before it increments it
     s.lr_t = (float)lr;
+}
+
+__global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void sgd_tick_kernel(ssdhip_sgd_state* st) { sgd_tick(st); }
+
+// The tick of a clipped step: a skipped step (ssdhip_clip_finish's decision) leaves the block as it is.
+__global__ __launch_bounds__(SSDHIP_ADAM_MAX_GROUPS) void sgd_tick_clipped_kernel(ssdhip_sgd_state* st, const ssdhip_clip_state* clip) {
+    if (clip->skip) return;
+    sgd_tick(st);
 }
 
 // The state-block forms: the group's scalars are the values the tick has just written (uniform: scalar loads).
@@ -239,6 +247,29 @@ __global__ __launch_bounds__(256) void sgd_step_bf16_kernel(const SgdBf16Args a,
     if (group >= st->n_groups) return;
     const ssdhip_sgd_group& s = st->groups[group];
     optim_step<SgdRule<RULE, NESTEROV>, true>(a, {s.lr_t, s.momentum_f, s.weight_decay});
+}
+
+// The clipped forms: the same two kernels with Clipped<SgdRule> as their rule, nothing at all on a skipped step.
+static_assert(sizeof(SgdBf16Args) + 2 * sizeof(void*) + sizeof(int) <= 4096, "the tensor table must fit the kernel arguments");
+
+template <int RULE, bool NESTEROV, bool BF16, class Table>
+__device__ __forceinline__ void sgd_step_clipped(const Table& a, const ssdhip_sgd_state* __restrict__ st, int group,
+                                                 const ssdhip_clip_state* __restrict__ clip) {
+    if (group >= st->n_groups || clip->skip) return;
+    const ssdhip_sgd_group& s = st->groups[group];
+    optim_step<Clipped<SgdRule<RULE, NESTEROV>>, BF16>(a, {{s.lr_t, s.momentum_f, 0.f}, s.weight_decay, clip});
+}
+
+template <int RULE, bool NESTEROV>
+__global__ __launch_bounds__(256) void sgd_step_clipped_kernel(const SgdArgs a, const ssdhip_sgd_state* __restrict__ st, int group,
+                                                               const ssdhip_clip_state* __restrict__ clip) {
+    sgd_step_clipped<RULE, NESTEROV, false>(a, st, group, clip);
+}
+
+template <int RULE, bool NESTEROV>
+__global__ __launch_bounds__(256) void sgd_step_bf16_clipped_kernel(const SgdBf16Args a, const ssdhip_sgd_state* __restrict__ st, int group,
+                                                                    const ssdhip_clip_state* __restrict__ clip) {
+    sgd_step_clipped<RULE, NESTEROV, true>(a, st, group, clip);
 }
 
 }  // namespace ssdhip
@@ -298,4 +329,22 @@ extern "C" int ssdhip_sgd_step_bf16(int n_tensors, void* const* params_h, const 
     if (rule < 0 || rule > 1) return SSDHIP_E_BADARG;
     return optim_state_step<SGD_CHUNK>(n_tensors, {params_h, grads_h, master_h, bufs_h}, numel_h, group, state, tick, stream_,
                                        sgd_tick_kernel, SGD_PICK(sgd_step_bf16_kernel, rule, nesterov));
+}
+
+extern "C" int ssdhip_sgd_step_clipped(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* bufs_h,
+                                       const long long* numel_h, int group, void* state, int rule, int nesterov, int tick, void* clip,
+                                       void* stream_) {
+    const ssdhip_clip_state* cl = optim_clip_block(clip);
+    if (rule < 0 || rule > 1 || !cl) return SSDHIP_E_BADARG;
+    return optim_state_step<SGD_CHUNK>(n_tensors, {params_h, grads_h, bufs_h}, numel_h, group, state, tick, stream_,
+                                       sgd_tick_clipped_kernel, SGD_PICK(sgd_step_clipped_kernel, rule, nesterov), cl);
+}
+
+extern "C" int ssdhip_sgd_step_bf16_clipped(int n_tensors, void* const* params_h, const void* const* grads_h, void* const* master_h,
+                                            void* const* bufs_h, const long long* numel_h, int group, void* state, int rule, int nesterov,
+                                            int tick, void* clip, void* stream_) {
+    const ssdhip_clip_state* cl = optim_clip_block(clip);
+    if (rule < 0 || rule > 1 || !cl) return SSDHIP_E_BADARG;
+    return optim_state_step<SGD_CHUNK>(n_tensors, {params_h, grads_h, master_h, bufs_h}, numel_h, group, state, tick, stream_,
+                                       sgd_tick_clipped_kernel, SGD_PICK(sgd_step_bf16_clipped_kernel, rule, nesterov), cl);
 }

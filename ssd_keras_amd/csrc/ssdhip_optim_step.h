@@ -106,6 +106,33 @@ __device__ __forceinline__ void optim_step(const Table& a, const typename Rule::
     }
 }
 
+// A rule behind Keras's gradient clipping (Optimizer.get_gradients: clipnorm, then clipvalue, on the gradient of the penalised loss).
+// The gradient is completed here -- t = g + wd * p, the value whose square ssdhip_grad_sumsq_partials summed --, scaled by what
+// ssdhip_clip_finish left in the clip state block, clamped, and handed to Rule::update with the rule's own weight decay 0 so that the
+// term is not applied twice.  One IEEE float32 operation each.  The multiplication always happens when clipnorm is on (scale is 1.0f
+// when the norm is below it); the clamp is comparisons, so a NaN stays a NaN as in TensorFlow's minimum / maximum.  A step kernel
+// names Clipped<Rule> where it named Rule: optim_step and the rules themselves do not know about clipping.
+template <class Rule>
+struct Clipped {
+    static constexpr int NBUF = Rule::NBUF;
+    struct Scalars {
+        typename Rule::Scalars rule;                       // with weight decay 0
+        float wd, scale, clipvalue;
+        bool by_norm;
+        __device__ Scalars(const typename Rule::Scalars& r, float wd_, const ssdhip_clip_state* __restrict__ cl)
+            : rule(r), wd(wd_), scale(cl->scale), clipvalue(cl->clipvalue), by_norm(cl->clipnorm > 0.f) {}
+    };
+    static __device__ __forceinline__ void update(float& p, float g, float* bufs, const Scalars& c) {
+        if (c.wd != 0.f) g = g + c.wd * p;
+        if (c.by_norm) g = g * c.scale;
+        if (c.clipvalue > 0.f) {
+            g = g > c.clipvalue ? c.clipvalue : g;
+            g = g < -c.clipvalue ? -c.clipvalue : g;
+        }
+        Rule::update(p, g, bufs, c.rule);
+    }
+};
+
 // A group's base learning rate into a state block of either optimizer, stream-ordered.
 template <class State>
 __global__ __launch_bounds__(64) void optim_set_lr_kernel(State* st, int group, double lr) {
@@ -161,17 +188,24 @@ int optim_launch(hipStream_t stream, int n_tensors, const void* const* const (&c
 }
 
 // The step of an optimizer whose scalars live in a state block: the block's own checks, then optim_launch behind the optimizer's tick.
-template <int CHUNK, int NCOL, class State, class Kernel>
+// `extra`: what tick and update take behind their own arguments -- nothing, or the clip state block that ssdhip_clip_finish wrote for
+// this step (the tick reads its skip decision, the update its scale).
+template <int CHUNK, int NCOL, class State, class Kernel, class... Extra>
 int optim_state_step(int n_tensors, const void* const* const (&cols)[NCOL], const long long* numel_h, int group, void* state, int tick,
-                     void* stream_, void (*tick_kernel)(State*), Kernel kernel) {
+                     void* stream_, void (*tick_kernel)(State*, Extra...), Kernel kernel, Extra... extra) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!state || ((uintptr_t)state & 15) || group < 0 || group >= SSDHIP_ADAM_MAX_GROUPS) return SSDHIP_E_BADARG;
     State* st = static_cast<State*>(state);
     const auto ticker = [=] {
-        if (tick) hipLaunchKernelGGL(tick_kernel, dim3(1), dim3(SSDHIP_ADAM_MAX_GROUPS), 0, stream, st);
+        if (tick) hipLaunchKernelGGL(tick_kernel, dim3(1), dim3(SSDHIP_ADAM_MAX_GROUPS), 0, stream, st, extra...);
         return !tick || hipGetLastError() == hipSuccess;
     };
-    return optim_launch<CHUNK>(stream, n_tensors, cols, numel_h, ticker, kernel, static_cast<const State*>(st), group);
+    return optim_launch<CHUNK>(stream, n_tensors, cols, numel_h, ticker, kernel, static_cast<const State*>(st), group, extra...);
+}
+
+// A clipped step's `clip` argument as the kernels take it; NULL where the call is to be refused (no block, or not 16-byte aligned).
+inline const ssdhip_clip_state* optim_clip_block(const void* clip) {
+    return ((uintptr_t)clip & 15) ? nullptr : static_cast<const ssdhip_clip_state*>(clip);
 }
 
 }  // namespace ssdhip

@@ -28,7 +28,22 @@ half an ulp of the weight -- 2^-9 of its magnitude -- rounds to nothing, step af
 In both, float32 parameters on a GPU with gradients of their own memory layout take the fused launch, and so do bf16 parameters with
 bf16 gradients under `master_weights` (a launch of their own: ssdhip_adam_step_bf16 / ssdhip_sgd_step_bf16); anything else (CPU
 tensors, other dtypes, bf16 without masters, SGD with momentum 0) the plain tensor expressions of the same rule.  All four launches
-are ONE update body and one host launcher (csrc/ssdhip_optim_step.h) with the optimizer's rule in it, planned in one place here."""
+are ONE update body and one host launcher (csrc/ssdhip_optim_step.h) with the optimizer's rule in it, planned in one place here.
+
+`clipnorm=` / `clipvalue=` -- the two keywords every keras.optimizers.Optimizer takes, as Keras 2.2.4's `Optimizer.get_gradients` /
+`clip_norm` define them (restated from its source in tests/np_clip.py: there is no Keras where this runs): ONE norm over all
+parameters of the optimizer, `g * clipnorm / norm` when `norm >= clipnorm`, then the clamp to `[-clipvalue, clipvalue]`.  `g` is the
+gradient of the PENALISED loss, here `g + weight_decay * w` (w the parameter, or its master), which `torch.nn.utils.clip_grad_norm_`
+between `backward()` and `step()` never sees -- and that call could not be captured.  The norm is taken on the device over the step's
+own tensor tables (ssdhip_grad_sumsq_partials, one launch per table, in the written-down order of additions of
+ssdhip_sumsq_partials), ssdhip_clip_finish turns it into a scale in a clip state block, and the clipped forms of the four step
+launches apply it: a captured step replays with the norm of ITS gradients.  A NaN norm clips nothing and an infinite one scales by 0,
+as in Keras.  `skip_nonfinite=True` is this package's own (as `rule='torch'` is): a step whose sum of squares is not finite does
+nothing -- no parameter, master or buffer is written, `iterations` and Adam's products stay --, and is counted; it may be given
+alone.  `grad_norm` reads the last norm back, `clip_stats` the counters {'steps', 'clipped', 'skipped'}.  The three are
+optimizer-wide; with any of them set every parameter that has a gradient must take the fused launch, on one device -- the tensor
+expressions (SGD with momentum 0, bf16 without masters, CPU tensors, other dtypes) do not clip and `step()` refuses them with a
+ValueError before anything is launched.  Without the keywords no clip block exists and the step is the one described above."""
 from __future__ import annotations
 
 import math
@@ -53,11 +68,13 @@ class _MasterWeightsOption(type):
     the parameter groups.  The price: `inspect.signature(SGD)` and `help(SGD)` show `(*args, master_weights=False, **kwargs)` -- the
     Keras parameters are on `SGD.__init__` --, and a subclass cannot forward the option through `super().__init__`: it passes it where
     it constructs (`Sub(..., master_weights=True)`), or sets `group["master_weights"]` before the first step.  Once those two lists may
-    grow, this class goes and `master_weights=False` becomes a keyword-only parameter of the two constructors."""
+    grow, this class goes and `master_weights=False` becomes a keyword-only parameter of the two constructors.
+    `clipnorm=`, `clipvalue=` and `skip_nonfinite=` (gradient clipping, `_OneLaunchOptimizer`) are taken the same way."""
 
-    def __call__(cls, *args, master_weights=False, **kwargs):
+    def __call__(cls, *args, master_weights=False, clipnorm=None, clipvalue=None, skip_nonfinite=False, **kwargs):
         self = cls.__new__(cls)
         self._master_weights_default = bool(master_weights)
+        self._clip_default = dict(clipnorm=clipnorm, clipvalue=clipvalue, skip_nonfinite=bool(skip_nonfinite))   # (the same route)
         self.__init__(*args, **kwargs)
         return self
 
@@ -86,17 +103,28 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
 
     A subclass names its state (`_buffers`, `_BLOCK`, `_HOST`), says which buffers a group's parameters have (`_group_buffers`) and
     whether it can take the fused launch (`_fusable`), and supplies `_check`, `_hyper` (lr first), `_tag`, the block's three native
-    calls, `_table`, `_launch` and `_expressions`."""
+    calls, `_table`, `_launch` and `_expressions`.
+
+    Clipping (`clipnorm`, `clipvalue`, `skip_nonfinite`; the module docstring): the settings live in the groups' defaults, so
+    `state_dict`, `load_state_dict` and pickling carry them; the clip state block is `state["clip_state:" + device]`, the partials
+    buffer (one float32 per 8192-element chunk of every parameter) an attribute that is never saved; both are made by the first eager
+    step or by `init_state()`, never inside a capture.  The block sits in `state` beside the optimizer's state block, so
+    `state_dict()` writes its 64 bytes; `load_state_dict` ignores them and a restored optimizer starts its counters again from the
+    settings in the groups.  On a step that `skip_nonfinite` skips the host cannot know (it reads nothing back): the parameters'
+    `_version` is bumped as on every step, and caches keyed on it refresh from unchanged weights."""
 
     _buffers = ()                                            # names of the per-parameter state tensors the kernel touches
     _BLOCK = None                                            # self.state[_BLOCK + device]: the device's state block, a uint8 tensor
     _HOST = None                                             # self.state[_HOST]: the same scalars for the tensor-expression path
+    _FUSED_NEEDS = ""                                        # what else the fused launch asks of a group, for _clip_refuse's message
 
     def __init__(self, params, defaults):
-        defaults = dict(defaults, master_weights=self.__dict__.pop("_master_weights_default", False))   # (_MasterWeightsOption)
+        defaults = dict(defaults, master_weights=self.__dict__.pop("_master_weights_default", False),   # (_MasterWeightsOption)
+                        **self.__dict__.pop("_clip_default", _NO_CLIP))
         self._check(defaults)
         super().__init__(params, defaults)
         self._tables, self._seen, self._versions, self._mastering = {}, {}, {}, {}
+        self._clip_partials, self._clip_set = {}, {}
         for group in self.param_groups:
             self._check(group)
         self._check_groups()
@@ -104,6 +132,23 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
     def _check_groups(self):
         if len(self.param_groups) > nat.ADAM_MAX_GROUPS:
             raise ValueError("at most %d parameter groups (the device state block's size)" % nat.ADAM_MAX_GROUPS)
+        self._clip()
+
+    def _clip(self):
+        """(clipnorm, clipvalue, skip_nonfinite) of the optimizer, 0.0 for a bound that is off, or None when none of the three is set:
+        they are optimizer-wide (ONE norm over every parameter), so groups that disagree raise, and so does a negative bound."""
+        name, found = type(self).__name__, None
+        for gi, group in enumerate(self.param_groups):
+            cn, cv = group.get("clipnorm"), group.get("clipvalue")
+            for what, x in (("clipnorm", cn), ("clipvalue", cv)):
+                if x is not None and not float(x) >= 0.0:
+                    raise ValueError("%s: %s must be non-negative (group %d: %r)" % (name, what, gi, x))
+            here = (float(cn or 0.0), float(cv or 0.0), bool(group.get("skip_nonfinite", False)))
+            if found is not None and here != found:
+                raise ValueError("%s: clipnorm, clipvalue and skip_nonfinite are optimizer-wide (group 0: %r, group %d: %r)"
+                                 % (name, found, gi, here))
+            found = here
+        return found if found and (found[0] > 0.0 or found[1] > 0.0 or found[2]) else None
 
     # The device tables hold RAW pointers (parameter, gradient, state buffers): everything that can replace one of those tensors
     # drops them, and the per-step key below covers all their addresses as well (ADVICE r5: the key used to hold the gradients'
@@ -111,8 +156,14 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._tables, self._versions, self._mastering = {}, {}, {}
-        for group in self.param_groups:                       # (a checkpoint from before the option existed)
+        for group in self.param_groups:                       # (a checkpoint from before the options existed)
             group.setdefault("master_weights", False)
+            for k, v in _NO_CLIP.items():
+                group.setdefault(k, v)
+        for k in [k for k in self.state if isinstance(k, str) and k.startswith(_CLIP_BLOCK)]:
+            del self.state[k]                                 # (made again, counters at zero, from the settings just loaded)
+        self._clip_partials = {}
+        self._clip()
         # (the framework casts every floating-point state tensor to its parameter's dtype: the float32 state of a bf16 parameter is
         #  taken from the checkpoint again, as it was saved)
         saved, ids = state_dict["state"], [i for g in state_dict["param_groups"] for i in g["params"]]
@@ -133,10 +184,13 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
         self._versions, self._mastering = {}, {}              # (keyed by the parameters of the optimizer this was copied from)
         for group in self.param_groups:
             group.setdefault("master_weights", False)
+            for k, v in _NO_CLIP.items():
+                group.setdefault(k, v)
+        self._clip_partials, self._clip_set = {}, {}
 
     def __getstate__(self):
         state = dict(super().__getstate__()) if hasattr(super(), "__getstate__") else dict(self.__dict__)
-        for name in ("_tables", "_versions", "_mastering"):
+        for name in ("_tables", "_versions", "_mastering", "_clip_partials", "_clip_set"):
             state.pop(name, None)
         return state
 
@@ -148,6 +202,7 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
         self._tables = {}
         if late:
             self._check(self.param_groups[-1])
+            self._clip()
             host = self.state.get(self._HOST)
             if host is not None:
                 self._host_add_group(host, self.param_groups[-1])
@@ -356,11 +411,86 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
 
     # ---- the step -------------------------------------------------------------------------------------------------------------------
     def init_state(self):
-        """What the first step allocates -- state buffers of the parameters that have a gradient now, the state block -- without a
-        step: so that `step()` can be captured into a graph from step 1 on."""
-        for gi, group in enumerate(self.param_groups):
-            for _, _, _, dev, _ in self._planned(gi, group, self._tag(group))[0]:
+        """What the first step allocates -- state buffers of the parameters that have a gradient now, the state block, with clipping
+        the clip block and the partials buffer -- without a step: so that `step()` can be captured into a graph from step 1 on."""
+        clip = self._clip()
+        if clip is not None:
+            self._clip_refuse()
+        plans = [self._planned(gi, group, self._tag(group)) for gi, group in enumerate(self.param_groups)]
+        for tables, _ in plans:
+            for _, _, _, dev, _ in tables:
                 self._block(dev)
+        if clip is not None:
+            self._clip_buffers(plans, clip)
+
+    # ---- gradient clipping: Keras's clipnorm / clipvalue, and skip_nonfinite ----------------------------------------------------------
+    def _clip_refuse(self):
+        """With clipping every parameter that has a gradient takes the fused launch, on one device (the norm is ONE launch sequence on
+        one stream): anything else is refused here, BEFORE anything is allocated or launched, naming the first such parameter.
+        Decided anew at every step (`_split`, cheap beside `_planned`): a group's momentum or `master_weights` may have changed."""
+        name, first = type(self).__name__, None
+        for gi, group in enumerate(self.param_groups):
+            fused, rest = self._split(group, fusable=self._fusable(group))
+            bad = rest[0] if rest else None
+            for (dev, _), ps in fused.items():
+                first = first or dev
+                if dev != first and bad is None:
+                    bad = ps[0]
+            if bad is not None:
+                i = [id(p) for p in group["params"]].index(id(bad))
+                raise ValueError(
+                    "%s: clipnorm / clipvalue / skip_nonfinite need every parameter on the fused launch, on one device -- float32 (or bf16 "
+                    "with master_weights) on a GPU, a dense gradient of its dtype and layout%s; parameter %d of group %d (shape %s, %s, %s) "
+                    "is not" % (name, self._FUSED_NEEDS, i, gi, tuple(bad.shape), bad.dtype, bad.device))
+
+    def _clip_buffers(self, plans, clip):
+        """(clip block, partials buffer, number of partials) of this step's tables; creates what is missing (never inside a capture)
+        and sends changed settings to the block (eager steps only).  The partials buffer is sized once for EVERY parameter of the
+        optimizer, with a gradient or not, so that it never moves under a captured step when further parameters get gradients; only
+        `add_param_group` can outgrow it, and that invalidates earlier captures anyway (it drops the tables)."""
+        tables = [t for ts, _ in plans for t in ts]
+        if not tables:
+            return None, None, 0
+        dev = tables[0][3]
+        chunks = sum(nat.sumsq_chunks(p.numel() for p in ps) for _, ps, _, _, _ in tables)
+        key = _CLIP_BLOCK + str(dev)
+        blk, partials = self.state.get(key), self._clip_partials.get(dev)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing and (blk is None or partials is None or partials.numel() < chunks or self._clip_set.get(key) != clip):
+            raise RuntimeError("%s: the clip block and its partials cannot be created or changed inside a graph capture; take an eager "
+                               "step or call init_state() first" % type(self).__name__)
+        if blk is None:
+            blk = self.state[key] = torch.zeros((nat.clip_state_bytes(),), dtype=torch.uint8, device=dev)
+            self._clip_set.pop(key, None)
+        if self._clip_set.get(key) != clip:
+            if key in self._clip_set:
+                raise ValueError("%s: clipnorm, clipvalue and skip_nonfinite cannot change after the first step" % type(self).__name__)
+            nat.clip_state_init(blk, *clip)
+            self._clip_set[key] = clip
+        if partials is None or partials.numel() < chunks:
+            most = sum(nat.sumsq_chunks(p.numel() for p in group["params"]) for group in self.param_groups)
+            partials = self._clip_partials[dev] = torch.empty((most,), dtype=torch.float32, device=dev)
+        return blk, partials, chunks
+
+    def _clip_read(self):
+        for k in self.state:
+            if isinstance(k, str) and k.startswith(_CLIP_BLOCK):
+                return nat.clip_state_read(self.state[k])
+        return None
+
+    @property
+    def grad_norm(self):
+        """The global norm of the last step's gradients (of the penalised loss), as the device computed it: a read-back like
+        `iterations`.  None before the first step of an optimizer that clips, and always in one that does not."""
+        st = self._clip_read()
+        return float(st["norm"]) if st is not None and st["steps"] > 0 else None
+
+    @property
+    def clip_stats(self):
+        """{'steps', 'clipped', 'skipped'}: steps taken with clipping on, of them scaled down by `clipnorm`, of them skipped by
+        `skip_nonfinite` (a read-back; the counters start again with a restored optimizer)."""
+        st = self._clip_read()
+        return {k: int(st[k]) if st is not None else 0 for k in ("steps", "clipped", "skipped")}
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -369,6 +499,9 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
             with torch.enable_grad():
                 loss = closure()
         groups = self.param_groups
+        clip = self._clip()
+        if clip is not None:
+            self._clip_refuse()
         for gi, group in enumerate(groups):
             if self._mastering.setdefault(gi, group["master_weights"]) != group["master_weights"]:
                 raise ValueError("%s: `master_weights` cannot change after the first step (group %d)" % (type(self).__name__, gi))
@@ -386,10 +519,21 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
         for gi, (tables, _) in enumerate(plans):
             for _, _, key, dev, _ in tables:
                 self._push(key, gi, groups[gi], self._block(dev))
+        cblk = None
+        if clip is not None:                                       # the norm of g + weight_decay * w over every table, then the scale
+            cblk, partials, chunks = self._clip_buffers(plans, clip)
+            at = 0
+            for gi, (tables, _) in enumerate(plans):
+                for table, ps, _, _, bf16 in tables:
+                    n = nat.sumsq_chunks(p.numel() for p in ps)
+                    nat.optim_grad_sumsq_partials(table, bf16, groups[gi]["weight_decay"], partials[at:at + n])
+                    at += n
+            if cblk is not None:
+                nat.clip_finish(cblk, partials[:chunks])
         ticked = set()
         for gi, (tables, _) in enumerate(plans):
             for table, ps, key, _, bf16 in tables:
-                self._launch(table, self.state[key], gi, groups[gi], key not in ticked, bf16)
+                self._launch(table, self.state[key], gi, groups[gi], key not in ticked, bf16, cblk)
                 ticked.add(key)
                 _bump_versions(ps)                                  # caches keyed on `_version` (the bf16 shadows) must see the update
         if any(rest for _, rest in plans):
@@ -401,6 +545,8 @@ class _OneLaunchOptimizer(torch.optim.Optimizer, metaclass=_MasterWeightsOption)
 
 
 _flat = lambda t: t.detach().as_strided((t.numel(),), (1,))
+_NO_CLIP = dict(clipnorm=None, clipvalue=None, skip_nonfinite=False)   # the groups' defaults: no clipping
+_CLIP_BLOCK = "clip_state:"                                  # self.state[_CLIP_BLOCK + device]: the device's clip state block
 
 
 class SGD(_OneLaunchOptimizer):
@@ -414,6 +560,7 @@ class SGD(_OneLaunchOptimizer):
     _BLOCK = "sgd_state:"
     _HOST = "sgd_host"
     _BUFFER = {"torch": "momentum_buffer", "keras": "velocity"}
+    _FUSED_NEEDS = ", a non-zero momentum"
 
     def __init__(self, params, lr=0.01, momentum=0.0, weight_decay=0.0, decay=0.0, nesterov=False, rule="torch"):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, decay=decay, nesterov=bool(nesterov), rule=rule))
@@ -468,8 +615,8 @@ class SGD(_OneLaunchOptimizer):
         return (nat.sgd_table_bf16 if bf16 else nat.sgd_table)(*cols, dev)
 
     @staticmethod
-    def _launch(table, blk, gi, group, tick, bf16):
-        (nat.sgd_step_bf16 if bf16 else nat.sgd_step)(table, blk, gi, nat.SGD_RULES[group["rule"]], group["nesterov"], tick)
+    def _launch(table, blk, gi, group, tick, bf16, clip=None):
+        (nat.sgd_step_bf16 if bf16 else nat.sgd_step)(table, blk, gi, nat.SGD_RULES[group["rule"]], group["nesterov"], tick, clip)
 
     def _expressions(self, plans, lr_ts):
         for (_, rest), group, lr in zip(plans, self.param_groups, lr_ts):
@@ -580,8 +727,8 @@ class Adam(_OneLaunchOptimizer):
         return (nat.adam_table_bf16 if bf16 else nat.adam_table)(*cols, *[None] * ((6 if bf16 else 5) - len(cols)), dev)
 
     @staticmethod
-    def _launch(table, blk, gi, group, tick, bf16):
-        (nat.adam_step_bf16 if bf16 else nat.adam_step)(table, blk, gi, tick=tick)
+    def _launch(table, blk, gi, group, tick, bf16, clip=None):
+        (nat.adam_step_bf16 if bf16 else nat.adam_step)(table, blk, gi, tick=tick, clip=clip)
 
     def _expressions(self, plans, lr_ts):
         for (_, rest), group, lr_t in zip(plans, self.param_groups, lr_ts):

@@ -27,6 +27,23 @@ the prediction assembly, the framework's calls against the libssdhip call (the w
 the nodes of each captured graph.  Writes profiles/ssd7_head_training.json.
 
     python tools/time_ssd7_train_step.py --heads [--out FILE] [--batches 8,32] [--rounds 7] [--steps 200]
+
+--clipnorm VALUE times what gradient clipping adds to the `heads=True` step with SGD(master_weights=True): the optimizer built without
+the keyword ("clip_off": the step of before, no launch added) against `clipnorm=VALUE` ("clip_on": one sum-of-squares launch per tensor
+table, the finish launch, the clipped update), alternating in one process under the same protocol; plus the nodes of each captured
+graph and the clipped arm's `clip_stats` and last `grad_norm`.  The cost does not depend on whether VALUE binds: the multiplication by
+the scale always happens.  The result is one more entry of "visits" in profiles/optim_clip.json (the file is kept and appended to).
+
+    python tools/time_ssd7_train_step.py --clipnorm 1.0 [--out FILE] [--batches 8,32] [--rounds 7] [--steps 200]
+
+The unclipped arm against ANOTHER COMMIT (the parent of the change) is three more calls.  --clip-baseline is the same process with two
+unclipped arms ("clip_off", "clip_off_twin": two models and two graphs alternating, as above); it uses nothing but this file and the
+package's public interface, so a copy of this file runs it in a checkout of the other commit -- once before and once after the
+--clipnorm run.  --clip-parents BEFORE,AFTER (no GPU needed) then writes the two into the last visit as "parent_commit", with
+clip_off minus each and whether it lies within the sum of the two arms' spreads, and recounts "summary" over all visits.
+
+    python tools/time_ssd7_train_step.py --clip-baseline --out FILE          (in the other commit's checkout, before and after)
+    python tools/time_ssd7_train_step.py --clip-parents BEFORE,AFTER [--out profiles/optim_clip.json]
 """
 import argparse
 import json
@@ -65,14 +82,15 @@ def timed(torch, fn, n):
     return a.elapsed_time(b) / n
 
 
-def graphed_step(torch, model, images, y_true, optimizer="sgd", master_weights=False, counted=False):
-    """The replay of the step captured as one HIP graph; with `counted` (replay, the eager step, the graph object kept for its nodes)."""
+def graphed_step(torch, model, images, y_true, optimizer="sgd", master_weights=False, counted=False, clip=None):
+    """The replay of the step captured as one HIP graph; with `counted` (replay, the eager step, the graph object kept for its nodes,
+    the optimizer).  `clip`: the optimizer's clipping keywords."""
     from ssd_keras_amd.keras_loss_function.keras_ssd_loss import SSDLoss
     from ssd_keras_amd.optimizers import SGD, Adam
     if optimizer == "sgd":
-        opt = SGD(model.parameters(), lr=1e-5, momentum=0.9, master_weights=master_weights)
+        opt = SGD(model.parameters(), lr=1e-5, momentum=0.9, master_weights=master_weights, **(clip or {}))
     else:
-        opt = Adam(model.parameters(), lr=1e-5, epsilon=1e-8, master_weights=master_weights)
+        opt = Adam(model.parameters(), lr=1e-5, epsilon=1e-8, master_weights=master_weights, **(clip or {}))
     lf = SSDLoss(neg_pos_ratio=3, n_neg_min=0, alpha=1.0)
 
     def step():
@@ -97,7 +115,7 @@ def graphed_step(torch, model, images, y_true, optimizer="sgd", master_weights=F
     with torch.cuda.graph(graph):
         step()
     torch.cuda.synchronize()
-    return (graph.replay, step, graph) if counted else graph.replay
+    return (graph.replay, step, graph, opt) if counted else graph.replay
 
 
 def _graphed(torch, fn):
@@ -431,6 +449,101 @@ def heads_arms(torch, args):
     return result
 
 
+def clip_arms(torch, args):
+    """The `heads=True` step with SGD(master_weights=True) built without clipping keywords and with `clipnorm`: arms alternating, median
+    and spread as in main(); then the nodes of each captured graph and what the clipped optimizer counted."""
+    arms = {"clip_off": None, "clip_off_twin": None} if args.clip_baseline else {"clip_off": None, "clip_on": {"clipnorm": args.clipnorm}}
+    result = {"device": torch.cuda.get_device_name(0), "model": "SSD7 300x300x3, 5 classes, bf16, train(), fused_blocks(True, training=True, "
+              "convolutions=True, heads=True)", "clipnorm": args.clipnorm,
+              "step": "forward + SSDLoss + backward + ssd_keras_amd.optimizers.SGD(master_weights=True[, clipnorm=...]), one HIP graph",
+              "rounds": args.rounds, "steps_per_round": args.steps, "batches": {}}
+    for batch in [int(b) for b in args.batches.split(",")]:
+        images = torch.from_numpy(np.random.RandomState(100).randint(0, 256, size=(batch, 300, 300, 3)).astype(np.float32)).cuda()
+        models = {arm: build(torch, "conv").fused_blocks(True, training=True, convolutions=True, heads=True) for arm in arms}
+        with torch.no_grad():
+            n_anchor, width = build(torch, "off").eval()(images[:1]).shape[1:]
+        y_true = torch.from_numpy(synthetic_targets(batch, n_anchor, width)).cuda()
+        captured = {arm: graphed_step(torch, models[arm], images, y_true, "sgd", True, counted=True, clip=clip) for arm, clip in arms.items()}
+        replays = {arm: c[0] for arm, c in captured.items()}
+        for fn in replays.values():
+            timed(torch, fn, 40)
+        rounds = {arm: [] for arm in arms}
+        for _ in range(args.rounds):
+            for arm in arms:
+                rounds[arm].append(timed(torch, replays[arm], args.steps))
+        entry = {}
+        for arm in arms:
+            entry[arm] = {"median_ms": round(float(np.median(rounds[arm])), 4), "spread_ms": round(max(rounds[arm]) - min(rounds[arm]), 4),
+                          "rounds_ms": [round(v, 4) for v in rounds[arm]]}
+        for arm in arms:                                           # last: nothing here may disturb the timings above
+            entry[arm]["graph_nodes"] = graph_nodes(captured[arm][2])
+        if not args.clip_baseline:
+            opt = captured["clip_on"][3]
+            entry["clip_on"]["clip_stats"], entry["clip_on"]["grad_norm"] = opt.clip_stats, opt.grad_norm
+            entry["on_minus_off_ms"] = round(entry["clip_on"]["median_ms"] - entry["clip_off"]["median_ms"], 4)
+            del opt
+        result["batches"][str(batch)] = entry
+        print(json.dumps({"batch": batch, **entry}), flush=True)
+        del replays, captured, models
+        torch.cuda.empty_cache()
+    if args.clip_baseline:
+        return result
+    whole = _clip_file(args.out) or {k: v for k, v in result.items() if k != "batches"}
+    whole.setdefault("visits", []).append({"parent_protocol": CLIP_PROTOCOL, "batches": result["batches"]})
+    return _clip_summary(whole)
+
+
+CLIP_PROTOCOL = "--clip-baseline: two unclipped models and graphs alternating in the other commit's process, its first arm compared"
+CLIP_NOTE = ("one entry of `visits` per --clipnorm run.  clip_off is the optimizer built without the keywords: the step of before, no launch "
+             "added; on_minus_off_ms is what clipping costs and is reported, not gated.  parent_commit: the same step in a checkout of the "
+             "parent commit, processes of their own before and after the --clipnorm run; off_minus_parent_ms: clip_off's median minus "
+             "each; off_within_the_spreads: |that| <= the sum of the two arms' spreads (max - min over the rounds).  summary counts the "
+             "comparisons of all visits.  graph_nodes: the nodes of the captured step by type, read from the HIP graph itself")
+
+
+def _clip_file(path):
+    if os.path.exists(path):
+        with open(path) as f:
+            whole = json.load(f)
+        if "visits" in whole:
+            return whole
+    return None
+
+
+def _clip_summary(whole):
+    diffs, within = [], 0
+    for visit in whole["visits"]:
+        for entry in visit["batches"].values():
+            for when, d in entry.get("off_minus_parent_ms", {}).items():
+                diffs.append(round(1e3 * d, 1))
+                within += bool(entry["off_within_the_spreads"][when])
+    whole["summary"] = {"comparisons_with_the_parent_commit": len(diffs), "within_the_spreads": within,
+                        "outside_the_spreads": len(diffs) - within, "off_minus_parent_us": diffs}
+    whole["note"] = CLIP_NOTE
+    return whole
+
+
+def clip_parents(args):
+    """--clip-parents BEFORE,AFTER: the other commit's two --clip-baseline runs into the last visit of the file."""
+    whole = _clip_file(args.out)
+    if whole is None:
+        raise SystemExit("%s holds no --clipnorm visit to add the parent commit's runs to" % args.out)
+    runs = {}
+    for when, path in zip(("before", "after"), args.clip_parents.split(",")):
+        with open(path) as f:
+            runs[when] = json.load(f)["batches"]
+    visit = whole["visits"][-1]
+    visit["parent_protocol"] = CLIP_PROTOCOL
+    for batch, entry in visit["batches"].items():
+        off = entry["clip_off"]
+        entry["parent_commit"] = {when: run[batch]["clip_off"] for when, run in runs.items()}
+        entry["parent_commit_twin"] = {when: run[batch]["clip_off_twin"] for when, run in runs.items()}
+        entry["off_minus_parent_ms"] = {when: round(off["median_ms"] - was["median_ms"], 4) for when, was in entry["parent_commit"].items()}
+        entry["off_within_the_spreads"] = {when: bool(abs(off["median_ms"] - was["median_ms"]) <= off["spread_ms"] + was["spread_ms"])
+                                           for when, was in entry["parent_commit"].items()}
+    return _clip_summary(whole)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default: profiles/ssd7_conv_training.json (profiles/ssd7_master_weights.json with "
@@ -438,20 +551,37 @@ def main():
     ap.add_argument("--master-weights", action="store_true", help="time the optimizer's masters off against on instead of the three routes")
     ap.add_argument("--heads", action="store_true", help="time heads=True against the parent route (training=True, convolutions=True), "
                     "both with SGD(master_weights=True), instead of the three routes")
+    ap.add_argument("--clipnorm", type=float, default=None, help="time SGD(master_weights=True) without and with clipnorm=VALUE on the "
+                    "heads=True step instead of the three routes")
+    ap.add_argument("--clip-baseline", action="store_true", help="the --clipnorm process with two unclipped arms: run by a copy of this "
+                    "file in another commit's checkout")
+    ap.add_argument("--clip-parents", default=None, metavar="BEFORE,AFTER", help="two --clip-baseline results of the parent commit into "
+                    "the last visit of --out (no GPU)")
     ap.add_argument("--optimizer", choices=("sgd", "adam"), default="sgd", help="the optimizer of the --master-weights arms")
     ap.add_argument("--all-layers", action="store_true", help="the conv arm routes all seven layers, not SSD7.TRAIN_CONVS")
     ap.add_argument("--batches", default="8,32")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=200)
     args = ap.parse_args()
+    clipping = args.clipnorm is not None or args.clip_baseline
+    if args.clip_parents:                                          # (arithmetic on files: no GPU)
+        args.out = args.out or os.path.join(ROOT, "profiles", "optim_clip.json")
+        result = clip_parents(args)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps(result["summary"]))
+        return
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("time_ssd7_train_step.py needs a GPU: there is nothing to time without one")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "ssd7_head_training.json" if args.heads else
+        args.out = os.path.join(ROOT, "profiles", "optim_clip.json" if clipping else
+                                "ssd7_head_training.json" if args.heads else
                                 "ssd7_master_weights.json" if args.master_weights else "ssd7_conv_training.json")
-    if args.heads or args.master_weights:
-        result = heads_arms(torch, args) if args.heads else master_weights_arms(torch, args)
+    if clipping or args.heads or args.master_weights:
+        result = (clip_arms(torch, args) if clipping else
+                  heads_arms(torch, args) if args.heads else master_weights_arms(torch, args))
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1)
