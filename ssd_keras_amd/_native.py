@@ -1680,7 +1680,7 @@ def conv_bn_elu_pack(weight, out=None):
     if not weight.is_cuda or weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
         raise SsdHipError("weight must be a (Cout, Cin, k, k) CUDA tensor")
     cout, cin, k, _ = weight.shape
-    nbytes = int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(k)))
+    nbytes = _ssd7_image_bytes(cin, cout, k)
     if nbytes == 0:
         raise SsdHipError("conv_bn_elu: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, k))
     wb = weight.detach().to(torch.bfloat16)
@@ -1709,9 +1709,8 @@ def conv_bn_elu(x, packed, scale, shift, kernel, pool, out=None):
         x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
     b, cin, h, w = x.shape
     cout = scale.numel()
-    if (scale.dtype != torch.float32 or shift.dtype != torch.float32 or shift.numel() != cout or not scale.is_contiguous()
-            or not shift.is_contiguous() or not packed.is_contiguous() or packed.dtype != torch.bfloat16
-            or packed.numel() * 2 != int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(kernel)))):
+    if (scale.dtype != torch.float32 or shift.dtype != torch.float32 or shift.numel() != cout or not scale.is_contiguous() or not shift.is_contiguous()
+            or not packed.is_contiguous() or packed.dtype != torch.bfloat16 or packed.numel() * 2 != _ssd7_image_bytes(cin, cout, kernel)):
         raise SsdHipError("conv_bn_elu: float32 (Cout,) tables and the packed filters of this geometry (Cin = %d, Cout = %d, k = %d)"
                           % (cin, cout, kernel))
     ho, wo = (h // 2, w // 2) if pool else (h, w)
@@ -1736,9 +1735,29 @@ def _ssd7_map(t, name):
     return b, h, w, c
 
 
+def _ssd7_image_bytes(cin, cout, kernel):
+    """Bytes of the filter image of a (Cout, Cin, k, k) layer, 0 for a geometry that is none of SSD7's (ssdhip_conv_bn_elu_pack_bytes)."""
+    return int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(kernel)))
+
+
+def _ssd7_is_image(t, nbytes, dev=None):
+    """Whether `t` is a contiguous bf16 CUDA buffer of `nbytes` bytes (on `dev`, where given): the filter image of that size."""
+    return t.is_cuda and t.dtype == _torch().bfloat16 and t.is_contiguous() and t.numel() * 2 == nbytes and (dev is None or t.device == dev)
+
+
+def _ssd7_grad_outputs(likes, need, dev):
+    """What a weight-gradient entry writes, uninitialised: ([dw, db, ...], [dw's strides as the entry's `long long[4]`, ...], workspace of
+    `need` bytes) -- per tensor of `likes` a dw of its shape, dtype and element strides and a dense db of its dtype."""
+    torch = _torch()
+    outs = [t for like in likes for t in (torch.empty_strided(like.shape, like.stride(), dtype=like.dtype, device=dev),
+                                          torch.empty((like.shape[0],), dtype=like.dtype, device=dev))]
+    strides = [(ctypes.c_longlong * 4)(*[int(v) for v in like.stride()]) for like in likes]
+    return outs, strides, torch.empty((need,), dtype=torch.uint8, device=dev)
+
+
 def ssd7_conv_geometry(cin, cout, kernel):
     """Whether (Cin, Cout, kernel) is one of SSD7's seven convolutions -- what `ssd7_conv_bias` and `ssd7_conv_wgrad` cover."""
-    return int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(kernel))) != 0
+    return _ssd7_image_bytes(cin, cout, kernel) != 0
 
 
 def ssd7_conv_bias(x, packed, bias, cout, kernel, out=None):
@@ -1748,10 +1767,10 @@ def ssd7_conv_bias(x, packed, bias, cout, kernel, out=None):
     with the flipped image and no bias.  Returns (B, Cout, H, W) bf16 with NHWC memory."""
     torch = _torch()
     b, h, w, cin = _ssd7_map(x, "x")
-    nbytes = int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(kernel)))
+    nbytes = _ssd7_image_bytes(cin, cout, kernel)
     if nbytes == 0:
         raise SsdHipError("ssd7_conv_bias: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, kernel))
-    if not packed.is_cuda or packed.dtype != torch.bfloat16 or not packed.is_contiguous() or packed.numel() * 2 != nbytes:
+    if not _ssd7_is_image(packed, nbytes):
         raise SsdHipError("ssd7_conv_bias: `packed` must be the %d-byte bf16 filter image of this geometry" % nbytes)
     if bias is not None and (not bias.is_cuda or bias.dtype != torch.bfloat16 or bias.numel() != cout or not bias.is_contiguous()):
         raise SsdHipError("ssd7_conv_bias: bias must be a contiguous (%d,) bfloat16 CUDA tensor" % cout)
@@ -1770,11 +1789,11 @@ def ssd7_pack_images(weights):
     fwd, flipped = [], []
     for wt in weights:
         cout, cin, k, _ = wt.shape
-        n = int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(k)))
+        n = _ssd7_image_bytes(cin, cout, k)
         if n == 0:
             raise SsdHipError("ssd7_pack_images: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, k))
         fwd.append(torch.empty((n // 2,), dtype=torch.bfloat16, device=wt.device))
-        nt = int(load().ssdhip_conv_bn_elu_pack_bytes(int(cout), int(cin), int(k))) if k == 3 else 0
+        nt = _ssd7_image_bytes(cout, cin, k) if k == 3 else 0
         flipped.append(torch.empty((nt // 2,), dtype=torch.bfloat16, device=wt.device) if nt else None)
     return fwd, flipped
 
@@ -1793,16 +1812,12 @@ def ssd7_pack_filters(weights, fwd, flipped):
         if not wt.is_cuda or wt.dtype != torch.bfloat16 or wt.dim() != 4 or wt.shape[2] != wt.shape[3] or wt.device != dev:
             raise SsdHipError("ssd7_pack_filters: the weights are (Cout, Cin, k, k) bfloat16 tensors on one GPU")
         cout, cin, k, _ = wt.shape
-        need = (int(load().ssdhip_conv_bn_elu_pack_bytes(int(cin), int(cout), int(k))),
-                int(load().ssdhip_conv_bn_elu_pack_bytes(int(cout), int(cin), int(k))) if k == 3 else 0)
-        for img, nbytes in ((f, need[0]), (t, need[1])):
-            if img is not None and (nbytes == 0 or not img.is_cuda or img.device != dev or img.dtype != torch.bfloat16
-                                    or not img.is_contiguous() or img.numel() * 2 != nbytes):
+        for img, nbytes in ((f, _ssd7_image_bytes(cin, cout, k)), (t, _ssd7_image_bytes(cout, cin, k) if k == 3 else 0)):
+            if img is not None and (nbytes == 0 or not _ssd7_is_image(img, nbytes, dev)):
                 raise SsdHipError("ssd7_pack_filters: an image does not fit its layer (Cin = %d, Cout = %d, k = %d)" % (cin, cout, k))
         if f is None:
             raise SsdHipError("ssd7_pack_filters: every layer needs its forward image")
-    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in ts])
-    ints = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+    ptrs, ints = _host_arrays(n)
     strides = (ctypes.c_longlong * (4 * n))(*[int(v) for wt in weights for v in wt.stride()])
     launch("ssdhip_ssd7_pack_filters", dev, n, ptrs(weights), ptrs(fwd), ptrs(flipped), ints(wt.shape[1] for wt in weights),
            ints(wt.shape[0] for wt in weights), ints(wt.shape[2] for wt in weights), strides)
@@ -1830,15 +1845,11 @@ def ssd7_conv_wgrad(x, dy, kernel, like=None):
     need = int(load().ssdhip_ssd7_conv_wgrad_workspace_bytes(b, h, w, cin, cout, k))
     if need == 0:
         raise SsdHipError("ssd7_conv_wgrad: no kernel for Cin = %d, Cout = %d, k = %d" % (cin, cout, k))
-    if like is None:
-        dw = _empty_nhwc(cout, k, k, cin, torch.float32, dev)
-    else:
-        if tuple(like.shape) != (cout, cin, k, k) or like.dtype not in (torch.float32, torch.bfloat16):
-            raise SsdHipError("ssd7_conv_wgrad: `like` must be a (%d, %d, %d, %d) float32 or bfloat16 tensor" % (cout, cin, k, k))
-        dw = torch.empty_strided(like.shape, like.stride(), dtype=like.dtype, device=dev)
-    db = torch.empty((cout,), dtype=dw.dtype, device=dev)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    strides = (ctypes.c_longlong * 4)(*[int(v) for v in dw.stride()])
+    if like is None:                                     # (a shape-only tensor: nothing is allocated for it)
+        like = torch.empty((cout, k, k, cin), dtype=torch.float32, device="meta").permute(0, 3, 1, 2)
+    elif tuple(like.shape) != (cout, cin, k, k) or like.dtype not in (torch.float32, torch.bfloat16):
+        raise SsdHipError("ssd7_conv_wgrad: `like` must be a (%d, %d, %d, %d) float32 or bfloat16 tensor" % (cout, cin, k, k))
+    (dw, db), (strides,), ws = _ssd7_grad_outputs([like], need, dev)
     launch("ssdhip_ssd7_conv_wgrad_nhwc_bf16", dev, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), b, h, w, cin, cout, k,
            int(dw.dtype == torch.bfloat16), strides, _ptr(ws), need)
     return dw, db
@@ -1868,10 +1879,9 @@ def ssd7_head_images(conf_ws, loc_ws):
     fwd, flipped, bias = [], [], []
     for cw, lw in zip(conf_ws, loc_ws):
         torch = _ssd7_head_params(cw, lw, "ssd7_head_images")
-        cin = int(cw.shape[1])
         new = lambda n: torch.empty((n,), dtype=torch.bfloat16, device=cw.device)
-        fwd.append(new(int(load().ssdhip_conv_bn_elu_pack_bytes(cin, SSD7_HEAD_CP, 3)) // 2))
-        flipped.append(new(int(load().ssdhip_conv_bn_elu_pack_bytes(SSD7_HEAD_CP, cin, 3)) // 2))
+        fwd.append(new(_ssd7_image_bytes(cw.shape[1], SSD7_HEAD_CP, 3) // 2))
+        flipped.append(new(_ssd7_image_bytes(SSD7_HEAD_CP, cw.shape[1], 3) // 2))
         bias.append(new(SSD7_HEAD_CP))
     return fwd, flipped, bias
 
@@ -1893,14 +1903,10 @@ def ssd7_pack_heads(conf_ws, loc_ws, conf_bs, loc_bs, fwd, flipped, bias):
         for b_, wt in ((cb, cw), (lb, lw)):
             if b_.dtype != torch.bfloat16 or b_.device != dev or tuple(b_.shape) != (wt.shape[0],) or not b_.is_contiguous():
                 raise SsdHipError("ssd7_pack_heads: a head's bias is a contiguous (n,) bfloat16 tensor beside its filters")
-        need = (int(load().ssdhip_conv_bn_elu_pack_bytes(cin, SSD7_HEAD_CP, 3)), int(load().ssdhip_conv_bn_elu_pack_bytes(SSD7_HEAD_CP, cin, 3)),
-                2 * SSD7_HEAD_CP)
-        for img, nbytes in zip((f, t, pb), need):
-            if (img is None or not img.is_cuda or img.device != dev or img.dtype != torch.bfloat16 or not img.is_contiguous()
-                    or img.numel() * 2 != nbytes):
+        for img, nbytes in ((f, _ssd7_image_bytes(cin, SSD7_HEAD_CP, 3)), (t, _ssd7_image_bytes(SSD7_HEAD_CP, cin, 3)), (pb, 2 * SSD7_HEAD_CP)):
+            if img is None or not _ssd7_is_image(img, nbytes, dev):
                 raise SsdHipError("ssd7_pack_heads: a buffer does not fit its map (Cin = %d): see ssd7_head_images" % cin)
-    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-    ints = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+    ptrs, ints = _host_arrays(n)
     strides = (ctypes.c_longlong * (8 * n))(*[int(v) for cw, lw in zip(conf_ws, loc_ws) for v in tuple(cw.stride()) + tuple(lw.stride())])
     launch("ssdhip_ssd7_pack_heads", dev, n, ptrs(conf_ws), ptrs(loc_ws), ptrs(conf_bs), ptrs(loc_bs), ptrs(fwd), ptrs(flipped), ptrs(bias),
            ints(cw.shape[1] for cw in conf_ws), ints(cw.shape[0] for cw in conf_ws), ints(lw.shape[0] for lw in loc_ws), strides)
@@ -1931,13 +1937,7 @@ def ssd7_head_wgrad(x, dy, like_conf, like_loc):
     need = int(load().ssdhip_ssd7_head_wgrad_workspace_bytes(b, h, w, cin, SSD7_HEAD_CP))
     if need == 0:
         raise SsdHipError("ssd7_head_wgrad: no kernel for a %d x %d map of %d channels" % (h, w, cin))
-    outs = []
-    for like in (like_conf, like_loc):
-        outs.append(torch.empty_strided(like.shape, like.stride(), dtype=like.dtype, device=dev))
-        outs.append(torch.empty((like.shape[0],), dtype=like.dtype, device=dev))
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    sc = (ctypes.c_longlong * 4)(*[int(v) for v in outs[0].stride()])
-    sl = (ctypes.c_longlong * 4)(*[int(v) for v in outs[2].stride()])
+    outs, (sc, sl), ws = _ssd7_grad_outputs([like_conf, like_loc], need, dev)
     launch("ssdhip_ssd7_head_wgrad_nhwc_bf16", dev, _ptr(x), _ptr(dy), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), b, h, w,
            cin, SSD7_HEAD_CP, int(like_conf.shape[0]), int(like_loc.shape[0]), int(like_conf.dtype == torch.bfloat16), sc, sl, _ptr(ws), need)
     return tuple(outs)

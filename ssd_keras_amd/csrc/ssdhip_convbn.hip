@@ -2,6 +2,8 @@
 // [-> MaxPooling2D(2, 2) 'valid'] (reference models/keras_ssd7.py:277-309), as ONE launch each: gfx950, bf16 NHWC maps, float32
 // accumulation on v_mfma_f32_32x32x16_bf16, plain C++ and the MFMA builtin only.
 //
+// What this file shares with the weight-gradient files (geometries, tile grid, halo layouts, launch helper) is in ssdhip_ssd7.h.
+//
 // Geometries (exactly SSD7's; anything else is SSDHIP_E_BADARG):
 //   * 3 x 3, stride 1, pad 1, (Cin, Cout) in {(32, 48), (48, 64), (64, 64), (64, 48), (48, 48), (48, 32)}: K = 9 Cin, taps outer,
 //     channels inner.  Cout = 48 runs as two 32-column tiles whose last 16 filter rows are zero and whose lanes store nothing.
@@ -27,12 +29,12 @@
 
 #include "ssdhip.h"
 #include "ssdhip_bf16.h"
+#include "ssdhip_ssd7.h"
 
 namespace ssdhip {
 namespace {
 
-constexpr int CBN_THREADS = 256;                         // four waves: wave i owns rows 2 i, 2 i + 1 of a tile
-constexpr int CBN_TH = 8, CBN_TW = 32;                   // output tile
+// Four waves (S7_THREADS) on an S7_TH x S7_TW output tile: wave i owns rows 2 i, 2 i + 1.
 constexpr int CBN_TAB = 512;                             // LDS: scale[64] | shift[64] float32
 // Epilogue modes.  CBN_BN_ELU: the block of the inference path (below).  CBN_BIAS: the plain convolution of the TRAINING step and its
 // data gradient -- y = bf16(acc + float(bias[c])), one float32 add and one rounding, full-size map only; the bias is the layer's own
@@ -51,13 +53,6 @@ struct CbnParams {
 };
 
 __device__ __forceinline__ float cbn_max(float a, float b) { return (a > b || a != a) ? a : b; }    // NaN wins, as in max_pool2d
-
-__device__ __forceinline__ void cbn_tile_origin(const CbnParams& p, int tile, int& b, int& h0, int& w0) {
-    const int wt = tile % p.WT, q = tile / p.WT;
-    b = q / p.HT;
-    h0 = (q - b * p.HT) * CBN_TH;
-    w0 = wt * CBN_TW;
-}
 
 // acc[r][nt]: rows h, h + 1 of image b, column w = the lane's (lane & 31), channel (v & 3) + 8 (v >> 2) + 4 (lane >> 5) of tile nt.
 template <int COUT, bool POOL, int EPI>
@@ -120,21 +115,21 @@ __device__ __forceinline__ void cbn_load_tables(float* tab, const CbnParams& p, 
 }
 
 // ---- 3 x 3 ------------------------------------------------------------------------------------------------------------------------
-// LDS: tables | filters [tap][NT 32 co][Cin + 8] | halo [10 x 34 pixels][Cin + 8].  The 16 bytes of padding behind every row of Cin
-// values keep the fragment reads of 32 consecutive rows off one bank set; they are never read.
+// LDS: tables | filters [tap][NT 32 co][Cin + 8] | halo [10 x 34 pixels][Cin + 8] (S7Halo3).  The 16 bytes of padding behind every row
+// of Cin values keep the fragment reads of 32 consecutive rows off one bank set; they are never read.
 template <int CIN, int COUT>
 struct Cbn3 {
-    static constexpr int NT = (COUT + 31) / 32, PS = CIN * 2 + 16, KS = CIN / 16, CH = CIN / 8;
-    static constexpr int HR = CBN_TH + 2, HC = CBN_TW + 2, HPX = HR * HC, NCHUNK = HPX * CH;
-    static constexpr int NLD = (NCHUNK + CBN_THREADS - 1) / CBN_THREADS;
-    static constexpr int WBYTES = 9 * NT * 32 * PS, LDS = CBN_TAB + WBYTES + HPX * PS;
+    using Halo = S7Halo3<CIN>;
+    static constexpr int NT = (COUT + 31) / 32, PS = Halo::PS, KS = CIN / 16;
+    static constexpr int WBYTES = 9 * NT * 32 * PS, LDS = CBN_TAB + WBYTES + Halo::BYTES;
     static_assert(LDS <= 160 * 1024 && CIN % 16 == 0, "LDS budget; whole MFMA steps");
 };
 
 template <int CIN, int COUT, bool POOL, int EPI>
-__global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p) {
+__global__ __launch_bounds__(S7_THREADS) void convbn3_kernel(const CbnParams p) {
     using G = Cbn3<CIN, COUT>;
-    constexpr int NT = G::NT, PS = G::PS, KS = G::KS, CH = G::CH, HC = G::HC, NCHUNK = G::NCHUNK, NLD = G::NLD;
+    using Halo = typename G::Halo;
+    constexpr int NT = G::NT, PS = G::PS, KS = G::KS, CH = Halo::CH, HC = Halo::HC, NCHUNK = Halo::NCHUNK, NLD = Halo::NLD;
     extern __shared__ __attribute__((aligned(16))) unsigned char cbn_lds[];
     float* tab = reinterpret_cast<float*>(cbn_lds);
     unsigned char* wl = cbn_lds + CBN_TAB;
@@ -145,13 +140,13 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
     int tile = (int)blockIdx.x;
     if (tile >= p.tiles) return;
 
-    // the 16-byte chunks of a tile's halo, dealt to the threads: chunk n = pixel n / CH (row hr, column hc), channels 8 (n % CH) ...
+    // the 16-byte chunks of a tile's halo (S7Halo3), dealt to the threads: chunk n = pixel n / CH (row hr, column hc), channels 8 (n % CH) ...
     auto fetch = [&](int t, u32x4 (&r)[NLD]) {
         int b, h0, w0;
-        cbn_tile_origin(p, t, b, h0, w0);
+        ssd7_tile_origin(p, t, b, h0, w0);
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            const int n = tid + CBN_THREADS * i, px = n / CH, c = n - px * CH, hr = px / HC, hc = px - hr * HC;
+            const int n = tid + S7_THREADS * i, px = n / CH, c = n - px * CH, hr = px / HC, hc = px - hr * HC;
             const int h = h0 - 1 + hr, w = w0 - 1 + hc;
             r[i] = u32x4{0u, 0u, 0u, 0u};            // outside the image: the layer's zero padding
             if (n < NCHUNK && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W)
@@ -161,14 +156,14 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
     auto stash = [&](const u32x4 (&r)[NLD]) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            const int n = tid + CBN_THREADS * i, px = n / CH, c = n - px * CH;
+            const int n = tid + S7_THREADS * i, px = n / CH, c = n - px * CH;
             if (n < NCHUNK) *reinterpret_cast<u32x4*>(hl + px * PS + c * 16) = r[i];
         }
     };
 
     u32x4 raw[NLD];
     fetch(tile, raw);
-    for (int i = tid; i < G::WBYTES / 16; i += CBN_THREADS)              // the resident filters: the packed image as it is
+    for (int i = tid; i < G::WBYTES / 16; i += S7_THREADS)              // the resident filters: the packed image as it is
         reinterpret_cast<u32x4*>(wl)[i] = reinterpret_cast<const u32x4*>(p.w)[i];
     cbn_load_tables<EPI>(tab, p, COUT, tid);
 
@@ -201,21 +196,20 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn3_kernel(const CbnParams p)
                 }
             }
         int b, h0, w0;
-        cbn_tile_origin(p, tile, b, h0, w0);
+        ssd7_tile_origin(p, tile, b, h0, w0);
         cbn_epilogue<COUT, POOL, EPI>(acc, tab, p, b, h0 + 2 * wave, w0 + r31, lane);
         __syncthreads();                                 // every wave is done with the halo before the next one overwrites it
     }
 }
 
 // ---- 5 x 5, Cin = 3, Cout = 32 ------------------------------------------------------------------------------------------------
-// Halo: 12 rows x 36 pixels x 3 channels = 108 bf16 a row, in 224-byte LDS rows (the 8 bytes behind the data stay zero: the sixteenth
-// k of the last columns and the aligned dword reads reach into them).  Packed filters: [kh][co][16] bf16, k = 3 kw + ci, k = 15 zero.
-constexpr int CBN5_HR = CBN_TH + 4, CBN5_HC = CBN_TW + 4, CBN5_ROW = CBN5_HC * 3, CBN5_RS = 224, CBN5_NEL = CBN5_HR * CBN5_ROW;
-constexpr int CBN5_NLD = (CBN5_NEL + CBN_THREADS - 1) / CBN_THREADS;
+// Halo: S7Halo5 (the 8 bytes behind a row's data stay zero: the sixteenth k of the last columns and the aligned dword reads reach into
+// them).  Packed filters: [kh][co][16] bf16, k = 3 kw + ci, k = 15 zero.
 
 template <bool POOL, int EPI>
-__global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p) {
-    __shared__ __attribute__((aligned(16))) unsigned char cbn_lds[CBN_TAB + CBN5_HR * CBN5_RS];
+__global__ __launch_bounds__(S7_THREADS) void convbn5_kernel(const CbnParams p) {
+    using Halo = S7Halo5;
+    __shared__ __attribute__((aligned(16))) unsigned char cbn_lds[CBN_TAB + Halo::BYTES];
     float* tab = reinterpret_cast<float*>(cbn_lds);
     unsigned char* hl = cbn_lds + CBN_TAB;
 
@@ -223,40 +217,41 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p)
     const int stride = (int)gridDim.x;
     int tile = (int)blockIdx.x;
     if (tile >= p.tiles) return;
+
     const unsigned short* x = reinterpret_cast<const unsigned short*>(p.x);
 
-    auto fetch = [&](int t, unsigned short (&r)[CBN5_NLD]) {
+    auto fetch = [&](int t, unsigned short (&r)[Halo::NLD]) {
         int b, h0, w0;
-        cbn_tile_origin(p, t, b, h0, w0);
+        ssd7_tile_origin(p, t, b, h0, w0);
 #pragma unroll
-        for (int i = 0; i < CBN5_NLD; ++i) {
-            const int n = tid + CBN_THREADS * i, hr = n / CBN5_ROW, e = n - hr * CBN5_ROW, hc = e / 3;
+        for (int i = 0; i < Halo::NLD; ++i) {
+            const int n = tid + S7_THREADS * i, hr = n / Halo::ROW, e = n - hr * Halo::ROW, hc = e / 3;
             const int h = h0 - 2 + hr, w = w0 - 2 + hc;
             r[i] = 0;
-            if (n < CBN5_NEL && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W)
+            if (n < Halo::NEL && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W)
                 r[i] = x[(((size_t)b * p.H + h) * p.W + w) * 3 + (e - hc * 3)];
         }
     };
-    auto stash = [&](const unsigned short (&r)[CBN5_NLD]) {
+    auto stash = [&](const unsigned short (&r)[Halo::NLD]) {
 #pragma unroll
-        for (int i = 0; i < CBN5_NLD; ++i) {
-            const int n = tid + CBN_THREADS * i, hr = n / CBN5_ROW, e = n - hr * CBN5_ROW;
-            if (n < CBN5_NEL) *reinterpret_cast<unsigned short*>(hl + hr * CBN5_RS + e * 2) = r[i];
+        for (int i = 0; i < Halo::NLD; ++i) {
+            const int n = tid + S7_THREADS * i, hr = n / Halo::ROW, e = n - hr * Halo::ROW;
+            if (n < Halo::NEL) *reinterpret_cast<unsigned short*>(hl + hr * Halo::RS + e * 2) = r[i];
         }
     };
 
-    unsigned short raw[CBN5_NLD];
+    unsigned short raw[Halo::NLD];
     fetch(tile, raw);
     bf16x8 a[5];
 #pragma unroll
     for (int kh = 0; kh < 5; ++kh) a[kh] = *reinterpret_cast<const bf16x8*>(p.w + ((kh * 32 + r31) * 16 + khalf * 8) * 2);
     cbn_load_tables<EPI>(tab, p, 32, tid);
-    if (tid < CBN5_HR * 2) *reinterpret_cast<unsigned*>(hl + (tid >> 1) * CBN5_RS + CBN5_ROW * 2 + (tid & 1) * 4) = 0u;
+    if (tid < Halo::HR * 2) *reinterpret_cast<unsigned*>(hl + (tid >> 1) * Halo::RS + Halo::ROW * 2 + (tid & 1) * 4) = 0u;
 
     // the lane's operand of kernel row kh: 16 bytes at 6 bytes a column, i.e. on a half-dword boundary for odd columns -- five aligned
     // dwords, shifted by two bytes where needed; the sixteenth k (the next pixel's first channel) is cleared, its filter value is zero
     const unsigned off = (unsigned)(r31 * 6 + khalf * 16);
-    const unsigned char* bptr = hl + (2 * wave) * CBN5_RS + (off & ~3u);
+    const unsigned char* bptr = hl + (2 * wave) * Halo::RS + (off & ~3u);
     const unsigned shift = (off & 2u) * 8u, last = khalf ? 0x0000ffffu : 0xffffffffu;
     for (; tile < p.tiles; tile += stride) {
         stash(raw);
@@ -272,7 +267,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p)
         for (int kh = 0; kh < 5; ++kh)
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                const unsigned* q = reinterpret_cast<const unsigned*>(bptr + (r + kh) * CBN5_RS);
+                const unsigned* q = reinterpret_cast<const unsigned*>(bptr + (r + kh) * Halo::RS);
                 const unsigned d[5] = {q[0], q[1], q[2], q[3], q[4]};
                 u32x4 f;
 #pragma unroll
@@ -281,7 +276,7 @@ __global__ __launch_bounds__(CBN_THREADS) void convbn5_kernel(const CbnParams p)
                 acc[r][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[kh], __builtin_bit_cast(bf16x8, f), acc[r][0], 0, 0, 0);
             }
         int b, h0, w0;
-        cbn_tile_origin(p, tile, b, h0, w0);
+        ssd7_tile_origin(p, tile, b, h0, w0);
         cbn_epilogue<32, POOL, EPI>(acc, tab, p, b, h0 + 2 * wave, w0 + r31, lane);
         __syncthreads();
     }
@@ -297,23 +292,23 @@ int cbn_cu_count() {
     return n;
 }
 
-template <int CIN, int COUT, bool POOL, int EPI = CBN_BN_ELU>
-int cbn_launch3(const CbnParams& p, hipStream_t stream) {
-    using G = Cbn3<CIN, COUT>;
-    auto fn = convbn3_kernel<CIN, COUT, POOL, EPI>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (attr != hipSuccess) return SSDHIP_E_LAUNCH;
-    int per_cu = (160 * 1024) / G::LDS;                  // workgroups that fit a CU's LDS; two keep a CU busy across the barriers
-    per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
-    const long long cap = (long long)cbn_cu_count() * per_cu;
-    const int grid = (int)(p.tiles < cap ? p.tiles : cap);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(CBN_THREADS), G::LDS, stream, p);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
-}
-
-template <int CIN, int COUT>
-int cbn_launch3(const CbnParams& p, int pool, hipStream_t stream) {
-    return pool ? cbn_launch3<CIN, COUT, true>(p, stream) : cbn_launch3<CIN, COUT, false>(p, stream);
+// The geometry's instantiation of one epilogue.  3 x 3: as many workgroups as fit the CUs' LDS, at most two a CU (two keep a CU busy
+// across the barriers); 5 x 5: four a CU.
+template <bool POOL, int EPI>
+int cbn_launch(const CbnParams& p, int Cin, int Cout, int kernel, hipStream_t stream) {
+    if (kernel == 5) {
+        const long long cap = (long long)cbn_cu_count() * 4;
+        return ssd7_launch<convbn5_kernel<POOL, EPI>>(dim3((int)(p.tiles < cap ? p.tiles : cap)), 0, 0, stream, p);
+    }
+    int rc = SSDHIP_E_BADARG;
+    ssd7_for_pair3(Cin, Cout, [&](auto ci, auto co) {
+        constexpr int CIN = decltype(ci)::value, COUT = decltype(co)::value, LDS = Cbn3<CIN, COUT>::LDS;
+        int per_cu = (160 * 1024) / LDS;
+        per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
+        const long long cap = (long long)cbn_cu_count() * per_cu;
+        rc = ssd7_launch<convbn3_kernel<CIN, COUT, POOL, EPI>>(dim3((int)(p.tiles < cap ? p.tiles : cap)), LDS, LDS, stream, p);
+    });
+    return rc;
 }
 
 // ---- filter images, refreshed on the device ----------------------------------------------------------------------------------------
@@ -332,10 +327,7 @@ struct CbnPackTable {
     CbnPackLayer layer[CBN_PACK_MAX];
 };
 
-// elements of the image of a (rows = Cout, cols = Cin) 3 x 3 layer
-__host__ __device__ inline int cbn_image3_elems(int cin, int cout) { return 9 * ((cout + 31) / 32) * 32 * (cin + 8); }
-
-__global__ __launch_bounds__(256) void cbn_pack_kernel(const CbnPackTable t) {
+__global__ __launch_bounds__(S7_THREADS) void cbn_pack_kernel(const CbnPackTable t) {
     const CbnPackLayer& L = t.layer[blockIdx.y >> 1];
     const bool flip = blockIdx.y & 1;
     bf16_t* out = flip ? L.flip : L.fwd;
@@ -349,14 +341,11 @@ __global__ __launch_bounds__(256) void cbn_pack_kernel(const CbnPackTable t) {
         return;
     }
     // the image's rows / columns: forward (Cout, Cin); flipped (Cin, Cout), element (kh, kw, r, c) = w[c][r][2 - kh][2 - kw]
-    const int rows = flip ? L.cin : L.cout, cols = flip ? L.cout : L.cin, rp = (rows + 31) / 32 * 32, cp = cols + 8;
-    for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i < 9 * rp * cp; i += step) {
-        const int c = i % cp, q = i / cp, r = q % rp, tap = q / rp, kh = tap / 3, kw = tap - 3 * kh;
-        bf16_t v = 0;
-        if (r < rows && c < cols)
-            v = flip ? L.w[c * L.s[0] + r * L.s[1] + (2 - kh) * L.s[2] + (2 - kw) * L.s[3]] : L.w[r * L.s[0] + c * L.s[1] + kh * L.s[2] + kw * L.s[3]];
-        out[i] = v;
-    }
+    ssd7_write_image3(out, flip ? L.cin : L.cout, flip ? L.cout : L.cin, (int)(blockIdx.x * blockDim.x + threadIdx.x), step,
+                      [&](int r, int c, int kh, int kw) {
+                          return flip ? L.w[c * L.s[0] + r * L.s[1] + (2 - kh) * L.s[2] + (2 - kw) * L.s[3]]
+                                      : L.w[r * L.s[0] + c * L.s[1] + kh * L.s[2] + kw * L.s[3]];
+                      });
 }
 
 }  // namespace
@@ -365,10 +354,8 @@ __global__ __launch_bounds__(256) void cbn_pack_kernel(const CbnPackTable t) {
 using namespace ssdhip;
 
 extern "C" size_t ssdhip_conv_bn_elu_pack_bytes(int Cin, int Cout, int kernel) {
-    if (kernel == 5 && Cin == 3 && Cout == 32) return 5 * 32 * 16 * 2;
-    if (kernel != 3) return 0;
-    const bool ok = (Cin == 32 && Cout == 48) || (Cin == 48 && (Cout == 64 || Cout == 48 || Cout == 32)) || (Cin == 64 && (Cout == 64 || Cout == 48));
-    return ok ? (size_t)9 * ((Cout + 31) / 32) * 32 * (Cin * 2 + 16) : 0;
+    if (!ssd7_geometry(Cin, Cout, kernel)) return 0;
+    return kernel == 5 ? 5 * 32 * 16 * 2 : (size_t)ssd7_image3_elems(Cout, Cin) * 2;
 }
 
 namespace ssdhip {
@@ -376,39 +363,19 @@ namespace {
 // Both epilogues: the checks every launch shares, then the geometry's instantiation (scale / shift: CBN_BN_ELU; bias: CBN_BIAS).
 int cbn_run(int epi, const void* x, const void* w_packed, const float* scale, const float* shift, const void* bias, void* y, int B, int H, int W,
             int Cin, int Cout, int kernel, int pool, hipStream_t stream) {
-    if (!x || !w_packed || !y || B <= 0 || H <= 0 || W <= 0) return SSDHIP_E_BADARG;
+    if (!x || !w_packed || !y || !ssd7_geometry(Cin, Cout, kernel)) return SSDHIP_E_BADARG;
     if (epi == CBN_BN_ELU && (!scale || !shift)) return SSDHIP_E_BADARG;
-    if (ssdhip_conv_bn_elu_pack_bytes(Cin, Cout, kernel) == 0) return SSDHIP_E_BADARG;
     if (pool && (H < 2 || W < 2)) return SSDHIP_E_BADARG;
     if ((((uintptr_t)w_packed | (uintptr_t)y) & 15) || ((uintptr_t)x & (kernel == 3 ? 15 : 1)) || (((uintptr_t)scale | (uintptr_t)shift) & 3) ||
         ((uintptr_t)bias & 1))
         return SSDHIP_E_BADARG;
     CbnParams p;
+    if (!ssd7_tile_grid(B, H, W, p)) return SSDHIP_E_BADARG;
     p.x = static_cast<const unsigned char*>(x); p.w = static_cast<const unsigned char*>(w_packed);
     p.scale = scale; p.shift = shift; p.bias = static_cast<const bf16_t*>(bias); p.y = static_cast<unsigned char*>(y);
-    p.B = B; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;
-    p.HT = (H + CBN_TH - 1) / CBN_TH; p.WT = (W + CBN_TW - 1) / CBN_TW;
-    const long long tiles = (long long)B * p.HT * p.WT;
-    if (tiles > 0x3fffffffLL || (long long)B * H * W > 0x3fffffffLL) return SSDHIP_E_BADARG;
-    p.tiles = (int)tiles;
-    if (kernel == 5) {
-        const long long cap = (long long)cbn_cu_count() * 4;
-        const int grid = (int)(tiles < cap ? tiles : cap);
-        if (epi == CBN_BIAS) hipLaunchKernelGGL((convbn5_kernel<false, CBN_BIAS>), dim3(grid), dim3(CBN_THREADS), 0, stream, p);
-        else if (pool) hipLaunchKernelGGL((convbn5_kernel<true, CBN_BN_ELU>), dim3(grid), dim3(CBN_THREADS), 0, stream, p);
-        else hipLaunchKernelGGL((convbn5_kernel<false, CBN_BN_ELU>), dim3(grid), dim3(CBN_THREADS), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
-    }
-    if (epi == CBN_BIAS) {
-        if (Cin == 32) return cbn_launch3<32, 48, false, CBN_BIAS>(p, stream);
-        if (Cin == 48)
-            return Cout == 64 ? cbn_launch3<48, 64, false, CBN_BIAS>(p, stream)
-                              : Cout == 48 ? cbn_launch3<48, 48, false, CBN_BIAS>(p, stream) : cbn_launch3<48, 32, false, CBN_BIAS>(p, stream);
-        return Cout == 64 ? cbn_launch3<64, 64, false, CBN_BIAS>(p, stream) : cbn_launch3<64, 48, false, CBN_BIAS>(p, stream);
-    }
-    if (Cin == 32) return cbn_launch3<32, 48>(p, pool, stream);
-    if (Cin == 48) return Cout == 64 ? cbn_launch3<48, 64>(p, pool, stream) : Cout == 48 ? cbn_launch3<48, 48>(p, pool, stream) : cbn_launch3<48, 32>(p, pool, stream);
-    return Cout == 64 ? cbn_launch3<64, 64>(p, pool, stream) : cbn_launch3<64, 48>(p, pool, stream);
+    p.Ho = H / 2; p.Wo = W / 2;
+    if (epi == CBN_BIAS) return cbn_launch<false, CBN_BIAS>(p, Cin, Cout, kernel, stream);
+    return pool ? cbn_launch<true, CBN_BN_ELU>(p, Cin, Cout, kernel, stream) : cbn_launch<false, CBN_BN_ELU>(p, Cin, Cout, kernel, stream);
 }
 }  // namespace
 }  // namespace ssdhip
@@ -430,23 +397,15 @@ extern "C" int ssdhip_ssd7_pack_filters(int n_layers, const void* const* weights
     int most = 0;
     for (int i = 0; i < n_layers; ++i) {
         CbnPackLayer& L = t.layer[i];
-        if (!weights[i] || !fwd[i] || ssdhip_conv_bn_elu_pack_bytes(Cin[i], Cout[i], kernel[i]) == 0) return SSDHIP_E_BADARG;
+        if (!weights[i] || !fwd[i] || !ssd7_geometry(Cin[i], Cout[i], kernel[i])) return SSDHIP_E_BADARG;
         if (kernel[i] == 5 && flipped[i]) return SSDHIP_E_BADARG;       // the first layer has no data gradient
         if (((uintptr_t)weights[i] | (uintptr_t)fwd[i] | (uintptr_t)flipped[i]) & 1) return SSDHIP_E_BADARG;
-        long long reach = 0;                              // the farthest element the strides address: a sanity bound, not the tensor's size
-        const int dims[4] = {Cout[i], Cin[i], kernel[i], kernel[i]};
-        for (int d = 0; d < 4; ++d) {
-            if (strides[4 * i + d] < 0) return SSDHIP_E_BADARG;
-            reach += strides[4 * i + d] * (dims[d] - 1);
-            L.s[d] = strides[4 * i + d];
-        }
-        if (reach > 0x3fffffffLL) return SSDHIP_E_BADARG;
+        if (!ssd7_strides(strides + 4 * i, Cout[i], Cin[i], kernel[i], L.s)) return SSDHIP_E_BADARG;
         L.w = static_cast<const bf16_t*>(weights[i]); L.fwd = static_cast<bf16_t*>(fwd[i]); L.flip = static_cast<bf16_t*>(flipped[i]);
         L.cin = Cin[i]; L.cout = Cout[i]; L.kernel = kernel[i];
-        const int n = kernel[i] == 5 ? 5 * 32 * 16 : cbn_image3_elems(Cin[i] > Cout[i] ? Cin[i] : Cout[i], Cin[i] > Cout[i] ? Cin[i] : Cout[i]);
+        const int side = Cin[i] > Cout[i] ? Cin[i] : Cout[i], n = kernel[i] == 5 ? 5 * 32 * 16 : ssd7_image3_elems(side, side);
         most = n > most ? n : most;
     }
-    const int bx = (most + 256 * 4 - 1) / (256 * 4);      // about four elements a thread in the largest image
-    hipLaunchKernelGGL(cbn_pack_kernel, dim3(bx, 2 * n_layers), dim3(256), 0, static_cast<hipStream_t>(stream_), t);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    const int bx = (most + S7_THREADS * 4 - 1) / (S7_THREADS * 4);      // about four elements a thread in the largest image
+    return ssd7_launch<cbn_pack_kernel>(dim3(bx, 2 * n_layers), 0, 0, static_cast<hipStream_t>(stream_), t);
 }

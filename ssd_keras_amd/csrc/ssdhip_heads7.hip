@@ -18,7 +18,7 @@
 // useful share of the contraction is H W / ((H + 2)(W + 2)): 90 / 81 / 67 / 44 % on 37 / 18 / 9 / 4-pixel maps.
 //   * a workgroup of four waves walks chunks of 256 list positions.  Per chunk the loader writes the dy rows [256][48 + 8] and the x
 //     rows [256 + 2 (W + 3)][Cin + 8] into LDS -- zeros on the border and outside the list, written by the loader itself -- and both
-//     operands are read with ds_read_b64_tr_b16 exactly as in ssdhip_wgrad7.hip (a lane gets four consecutive positions of its
+//     operands are read with ds_read_b64_tr_b16 through ssd7_fragment (ssdhip_ssd7.h: a lane gets four consecutive positions of its
 //     channel; 48 channels run as two 32-channel blocks whose upper 16 lanes read what lies behind the row, inside the allocation, and
 //     whose results are never stored).  A tap displaces the x row address by a multiple of the row pitch: always 8-byte aligned.
 //   * the work is split over position chunks (grid x: split s owns chunks [s T, (s + 1) T)) AND over the three kernel rows (grid y),
@@ -26,7 +26,7 @@
 //     accumulators, one block per wave.  Cin = 32 has only two blocks: its second pair of waves takes the odd 16-position steps and
 //     writes a partial tile of its own.  The kernel row kh = 1 also adds the bias gradient (one more MFMA per step against ones).
 //   * every (split, step parity) writes one float32 partial [48][3][3][Cin] + [48], each element exactly once (the three kernel rows
-//     write disjoint thirds); a second launch adds the partials in index order in float32 and writes dw_conf, db_conf, dw_loc and
+//     write disjoint thirds); a second launch (ssd7_reduce_kernel) adds the partials in index order in float32 and writes dw_conf, db_conf, dw_loc and
 //     db_loc once -- float32, or rounded once to bf16 -- through the parameters' element strides, dropping the padding rows.
 //     Bit-reproducible; no atomics, no last-workgroup finish, no memset.  The plan is host arithmetic on the shape only.
 #include <hip/hip_runtime.h>
@@ -34,20 +34,18 @@
 
 #include "ssdhip.h"
 #include "ssdhip_bf16.h"
+#include "ssdhip_ssd7.h"
 
 namespace ssdhip {
 namespace {
 
-constexpr int H7_THREADS = 256;                          // four waves
-constexpr int H7_CP = 48;                                // packed output channels
+constexpr int H7_CP = 48;                               // packed output channels
 constexpr int H7_CHUNK = 256;                            // list positions per chunk: 16 MFMA steps of 16
 constexpr int H7_MIN_SPLITS = 8, H7_MAX_SPLITS = 64;     // x 3 kernel rows = 24 .. 192 workgroups
 constexpr int H7_MAX_W = 256;                            // x rows in LDS: 256 + 2 (W + 3), at most 774 x 144 bytes
 constexpr int H7_DS = H7_CP * 2 + 16;                    // dy row pitch
 constexpr int H7_TAIL = 64;                              // LDS behind the last dy row: what the padded lanes of that row reach
 constexpr int H7_PACK_MAX = 8;
-
-typedef short h7_s16x4 __attribute__((ext_vector_type(4)));
 
 struct H7Plan {
     int splits, chunks_per_split, chunks, last_chunks, positions, ksplit;
@@ -62,7 +60,7 @@ size_t h7_lds_bytes(int W, int Cin) { return (size_t)(H7_CHUNK + 2 * (W + 3)) * 
 bool h7_plan(int B, int H, int W, int Cin, int Cp, H7Plan& pl) {
     if (B <= 0 || H <= 0 || W <= 0 || W > H7_MAX_W || Cp != H7_CP || !h7_cin(Cin)) return false;
     const long long positions = (long long)B * (H + 2) * (W + 2);
-    if (positions > 0x3fffffffLL) return false;
+    if (positions > S7_MAX_INDEX) return false;
     const long long chunks = (positions + H7_CHUNK - 1) / H7_CHUNK;
     const int ksplit = Cin == 32 ? 2 : 1;
     const long long operand = (long long)B * H * W * (Cin + H7_CP) * 2, slot = h7_slot_floats(Cin) * 4 * ksplit;
@@ -87,18 +85,6 @@ struct H7Params {
     int positions, chunks, chunks_per_split;
 };
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __attribute__((address_space(3))) unsigned char h7_lds_byte;
-// the fragment of a 16-position step (ssdhip_wgrad7.hip, w7_fragment): element j of lane half h is position 8 (j >> 2) + 4 h + (j & 3)
-// of the step, in both operands
-__device__ __forceinline__ u32x4 h7_fragment(h7_lds_byte* lds, u32 off, u32 rows8) {
-    const h7_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) h7_s16x4*)(lds + off));
-    const h7_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) h7_s16x4*)(lds + off + rows8));
-    const u32x2 l = __builtin_bit_cast(u32x2, lo), h = __builtin_bit_cast(u32x2, hi);
-    return u32x4{l.x, l.y, h.x, h.y};
-}
-#endif
-
 // rows [first, first + rows) of the padded list of a [B, H, W, C] map into LDS at `pitch` bytes a row: 16-byte pieces dealt to the
 // threads; a border pixel and a position outside the list are zeros
 template <int C>
@@ -106,7 +92,7 @@ __device__ __forceinline__ void h7_load_rows(const unsigned char* src, unsigned 
                                              int positions, int tid) {
     constexpr int CH = C / 8;
     const int Wp = W + 2, plane = (H + 2) * Wp;
-    for (int n = tid; n < rows * CH; n += H7_THREADS) {
+    for (int n = tid; n < rows * CH; n += S7_THREADS) {
         const int j = n / CH, c = n - j * CH, q = first + j;
         u32x4 v = u32x4{0u, 0u, 0u, 0u};
         if (q >= 0 && q < positions) {
@@ -120,7 +106,7 @@ __device__ __forceinline__ void h7_load_rows(const unsigned char* src, unsigned 
 
 // LDS: x rows [256 + 2 (W + 3)][Cin + 8] | dy rows [256][48 + 8] | tail.  x row j is list position chunk 256 - (W + 3) + j.
 template <int CIN>
-__global__ __launch_bounds__(H7_THREADS) void head_wgrad_kernel(const H7Params p) {
+__global__ __launch_bounds__(S7_THREADS) void head_wgrad_kernel(const H7Params p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int NT = (CIN + 31) / 32, UNITS = 2 * NT, KSPLIT = 4 / UNITS, PS = CIN * 2 + 16, DS = H7_DS;
     static_assert(UNITS == 2 || UNITS == 4, "four waves share the 32 x 32 blocks");
@@ -128,7 +114,7 @@ __global__ __launch_bounds__(H7_THREADS) void head_wgrad_kernel(const H7Params p
     const int Wp = p.W + 2, halo = Wp + 1, xrows = H7_CHUNK + 2 * halo;
     unsigned char* xl = h7_lds;
     unsigned char* dl = h7_lds + (size_t)xrows * PS;
-    h7_lds_byte* const ldsp = (h7_lds_byte*)h7_lds;
+    s7_lds_byte* const ldsp = (s7_lds_byte*)h7_lds;
 
     const int tid = threadIdx.x, lane = tid & 63, r31 = lane & 31, khalf = lane >> 5, i16 = lane & 15, g16 = (lane >> 4) & 1;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(H7_THREADS) void head_wgrad_kernel(const H7Params p
     int end = chunk + p.chunks_per_split;
     end = end > p.chunks ? p.chunks : end;
 
-    // the lane's row inside a step and its 8 bytes of the 32-channel block (h7_fragment)
+    // the lane's row inside a step and its 8 bytes of the 32-channel block (ssd7_fragment)
     const u32 lrow = (u32)(khalf * 4 + (i16 >> 2)), lcol = (u32)(g16 * 32 + (i16 & 3) * 8);
     const u32 a_lane = (u32)(xrows * PS) + lrow * DS + (u32)(mt * 64) + lcol;
     const u32 b_lane = lrow * PS + (u32)(nt * 64) + lcol;
@@ -164,11 +150,11 @@ __global__ __launch_bounds__(H7_THREADS) void head_wgrad_kernel(const H7Params p
         __syncthreads();                                 // this chunk's rows are in LDS
 #pragma unroll 2
         for (int s = ks; s < H7_CHUNK / 16; s += KSPLIT) {
-            const bf16x8 a = __builtin_bit_cast(bf16x8, h7_fragment(ldsp, a_lane + (u32)(s * 16 * DS), 8 * DS));
+            const bf16x8 a = __builtin_bit_cast(bf16x8, ssd7_fragment(ldsp, a_lane + (u32)(s * 16 * DS), 8 * DS));
             const u32 b0 = b_lane + (u32)(s * 16 * PS);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                const bf16x8 b = __builtin_bit_cast(bf16x8, h7_fragment(ldsp, b0 + toff[j], 8 * PS));
+                const bf16x8 b = __builtin_bit_cast(bf16x8, ssd7_fragment(ldsp, b0 + toff[j], 8 * PS));
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
             }
             if (sums) accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, accb, 0, 0, 0);
@@ -176,7 +162,7 @@ __global__ __launch_bounds__(H7_THREADS) void head_wgrad_kernel(const H7Params p
         __syncthreads();                                 // every wave is done with the chunk before the next one overwrites it
     }
 
-    // partial tile: the lane's column is input channel nt 32 + r31, register v output channel mt 32 + 8 (v / 4) + 4 khalf + v % 4
+    // partial tile of this (split, step parity): the lane's column is input channel nt 32 + r31, register v output channel ssd7_acc_row
     float* out = p.part + (size_t)(split * KSPLIT + ks) * (H7_CP * 9 * CIN + H7_CP);
     const int ci = nt * 32 + r31;
     if (ci < CIN) {
@@ -184,60 +170,24 @@ __global__ __launch_bounds__(H7_THREADS) void head_wgrad_kernel(const H7Params p
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int co = mt * 32 + 8 * (v >> 2) + 4 * khalf + (v & 3);
+                const int co = ssd7_acc_row(mt, v, khalf);
                 if (co < H7_CP) out[((size_t)co * 9 + 3 * kh + j) * CIN + ci] = acc[j][v];
             }
     }
     if (sums && r31 == 0) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int co = mt * 32 + 8 * (v >> 2) + 4 * khalf + (v & 3);
+            const int co = ssd7_acc_row(mt, v, khalf);
             if (co < H7_CP) out[H7_CP * 9 * CIN + co] = accb[v];
         }
     }
 #endif
 }
 
-// The partial tiles added in index order in float32; packed row co < n_conf is row co of the conf head, the next n_loc rows are the loc
-// head's, the rest is padding and goes nowhere.  Written once: float32, or rounded once to bf16, dw through the parameter's element
-// strides (Cout, Cin, kh, kw).
-struct H7Reduce {
-    const float* part;
-    void* dw[2];
-    void* db[2];
-    long long s[2][4];
-    int slots, cin, n_conf, n_loc, out_bf16;
-};
-
-__global__ __launch_bounds__(256) void head_wgrad_reduce_kernel(const H7Reduce q) {
-    const int kkc = 9 * q.cin, nw = H7_CP * kkc, n = nw + H7_CP;
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= n) return;
-    int co = i < nw ? i / kkc : i - nw;
-    if (co >= q.n_conf + q.n_loc) return;
-    float sum = q.part[i];
-    for (int s = 1; s < q.slots; ++s) sum += q.part[(size_t)s * n + i];
-    const int head = co >= q.n_conf;
-    if (head) co -= q.n_conf;
-    if (i < nw) {
-        const int r = i % kkc, t = r / q.cin, ci = r - t * q.cin, kh = t / 3, kw = t - kh * 3;
-        const long long at = co * q.s[head][0] + ci * q.s[head][1] + kh * q.s[head][2] + kw * q.s[head][3];
-        if (q.out_bf16) static_cast<bf16_t*>(q.dw[head])[at] = bf16_bits<bf16_t>(sum);
-        else static_cast<float*>(q.dw[head])[at] = sum;
-    } else {
-        if (q.out_bf16) static_cast<bf16_t*>(q.db[head])[co] = bf16_bits<bf16_t>(sum);
-        else static_cast<float*>(q.db[head])[co] = sum;
-    }
-}
-
+// the kernel of a Cin, its dynamic LDS allowed up to what the widest map needs
 template <int CIN>
 int h7_launch(const H7Params& p, const H7Plan& pl, size_t lds, hipStream_t stream) {
-    auto fn = head_wgrad_kernel<CIN>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)h7_lds_bytes(H7_MAX_W, CIN));
-    if (attr != hipSuccess) return SSDHIP_E_LAUNCH;
-    hipLaunchKernelGGL(fn, dim3(pl.splits, 3), dim3(H7_THREADS), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    return ssd7_launch<head_wgrad_kernel<CIN>>(dim3(pl.splits, 3), (int)h7_lds_bytes(H7_MAX_W, CIN), lds, stream, p);
 }
 
 // ---- the packed images and bias of the heads, refreshed on the device --------------------------------------------------------------
@@ -262,7 +212,7 @@ __device__ __forceinline__ bf16_t h7_packed_filter(const H7PackMap& M, int r, in
     return M.w[head][r * M.s[head][0] + c * M.s[head][1] + kh * M.s[head][2] + kw * M.s[head][3]];
 }
 
-__global__ __launch_bounds__(256) void head_pack_kernel(const H7PackTable t) {
+__global__ __launch_bounds__(S7_THREADS) void head_pack_kernel(const H7PackTable t) {
     const H7PackMap& M = t.map[blockIdx.y / 3];
     const int what = (int)(blockIdx.y % 3);
     const int step = (int)(gridDim.x * blockDim.x), first = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -271,15 +221,10 @@ __global__ __launch_bounds__(256) void head_pack_kernel(const H7PackTable t) {
             M.bias[i] = i < M.n[0] ? M.b[0][i] : (i < M.n[0] + M.n[1] ? M.b[1][i - M.n[0]] : (bf16_t)0);
         return;
     }
-    const bool flip = what == 1;
-    bf16_t* out = flip ? M.flip : M.fwd;
-    const int rows = flip ? M.cin : H7_CP, cols = flip ? H7_CP : M.cin, rp = (rows + 31) / 32 * 32, cp = cols + 8;
-    for (int i = first; i < 9 * rp * cp; i += step) {
-        const int c = i % cp, q = i / cp, r = q % rp, tap = q / rp, kh = tap / 3, kw = tap - 3 * kh;
-        bf16_t v = 0;
-        if (r < rows && c < cols) v = flip ? h7_packed_filter(M, c, r, 2 - kh, 2 - kw) : h7_packed_filter(M, r, c, kh, kw);
-        out[i] = v;
-    }
+    const bool flip = what == 1;                         // forward: (48, Cin); flipped: (Cin, 48), rows / columns swapped and taps flipped
+    ssd7_write_image3(flip ? M.flip : M.fwd, flip ? M.cin : H7_CP, flip ? H7_CP : M.cin, first, step, [&](int r, int c, int kh, int kw) {
+        return flip ? h7_packed_filter(M, c, r, 2 - kh, 2 - kw) : h7_packed_filter(M, r, c, kh, kw);
+    });
 }
 
 }  // namespace
@@ -301,26 +246,15 @@ extern "C" int ssdhip_ssd7_pack_heads(int n_maps, const void* const* conf_w, con
         if (((uintptr_t)conf_w[i] | (uintptr_t)loc_w[i] | (uintptr_t)conf_b[i] | (uintptr_t)loc_b[i] | (uintptr_t)fwd[i] |
              (uintptr_t)flipped[i] | (uintptr_t)bias[i]) & 1)
             return SSDHIP_E_BADARG;
-        for (int h = 0; h < 2; ++h) {
-            long long reach = 0;                          // the farthest element the strides address: a sanity bound
-            const int dims[4] = {h ? n_loc[i] : n_conf[i], Cin[i], 3, 3};
-            for (int d = 0; d < 4; ++d) {
-                const long long s = strides[8 * i + 4 * h + d];
-                if (s < 0) return SSDHIP_E_BADARG;
-                reach += s * (dims[d] - 1);
-                M.s[h][d] = s;
-            }
-            if (reach > 0x3fffffffLL) return SSDHIP_E_BADARG;
-        }
+        for (int h = 0; h < 2; ++h)
+            if (!ssd7_strides(strides + 8 * i + 4 * h, h ? n_loc[i] : n_conf[i], Cin[i], 3, M.s[h])) return SSDHIP_E_BADARG;
         M.w[0] = static_cast<const bf16_t*>(conf_w[i]); M.w[1] = static_cast<const bf16_t*>(loc_w[i]);
         M.b[0] = static_cast<const bf16_t*>(conf_b[i]); M.b[1] = static_cast<const bf16_t*>(loc_b[i]);
         M.fwd = static_cast<bf16_t*>(fwd[i]); M.flip = static_cast<bf16_t*>(flipped[i]); M.bias = static_cast<bf16_t*>(bias[i]);
         M.cin = Cin[i]; M.n[0] = n_conf[i]; M.n[1] = n_loc[i];
     }
-    const int most = 9 * 64 * (64 + 8);                   // the largest image
-    const int bx = (most + 256 * 4 - 1) / (256 * 4);      // about four elements a thread
-    hipLaunchKernelGGL(head_pack_kernel, dim3(bx, 3 * n_maps), dim3(256), 0, static_cast<hipStream_t>(stream_), t);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    const int bx = (ssd7_image3_elems(64, 64) + S7_THREADS * 4 - 1) / (S7_THREADS * 4);      // about four elements a thread in the largest image
+    return ssd7_launch<head_pack_kernel>(dim3(bx, 3 * n_maps), 0, 0, static_cast<hipStream_t>(stream_), t);
 }
 
 extern "C" int ssdhip_ssd7_head_wgrad_plan(int B, int H, int W, int Cin, int Cp, int* plan) {
@@ -350,20 +284,8 @@ extern "C" int ssdhip_ssd7_head_wgrad_nhwc_bf16(const void* x, const void* dy, v
     if ((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)workspace) & 15) ||
         (((uintptr_t)dw_conf | (uintptr_t)db_conf | (uintptr_t)dw_loc | (uintptr_t)db_loc) & omask))
         return SSDHIP_E_BADARG;
-    H7Reduce q;
-    const long long* given[2] = {dw_conf_strides, dw_loc_strides};
-    for (int h = 0; h < 2; ++h) {
-        q.s[h][0] = 9LL * Cin; q.s[h][1] = 1; q.s[h][2] = 3LL * Cin; q.s[h][3] = Cin;                   // dense [n][3][3][Cin]
-        if (!given[h]) continue;
-        long long reach = 0;
-        const int dims[4] = {h ? n_loc : n_conf, Cin, 3, 3};
-        for (int d = 0; d < 4; ++d) {
-            if (given[h][d] < 0) return SSDHIP_E_BADARG;
-            q.s[h][d] = given[h][d];
-            reach += given[h][d] * (dims[d] - 1);
-        }
-        if (reach > 0x3fffffffLL) return SSDHIP_E_BADARG;
-    }
+    S7Reduce q;                                          // two destinations: the conf head's rows, then the loc head's
+    if (!ssd7_strides(dw_conf_strides, n_conf, Cin, 3, q.s[0]) || !ssd7_strides(dw_loc_strides, n_loc, Cin, 3, q.s[1])) return SSDHIP_E_BADARG;
     H7Params p;
     p.x = static_cast<const unsigned char*>(x); p.dy = static_cast<const unsigned char*>(dy); p.part = static_cast<float*>(workspace);
     p.H = H; p.W = W; p.positions = pl.positions; p.chunks = pl.chunks; p.chunks_per_split = pl.chunks_per_split;
@@ -371,8 +293,6 @@ extern "C" int ssdhip_ssd7_head_wgrad_nhwc_bf16(const void* x, const void* dy, v
     const int rc = Cin == 64 ? h7_launch<64>(p, pl, lds, stream) : Cin == 48 ? h7_launch<48>(p, pl, lds, stream) : h7_launch<32>(p, pl, lds, stream);
     if (rc != SSDHIP_OK) return rc;
     q.part = p.part; q.dw[0] = dw_conf; q.dw[1] = dw_loc; q.db[0] = db_conf; q.db[1] = db_loc;
-    q.slots = pl.splits * pl.ksplit; q.cin = Cin; q.n_conf = n_conf; q.n_loc = n_loc; q.out_bf16 = out_bf16 ? 1 : 0;
-    const int n = (int)h7_slot_floats(Cin);
-    hipLaunchKernelGGL(head_wgrad_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, q);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    q.slots = pl.splits * pl.ksplit; q.cin = Cin; q.kernel = 3; q.rows = H7_CP; q.n[0] = n_conf; q.n[1] = n_loc; q.out_bf16 = out_bf16 ? 1 : 0;
+    return ssd7_reduce(q, stream);
 }

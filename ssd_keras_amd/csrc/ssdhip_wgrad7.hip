@@ -10,7 +10,7 @@
 //   * Cout <= 64 and k k Cin <= 576, so ONE workgroup holds a layer's whole [Cout][k k Cin] float32 tile in accumulators: four waves,
 //     each a 32 x 32 (output channels x input channels) block for all nine taps -- or, where the layer has only two such blocks, for
 //     five / four of the taps.  A persistent workgroup walks its share of the 8 x 32 position tiles of the forward kernel
-//     (ssdhip_convbn.hip) with that kernel's halo loader: the NEXT tile's halo and dy tile are requested before the current tile's
+//     (ssdhip_convbn.hip) on that kernel's halo layout (ssdhip_ssd7.h): the NEXT tile's halo and dy tile are requested before the current tile's
 //     MFMAs and stored into LDS behind them.  Zero padding -- at the map border, between images and in the columns / rows of a partial
 //     tile -- is written by the loader (dy is zero outside its image, so the finite x values beside a partial tile add nothing); no memset.
 //   * both operands sit in LDS as [position][channels] images and are read with ds_read_b64_tr_b16: a lane gets four consecutive
@@ -23,7 +23,7 @@
 //     (the lanes' upper half reads one halo row further down), three blocks cover the five rows, the fourth wave adds the bias gradient.
 //   * the bias gradient is one more MFMA per K-step against a fragment of ones: the same float32 accumulation, no extra pass.
 //   * the sum is split over the tiles: split s owns tiles [s T, (s + 1) T) and writes one float32 partial [Cout][k][k][Cin] tile and one
-//     [Cout] row; a second launch adds the splits in index order in float32 (the rule of wgrad_reduce_kernel) and writes dw and db
+//     [Cout] row; a second launch (ssd7_reduce_kernel, ssdhip_ssd7.h) adds the splits in index order in float32 and writes dw and db
 //     once -- float32, or rounded once to bf16 -- through the parameter's element strides.  No atomics, no last-workgroup finish.
 //     The number of splits is host arithmetic (ssdhip_ssd7_conv_wgrad_plan): the partial tiles, written and read back, must not exceed
 //     the operand bytes the launch reads.
@@ -32,16 +32,13 @@
 
 #include "ssdhip.h"
 #include "ssdhip_bf16.h"
+#include "ssdhip_ssd7.h"
 
 namespace ssdhip {
 namespace {
 
-constexpr int W7_THREADS = 256;                          // four waves
-constexpr int W7_TH = 8, W7_TW = 32;                     // position tile (the forward kernel's)
 constexpr int W7_MAX_SPLITS = 256;                       // the part's CU count: a constant, so that the plan is host arithmetic
 constexpr int W7_TAIL = 64;                              // LDS behind the last image: what the padded lanes of its last position reach
-
-typedef short w7_s16x4 __attribute__((ext_vector_type(4)));
 
 struct W7Params {
     const unsigned char* x;      // [B, H, W, Cin] bf16
@@ -55,62 +52,35 @@ struct W7Plan {
     int splits, tiles_per_split, tiles, last_tiles;
 };
 
-bool w7_geometry(int Cin, int Cout, int kernel) {
-    if (kernel == 5) return Cin == 3 && Cout == 32;
-    if (kernel != 3) return false;
-    return (Cin == 32 && Cout == 48) || (Cin == 48 && (Cout == 64 || Cout == 48 || Cout == 32)) || (Cin == 64 && (Cout == 64 || Cout == 48));
-}
-
 long long w7_slot_floats(int Cin, int Cout, int kernel) { return (long long)Cout * kernel * kernel * Cin + Cout; }
 
-bool w7_plan(int B, int H, int W, int Cin, int Cout, int kernel, W7Plan& pl) {
-    if (B <= 0 || H <= 0 || W <= 0 || !w7_geometry(Cin, Cout, kernel)) return false;
-    const long long tiles = (long long)B * ((H + W7_TH - 1) / W7_TH) * ((W + W7_TW - 1) / W7_TW);
-    if (tiles > 0x3fffffffLL || (long long)B * H * W > 0x3fffffffLL) return false;
-    const long long operand = (long long)B * H * W * (Cin + Cout) * 2, slot = w7_slot_floats(Cin, Cout, kernel) * 4;
+// The plan, and with it the tile fields of the kernel's arguments (p.B .. p.tiles, p.tiles_per_split).
+bool w7_plan(int B, int H, int W, int Cin, int Cout, int kernel, W7Plan& pl, W7Params& p) {
+    if (!ssd7_geometry(Cin, Cout, kernel) || !ssd7_tile_grid(B, H, W, p)) return false;
+    const long long tiles = p.tiles, operand = (long long)B * H * W * (Cin + Cout) * 2, slot = w7_slot_floats(Cin, Cout, kernel) * 4;
     long long most = operand / (2 * slot);               // a partial tile is written once and read once
     most = most > W7_MAX_SPLITS ? W7_MAX_SPLITS : most;
     most = most > tiles ? tiles : most;
     most = most < 1 ? 1 : most;
-    pl.tiles = (int)tiles;
-    pl.tiles_per_split = (int)((tiles + most - 1) / most);
+    pl.tiles = p.tiles;
+    pl.tiles_per_split = p.tiles_per_split = (int)((tiles + most - 1) / most);
     pl.splits = (pl.tiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
     pl.last_tiles = pl.tiles - (pl.splits - 1) * pl.tiles_per_split;
     return true;
 }
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __attribute__((address_space(3))) unsigned char w7_lds_byte;
-// ds_read_b64_tr_b16: per 16 lanes a 4-row x 16-column block of 16-bit values; lane 4 q + p gives the address of row q, columns 4 p ..
-// 4 p + 3, lane i receives column i of the four rows.  Two reads (rows + 0, + 8) make the fragment of a 16-position K-step: element j of
-// lane half h is position 8 (j >> 2) + 4 h + (j & 3) -- in BOTH operands, which is all the MFMA asks of the K order.
-__device__ __forceinline__ u32x4 w7_fragment(w7_lds_byte* lds, u32 off, u32 rows8) {
-    const w7_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) w7_s16x4*)(lds + off));
-    const w7_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) w7_s16x4*)(lds + off + rows8));
-    const u32x2 l = __builtin_bit_cast(u32x2, lo), h = __builtin_bit_cast(u32x2, hi);
-    return u32x4{l.x, l.y, h.x, h.y};
-}
-#endif
-
-__device__ __forceinline__ void w7_tile_origin(const W7Params& p, int tile, int& b, int& h0, int& w0) {
-    const int wt = tile % p.WT, q = tile / p.WT;
-    b = q / p.HT;
-    h0 = (q - b * p.HT) * W7_TH;
-    w0 = wt * W7_TW;
-}
-
 // the dy tile, [8 x 32 positions][COUT + 8] in LDS: 16-byte chunks dealt to the threads, zeros outside the image
 template <int COUT>
 struct W7Dy {
-    static constexpr int DS = COUT * 2 + 16, CH = COUT / 8, NLD = W7_TH * W7_TW * CH / W7_THREADS, BYTES = W7_TH * W7_TW * DS;
-    static_assert(W7_TH * W7_TW * CH % W7_THREADS == 0, "whole chunks per thread");
+    static constexpr int DS = COUT * 2 + 16, CH = COUT / 8, NLD = S7_TH * S7_TW * CH / S7_THREADS, BYTES = S7_TH * S7_TW * DS;
+    static_assert(S7_TH * S7_TW * CH % S7_THREADS == 0, "whole chunks per thread");
 
     static __device__ __forceinline__ void fetch(const W7Params& p, int tile, int tid, u32x4 (&r)[NLD]) {
         int b, h0, w0;
-        w7_tile_origin(p, tile, b, h0, w0);
+        ssd7_tile_origin(p, tile, b, h0, w0);
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            const int n = tid + W7_THREADS * i, px = n / CH, c = n - px * CH, h = h0 + (px >> 5), w = w0 + (px & 31);
+            const int n = tid + S7_THREADS * i, px = n / CH, c = n - px * CH, h = h0 + (px >> 5), w = w0 + (px & 31);
             r[i] = u32x4{0u, 0u, 0u, 0u};
             if (h < p.H && w < p.W) r[i] = *reinterpret_cast<const u32x4*>(p.dy + (((size_t)b * p.H + h) * p.W + w) * (COUT * 2) + c * 16);
         }
@@ -118,35 +88,36 @@ struct W7Dy {
     static __device__ __forceinline__ void stash(unsigned char* dl, int tid, const u32x4 (&r)[NLD]) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            const int n = tid + W7_THREADS * i, px = n / CH, c = n - px * CH;
+            const int n = tid + S7_THREADS * i, px = n / CH, c = n - px * CH;
             *reinterpret_cast<u32x4*>(dl + px * DS + c * 16) = r[i];
         }
     }
 };
 
 // ---- 3 x 3 ------------------------------------------------------------------------------------------------------------------------
-// LDS: halo [10 x 34 positions][Cin + 8] | dy tile [8 x 32][Cout + 8] | tail.
+// LDS: halo [10 x 34 positions][Cin + 8] (S7Halo3) | dy tile [8 x 32][Cout + 8] | tail.
 template <int CIN, int COUT>
 struct W73 {
     using Dy = W7Dy<COUT>;
+    using Halo = S7Halo3<CIN>;
     static constexpr int MT = (COUT + 31) / 32, NT = (CIN + 31) / 32, UNITS = MT * NT, TG = 4 / UNITS, NTAP = TG == 1 ? 9 : 5;
-    static constexpr int PS = CIN * 2 + 16, CH = CIN / 8, HR = W7_TH + 2, HC = W7_TW + 2, HPX = HR * HC, NCHUNK = HPX * CH;
-    static constexpr int NLD = (NCHUNK + W7_THREADS - 1) / W7_THREADS;
-    static constexpr int HBYTES = HPX * PS, LDS = HBYTES + Dy::BYTES + W7_TAIL;
+    static constexpr int HBYTES = Halo::BYTES, LDS = HBYTES + Dy::BYTES + W7_TAIL;
     static_assert(UNITS == 2 || UNITS == 4, "four waves share the 32 x 32 blocks");
     static_assert(LDS <= 160 * 1024 && HBYTES % 16 == 0, "LDS budget and alignment");
 };
 
 template <int CIN, int COUT>
-__global__ __launch_bounds__(W7_THREADS) void wgrad7_k3_kernel(const W7Params p) {
+__global__ __launch_bounds__(S7_THREADS) void wgrad7_k3_kernel(const W7Params p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using G = W73<CIN, COUT>;
     using Dy = typename G::Dy;
-    constexpr int NT = G::NT, UNITS = G::UNITS, NTAP = G::NTAP, PS = G::PS, CH = G::CH, HC = G::HC, NCHUNK = G::NCHUNK, NLD = G::NLD, DS = Dy::DS;
+    using Halo = typename G::Halo;
+    constexpr int NT = G::NT, UNITS = G::UNITS, NTAP = G::NTAP, DS = Dy::DS;
+    constexpr int PS = Halo::PS, CH = Halo::CH, HC = Halo::HC, NCHUNK = Halo::NCHUNK, NLD = Halo::NLD;
     extern __shared__ __attribute__((aligned(16))) unsigned char w7_lds[];
     unsigned char* hl = w7_lds;
     unsigned char* dl = w7_lds + G::HBYTES;
-    w7_lds_byte* const ldsp = (w7_lds_byte*)w7_lds;
+    s7_lds_byte* const ldsp = (s7_lds_byte*)w7_lds;
 
     const int tid = threadIdx.x, lane = tid & 63, r31 = lane & 31, khalf = lane >> 5, i16 = lane & 15, g16 = (lane >> 4) & 1;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -157,12 +128,13 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k3_kernel(const W7Params p)
     int end = tile + p.tiles_per_split;
     end = end > p.tiles ? p.tiles : end;
 
+    // the halo's chunks (S7Halo3), as in convbn3_kernel
     auto fetch = [&](int t, u32x4 (&r)[NLD]) {
         int b, h0, w0;
-        w7_tile_origin(p, t, b, h0, w0);
+        ssd7_tile_origin(p, t, b, h0, w0);
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            const int n = tid + W7_THREADS * i, px = n / CH, c = n - px * CH, hr = px / HC, hc = px - hr * HC;
+            const int n = tid + S7_THREADS * i, px = n / CH, c = n - px * CH, hr = px / HC, hc = px - hr * HC;
             const int h = h0 - 1 + hr, w = w0 - 1 + hc;
             r[i] = u32x4{0u, 0u, 0u, 0u};            // outside the image: the layer's zero padding
             if (n < NCHUNK && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W)
@@ -172,12 +144,12 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k3_kernel(const W7Params p)
     auto stash = [&](const u32x4 (&r)[NLD]) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            const int n = tid + W7_THREADS * i, px = n / CH, c = n - px * CH;
+            const int n = tid + S7_THREADS * i, px = n / CH, c = n - px * CH;
             if (n < NCHUNK) *reinterpret_cast<u32x4*>(hl + px * PS + c * 16) = r[i];
         }
     };
 
-    // the lane's row inside a K-step and its 8 bytes of the 32-channel block (w7_fragment)
+    // the lane's row inside a K-step and its 8 bytes of the 32-channel block (ssd7_fragment)
     const u32 lrow = (u32)(khalf * 4 + (i16 >> 2)), lcol = (u32)(g16 * 32 + (i16 & 3) * 8);
     const u32 a_lane = (u32)G::HBYTES + lrow * DS + (u32)(mt * 64) + lcol;
     const u32 b_lane = lrow * PS + (u32)(nt * 64) + lcol;
@@ -211,14 +183,14 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k3_kernel(const W7Params p)
             Dy::fetch(p, tile + 1, tid, rd);
         }
 #pragma unroll 1
-        for (int r = 0; r < W7_TH; ++r)
+        for (int r = 0; r < S7_TH; ++r)
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-                const bf16x8 a = __builtin_bit_cast(bf16x8, w7_fragment(ldsp, a_lane + (u32)((r * W7_TW + hf * 16) * DS), 8 * DS));
+                const bf16x8 a = __builtin_bit_cast(bf16x8, ssd7_fragment(ldsp, a_lane + (u32)((r * S7_TW + hf * 16) * DS), 8 * DS));
                 const u32 b0 = b_lane + (u32)((r * HC + hf * 16) * PS);
 #pragma unroll
                 for (int j = 0; j < NTAP; ++j) {
-                    const bf16x8 b = __builtin_bit_cast(bf16x8, w7_fragment(ldsp, b0 + toff[j], 8 * PS));
+                    const bf16x8 b = __builtin_bit_cast(bf16x8, ssd7_fragment(ldsp, b0 + toff[j], 8 * PS));
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
                 }
                 if (sums) accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, accb, 0, 0, 0);
@@ -226,7 +198,7 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k3_kernel(const W7Params p)
         __syncthreads();                                 // every wave is done with the tile before the next one overwrites it
     }
 
-    // partial tile: the lane's column is input channel nt 32 + r31, register v output channel mt 32 + 8 (v / 4) + 4 khalf + v % 4
+    // partial tile: the lane's column is input channel nt 32 + r31, register v output channel ssd7_acc_row
     float* out = p.part + (size_t)split * (COUT * 9 * CIN + COUT);
     const int ci = nt * 32 + r31;
 #pragma unroll
@@ -234,14 +206,14 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k3_kernel(const W7Params p)
         if (j < ntaps && ci < CIN) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int co = mt * 32 + 8 * (v >> 2) + 4 * khalf + (v & 3);
+                const int co = ssd7_acc_row(mt, v, khalf);
                 if (co < COUT) out[((size_t)co * 9 + t0 + j) * CIN + ci] = acc[j][v];
             }
         }
     if (sums && r31 == 0) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int co = mt * 32 + 8 * (v >> 2) + 4 * khalf + (v & 3);
+            const int co = ssd7_acc_row(mt, v, khalf);
             if (co < COUT) out[COUT * 9 * CIN + co] = accb[v];
         }
     }
@@ -249,22 +221,21 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k3_kernel(const W7Params p)
 }
 
 // ---- 5 x 5, Cin = 3, Cout = 32 ------------------------------------------------------------------------------------------------
-// LDS: halo [12 rows][224 bytes] (108 bf16 of 36 pixels) | expanded [12 rows][32 columns][16 bf16]
+// LDS: halo [12 rows][224 bytes] (108 bf16 of 36 pixels: S7Halo5) | expanded [12 rows][32 columns][16 bf16]
 // (element j = 3 kw + ci of column c is halo element 3 c + j; j = 15 zero) | dy tile [8 x 32][32 + 8] | tail.
-constexpr int W75_HR = W7_TH + 4, W75_ROW = (W7_TW + 4) * 3, W75_RS = 224, W75_NEL = W75_HR * W75_ROW;
-[[maybe_unused]] constexpr int W75_NLD = (W75_NEL + W7_THREADS - 1) / W7_THREADS;
-constexpr int W75_HBYTES = W75_HR * W75_RS, W75_EBYTES = W75_HR * W7_TW * 32;
+constexpr int W75_HR = S7Halo5::HR, W75_HBYTES = S7Halo5::BYTES, W75_EBYTES = W75_HR * S7_TW * 32;
 [[maybe_unused]] constexpr int W75_LDS = W75_HBYTES + W75_EBYTES + W7Dy<32>::BYTES + W7_TAIL;
 
-__global__ __launch_bounds__(W7_THREADS) void wgrad7_k5_kernel(const W7Params p) {
+__global__ __launch_bounds__(S7_THREADS) void wgrad7_k5_kernel(const W7Params p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     using Dy = W7Dy<32>;
+    using Halo = S7Halo5;
     constexpr int DS = Dy::DS;
     __shared__ __attribute__((aligned(16))) unsigned char w7_lds[W75_LDS];
     unsigned char* hl = w7_lds;
     unsigned char* el = w7_lds + W75_HBYTES;
     unsigned char* dl = el + W75_EBYTES;
-    w7_lds_byte* const ldsp = (w7_lds_byte*)w7_lds;
+    s7_lds_byte* const ldsp = (s7_lds_byte*)w7_lds;
 
     const int tid = threadIdx.x, lane = tid & 63, r31 = lane & 31, khalf = lane >> 5, i16 = lane & 15, g16 = (lane >> 4) & 1;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -274,30 +245,30 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k5_kernel(const W7Params p)
     end = end > p.tiles ? p.tiles : end;
     const unsigned short* x = reinterpret_cast<const unsigned short*>(p.x);
 
-    auto fetch = [&](int t, unsigned short (&r)[W75_NLD]) {
+    auto fetch = [&](int t, unsigned short (&r)[Halo::NLD]) {
         int b, h0, w0;
-        w7_tile_origin(p, t, b, h0, w0);
+        ssd7_tile_origin(p, t, b, h0, w0);
 #pragma unroll
-        for (int i = 0; i < W75_NLD; ++i) {
-            const int n = tid + W7_THREADS * i, hr = n / W75_ROW, e = n - hr * W75_ROW, hc = e / 3;
+        for (int i = 0; i < Halo::NLD; ++i) {
+            const int n = tid + S7_THREADS * i, hr = n / Halo::ROW, e = n - hr * Halo::ROW, hc = e / 3;
             const int h = h0 - 2 + hr, w = w0 - 2 + hc;
             r[i] = 0;
-            if (n < W75_NEL && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W)
+            if (n < Halo::NEL && (unsigned)h < (unsigned)p.H && (unsigned)w < (unsigned)p.W)
                 r[i] = x[(((size_t)b * p.H + h) * p.W + w) * 3 + (e - hc * 3)];
         }
     };
-    auto stash = [&](const unsigned short (&r)[W75_NLD]) {
+    auto stash = [&](const unsigned short (&r)[Halo::NLD]) {
 #pragma unroll
-        for (int i = 0; i < W75_NLD; ++i) {
-            const int n = tid + W7_THREADS * i, hr = n / W75_ROW, e = n - hr * W75_ROW;
-            if (n < W75_NEL) *reinterpret_cast<unsigned short*>(hl + hr * W75_RS + e * 2) = r[i];
+        for (int i = 0; i < Halo::NLD; ++i) {
+            const int n = tid + S7_THREADS * i, hr = n / Halo::ROW, e = n - hr * Halo::ROW;
+            if (n < Halo::NEL) *reinterpret_cast<unsigned short*>(hl + hr * Halo::RS + e * 2) = r[i];
         }
     };
     // halo -> expanded image: position (hr, c) takes the 15 halo elements from 3 c on and a zero
     auto expand = [&]() {
-        for (int n = tid; n < W75_HR * W7_TW; n += W7_THREADS) {
+        for (int n = tid; n < W75_HR * S7_TW; n += S7_THREADS) {
             const int hr = n >> 5, c = n & 31;
-            const unsigned short* src = reinterpret_cast<const unsigned short*>(hl + hr * W75_RS) + 3 * c;
+            const unsigned short* src = reinterpret_cast<const unsigned short*>(hl + hr * Halo::RS) + 3 * c;
             u32 d[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) d[j] = (u32)src[2 * j] | (j < 7 ? (u32)src[2 * j + 1] << 16 : 0u);
@@ -311,7 +282,7 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k5_kernel(const W7Params p)
     const int kh = 2 * wave + g16 < 4 ? 2 * wave + g16 : 4;
     const u32 lrow = (u32)(khalf * 4 + (i16 >> 2));
     const u32 a_lane = (u32)(W75_HBYTES + W75_EBYTES) + lrow * DS + (u32)(g16 * 32 + (i16 & 3) * 8);
-    const u32 b_lane = (u32)W75_HBYTES + (u32)((kh * W7_TW + lrow) * 32 + (i16 & 3) * 8);
+    const u32 b_lane = (u32)W75_HBYTES + (u32)((kh * S7_TW + lrow) * 32 + (i16 & 3) * 8);
     const u32 one2 = 0x3f803f80u;
     const bf16x8 ones = __builtin_bit_cast(bf16x8, (u32x4{one2, one2, one2, one2}));
 
@@ -319,7 +290,7 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k5_kernel(const W7Params p)
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = 0.f;
 
-    unsigned short rx[W75_NLD];
+    unsigned short rx[Halo::NLD];
     u32x4 rd[Dy::NLD];
     fetch(tile, rx);
     Dy::fetch(p, tile, tid, rd);
@@ -334,12 +305,12 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k5_kernel(const W7Params p)
         expand();
         __syncthreads();
 #pragma unroll 1
-        for (int r = 0; r < W7_TH; ++r)
+        for (int r = 0; r < S7_TH; ++r)
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-                const bf16x8 a = __builtin_bit_cast(bf16x8, w7_fragment(ldsp, a_lane + (u32)((r * W7_TW + hf * 16) * DS), 8 * DS));
+                const bf16x8 a = __builtin_bit_cast(bf16x8, ssd7_fragment(ldsp, a_lane + (u32)((r * S7_TW + hf * 16) * DS), 8 * DS));
                 bf16x8 b = ones;
-                if (wave < 3) b = __builtin_bit_cast(bf16x8, w7_fragment(ldsp, b_lane + (u32)((r * W7_TW + hf * 16) * 32), 8 * 32));
+                if (wave < 3) b = __builtin_bit_cast(bf16x8, ssd7_fragment(ldsp, b_lane + (u32)((r * S7_TW + hf * 16) * 32), 8 * 32));
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
             }
         __syncthreads();
@@ -349,53 +320,13 @@ __global__ __launch_bounds__(W7_THREADS) void wgrad7_k5_kernel(const W7Params p)
     if (wave < 3) {
         if (2 * wave + g16 < 5 && i16 < 15) {
 #pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int co = 8 * (v >> 2) + 4 * khalf + (v & 3);
-                out[co * 75 + kh * 15 + i16] = acc[v];
-            }
+            for (int v = 0; v < 16; ++v) out[ssd7_acc_row(0, v, khalf) * 75 + kh * 15 + i16] = acc[v];
         }
     } else if (r31 == 0) {
 #pragma unroll
-        for (int v = 0; v < 16; ++v) out[32 * 75 + 8 * (v >> 2) + 4 * khalf + (v & 3)] = acc[v];
+        for (int v = 0; v < 16; ++v) out[32 * 75 + ssd7_acc_row(0, v, khalf)] = acc[v];
     }
 #endif
-}
-
-// dw / db = the splits' partials added in index order in float32, written once: float32, or rounded once to bf16, dw through the
-// parameter's element strides (Cout, Cin, kh, kw).
-struct W7Reduce {
-    const float* part;
-    void* dw;
-    void* db;
-    long long s[4];
-    int splits, cin, cout, kernel, out_bf16;
-};
-
-__global__ __launch_bounds__(256) void wgrad7_reduce_kernel(const W7Reduce q) {
-    const int kkc = q.kernel * q.kernel * q.cin, nw = q.cout * kkc, n = nw + q.cout;
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= n) return;
-    float sum = q.part[i];
-    for (int s = 1; s < q.splits; ++s) sum += q.part[(size_t)s * n + i];
-    if (i < nw) {
-        const int co = i / kkc, r = i - co * kkc, t = r / q.cin, ci = r - t * q.cin, kh = t / q.kernel, kw = t - kh * q.kernel;
-        const long long at = co * q.s[0] + ci * q.s[1] + kh * q.s[2] + kw * q.s[3];
-        if (q.out_bf16) static_cast<bf16_t*>(q.dw)[at] = bf16_bits<bf16_t>(sum);
-        else static_cast<float*>(q.dw)[at] = sum;
-    } else if (q.db) {
-        if (q.out_bf16) static_cast<bf16_t*>(q.db)[i - nw] = bf16_bits<bf16_t>(sum);
-        else static_cast<float*>(q.db)[i - nw] = sum;
-    }
-}
-
-template <int CIN, int COUT>
-int w7_launch3(const W7Params& p, int splits, hipStream_t stream) {
-    using G = W73<CIN, COUT>;
-    auto fn = wgrad7_k3_kernel<CIN, COUT>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-    if (attr != hipSuccess) return SSDHIP_E_LAUNCH;
-    hipLaunchKernelGGL(fn, dim3(splits), dim3(W7_THREADS), G::LDS, stream, p);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 
 }  // namespace
@@ -405,14 +336,16 @@ using namespace ssdhip;
 
 extern "C" int ssdhip_ssd7_conv_wgrad_plan(int B, int H, int W, int Cin, int Cout, int kernel, int* plan) {
     W7Plan pl;
-    if (!plan || !w7_plan(B, H, W, Cin, Cout, kernel, pl)) return SSDHIP_E_BADARG;
+    W7Params p;
+    if (!plan || !w7_plan(B, H, W, Cin, Cout, kernel, pl, p)) return SSDHIP_E_BADARG;
     plan[0] = pl.splits; plan[1] = pl.tiles_per_split; plan[2] = pl.tiles; plan[3] = pl.last_tiles;
     return SSDHIP_OK;
 }
 
 extern "C" size_t ssdhip_ssd7_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kernel) {
     W7Plan pl;
-    if (!w7_plan(B, H, W, Cin, Cout, kernel, pl)) return 0;
+    W7Params p;
+    if (!w7_plan(B, H, W, Cin, Cout, kernel, pl, p)) return 0;
     return (size_t)pl.splits * (size_t)w7_slot_floats(Cin, Cout, kernel) * 4;
 }
 
@@ -421,42 +354,25 @@ extern "C" int ssdhip_ssd7_conv_wgrad_nhwc_bf16(const void* x, const void* dy, v
                                                 size_t workspace_bytes, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     W7Plan pl;
-    if (!x || !dy || !dw || !workspace || !w7_plan(B, H, W, Cin, Cout, kernel, pl)) return SSDHIP_E_BADARG;
+    W7Params p;
+    if (!x || !dy || !dw || !workspace || !w7_plan(B, H, W, Cin, Cout, kernel, pl, p)) return SSDHIP_E_BADARG;
     if (workspace_bytes < (size_t)pl.splits * (size_t)w7_slot_floats(Cin, Cout, kernel) * 4) return SSDHIP_E_BADARG;
     const uintptr_t omask = out_bf16 ? 1 : 3;
     if (((uintptr_t)x & (kernel == 3 ? 15 : 1)) || (((uintptr_t)dy | (uintptr_t)workspace) & 15) || (((uintptr_t)dw | (uintptr_t)db) & omask))
         return SSDHIP_E_BADARG;
-    W7Reduce q;
-    q.s[0] = (long long)kernel * kernel * Cin; q.s[1] = 1; q.s[2] = (long long)kernel * Cin; q.s[3] = Cin;      // [Cout][k][k][Cin]
-    if (dw_strides) {
-        long long reach = 0;
-        const int dims[4] = {Cout, Cin, kernel, kernel};
-        for (int d = 0; d < 4; ++d) {
-            if (dw_strides[d] < 0) return SSDHIP_E_BADARG;
-            q.s[d] = dw_strides[d];
-            reach += dw_strides[d] * (dims[d] - 1);
-        }
-        if (reach > 0x3fffffffLL) return SSDHIP_E_BADARG;
-    }
-    W7Params p;
+    S7Reduce q = {};                                     // one destination: every row of the tile is dw's, db may be NULL
+    if (!ssd7_strides(dw_strides, Cout, Cin, kernel, q.s[0])) return SSDHIP_E_BADARG;
     p.x = static_cast<const unsigned char*>(x); p.dy = static_cast<const unsigned char*>(dy); p.part = static_cast<float*>(workspace);
-    p.B = B; p.H = H; p.W = W;
-    p.HT = (H + W7_TH - 1) / W7_TH; p.WT = (W + W7_TW - 1) / W7_TW;
-    p.tiles = pl.tiles; p.tiles_per_split = pl.tiles_per_split;
-    int rc;
-    if (kernel == 5) {
-        hipLaunchKernelGGL(wgrad7_k5_kernel, dim3(pl.splits), dim3(W7_THREADS), 0, stream, p);
-        rc = hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
-    } else if (Cin == 32) {
-        rc = w7_launch3<32, 48>(p, pl.splits, stream);
-    } else if (Cin == 48) {
-        rc = Cout == 64 ? w7_launch3<48, 64>(p, pl.splits, stream) : Cout == 48 ? w7_launch3<48, 48>(p, pl.splits, stream) : w7_launch3<48, 32>(p, pl.splits, stream);
-    } else {
-        rc = Cout == 64 ? w7_launch3<64, 64>(p, pl.splits, stream) : w7_launch3<64, 48>(p, pl.splits, stream);
-    }
+    int rc = SSDHIP_E_BADARG;
+    if (kernel == 5)
+        rc = ssd7_launch<wgrad7_k5_kernel>(dim3(pl.splits), 0, 0, stream, p);
+    else
+        ssd7_for_pair3(Cin, Cout, [&](auto ci, auto co) {
+            constexpr int CIN = decltype(ci)::value, COUT = decltype(co)::value, LDS = W73<CIN, COUT>::LDS;
+            rc = ssd7_launch<wgrad7_k3_kernel<CIN, COUT>>(dim3(pl.splits), LDS, LDS, stream, p);
+        });
     if (rc != SSDHIP_OK) return rc;
-    q.part = p.part; q.dw = dw; q.db = db; q.splits = pl.splits; q.cin = Cin; q.cout = Cout; q.kernel = kernel; q.out_bf16 = out_bf16 ? 1 : 0;
-    const int n = (int)w7_slot_floats(Cin, Cout, kernel);
-    hipLaunchKernelGGL(wgrad7_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, q);
-    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+    q.part = p.part; q.dw[0] = dw; q.db[0] = db; q.n[0] = q.rows = Cout; q.slots = pl.splits; q.cin = Cin; q.kernel = kernel;
+    q.out_bf16 = out_bf16 ? 1 : 0;
+    return ssd7_reduce(q, stream);
 }

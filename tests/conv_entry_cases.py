@@ -25,7 +25,8 @@ LIM = 0x7ffff000                             # the 31-bit byte-offset limit of b
 _BASE, _STEP = 1 << 28, 1 << 24              # pointer argument number s of a call is the made-up address _BASE + s * _STEP
 
 # Argument kinds: "p" device pointer (value: byte offset from its made-up address, None = null), "i" int, "f" float, "z" size_t,
-# "P" HOST array of device pointers (list of offsets / None, or None for a null array), "I" HOST array of ints.
+# "P" HOST array of device pointers (list of offsets / None, or None for a null array), "I" HOST array of ints, "L" HOST array of
+# long long (element strides; None for a null array).
 _CONV = [("x", "p", 0), ("weight", "p", 0), ("bias", "p", 0), ("y", "p", 0), ("B", "i", 2), ("H", "i", 9), ("W", "i", 7)]
 _SAME = _CONV + [("Cin", "i", 64), ("Cout", "i", 64), ("kernel", "i", 3), ("dilation", "i", 1), ("relu", "i", 1)]
 _GENERAL = _CONV + [("Cin", "i", 64), ("Cout", "i", 64), ("kernel", "i", 3), ("stride", "i", 1), ("pad", "i", 1), ("dilation", "i", 1),
@@ -76,13 +77,46 @@ ENTRIES = {
                                      ("n_workgroups", "i", 0)],
 }
 
+
+def _dense(cout, cin, k):
+    """element strides (Cout, Cin, kh, kw) of a contiguous (Cout, Cin, k, k) parameter"""
+    return [cin * k * k, k * k, k, 1]
+
+
+# --- the SSD7 family (csrc/ssdhip_convbn.hip, ssdhip_wgrad7.hip, ssdhip_heads7.hip).  The weight gradients' base workspace is larger
+# than any perturbation of the base call needs; the exact sizes are cases of their own (_special)
+SSD7_GEOMETRIES = ((32, 48, 3), (48, 64, 3), (48, 48, 3), (48, 32, 3), (64, 64, 3), (64, 48, 3), (3, 32, 5))
+_MAP7 = [("B", "i", 2), ("H", "i", 9), ("W", "i", 7)]
+SSD7_ENTRIES = ("ssdhip_conv_bn_elu_nhwc_bf16", "ssdhip_conv_same_bias_nhwc_bf16", "ssdhip_ssd7_pack_filters", "ssdhip_ssd7_pack_heads",
+                "ssdhip_ssd7_conv_wgrad_nhwc_bf16", "ssdhip_ssd7_head_wgrad_nhwc_bf16")
+ENTRIES.update({
+    "ssdhip_conv_bn_elu_nhwc_bf16": [("x", "p", 0), ("w_packed", "p", 0), ("scale", "p", 0), ("shift", "p", 0), ("y", "p", 0)] + _MAP7 +
+                                    [("Cin", "i", 64), ("Cout", "i", 64), ("kernel", "i", 3), ("pool", "i", 0)],
+    "ssdhip_conv_same_bias_nhwc_bf16": [("x", "p", 0), ("w_packed", "p", 0), ("bias", "p", 0), ("y", "p", 0)] + _MAP7 +
+                                       [("Cin", "i", 64), ("Cout", "i", 64), ("kernel", "i", 3)],
+    "ssdhip_ssd7_pack_filters": [("n_layers", "i", 2), ("weights", "P", [0, 0]), ("fwd", "P", [0, 0]), ("flipped", "P", [0, 0]),
+                                 ("Cin", "I", [64, 48]), ("Cout", "I", [64, 32]), ("kernel", "I", [3, 3]),
+                                 ("strides", "L", _dense(64, 64, 3) + _dense(32, 48, 3))],
+    "ssdhip_ssd7_pack_heads": [("n_maps", "i", 2)] + [(n, "P", [0, 0]) for n in ("conf_w", "loc_w", "conf_b", "loc_b", "fwd", "flipped", "bias")] +
+                              [("Cin", "I", [64, 48]), ("n_conf", "I", [24, 20]), ("n_loc", "I", [16, 16]),
+                               ("strides", "L", _dense(24, 64, 3) + _dense(16, 64, 3) + _dense(20, 48, 3) + _dense(16, 48, 3))],
+    "ssdhip_ssd7_conv_wgrad_nhwc_bf16": [("x", "p", 0), ("dy", "p", 0), ("dw", "p", 0), ("db", "p", 0)] + _MAP7 +
+                                        [("Cin", "i", 64), ("Cout", "i", 64), ("kernel", "i", 3), ("out_bf16", "i", 0),
+                                         ("dw_strides", "L", _dense(64, 64, 3)), ("workspace", "p", 0), ("workspace_bytes", "z", 1 << 20)],
+    "ssdhip_ssd7_head_wgrad_nhwc_bf16": [("x", "p", 0), ("dy", "p", 0), ("dw_conf", "p", 0), ("db_conf", "p", 0), ("dw_loc", "p", 0),
+                                         ("db_loc", "p", 0)] + _MAP7 +
+                                        [("Cin", "i", 64), ("Cp", "i", 48), ("n_conf", "i", 24), ("n_loc", "i", 16), ("out_bf16", "i", 0),
+                                         ("dw_conf_strides", "L", _dense(24, 64, 3)), ("dw_loc_strides", "L", _dense(16, 64, 3)),
+                                         ("workspace", "p", 0), ("workspace_bytes", "z", 1 << 20)],
+})
+
 CHANNELS = (0, -1, 1, 32, 48, 64, 96, 128, 192)
 DIMS = (0, -1, 1)
 _VALUES = {"B": DIMS, "H": DIMS, "W": DIMS, "Cin": CHANNELS, "C": CHANNELS, "Cout": CHANNELS, "kernel": (0, 1, 2, 3, 5),
            "ksize": (0, 1, 2, 3, 5), "stride": (0, 1, 2, 3, 4, 5), "dilation": (0, 1, 8, 9, 16, 17), "relu": (0, 2), "pool": (0, 1, 2),
            "out_f32": (0, 1), "n_workgroups": (-1, 1, 3, 8, 256, 5000), "max_workgroups": (-1, 7, 8, 64), "variant": tuple(range(0, 10)),
            "n_problems": (0, -1, 1), "ksplit": (0, -1, 1, 9, 10, 1000), "oscale": (0.0, -1.0, 1.0, float("nan")),
-           "bias_rows": (31, 33, 0)}
+           "bias_rows": (31, 33, 0), "Cp": CHANNELS, "n_conf": (0,), "n_loc": (0,), "out_bf16": (0, 1)}
 
 
 def _below(limit, per, const=0):
@@ -103,6 +137,8 @@ def _generic(entry):
             out += [{name: None}] + [{name: [0, v]} for v in (None, 1, 2, 4, 8)]
         elif kind == "I":
             out += [{name: None}] + [{name: [base[name][0], v]} for v in _VALUES.get(name, ()) if v != base[name][1]]
+        elif kind == "L":                                  # the array null (dense, where the entry allows it); one negative stride
+            out += [{name: None}, {name: [-1] + base[name][1:]}]
         else:
             out += [{name: v} for v in _VALUES.get(name, ()) if v != base[name]]
     if "pad" in base and "stride" in base and "halo" not in entry:
@@ -119,7 +155,7 @@ def _generic(entry):
     if "pad" in base and "halo" in entry:                  # the strided slab form: stride 1 | 2, pad 0 | 1, the 3 x 3 span, W <= 94
         out += [{"pad": v} for v in (-1, 0, 2)] + [{"stride": s, "pad": p_} for s in (1, 2) for p_ in (0, 1)]
         out += [{"pad": 0, "H": h} for h in (2, 3)] + [{"pad": 0, "W": w} for w in (2, 3)] + [{"pad": 1, "H": 1, "W": 1}]
-    if not group and "W" in base and "image" not in entry:
+    if not group and "W" in base and "image" not in entry and entry not in SSD7_ENTRIES:
         out += [{"W": w} for w in (30, 31, 62, 63, 94, 95)]
     return out
 
@@ -310,6 +346,65 @@ def _special():
     # variant 7 of the 'same' profiling entry is the slab kernel: 3 x 3, dilation 1, 128-channel multiples
     for kw in ({"Cin": 128, "Cout": 128}, {"Cin": 128, "Cout": 128, "kernel": 1}, {"Cin": 128, "Cout": 128, "dilation": 2}, {}):
         add(samev, variant=7, **kw)
+    # --- the SSD7 family: each of the seven geometries once per entry; beside them the swapped pair, which is none
+    cbn, cbias, packf, packh = "ssdhip_conv_bn_elu_nhwc_bf16", "ssdhip_conv_same_bias_nhwc_bf16", "ssdhip_ssd7_pack_filters", "ssdhip_ssd7_pack_heads"
+    w7, h7 = "ssdhip_ssd7_conv_wgrad_nhwc_bf16", "ssdhip_ssd7_head_wgrad_nhwc_bf16"
+    for ci, co, k in SSD7_GEOMETRIES + ((32, 3, 5), (48, 3, 3)):
+        add(cbn, Cin=ci, Cout=co, kernel=k, pool=1)
+        add(cbias, Cin=ci, Cout=co, kernel=k)
+        add(w7, Cin=ci, Cout=co, kernel=k, dw_strides=_dense(co, ci, k))
+        add(packf, Cin=[64, ci], Cout=[64, co], kernel=[3, k], strides=_dense(64, 64, 3) + _dense(co, ci, k), flipped=[0, None])
+    add(packf, Cin=[64, 3], Cout=[64, 32], kernel=[3, 5], strides=_dense(64, 64, 3) + _dense(32, 3, 5))    # a flipped image of the 5 x 5 layer
+    add(packf, flipped=[None, None])
+    for e in (cbn, cbias, w7):                            # the 5 x 5 layer reads x at 2-byte alignment
+        add(e, Cin=3, Cout=32, kernel=5, x=2)
+        add(e, Cin=3, Cout=32, kernel=5, x=1)
+    for kw in ({"H": 1}, {"W": 1}, {"H": 2, "W": 2}):
+        add(cbn, pool=1, **kw)
+    add(cbn, pool=0, H=1, W=1)
+    # the position limits: B H W (and with it the tile count) <= 0x3fffffff; the heads' padded list B (H + 2)(W + 2) likewise
+    for b in (0x3fffffff, 0x40000000):
+        for e in (cbn, cbias):
+            add(e, B=b, H=1, W=1)
+        add(w7, B=b, H=1, W=1, workspace_bytes=1 << 62)
+    for b in (0x3fffffff // 9, 0x3fffffff // 9 + 1):
+        add(h7, B=b, H=1, W=1, workspace_bytes=1 << 62)
+    for w in (255, 256, 257):                             # the head kernel keeps 256 + 2 (W + 3) rows in LDS: W <= 256
+        add(h7, W=w, workspace_bytes=1 << 62)
+    # the workspaces: exact and one byte short.  Base calls: one split of (64 x 9 x 64 + 64) / (48 x 9 x 64 + 48) floats; Cin = 32 heads
+    # keep two step-parity partials; 8 x 40 x 70 at (48, 64) splits 20 ways, the heads' 32 x 37 x 37 64 ways
+    for e, kw, need in ((w7, {}, 147712), (w7, {"B": 8, "H": 40, "W": 70, "Cin": 48}, 20 * 110848), (h7, {}, 110784),
+                        (h7, {"Cin": 32}, 2 * 55488), (h7, {"B": 32, "H": 37, "W": 37}, 64 * 110784)):
+        for n in (need, need - 1):
+            add(e, workspace_bytes=n, **kw)
+    # outputs at 2-byte alignment: bf16 only
+    for bf in (1, 0):
+        add(w7, out_bf16=bf, dw=2, db=2)
+        add(h7, out_bf16=bf, dw_conf=2, db_conf=2, dw_loc=2, db_loc=2)
+    add(w7, db=None, out_bf16=1)
+    # element strides: zero is allowed; the farthest element they address (Cin = 64: 63 s1 + 2 s2) at 0x3fffffff and one past it
+    at, past = [0, 0x3fffffff // 63, 0, 0], [0, 0x3fffffff // 63 - 1, 32, 0]
+    for s in (at, past, [0, 0, 0, 0]):
+        add(w7, dw_strides=s)
+        add(h7, dw_conf_strides=s)
+        add(h7, dw_loc_strides=s)
+        add(packf, strides=s + _dense(32, 48, 3))
+        add(packh, strides=_dense(24, 64, 3) + s + _dense(20, 48, 3) + _dense(16, 48, 3))
+    add(packf, strides=_dense(64, 64, 3) + [5, 5, -5, 5])
+    add(packh, strides=_dense(24, 64, 3) + _dense(16, 64, 3) + _dense(20, 48, 3) + [1, 1, 1, -1])
+    add(h7, dw_conf_strides=None, dw_loc_strides=None)
+    # the heads' rows: n_conf + n_loc <= 48
+    for nc, nl in ((24, 24), (25, 24), (47, 1), (48, 1), (-1, 16)):
+        add(h7, n_conf=nc, n_loc=nl)
+        add(packh, n_conf=[24, nc], n_loc=[16, nl])
+    # the tables: 1, the maximum and one more layer / map; a later layer's pointer missing
+    for n in (0, 1, 8, 9):
+        add(packf, n_layers=n, weights=[0] * 9, fwd=[0] * 9, flipped=[0] * 9, Cin=[64] * 9, Cout=[64] * 9, kernel=[3] * 9,
+            strides=_dense(64, 64, 3) * 9)
+        add(packh, n_maps=n, Cin=[64] * 9, n_conf=[24] * 9, n_loc=[16] * 9, strides=_dense(24, 64, 3) * 18,
+            **{name: [0] * 9 for name in ("conf_w", "loc_w", "conf_b", "loc_b", "fwd", "flipped", "bias")})
+    add(packf, n_layers=8, weights=[0] * 7 + [None], fwd=[0] * 8, flipped=[0] * 8, Cin=[64] * 8, Cout=[64] * 8, kernel=[3] * 8,
+        strides=_dense(64, 64, 3) * 8)
     return c
 
 
@@ -366,6 +461,35 @@ def queries():
         add("ssdhip_conv3x3_halo_masked_bias_rows", r)
     for r in rows[:20:3]:
         add("ssdhip_conv3x3_halo_masked_bias_rows", r, {"SSDHIP_CONVH_GRID": "1"})
+    # the SSD7 family: the image size of the seven geometries and of their neighbours; the weight gradients' workspaces on the GPU
+    # suites' maps for every geometry, their plans (several ints each) for one map per geometry, and the limits
+    for geo in SSD7_GEOMETRIES + ((32, 3, 5), (48, 3, 3), (64, 32, 3), (32, 32, 3), (96, 64, 3), (64, 64, 1), (64, 64, 5), (0, 48, 3), (3, 32, 3)):
+        add("ssdhip_conv_bn_elu_pack_bytes", geo)
+    maps = [(3, 19, 37), (2, 10, 150), (1, 6, 480), (3, 40, 70), (8, 40, 70), (32, 300, 480), (32, 150, 240)]
+    bad = [(0, 9, 7), (2, -1, 7), (2, 9, 0), (0x3fffffff, 1, 1), (0x40000000, 1, 1), (1 << 16, 1 << 8, 1 << 6)]
+    for i, geo in enumerate(SSD7_GEOMETRIES):
+        add("ssdhip_ssd7_conv_wgrad_plan", maps[i] + geo)
+        for m in maps:
+            add("ssdhip_ssd7_conv_wgrad_workspace_bytes", m + geo)
+    for m in bad:                                         # (a refused plan is a line per int in the verdict file: two of them)
+        add("ssdhip_ssd7_conv_wgrad_workspace_bytes", m + (64, 64, 3))
+    for geo in ((64, 32, 3), (3, 32, 3)):
+        add("ssdhip_ssd7_conv_wgrad_workspace_bytes", maps[0] + geo)
+    add("ssdhip_ssd7_conv_wgrad_plan", bad[4] + (64, 64, 3))
+    add("ssdhip_ssd7_conv_wgrad_plan", maps[0] + (64, 32, 3))
+    maps = [(1, 4, 4), (8, 9, 9), (32, 18, 18), (32, 37, 37), (2, 9, 256), (512, 64, 256)]
+    bad = [(2, 9, 257), (0, 9, 7), (2, 0, 7), (2, 9, -1), (0x3fffffff // 9, 1, 1), (0x3fffffff // 9 + 1, 1, 1)]
+    for i, ci in enumerate((64, 48, 32)):
+        for m in maps:
+            add("ssdhip_ssd7_head_wgrad_workspace_bytes", m + (ci, 48))
+        for m in (maps[i], maps[3]):
+            add("ssdhip_ssd7_head_wgrad_plan", m + (ci, 48))
+    for m in bad:
+        add("ssdhip_ssd7_head_wgrad_workspace_bytes", m + (64, 48))
+    for ci, cp in ((96, 48), (3, 48), (64, 64), (64, 32)):
+        add("ssdhip_ssd7_head_wgrad_workspace_bytes", maps[1] + (ci, cp))
+    add("ssdhip_ssd7_head_wgrad_plan", bad[0] + (64, 48))
+    add("ssdhip_ssd7_head_wgrad_plan", maps[1] + (64, 64))
     return q
 
 
@@ -402,24 +526,25 @@ def run_case(lib, entry, over, env):
                 keep.append(arr)
                 args.append(ctypes.cast(arr, ctypes.c_void_p))
             slot += 1
-        elif kind == "I":
+        elif kind in ("I", "L"):
             if v is None:
                 args.append(None)
             else:
-                arr = (ctypes.c_int * len(v))(*v)
-                keep.append(arr)
-                args.append(ctypes.cast(arr, ctypes.c_void_p))
+                args.append(((ctypes.c_int if kind == "I" else ctypes.c_longlong) * len(v))(*v))   # as void* or as a typed pointer
         else:
             args.append(v)
     with _Env(env):
         return int(getattr(lib, entry)(*args, None))
 
 
+_PLAN_INTS = {"ssdhip_conv3x3_halo_plan": 4, "ssdhip_ssd7_conv_wgrad_plan": 4, "ssdhip_ssd7_head_wgrad_plan": 8}     # ints a plan query writes
+
+
 def run_query(lib, name, args, env):
     with _Env(env):
-        if name == "ssdhip_conv3x3_halo_plan":
-            plan = (ctypes.c_int * 4)(-7, -7, -7, -7)
-            rc = lib.ssdhip_conv3x3_halo_plan(*args, plan)
+        if name in _PLAN_INTS:
+            plan = (ctypes.c_int * _PLAN_INTS[name])(*[-7] * _PLAN_INTS[name])
+            rc = getattr(lib, name)(*args, plan)
             return [int(rc)] + list(plan)
         return int(getattr(lib, name)(*args))
 

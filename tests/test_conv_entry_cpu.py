@@ -3,7 +3,9 @@ tests/conv_entry_verdicts.json: per entry a valid base call and one-at-a-time pe
 off), dimension, channel count, kernel / stride / pad / dilation, of the form-specific arguments (pool, y2, bias_rows, oscale, ksplit
 and its workspace, n_problems, variant), both sides of every reachable byte / index limit and of the map-size and width limits, and
 the three host-only queries (split-K workspace bytes, the slab kernel's tiling plan, the masked form's bias rows), a few of them
-under SSDHIP_CONVH_GRID=1 / SSDHIP_CONVH_STACK=0 (tests/conv_entry_cases.py).
+under SSDHIP_CONVH_GRID=1 / SSDHIP_CONVH_STACK=0 (tests/conv_entry_cases.py).  The SSD7 family is in it too: its two convolution
+entries, two pack entries and two weight gradients (element strides, workspaces, the seven geometries, the heads' row counts) and
+its five queries (image bytes, the weight gradients' plans and workspace bytes).
 
 The addresses are made up, so this runs only where no launch can succeed: there host validation is all that happens, an accepted call
 ends as SSDHIP_E_LAUNCH (-3) and a refused one as SSDHIP_E_BADARG (-1) or SSDHIP_E_WORKSPACE (-2).
