@@ -1077,6 +1077,47 @@ int ssdhip_ssd_augment_decide_stream_ragged(const ssdhip_augment_params* params,
 int ssdhip_augment_plans_ragged(const int* geometry_dev, const long long* table_dev, int B, int out_h, int out_w, int n_taps, int* plan_dev,
                                 int* ix_dev, double* wx_dev, int* iy_dev, double* wy_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The decisions of the constant-input-size chain (DataAugmentationConstantInputSize, the chain ssd7_training.ipynb trains with;
+ * data_generator/data_augmentation_chain_constant_input_size.py) for a whole batch in ONE launch: per image `np.random.choice(2)` picks
+ * the sequence, the photometric draws follow in that sequence's order (brightness, contrast, saturation, hue | brightness, saturation,
+ * hue, contrast) and become the image's program for ssdhip_image_program, then RandomTranslate, RandomScale (zoom in | zoom out) and
+ * RandomFlip of object_detection_2d_geometric_ops.py run in the sequence's order (translate, zoom in, flip | zoom out, translate,
+ * flip) with their trial loops, the 'area' ImageValidator / BoxFilter (border_pixels 'half', restated from ssdhip_box_filter) and
+ * Translate's / Scale's / Flip's label arithmetic.  The random numbers are NumPy's MT19937 stream, consumed as numpy.random does.
+ *   ssdhip_const_augment_decide         one wave per image, image b on its own state: mt_state / mt_state_out [B][625];
+ *   ssdhip_const_augment_decide_stream  one wave walks the batch in order on ONE state: mt_state / mt_state_out [625].
+ *   labels [B][64][5] float64 rows (class_id, xmin, ymin, xmax, ymax), n_labels [B] <= 64; labels_out / n_labels_out likewise;
+ *   programs_ops [B][16] int32, programs_args [B][16] float64: the programs, read from the device by ssdhip_image_program;
+ *   geometry [B][8] float64: sequence (1 | 2), translated?, dx, dy (whole pixels, signed), scaled?, factor, flipped?, zoom before
+ *   the translation? (sequence 2) -- what ssdhip_const_augment_plans needs.
+ * SSDHIP_E_BADARG, with nothing launched, for a null pointer, B <= 0, a size <= 0, a probability outside [0, 1], n_trials outside
+ * [1, 64], n_boxes_min < 1, an empty range (max < min) or a zoom factor <= 0. */
+typedef struct ssdhip_const_augment_params {
+    int img_height, img_width;                       /* size of the batch's images */
+    double photo_prob[4], photo_lower[4], photo_upper[4];   /* RandomBrightness, RandomContrast, RandomSaturation, RandomHue */
+    double translate_prob, dy_min, dy_max, dx_min, dx_max;  /* RandomTranslate */
+    double zoom_in_prob, zoom_in_min, zoom_in_max;          /* RandomScale of sequence 1 */
+    double zoom_out_prob, zoom_out_min, zoom_out_max;       /* RandomScale of sequence 2 */
+    double flip_prob;
+    int n_trials;                                    /* max(1, n_trials_max) of RandomTranslate and RandomScale */
+    int clip_boxes;
+    int n_boxes_min;                                 /* ImageValidator */
+    double validator_lower, validator_upper;         /* ImageValidator's bounds ('area') */
+    double filter_lower, filter_upper, filter_min_area;     /* BoxFilter: overlap bounds ('area'), min_area; degenerate boxes dropped */
+} ssdhip_const_augment_params;
+int ssdhip_const_augment_decide(const ssdhip_const_augment_params* params, int B, const unsigned int* mt_state, const double* labels,
+                                const int* n_labels, int* programs_ops, double* programs_args, double* geometry, double* labels_out,
+                                int* n_labels_out, unsigned int* mt_state_out, void* stream);
+int ssdhip_const_augment_decide_stream(const ssdhip_const_augment_params* params, int B, const unsigned int* mt_state,
+                                       const double* labels, const int* n_labels, int* programs_ops, double* programs_args,
+                                       double* geometry, double* labels_out, int* n_labels_out, unsigned int* mt_state_out, void* stream);
+/* The tables of ssdhip_image_warp_affine_u8 for the batch, built on the device from `geometry` with the arithmetic of cv2.warpAffine's
+ * host side (the float64 inversion of cv2.getRotationMatrix2D((W / 2, H / 2), 0, factor), cvRound(. * 1024), + 16 on the row entries):
+ * geo [B][5] int32 = flip, pre dx, pre dy, post dx, post dy -- a translation before the zoom (or without one) is `pre`, one after it
+ * `post`; xtab [B][W][2], ytab [B][H][2] int32, the identity's for an image that is not zoomed. */
+int ssdhip_const_augment_plans(const double* geometry_dev, int B, int H, int W, int* geo_dev, int* xtab_dev, int* ytab_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,19 @@ class _AugPhoto(ctypes.Structure):                   # struct ssdhip_augment_pho
     _fields_ = [("prob", ctypes.c_double * 4), ("lower", ctypes.c_double * 4), ("upper", ctypes.c_double * 4), ("swap_prob", ctypes.c_double)]
 
 
+class _ConstAugParams(ctypes.Structure):             # struct ssdhip_const_augment_params (include/ssdhip.h)
+    _fields_ = [("img_height", ctypes.c_int), ("img_width", ctypes.c_int),
+                ("photo_prob", ctypes.c_double * 4), ("photo_lower", ctypes.c_double * 4), ("photo_upper", ctypes.c_double * 4),
+                ("translate_prob", ctypes.c_double), ("dy_min", ctypes.c_double), ("dy_max", ctypes.c_double),
+                ("dx_min", ctypes.c_double), ("dx_max", ctypes.c_double),
+                ("zoom_in_prob", ctypes.c_double), ("zoom_in_min", ctypes.c_double), ("zoom_in_max", ctypes.c_double),
+                ("zoom_out_prob", ctypes.c_double), ("zoom_out_min", ctypes.c_double), ("zoom_out_max", ctypes.c_double),
+                ("flip_prob", ctypes.c_double),
+                ("n_trials", ctypes.c_int), ("clip_boxes", ctypes.c_int), ("n_boxes_min", ctypes.c_int),
+                ("validator_lower", ctypes.c_double), ("validator_upper", ctypes.c_double),
+                ("filter_lower", ctypes.c_double), ("filter_upper", ctypes.c_double), ("filter_min_area", ctypes.c_double)]
+
+
 # The C ABI of include/ssdhip.h, one entry per export in the header's order: name -> (restype, argtypes).  load() applies it;
 # tests/test_host_cpu.py checks it against the header's prototypes.
 _I, _LL, _SZ, _D, _F, _P = ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_double, ctypes.c_float, ctypes.c_void_p
@@ -199,6 +212,9 @@ SIGNATURES = {
     "ssdhip_ssd_augment_decide_stream": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 10),
     "ssdhip_ssd_augment_decide_stream_ragged": (_I, [_PARAMS, _PHOTO, _I] + [_P] * 11),
     "ssdhip_augment_plans_ragged": (_I, [_P, _P] + [_I] * 4 + [_P] * 6),
+    "ssdhip_const_augment_decide": (_I, [ctypes.POINTER(_ConstAugParams), _I] + [_P] * 10),
+    "ssdhip_const_augment_decide_stream": (_I, [ctypes.POINTER(_ConstAugParams), _I] + [_P] * 10),
+    "ssdhip_const_augment_plans": (_I, [_P] + [_I] * 3 + [_P] * 4),
 }
 
 
@@ -2614,3 +2630,73 @@ def augment_plans_ragged(geo_dev, table, out_h, out_w, n_taps):
     launch("ssdhip_augment_plans_ragged", dev, _ptr(geo_dev), _ptr(table), B, int(out_h), int(out_w), int(n_taps), _ptr(plans), _ptr(ix),
            _ptr(wx), _ptr(iy), _ptr(wy))
     return plans, ix, wx, iy, wy
+
+
+# ---- the decisions of the constant-input-size chain for a whole batch (csrc/ssdhip_augment.hip) --------------------------------------
+CONST_AUG_GEO = 8                                     # geometry row: sequence, translated?, dx, dy, scaled?, factor, flipped?, zoom first?
+CONST_AUG_MAX_TRIALS = 64                             # the largest max(1, n_trials_max) the decision kernel takes
+
+
+def const_augment_decide(params, mt_states, labels, n_labels, device):
+    """`ssdhip_const_augment_decide` (mt_states (B, 625): image b on its own MT19937 state) or `ssdhip_const_augment_decide_stream`
+    (mt_states (625,): the batch in order on one state).  params: a dict of the fields of ssdhip_const_augment_params; labels
+    (B, 64, 5) float64, n_labels (B,) int32 NumPy arrays (ONE upload).  Returns (ops (B, 16) int32 and args (B, 16) float64 CUDA tensors
+    = the programs of image_program, geometry (B, 8) float64 CUDA tensor for const_augment_plans, fetch) where fetch() downloads
+    (geometry (B, 8), labels_out (B, 64, 5), n_out (B,), mt_states_out (B, 625) | (625,)) as NumPy arrays."""
+    torch = _torch()
+    q = _ConstAugParams()
+    for k, v in params.items():
+        if isinstance(v, (list, tuple)):
+            arr = getattr(q, k)
+            for i, e in enumerate(v):
+                arr[i] = e
+        else:
+            setattr(q, k, v)
+    B = int(labels.shape[0])
+    stream_mode = mt_states.ndim == 1
+    if mt_states.shape != ((625,) if stream_mode else (B, 625)) or labels.shape != (B, AUG_MAX_BOXES, 5) or n_labels.shape != (B,):
+        raise SsdHipError("const_augment_decide: mt_states (B, 625) or (625,), labels (B, 64, 5), n_labels (B,)")
+    # one packed upload: [labels f64 | mt u32 (padded to 8 bytes) | n i32];
+    # one packed download: [labels_out f64 | args f64 | geometry f64 | mt_out u32 (padded) | ops i32 | n_out i32]
+    n_mt = mt_states.size * 4
+    nl, nm = B * AUG_MAX_BOXES * 5 * 8, (n_mt + 7) // 8 * 8
+    host = np.zeros((nl + nm + B * 4,), dtype=np.uint8)
+    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
+    host[nl:nl + n_mt] = np.ascontiguousarray(mt_states, dtype=np.uint32).view(np.uint8).ravel()
+    host[nl + nm:] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
+    dev_in = torch.from_numpy(host).to(device)
+    na, ng = B * IMG_PROG * 8, B * CONST_AUG_GEO * 8
+    o_args, o_geo, o_mt = nl, nl + na, nl + na + ng
+    o_ops = o_mt + nm
+    o_n = o_ops + B * IMG_PROG * 4
+    dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
+    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
+    vp = ctypes.c_void_p
+    launch("ssdhip_const_augment_decide_stream" if stream_mode else "ssdhip_const_augment_decide", device, ctypes.byref(q), B,
+           vp(base_in + nl), vp(base_in), vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args), vp(base_out + o_geo),
+           vp(base_out), vp(base_out + o_n), vp(base_out + o_mt))
+    ops_dev = dev_out[o_ops:o_ops + B * IMG_PROG * 4].view(torch.int32).view(B, IMG_PROG)
+    args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG)
+    geo_dev = dev_out[o_geo:o_geo + ng].view(torch.float64).view(B, CONST_AUG_GEO)
+
+    def fetch():
+        """(geometry, labels_out, n_out, mt_states_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
+        out = dev_out.cpu().numpy()
+        return (out[o_geo:o_geo + ng].view(np.float64).reshape(B, CONST_AUG_GEO), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
+                out[o_n:].view(np.int32), out[o_mt:o_mt + n_mt].view(np.uint32).reshape(mt_states.shape).copy())
+    return ops_dev, args_dev, geo_dev, fetch
+
+
+def const_augment_plans(geo_dev, H, W):
+    """`ssdhip_const_augment_plans`: geometry (B, 8) float64 CUDA tensor (const_augment_decide's) -> (geo (B, 5) int32, xtab (B, W, 2),
+    ytab (B, H, 2) int32 CUDA tensors), what image_warp_affine_u8 takes for an output of the images' own size."""
+    torch = _torch()
+    require_cuda(geo_dev, "geometry")
+    if geo_dev.dim() != 2 or geo_dev.shape[1] != CONST_AUG_GEO or geo_dev.dtype != torch.float64:
+        raise SsdHipError("const_augment_plans: geometry (B, 8) float64")
+    B, dev = int(geo_dev.shape[0]), geo_dev.device
+    geo = torch.empty((B, 5), dtype=torch.int32, device=dev)
+    xtab = torch.empty((B, int(W), 2), dtype=torch.int32, device=dev)
+    ytab = torch.empty((B, int(H), 2), dtype=torch.int32, device=dev)
+    launch("ssdhip_const_augment_plans", dev, _ptr(geo_dev), B, int(H), int(W), _ptr(geo), _ptr(xtab), _ptr(ytab))
+    return geo, xtab, ytab

@@ -250,6 +250,37 @@ struct RaggedHW {
 };                              // steps of a program (include/ssdhip.h: SSDHIP_IMG_PROG)
 enum { OP_END = 0, OP_TO_F32 = 1, OP_TO_U8 = 2, OP_BRIGHTNESS = 3, OP_CONTRAST = 4, OP_SATURATION = 5, OP_HUE = 6, OP_RGB2HSV = 7, OP_HSV2RGB = 8 };
 
+// The photometric draws of one image as its program for ssdhip_image_program (SSDPhotometricDistortions.draw and
+// DataAugmentationConstantInputSize._draw): `if np.random.choice(2)` picks the sequence, every random op -- brightness, contrast,
+// saturation, hue = entries 0 .. 3 of prob / lo / hi -- draws uniform(0, 1) and, when it fires (>= 1 - prob), its parameter
+// uniform(lo, hi).  swap_draw: a RandomChannelSwap(prob = 0.0) ends the sequence -- its uniform(0, 1) >= 1.0 never holds, the draw is
+// consumed.  Returns whether sequence 1 (contrast before the HSV part) was drawn.
+__device__ __forceinline__ bool aug_photo_program(Mt& s, const int lane, const double* prob, const double* lo, const double* hi,
+                                                  const bool swap_draw, const int b, int* __restrict__ prog_ops,
+                                                  double* __restrict__ prog_args) {
+    int ops[AUG_PROG];
+    double args[AUG_PROG];
+    int k = 0;
+    auto push = [&](int op, double a) { ops[k] = op; args[k] = a; ++k; };
+    auto maybe = [&](int which, int op) {                // RandomX.draw(): the firing draw, then uniform(lower, upper)
+        if (mt_uniform(s, lane, 0.0, 1.0) >= (1.0 - prob[which])) push(op, mt_uniform(s, lane, lo[which], hi[which]));
+    };
+    const bool contrast_first = mt_randint(s, lane, 0, 2) != 0;
+    push(OP_TO_F32, 0.0);
+    maybe(0, OP_BRIGHTNESS);
+    if (contrast_first) maybe(1, OP_CONTRAST);
+    push(OP_TO_U8, 0.0); push(OP_RGB2HSV, 0.0); push(OP_TO_F32, 0.0);
+    maybe(2, OP_SATURATION);
+    maybe(3, OP_HUE);
+    push(OP_TO_U8, 0.0); push(OP_HSV2RGB, 0.0);
+    if (!contrast_first) { push(OP_TO_F32, 0.0); maybe(1, OP_CONTRAST); push(OP_TO_U8, 0.0); }
+    if (swap_draw) (void)mt_uniform(s, lane, 0.0, 1.0);
+    for (; k < AUG_PROG; ) push(OP_END, 0.0);
+    if (lane == 0)
+        for (int i = 0; i < AUG_PROG; ++i) { prog_ops[(size_t)b * AUG_PROG + i] = ops[i]; prog_args[(size_t)b * AUG_PROG + i] = args[i]; }
+    return contrast_first;
+}
+
 template <class HW>
 __global__ __launch_bounds__(64) void ssd_augment_stream_kernel(AugParams p, AugPhoto ph, HW hw, int B, const u32* __restrict__ mt_in,
                                                                 const double* __restrict__ lab_in, const int* __restrict__ n_in,
@@ -265,28 +296,8 @@ __global__ __launch_bounds__(64) void ssd_augment_stream_kernel(AugParams p, Aug
     s.base = -1; s.win = 0u;
     __syncthreads();
     for (int b = 0; b < B; ++b) {
-        // ---- SSDPhotometricDistortions.__call__: `if np.random.choice(2)` picks the sequence, every random op draws uniform(0, 1) and,
-        //      when it fires (>= 1 - prob), its parameter; RandomChannelSwap(prob 0) draws and never fires ---------------------------------
-        int ops[AUG_PROG];
-        double args[AUG_PROG];
-        int k = 0;
-        auto push = [&](int op, double a) { ops[k] = op; args[k] = a; ++k; };
-        auto maybe = [&](int which, int op) {            // RandomX.draw(): the firing draw, then uniform(lower, upper)
-            if (mt_uniform(s, lane, 0.0, 1.0) >= (1.0 - ph.prob[which])) push(op, mt_uniform(s, lane, ph.lo[which], ph.hi[which]));
-        };
-        const bool contrast_first = mt_randint(s, lane, 0, 2) != 0;
-        push(OP_TO_F32, 0.0);
-        maybe(0, OP_BRIGHTNESS);
-        if (contrast_first) maybe(1, OP_CONTRAST);
-        push(OP_TO_U8, 0.0); push(OP_RGB2HSV, 0.0); push(OP_TO_F32, 0.0);
-        maybe(2, OP_SATURATION);
-        maybe(3, OP_HUE);
-        push(OP_TO_U8, 0.0); push(OP_HSV2RGB, 0.0);
-        if (!contrast_first) { push(OP_TO_F32, 0.0); maybe(1, OP_CONTRAST); push(OP_TO_U8, 0.0); }
-        (void)mt_uniform(s, lane, 0.0, 1.0);             // RandomChannelSwap(prob = 0.0): uniform(0, 1) >= 1.0 never holds
-        for (; k < AUG_PROG; ) push(OP_END, 0.0);
-        if (lane == 0)
-            for (int i = 0; i < AUG_PROG; ++i) { prog_ops[(size_t)b * AUG_PROG + i] = ops[i]; prog_args[(size_t)b * AUG_PROG + i] = args[i]; }
+        // ---- SSDPhotometricDistortions.__call__; RandomChannelSwap(prob 0) draws and never fires ---------------------------------------
+        (void)aug_photo_program(s, lane, ph.prob, ph.lo, ph.hi, true, b, prog_ops, prog_args);
         // ---- the geometric half on the same stream ------------------------------------------------------------------------------------
         aug_decide_image(p, s, lane, b, hw.h(b), hw.w(b), lab_in, n_in, geo, lab_out, n_out);
     }
@@ -468,6 +479,201 @@ __global__ __launch_bounds__(128) void aug_plan_kernel(const int* __restrict__ g
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// DataAugmentationConstantInputSize (data_generator/data_augmentation_chain_constant_input_size.py), the chain ssd7_training.ipynb
+// trains with: per image `np.random.choice(2)` picks the sequence, the photometric draws follow in that sequence's order (`_draw`), then
+// RandomTranslate / RandomScale / RandomFlip of object_detection_2d_geometric_ops.py run in the sequence's order -- their firing draws,
+// their trial loops (ImageValidator on the candidate labels, the first valid trial ends the loop and the draws), and Translate's /
+// Scale's / Flip's label arithmetic (shift or matrix + rint, BoxFilter, clip).  The host ran this per image with one validator / box-filter
+// launch and download per trial (10.1 ms for a batch of 32 whose two pixel kernels take a fraction of that); here a wave does it on the
+// image's MT19937 stream, lane = ground truth box.  The pixels stay where they were: the programs go to ssdhip_image_program, the
+// geometry rows to const_plan_kernel below and from there to ssdhip_image_warp_affine_u8.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+struct ConstAugParams {
+    int H, W;
+    double ph_prob[4], ph_lo[4], ph_hi[4];                // RandomBrightness, RandomContrast, RandomSaturation, RandomHue
+    double tr_prob, dy_lo, dy_hi, dx_lo, dx_hi;           // RandomTranslate
+    double zin_prob, zin_lo, zin_hi;                      // RandomScale of sequence 1 (zoom in)
+    double zout_prob, zout_lo, zout_hi;                   // RandomScale of sequence 2 (zoom out)
+    double flip_prob;
+    int n_trials, clip, n_min;                            // max(1, n_trials_max), clip_boxes, ImageValidator's n_boxes_min
+    double val_lo, val_hi;                                // ImageValidator's bounds
+    double flt_lo, flt_hi, min_area;                      // BoxFilter's overlap bounds and min_area
+};
+constexpr int CAUG_GEO = 8;                               // geometry row: sequence, translated?, dx, dy, scaled?, factor, flipped?, zoom first?
+
+// BoxFilter's 'area' criterion with border_pixels 'half' (d = 0), as box_filter_kernel (csrc/ssdhip_boxes.hip) evaluates it: the box's
+// area inside the image over its whole area within (lower, upper] -- [lower, upper] for a lower bound that is not 0.
+__device__ __forceinline__ bool caug_area_ok(double xmin, double ymin, double xmax, double ymax, double H, double W, double lower,
+                                             double upper) {
+    const double d = 0.0;
+    const double box_area_ = ((xmax - xmin) + d) * ((ymax - ymin) + d);
+    const double cy0 = np_minimum<double>(np_maximum<double>(ymin, 0.0), H - 1.0), cy1 = np_minimum<double>(np_maximum<double>(ymax, 0.0), H - 1.0);
+    const double cx0 = np_minimum<double>(np_maximum<double>(xmin, 0.0), W - 1.0), cx1 = np_minimum<double>(np_maximum<double>(xmax, 0.0), W - 1.0);
+    const double inter = ((cx1 - cx0) + d) * ((cy1 - cy0) + d);
+    const bool lo = lower == 0.0 ? (inter > lower * box_area_) : (inter >= lower * box_area_);
+    return lo && (inter <= upper * box_area_);
+}
+// the chain's BoxFilter (check_overlap 'area', check_min_area, check_degenerate), then the clip of Translate / Scale
+__device__ __forceinline__ void caug_filter_clip(const ConstAugParams& p, bool& alive, double& x0, double& y0, double& x1, double& y1) {
+    const double H = (double)p.H, W = (double)p.W;
+    alive = alive && (x1 > x0) && (y1 > y0) && ((x1 - x0) * (y1 - y0) >= p.min_area) && caug_area_ok(x0, y0, x1, y1, H, W, p.flt_lo, p.flt_hi);
+    if (p.clip) {
+        y0 = np_minimum<double>(np_maximum<double>(y0, 0.0), H - 1.0); y1 = np_minimum<double>(np_maximum<double>(y1, 0.0), H - 1.0);
+        x0 = np_minimum<double>(np_maximum<double>(x0, 0.0), W - 1.0); x1 = np_minimum<double>(np_maximum<double>(x1, 0.0), W - 1.0);
+    }
+}
+// _image_ops.rotation_matrix_2d((W / 2, H / 2), 0, factor): the centre is a Point2f, the result float64
+__device__ __forceinline__ void caug_matrix(double factor, int H, int W, double* m) {
+    const double cx = (double)(float)((double)W / 2.0), cy = (double)(float)((double)H / 2.0);
+    const double a = 1.0 * factor, b = 0.0 * factor;     // cos(0) scale, sin(0) scale
+    m[0] = a; m[1] = b; m[2] = (1.0 - a) * cx - b * cy;
+    m[3] = -b; m[4] = a; m[5] = b * cx + (1.0 - a) * cy;
+}
+
+// RandomTranslate.__call__ (:200-224) + Translate's label arithmetic (:154-172)
+__device__ __forceinline__ void caug_translate(const ConstAugParams& p, Mt& s, const int lane, bool& alive, double& x0, double& y0,
+                                               double& x1, double& y1, double* g) {
+    if (!(mt_uniform(s, lane, 0.0, 1.0) >= (1.0 - p.tr_prob))) return;
+    for (int t = 0; t < p.n_trials; ++t) {
+        const double dy_abs = mt_uniform(s, lane, p.dy_lo, p.dy_hi);
+        const double dx_abs = mt_uniform(s, lane, p.dx_lo, p.dx_hi);
+        const double dy = mt_randint(s, lane, 0, 2) ? dy_abs : -dy_abs;       // np.random.choice([-dy_abs, dy_abs])
+        const double dx = mt_randint(s, lane, 0, 2) ? dx_abs : -dx_abs;
+        const double sy = __builtin_rint((double)p.H * dy), sx = __builtin_rint((double)p.W * dx);   // int(round(.)): ties to even
+        const bool ok = alive && caug_area_ok(x0 + sx, y0 + sy, x1 + sx, y1 + sy, (double)p.H, (double)p.W, p.val_lo, p.val_hi);
+        if (__popcll(__ballot(ok)) < p.n_min) continue;
+        x0 += sx; x1 += sx; y0 += sy; y1 += sy;
+        caug_filter_clip(p, alive, x0, y0, x1, y1);
+        g[1] = 1.0; g[2] = sx; g[3] = sy;
+        return;
+    }
+}
+// RandomScale.__call__ (:282-304) + Scale's label arithmetic (:241-258): the corners through M as np.dot(M, [x, y, 1]) sums them
+__device__ __forceinline__ void caug_scale(const ConstAugParams& p, Mt& s, const int lane, double prob, double lo, double hi, bool& alive,
+                                           double& x0, double& y0, double& x1, double& y1, double* g) {
+    if (!(mt_uniform(s, lane, 0.0, 1.0) >= (1.0 - prob))) return;
+    for (int t = 0; t < p.n_trials; ++t) {
+        const double factor = mt_uniform(s, lane, lo, hi);
+        double m[6];
+        caug_matrix(factor, p.H, p.W, m);
+        const double nx0 = __builtin_rint((m[0] * x0 + m[1] * y0) + m[2] * 1.0), ny0 = __builtin_rint((m[3] * x0 + m[4] * y0) + m[5] * 1.0);
+        const double nx1 = __builtin_rint((m[0] * x1 + m[1] * y1) + m[2] * 1.0), ny1 = __builtin_rint((m[3] * x1 + m[4] * y1) + m[5] * 1.0);
+        const bool ok = alive && caug_area_ok(nx0, ny0, nx1, ny1, (double)p.H, (double)p.W, p.val_lo, p.val_hi);
+        if (__popcll(__ballot(ok)) < p.n_min) continue;
+        x0 = nx0; y0 = ny0; x1 = nx1; y1 = ny1;
+        caug_filter_clip(p, alive, x0, y0, x1, y1);
+        g[4] = 1.0; g[5] = factor;
+        return;
+    }
+}
+
+// ONE image of the chain by one wave on the generator state `s`: `_draw`, then the three geometric ops.
+__device__ __forceinline__ void caug_decide_image(const ConstAugParams& p, Mt& s, const int lane, const int b,
+                                                  const double* __restrict__ lab_in, const int* __restrict__ n_in,
+                                                  int* __restrict__ prog_ops, double* __restrict__ prog_args, double* __restrict__ geo,
+                                                  double* __restrict__ lab_out, int* __restrict__ n_out) {
+    // ---- _draw: the sequence choice and the photometric draws in that sequence's order (this chain has no channel swap) ---------------
+    const bool seq1 = aug_photo_program(s, lane, p.ph_prob, p.ph_lo, p.ph_hi, false, b, prog_ops, prog_args);
+
+    // ---- the geometric ops on the same stream: translate, zoom in, flip | zoom out, translate, flip -----------------------------------
+    const int n = n_in[b];
+    bool alive = lane < n;
+    double cls = 0.0, x0 = 0.0, y0 = 0.0, x1 = 0.0, y1 = 0.0;
+    if (alive) {
+        const double* r = lab_in + ((size_t)b * AUG_MAXG + lane) * 5;
+        cls = r[0]; x0 = r[1]; y0 = r[2]; x1 = r[3]; y1 = r[4];
+    }
+    double g[CAUG_GEO] = {seq1 ? 1.0 : 2.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, seq1 ? 0.0 : 1.0};
+    if (seq1) {
+        caug_translate(p, s, lane, alive, x0, y0, x1, y1, g);
+        caug_scale(p, s, lane, p.zin_prob, p.zin_lo, p.zin_hi, alive, x0, y0, x1, y1, g);
+    } else {
+        caug_scale(p, s, lane, p.zout_prob, p.zout_lo, p.zout_hi, alive, x0, y0, x1, y1, g);
+        caug_translate(p, s, lane, alive, x0, y0, x1, y1, g);
+    }
+    if (!(mt_uniform(s, lane, 0.0, 1.0) < (1.0 - p.flip_prob))) {                           // RandomFlip('horizontal') :121-125, Flip :99-105
+        const double nx0 = (double)p.W - x1, nx1 = (double)p.W - x0;
+        x0 = nx0; x1 = nx1;
+        g[6] = 1.0;
+    }
+
+    const u64 keep = __ballot(alive);
+    if (alive) {
+        const int pos = __popcll(keep & lanemask_lt());
+        double* r = lab_out + ((size_t)b * AUG_MAXG + pos) * 5;
+        r[0] = cls; r[1] = x0; r[2] = y0; r[3] = x1; r[4] = y1;
+    }
+    if (lane == 0) {
+        n_out[b] = __popcll(keep);
+        for (int i = 0; i < CAUG_GEO; ++i) geo[(size_t)b * CAUG_GEO + i] = g[i];
+    }
+}
+
+// STREAM = false: one wave per image, image b on its own state (mt [B][625]); true: one wave walks the B images in order on one state
+template <bool STREAM>
+__global__ __launch_bounds__(64) void const_augment_decide_kernel(ConstAugParams p, int B, const u32* __restrict__ mt_in,
+                                                                  const double* __restrict__ lab_in, const int* __restrict__ n_in,
+                                                                  int* __restrict__ prog_ops, double* __restrict__ prog_args,
+                                                                  double* __restrict__ geo, double* __restrict__ lab_out,
+                                                                  int* __restrict__ n_out, u32* __restrict__ mt_out) {
+    __shared__ u32 key[624];
+    const int lane = (int)threadIdx.x;
+    const size_t at = STREAM ? 0 : (size_t)blockIdx.x * 625;
+    for (int i = lane; i < 624; i += 64) key[i] = mt_in[at + i];
+    Mt s;
+    s.key = key;
+    s.pos = (int)mt_in[at + 624];
+    s.base = -1; s.win = 0u;
+    __syncthreads();
+    if (STREAM) {
+        for (int b = 0; b < B; ++b) caug_decide_image(p, s, lane, b, lab_in, n_in, prog_ops, prog_args, geo, lab_out, n_out);
+    } else {
+        caug_decide_image(p, s, lane, (int)blockIdx.x, lab_in, n_in, prog_ops, prog_args, geo, lab_out, n_out);
+    }
+    if (lane == 0) mt_out[at + 624] = (u32)s.pos;
+    __syncthreads();
+    for (int i = lane; i < 624; i += 64) mt_out[at + i] = key[i];
+}
+
+// The geometry rows -> what ssdhip_image_warp_affine_u8 takes, by _image_ops.WarpImage's composition rules (a whole-pixel translation
+// before the zoom, or without one, is `pre`; one after it is `post`; a zoom by exactly 1 is a translation by (0, 0)) and the float64
+// arithmetic of _image_ops.invert_affine / warp_tables.  grid (blocks over positions, 2 axes, B); axis 0 = columns, 1 = rows.
+__global__ __launch_bounds__(128) void const_plan_kernel(const double* __restrict__ geometry, int H, int W, int* __restrict__ geo,
+                                                         int* __restrict__ xtab, int* __restrict__ ytab) {
+    const int b = (int)blockIdx.z, axis = (int)blockIdx.y;
+    const int i = (int)blockIdx.x * 128 + (int)threadIdx.x;
+    const double* g = geometry + (size_t)b * CAUG_GEO;
+    const bool translated = g[1] != 0.0, scaled = g[4] != 0.0 && g[5] != 1.0;
+    if (axis == 0 && i == 0) {
+        const bool post = translated && scaled && g[7] != 0.0;
+        const int dx = translated ? (int)g[2] : 0, dy = translated ? (int)g[3] : 0;
+        int* o = geo + (size_t)b * 5;
+        o[0] = g[6] != 0.0 ? 1 : 0;
+        o[1] = post ? 0 : dx; o[2] = post ? 0 : dy;
+        o[3] = post ? dx : 0; o[4] = post ? dy : 0;
+    }
+    double m[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    if (scaled) caug_matrix(g[5], H, W, m);
+    double d = m[0] * m[4] - m[1] * m[3];                                     // invert_affine
+    d = d != 0.0 ? 1.0 / d : 0.0;
+    const double a11 = m[4] * d, a22 = m[0] * d;
+    m[0] = a11; m[1] = m[1] * -d; m[3] = m[3] * -d; m[4] = a22;
+    const double b1 = -m[0] * m[2] - m[1] * m[5];
+    const double b2 = -m[3] * m[2] - m[4] * m[5];
+    m[2] = b1; m[5] = b2;
+    const double v = (double)i;                                               // warp_tables
+    if (axis == 0 && i < W) {
+        int* o = xtab + ((size_t)b * W + i) * 2;
+        o[0] = (int)__builtin_rint(m[0] * v * 1024.0);
+        o[1] = (int)__builtin_rint(m[3] * v * 1024.0);
+    } else if (axis == 1 && i < H) {
+        int* o = ytab + ((size_t)b * H + i) * 2;
+        o[0] = (int)(__builtin_rint((m[1] * v + m[2]) * 1024.0) + 16.0);
+        o[1] = (int)(__builtin_rint((m[4] * v + m[5]) * 1024.0) + 16.0);
+    }
+}
+
 }  // namespace ssdhip
 
 using namespace ssdhip;
@@ -580,5 +786,73 @@ extern "C" int ssdhip_augment_plans_ragged(const int* geometry_dev, const long l
     const int n = out_h > out_w ? out_h : out_w;
     hipLaunchKernelGGL(aug_plan_kernel<RaggedHW>, dim3((unsigned)((n + 127) / 128), 2, (unsigned)B), dim3(128), 0, stream, geometry_dev,
                        RaggedHW{table_dev}, out_h, out_w, n_taps, plan_dev, ix_dev, wx_dev, iy_dev, wy_dev);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// ---- DataAugmentationConstantInputSize: the decisions of a batch (seeded: B states; stream: one) and the warp launch's tables -----------
+static int const_params_from(const ssdhip_const_augment_params* q, ConstAugParams& p) {
+    const auto prob = [](double v) { return v >= 0.0 && v <= 1.0; };
+    if (q->img_height <= 0 || q->img_width <= 0 || q->img_height > 32767 || q->img_width > 32767) return SSDHIP_E_BADARG;
+    for (int i = 0; i < 4; ++i)
+        if (!prob(q->photo_prob[i]) || !(q->photo_upper[i] >= q->photo_lower[i])) return SSDHIP_E_BADARG;
+    if (!prob(q->translate_prob) || !prob(q->zoom_in_prob) || !prob(q->zoom_out_prob) || !prob(q->flip_prob)) return SSDHIP_E_BADARG;
+    if (!(q->dy_min >= 0.0) || !(q->dy_max >= q->dy_min) || !(q->dx_min >= 0.0) || !(q->dx_max >= q->dx_min)) return SSDHIP_E_BADARG;
+    if (!(q->zoom_in_min > 0.0) || !(q->zoom_in_max >= q->zoom_in_min) || !(q->zoom_out_min > 0.0) || !(q->zoom_out_max >= q->zoom_out_min))
+        return SSDHIP_E_BADARG;
+    if (q->n_trials < 1 || q->n_trials > 64 || q->n_boxes_min < 1) return SSDHIP_E_BADARG;
+    if (!(q->validator_upper >= q->validator_lower) || !(q->filter_upper >= q->filter_lower) || !(q->filter_min_area == q->filter_min_area))
+        return SSDHIP_E_BADARG;
+    p.H = q->img_height; p.W = q->img_width;
+    for (int i = 0; i < 4; ++i) { p.ph_prob[i] = q->photo_prob[i]; p.ph_lo[i] = q->photo_lower[i]; p.ph_hi[i] = q->photo_upper[i]; }
+    p.tr_prob = q->translate_prob; p.dy_lo = q->dy_min; p.dy_hi = q->dy_max; p.dx_lo = q->dx_min; p.dx_hi = q->dx_max;
+    p.zin_prob = q->zoom_in_prob; p.zin_lo = q->zoom_in_min; p.zin_hi = q->zoom_in_max;
+    p.zout_prob = q->zoom_out_prob; p.zout_lo = q->zoom_out_min; p.zout_hi = q->zoom_out_max;
+    p.flip_prob = q->flip_prob;
+    p.n_trials = q->n_trials; p.clip = q->clip_boxes != 0; p.n_min = q->n_boxes_min;
+    p.val_lo = q->validator_lower; p.val_hi = q->validator_upper;
+    p.flt_lo = q->filter_lower; p.flt_hi = q->filter_upper; p.min_area = q->filter_min_area;
+    return SSDHIP_OK;
+}
+
+template <bool STREAM>
+static int const_decide(const ssdhip_const_augment_params* q, int B, const unsigned int* mt_state, const double* labels, const int* n_labels,
+                        int* programs_ops, double* programs_args, double* geometry, double* labels_out, int* n_labels_out,
+                        unsigned int* mt_state_out, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!q || B <= 0 || !mt_state || !labels || !n_labels || !programs_ops || !programs_args || !geometry || !labels_out || !n_labels_out ||
+        !mt_state_out)
+        return SSDHIP_E_BADARG;
+    ConstAugParams p;
+    const int rc = const_params_from(q, p);
+    if (rc != SSDHIP_OK) return rc;
+    hipLaunchKernelGGL(const_augment_decide_kernel<STREAM>, dim3(STREAM ? 1u : (unsigned)B), dim3(64), 0, stream, p, B, mt_state, labels,
+                       n_labels, programs_ops, programs_args, geometry, labels_out, n_labels_out, mt_state_out);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_const_augment_decide(const ssdhip_const_augment_params* params, int B, const unsigned int* mt_state,
+                                           const double* labels, const int* n_labels, int* programs_ops, double* programs_args,
+                                           double* geometry, double* labels_out, int* n_labels_out, unsigned int* mt_state_out,
+                                           void* stream) {
+    return const_decide<false>(params, B, mt_state, labels, n_labels, programs_ops, programs_args, geometry, labels_out, n_labels_out,
+                               mt_state_out, stream);
+}
+
+extern "C" int ssdhip_const_augment_decide_stream(const ssdhip_const_augment_params* params, int B, const unsigned int* mt_state,
+                                                  const double* labels, const int* n_labels, int* programs_ops, double* programs_args,
+                                                  double* geometry, double* labels_out, int* n_labels_out, unsigned int* mt_state_out,
+                                                  void* stream) {
+    return const_decide<true>(params, B, mt_state, labels, n_labels, programs_ops, programs_args, geometry, labels_out, n_labels_out,
+                              mt_state_out, stream);
+}
+
+extern "C" int ssdhip_const_augment_plans(const double* geometry_dev, int B, int H, int W, int* geo_dev, int* xtab_dev, int* ytab_dev,
+                                          void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!geometry_dev || !geo_dev || !xtab_dev || !ytab_dev || B <= 0 || B > 65535 || H <= 0 || W <= 0 || H > 32767 || W > 32767)
+        return SSDHIP_E_BADARG;
+    const int n = H > W ? H : W;
+    hipLaunchKernelGGL(const_plan_kernel, dim3((unsigned)((n + 127) / 128), 2, (unsigned)B), dim3(128), 0, stream, geometry_dev, H, W,
+                       geo_dev, xtab_dev, ytab_dev);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }

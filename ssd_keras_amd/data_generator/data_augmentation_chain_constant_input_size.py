@@ -5,8 +5,11 @@ two orders drawn per image (`np.random.choice(2)`), for images that all have one
 `__call__` runs the reference's list of transforms image by image; the photometric part is one pixel program per image (the ops' own
 `draw()` in the reference's order, csrc/ssdhip_image.hip) and each translation / zoom is one cv2.warpAffine launch (csrc/ssdhip_warp.hip).
 `augment_batch` does the same for a CUDA batch in TWO pixel launches: every image's photometric program in one, and translation, zoom
-and flip of the whole batch as one warp -- the geometric ops run on a lazy image (`_image_ops.WarpImage`) that only records them, so
-their random draws, validation and label arithmetic are the per-image chain's own code in the per-image chain's order."""
+and flip of the whole batch as one warp.  The random draws, the validation of every trial and the label arithmetic of a batch run on the
+device too (csrc/ssdhip_augment.hip: `ssdhip_const_augment_decide[_stream]` on NumPy's MT19937 stream -- the global one, or one per image
+with `seeds=` -- and `ssdhip_const_augment_plans` for the warp's tables); what that kernel does not cover (`_device_params`) runs the
+geometric ops on a lazy image (`_image_ops.WarpImage`) that only records them, so their draws, validation and label arithmetic are the
+per-image chain's own code in the per-image chain's order.  Either way the results are those of the `__call__` loop, bit for bit."""
 from __future__ import annotations
 
 import numpy as np
@@ -16,6 +19,29 @@ from .object_detection_2d_geometric_ops import RandomFlip, RandomScale, RandomTr
 from .object_detection_2d_image_boxes_validation_utils import BoxFilter, ImageValidator
 from .object_detection_2d_photometric_ops import (ConvertColor, ConvertDataType, ConvertTo3Channels, RandomBrightness, RandomContrast,
                                                   RandomHue, RandomSaturation)
+
+
+def _seed_states(seeds):
+    """(B, 625) uint32: per seed the MT19937 state `np.random.seed(seed)` leaves in the global generator (624 key words + the position),
+    without touching that generator.  `RandomState.get_state()` builds its tuple in 50 - 180 us, more than the rest of a seeded batch
+    takes per image, so the words are read where NumPy keeps them (`MT19937().ctypes.state_address`: uint32 key[624], int pos); the
+    first row of every call is held against `get_state()`, and if NumPy ever lays the state out differently all rows come from it."""
+    import ctypes
+    bit_generator = np.random.MT19937()
+    rs = np.random.RandomState(bit_generator)
+    out = np.empty((len(seeds), 625), dtype=np.uint32)
+    direct = True
+    for i, seed in enumerate(seeds):
+        rs.seed(int(seed))
+        if direct:
+            out[i] = np.frombuffer(ctypes.string_at(bit_generator.ctypes.state_address, 2500), dtype=np.uint32)
+        if i == 0 or not direct:
+            st = rs.get_state()
+            if i == 0 and not (np.array_equal(out[0, :624], st[1]) and int(out[0, 624]) == st[2]):
+                direct = False
+            if not direct:
+                out[i, :624], out[i, 624] = st[1], st[2]
+    return out
 
 
 class DataAugmentationConstantInputSize:
@@ -111,18 +137,145 @@ class DataAugmentationConstantInputSize:
             image = transform(image)
         return image
 
-    def augment_batch(self, images, labels):
+    def _device_params(self, labels=None, generator='MT19937'):
+        """The chain's configuration as the fields of ssdhip_const_augment_params (without the image size), or None for anything the
+        decision kernel (csrc/ssdhip_augment.hip) does not cover: an overlap criterion other than 'area', `border_pixels` other than
+        'half', `n_boxes_min == 'all'`, more than 64 trials (`nat.CONST_AUG_MAX_TRIALS`), a probability outside [0, 1], bounds that are
+        not a pair of numbers, ops that no longer share the chain's box filter / validator / clipping / background -- and, when `labels`
+        is given, label arrays that are not (n, 5), of mixed dtype, not int64 / float64 or longer than `nat.AUG_MAX_BOXES`; `generator`:
+        the name of np.random's bit generator, MT19937 is the one the kernel steps."""
+        from .. import _native as nat
+        tr, zin, zout, fl = self.random_translate, self.random_zoom_in, self.random_zoom_out, self.random_flip
+        bf, val = self.box_filter, self.image_validator
+        photo = (self.random_brightness, self.random_contrast, self.random_saturation, self.random_hue)
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+        pair = lambda v: isinstance(v, (list, tuple)) and len(v) == 2 and number(v[0]) and number(v[1]) and v[0] <= v[1]
+        ok = (generator == 'MT19937'
+              and all(op.box_filter is bf and op.image_validator is val for op in (tr, zin, zout))
+              and isinstance(bf, BoxFilter) and isinstance(val, ImageValidator)
+              and bf.overlap_criterion == 'area' and val.overlap_criterion == 'area'
+              and bf.border_pixels == 'half' and val.border_pixels == 'half'
+              and bf.check_overlap and bf.check_min_area and bf.check_degenerate and number(bf.min_area)
+              and pair(bf.overlap_bounds) and pair(val.bounds)
+              and val.n_boxes_min != 'all' and isinstance(val.n_boxes_min, (int, np.integer)) and val.n_boxes_min >= 1
+              and all(isinstance(op.n_trials_max, (int, np.integer)) for op in (tr, zin, zout))
+              and tr.n_trials_max == zin.n_trials_max == zout.n_trials_max and max(1, tr.n_trials_max) <= nat.CONST_AUG_MAX_TRIALS
+              and bool(tr.clip_boxes) == bool(zin.clip_boxes) == bool(zout.clip_boxes)
+              and all(number(op.prob) and 0.0 <= op.prob <= 1.0 for op in photo + (tr, zin, zout, fl))
+              and fl.dim == 'horizontal' and pair(tr.dy_minmax) and pair(tr.dx_minmax) and tr.dy_minmax[0] >= 0 and tr.dx_minmax[0] >= 0
+              and 0 < zin.min_factor <= zin.max_factor and 0 < zout.min_factor <= zout.max_factor
+              and sorted(self.labels_format.get(k, -1) for k in ('class_id', 'xmin', 'ymin', 'xmax', 'ymax')) == [0, 1, 2, 3, 4])
+        if ok:
+            try:
+                bgs = {tuple(int(v) for v in iop.border_value(op.background, 3)) for op in (tr, zin, zout)}
+                ok = len(bgs) == 1
+            except (TypeError, ValueError):
+                ok = False
+        if ok and labels is not None:
+            arrs = [np.asarray(lab) for lab in labels]
+            dtypes = {a.dtype for a in arrs}
+            ok = (len(dtypes) == 1 and next(iter(dtypes)) in (np.dtype(np.int64), np.dtype(np.float64))
+                  and all(a.ndim == 2 and a.shape[1] == 5 and a.shape[0] <= nat.AUG_MAX_BOXES for a in arrs))
+        if not ok:
+            return None
+        return dict(photo_prob=[float(op.prob) for op in photo],
+                    photo_lower=[float(op.lower) for op in photo[:3]] + [-float(self.random_hue.max_delta)],
+                    photo_upper=[float(op.upper) for op in photo[:3]] + [float(self.random_hue.max_delta)],
+                    translate_prob=float(tr.prob), dy_min=float(tr.dy_minmax[0]), dy_max=float(tr.dy_minmax[1]),
+                    dx_min=float(tr.dx_minmax[0]), dx_max=float(tr.dx_minmax[1]),
+                    zoom_in_prob=float(zin.prob), zoom_in_min=float(zin.min_factor), zoom_in_max=float(zin.max_factor),
+                    zoom_out_prob=float(zout.prob), zoom_out_min=float(zout.min_factor), zoom_out_max=float(zout.max_factor),
+                    flip_prob=float(fl.prob), n_trials=int(max(1, tr.n_trials_max)), clip_boxes=int(bool(tr.clip_boxes)),
+                    n_boxes_min=int(val.n_boxes_min), validator_lower=float(val.bounds[0]), validator_upper=float(val.bounds[1]),
+                    filter_lower=float(bf.overlap_bounds[0]), filter_upper=float(bf.overlap_bounds[1]), filter_min_area=float(bf.min_area))
+
+    def _augment_batch_device(self, images, labels, params, mt):
+        """The four launches behind `_device_params`: decisions (`ssdhip_const_augment_decide[_stream]`: mt (B, 625) = one generator
+        state per image, (625,) = one for the batch), the photometric programs read from the device, the warp launch's tables
+        (`ssdhip_const_augment_plans`) and the warp; ONE download at the end.  Returns (batch, labels, generator state(s))."""
+        import torch
+        from .. import _native as nat
+        B, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+        lf = self.labels_format
+        cols = [lf['class_id'], lf['xmin'], lf['ymin'], lf['xmax'], lf['ymax']]
+        arrs = [np.asarray(lab) for lab in labels]
+        lab_in = np.zeros((B, nat.AUG_MAX_BOXES, 5), dtype=np.float64)
+        n_in = np.empty((B,), dtype=np.int32)
+        for i, a in enumerate(arrs):
+            n_in[i] = a.shape[0]
+            if a.shape[0]:
+                lab_in[i, :a.shape[0]] = a[:, cols]
+        ops_dev, args_dev, geo_dev, fetch = nat.const_augment_decide(dict(params, img_height=h, img_width=w), mt, lab_in, n_in, images.device)
+        distorted = nat.image_program(images.contiguous(), ops_dev, args_dev, torch.uint8)         # both sequences end in 'to_u8'
+        geo5, xtab, ytab = nat.const_augment_plans(geo_dev, h, w)
+        row = tuple(int(v) for v in iop.border_value(self.random_translate.background, 3))
+        bg = self.__dict__.get("_bg_rows")
+        if bg is None or bg[0] != (B, str(images.device), row):
+            bg = ((B, str(images.device), row), nat.to_device(np.repeat(np.array(row, dtype=np.uint8)[None], B, 0), device=images.device))
+            self.__dict__["_bg_rows"] = bg
+        out = nat.image_warp_affine_u8(distorted, h, w, geo5, xtab, ytab, bg[1])
+        _, lab_out, n_out, mt_out = fetch()
+        inv, dt = np.argsort(cols), arrs[0].dtype
+        return out, [np.ascontiguousarray(lab_out[i, :int(n_out[i])][:, inv]).astype(dt) for i in range(B)], mt_out
+
+    def augment_batch(self, images, labels, seeds=None):
         """The chain on a device-resident batch: images (B, H, W, 3) CUDA uint8, labels a list of B label arrays -> ((B, H, W, 3) CUDA
-        uint8 batch, list of B label arrays).  Every random draw is made on the host in the order a loop of `__call__` over the batch
-        makes it (np.random ends where that loop leaves it); the pixels take TWO launches -- the photometric programs
-        (`ssdhip_image_program`) and translation + zoom + flip of the whole batch (`ssdhip_image_warp_affine_u8`)."""
+        uint8 batch, list of B label arrays).  The pixels take TWO launches -- the photometric programs (`ssdhip_image_program`) and
+        translation + zoom + flip of the whole batch (`ssdhip_image_warp_affine_u8`).
+
+        `seeds=None`: every random draw is the one a loop of `__call__` over the batch makes on the global np.random stream, and
+        np.random ends where that loop leaves it.  The draws, the validation of every trial and the label arithmetic run on the device
+        (`ssdhip_const_augment_decide_stream`: one wave walks the batch on np.random's MT19937 state, which is put back afterwards);
+        `SSDHIP_AUG_HOST_STREAM=1`, or a configuration `_device_params` does not cover, takes the host loop below instead -- same
+        results.
+
+        `seeds=[s_0, ...]`: image i comes out exactly as `np.random.seed(s_i); chain(image_i, labels_i)` gives it, every image on its own
+        stream (`ssdhip_const_augment_decide`: one wave per image), the global generator untouched; `_last_generator_states` (B, 625)
+        holds the state behind each image.  What `_device_params` does not cover runs the per-image code under each seed."""
+        import os
         import torch
         if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3):
             raise TypeError("augment_batch takes a (B, H, W, 3) CUDA uint8 batch")
         if len(labels) != images.shape[0]:
             raise ValueError("one label array per image")
+        if seeds is not None and len(seeds) != images.shape[0]:
+            raise ValueError("one seed per image")
         self._sync_formats()
         h, w = int(images.shape[1]), int(images.shape[2])
+        B = int(images.shape[0])
+        if seeds is not None:
+            params = self._device_params(labels) if B else None
+            if params is not None:
+                out, out_labels, mt_out = self._augment_batch_device(images, labels, params, _seed_states(seeds))
+                self.__dict__["_last_generator_states"] = mt_out
+                return out, out_labels
+            saved = np.random.get_state()
+            try:
+                programs, lazies, out_labels, states = [], [], [], np.empty((B, 625), dtype=np.uint32)
+                for i, (lab, seed) in enumerate(zip(labels, seeds)):
+                    np.random.seed(int(seed))
+                    _, steps, geometric = self._draw()
+                    img = iop.WarpImage.of(h, w)
+                    for transform in geometric:
+                        img, lab = transform(img, lab)
+                    programs.append(steps)
+                    lazies.append(img)
+                    out_labels.append(lab)
+                    st = np.random.get_state()
+                    states[i, :624], states[i, 624] = st[1], st[2]
+            finally:
+                np.random.set_state(saved)
+            self.__dict__["_last_generator_states"] = states
+            return iop.warp_batch(iop.run_batch(images, programs), lazies), out_labels
+        if os.environ.get("SSDHIP_AUG_HOST_STREAM", "0") != "1" and B:
+            state = np.random.get_state()
+            params = self._device_params(labels, generator=state[0])
+            if params is not None:
+                mt = np.empty((625,), dtype=np.uint32)
+                mt[:624], mt[624] = state[1], state[2]
+                out, out_labels, mt_out = self._augment_batch_device(images, labels, params, mt)
+                np.random.set_state((state[0], mt_out[:624], int(mt_out[624]), state[3], state[4]))   # the stream goes on behind the batch
+                return out, out_labels
         programs, lazies, out_labels = [], [], []
         for lab in labels:
             _, steps, geometric = self._draw()
