@@ -1118,6 +1118,59 @@ int ssdhip_const_augment_decide_stream(const ssdhip_const_augment_params* params
  * `post`; xtab [B][W][2], ytab [B][H][2] int32, the identity's for an image that is not zoomed. */
 int ssdhip_const_augment_plans(const double* geometry_dev, int B, int H, int W, int* geo_dev, int* xtab_dev, int* ytab_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The decisions of the variable-input-size chain (DataAugmentationVariableInputSize, the chain for a dataset of images of different
+ * sizes; data_generator/data_augmentation_chain_variable_input_size.py:29-152) for a whole batch in ONE launch.  Per image, on NumPy's
+ * MT19937 stream in the order of the chain's one list of transforms: the photometric draws (brightness, contrast, saturation, hue; no
+ * sequence draw, no channel swap) become the image's program for ssdhip_image_program; RandomPatch
+ * (object_detection_2d_patch_sampling_ops.py:423-581: the firing draw, then up to max(1, n_trials) patches of PatchCoordinateGenerator
+ * :24-178 with must_match 'w_ar' -- width scale, aspect ratio, top, left -- the first one the ImageValidator accepts is cut by CropPad
+ * :180-339: shift, BoxFilter, clip; none accepted: image and labels unaltered); RandomFlip
+ * (object_detection_2d_geometric_ops.py:202-262); Resize's label arithmetic :27-84 with a (degenerate, min_area) BoxFilter.  Validator and patch filter share one overlap criterion (border_pixels 'half',
+ * restated from ssdhip_box_filter); n_boxes_min 0 stands for 'all' (an image without boxes then validates, with a count it never does).
+ *   ssdhip_var_augment_decide                one wave per image, image b on its own state: mt_state / mt_state_out [B][625]; table_dev
+ *                                            NULL: every image is params->img_height x img_width, else image b's size is its table entry
+ *                                            ([B][4] int64 as ssdhip_image_resize_gather_ragged_u8's) and the two fields are not read;
+ *   ssdhip_var_augment_decide_stream         one wave walks the batch in order on ONE state: mt_state / mt_state_out [625], one size;
+ *   ssdhip_var_augment_decide_stream_ragged  the same walk, image b's size from table_dev.
+ *   labels [B][64][5] float64 rows (class_id, xmin, ymin, xmax, ymax), n_labels [B] (device), n_boxes_max: the largest of them as the
+ *   host counted it, <= 64; labels_out / n_labels_out likewise; programs_ops [B][16] int32, programs_args [B][16] float64;
+ *   geometry [B][12] int32 as ssdhip_ssd_augment_decide's: the patch is the FIRST window (it may cut the image on either axis as well
+ *   as pad it), no second window, [8], [9] = the size in front of the resize, [10] = flipped?, [11] = params->interpolation -- what
+ *   ssdhip_augment_plans and ssdhip_augment_plans_ragged need.
+ * SSDHIP_E_BADARG, with nothing launched, for a null pointer, B <= 0, n_boxes_max outside [0, 64], a size <= 0, a probability outside
+ * [0, 1], an empty range (max < min), a scale or aspect ratio <= 0, n_trials < 0, n_boxes_min < 0, an unknown criterion or
+ * interpolation code.  The exports only enqueue: no allocation, no host synchronisation. */
+#define SSDHIP_VAR_AUG_CENTER_POINT 0
+#define SSDHIP_VAR_AUG_IOU 1
+#define SSDHIP_VAR_AUG_AREA 2
+typedef struct ssdhip_var_augment_params {
+    int img_height, img_width;                       /* size of the batch's images (the forms without a table) */
+    double photo_prob[4], photo_lower[4], photo_upper[4];   /* RandomBrightness, RandomContrast, RandomSaturation, RandomHue */
+    double patch_prob;                               /* RandomPatch */
+    double min_scale, max_scale, min_aspect_ratio, max_aspect_ratio;   /* PatchCoordinateGenerator */
+    int n_trials;                                    /* RandomPatch's n_trials_max (0 counts as 1) */
+    int clip_boxes;
+    int criterion;                                   /* SSDHIP_VAR_AUG_*: ImageValidator's and the patch BoxFilter's overlap criterion */
+    int n_boxes_min;                                 /* ImageValidator: a count >= 1, or 0 = 'all' */
+    double validator_lower, validator_upper;         /* ImageValidator's bounds */
+    double filter_lower, filter_upper;               /* the patch BoxFilter's overlap bounds */
+    double flip_prob;
+    int out_height, out_width, interpolation;        /* Resize; interpolation 0 .. 4 as cv2's INTER_* */
+    double resize_min_area;                          /* the resize BoxFilter's min_area */
+} ssdhip_var_augment_params;
+int ssdhip_var_augment_decide(const ssdhip_var_augment_params* params, int B, int n_boxes_max, const long long* table_dev,
+                              const unsigned int* mt_state, const double* labels, const int* n_labels, int* programs_ops,
+                              double* programs_args, int* geometry, double* labels_out, int* n_labels_out, unsigned int* mt_state_out,
+                              void* stream);
+int ssdhip_var_augment_decide_stream(const ssdhip_var_augment_params* params, int B, int n_boxes_max, const unsigned int* mt_state,
+                                     const double* labels, const int* n_labels, int* programs_ops, double* programs_args, int* geometry,
+                                     double* labels_out, int* n_labels_out, unsigned int* mt_state_out, void* stream);
+int ssdhip_var_augment_decide_stream_ragged(const ssdhip_var_augment_params* params, int B, int n_boxes_max, const long long* table_dev,
+                                            const unsigned int* mt_state, const double* labels, const int* n_labels, int* programs_ops,
+                                            double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
+                                            unsigned int* mt_state_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,20 @@ class _ConstAugParams(ctypes.Structure):             # struct ssdhip_const_augme
                 ("filter_lower", ctypes.c_double), ("filter_upper", ctypes.c_double), ("filter_min_area", ctypes.c_double)]
 
 
+class _VarAugParams(ctypes.Structure):               # struct ssdhip_var_augment_params (include/ssdhip.h)
+    _fields_ = [("img_height", ctypes.c_int), ("img_width", ctypes.c_int),
+                ("photo_prob", ctypes.c_double * 4), ("photo_lower", ctypes.c_double * 4), ("photo_upper", ctypes.c_double * 4),
+                ("patch_prob", ctypes.c_double),
+                ("min_scale", ctypes.c_double), ("max_scale", ctypes.c_double),
+                ("min_aspect_ratio", ctypes.c_double), ("max_aspect_ratio", ctypes.c_double),
+                ("n_trials", ctypes.c_int), ("clip_boxes", ctypes.c_int), ("criterion", ctypes.c_int), ("n_boxes_min", ctypes.c_int),
+                ("validator_lower", ctypes.c_double), ("validator_upper", ctypes.c_double),
+                ("filter_lower", ctypes.c_double), ("filter_upper", ctypes.c_double),
+                ("flip_prob", ctypes.c_double),
+                ("out_height", ctypes.c_int), ("out_width", ctypes.c_int), ("interpolation", ctypes.c_int),
+                ("resize_min_area", ctypes.c_double)]
+
+
 # The C ABI of include/ssdhip.h, one entry per export in the header's order: name -> (restype, argtypes).  load() applies it;
 # tests/test_host_cpu.py checks it against the header's prototypes.
 _I, _LL, _SZ, _D, _F, _P = ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_double, ctypes.c_float, ctypes.c_void_p
@@ -215,6 +229,9 @@ SIGNATURES = {
     "ssdhip_const_augment_decide": (_I, [ctypes.POINTER(_ConstAugParams), _I] + [_P] * 10),
     "ssdhip_const_augment_decide_stream": (_I, [ctypes.POINTER(_ConstAugParams), _I] + [_P] * 10),
     "ssdhip_const_augment_plans": (_I, [_P] + [_I] * 3 + [_P] * 4),
+    "ssdhip_var_augment_decide": (_I, [ctypes.POINTER(_VarAugParams), _I, _I] + [_P] * 11),
+    "ssdhip_var_augment_decide_stream": (_I, [ctypes.POINTER(_VarAugParams), _I, _I] + [_P] * 10),
+    "ssdhip_var_augment_decide_stream_ragged": (_I, [ctypes.POINTER(_VarAugParams), _I, _I] + [_P] * 11),
 }
 
 
@@ -2700,3 +2717,70 @@ def const_augment_plans(geo_dev, H, W):
     ytab = torch.empty((B, int(H), 2), dtype=torch.int32, device=dev)
     launch("ssdhip_const_augment_plans", dev, _ptr(geo_dev), B, int(H), int(W), _ptr(geo), _ptr(xtab), _ptr(ytab))
     return geo, xtab, ytab
+
+
+# ---- the decisions of the variable-input-size chain for a whole batch (csrc/ssdhip_augment.hip) --------------------------------------
+VAR_AUG_CRITERION = {"center_point": 0, "iou": 1, "area": 2}      # SSDHIP_VAR_AUG_*
+
+
+def var_augment_decide(params, mt_states, labels, n_labels, device, table=None):
+    """`ssdhip_var_augment_decide` (mt_states (B, 625): image b on its own MT19937 state; `table` optional) or
+    `ssdhip_var_augment_decide_stream` / `ssdhip_var_augment_decide_stream_ragged` (mt_states (625,): the batch in order on one state;
+    without / with `table`).  params: a dict of the fields of ssdhip_var_augment_params (img_height / img_width only without a table);
+    table: the ragged batch's (B, 4) int64 CUDA tensor (pack_ragged's: byte offset, H, W, C); labels (B, 64, 5) float64, n_labels (B,)
+    int32 NumPy arrays (ONE upload).  Returns (ops (B, 16) int32 and args (B, 16) float64 CUDA tensors = the programs of image_program,
+    geometry (B, 12) int32 CUDA tensor for augment_plans[_ragged], fetch) where fetch() downloads (geometry (B, 12), labels_out
+    (B, 64, 5), n_out (B,), mt_states_out (B, 625) | (625,)) as NumPy arrays."""
+    torch = _torch()
+    q = _VarAugParams()
+    for k, v in params.items():
+        if isinstance(v, (list, tuple)):
+            arr = getattr(q, k)
+            for i, e in enumerate(v):
+                arr[i] = e
+        else:
+            setattr(q, k, v)
+    B = int(labels.shape[0])
+    stream_mode = mt_states.ndim == 1
+    if mt_states.shape != ((625,) if stream_mode else (B, 625)) or labels.shape != (B, AUG_MAX_BOXES, 5) or n_labels.shape != (B,):
+        raise SsdHipError("var_augment_decide: mt_states (B, 625) or (625,), labels (B, 64, 5), n_labels (B,)")
+    if table is not None:
+        require_cuda(table, "table")
+        if tuple(table.shape) != (B, 4) or table.dtype != torch.int64:
+            raise SsdHipError("var_augment_decide: table (B, 4) int64")
+    # one packed upload: [labels f64 | mt u32 (padded to 8 bytes) | n i32];
+    # one packed download: [labels_out f64 | args f64 | mt_out u32 (padded) | geometry i32 | ops i32 | n_out i32]
+    n_mt = mt_states.size * 4
+    nl, nm = B * AUG_MAX_BOXES * 5 * 8, (n_mt + 7) // 8 * 8
+    host = np.zeros((nl + nm + B * 4,), dtype=np.uint8)
+    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
+    host[nl:nl + n_mt] = np.ascontiguousarray(mt_states, dtype=np.uint32).view(np.uint8).ravel()
+    host[nl + nm:] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
+    dev_in = torch.from_numpy(host).to(device)
+    na, ng = B * IMG_PROG * 8, B * 12 * 4
+    o_args, o_mt = nl, nl + na
+    o_geo = o_mt + nm
+    o_ops = o_geo + ng
+    o_n = o_ops + B * IMG_PROG * 4
+    dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
+    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
+    vp = ctypes.c_void_p
+    ptrs = (vp(base_in + nl), vp(base_in), vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args), vp(base_out + o_geo),
+            vp(base_out), vp(base_out + o_n), vp(base_out + o_mt))
+    n_max = int(n_labels.max()) if B else 0
+    if not stream_mode:
+        launch("ssdhip_var_augment_decide", device, ctypes.byref(q), B, n_max, _ptr(table) if table is not None else None, *ptrs)
+    elif table is None:
+        launch("ssdhip_var_augment_decide_stream", device, ctypes.byref(q), B, n_max, *ptrs)
+    else:
+        launch("ssdhip_var_augment_decide_stream_ragged", device, ctypes.byref(q), B, n_max, _ptr(table), *ptrs)
+    ops_dev = dev_out[o_ops:o_ops + B * IMG_PROG * 4].view(torch.int32).view(B, IMG_PROG)
+    args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG)
+    geo_dev = dev_out[o_geo:o_geo + ng].view(torch.int32).view(B, 12)
+
+    def fetch():
+        """(geometry, labels_out, n_out, mt_states_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
+        out = dev_out.cpu().numpy()
+        return (out[o_geo:o_geo + ng].view(np.int32).reshape(B, 12), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
+                out[o_n:].view(np.int32), out[o_mt:o_mt + n_mt].view(np.uint32).reshape(mt_states.shape).copy())
+    return ops_dev, args_dev, geo_dev, fetch

@@ -254,10 +254,11 @@ enum { OP_END = 0, OP_TO_F32 = 1, OP_TO_U8 = 2, OP_BRIGHTNESS = 3, OP_CONTRAST =
 // DataAugmentationConstantInputSize._draw): `if np.random.choice(2)` picks the sequence, every random op -- brightness, contrast,
 // saturation, hue = entries 0 .. 3 of prob / lo / hi -- draws uniform(0, 1) and, when it fires (>= 1 - prob), its parameter
 // uniform(lo, hi).  swap_draw: a RandomChannelSwap(prob = 0.0) ends the sequence -- its uniform(0, 1) >= 1.0 never holds, the draw is
-// consumed.  Returns whether sequence 1 (contrast before the HSV part) was drawn.
+// consumed.  choose_sequence = false: a chain with ONE fixed list of transforms (DataAugmentationVariableInputSize) -- no
+// `np.random.choice(2)` draw, the order is sequence 1's.  Returns whether sequence 1 (contrast before the HSV part) runs.
 __device__ __forceinline__ bool aug_photo_program(Mt& s, const int lane, const double* prob, const double* lo, const double* hi,
-                                                  const bool swap_draw, const int b, int* __restrict__ prog_ops,
-                                                  double* __restrict__ prog_args) {
+                                                  const bool choose_sequence, const bool swap_draw, const int b,
+                                                  int* __restrict__ prog_ops, double* __restrict__ prog_args) {
     int ops[AUG_PROG];
     double args[AUG_PROG];
     int k = 0;
@@ -265,7 +266,7 @@ __device__ __forceinline__ bool aug_photo_program(Mt& s, const int lane, const d
     auto maybe = [&](int which, int op) {                // RandomX.draw(): the firing draw, then uniform(lower, upper)
         if (mt_uniform(s, lane, 0.0, 1.0) >= (1.0 - prob[which])) push(op, mt_uniform(s, lane, lo[which], hi[which]));
     };
-    const bool contrast_first = mt_randint(s, lane, 0, 2) != 0;
+    const bool contrast_first = choose_sequence ? mt_randint(s, lane, 0, 2) != 0 : true;
     push(OP_TO_F32, 0.0);
     maybe(0, OP_BRIGHTNESS);
     if (contrast_first) maybe(1, OP_CONTRAST);
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(64) void ssd_augment_stream_kernel(AugParams p, Aug
     __syncthreads();
     for (int b = 0; b < B; ++b) {
         // ---- SSDPhotometricDistortions.__call__; RandomChannelSwap(prob 0) draws and never fires ---------------------------------------
-        (void)aug_photo_program(s, lane, ph.prob, ph.lo, ph.hi, true, b, prog_ops, prog_args);
+        (void)aug_photo_program(s, lane, ph.prob, ph.lo, ph.hi, true, true, b, prog_ops, prog_args);
         // ---- the geometric half on the same stream ------------------------------------------------------------------------------------
         aug_decide_image(p, s, lane, b, hw.h(b), hw.w(b), lab_in, n_in, geo, lab_out, n_out);
     }
@@ -574,7 +575,7 @@ __device__ __forceinline__ void caug_decide_image(const ConstAugParams& p, Mt& s
                                                   int* __restrict__ prog_ops, double* __restrict__ prog_args, double* __restrict__ geo,
                                                   double* __restrict__ lab_out, int* __restrict__ n_out) {
     // ---- _draw: the sequence choice and the photometric draws in that sequence's order (this chain has no channel swap) ---------------
-    const bool seq1 = aug_photo_program(s, lane, p.ph_prob, p.ph_lo, p.ph_hi, false, b, prog_ops, prog_args);
+    const bool seq1 = aug_photo_program(s, lane, p.ph_prob, p.ph_lo, p.ph_hi, true, false, b, prog_ops, prog_args);
 
     // ---- the geometric ops on the same stream: translate, zoom in, flip | zoom out, translate, flip -----------------------------------
     const int n = n_in[b];
@@ -672,6 +673,143 @@ __global__ __launch_bounds__(128) void const_plan_kernel(const double* __restric
         o[0] = (int)(__builtin_rint((m[1] * v + m[2]) * 1024.0) + 16.0);
         o[1] = (int)(__builtin_rint((m[4] * v + m[5]) * 1024.0) + 16.0);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// DataAugmentationVariableInputSize (data_generator/data_augmentation_chain_variable_input_size.py), the chain for a dataset of images of
+// different sizes: ONE list of transforms -- the photometric ops in sequence 1's order (no sequence draw, no channel swap), then
+// RandomPatch(prob, can_fail = False) over PatchCoordinateGenerator(must_match = 'w_ar') with ONE overlap criterion ('area' | 'iou' |
+// 'center_point') behind both its ImageValidator and its BoxFilter, RandomFlip('horizontal') and Resize with a (min_area, degenerate) box
+// filter.  The host ran a validator launch + download per patch search and a box-filter launch + download per cut and per resize; here a
+// wave does it on the image's MT19937 stream, lane = ground truth box.  The patch goes into the FIRST window slot of the 12-int geometry
+// record aug_plan_kernel reads: unlike SSDExpand's canvas it may CUT the image on either axis, which that kernel's `j + top / left outside
+// [0, H) / [0, W) -> -1` covers as it stands.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+struct VarAugParams {
+    double ph_prob[4], ph_lo[4], ph_hi[4];                // RandomBrightness, RandomContrast, RandomSaturation, RandomHue
+    double patch_prob, scale_lo, scale_hi, ar_lo, ar_hi;  // RandomPatch(prob); PatchCoordinateGenerator: scales of the width, aspect ratios
+    int n_trials, clip;                                   // max(1, n_trials_max), clip_boxes
+    int criterion, n_min;                                 // SSDHIP_VAR_AUG_*; ImageValidator's n_boxes_min, 0 = 'all'
+    double val_lo, val_hi, flt_lo, flt_hi;                // ImageValidator's bounds, the patch BoxFilter's overlap bounds
+    double flip_prob;
+    int out_h, out_w, interp;                             // Resize
+    double min_area;                                      // the resize BoxFilter's min_area (degenerate boxes dropped too)
+};
+
+// BoxFilter's overlap test (border_pixels 'half') of a box against an H x W image, as box_filter_kernel (csrc/ssdhip_boxes.hip) has it
+__device__ __forceinline__ bool vaug_overlap_ok(const int criterion, double x0, double y0, double x1, double y1, double H, double W,
+                                                double lower, double upper) {
+    if (criterion == SSDHIP_VAR_AUG_IOU) {
+        PxBox<double> im, bb;
+        im.x0 = 0.0; im.y0 = 0.0; im.x1 = W; im.y1 = H;
+        im.area = box_area<double>(im.x0, im.y0, im.x1, im.y1, 0.0);
+        bb.x0 = x0; bb.y0 = y0; bb.x1 = x1; bb.y1 = y1;
+        bb.area = box_area<double>(x0, y0, x1, y1, 0.0);
+        const double v = iou_px<double>(im, bb);
+        return v > lower && v <= upper;
+    }
+    if (criterion == SSDHIP_VAR_AUG_AREA) return caug_area_ok(x0, y0, x1, y1, H, W, lower, upper);
+    const double cy = (y0 + y1) / 2.0, cx = (x0 + x1) / 2.0;
+    return cy >= 0.0 && cy <= H - 1.0 && cx >= 0.0 && cx <= W - 1.0;
+}
+
+// ONE image of the chain by one wave on the generator state `s`; (H0, W0): the image's size.
+__device__ __forceinline__ void vaug_decide_image(const VarAugParams& p, Mt& s, const int lane, const int b, const int H0, const int W0,
+                                                  const double* __restrict__ lab_in, const int* __restrict__ n_in,
+                                                  int* __restrict__ prog_ops, double* __restrict__ prog_args, int* __restrict__ geo,
+                                                  double* __restrict__ lab_out, int* __restrict__ n_out) {
+    (void)aug_photo_program(s, lane, p.ph_prob, p.ph_lo, p.ph_hi, false, false, b, prog_ops, prog_args);
+
+    int n = n_in[b];
+    n = n < 0 ? 0 : (n > AUG_MAXG ? AUG_MAXG : n);
+    bool alive = lane < n;
+    double cls = 0.0, x0 = 0.0, y0 = 0.0, x1 = 0.0, y1 = 0.0;
+    if (alive) {
+        const double* r = lab_in + ((size_t)b * AUG_MAXG + lane) * 5;
+        cls = r[0]; x0 = r[1]; y0 = r[2]; x1 = r[3]; y1 = r[4];
+    }
+    int H = H0, W = W0;
+    int g[12] = {0, 0, 0, H, W, 0, 0, 0, H, W, 0, p.interp};
+
+    // ---- RandomPatch: the firing draw, then up to n_trials patches; the first one the validator accepts is cut (CropPad) ---------------
+    if (!(mt_uniform(s, lane, 0.0, 1.0) < (1.0 - p.patch_prob))) {
+        for (int t = 0; t < p.n_trials; ++t) {
+            const int w = (int)(mt_uniform(s, lane, p.scale_lo, p.scale_hi) * (double)W);
+            const double ar = mt_uniform(s, lane, p.ar_lo, p.ar_hi);
+            const int h = (int)((double)w / ar);
+            const int top = aug_position(s, lane, H, h), left = aug_position(s, lane, W, w);
+            const double sx0 = x0 - (double)left, sy0 = y0 - (double)top, sx1 = x1 - (double)left, sy1 = y1 - (double)top;
+            const bool ok = alive && vaug_overlap_ok(p.criterion, sx0, sy0, sx1, sy1, (double)h, (double)w, p.val_lo, p.val_hi);
+            const int n_ok = __popcll(__ballot(ok));
+            if (p.n_min > 0 ? n_ok < p.n_min : n_ok != n) continue;
+            x0 = sx0; y0 = sy0; x1 = sx1; y1 = sy1;
+            alive = alive && vaug_overlap_ok(p.criterion, x0, y0, x1, y1, (double)h, (double)w, p.flt_lo, p.flt_hi);
+            if (p.clip) {
+                const double ymax = (double)h - 1.0, xmax = (double)w - 1.0;
+                y0 = np_minimum<double>(np_maximum<double>(y0, 0.0), ymax); y1 = np_minimum<double>(np_maximum<double>(y1, 0.0), ymax);
+                x0 = np_minimum<double>(np_maximum<double>(x0, 0.0), xmax); x1 = np_minimum<double>(np_maximum<double>(x1, 0.0), xmax);
+            }
+            g[0] = 1; g[1] = top; g[2] = left; g[3] = h; g[4] = w;
+            H = h; W = w;
+            break;
+        }
+    }
+    g[8] = H; g[9] = W;
+
+    // ---- RandomFlip('horizontal', prob) ----------------------------------------------------------------------------------------------
+    if (!(mt_uniform(s, lane, 0.0, 1.0) < (1.0 - p.flip_prob))) {
+        const double nx0 = (double)W - x1, nx1 = (double)W - x0;
+        x0 = nx0; x1 = nx1;
+        g[10] = 1;
+    }
+
+    // ---- Resize: no draw; np.round(coordinate * (out / size)), then the (degenerate, min_area) box filter --------------------------------
+    {
+        const double sy = (double)p.out_h / (double)H, sx = (double)p.out_w / (double)W;
+        y0 = __builtin_rint(y0 * sy); y1 = __builtin_rint(y1 * sy);
+        x0 = __builtin_rint(x0 * sx); x1 = __builtin_rint(x1 * sx);
+        alive = alive && x1 > x0 && y1 > y0 && ((x1 - x0) * (y1 - y0) >= p.min_area);
+    }
+
+    const u64 keep = __ballot(alive);
+    if (alive) {
+        const int pos = __popcll(keep & lanemask_lt());
+        double* r = lab_out + ((size_t)b * AUG_MAXG + pos) * 5;
+        r[0] = cls; r[1] = x0; r[2] = y0; r[3] = x1; r[4] = y1;
+    }
+    if (lane == 0) {
+        n_out[b] = __popcll(keep);
+        for (int i = 0; i < 12; ++i) geo[(size_t)b * 12 + i] = g[i];
+    }
+}
+
+// STREAM = false: one wave per image, image b on its own state (mt [B][625]); true: one wave walks the B images in order on one state.
+// HW: the images' one size, or each image's own from the ragged table.
+template <bool STREAM, class HW>
+__global__ __launch_bounds__(64) void var_augment_decide_kernel(VarAugParams p, HW hw, int B, const u32* __restrict__ mt_in,
+                                                                const double* __restrict__ lab_in, const int* __restrict__ n_in,
+                                                                int* __restrict__ prog_ops, double* __restrict__ prog_args,
+                                                                int* __restrict__ geo, double* __restrict__ lab_out,
+                                                                int* __restrict__ n_out, u32* __restrict__ mt_out) {
+    __shared__ u32 key[624];
+    const int lane = (int)threadIdx.x;
+    const size_t at = STREAM ? 0 : (size_t)blockIdx.x * 625;
+    for (int i = lane; i < 624; i += 64) key[i] = mt_in[at + i];
+    Mt s;
+    s.key = key;
+    s.pos = (int)mt_in[at + 624];
+    s.base = -1; s.win = 0u;
+    __syncthreads();
+    if (STREAM) {
+        for (int b = 0; b < B; ++b)
+            vaug_decide_image(p, s, lane, b, hw.h(b), hw.w(b), lab_in, n_in, prog_ops, prog_args, geo, lab_out, n_out);
+    } else {
+        const int b = (int)blockIdx.x;
+        vaug_decide_image(p, s, lane, b, hw.h(b), hw.w(b), lab_in, n_in, prog_ops, prog_args, geo, lab_out, n_out);
+    }
+    if (lane == 0) mt_out[at + 624] = (u32)s.pos;
+    __syncthreads();
+    for (int i = lane; i < 624; i += 64) mt_out[at + i] = key[i];
 }
 
 }  // namespace ssdhip
@@ -855,4 +993,79 @@ extern "C" int ssdhip_const_augment_plans(const double* geometry_dev, int B, int
     hipLaunchKernelGGL(const_plan_kernel, dim3((unsigned)((n + 127) / 128), 2, (unsigned)B), dim3(128), 0, stream, geometry_dev, H, W,
                        geo_dev, xtab_dev, ytab_dev);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// ---- DataAugmentationVariableInputSize: the decisions of a batch (seeded: B states; stream: one), uniform or ragged sizes ----------------
+static int var_params_from(const ssdhip_var_augment_params* q, bool ragged, int n_boxes_max, VarAugParams& p) {
+    const auto prob = [](double v) { return v >= 0.0 && v <= 1.0; };
+    if (!ragged && (q->img_height <= 0 || q->img_width <= 0)) return SSDHIP_E_BADARG;
+    if (n_boxes_max < 0 || n_boxes_max > AUG_MAXG) return SSDHIP_E_BADARG;
+    for (int i = 0; i < 4; ++i)
+        if (!prob(q->photo_prob[i]) || !(q->photo_upper[i] >= q->photo_lower[i])) return SSDHIP_E_BADARG;
+    if (!prob(q->patch_prob) || !prob(q->flip_prob)) return SSDHIP_E_BADARG;
+    if (!(q->min_scale > 0.0) || !(q->max_scale >= q->min_scale) || !(q->min_aspect_ratio > 0.0) ||
+        !(q->max_aspect_ratio >= q->min_aspect_ratio))
+        return SSDHIP_E_BADARG;
+    if (q->n_trials < 0 || q->n_boxes_min < 0) return SSDHIP_E_BADARG;
+    if (q->criterion != SSDHIP_VAR_AUG_CENTER_POINT && q->criterion != SSDHIP_VAR_AUG_IOU && q->criterion != SSDHIP_VAR_AUG_AREA)
+        return SSDHIP_E_BADARG;
+    if (!(q->validator_upper >= q->validator_lower) || !(q->filter_upper >= q->filter_lower) || !(q->resize_min_area == q->resize_min_area))
+        return SSDHIP_E_BADARG;
+    if (q->out_height <= 0 || q->out_width <= 0 || q->interpolation < 0 || q->interpolation > 4) return SSDHIP_E_BADARG;
+    for (int i = 0; i < 4; ++i) { p.ph_prob[i] = q->photo_prob[i]; p.ph_lo[i] = q->photo_lower[i]; p.ph_hi[i] = q->photo_upper[i]; }
+    p.patch_prob = q->patch_prob; p.scale_lo = q->min_scale; p.scale_hi = q->max_scale;
+    p.ar_lo = q->min_aspect_ratio; p.ar_hi = q->max_aspect_ratio;
+    p.n_trials = q->n_trials > 1 ? q->n_trials : 1;                          // max(1, n_trials_max)
+    p.clip = q->clip_boxes != 0; p.criterion = q->criterion; p.n_min = q->n_boxes_min;
+    p.val_lo = q->validator_lower; p.val_hi = q->validator_upper; p.flt_lo = q->filter_lower; p.flt_hi = q->filter_upper;
+    p.flip_prob = q->flip_prob;
+    p.out_h = q->out_height; p.out_w = q->out_width; p.interp = q->interpolation; p.min_area = q->resize_min_area;
+    return SSDHIP_OK;
+}
+
+template <bool STREAM>
+static int var_decide(const ssdhip_var_augment_params* q, int B, int n_boxes_max, const long long* table_dev, const unsigned int* mt_state,
+                      const double* labels, const int* n_labels, int* programs_ops, double* programs_args, int* geometry,
+                      double* labels_out, int* n_labels_out, unsigned int* mt_state_out, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!q || B <= 0 || !mt_state || !labels || !n_labels || !programs_ops || !programs_args || !geometry || !labels_out || !n_labels_out ||
+        !mt_state_out)
+        return SSDHIP_E_BADARG;
+    VarAugParams p;
+    const int rc = var_params_from(q, table_dev != nullptr, n_boxes_max, p);
+    if (rc != SSDHIP_OK) return rc;
+    const dim3 grid(STREAM ? 1u : (unsigned)B);
+    if (table_dev)
+        hipLaunchKernelGGL((var_augment_decide_kernel<STREAM, RaggedHW>), grid, dim3(64), 0, stream, p, RaggedHW{table_dev}, B, mt_state,
+                           labels, n_labels, programs_ops, programs_args, geometry, labels_out, n_labels_out, mt_state_out);
+    else
+        hipLaunchKernelGGL((var_augment_decide_kernel<STREAM, UniformHW>), grid, dim3(64), 0, stream, p,
+                           UniformHW{q->img_height, q->img_width}, B, mt_state, labels, n_labels, programs_ops, programs_args, geometry,
+                           labels_out, n_labels_out, mt_state_out);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_var_augment_decide(const ssdhip_var_augment_params* params, int B, int n_boxes_max, const long long* table_dev,
+                                         const unsigned int* mt_state, const double* labels, const int* n_labels, int* programs_ops,
+                                         double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
+                                         unsigned int* mt_state_out, void* stream) {
+    return var_decide<false>(params, B, n_boxes_max, table_dev, mt_state, labels, n_labels, programs_ops, programs_args, geometry,
+                             labels_out, n_labels_out, mt_state_out, stream);
+}
+
+extern "C" int ssdhip_var_augment_decide_stream(const ssdhip_var_augment_params* params, int B, int n_boxes_max,
+                                                const unsigned int* mt_state, const double* labels, const int* n_labels, int* programs_ops,
+                                                double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
+                                                unsigned int* mt_state_out, void* stream) {
+    return var_decide<true>(params, B, n_boxes_max, nullptr, mt_state, labels, n_labels, programs_ops, programs_args, geometry, labels_out,
+                            n_labels_out, mt_state_out, stream);
+}
+
+extern "C" int ssdhip_var_augment_decide_stream_ragged(const ssdhip_var_augment_params* params, int B, int n_boxes_max,
+                                                       const long long* table_dev, const unsigned int* mt_state, const double* labels,
+                                                       const int* n_labels, int* programs_ops, double* programs_args, int* geometry,
+                                                       double* labels_out, int* n_labels_out, unsigned int* mt_state_out, void* stream) {
+    if (!table_dev) return SSDHIP_E_BADARG;
+    return var_decide<true>(params, B, n_boxes_max, table_dev, mt_state, labels, n_labels, programs_ops, programs_args, geometry, labels_out,
+                            n_labels_out, mt_state_out, stream);
 }

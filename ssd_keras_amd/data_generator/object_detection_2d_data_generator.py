@@ -11,6 +11,8 @@ chains read too).
     inverters are the transforms' own host code on lazy images (`_image_ops.GeoImage`), the pixels of the batch ONE gather launch over the
     ragged batch (`_image_ops.gather_batch_ragged`, 1- and 4-channel images folded to three channels in the read);
   * `[DataAugmentationConstantInputSize]` on images of one size: `DataAugmentationConstantInputSize.augment_batch`;
+  * `[DataAugmentationVariableInputSize]`: like the first item, the images (any sizes) as ONE ragged batch through
+    `DataAugmentationVariableInputSize.augment_batch` on the list (110 ms -> 2.1 ms per batch of 32, profiles/variable_chain_device.json);
   * anything else: the reference's per-image loop over the package's transforms.
 Every path gives the per-image loop's pixels, labels, inverters and final `np.random` state.  Images are decoded by PIL on the host, as in
 the reference.  HDF5 datasets are not supported (h5py is not a dependency of this package); their parameter and methods raise
@@ -335,6 +337,7 @@ class DataGenerator:
         """Which batch path a transformation list takes (see the module docstring); None = the per-image loop."""
         from .data_augmentation_chain_constant_input_size import DataAugmentationConstantInputSize
         from .data_augmentation_chain_original_ssd import SSDDataAugmentation
+        from .data_augmentation_chain_variable_input_size import DataAugmentationVariableInputSize
         from .object_detection_2d_geometric_ops import Resize
         from .object_detection_2d_patch_sampling_ops import RandomPadFixedAR
         from .object_detection_2d_photometric_ops import ConvertTo3Channels
@@ -352,6 +355,8 @@ class DataGenerator:
         if (kinds == [DataAugmentationConstantInputSize] and len({im.shape for im in images}) == 1 and images[0].ndim == 3
                 and images[0].shape[2] == 3):
             return 'constant'
+        if kinds == [DataAugmentationVariableInputSize]:
+            return 'variable'
         return None
 
     def _transform_batch(self, path, transformations, images, labels, want_inverters):
@@ -359,10 +364,11 @@ class DataGenerator:
         uint8 batch, labels or None, inverters per item)."""
         import torch
         from . import _image_ops as iop
-        if path == 'ssd':
-            three = [im if (im.ndim == 3 and im.shape[2] == 3) else transformations[0].photometric_distortions.convert_to_3_channels(im)
-                     for im in images]
-            out, out_labels = transformations[0].augment_batch(three, labels)
+        if path in ('ssd', 'variable'):
+            chain = transformations[0]
+            to_three = (chain.photometric_distortions if path == 'ssd' else chain).convert_to_3_channels
+            three = [im if (im.ndim == 3 and im.shape[2] == 3) else to_three(im) for im in images]
+            out, out_labels = chain.augment_batch(three, labels)
             return out, out_labels, [[] for _ in images]
         if path == 'constant':
             batch = torch.from_numpy(np.stack(images)).to(torch.device('cuda', torch.cuda.current_device()))
