@@ -1171,6 +1171,56 @@ int ssdhip_var_augment_decide_stream_ragged(const ssdhip_var_augment_params* par
                                             double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
                                             unsigned int* mt_state_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The decisions of the satellite chain (DataAugmentationSatellite, the chain for images in bird's eye view;
+ * data_generator/data_augmentation_chain_satellite.py:28-157) for a whole batch in ONE launch: the variable-input-size chain's steps in
+ * this chain's order -- the photometric draws, RandomFlip 'horizontal', RandomFlip 'vertical', RandomRotate
+ * (object_detection_2d_geometric_ops.py:659-772), RandomPatch on the ROTATED image's height and width, Resize.  `var` holds everything the
+ * two chains share (var.flip_prob: the horizontal flip's).  RandomRotate's angle is a draw from Python's `random`, which the device does
+ * not step: turns_dev [B] int32 (device) holds quarter turns 1 .. 3 the host drew in advance; the one-state forms hand the k-th value to
+ * the k-th image that rotates, the form with one state per image hands value b to image b.  Rotate's label arithmetic is the closed
+ * integer form of the reference's adjusted matrix (see csrc/ssdhip_augment.hip): exact for whole-number coordinates only.
+ *   The three forms, their states, tables and outputs are those of the ssdhip_var_augment_decide family, except
+ *   geometry [B][12] int32: [0] patched? [1 .. 4] the patch's top, left, height, width on the rotated image, [5] flipped horizontally?
+ *   [6] vertically? [7] quarter turns 0 .. 3 (how many images rotated = how many rows have [7] != 0), [8], [9] the size in front of the
+ *   resize, [10] 0, [11] var.interpolation -- what the two plan exports below need.
+ * The plan exports build the tap tables of the turn gathers (ssdhip_image_resize_gather_turn_cv_u8 and its ragged form) as
+ * ssdhip_augment_plans does, composed resize <- patch <- rotation <- vertical flip <- horizontal flip, and transposed_dev [B] int32:
+ * 1 = the image's row table addresses source columns and its column table source rows (90 / 270 degrees).  Index -1 = the patch's
+ * background, -2 = the rotation's border (0).  H, W: the size of the batch's images; table_dev: each image's own.
+ * SSDHIP_E_BADARG as for the variable chain's exports, and for a probability of the vertical flip or the rotation outside [0, 1]. */
+typedef struct ssdhip_sat_augment_params {
+    ssdhip_var_augment_params var;
+    double vflip_prob;                               /* RandomFlip('vertical') */
+    double rotate_prob;                              /* RandomRotate */
+} ssdhip_sat_augment_params;
+int ssdhip_sat_augment_decide(const ssdhip_sat_augment_params* params, int B, int n_boxes_max, const long long* table_dev,
+                              const int* turns_dev, const unsigned int* mt_state, const double* labels, const int* n_labels,
+                              int* programs_ops, double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
+                              unsigned int* mt_state_out, void* stream);
+int ssdhip_sat_augment_decide_stream(const ssdhip_sat_augment_params* params, int B, int n_boxes_max, const int* turns_dev,
+                                     const unsigned int* mt_state, const double* labels, const int* n_labels, int* programs_ops,
+                                     double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
+                                     unsigned int* mt_state_out, void* stream);
+int ssdhip_sat_augment_decide_stream_ragged(const ssdhip_sat_augment_params* params, int B, int n_boxes_max, const long long* table_dev,
+                                            const int* turns_dev, const unsigned int* mt_state, const double* labels, const int* n_labels,
+                                            int* programs_ops, double* programs_args, int* geometry, double* labels_out,
+                                            int* n_labels_out, unsigned int* mt_state_out, void* stream);
+int ssdhip_sat_augment_plans(const int* geometry_dev, int B, int H, int W, int out_h, int out_w, int n_taps, int* plan_dev, int* ix_dev,
+                             double* wx_dev, int* iy_dev, double* wy_dev, int* transposed_dev, void* stream);
+int ssdhip_sat_augment_plans_ragged(const int* geometry_dev, const long long* table_dev, int B, int out_h, int out_w, int n_taps,
+                                    int* plan_dev, int* ix_dev, double* wx_dev, int* iy_dev, double* wy_dev, int* transposed_dev,
+                                    void* stream);
+/* ssdhip_image_resize_gather_cv_u8 / ssdhip_image_resize_gather_ragged_u8 for such plans: the same arguments plus transposed_dev [B]
+ * in front of the background; source indices are clamped into the image. */
+int ssdhip_image_resize_gather_turn_cv_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* plan_dev,
+                                          const int* ix_dev, const double* wx_dev, int nx, const int* iy_dev, const double* wy_dev, int ny,
+                                          const int* transposed_dev, const void* background_dev, void* stream);
+int ssdhip_image_resize_gather_turn_ragged_u8(const void* x, const long long* table_dev, void* y, int B, int Ho, int Wo,
+                                              const int* plan_dev, const int* ix_dev, const double* wx_dev, int nx, const int* iy_dev,
+                                              const double* wy_dev, int ny, const int* transposed_dev, const void* background_dev,
+                                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,10 @@ class _VarAugParams(ctypes.Structure):               # struct ssdhip_var_augment
                 ("resize_min_area", ctypes.c_double)]
 
 
+class _SatAugParams(ctypes.Structure):               # struct ssdhip_sat_augment_params (include/ssdhip.h)
+    _fields_ = [("var", _VarAugParams), ("vflip_prob", ctypes.c_double), ("rotate_prob", ctypes.c_double)]
+
+
 # The C ABI of include/ssdhip.h, one entry per export in the header's order: name -> (restype, argtypes).  load() applies it;
 # tests/test_host_cpu.py checks it against the header's prototypes.
 _I, _LL, _SZ, _D, _F, _P = ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_double, ctypes.c_float, ctypes.c_void_p
@@ -232,6 +236,13 @@ SIGNATURES = {
     "ssdhip_var_augment_decide": (_I, [ctypes.POINTER(_VarAugParams), _I, _I] + [_P] * 11),
     "ssdhip_var_augment_decide_stream": (_I, [ctypes.POINTER(_VarAugParams), _I, _I] + [_P] * 10),
     "ssdhip_var_augment_decide_stream_ragged": (_I, [ctypes.POINTER(_VarAugParams), _I, _I] + [_P] * 11),
+    "ssdhip_sat_augment_decide": (_I, [ctypes.POINTER(_SatAugParams), _I, _I] + [_P] * 12),
+    "ssdhip_sat_augment_decide_stream": (_I, [ctypes.POINTER(_SatAugParams), _I, _I] + [_P] * 11),
+    "ssdhip_sat_augment_decide_stream_ragged": (_I, [ctypes.POINTER(_SatAugParams), _I, _I] + [_P] * 12),
+    "ssdhip_sat_augment_plans": (_I, [_P] + [_I] * 6 + [_P] * 7),
+    "ssdhip_sat_augment_plans_ragged": (_I, [_P, _P] + [_I] * 4 + [_P] * 7),
+    "ssdhip_image_resize_gather_turn_cv_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 3 + [_I, _P, _P, _I, _P, _P, _P]),
+    "ssdhip_image_resize_gather_turn_ragged_u8": (_I, [_P, _P, _P] + [_I] * 3 + [_P] * 3 + [_I, _P, _P, _I, _P, _P, _P]),
 }
 
 
@@ -2784,3 +2795,134 @@ def var_augment_decide(params, mt_states, labels, n_labels, device, table=None):
         return (out[o_geo:o_geo + ng].view(np.int32).reshape(B, 12), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
                 out[o_n:].view(np.int32), out[o_mt:o_mt + n_mt].view(np.uint32).reshape(mt_states.shape).copy())
     return ops_dev, args_dev, geo_dev, fetch
+
+
+# ---- the decisions of the satellite chain for a whole batch (csrc/ssdhip_augment.hip) ------------------------------------------------
+def sat_augment_decide(params, turns, mt_states, labels, n_labels, device, table=None):
+    """`ssdhip_sat_augment_decide` / `_stream` / `_stream_ragged`, chosen as var_augment_decide chooses: params a dict of
+    ssdhip_var_augment_params' fields plus `vflip_prob` and `rotate_prob`; turns (B,) the quarter turns (1 .. 3) drawn from Python's
+    `random` in advance (stream mode: the k-th image that rotates takes turns[k]; seeded: image b takes turns[b]).  Inputs, outputs and
+    fetch() as var_augment_decide's; the geometry (B, 12) int32 is the satellite record, for sat_augment_plans[_ragged]."""
+    torch = _torch()
+    q = _SatAugParams()
+    for k, v in params.items():
+        target = q if k in ("vflip_prob", "rotate_prob") else q.var
+        if isinstance(v, (list, tuple)):
+            arr = getattr(target, k)
+            for i, e in enumerate(v):
+                arr[i] = e
+        else:
+            setattr(target, k, v)
+    B = int(labels.shape[0])
+    turns = np.ascontiguousarray(turns, dtype=np.int32)
+    stream_mode = mt_states.ndim == 1
+    if mt_states.shape != ((625,) if stream_mode else (B, 625)) or labels.shape != (B, AUG_MAX_BOXES, 5) or n_labels.shape != (B,):
+        raise SsdHipError("sat_augment_decide: mt_states (B, 625) or (625,), labels (B, 64, 5), n_labels (B,)")
+    if turns.shape != (B,) or (B and (turns.min() < 1 or turns.max() > 3)):
+        raise SsdHipError("sat_augment_decide: turns (B,) with values 1 .. 3")
+    if table is not None:
+        require_cuda(table, "table")
+        if tuple(table.shape) != (B, 4) or table.dtype != torch.int64:
+            raise SsdHipError("sat_augment_decide: table (B, 4) int64")
+    # one packed upload: [labels f64 | mt u32 (padded to 8 bytes) | n i32 | turns i32]; the download is var_augment_decide's
+    n_mt = mt_states.size * 4
+    nl, nm = B * AUG_MAX_BOXES * 5 * 8, (n_mt + 7) // 8 * 8
+    host = np.zeros((nl + nm + B * 8,), dtype=np.uint8)
+    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
+    host[nl:nl + n_mt] = np.ascontiguousarray(mt_states, dtype=np.uint32).view(np.uint8).ravel()
+    host[nl + nm:nl + nm + B * 4] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
+    host[nl + nm + B * 4:] = turns.view(np.uint8).ravel()
+    dev_in = torch.from_numpy(host).to(device)
+    na, ng = B * IMG_PROG * 8, B * 12 * 4
+    o_args, o_mt = nl, nl + na
+    o_geo = o_mt + nm
+    o_ops = o_geo + ng
+    o_n = o_ops + B * IMG_PROG * 4
+    dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
+    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
+    vp = ctypes.c_void_p
+    ptrs = (vp(base_in + nl + nm + B * 4), vp(base_in + nl), vp(base_in), vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args),
+            vp(base_out + o_geo), vp(base_out), vp(base_out + o_n), vp(base_out + o_mt))
+    n_max = int(n_labels.max()) if B else 0
+    if not stream_mode:
+        launch("ssdhip_sat_augment_decide", device, ctypes.byref(q), B, n_max, _ptr(table) if table is not None else None, *ptrs)
+    elif table is None:
+        launch("ssdhip_sat_augment_decide_stream", device, ctypes.byref(q), B, n_max, *ptrs)
+    else:
+        launch("ssdhip_sat_augment_decide_stream_ragged", device, ctypes.byref(q), B, n_max, _ptr(table), *ptrs)
+    ops_dev = dev_out[o_ops:o_ops + B * IMG_PROG * 4].view(torch.int32).view(B, IMG_PROG)
+    args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG)
+    geo_dev = dev_out[o_geo:o_geo + ng].view(torch.int32).view(B, 12)
+
+    def fetch():
+        """(geometry, labels_out, n_out, mt_states_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
+        out = dev_out.cpu().numpy()
+        return (out[o_geo:o_geo + ng].view(np.int32).reshape(B, 12), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
+                out[o_n:].view(np.int32), out[o_mt:o_mt + n_mt].view(np.uint32).reshape(mt_states.shape).copy())
+    return ops_dev, args_dev, geo_dev, fetch
+
+
+def sat_augment_plans(geo_dev, out_h, out_w, n_taps, size=None, table=None):
+    """`ssdhip_sat_augment_plans` (size = the batch's (H, W)) or `ssdhip_sat_augment_plans_ragged` (table (B, 4) int64 CUDA tensor):
+    the turn gathers' per-image plans from the satellite chain's geometry -> (plans (B, 4), ix, wx, iy, wy, transposed (B,) int32)."""
+    torch = _torch()
+    B, dev = int(geo_dev.shape[0]), geo_dev.device
+    if (size is None) == (table is None):
+        raise SsdHipError("sat_augment_plans: one of size and table")
+    plans = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ix = torch.empty((B, out_w, n_taps), dtype=torch.int32, device=dev)
+    wx = torch.empty((B, out_w, n_taps), dtype=torch.float64, device=dev)
+    iy = torch.empty((B, out_h, n_taps), dtype=torch.int32, device=dev)
+    wy = torch.empty((B, out_h, n_taps), dtype=torch.float64, device=dev)
+    transposed = torch.empty((B,), dtype=torch.int32, device=dev)
+    if table is None:
+        launch("ssdhip_sat_augment_plans", dev, _ptr(geo_dev), B, int(size[0]), int(size[1]), int(out_h), int(out_w), int(n_taps),
+               _ptr(plans), _ptr(ix), _ptr(wx), _ptr(iy), _ptr(wy), _ptr(transposed))
+    else:
+        require_cuda(table, "table")
+        if tuple(table.shape) != (B, 4) or table.dtype != torch.int64:
+            raise SsdHipError("sat_augment_plans: table (B, 4) int64")
+        launch("ssdhip_sat_augment_plans_ragged", dev, _ptr(geo_dev), _ptr(table), B, int(out_h), int(out_w), int(n_taps), _ptr(plans),
+               _ptr(ix), _ptr(wx), _ptr(iy), _ptr(wy), _ptr(transposed))
+    return plans, ix, wx, iy, wy, transposed
+
+
+def image_resize_gather_turn_u8(images, table, out_h, out_w, plans, ix, wx, iy, wy, transposed, background):
+    """`ssdhip_image_resize_gather_turn_cv_u8` (images (B, H, W, C) CUDA uint8, table None) or `..._turn_ragged_u8` (images: a ragged
+    batch's buffer, table its (B, 4) int64 table): the gathers of image_resize_gather_cv_u8 / image_resize_gather_ragged_u8 for plans with
+    quarter turns -- transposed (B,) int32: the image's row table addresses source columns; index -1 = background, -2 = 0."""
+    torch = _torch()
+    require_cuda(images, "images")
+    dev = images.device
+    if table is None:
+        if images.dtype != torch.uint8 or images.dim() != 4 or not images.is_contiguous():
+            raise SsdHipError("images must be a contiguous (B, H, W, C) uint8 tensor")
+        b, h, w, c = images.shape
+    else:
+        require_cuda(table, "table")
+        if images.dtype != torch.uint8 or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4:
+            raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
+        b, c = int(table.shape[0]), 3
+    plans = to_device(plans, device=dev, dtype=torch.int32).contiguous()
+    ix = to_device(ix, device=dev, dtype=torch.int32).contiguous()
+    wx = to_device(wx, device=dev, dtype=torch.float64).contiguous()
+    iy = to_device(iy, device=dev, dtype=torch.int32).contiguous()
+    wy = to_device(wy, device=dev, dtype=torch.float64).contiguous()
+    tr = to_device(transposed, device=dev, dtype=torch.int32).contiguous()
+    bg = to_device(background, device=dev, dtype=torch.uint8).contiguous()
+    pad = lambda t: torch.cat([t, torch.zeros_like(t)], dim=2)
+    if ix.shape[2] < 2:
+        ix, wx = pad(ix), pad(wx)
+    if iy.shape[2] < 2:
+        iy, wy = pad(iy), pad(wy)
+    if (ix.shape != wx.shape or iy.shape != wy.shape or tuple(ix.shape[:2]) != (b, out_w) or tuple(iy.shape[:2]) != (b, out_h)
+            or tuple(bg.shape) != (b, c) or tuple(plans.shape) != (b, 4) or tuple(tr.shape) != (b,)):
+        raise SsdHipError("plans must be (B, 4), tap tables (B, out_w, nx) / (B, out_h, ny), transposed (B,), background (B, C)")
+    out = torch.empty((b, out_h, out_w, c), dtype=torch.uint8, device=dev)
+    if table is None:
+        launch("ssdhip_image_resize_gather_turn_cv_u8", dev, _ptr(images), _ptr(out), b, h, w, int(out_h), int(out_w), c, _ptr(plans),
+               _ptr(ix), _ptr(wx), int(ix.shape[2]), _ptr(iy), _ptr(wy), int(iy.shape[2]), _ptr(tr), _ptr(bg))
+    else:
+        launch("ssdhip_image_resize_gather_turn_ragged_u8", dev, _ptr(images), _ptr(table), _ptr(out), b, int(out_h), int(out_w), _ptr(plans),
+               _ptr(ix), _ptr(wx), int(ix.shape[2]), _ptr(iy), _ptr(wy), int(iy.shape[2]), _ptr(tr), _ptr(bg))
+    return out

@@ -362,24 +362,11 @@ __device__ __forceinline__ AugPlan aug_plan_of(int Hc, int Wc, int out_h, int ou
     return q;
 }
 
-// grid (blocks over positions, 2 axes, B); axis 0 = columns (x), 1 = rows (y); plan [B][4] = kind, area, taps per column, taps per row
-template <class HW>
-__global__ __launch_bounds__(128) void aug_plan_kernel(const int* __restrict__ geo, HW hw, int out_h, int out_w, int n_taps,
-                                                       int* __restrict__ plan, int* __restrict__ ix, double* __restrict__ wx,
-                                                       int* __restrict__ iy, double* __restrict__ wy) {
-    const int b = (int)blockIdx.z, axis = (int)blockIdx.y;
-    const int n_dst = axis == 0 ? out_w : out_h;
-    const int i = (int)blockIdx.x * 128 + (int)threadIdx.x;
-    const int* g = geo + (size_t)b * 12;
-    const int H = hw.h(b), W = hw.w(b);
-    const int Hc = g[8], Wc = g[9];
-    const AugPlan q = aug_plan_of(Hc, Wc, out_h, out_w, g[11], n_taps);
-    if (axis == 0 && i == 0) { plan[b * 4] = q.kind; plan[b * 4 + 1] = q.area; plan[b * 4 + 2] = q.tx; plan[b * 4 + 3] = q.ty; }
-    if (i >= n_dst) return;
-    const int n_src = axis == 0 ? Wc : Hc;
+// The taps of destination position i of one axis (0 = columns, 1 = rows) of plan q: indices into the n_src positions of the image in front
+// of the resize and the table values, idx / w [64]; returns how many.
+__device__ __forceinline__ int aug_axis_taps(const AugPlan& q, const int axis, const int i, const int n_src, const int n_dst, int* idx,
+                                             double* w) {
     const double inv = (double)n_dst / (double)n_src, scale = 1.0 / inv;
-    int idx[64];
-    double w[64];
     int T = 1;
     if (q.kind == PK_COPY) { idx[0] = i; w[0] = 1.0; }
     else if (q.kind == PK_NEAREST) {
@@ -464,6 +451,27 @@ __global__ __launch_bounds__(128) void aug_plan_kernel(const int* __restrict__ g
             w[t] = aug_to_short(co[t]);
         }
     }
+    return T;
+}
+
+// grid (blocks over positions, 2 axes, B); axis 0 = columns (x), 1 = rows (y); plan [B][4] = kind, area, taps per column, taps per row
+template <class HW>
+__global__ __launch_bounds__(128) void aug_plan_kernel(const int* __restrict__ geo, HW hw, int out_h, int out_w, int n_taps,
+                                                       int* __restrict__ plan, int* __restrict__ ix, double* __restrict__ wx,
+                                                       int* __restrict__ iy, double* __restrict__ wy) {
+    const int b = (int)blockIdx.z, axis = (int)blockIdx.y;
+    const int n_dst = axis == 0 ? out_w : out_h;
+    const int i = (int)blockIdx.x * 128 + (int)threadIdx.x;
+    const int* g = geo + (size_t)b * 12;
+    const int H = hw.h(b), W = hw.w(b);
+    const int Hc = g[8], Wc = g[9];
+    const AugPlan q = aug_plan_of(Hc, Wc, out_h, out_w, g[11], n_taps);
+    if (axis == 0 && i == 0) { plan[b * 4] = q.kind; plan[b * 4 + 1] = q.area; plan[b * 4 + 2] = q.tx; plan[b * 4 + 3] = q.ty; }
+    if (i >= n_dst) return;
+    const int n_src = axis == 0 ? Wc : Hc;
+    int idx[64];
+    double w[64];
+    const int T = aug_axis_taps(q, axis, i, n_src, n_dst, idx, w);
     // the recorded geometry: position j of the final (pre-resize) image <- flip <- crop window <- expansion canvas <- the image
     int* oi = (axis == 0 ? ix : iy) + ((size_t)b * n_dst + i) * n_taps;
     double* ow = (axis == 0 ? wx : wy) + ((size_t)b * n_dst + i) * n_taps;
@@ -713,25 +721,24 @@ __device__ __forceinline__ bool vaug_overlap_ok(const int criterion, double x0, 
     return cy >= 0.0 && cy <= H - 1.0 && cx >= 0.0 && cx <= W - 1.0;
 }
 
-// ONE image of the chain by one wave on the generator state `s`; (H0, W0): the image's size.
-__device__ __forceinline__ void vaug_decide_image(const VarAugParams& p, Mt& s, const int lane, const int b, const int H0, const int W0,
-                                                  const double* __restrict__ lab_in, const int* __restrict__ n_in,
-                                                  int* __restrict__ prog_ops, double* __restrict__ prog_args, int* __restrict__ geo,
-                                                  double* __restrict__ lab_out, int* __restrict__ n_out) {
-    (void)aug_photo_program(s, lane, p.ph_prob, p.ph_lo, p.ph_hi, false, false, b, prog_ops, prog_args);
-
+// The labels of image b, one box per lane: returns the clamped count, `alive` = this lane holds a box.
+__device__ __forceinline__ int vaug_load_labels(const int lane, const int b, const double* __restrict__ lab_in, const int* __restrict__ n_in,
+                                                bool& alive, double& cls, double& x0, double& y0, double& x1, double& y1) {
     int n = n_in[b];
     n = n < 0 ? 0 : (n > AUG_MAXG ? AUG_MAXG : n);
-    bool alive = lane < n;
-    double cls = 0.0, x0 = 0.0, y0 = 0.0, x1 = 0.0, y1 = 0.0;
+    alive = lane < n;
+    cls = 0.0; x0 = 0.0; y0 = 0.0; x1 = 0.0; y1 = 0.0;
     if (alive) {
         const double* r = lab_in + ((size_t)b * AUG_MAXG + lane) * 5;
         cls = r[0]; x0 = r[1]; y0 = r[2]; x1 = r[3]; y1 = r[4];
     }
-    int H = H0, W = W0;
-    int g[12] = {0, 0, 0, H, W, 0, 0, 0, H, W, 0, p.interp};
+    return n;
+}
 
-    // ---- RandomPatch: the firing draw, then up to n_trials patches; the first one the validator accepts is cut (CropPad) ---------------
+// RandomPatch on an H x W image: the firing draw, then up to n_trials patches; the first one the validator accepts is cut (CropPad: shift,
+// box filter, clip) and becomes the image -- win = (top, left, height, width), H and W the patch's.  Returns whether a patch was cut.
+__device__ __forceinline__ bool vaug_random_patch(const VarAugParams& p, Mt& s, const int lane, const int n, bool& alive, double& x0, double& y0,
+                                                  double& x1, double& y1, int& H, int& W, int* win) {
     if (!(mt_uniform(s, lane, 0.0, 1.0) < (1.0 - p.patch_prob))) {
         for (int t = 0; t < p.n_trials; ++t) {
             const int w = (int)(mt_uniform(s, lane, p.scale_lo, p.scale_hi) * (double)W);
@@ -749,28 +756,26 @@ __device__ __forceinline__ void vaug_decide_image(const VarAugParams& p, Mt& s, 
                 y0 = np_minimum<double>(np_maximum<double>(y0, 0.0), ymax); y1 = np_minimum<double>(np_maximum<double>(y1, 0.0), ymax);
                 x0 = np_minimum<double>(np_maximum<double>(x0, 0.0), xmax); x1 = np_minimum<double>(np_maximum<double>(x1, 0.0), xmax);
             }
-            g[0] = 1; g[1] = top; g[2] = left; g[3] = h; g[4] = w;
+            win[0] = top; win[1] = left; win[2] = h; win[3] = w;
             H = h; W = w;
-            break;
+            return true;
         }
     }
-    g[8] = H; g[9] = W;
+    return false;
+}
 
-    // ---- RandomFlip('horizontal', prob) ----------------------------------------------------------------------------------------------
-    if (!(mt_uniform(s, lane, 0.0, 1.0) < (1.0 - p.flip_prob))) {
-        const double nx0 = (double)W - x1, nx1 = (double)W - x0;
-        x0 = nx0; x1 = nx1;
-        g[10] = 1;
-    }
+// Resize: no draw; np.round(coordinate * (out / size)), then the (degenerate, min_area) box filter
+__device__ __forceinline__ void vaug_resize_labels(const VarAugParams& p, const int H, const int W, bool& alive, double& x0, double& y0,
+                                                   double& x1, double& y1) {
+    const double sy = (double)p.out_h / (double)H, sx = (double)p.out_w / (double)W;
+    y0 = __builtin_rint(y0 * sy); y1 = __builtin_rint(y1 * sy);
+    x0 = __builtin_rint(x0 * sx); x1 = __builtin_rint(x1 * sx);
+    alive = alive && x1 > x0 && y1 > y0 && ((x1 - x0) * (y1 - y0) >= p.min_area);
+}
 
-    // ---- Resize: no draw; np.round(coordinate * (out / size)), then the (degenerate, min_area) box filter --------------------------------
-    {
-        const double sy = (double)p.out_h / (double)H, sx = (double)p.out_w / (double)W;
-        y0 = __builtin_rint(y0 * sy); y1 = __builtin_rint(y1 * sy);
-        x0 = __builtin_rint(x0 * sx); x1 = __builtin_rint(x1 * sx);
-        alive = alive && x1 > x0 && y1 > y0 && ((x1 - x0) * (y1 - y0) >= p.min_area);
-    }
-
+// The surviving boxes of image b, compacted in lane order, their count and the 12-int geometry record.
+__device__ __forceinline__ void vaug_store(const int lane, const int b, const bool alive, double cls, double x0, double y0, double x1, double y1,
+                                           const int* g, int* __restrict__ geo, double* __restrict__ lab_out, int* __restrict__ n_out) {
     const u64 keep = __ballot(alive);
     if (alive) {
         const int pos = __popcll(keep & lanemask_lt());
@@ -781,6 +786,34 @@ __device__ __forceinline__ void vaug_decide_image(const VarAugParams& p, Mt& s, 
         n_out[b] = __popcll(keep);
         for (int i = 0; i < 12; ++i) geo[(size_t)b * 12 + i] = g[i];
     }
+}
+
+// ONE image of the chain by one wave on the generator state `s`; (H0, W0): the image's size.
+__device__ __forceinline__ void vaug_decide_image(const VarAugParams& p, Mt& s, const int lane, const int b, const int H0, const int W0,
+                                                  const double* __restrict__ lab_in, const int* __restrict__ n_in,
+                                                  int* __restrict__ prog_ops, double* __restrict__ prog_args, int* __restrict__ geo,
+                                                  double* __restrict__ lab_out, int* __restrict__ n_out) {
+    (void)aug_photo_program(s, lane, p.ph_prob, p.ph_lo, p.ph_hi, false, false, b, prog_ops, prog_args);
+
+    bool alive;
+    double cls, x0, y0, x1, y1;
+    const int n = vaug_load_labels(lane, b, lab_in, n_in, alive, cls, x0, y0, x1, y1);
+    int H = H0, W = W0;
+    int g[12] = {0, 0, 0, H, W, 0, 0, 0, H, W, 0, p.interp};
+
+    // ---- RandomPatch ---------------------------------------------------------------------------------------------------------------
+    if (vaug_random_patch(p, s, lane, n, alive, x0, y0, x1, y1, H, W, g + 1)) g[0] = 1;
+    g[8] = H; g[9] = W;
+
+    // ---- RandomFlip('horizontal', prob) ----------------------------------------------------------------------------------------------
+    if (!(mt_uniform(s, lane, 0.0, 1.0) < (1.0 - p.flip_prob))) {
+        const double nx0 = (double)W - x1, nx1 = (double)W - x0;
+        x0 = nx0; x1 = nx1;
+        g[10] = 1;
+    }
+
+    vaug_resize_labels(p, H, W, alive, x0, y0, x1, y1);
+    vaug_store(lane, b, alive, cls, x0, y0, x1, y1, g, geo, lab_out, n_out);
 }
 
 // STREAM = false: one wave per image, image b on its own state (mt [B][625]); true: one wave walks the B images in order on one state.
@@ -810,6 +843,150 @@ __global__ __launch_bounds__(64) void var_augment_decide_kernel(VarAugParams p, 
     if (lane == 0) mt_out[at + 624] = (u32)s.pos;
     __syncthreads();
     for (int i = lane; i < 624; i += 64) mt_out[at + i] = key[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// DataAugmentationSatellite (data_generator/data_augmentation_chain_satellite.py), the chain for images in bird's eye view: the variable
+// chain's photometric draws, then RandomFlip('horizontal'), RandomFlip('vertical'), RandomRotate by 90 / 180 / 270 degrees, RandomPatch on
+// the ROTATED image's height and width, and Resize.  The angle of a rotation is the one draw of the chain that comes from Python's
+// `random`, not from NumPy: the host draws `random.choice(angles)` B times in advance from a copy of that generator and uploads the
+// quarter turns (1 .. 3); a wave that walks the batch on one stream hands the k-th value to the k-th image that rotates, a wave on its own
+// stream (one per image) takes value b.  Rotate's labels under the reference's adjusted matrix, for whole-number coordinates, are
+//   90: (ymin, W - xmax, ymax, W - xmin)   180: (W - xmax, H - ymax, W - xmin, H - ymin)   270: (H - ymax, xmin, H - ymin, xmax)
+// (H x W: the image in front of the rotation).  Geometry record, 12 ints: [0] patched? [1 .. 4] the patch's top, left, height, width on
+// the rotated image (the first window slot of the other chains' record), [5] flipped horizontally? [6] vertically? [7] quarter turns,
+// [8], [9] the size in front of the resize, [10] 0, [11] the interpolation mode.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+struct SatAugParams {
+    VarAugParams v;                                       // v.flip_prob: the horizontal flip's
+    double vflip_prob, rot_prob;
+};
+
+// ONE image by one wave; `turns`: the quarter turns this image takes IF it rotates.  Returns whether it rotated.
+__device__ __forceinline__ bool saug_decide_image(const SatAugParams& p, Mt& s, const int lane, const int b, const int H0, const int W0,
+                                                  int turns, const double* __restrict__ lab_in, const int* __restrict__ n_in,
+                                                  int* __restrict__ prog_ops, double* __restrict__ prog_args, int* __restrict__ geo,
+                                                  double* __restrict__ lab_out, int* __restrict__ n_out) {
+    (void)aug_photo_program(s, lane, p.v.ph_prob, p.v.ph_lo, p.v.ph_hi, false, false, b, prog_ops, prog_args);
+
+    bool alive;
+    double cls, x0, y0, x1, y1;
+    const int n = vaug_load_labels(lane, b, lab_in, n_in, alive, cls, x0, y0, x1, y1);
+    int H = H0, W = W0;
+    int g[12] = {0, 0, 0, H, W, 0, 0, 0, H, W, 0, p.v.interp};
+
+    // ---- RandomFlip('horizontal', prob), RandomFlip('vertical', prob): `uniform < 1 - prob` leaves the image alone -----------------------
+    if (!(mt_uniform(s, lane, 0.0, 1.0) < (1.0 - p.v.flip_prob))) {
+        const double nx0 = (double)W - x1, nx1 = (double)W - x0;
+        x0 = nx0; x1 = nx1;
+        g[5] = 1;
+    }
+    if (!(mt_uniform(s, lane, 0.0, 1.0) < (1.0 - p.vflip_prob))) {
+        const double ny0 = (double)H - y1, ny1 = (double)H - y0;
+        y0 = ny0; y1 = ny1;
+        g[6] = 1;
+    }
+
+    // ---- RandomRotate: `uniform >= 1 - prob` rotates, by the angle the host drew ------------------------------------------------------------
+    const bool rotated = mt_uniform(s, lane, 0.0, 1.0) >= (1.0 - p.rot_prob);
+    if (rotated) {
+        turns = turns < 1 ? 1 : (turns > 3 ? 3 : turns);
+        const double dH = (double)H, dW = (double)W;
+        const double ax0 = x0, ay0 = y0, ax1 = x1, ay1 = y1;
+        if (turns == 1) { x0 = ay0; y0 = dW - ax1; x1 = ay1; y1 = dW - ax0; }
+        else if (turns == 2) { x0 = dW - ax1; y0 = dH - ay1; x1 = dW - ax0; y1 = dH - ay0; }
+        else { x0 = dH - ay1; y0 = ax0; x1 = dH - ay0; y1 = ax1; }
+        if (turns & 1) { const int t = H; H = W; W = t; }
+        g[7] = turns;
+    }
+
+    // ---- RandomPatch on the rotated image, Resize ------------------------------------------------------------------------------------------
+    g[3] = H; g[4] = W;
+    if (vaug_random_patch(p.v, s, lane, n, alive, x0, y0, x1, y1, H, W, g + 1)) g[0] = 1;
+    g[8] = H; g[9] = W;
+    vaug_resize_labels(p.v, H, W, alive, x0, y0, x1, y1);
+    vaug_store(lane, b, alive, cls, x0, y0, x1, y1, g, geo, lab_out, n_out);
+    return rotated;
+}
+
+// STREAM / HW as var_augment_decide_kernel's; turns [B]: the quarter turns drawn on the host (see above).
+template <bool STREAM, class HW>
+__global__ __launch_bounds__(64) void sat_augment_decide_kernel(SatAugParams p, HW hw, int B, const int* __restrict__ turns,
+                                                                const u32* __restrict__ mt_in, const double* __restrict__ lab_in,
+                                                                const int* __restrict__ n_in, int* __restrict__ prog_ops,
+                                                                double* __restrict__ prog_args, int* __restrict__ geo,
+                                                                double* __restrict__ lab_out, int* __restrict__ n_out,
+                                                                u32* __restrict__ mt_out) {
+    __shared__ u32 key[624];
+    const int lane = (int)threadIdx.x;
+    const size_t at = STREAM ? 0 : (size_t)blockIdx.x * 625;
+    for (int i = lane; i < 624; i += 64) key[i] = mt_in[at + i];
+    Mt s;
+    s.key = key;
+    s.pos = (int)mt_in[at + 624];
+    s.base = -1; s.win = 0u;
+    __syncthreads();
+    if (STREAM) {
+        int k = 0;                                        // how many images have rotated so far (k <= b < B)
+        for (int b = 0; b < B; ++b)
+            if (saug_decide_image(p, s, lane, b, hw.h(b), hw.w(b), turns[k], lab_in, n_in, prog_ops, prog_args, geo, lab_out, n_out)) ++k;
+    } else {
+        const int b = (int)blockIdx.x;
+        (void)saug_decide_image(p, s, lane, b, hw.h(b), hw.w(b), turns[b], lab_in, n_in, prog_ops, prog_args, geo, lab_out, n_out);
+    }
+    if (lane == 0) mt_out[at + 624] = (u32)s.pos;
+    __syncthreads();
+    for (int i = lane; i < 624; i += 64) mt_out[at + i] = key[i];
+}
+
+// The gather's plans for that record: resize taps <- patch window <- rotation <- vertical flip <- horizontal flip.  A rotated image is still
+// two index maps: under the reference's matrices output pixel (row y, column x) of an H x W source reads source (column, row)
+//   90: (W - y, x)     180: (W - x, H - y)     270: (y, H - x)
+// so for 90 / 270 the ROW map (iy) addresses source columns and the column map (ix) source rows -- transposed [b] = 1 tells the gather to
+// swap them.  Index -1 = outside the patch window (the patch's background colour), -2 = outside the source under the rotation (always 0).
+// grid, plan and tables as aug_plan_kernel's.
+template <class HW>
+__global__ __launch_bounds__(128) void sat_plan_kernel(const int* __restrict__ geo, HW hw, int out_h, int out_w, int n_taps,
+                                                       int* __restrict__ plan, int* __restrict__ ix, double* __restrict__ wx,
+                                                       int* __restrict__ iy, double* __restrict__ wy, int* __restrict__ transposed) {
+    const int b = (int)blockIdx.z, axis = (int)blockIdx.y;
+    const int n_dst = axis == 0 ? out_w : out_h;
+    const int i = (int)blockIdx.x * 128 + (int)threadIdx.x;
+    const int* g = geo + (size_t)b * 12;
+    const int Hs = hw.h(b), Ws = hw.w(b);                                        // the source image
+    const int turns = g[7];
+    const int Hr = (turns & 1) ? Ws : Hs, Wr = (turns & 1) ? Hs : Ws;            // the rotated image
+    const int Hc = g[8], Wc = g[9];
+    const AugPlan q = aug_plan_of(Hc, Wc, out_h, out_w, g[11], n_taps);
+    if (axis == 0 && i == 0) {
+        plan[b * 4] = q.kind; plan[b * 4 + 1] = q.area; plan[b * 4 + 2] = q.tx; plan[b * 4 + 3] = q.ty;
+        transposed[b] = turns & 1;
+    }
+    if (i >= n_dst) return;
+    const int n_src = axis == 0 ? Wc : Hc;
+    int idx[64];
+    double w[64];
+    const int T = aug_axis_taps(q, axis, i, n_src, n_dst, idx, w);
+    int* oi = (axis == 0 ? ix : iy) + ((size_t)b * n_dst + i) * n_taps;
+    double* ow = (axis == 0 ? wx : wy) + ((size_t)b * n_dst + i) * n_taps;
+    for (int t = 0; t < n_taps; ++t) {
+        int j = idx[t < T ? t : T - 1];
+        if (g[0]) {                                                               // the patch: the rotated image sits at (-top, -left)
+            j += axis == 0 ? g[2] : g[1];
+            if (j < 0 || j >= (axis == 0 ? Wr : Hr)) j = -1;
+        }
+        if (j >= 0) {
+            bool column = axis == 0;                                              // does j address a source column?
+            if (turns == 1) { column = axis == 1; if (axis == 1) j = Ws - j; }
+            else if (turns == 2) j = (axis == 0 ? Ws : Hs) - j;
+            else if (turns == 3) { column = axis == 1; if (axis == 0) j = Hs - j; }
+            const int extent = column ? Ws : Hs;
+            if (j >= extent) j = -2;                                              // the rotation's one border row / column
+            else if (column ? g[5] : g[6]) j = extent - 1 - j;                    // the two flips
+        }
+        oi[t] = j;
+        ow[t] = t < T ? w[t] : 0.0;
+    }
 }
 
 }  // namespace ssdhip
@@ -1068,4 +1245,82 @@ extern "C" int ssdhip_var_augment_decide_stream_ragged(const ssdhip_var_augment_
     if (!table_dev) return SSDHIP_E_BADARG;
     return var_decide<true>(params, B, n_boxes_max, table_dev, mt_state, labels, n_labels, programs_ops, programs_args, geometry, labels_out,
                             n_labels_out, mt_state_out, stream);
+}
+
+// ---- DataAugmentationSatellite: the decisions of a batch (seeded: B states; stream: one), uniform or ragged sizes, and its plans ----------
+template <bool STREAM>
+static int sat_decide(const ssdhip_sat_augment_params* q, int B, int n_boxes_max, const long long* table_dev, const int* turns_dev,
+                      const unsigned int* mt_state, const double* labels, const int* n_labels, int* programs_ops, double* programs_args,
+                      int* geometry, double* labels_out, int* n_labels_out, unsigned int* mt_state_out, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!q || B <= 0 || !turns_dev || !mt_state || !labels || !n_labels || !programs_ops || !programs_args || !geometry || !labels_out ||
+        !n_labels_out || !mt_state_out)
+        return SSDHIP_E_BADARG;
+    if (!(q->vflip_prob >= 0.0 && q->vflip_prob <= 1.0) || !(q->rotate_prob >= 0.0 && q->rotate_prob <= 1.0)) return SSDHIP_E_BADARG;
+    SatAugParams p;
+    const int rc = var_params_from(&q->var, table_dev != nullptr, n_boxes_max, p.v);
+    if (rc != SSDHIP_OK) return rc;
+    p.vflip_prob = q->vflip_prob; p.rot_prob = q->rotate_prob;
+    const dim3 grid(STREAM ? 1u : (unsigned)B);
+    if (table_dev)
+        hipLaunchKernelGGL((sat_augment_decide_kernel<STREAM, RaggedHW>), grid, dim3(64), 0, stream, p, RaggedHW{table_dev}, B, turns_dev,
+                           mt_state, labels, n_labels, programs_ops, programs_args, geometry, labels_out, n_labels_out, mt_state_out);
+    else
+        hipLaunchKernelGGL((sat_augment_decide_kernel<STREAM, UniformHW>), grid, dim3(64), 0, stream, p,
+                           UniformHW{q->var.img_height, q->var.img_width}, B, turns_dev, mt_state, labels, n_labels, programs_ops,
+                           programs_args, geometry, labels_out, n_labels_out, mt_state_out);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_sat_augment_decide(const ssdhip_sat_augment_params* params, int B, int n_boxes_max, const long long* table_dev,
+                                         const int* turns_dev, const unsigned int* mt_state, const double* labels, const int* n_labels,
+                                         int* programs_ops, double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
+                                         unsigned int* mt_state_out, void* stream) {
+    return sat_decide<false>(params, B, n_boxes_max, table_dev, turns_dev, mt_state, labels, n_labels, programs_ops, programs_args, geometry,
+                             labels_out, n_labels_out, mt_state_out, stream);
+}
+
+extern "C" int ssdhip_sat_augment_decide_stream(const ssdhip_sat_augment_params* params, int B, int n_boxes_max, const int* turns_dev,
+                                                const unsigned int* mt_state, const double* labels, const int* n_labels, int* programs_ops,
+                                                double* programs_args, int* geometry, double* labels_out, int* n_labels_out,
+                                                unsigned int* mt_state_out, void* stream) {
+    return sat_decide<true>(params, B, n_boxes_max, nullptr, turns_dev, mt_state, labels, n_labels, programs_ops, programs_args, geometry,
+                            labels_out, n_labels_out, mt_state_out, stream);
+}
+
+extern "C" int ssdhip_sat_augment_decide_stream_ragged(const ssdhip_sat_augment_params* params, int B, int n_boxes_max,
+                                                       const long long* table_dev, const int* turns_dev, const unsigned int* mt_state,
+                                                       const double* labels, const int* n_labels, int* programs_ops, double* programs_args,
+                                                       int* geometry, double* labels_out, int* n_labels_out, unsigned int* mt_state_out,
+                                                       void* stream) {
+    if (!table_dev) return SSDHIP_E_BADARG;
+    return sat_decide<true>(params, B, n_boxes_max, table_dev, turns_dev, mt_state, labels, n_labels, programs_ops, programs_args, geometry,
+                            labels_out, n_labels_out, mt_state_out, stream);
+}
+
+extern "C" int ssdhip_sat_augment_plans(const int* geometry_dev, int B, int H, int W, int out_h, int out_w, int n_taps, int* plan_dev,
+                                        int* ix_dev, double* wx_dev, int* iy_dev, double* wy_dev, int* transposed_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!geometry_dev || !plan_dev || !ix_dev || !wx_dev || !iy_dev || !wy_dev || !transposed_dev || B <= 0 || B > 65535 || H <= 0 ||
+        W <= 0 || out_h <= 0 || out_w <= 0)
+        return SSDHIP_E_BADARG;
+    if (n_taps < 8 || n_taps > 64) return SSDHIP_E_BADARG;
+    const int n = out_h > out_w ? out_h : out_w;
+    hipLaunchKernelGGL(sat_plan_kernel<UniformHW>, dim3((unsigned)((n + 127) / 128), 2, (unsigned)B), dim3(128), 0, stream, geometry_dev,
+                       UniformHW{H, W}, out_h, out_w, n_taps, plan_dev, ix_dev, wx_dev, iy_dev, wy_dev, transposed_dev);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_sat_augment_plans_ragged(const int* geometry_dev, const long long* table_dev, int B, int out_h, int out_w, int n_taps,
+                                               int* plan_dev, int* ix_dev, double* wx_dev, int* iy_dev, double* wy_dev, int* transposed_dev,
+                                               void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!geometry_dev || !table_dev || !plan_dev || !ix_dev || !wx_dev || !iy_dev || !wy_dev || !transposed_dev || B <= 0 || B > 65535 ||
+        out_h <= 0 || out_w <= 0)
+        return SSDHIP_E_BADARG;
+    if (n_taps < 8 || n_taps > 64) return SSDHIP_E_BADARG;
+    const int n = out_h > out_w ? out_h : out_w;
+    hipLaunchKernelGGL(sat_plan_kernel<RaggedHW>, dim3((unsigned)((n + 127) / 128), 2, (unsigned)B), dim3(128), 0, stream, geometry_dev,
+                       RaggedHW{table_dev}, out_h, out_w, n_taps, plan_dev, ix_dev, wx_dev, iy_dev, wy_dev, transposed_dev);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }

@@ -11,7 +11,8 @@
 //                            its own program (the random draws stay on the host, in the reference's order);
 //   * resize_cv_kernel / resize_gather_cv_kernel   cv2.resize with OpenCV's own 8-bit arithmetic, from a plan of source indices
 //                            and weights per output column / row (one plan for the batch, or one per image with the augmentation
-//                            chain's expansion / crop / flip composed in);
+//                            chain's expansion / crop / flip composed in; resize_gather_turn_cv_kernel: the same for plans that
+//                            hold a rotation by quarter turns -- a transposed bit per image swaps the source address);
 //   * hist_u8_kernel / lut_u8_kernel   cv2.equalizeHist (histogram on the device, the 256-entry table on the host) and cv2.LUT.
 // Arithmetic is written operation by operation (-ffp-contract=off): bit-identical to the NumPy restatement in oracle/np_image.py.
 #include <hip/hip_runtime.h>
@@ -353,6 +354,8 @@ struct UniformGatherSrc {
         __device__ __forceinline__ int at(int sy, int sx) const { return (int)p[((size_t)sy * W + sx) * C]; }
     };
     __device__ __forceinline__ View view(int b, int ch) const { return View{x + (size_t)b * H * W * C + ch, W, C}; }
+    __device__ __forceinline__ int height(int) const { return H; }
+    __device__ __forceinline__ int width(int) const { return W; }
 };
 struct RaggedGatherSrc {
     const unsigned char* x;
@@ -370,6 +373,8 @@ struct RaggedGatherSrc {
         const int c = (int)t[3];
         return View{x + t[0] + (c == 1 ? 0 : ch), (int)t[1], (int)t[2], c};
     }
+    __device__ __forceinline__ int height(int b) const { return (int)table[(size_t)b * 4 + 1]; }
+    __device__ __forceinline__ int width(int b) const { return (int)table[(size_t)b * 4 + 2]; }
 };
 
 // every image its own plan (the augmentation chain's gather launch): plan [B][4] = kind, area, taps per column, taps per row (<= nx, ny =
@@ -391,6 +396,39 @@ __global__ __launch_bounds__(256) void resize_gather_cv_kernel(Src src, unsigned
     auto px = [&](int j, int k) -> int {
         const int sy = iyb[j], sx = ixb[k];
         return (sy < 0 || sx < 0) ? bg : img.at(sy, sx);
+    };
+    y[((size_t)b * Ho + yo) * Wo * C + v] = cv_resample(kind, area, tx < nx ? tx : nx, ty < ny ? ty : ny, wx + ((size_t)b * Wo + xo) * nx,
+                                                        wy + ((size_t)b * Ho + yo) * ny, px);
+}
+
+// The gather for plans that hold a rotation by quarter turns (ssdhip_sat_augment_plans): transposed [B] = 1 -> image b's ROW table (iy)
+// addresses source columns and its column table (ix) source rows, so the source address is swapped; index -1 = background [B][C] (the
+// patch's padding), -2 = 0 (what the rotation's warpAffine leaves outside the source), -1 in either table wins.  Indices are clamped into
+// the image.  Same arithmetic (cv_resample), grid and tables as resize_gather_cv_kernel.
+template <class Src>
+__global__ __launch_bounds__(256) void resize_gather_turn_cv_kernel(Src src, unsigned char* __restrict__ y, int Ho, int Wo, int C,
+                                                                    const int* __restrict__ plan, const int* __restrict__ ix,
+                                                                    const double* __restrict__ wx, int nx, const int* __restrict__ iy,
+                                                                    const double* __restrict__ wy, int ny,
+                                                                    const int* __restrict__ transposed,
+                                                                    const unsigned char* __restrict__ background) {
+    const int v = (int)blockIdx.x * 256 + (int)threadIdx.x, yo = (int)blockIdx.y, b = (int)blockIdx.z;
+    if (v >= Wo * C) return;
+    const int xo = v / C, ch = v - xo * C;
+    const int kind = plan[b * 4], area = plan[b * 4 + 1], tx = plan[b * 4 + 2], ty = plan[b * 4 + 3];
+    const int bg = (int)background[b * C + ch];
+    const bool turned = transposed[b] != 0;
+    const int* ixb = ix + ((size_t)b * Wo + xo) * nx;
+    const int* iyb = iy + ((size_t)b * Ho + yo) * ny;
+    const typename Src::View img = src.view(b, ch);
+    const int H = src.height(b), W = src.width(b);
+    auto px = [&](int j, int k) -> int {
+        const int a = iyb[j], c = ixb[k];
+        if (a == -1 || c == -1) return bg;
+        if (a < 0 || c < 0) return 0;
+        int sy = turned ? c : a, sx = turned ? a : c;
+        sy = sy < H ? sy : H - 1; sx = sx < W ? sx : W - 1;
+        return img.at(sy, sx);
     };
     y[((size_t)b * Ho + yo) * Wo * C + v] = cv_resample(kind, area, tx < nx ? tx : nx, ty < ny ? ty : ny, wx + ((size_t)b * Wo + xo) * nx,
                                                         wy + ((size_t)b * Ho + yo) * ny, px);
@@ -487,6 +525,39 @@ extern "C" int ssdhip_image_resize_gather_ragged_u8(const void* x, const long lo
     hipLaunchKernelGGL(resize_gather_cv_kernel<RaggedGatherSrc>, dim3((unsigned)((Wo * 3 + 255) / 256), (unsigned)Ho, (unsigned)B), dim3(256),
                        0, stream, RaggedGatherSrc{static_cast<const unsigned char*>(x), table_dev}, static_cast<unsigned char*>(y), Ho, Wo,
                        3, plan_dev, ix_dev, wx_dev, nx, iy_dev, wy_dev, ny, static_cast<const unsigned char*>(background_dev));
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+// The two gathers above for plans with quarter turns (ssdhip_sat_augment_plans[_ragged]): transposed_dev [B] swaps image b's source
+// address, index -2 reads 0.
+extern "C" int ssdhip_image_resize_gather_turn_cv_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* plan_dev,
+                                                     const int* ix_dev, const double* wx_dev, int nx, const int* iy_dev,
+                                                     const double* wy_dev, int ny, const int* transposed_dev, const void* background_dev,
+                                                     void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!x || !y || !plan_dev || !ix_dev || !wx_dev || !iy_dev || !wy_dev || !transposed_dev || !background_dev) return SSDHIP_E_BADARG;
+    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || Ho <= 0 || Ho > 65535 || Wo <= 0 || C <= 0 || C > 4 || nx < 2 || ny < 2 || nx > 64 || ny > 64)
+        return SSDHIP_E_BADARG;
+    hipLaunchKernelGGL(resize_gather_turn_cv_kernel<UniformGatherSrc>, dim3((unsigned)((Wo * C + 255) / 256), (unsigned)Ho, (unsigned)B),
+                       dim3(256), 0, stream, UniformGatherSrc{static_cast<const unsigned char*>(x), H, W, C}, static_cast<unsigned char*>(y),
+                       Ho, Wo, C, plan_dev, ix_dev, wx_dev, nx, iy_dev, wy_dev, ny, transposed_dev,
+                       static_cast<const unsigned char*>(background_dev));
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_image_resize_gather_turn_ragged_u8(const void* x, const long long* table_dev, void* y, int B, int Ho, int Wo,
+                                                         const int* plan_dev, const int* ix_dev, const double* wx_dev, int nx,
+                                                         const int* iy_dev, const double* wy_dev, int ny, const int* transposed_dev,
+                                                         const void* background_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!x || !table_dev || !y || !plan_dev || !ix_dev || !wx_dev || !iy_dev || !wy_dev || !transposed_dev || !background_dev)
+        return SSDHIP_E_BADARG;
+    if (B <= 0 || B > 65535 || Ho <= 0 || Ho > 65535 || Wo <= 0 || Wo > (1 << 24) || nx < 2 || ny < 2 || nx > 64 || ny > 64)
+        return SSDHIP_E_BADARG;
+    hipLaunchKernelGGL(resize_gather_turn_cv_kernel<RaggedGatherSrc>, dim3((unsigned)((Wo * 3 + 255) / 256), (unsigned)Ho, (unsigned)B),
+                       dim3(256), 0, stream, RaggedGatherSrc{static_cast<const unsigned char*>(x), table_dev}, static_cast<unsigned char*>(y),
+                       Ho, Wo, 3, plan_dev, ix_dev, wx_dev, nx, iy_dev, wy_dev, ny, transposed_dev,
+                       static_cast<const unsigned char*>(background_dev));
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 

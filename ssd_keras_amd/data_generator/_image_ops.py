@@ -82,16 +82,18 @@ def run_batch(images, programs):
 # ---- lazy geometry: the geometric ops of a chain recorded instead of executed ----------------------------------------------------------
 class GeoImage:
     """An image that EXISTS ONLY AS INDEX MAPS into an image resident on the device: what the geometric ops of the augmentation chain
-    (expansion / crop = a window with a background, flips = reversed slices, the final resize) do to it is recorded as two index arrays
-    -- `ys[i]` / `xs[j]` = the row / column of the original image that row i / column j of the current virtual image shows, -1 = a
-    position filled with `background` -- and executed once, for a whole batch, by `ssdhip_image_resize_gather_cv_u8`.  Quacks like the
-    (H, W, 3) uint8 array the ops expect: `shape`, `ndim`, `dtype`, slicing with plain / reversed slices."""
+    (expansion / crop = a window with a background, flips = reversed slices, rotations by quarter turns, the final resize) do to it is
+    recorded as two index arrays -- `ys[i]` / `xs[j]` = the row / column of the original image that row i / column j of the current
+    virtual image shows, -1 = a position filled with `background`, -2 = a position a rotation left black -- and executed once, for a
+    whole batch, by `ssdhip_image_resize_gather_cv_u8` (its `_turn` form when an image has rotated).  `transposed`: after a rotation
+    by 90 or 270 degrees `ys` addresses the original's COLUMNS and `xs` its rows.  Quacks like the (H, W, 3) uint8 array the ops expect:
+    `shape`, `ndim`, `dtype`, slicing with plain / reversed slices."""
 
     ndim = 3
     dtype = np.dtype(np.uint8)
 
-    def __init__(self, ys, xs, background=None, resized=None):
-        self.ys, self.xs, self.background, self.resized = ys, xs, background, resized
+    def __init__(self, ys, xs, background=None, resized=None, transposed=False):
+        self.ys, self.xs, self.background, self.resized, self.transposed = ys, xs, background, resized, bool(transposed)
 
     @classmethod
     def of(cls, height, width):
@@ -103,6 +105,11 @@ class GeoImage:
             return (self.resized[0], self.resized[1], 3)
         return (len(self.ys), len(self.xs), 3)
 
+    @property
+    def turned(self):
+        """Whether a rotation is part of the recorded geometry (the plain gather cannot execute it)."""
+        return self.transposed or bool((self.ys == -2).any() or (self.xs == -2).any())
+
     def __getitem__(self, key):
         if self.resized is not None:
             raise TypeError("a resized lazy image is final")
@@ -112,7 +119,7 @@ class GeoImage:
             raise TypeError("lazy images take row / column slices only")
         ys = self.ys[key[0]]
         xs = self.xs[key[1]] if len(key) > 1 else self.xs
-        return GeoImage(ys, xs, self.background)
+        return GeoImage(ys, xs, self.background, transposed=self.transposed)
 
     def window(self, top, left, height, width, background):
         """CropPad's window (data_generator/object_detection_2d_patch_sampling_ops.py: the patch, background where it leaves the image)."""
@@ -123,20 +130,72 @@ class GeoImage:
         xs = np.where((cols >= 0) & (cols < w), self.xs[np.clip(cols, 0, w - 1)], -1)
         bg = tuple(int(v) for v in background)
         padded = bool(top < 0 or left < 0 or top + height > h or left + width > w)     # THIS window leaves the (virtual) image
-        had = bool((self.ys < 0).any() or (self.xs < 0).any())
+        had = bool((self.ys == -1).any() or (self.xs == -1).any())
         if padded and had and self.background is not None and tuple(self.background) != bg:
             raise NotImplementedError("two paddings with different background colours cannot be composed lazily")
-        return GeoImage(ys, xs, bg if (padded or self.background is None) else self.background)
+        return GeoImage(ys, xs, bg if (padded or self.background is None) else self.background, transposed=self.transposed)
+
+    def turn(self, angle):
+        """Rotate's warpAffine (object_detection_2d_geometric_ops.Rotate: the reference's adjusted matrix, border 0) as the exact index
+        permutation it is: output pixel (row y, column x) of an H x W image reads (column, row) = (W - y, x) for 90 degrees, (W - x, H - y)
+        for 180, (y, H - x) for 270; a position outside the image is black (-2)."""
+        if self.resized is not None:
+            raise TypeError("a resized lazy image is final")
+        if (self.ys == -1).any() or (self.xs == -1).any():
+            raise NotImplementedError("a rotation after a padding cannot be composed lazily")
+        h, w = len(self.ys), len(self.xs)
+        ys_back = np.append(self.ys, -2)[h - np.arange(h)]        # position k -> what sits at h - k (h itself: outside)
+        xs_back = np.append(self.xs, -2)[w - np.arange(w)]
+        if angle == 90:
+            return GeoImage(xs_back, self.ys, self.background, transposed=not self.transposed)
+        if angle == 180:
+            return GeoImage(ys_back, xs_back, self.background, transposed=self.transposed)
+        if angle == 270:
+            return GeoImage(self.xs, ys_back, self.background, transposed=not self.transposed)
+        raise NotImplementedError("lazy images rotate by 90, 180 or 270 degrees only")
+
+    def warp(self, M, dsize, background):
+        """cv2.warpAffine on a lazy image: only Rotate's three matrices for this image's size, with their output size and a black border,
+        are index permutations (`turn`); anything else cannot be recorded."""
+        if np.any(border_value(background, 3) != 0):
+            raise NotImplementedError("lazy images take Rotate's warps (border 0) only")
+        h, w = len(self.ys), len(self.xs)
+        m = np.asarray(M, dtype=np.float64)
+        for angle in (90, 180, 270):
+            ref, size = quarter_turn_matrix(h, w, angle)
+            if m.shape == (2, 3) and np.array_equal(m, ref) and (int(dsize[0]), int(dsize[1])) == size:
+                return self.turn(angle)
+        raise NotImplementedError("lazy images take Rotate's warps (90, 180, 270 degrees about the centre) only")
 
     def resize(self, out_h, out_w, interp):
-        return GeoImage(self.ys, self.xs, self.background, resized=(int(out_h), int(out_w), int(interp)))
+        return GeoImage(self.ys, self.xs, self.background, resized=(int(out_h), int(out_w), int(interp)), transposed=self.transposed)
 
     def plan(self):
         """(kind, area, ix, wx, iy, wy) of the final resize (`resize_plan`), its tap indices composed with the index maps: a tap
-        addresses a column / row of the ORIGINAL image, or -1 = a position the expansion filled with the background colour."""
+        addresses a column / row of the ORIGINAL image (a row / column when `transposed`), or -1 = a position the expansion filled with
+        the background colour, -2 = one a rotation left black."""
         out_h, out_w, interp = self.resized
         kind, ix, wx, iy, wy, area = resize_plan(len(self.ys), len(self.xs), out_h, out_w, interp)
         return kind, area, self.xs[ix].astype(np.int32), wx, self.ys[iy].astype(np.int32), wy
+
+
+def _gather_tables(lazies, n_min):
+    """The padded per-image tables of a batch of resized GeoImages: (kinds (B, 4), ix, wx, iy, wy, background (B, 3), transposed (B,) |
+    None when no image has rotated, plans)."""
+    plans = [l.plan() for l in lazies]
+    n = max(max(pl[2].shape[1], pl[4].shape[1]) for pl in plans)
+    n = max(n_min, 1 if n <= 1 else (2 if n <= 2 else (4 if n <= 4 else (8 if n <= 8 else 16 if n <= 16 else n))))
+    b, (out_h, out_w) = len(lazies), lazies[0].resized[:2]
+    ix, wx = np.zeros((b, out_w, n), dtype=np.int32), np.zeros((b, out_w, n), dtype=np.float64)
+    iy, wy = np.zeros((b, out_h, n), dtype=np.int32), np.zeros((b, out_h, n), dtype=np.float64)
+    kinds = np.zeros((b, 4), dtype=np.int32)                      # kind, area, taps per column, taps per row
+    for k, (kind, area, sx, vx, sy, vy) in enumerate(plans):
+        ix[k, :, :sx.shape[1]], wx[k, :, :sx.shape[1]] = sx, vx
+        iy[k, :, :sy.shape[1]], wy[k, :, :sy.shape[1]] = sy, vy
+        kinds[k] = (kind, area, sx.shape[1], sy.shape[1])
+    bg = np.array([(l.background if l.background is not None else (0, 0, 0)) for l in lazies], dtype=np.uint8)
+    turned = np.array([int(l.transposed) for l in lazies], dtype=np.int32) if any(l.turned for l in lazies) else None
+    return kinds, ix, wx, iy, wy, bg, turned, plans
 
 
 def gather_batch(images, lazies):
@@ -146,18 +205,9 @@ def gather_batch(images, lazies):
     if len(sizes) != 1:
         raise ValueError("every image of a batch must end in the same size")
     out_h, out_w = sizes.pop()
-    plans = [l.plan() for l in lazies]
-    n = max(max(pl[2].shape[1], pl[4].shape[1]) for pl in plans)
-    n = 1 if n <= 1 else (2 if n <= 2 else (4 if n <= 4 else (8 if n <= 8 else 16 if n <= 16 else n)))
-    b = len(lazies)
-    ix, wx = np.zeros((b, out_w, n), dtype=np.int32), np.zeros((b, out_w, n), dtype=np.float64)
-    iy, wy = np.zeros((b, out_h, n), dtype=np.int32), np.zeros((b, out_h, n), dtype=np.float64)
-    kinds = np.zeros((b, 4), dtype=np.int32)                      # kind, area, taps per column, taps per row
-    for k, (kind, area, sx, vx, sy, vy) in enumerate(plans):
-        ix[k, :, :sx.shape[1]], wx[k, :, :sx.shape[1]] = sx, vx
-        iy[k, :, :sy.shape[1]], wy[k, :, :sy.shape[1]] = sy, vy
-        kinds[k] = (kind, area, sx.shape[1], sy.shape[1])
-    bg = np.array([(l.background if l.background is not None else (0, 0, 0)) for l in lazies], dtype=np.uint8)
+    kinds, ix, wx, iy, wy, bg, turned, _ = _gather_tables(lazies, 1)
+    if turned is not None:
+        return nat.image_resize_gather_turn_u8(images.contiguous(), None, out_h, out_w, kinds, ix, wx, iy, wy, turned, bg)
     return nat.image_resize_gather_cv_u8(images.contiguous(), out_h, out_w, kinds, ix, wx, iy, wy, bg)
 
 
@@ -232,21 +282,12 @@ def gather_batch_ragged(packed, lazies):
     if len(lazies) != len(packed):
         raise ValueError("one lazy image per image of the batch")
     out_h, out_w = sizes.pop()
-    plans = [l.plan() for l in lazies]
-    for (kind, area, sx, vx, sy, vy), (h, w, _) in zip(plans, packed.shapes):
-        if sx.max() >= w or sy.max() >= h:
+    kinds, ix, wx, iy, wy, bg, turned, plans = _gather_tables(lazies, 2)
+    for l, (kind, area, sx, vx, sy, vy), (h, w, _) in zip(lazies, plans, packed.shapes):
+        if sx.max() >= (h if l.transposed else w) or sy.max() >= (w if l.transposed else h):
             raise ValueError("the recorded geometry is not of these images")
-    n = max(max(pl[2].shape[1], pl[4].shape[1]) for pl in plans)
-    n = 2 if n <= 2 else (4 if n <= 4 else (8 if n <= 8 else 16 if n <= 16 else n))
-    b = len(lazies)
-    ix, wx = np.zeros((b, out_w, n), dtype=np.int32), np.zeros((b, out_w, n), dtype=np.float64)
-    iy, wy = np.zeros((b, out_h, n), dtype=np.int32), np.zeros((b, out_h, n), dtype=np.float64)
-    kinds = np.zeros((b, 4), dtype=np.int32)                      # kind, area, taps per column, taps per row
-    for k, (kind, area, sx, vx, sy, vy) in enumerate(plans):
-        ix[k, :, :sx.shape[1]], wx[k, :, :sx.shape[1]] = sx, vx
-        iy[k, :, :sy.shape[1]], wy[k, :, :sy.shape[1]] = sy, vy
-        kinds[k] = (kind, area, sx.shape[1], sy.shape[1])
-    bg = np.array([(l.background if l.background is not None else (0, 0, 0)) for l in lazies], dtype=np.uint8)
+    if turned is not None:
+        return nat.image_resize_gather_turn_u8(packed.data, packed.table, out_h, out_w, kinds, ix, wx, iy, wy, turned, bg)
     return nat.image_resize_gather_ragged_u8(packed.data, packed.table, out_h, out_w, kinds, ix, wx, iy, wy, bg)
 
 
@@ -509,6 +550,18 @@ def rotation_matrix_2d(center, angle, scale):
     return np.array([[a, b, (1 - a) * cx - b * cy], [-b, a, b * cx + (1 - a) * cy]], dtype=np.float64)
 
 
+def quarter_turn_matrix(height, width, angle):
+    """Rotate's adjusted matrix for a height x width image and its output size (width, height): getRotationMatrix2D about the centre, the
+    translation moved by half the change of size (object_detection_2d_geometric_ops.Rotate, the reference :693-705)."""
+    M = rotation_matrix_2d((width / 2, height / 2), angle, 1)
+    cos_angle, sin_angle = np.abs(M[0, 0]), np.abs(M[0, 1])
+    width_new = int(height * sin_angle + width * cos_angle)
+    height_new = int(height * cos_angle + width * sin_angle)
+    M[1, 2] += (height_new - height) / 2
+    M[0, 2] += (width_new - width) / 2
+    return M, (width_new, height_new)
+
+
 def invert_affine(M):
     """warpAffine's in-place inversion of the (float64-widened) forward matrix -> the six coefficients of the inverse map."""
     m = [float(v) for v in np.asarray(M, dtype=np.float64).reshape(6)]
@@ -638,10 +691,10 @@ def warp_batch(images, lazies):
 def warp_affine(image, M, dsize, background=0):
     """cv2.warpAffine(image, M, dsize=(width, height), borderMode=BORDER_CONSTANT, borderValue=background) for uint8 images: a NumPy
     (H, W[, C]) image (one upload, one launch, one download) or a `WarpImage` (recorded)."""
-    if isinstance(image, WarpImage):
+    if isinstance(image, (WarpImage, GeoImage)):
         return image.warp(M, dsize, background)
     if not isinstance(image, np.ndarray):
-        raise TypeError("warp_affine takes a NumPy image or a lazy WarpImage")
+        raise TypeError("warp_affine takes a NumPy image or a lazy WarpImage / GeoImage")
     if image.dtype != np.uint8:
         raise TypeError("warp_affine takes uint8 images")
     src = image if image.ndim == 3 else image[:, :, None]

@@ -13,6 +13,8 @@ chains read too).
   * `[DataAugmentationConstantInputSize]` on images of one size: `DataAugmentationConstantInputSize.augment_batch`;
   * `[DataAugmentationVariableInputSize]`: like the first item, the images (any sizes) as ONE ragged batch through
     `DataAugmentationVariableInputSize.augment_batch` on the list (110 ms -> 2.1 ms per batch of 32, profiles/variable_chain_device.json);
+  * `[DataAugmentationSatellite]`: the same for the chain with vertical flips and rotations by quarter turns
+    (`DataAugmentationSatellite.augment_batch`; np.random AND Python's `random` end where the per-image loop leaves them);
   * anything else: the reference's per-image loop over the package's transforms.
 Every path gives the per-image loop's pixels, labels, inverters and final `np.random` state.  Images are decoded by PIL on the host, as in
 the reference.  HDF5 datasets are not supported (h5py is not a dependency of this package); their parameter and methods raise
@@ -337,6 +339,7 @@ class DataGenerator:
         """Which batch path a transformation list takes (see the module docstring); None = the per-image loop."""
         from .data_augmentation_chain_constant_input_size import DataAugmentationConstantInputSize
         from .data_augmentation_chain_original_ssd import SSDDataAugmentation
+        from .data_augmentation_chain_satellite import DataAugmentationSatellite
         from .data_augmentation_chain_variable_input_size import DataAugmentationVariableInputSize
         from .object_detection_2d_geometric_ops import Resize
         from .object_detection_2d_patch_sampling_ops import RandomPadFixedAR
@@ -357,6 +360,8 @@ class DataGenerator:
             return 'constant'
         if kinds == [DataAugmentationVariableInputSize]:
             return 'variable'
+        if kinds == [DataAugmentationSatellite]:
+            return 'satellite'
         return None
 
     def _transform_batch(self, path, transformations, images, labels, want_inverters):
@@ -364,7 +369,7 @@ class DataGenerator:
         uint8 batch, labels or None, inverters per item)."""
         import torch
         from . import _image_ops as iop
-        if path in ('ssd', 'variable'):
+        if path in ('ssd', 'variable', 'satellite'):
             chain = transformations[0]
             to_three = (chain.photometric_distortions if path == 'ssd' else chain).convert_to_3_channels
             three = [im if (im.ndim == 3 and im.shape[2] == 3) else to_three(im) for im in images]
