@@ -744,6 +744,31 @@ int ssdhip_ssd7_head_wgrad_nhwc_bf16(const void* x, const void* dy, void* dw_con
  * ssdhip_image_lut_u8    y = table[x] on the channels of channel_mask, x elsewhere (cv2.LUT :359 / the equalisation table). */
 int ssdhip_image_program(const void* x, int in_dtype, void* y, int out_dtype, int n_images, long long pixels_per_image,
                          const int* ops_dev, const double* args_dev, void* stream);
+/* Programs with look-up tables: cv2.LUT (Gamma, :359) and cv2.equalizeHist (:407) as steps of a program, for a whole batch.
+ *     11 lut: on a uint8 state v[c] = luts[i][slot][v[c]] for the channels c of a mask; arg = slot + 4 mask, slot 0 .. 3, mask 1 .. 7
+ *   luts_dev [n_images][4][256] uint8 (dword aligned).
+ * ssdhip_image_program_lut, ssdhip_image_program_ragged_lut_u8   ssdhip_image_program / ssdhip_image_program_ragged_u8 with the tables;
+ *   the two old exports are these with luts_dev = NULL.  Without tables, or on a float state, step 11 changes nothing.
+ * ssdhip_image_program_check   the programs live on the device and the launching exports only enqueue, so a batch's programs are
+ *   checked on the HOST, before their upload: ops_host / args_host [n_images][16]; SSDHIP_E_BADARG for an unknown op code, for op 11
+ *   without tables (have_luts == 0: what the old exports take), on a state that is not uint8, or with an argument that is not
+ *   slot + 4 mask.  The package's launchers call it for every program that comes from the host.
+ * ssdhip_image_program_hist_u8   image i runs its program up to, not including, step stop[i] (stop[i] < 0: skipped, its row stays 0) and
+ *   channel channel[i] (0 .. 2) of the uint8 state it reaches is counted into hist[i][256]; nothing else is written.  table_dev: the
+ *   ragged batch's table (below), `pixels` its largest H W; table_dev NULL: x is [B][pixels][3].  hist is zeroed by a kernel of the
+ *   export; workgroups count in LDS and merge with integer atomicAdd (the result does not depend on the order).
+ * ssdhip_image_equalize_tables   hist [B][256] (16-byte aligned) -> luts[i][slot[i]] = cv2.equalizeHist's table (slot[i] < 0: skipped):
+ *   bins up to the first occupied one -> 0, the others round-to-nearest-even of float32(count behind the first occupied bin) times the
+ *   float32 255 / (total - hist[first]), clamped; a plane with one occupied bin gets the identity.  One wave per image. */
+int ssdhip_image_program_check(const int* ops_host, const double* args_host, int n_images, int in_dtype, int have_luts);
+int ssdhip_image_program_lut(const void* x, int in_dtype, void* y, int out_dtype, int n_images, long long pixels_per_image,
+                             const int* ops_dev, const double* args_dev, const void* luts_dev, void* stream);
+int ssdhip_image_program_ragged_lut_u8(const void* x, const long long* table_dev, void* y, int B, long long max_pixels, const int* ops_dev,
+                                       const double* args_dev, const void* luts_dev, void* stream);
+int ssdhip_image_program_hist_u8(const void* x, const long long* table_dev, int B, long long pixels, const int* ops_dev,
+                                 const double* args_dev, const void* luts_dev, const int* stop_dev, const int* channel_dev,
+                                 unsigned int* hist_dev, void* stream);
+int ssdhip_image_equalize_tables(const unsigned int* hist_dev, const int* slot_dev, void* luts_dev, int B, void* stream);
 /* cv2.resize on 8-bit images with OpenCV's own arithmetic (round 6; data_generator/object_detection_2d_geometric_ops.py:70-72 calls
  * cv2.resize -> imgproc/resize.cpp): `kind` 0 nearest, 1 linear (11-bit fixed-point coefficients, the two-stage vertical rounding),
  * 2 cubic / Lanczos-4 (fixed point, (sum + 2^21) >> 22), 3 area (float32 tables, cvRound), 4 fast area (block sum * (1.f / area)),

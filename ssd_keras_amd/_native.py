@@ -243,6 +243,11 @@ SIGNATURES = {
     "ssdhip_sat_augment_plans_ragged": (_I, [_P, _P] + [_I] * 4 + [_P] * 7),
     "ssdhip_image_resize_gather_turn_cv_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 3 + [_I, _P, _P, _I, _P, _P, _P]),
     "ssdhip_image_resize_gather_turn_ragged_u8": (_I, [_P, _P, _P] + [_I] * 3 + [_P] * 3 + [_I, _P, _P, _I, _P, _P, _P]),
+    "ssdhip_image_program_check": (_I, [_P, _P, _I, _I, _I]),
+    "ssdhip_image_program_lut": (_I, [_P, _I, _P, _I, _I, _LL] + [_P] * 4),
+    "ssdhip_image_program_ragged_lut_u8": (_I, [_P, _P, _P, _I, _LL] + [_P] * 4),
+    "ssdhip_image_program_hist_u8": (_I, [_P, _P, _I, _LL] + [_P] * 7),
+    "ssdhip_image_equalize_tables": (_I, [_P, _P, _P, _I, _P]),
 }
 
 
@@ -2340,8 +2345,37 @@ def box_filter(boxes, box_image, image_hw, check_overlap, check_min_area, check_
 # ---- image half of the augmentation (csrc/ssdhip_image.hip) ----------------------------------------------------------------------
 IMG_U8, IMG_F32, IMG_F64 = 0, 1, 2
 IMG_OPS = {"end": 0, "to_f32": 1, "to_u8": 2, "brightness": 3, "contrast": 4, "saturation": 5, "hue": 6, "rgb2hsv": 7, "hsv2rgb": 8,
-           "rgb2gray": 9, "swap": 10}
+           "rgb2gray": 9, "swap": 10, "lut": 11}
 IMG_PROG = 16
+IMG_LUT_SLOTS = 4                                            # look-up tables per image: luts (B, 4, 256) uint8
+
+
+def image_program_check(ops, args, in_code, have_luts):
+    """ssdhip_image_program_check on HOST programs (ops (B, 16) int32, args (B, 16) float64): raises for an unknown op code and for a
+    `lut` step without tables, on a state that is not uint8, or with a malformed argument."""
+    ops = np.ascontiguousarray(ops, dtype=np.int32)
+    args = np.ascontiguousarray(args, dtype=np.float64)
+    if ops.ndim != 2 or ops.shape[1] != IMG_PROG or args.shape != ops.shape:
+        raise SsdHipError("ops / args must be (B, %d)" % IMG_PROG)
+    check(load().ssdhip_image_program_check(ops.ctypes.data, args.ctypes.data, int(ops.shape[0]), int(in_code), int(bool(have_luts))),
+          "ssdhip_image_program_check")
+
+
+def _programs_to_device(ops, args, device, in_code, have_luts):
+    """Programs from the host are checked (image_program_check) and uploaded; programs already on the device (the decide exports write
+    them) pass as they are."""
+    torch = _torch()
+    if isinstance(ops, np.ndarray):
+        image_program_check(ops, args, in_code, have_luts)
+    return (to_device(ops, device=device, dtype=torch.int32).contiguous(), to_device(args, device=device, dtype=torch.float64).contiguous())
+
+
+def _luts_on_device(luts, b, device):
+    torch = _torch()
+    require_cuda(luts, "luts")
+    if luts.dtype != torch.uint8 or tuple(luts.shape) != (b, IMG_LUT_SLOTS, 256) or luts.device != device:
+        raise SsdHipError("luts must be a (%d, %d, 256) uint8 CUDA tensor on the images' device" % (b, IMG_LUT_SLOTS))
+    return luts
 
 
 def _img_dtype_code(t):
@@ -2352,22 +2386,77 @@ def _img_dtype_code(t):
     return code
 
 
-def image_program(images, ops, args, out_dtype):
+def image_program(images, ops, args, out_dtype, luts=None):
     """Run per-image pointwise programs (ssdhip_image_program): images (B, H, W, 3) CUDA uint8 | float32 | float64 contiguous; ops (B, 16) int32,
-    args (B, 16) float64 (host arrays or CUDA tensors); out_dtype a torch dtype (what the programs end in).  Returns (B, H, W, 3)."""
+    args (B, 16) float64 (host arrays or CUDA tensors); out_dtype a torch dtype (what the programs end in).  Returns (B, H, W, 3).
+    `luts` ((B, 4, 256) uint8 CUDA tensor): the tables of the programs' `lut` steps (ssdhip_image_program_lut)."""
     torch = _torch()
     require_cuda(images, "images")
     if images.dim() != 4 or images.shape[3] != 3 or not images.is_contiguous():
         raise SsdHipError("images must be a contiguous (B, H, W, 3) tensor")
     b, h, w, _ = images.shape
-    ops = to_device(ops, device=images.device, dtype=torch.int32).contiguous()
-    args = to_device(args, device=images.device, dtype=torch.float64).contiguous()
+    in_code = _img_dtype_code(images)
+    ops, args = _programs_to_device(ops, args, images.device, in_code, luts is not None)
     if tuple(ops.shape) != (b, IMG_PROG) or tuple(args.shape) != (b, IMG_PROG):
         raise SsdHipError("ops / args must be (%d, %d)" % (b, IMG_PROG))
     out = torch.empty((b, h, w, 3), dtype=out_dtype, device=images.device)
-    in_code = _img_dtype_code(images)
+    if luts is not None:
+        launch("ssdhip_image_program_lut", images.device, _ptr(images), in_code, _ptr(out), _img_dtype_code(out), b, h * w, _ptr(ops),
+               _ptr(args), _ptr(_luts_on_device(luts, b, images.device)))
+        return out
     launch("ssdhip_image_program", images.device, _ptr(images), in_code, _ptr(out), _img_dtype_code(out), b, h * w, _ptr(ops), _ptr(args))
     return out
+
+
+def image_program_hist_u8(data, table, pixels, ops, args, luts, stop, channel, hist=None):
+    """ssdhip_image_program_hist_u8: image i's program up to step stop[i] (< 0: skipped), channel channel[i] of the uint8 state counted into
+    row i of the returned (B, 256) int32 CUDA tensor (`hist`: a buffer to reuse; the export zeroes it).  data / table: a ragged batch
+    and `pixels` its largest H W, or table None: data a (B, H, W, 3) uint8 CUDA batch.  ops / args as image_program's, luts or None."""
+    torch = _torch()
+    require_cuda(data, "data")
+    if data.dtype != torch.uint8:
+        raise SsdHipError("histograms are taken of uint8 images")
+    dev = data.device
+    if table is None:
+        if data.dim() != 4 or data.shape[3] != 3:
+            raise SsdHipError("images must be a contiguous (B, H, W, 3) uint8 tensor")
+        b, pixels = int(data.shape[0]), int(data.shape[1]) * int(data.shape[2])
+    else:
+        require_cuda(table, "table")
+        if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4:
+            raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
+        b = int(table.shape[0])
+    ops, args = _programs_to_device(ops, args, dev, IMG_U8, luts is not None)
+    if tuple(ops.shape) != (b, IMG_PROG) or tuple(args.shape) != (b, IMG_PROG):
+        raise SsdHipError("ops / args must be (%d, %d)" % (b, IMG_PROG))
+    if isinstance(stop, np.ndarray) and (stop.shape != (b,) or (stop > IMG_PROG).any()):
+        raise SsdHipError("stop must be (%d,) step numbers" % b)
+    if isinstance(channel, np.ndarray) and (channel.shape != (b,) or (channel < 0).any() or (channel > 2).any()):
+        raise SsdHipError("channel must be (%d,) values out of 0, 1, 2" % b)
+    stop = to_device(stop, device=dev, dtype=torch.int32).contiguous()
+    channel = to_device(channel, device=dev, dtype=torch.int32).contiguous()
+    if hist is None:
+        hist = torch.empty((b, 256), dtype=torch.int32, device=dev)
+    elif hist.dtype != torch.int32 or tuple(hist.shape) != (b, 256) or not hist.is_contiguous() or hist.device != dev:
+        raise SsdHipError("hist must be a contiguous (%d, 256) int32 CUDA tensor" % b)
+    launch("ssdhip_image_program_hist_u8", dev, _ptr(data), None if table is None else _ptr(table), b, int(pixels), _ptr(ops), _ptr(args),
+           None if luts is None else _ptr(_luts_on_device(luts, b, dev)), _ptr(stop), _ptr(channel), _ptr(hist))
+    return hist
+
+
+def image_equalize_tables(hist, slot, luts):
+    """ssdhip_image_equalize_tables: hist (B, 256) int32 CUDA -> luts[i][slot[i]] = cv2.equalizeHist's table, in place (slot[i] < 0: image i
+    is skipped); luts (B, 4, 256) uint8 CUDA."""
+    torch = _torch()
+    require_cuda(hist, "hist")
+    b = int(hist.shape[0])
+    if hist.dtype != torch.int32 or tuple(hist.shape) != (b, 256):
+        raise SsdHipError("hist must be a (B, 256) int32 CUDA tensor")
+    if isinstance(slot, np.ndarray) and (slot.shape != (b,) or (slot >= IMG_LUT_SLOTS).any()):
+        raise SsdHipError("slot must be (%d,) values below %d" % (b, IMG_LUT_SLOTS))
+    slot = to_device(slot, device=hist.device, dtype=torch.int32).contiguous()
+    launch("ssdhip_image_equalize_tables", hist.device, _ptr(hist), _ptr(slot), _ptr(_luts_on_device(luts, b, hist.device)), b)
+    return luts
 
 
 def image_resize_cv_u8(images, out_h, out_w, kind, area, ix, wx, iy, wy):
@@ -2451,20 +2540,24 @@ def image_resize_gather_ragged_u8(data, table, out_h, out_w, plans, ix, wx, iy, 
     return out
 
 
-def image_program_ragged_u8(data, table, max_pixels, ops, args):
+def image_program_ragged_u8(data, table, max_pixels, ops, args, luts=None):
     """ssdhip_image_program_ragged_u8: per-image uint8 -> uint8 programs on a ragged batch of 3-channel images (data, table as
-    image_resize_gather_ragged_u8's); ops (B, 16) int32, args (B, 16) float64.  Returns a buffer with data's layout."""
+    image_resize_gather_ragged_u8's); ops (B, 16) int32, args (B, 16) float64.  Returns a buffer with data's layout.  `luts` ((B, 4, 256)
+    uint8 CUDA tensor): the tables of the programs' `lut` steps (ssdhip_image_program_ragged_lut_u8)."""
     torch = _torch()
     require_cuda(data, "data")
     require_cuda(table, "table")
     if data.dtype != torch.uint8 or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4:
         raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
     b, dev = int(table.shape[0]), data.device
-    ops = to_device(ops, device=dev, dtype=torch.int32).contiguous()
-    args = to_device(args, device=dev, dtype=torch.float64).contiguous()
+    ops, args = _programs_to_device(ops, args, dev, IMG_U8, luts is not None)
     if tuple(ops.shape) != (b, IMG_PROG) or tuple(args.shape) != (b, IMG_PROG):
         raise SsdHipError("ops / args must be (%d, %d)" % (b, IMG_PROG))
     out = torch.empty_like(data)
+    if luts is not None:
+        launch("ssdhip_image_program_ragged_lut_u8", dev, _ptr(data), _ptr(table), _ptr(out), b, int(max_pixels), _ptr(ops), _ptr(args),
+               _ptr(_luts_on_device(luts, b, dev)))
+        return out
     launch("ssdhip_image_program_ragged_u8", dev, _ptr(data), _ptr(table), _ptr(out), b, int(max_pixels), _ptr(ops), _ptr(args))
     return out
 

@@ -13,7 +13,10 @@
 //                            and weights per output column / row (one plan for the batch, or one per image with the augmentation
 //                            chain's expansion / crop / flip composed in; resize_gather_turn_cv_kernel: the same for plans that
 //                            hold a rotation by quarter turns -- a transposed bit per image swaps the source address);
-//   * hist_u8_kernel / lut_u8_kernel   cv2.equalizeHist (histogram on the device, the 256-entry table on the host) and cv2.LUT.
+//   * hist_u8_kernel / lut_u8_kernel   cv2.equalizeHist (histogram on the device, the 256-entry table on the host) and cv2.LUT, one image
+//                            at a time; for a batch both are steps of the programs: OP_LUT reads one of four tables per image,
+//                            program_hist_u8_kernel counts a channel of the state a program reaches at a given step and
+//                            equalize_tables_kernel turns the histograms into tables, one wave per image -- no host round trip.
 // Arithmetic is written operation by operation (-ffp-contract=off): bit-identical to the NumPy restatement in oracle/np_image.py.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,8 +28,9 @@ namespace ssdhip {
 
 enum { IMG_U8 = 0, IMG_F32 = 1, IMG_F64 = 2 };
 enum { OP_END = 0, OP_TO_F32 = 1, OP_TO_U8 = 2, OP_BRIGHTNESS = 3, OP_CONTRAST = 4, OP_SATURATION = 5, OP_HUE = 6, OP_RGB2HSV = 7,
-       OP_HSV2RGB = 8, OP_RGB2GRAY = 9, OP_SWAP = 10 };
+       OP_HSV2RGB = 8, OP_RGB2GRAY = 9, OP_SWAP = 10, OP_LUT = 11 };
 constexpr int IMG_PROG = 16;
+constexpr int IMG_LUT_SLOTS = 4;                             // tables per image: luts [n_images][IMG_LUT_SLOTS][256] uint8
 
 __device__ __forceinline__ double img_clip255(double v) { return v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v); }
 __device__ __forceinline__ float img_clip255f(float v) { return v < 0.f ? 0.f : (v > 255.f ? 255.f : v); }
@@ -95,9 +99,12 @@ __device__ __forceinline__ void img_rgb2hsv_f32(double (&c)[3]) {
 }
 
 // One program step on N pixels (the same step for all of them: a program is per image).  `tag` = the dtype the reference's array has at
-// this point of the chain; arithmetic per dtype as NumPy / OpenCV do it (see the file header).
+// this point of the chain; arithmetic per dtype as NumPy / OpenCV do it (see the file header).  `lut`: the image's IMG_LUT_SLOTS tables
+// (in LDS or in global memory), or null: OP_LUT then leaves the pixel alone, as it does on a float state -- ssdhip_image_program_check
+// refuses both while the program is still on the host.
 template <int N>
-__device__ __forceinline__ void img_apply(double (&px)[N][3], int& tag, const int o, const double a, const int* sdiv, const int* hdiv) {
+__device__ __forceinline__ void img_apply(double (&px)[N][3], int& tag, const int o, const double a, const int* sdiv, const int* hdiv,
+                                          const unsigned char* lut = nullptr) {
 #pragma unroll
     for (int n = 0; n < N; ++n) {
         double (&c)[3] = px[n];
@@ -157,6 +164,14 @@ __device__ __forceinline__ void img_apply(double (&px)[N][3], int& tag, const in
             const int code = (int)a;
             const double t0 = c[code & 3], t1 = c[(code >> 2) & 3], t2 = c[(code >> 4) & 3];
             c[0] = t0; c[1] = t1; c[2] = t2;
+        } else if (o == OP_LUT) {                                    // cv2.LUT: v = table[v]; argument = slot + 4 * channel mask
+            if (lut && tag == IMG_U8) {
+                const int code = (int)a;
+                const unsigned char* t = lut + (code & (IMG_LUT_SLOTS - 1)) * 256;
+#pragma unroll
+                for (int q = 0; q < 3; ++q)
+                    if ((code >> (2 + q)) & 1) c[q] = (double)t[(int)c[q] & 255];
+            }
         }
     }
     // the dtype after the step (the same for every pixel)
@@ -167,10 +182,12 @@ __device__ __forceinline__ void img_apply(double (&px)[N][3], int& tag, const in
 
 // x: [n_images][pixels][3] uint8, float32 or float64; y: uint8 / float32 / float64 as out_tag says; ops / args: [n_images][IMG_PROG].
 __global__ __launch_bounds__(256) void pixel_program_kernel(const void* __restrict__ x, int in_tag, void* __restrict__ y, int out_tag,
-                                                            long long pixels, const int* __restrict__ ops, const double* __restrict__ args) {
+                                                            long long pixels, const int* __restrict__ ops, const double* __restrict__ args,
+                                                            const unsigned char* __restrict__ luts) {
     const int img = blockIdx.y;
     const int* op = ops + (size_t)img * IMG_PROG;
     const double* arg = args + (size_t)img * IMG_PROG;
+    const unsigned char* lut = luts ? luts + (size_t)img * IMG_LUT_SLOTS * 256 : nullptr;
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (long long)gridDim.x * 256) {
         const size_t e = ((size_t)img * pixels + p) * 3;
         double c[3];
@@ -189,7 +206,7 @@ __global__ __launch_bounds__(256) void pixel_program_kernel(const void* __restri
         for (int k = 0; k < IMG_PROG; ++k) {
             const int o = op[k];
             if (o == OP_END) break;
-            img_apply<1>(px, tag, o, arg[k], nullptr, nullptr);
+            img_apply<1>(px, tag, o, arg[k], nullptr, nullptr, lut);
         }
         c[0] = px[0][0]; c[1] = px[0][1]; c[2] = px[0][2];
         if (out_tag == IMG_U8) {
@@ -223,15 +240,20 @@ struct RaggedImages {
 // a wave moves 768 contiguous bytes per load / store instruction instead of 64 single bytes at a 3-byte stride; every program step is
 // decoded once for the four pixels; OpenCV's two 8-bit HSV division tables sit in LDS (built once per workgroup) instead of two integer
 // divisions per pixel.  Same arithmetic, same results as pixel_program_kernel.  The last count % 4 pixels of an image (ragged batches
-// only: the uniform form is launched for pixels % 4 == 0) take one work item each, byte by byte.
+// only: the uniform form is launched for pixels % 4 == 0) take one work item each, byte by byte.  `luts` (or null): the image's four
+// tables come into LDS once per workgroup, one dword per thread.
 template <class Imgs>
 __global__ __launch_bounds__(256) void pixel_program_u8x4_kernel(const unsigned char* __restrict__ x, unsigned char* __restrict__ y, Imgs imgs,
-                                                                 const int* __restrict__ ops, const double* __restrict__ args) {
+                                                                 const int* __restrict__ ops, const double* __restrict__ args,
+                                                                 const unsigned char* __restrict__ luts) {
     __shared__ int sdiv[256], hdiv[256];
+    __shared__ unsigned int slut[IMG_LUT_SLOTS * 64];
+    const int img = blockIdx.y;
     sdiv[threadIdx.x] = img_div_table(255 << 12, (int)threadIdx.x, 1);
     hdiv[threadIdx.x] = img_div_table(180 << 12, (int)threadIdx.x, 6);
+    if (luts) slut[threadIdx.x] = reinterpret_cast<const unsigned int*>(luts)[(size_t)img * IMG_LUT_SLOTS * 64 + threadIdx.x];
     __syncthreads();
-    const int img = blockIdx.y;
+    const unsigned char* lut = luts ? reinterpret_cast<const unsigned char*>(slut) : nullptr;
     const int* op = ops + (size_t)img * IMG_PROG;
     const double* arg = args + (size_t)img * IMG_PROG;
     const long long pixels = imgs.count(img), off = imgs.offset(img);
@@ -246,7 +268,7 @@ __global__ __launch_bounds__(256) void pixel_program_u8x4_kernel(const unsigned 
             for (int k = 0; k < IMG_PROG; ++k) {
                 const int o = op[k];
                 if (o == OP_END) break;
-                img_apply<1>(px, tag, o, arg[k], sdiv, hdiv);
+                img_apply<1>(px, tag, o, arg[k], sdiv, hdiv, lut);
             }
             y[off + e] = (unsigned char)px[0][0]; y[off + e + 1] = (unsigned char)px[0][1]; y[off + e + 2] = (unsigned char)px[0][2];
             continue;
@@ -262,7 +284,7 @@ __global__ __launch_bounds__(256) void pixel_program_u8x4_kernel(const unsigned 
         for (int k = 0; k < IMG_PROG; ++k) {
             const int o = op[k];
             if (o == OP_END) break;
-            img_apply<4>(px, tag, o, arg[k], sdiv, hdiv);
+            img_apply<4>(px, tag, o, arg[k], sdiv, hdiv, lut);
         }
         unsigned int b[12];
 #pragma unroll
@@ -457,6 +479,112 @@ __global__ __launch_bounds__(256) void lut_u8_kernel(const unsigned char* __rest
     }
 }
 
+// cv2.equalizeHist's first half INSIDE a program: image i runs its program up to, not including, step stop[i] and channel channel[i] of
+// the uint8 state it reaches is counted into hist[i][256]; stop[i] < 0 = the image takes no part (its row keeps the zeros of the export's
+// zero-fill).  Nothing else is written: the half-distorted image never exists in memory.  Pixels are read as pixel_program_u8x4_kernel
+// reads them (N = 4: twelve bytes = three dwords per thread and trip, the last count % 4 pixels byte by byte) or, for a uniform batch
+// whose images do not start on dwords, one pixel per thread (N = 1).  A workgroup counts into its own 256 bins in LDS (ds_add_u32) and
+// adds the occupied ones to the image's row with one global atomicAdd each: sums of integers, the same in any order.
+template <class Imgs, int N>
+__global__ __launch_bounds__(256) void program_hist_u8_kernel(const unsigned char* __restrict__ x, Imgs imgs, const int* __restrict__ ops,
+                                                              const double* __restrict__ args, const unsigned char* __restrict__ luts,
+                                                              const int* __restrict__ stop, const int* __restrict__ channel,
+                                                              unsigned int* __restrict__ hist) {
+    const int img = blockIdx.y;
+    int n_steps = stop[img];
+    if (n_steps < 0) return;                                            // the same for the whole workgroup, in front of every barrier
+    n_steps = n_steps < IMG_PROG ? n_steps : IMG_PROG;
+    __shared__ int sdiv[256], hdiv[256];
+    __shared__ unsigned int slut[IMG_LUT_SLOTS * 64];
+    __shared__ unsigned int h[256];
+    sdiv[threadIdx.x] = img_div_table(255 << 12, (int)threadIdx.x, 1);
+    hdiv[threadIdx.x] = img_div_table(180 << 12, (int)threadIdx.x, 6);
+    if (luts) slut[threadIdx.x] = reinterpret_cast<const unsigned int*>(luts)[(size_t)img * IMG_LUT_SLOTS * 64 + threadIdx.x];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const unsigned char* lut = luts ? reinterpret_cast<const unsigned char*>(slut) : nullptr;
+    const int* op = ops + (size_t)img * IMG_PROG;
+    const double* arg = args + (size_t)img * IMG_PROG;
+    const int ch = channel[img];
+    const long long pixels = imgs.count(img), off = imgs.offset(img);
+    const long long groups = pixels / N, items = groups + (pixels - groups * N);
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < items; g += (long long)gridDim.x * 256) {
+        if (N == 1 || g >= groups) {                                     // one pixel
+            const size_t e = (size_t)(N == 1 ? g : groups * N + (g - groups)) * 3;
+            double px[1][3] = {{(double)x[off + e], (double)x[off + e + 1], (double)x[off + e + 2]}};
+            int tag = IMG_U8;
+            for (int k = 0; k < n_steps; ++k) {
+                const int o = op[k];
+                if (o == OP_END) break;
+                img_apply<1>(px, tag, o, arg[k], sdiv, hdiv, lut);
+            }
+            atomicAdd(&h[(int)(ch == 0 ? px[0][0] : (ch == 1 ? px[0][1] : px[0][2])) & 255], 1u);
+            continue;
+        }
+        const unsigned int* xw = reinterpret_cast<const unsigned int*>(x + off);
+        const size_t e = (size_t)g * 3;
+        const unsigned int w0 = xw[e], w1 = xw[e + 1], w2 = xw[e + 2];
+        double px[4][3];
+        px[0][0] = w0 & 255u; px[0][1] = (w0 >> 8) & 255u; px[0][2] = (w0 >> 16) & 255u;
+        px[1][0] = w0 >> 24; px[1][1] = w1 & 255u; px[1][2] = (w1 >> 8) & 255u;
+        px[2][0] = (w1 >> 16) & 255u; px[2][1] = w1 >> 24; px[2][2] = w2 & 255u;
+        px[3][0] = (w2 >> 8) & 255u; px[3][1] = (w2 >> 16) & 255u; px[3][2] = w2 >> 24;
+        int tag = IMG_U8;
+        for (int k = 0; k < n_steps; ++k) {
+            const int o = op[k];
+            if (o == OP_END) break;
+            img_apply<4>(px, tag, o, arg[k], sdiv, hdiv, lut);
+        }
+#pragma unroll
+        for (int n = 0; n < 4; ++n) atomicAdd(&h[(int)(ch == 0 ? px[n][0] : (ch == 1 ? px[n][1] : px[n][2])) & 255], 1u);
+    }
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&hist[(size_t)img * 256 + threadIdx.x], h[threadIdx.x]);
+}
+
+// cv2.equalizeHist's second half for a batch: hist [B][256] -> luts[i][slot[i]][256] (slot[i] < 0: image i is skipped), the rule of
+// data_generator/_image_ops.equalize_table: bins up to the first occupied one -> 0, the others -> the count of the pixels in the bins
+// behind the first occupied one up to theirs, times the float32 scale 255.f / (total - hist[first]), float32 product, rounded to nearest
+// even, clamped; one occupied bin (or none): the identity.  ONE WAVE per image: lane l holds bins 4 l .. 4 l + 3, a shuffle scan over
+// the lanes' sums gives every bin its cumulative count, and each lane stores its four table bytes as one dword.
+__global__ __launch_bounds__(64) void equalize_tables_kernel(const unsigned int* __restrict__ hist, const int* __restrict__ slot,
+                                                             unsigned char* __restrict__ luts) {
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const int s = slot[img];
+    if (s < 0 || s >= IMG_LUT_SLOTS) return;
+    const uint4 hv = reinterpret_cast<const uint4*>(hist + (size_t)img * 256)[lane];
+    const u64 hb[4] = {hv.x, hv.y, hv.z, hv.w};
+    const u64 mine = hb[0] + hb[1] + hb[2] + hb[3];
+    u64 incl = mine;                                                    // inclusive scan of the lanes' sums
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 t = __shfl_up(incl, d);
+        if (lane >= d) incl += t;
+    }
+    const u64 total = __shfl(incl, 63);
+    int first = hv.x ? 4 * lane : (hv.y ? 4 * lane + 1 : (hv.z ? 4 * lane + 2 : (hv.w ? 4 * lane + 3 : 256)));
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) first = min(first, __shfl_xor(first, d));
+    const int fq = first & 3;
+    const u64 h_first = __shfl(fq == 0 ? hb[0] : (fq == 1 ? hb[1] : (fq == 2 ? hb[2] : hb[3])), (first >> 2) & 63);
+    unsigned int packed = 0u;
+    if (first == 256 || h_first == total) {                             // a constant plane is left alone
+#pragma unroll
+        for (int j = 0; j < 4; ++j) packed |= (unsigned int)(4 * lane + j) << (8 * j);
+    } else {
+        const float scale = 255.f / (float)(total - h_first);
+        u64 cum = incl - mine;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cum += hb[j];
+            const u64 below = (4 * lane + j <= first) ? 0ull : cum - h_first;
+            const float r = rintf((float)below * scale);
+            packed |= (unsigned int)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r)) << (8 * j);
+        }
+    }
+    reinterpret_cast<unsigned int*>(luts + ((size_t)img * IMG_LUT_SLOTS + s) * 256)[lane] = packed;
+}
+
 }  // namespace ssdhip
 
 using namespace ssdhip;
@@ -468,20 +596,48 @@ static unsigned img_blocks(long long work, unsigned cap) {
     return (unsigned)b;
 }
 
-extern "C" int ssdhip_image_program(const void* x, int in_dtype, void* y, int out_dtype, int n_images, long long pixels_per_image,
-                                    const int* ops_dev, const double* args_dev, void* stream_) {
+// The check of a batch's programs while they are still on the HOST (the launching exports get them on the device and only enqueue):
+// every op code known; OP_LUT only with tables (have_luts), on a uint8 state, with slot + 4 * mask, mask 1 .. 7.
+extern "C" int ssdhip_image_program_check(const int* ops_host, const double* args_host, int n_images, int in_dtype, int have_luts) {
+    if (!ops_host || !args_host || n_images <= 0 || in_dtype < IMG_U8 || in_dtype > IMG_F64) return SSDHIP_E_BADARG;
+    for (int i = 0; i < n_images; ++i) {
+        int tag = in_dtype;
+        for (int k = 0; k < IMG_PROG; ++k) {
+            const int o = ops_host[(size_t)i * IMG_PROG + k];
+            if (o == OP_END) break;
+            if (o < OP_END || o > OP_LUT) return SSDHIP_E_BADARG;
+            if (o == OP_LUT) {
+                const double a = args_host[(size_t)i * IMG_PROG + k];
+                if (!have_luts || tag != IMG_U8 || !(a >= 4.0 && a <= 31.0) || a != (double)(int)a) return SSDHIP_E_BADARG;
+            }
+            if (o == OP_TO_F32) tag = IMG_F32;
+            else if (o == OP_TO_U8) tag = IMG_U8;
+            else if ((o == OP_BRIGHTNESS || o == OP_CONTRAST) && tag != IMG_F32) tag = IMG_F64;
+        }
+    }
+    return SSDHIP_OK;
+}
+
+extern "C" int ssdhip_image_program_lut(const void* x, int in_dtype, void* y, int out_dtype, int n_images, long long pixels_per_image,
+                                        const int* ops_dev, const double* args_dev, const void* luts_dev, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!x || !y || !ops_dev || !args_dev || n_images <= 0 || n_images > 65535 || pixels_per_image <= 0) return SSDHIP_E_BADARG;
-    if (in_dtype < IMG_U8 || in_dtype > IMG_F64 || out_dtype < IMG_U8 || out_dtype > IMG_F64) return SSDHIP_E_BADARG;
+    if (in_dtype < IMG_U8 || in_dtype > IMG_F64 || out_dtype < IMG_U8 || out_dtype > IMG_F64 || ((uintptr_t)luts_dev & 3)) return SSDHIP_E_BADARG;
+    const unsigned char* luts = static_cast<const unsigned char*>(luts_dev);
     if (in_dtype == IMG_U8 && out_dtype == IMG_U8 && pixels_per_image % 4 == 0 && !(((uintptr_t)x | (uintptr_t)y) & 3)) {
         hipLaunchKernelGGL(pixel_program_u8x4_kernel<UniformImages>, dim3(img_blocks(pixels_per_image / 4, 2048), n_images), dim3(256), 0,
                            stream, static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), UniformImages{pixels_per_image},
-                           ops_dev, args_dev);
+                           ops_dev, args_dev, luts);
         return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
     }
     hipLaunchKernelGGL(pixel_program_kernel, dim3(img_blocks(pixels_per_image, 4096), n_images), dim3(256), 0, stream, x, in_dtype, y, out_dtype,
-                       pixels_per_image, ops_dev, args_dev);
+                       pixels_per_image, ops_dev, args_dev, luts);
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_image_program(const void* x, int in_dtype, void* y, int out_dtype, int n_images, long long pixels_per_image,
+                                    const int* ops_dev, const double* args_dev, void* stream_) {
+    return ssdhip_image_program_lut(x, in_dtype, y, out_dtype, n_images, pixels_per_image, ops_dev, args_dev, nullptr, stream_);
 }
 
 extern "C" int ssdhip_image_resize_cv_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, int kind, int area,
@@ -563,13 +719,50 @@ extern "C" int ssdhip_image_resize_gather_turn_ragged_u8(const void* x, const lo
 
 // The photometric programs of ssdhip_image_program (uint8 -> uint8) on a ragged batch of 3-channel images, one program per image, ONE
 // launch: y has x's layout (the same table); max_pixels = the largest H W of the batch (sizes the grid).
-extern "C" int ssdhip_image_program_ragged_u8(const void* x, const long long* table_dev, void* y, int B, long long max_pixels,
-                                              const int* ops_dev, const double* args_dev, void* stream_) {
+extern "C" int ssdhip_image_program_ragged_lut_u8(const void* x, const long long* table_dev, void* y, int B, long long max_pixels,
+                                                  const int* ops_dev, const double* args_dev, const void* luts_dev, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!x || !table_dev || !y || !ops_dev || !args_dev || B <= 0 || B > 65535 || max_pixels <= 0) return SSDHIP_E_BADARG;
-    if (((uintptr_t)x | (uintptr_t)y) & 3) return SSDHIP_E_BADARG;
+    if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)luts_dev) & 3) return SSDHIP_E_BADARG;
     hipLaunchKernelGGL(pixel_program_u8x4_kernel<RaggedImages>, dim3(img_blocks((max_pixels + 3) / 4, 2048), B), dim3(256), 0, stream,
-                       static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), RaggedImages{table_dev}, ops_dev, args_dev);
+                       static_cast<const unsigned char*>(x), static_cast<unsigned char*>(y), RaggedImages{table_dev}, ops_dev, args_dev,
+                       static_cast<const unsigned char*>(luts_dev));
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_image_program_ragged_u8(const void* x, const long long* table_dev, void* y, int B, long long max_pixels,
+                                              const int* ops_dev, const double* args_dev, void* stream_) {
+    return ssdhip_image_program_ragged_lut_u8(x, table_dev, y, B, max_pixels, ops_dev, args_dev, nullptr, stream_);
+}
+
+// The histograms of one channel of a batch in the middle of its programs (program_hist_u8_kernel): table_dev = the ragged batch's table
+// and `pixels` its largest H W, or table_dev NULL: B images of `pixels` pixels each, (B, H, W, 3).  hist_dev [B][256] is zeroed here.
+extern "C" int ssdhip_image_program_hist_u8(const void* x, const long long* table_dev, int B, long long pixels, const int* ops_dev,
+                                            const double* args_dev, const void* luts_dev, const int* stop_dev, const int* channel_dev,
+                                            unsigned int* hist_dev, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!x || !ops_dev || !args_dev || !stop_dev || !channel_dev || !hist_dev || B <= 0 || B > 65535 || pixels <= 0) return SSDHIP_E_BADARG;
+    if ((uintptr_t)luts_dev & 3) return SSDHIP_E_BADARG;
+    if (table_dev && ((uintptr_t)x & 3)) return SSDHIP_E_BADARG;
+    if (zero_async(hist_dev, (size_t)B * 256 * sizeof(unsigned int), stream) != hipSuccess) return SSDHIP_E_LAUNCH;
+    const unsigned char* xs = static_cast<const unsigned char*>(x);
+    const unsigned char* luts = static_cast<const unsigned char*>(luts_dev);
+    if (table_dev)
+        hipLaunchKernelGGL((program_hist_u8_kernel<RaggedImages, 4>), dim3(img_blocks((pixels + 3) / 4, 64), B), dim3(256), 0, stream, xs,
+                           RaggedImages{table_dev}, ops_dev, args_dev, luts, stop_dev, channel_dev, hist_dev);
+    else if (pixels % 4 == 0 && !((uintptr_t)x & 3))
+        hipLaunchKernelGGL((program_hist_u8_kernel<UniformImages, 4>), dim3(img_blocks(pixels / 4, 64), B), dim3(256), 0, stream, xs,
+                           UniformImages{pixels}, ops_dev, args_dev, luts, stop_dev, channel_dev, hist_dev);
+    else
+        hipLaunchKernelGGL((program_hist_u8_kernel<UniformImages, 1>), dim3(img_blocks(pixels, 64), B), dim3(256), 0, stream, xs,
+                           UniformImages{pixels}, ops_dev, args_dev, luts, stop_dev, channel_dev, hist_dev);
+    return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+extern "C" int ssdhip_image_equalize_tables(const unsigned int* hist_dev, const int* slot_dev, void* luts_dev, int B, void* stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (!hist_dev || !slot_dev || !luts_dev || B <= 0 || ((uintptr_t)hist_dev & 15) || ((uintptr_t)luts_dev & 3)) return SSDHIP_E_BADARG;
+    hipLaunchKernelGGL(equalize_tables_kernel, dim3((unsigned)B), dim3(64), 0, stream, hist_dev, slot_dev, static_cast<unsigned char*>(luts_dev));
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
 }
 

@@ -54,8 +54,11 @@ def _torch_dtype(tag):
 
 
 def run(image, steps):
-    """One program on one image (NumPy (H, W, 3)) or the same program on every image of a CUDA batch (B, H, W, 3)."""
+    """One program on one image (NumPy (H, W, 3)) or the same program on every image of a CUDA batch (B, H, W, 3); a lazy `ProgramImage`
+    records the steps instead."""
     import torch
+    if isinstance(image, ProgramImage):
+        return image.record(steps)
     if isinstance(image, np.ndarray):
         if image.ndim != 3 or image.shape[2] != 3:
             raise ValueError("expected an (H, W, 3) image")
@@ -304,6 +307,184 @@ def run_ragged(packed, programs):
     return packed.like(out)
 
 
+# ---- lazy photometry: the photometric ops of a composed list recorded around the recorded geometry ------------------------------------
+class ProgramImage:
+    """An image that exists only as WHAT A TRANSFORMATION LIST DID TO IT: the photometric steps in front of the geometry (`pre`), the
+    geometry (a `GeoImage`), and the photometric steps behind it (`post`) -- executed for a whole batch by `run_program_batch`.  Steps are
+    the (name, argument) pairs of `encode` plus two that need a table: ("gamma", table) = cv2.LUT with a 256-entry uint8 table on all
+    three channels, ("equalize", channel) = cv2.equalizeHist on one channel.  Quacks like the array the ops expect: `shape`, `ndim` and
+    row / column slicing are the GeoImage's, `dtype` is what the recorded steps leave (`end_dtype`), `image[:, :, order]` is ChannelSwap.
+    What a NumPy image of that dtype would refuse is refused when it is recorded, with the same exception; what cannot be composed --
+    geometry on a state that is not uint8 or behind a step of `post`, more than 15 steps or four tables in a segment -- raises
+    NotImplementedError (the generator then runs the per-image loop)."""
+
+    ndim = 3
+
+    def __init__(self, geo, pre=(), post=(), moved=False):
+        self.geo, self.pre, self.post, self.moved = geo, list(pre), list(post), bool(moved)
+
+    @classmethod
+    def of(cls, height, width):
+        return cls(GeoImage.of(height, width))
+
+    @property
+    def shape(self):
+        return self.geo.shape
+
+    @property
+    def dtype(self):
+        return np.dtype(end_dtype(end_dtype(U8, self.pre), self.post))
+
+    def record(self, steps):
+        """The image after `steps`: appended to the segment in front of the geometry while no geometric op has been recorded, else behind it."""
+        tag = str(self.dtype)
+        segment = list(self.post if self.moved else self.pre)
+        for name, arg in steps:
+            if name == "gamma":
+                if tag != U8:
+                    raise TypeError("look-up tables apply to uint8 images")
+                arg = np.asarray(arg, dtype=np.uint8).reshape(256)
+            elif name == "equalize":
+                if tag != U8:
+                    raise TypeError("histogram equalisation takes uint8 images")
+                if int(arg) not in (0, 1, 2):
+                    raise ValueError("a channel is 0, 1 or 2")
+            else:
+                nat.IMG_OPS[name]
+            tag = end_dtype(tag, [(name, arg)])
+            segment.append((name, arg))
+        if len(segment) > nat.IMG_PROG - 1:
+            raise NotImplementedError("a recorded segment holds at most %d steps" % (nat.IMG_PROG - 1))
+        if sum(name in ("gamma", "equalize") for name, _ in segment) > nat.IMG_LUT_SLOTS:
+            raise NotImplementedError("a recorded segment holds at most %d look-up tables" % nat.IMG_LUT_SLOTS)
+        return ProgramImage(self.geo, self.pre, segment, True) if self.moved else ProgramImage(self.geo, segment)
+
+    def _geometry(self, geo_of):
+        if self.post:
+            raise NotImplementedError("geometry behind the second photometric segment cannot be composed lazily")
+        if self.dtype != np.uint8:
+            raise NotImplementedError("the recorded geometry takes uint8 images")
+        return ProgramImage(geo_of(self.geo), self.pre, (), True)
+
+    def __getitem__(self, key):
+        full = slice(None, None, None)
+        if isinstance(key, tuple) and len(key) == 3 and key[0] == full and key[1] == full and isinstance(key[2], (tuple, list, np.ndarray)):
+            return self.record([("swap", swap_code(key[2]))])                 # ChannelSwap: image[:, :, order]
+        if not all(isinstance(k, slice) for k in (key if isinstance(key, tuple) else (key,))):
+            raise NotImplementedError("lazy images take row / column slices and channel orders only")
+        return self._geometry(lambda geo: geo[key])
+
+    def window(self, top, left, height, width, background):
+        return self._geometry(lambda geo: geo.window(top, left, height, width, background))
+
+    def warp(self, M, dsize, background):
+        return self._geometry(lambda geo: geo.warp(M, dsize, background))
+
+    def resize(self, out_h, out_w, interp):
+        return self._geometry(lambda geo: geo.resize(out_h, out_w, interp))
+
+
+def _segment_tables(programs):
+    """A batch's recorded segments -> (the encodable programs: every table step as ("lut", slot + 4 mask), the slots dealt in step order;
+    the gamma tables in their slots, (B, 4, 256) uint8; per image its equalize steps [(position, channel, slot), ...]; tables used?)."""
+    luts = np.zeros((len(programs), nat.IMG_LUT_SLOTS, 256), dtype=np.uint8)
+    plain, equalizes, used = [], [], False
+    for i, program in enumerate(programs):
+        steps, eq, slot = [], [], 0
+        for k, (name, arg) in enumerate(program):
+            if name == "gamma":
+                luts[i, slot] = arg
+                steps.append(("lut", slot + 4 * 7))
+            elif name == "equalize":
+                eq.append((k, int(arg), slot))
+                steps.append(("lut", slot + 4 * (1 << int(arg))))
+            else:
+                steps.append((name, arg))
+                continue
+            slot += 1
+        used = used or slot > 0
+        plain.append(steps)
+        equalizes.append(eq)
+    return plain, luts, equalizes, used
+
+
+def _run_segment(programs, device, launch_program, launch_hist):
+    """One recorded segment of a batch (every image on a uint8 state): without tables ONE launch (`launch_program(ops, args, None)`); with
+    them the gamma tables go up once, every equalize position costs one histogram launch over the programs' prefixes
+    (`launch_hist(ops, args, luts, stop, channel, hist)`) and one table launch, then `launch_program(ops, args, luts)`."""
+    plain, luts_host, equalizes, used = _segment_tables(programs)
+    enc = [encode(p) for p in plain]
+    ops, args = np.stack([e[0] for e in enc]), np.stack([e[1] for e in enc])
+    if not used:
+        return launch_program(ops, args, None)
+    import torch
+    nat.image_program_check(ops, args, nat.IMG_U8, True)
+    ops, args = nat.to_device(ops, device=device, dtype=torch.int32), nat.to_device(args, device=device, dtype=torch.float64)
+    luts = nat.to_device(luts_host, device=device)
+    hist = None
+    for level in range(max(len(eq) for eq in equalizes)):
+        sel = np.full((3, len(programs)), -1, dtype=np.int32)              # stop, channel, slot
+        sel[1] = 0
+        for i, eq in enumerate(equalizes):
+            if len(eq) > level:
+                sel[:, i] = eq[level]
+        hist = launch_hist(ops, args, luts, sel[0], sel[1], hist)
+        nat.image_equalize_tables(hist, sel[2], luts)
+    return launch_program(ops, args, luts)
+
+
+def _three_channels(image):
+    """ConvertTo3Channels (object_detection_2d_photometric_ops): grey replicated, alpha dropped."""
+    if image.ndim == 2:
+        return np.stack([image] * 3, axis=-1)
+    if image.shape[2] == 1:
+        return np.concatenate([image] * 3, axis=-1)
+    return image[:, :, :3]
+
+
+def run_program_batch(images, lazies):
+    """Execute a batch of ProgramImages over the uint8 host images they were recorded for -> the CUDA batch (B, H, W, 3), uint8, float32 or
+    float64 as the programs end.  First segments on the ragged batch (nothing is launched when all are empty; 1- and 4-channel images are
+    made 3-channel on the host when one is not), then the ragged gather (a copy-kind plan for a list without a resize: every image must
+    end in one size), then the second segments on the gather's output.  NotImplementedError for sizes or dtypes that differ."""
+    import torch
+    if len(images) != len(lazies) or not lazies:
+        raise ValueError("one lazy image per image of the batch")
+    pres, posts, geos = [], [], []
+    for l in lazies:
+        pre, post = list(l.pre), list(l.post)
+        if not l.moved and end_dtype(U8, pre) != U8:                          # no geometry at all: the steps may as well follow it
+            pre, post = [], pre
+        if end_dtype(U8, pre) != U8:
+            raise NotImplementedError("the recorded geometry takes uint8 images")
+        pres.append(pre)
+        posts.append(post)
+        geos.append(l.geo if l.geo.resized is not None else l.geo.resize(l.geo.shape[0], l.geo.shape[1], INTER_NEAREST))
+    if len({g.resized[:2] for g in geos}) != 1:
+        raise NotImplementedError("every image of a batch must end in the same size")
+    tags = {end_dtype(U8, p) for p in posts}
+    if len(tags) != 1:
+        raise NotImplementedError("the programs of a batch must end in the same dtype")
+    if any(pres):
+        images = [im if (im.ndim == 3 and im.shape[2] == 3) else _three_channels(im) for im in images]
+    packed = pack_ragged(images)
+    device = packed.data.device
+    if any(pres):
+        packed = packed.like(_run_segment(
+            pres, device,
+            lambda ops, args, luts: nat.image_program_ragged_u8(packed.data, packed.table, packed.max_pixels, ops, args, luts),
+            lambda ops, args, luts, stop, channel, hist: nat.image_program_hist_u8(packed.data, packed.table, packed.max_pixels, ops, args,
+                                                                                 luts, stop, channel, hist)))
+    out = gather_batch_ragged(packed, geos)
+    if any(posts):
+        out_dtype = _torch_dtype(tags.pop())
+        out = _run_segment(
+            posts, device,
+            lambda ops, args, luts: nat.image_program(out, ops, args, out_dtype, luts),
+            lambda ops, args, luts, stop, channel, hist: nat.image_program_hist_u8(out, None, 0, ops, args, luts, stop, channel, hist))
+    return out
+
+
 # ---- cv2.resize for 8-bit images: the tables of OpenCV's imgproc/resize.cpp (3.4 / 4.x), the arithmetic runs in csrc/ssdhip_image.hip ----
 # cv::resize on CV_8U (round 6; the first version resampled with float64 weights and one rounding, off by one grey level here and there):
 #   LINEAR / CUBIC / LANCZOS4, and AREA when an axis grows ("area_mode" bilinear): per output column / row the float32 kernel values become
@@ -486,7 +667,7 @@ def resize_plan(src_h, src_w, dst_h, dst_w, interp):
 
 def resize(image, out_h, out_w, interp):
     """cv2.resize(image, dsize=(out_w, out_h), interpolation=interp) for uint8 images: NumPy (H, W[, C]) or CUDA (B, H, W, C)."""
-    if isinstance(image, GeoImage):
+    if isinstance(image, (GeoImage, ProgramImage)):
         return image.resize(out_h, out_w, interp)
     if isinstance(image, np.ndarray):
         if image.dtype != np.uint8:
@@ -501,6 +682,10 @@ def resize(image, out_h, out_w, interp):
 
 # ---- cv2.LUT / cv2.equalizeHist ----------------------------------------------------------------------------------------------------
 def lut(image, table, channel_mask):
+    if isinstance(image, ProgramImage):
+        if (int(channel_mask) & 7) != 7:
+            raise NotImplementedError("lazy images take tables for all three channels only")
+        return image.record([("gamma", table)])
     if isinstance(image, np.ndarray):
         if image.dtype != np.uint8:
             raise TypeError("look-up tables apply to uint8 images")
@@ -524,7 +709,9 @@ def equalize_table(hist):
 
 
 def equalize_channel(image, channel):
-    """image with cv2.equalizeHist applied to one channel (uint8; NumPy (H, W, C) or one CUDA image (H, W, C))."""
+    """image with cv2.equalizeHist applied to one channel (uint8; NumPy (H, W, C), one CUDA image (H, W, C), or a `ProgramImage`: recorded)."""
+    if isinstance(image, ProgramImage):
+        return image.record([("equalize", channel)])
     if isinstance(image, np.ndarray):
         if image.dtype != np.uint8:
             raise TypeError("histogram equalisation takes uint8 images")
@@ -691,7 +878,7 @@ def warp_batch(images, lazies):
 def warp_affine(image, M, dsize, background=0):
     """cv2.warpAffine(image, M, dsize=(width, height), borderMode=BORDER_CONSTANT, borderValue=background) for uint8 images: a NumPy
     (H, W[, C]) image (one upload, one launch, one download) or a `WarpImage` (recorded)."""
-    if isinstance(image, (WarpImage, GeoImage)):
+    if isinstance(image, (WarpImage, GeoImage, ProgramImage)):
         return image.warp(M, dsize, background)
     if not isinstance(image, np.ndarray):
         raise TypeError("warp_affine takes a NumPy image or a lazy WarpImage / GeoImage")

@@ -15,6 +15,13 @@ chains read too).
     `DataAugmentationVariableInputSize.augment_batch` on the list (110 ms -> 2.1 ms per batch of 32, profiles/variable_chain_device.json);
   * `[DataAugmentationSatellite]`: the same for the chain with vertical flips and rotations by quarter turns
     (`DataAugmentationSatellite.augment_batch`; np.random AND Python's `random` end where the per-image loop leaves them);
+  * any other list made of the package's own photometric ops, `Flip` / `RandomFlip`, `CropPad` / `Crop` / `Pad`, the random patch ops,
+    `Rotate` / `RandomRotate` and one `Resize` / `ResizeRandomInterp` in the order photometric, geometric (the resize last), photometric
+    (`_composable` has the rules): the list's own host code runs on lazy images that record the photometric steps around the recorded
+    geometry (`_image_ops.ProgramImage`), and the batch is a few launches (`_image_ops.run_program_batch`): the first photometric
+    segment on the ragged batch -- Gamma and HistogramEqualization as look-up-table steps of the per-image programs, the equalisation
+    tables built on the device --, the ragged gather, the second segment on its output (which may end in float32 or float64).  A batch
+    the lazy images cannot compose (NotImplementedError) goes through the per-image loop from the same random state;
   * anything else: the reference's per-image loop over the package's transforms.
 Every path gives the per-image loop's pixels, labels, inverters and final `np.random` state.  Images are decoded by PIL on the host, as in
 the reference.  HDF5 datasets are not supported (h5py is not a dependency of this package); their parameter and methods raise
@@ -351,22 +358,84 @@ class DataGenerator:
             return None
         if kinds in ([ConvertTo3Channels, Resize], [ConvertTo3Channels, RandomPadFixedAR, Resize]):
             return 'gather'
-        if not have_labels:
-            return None
-        if kinds == [SSDDataAugmentation]:
-            return 'ssd'
-        if (kinds == [DataAugmentationConstantInputSize] and len({im.shape for im in images}) == 1 and images[0].ndim == 3
-                and images[0].shape[2] == 3):
-            return 'constant'
-        if kinds == [DataAugmentationVariableInputSize]:
-            return 'variable'
-        if kinds == [DataAugmentationSatellite]:
-            return 'satellite'
-        return None
+        if have_labels:
+            if kinds == [SSDDataAugmentation]:
+                return 'ssd'
+            if (kinds == [DataAugmentationConstantInputSize] and len({im.shape for im in images}) == 1 and images[0].ndim == 3
+                    and images[0].shape[2] == 3):
+                return 'constant'
+            if kinds == [DataAugmentationVariableInputSize]:
+                return 'variable'
+            if kinds == [DataAugmentationSatellite]:
+                return 'satellite'
+        return 'program' if DataGenerator._composable(transformations, images) else None
+
+    @staticmethod
+    def _composable(transformations, images):
+        """Whether a list is built from the package's own photometric, index-geometry and patch ops in an order the lazy images can
+        record (the 'program' path of the module docstring): decided from the elements' types and the images alone, before any draw."""
+        from . import object_detection_2d_geometric_ops as geo
+        from . import object_detection_2d_patch_sampling_ops as patch
+        from . import object_detection_2d_photometric_ops as photo
+        fresh = (photo.ConvertColor, photo.ConvertDataType, photo.Brightness, photo.Contrast, photo.Gamma, photo.ChannelSwap, geo.Resize)
+        in_place = (photo.Hue, photo.RandomHue, photo.Saturation, photo.RandomSaturation, photo.HistogramEqualization,
+                    photo.RandomHistogramEqualization)
+        photometric = fresh[:-1] + in_place + (photo.RandomBrightness, photo.RandomContrast, photo.RandomGamma, photo.RandomChannelSwap)
+        resizes = (geo.Resize, geo.ResizeRandomInterp)
+        geometric = resizes + (geo.Flip, geo.RandomFlip, geo.Rotate, geo.RandomRotate, patch.CropPad, patch.Crop, patch.Pad,
+                               patch.RandomPatch, patch.RandomPatchInf, patch.RandomMaxCropFixedAR, patch.RandomPadFixedAR)
+        kinds = [type(t) for t in transformations]
+        if any(k not in photometric and k not in geometric and k is not photo.ConvertTo3Channels for k in kinds):
+            return False
+        if kinds[0] is not photo.ConvertTo3Channels and any(im.ndim != 3 or im.shape[2] != 3 for im in images):
+            return False
+        phase, resized, have_fresh = 0, False, False                   # phase: 0 photometric, 1 geometric, 2 photometric again
+        for t, k in zip(transformations, kinds):
+            if k is photo.ConvertTo3Channels:
+                continue
+            if k in geometric:
+                if phase == 2 or resized:                              # a lazy image is final after its resize
+                    return False
+                phase, resized = 1, k in resizes
+                if k is geo.Rotate and t.angle not in (90, 180, 270):
+                    return False
+                if k is geo.RandomRotate and any(a not in (90, 180, 270) for a in t.angles):
+                    return False
+            else:
+                phase = 2 if phase else 0
+                if k is photo.ConvertColor and not t.keep_3ch:
+                    return False
+                if k in in_place and not have_fresh:                   # it would write into the dataset's own image in the loop
+                    return False
+            have_fresh = have_fresh or k in fresh
+        return True
+
+    @staticmethod
+    def _walk(transformations, img, lab, want_inverters):
+        """The transforms' own host code on one (lazy) image: (image, labels, inverters in the order they are applied)."""
+        inv = []
+        for transform in transformations:
+            takes = want_inverters and ('return_inverter' in inspect.signature(transform).parameters)
+            if lab is not None:
+                if takes:
+                    img, lab, inverter = transform(img, lab, return_inverter=True)
+                    inv.append(inverter)
+                else:
+                    img, lab = transform(img, lab)
+            else:
+                if takes:
+                    img, inverter = transform(img, return_inverter=True)
+                    inv.append(inverter)
+                else:
+                    img = transform(img)
+            if img is None:
+                raise NotImplementedError("a transform that drops the image is the per-image loop's to handle")
+        return img, lab, inv[::-1]
 
     def _transform_batch(self, path, transformations, images, labels, want_inverters):
         """The batch paths: images (uint8 NumPy) and labels (arrays, or None) of the items that are transformed -> (CUDA (n, H, W, 3)
-        uint8 batch, labels or None, inverters per item)."""
+        batch -- uint8, or what a 'program' list ends in --, labels or None, inverters per item).  'program' raises NotImplementedError,
+        with both random generators where they were, for a batch its lazy images cannot compose."""
         import torch
         from . import _image_ops as iop
         if path in ('ssd', 'variable', 'satellite'):
@@ -379,6 +448,24 @@ class DataGenerator:
             batch = torch.from_numpy(np.stack(images)).to(torch.device('cuda', torch.cuda.current_device()))
             out, out_labels = transformations[0].augment_batch(batch, labels)
             return out, out_labels, [[] for _ in images]
+        if path == 'program':
+            # the transforms' own host code on lazy images that also record the photometric steps, then a few launches for the batch
+            import random
+            states = np.random.get_state(), random.getstate()
+            try:
+                lazies, out_labels, inverters = [], [], []
+                for k, im in enumerate(images):
+                    img, lab, inv = self._walk(transformations, iop.ProgramImage.of(int(im.shape[0]), int(im.shape[1])),
+                                               None if labels is None else labels[k], want_inverters)
+                    lazies.append(img)
+                    out_labels.append(lab)
+                    inverters.append(inv)
+                out = iop.run_program_batch(images, lazies)
+            except NotImplementedError:
+                np.random.set_state(states[0])
+                random.setstate(states[1])
+                raise
+            return out, (None if labels is None else out_labels), inverters
         # 'gather': the transforms' own host code on lazy images, then one launch for the pixels
         lazies, out_labels, inverters = [], [], []
         for k, im in enumerate(images):
@@ -488,19 +575,26 @@ class DataGenerator:
                             continue
                     todo.append(i)
                 if todo:
-                    processed, out_labels, inverters = self._transform_batch(
-                        path, transformations, [batch_X[i] for i in todo], None if self.labels is None else [batch_y[i] for i in todo],
-                        want_inverters)
-                    for k, i in enumerate(todo):
-                        batch_X[i] = k                         # a row of `processed`
-                        if self.labels is not None:
-                            batch_y[i] = out_labels[k]
-                inv_of = dict(zip(todo, inverters)) if todo else {}
-                batch_inverse_transforms = [inv_of.get(i, []) for i in range(len(batch_X))]
-                for i in todo:
-                    self._check_degenerate(i, batch_y, degenerate_box_handling, box_filter if degenerate_box_handling == 'remove' else None,
-                                           keep_images_without_gt, batch_items_to_remove)
-            else:
+                    try:
+                        processed, out_labels, inverters = self._transform_batch(
+                            path, transformations, [batch_X[i] for i in todo], None if self.labels is None else [batch_y[i] for i in todo],
+                            want_inverters)
+                    except NotImplementedError:
+                        if path != 'program':
+                            raise
+                        path, batch_items_to_remove = None, []     # this batch cannot be composed: the per-image loop, from the same draws
+                if path is not None:
+                    if todo:
+                        for k, i in enumerate(todo):
+                            batch_X[i] = k                         # a row of `processed`
+                            if self.labels is not None:
+                                batch_y[i] = out_labels[k]
+                    inv_of = dict(zip(todo, inverters)) if todo else {}
+                    batch_inverse_transforms = [inv_of.get(i, []) for i in range(len(batch_X))]
+                    for i in todo:
+                        self._check_degenerate(i, batch_y, degenerate_box_handling, box_filter if degenerate_box_handling == 'remove' else None,
+                                               keep_images_without_gt, batch_items_to_remove)
+            if path is None:
                 for i in range(len(batch_X)):
                     if self.labels is not None:
                         batch_y[i] = np.array(batch_y[i])

@@ -114,7 +114,7 @@ class CropPad:
         '''The patch as a fresh uint8 array: background canvas + the part of the image the window covers.'''
         img_height, img_width = image.shape[:2]
         top, left, height, width = self.patch_ymin, self.patch_xmin, self.patch_height, self.patch_width
-        if isinstance(image, iop.GeoImage):              # a lazy image (SSDDataAugmentation.augment_batch): record, do not copy
+        if isinstance(image, (iop.GeoImage, iop.ProgramImage)):     # a lazy image (augment_batch, generate()'s batch paths): record, do not copy
             return image.window(top, left, height, width, self.background)
         if image.ndim == 3:
             canvas = np.zeros((height, width, 3), dtype=np.uint8)

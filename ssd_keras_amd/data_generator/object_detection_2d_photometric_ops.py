@@ -7,6 +7,10 @@ batch through `SSDPhotometricDistortions.distort_batch` (data_augmentation_chain
 OpenCV -- cv2.cvtColor, cv2.LUT, cv2.equalizeHist -- is restated from OpenCV's published algorithms (8-bit HSV with H in [0, 180),
 float32 HSV with H in [0, 360)); the NumPy arithmetic around it follows the reference's expressions for the array's dtype.
 
+Given a lazy `_image_ops.ProgramImage` (generate()'s 'program' path) every op RECORDS its step instead of launching -- through `iop.run`,
+`iop.lut` (Gamma), `iop.equalize_channel` (HistogramEqualization) and `image[:, :, order]` (ChannelSwap) -- with the draws, the dtype the
+next op sees and the exceptions of the NumPy route; the in-place ops (`_assign`) have nothing to write into there.
+
 Two deliberate differences: `Gamma.__call__` works (the reference's reads an undefined global `table`, :359, and raises NameError),
 and `ConvertColor(current='HSV', to='GRAY')` raises ValueError (the reference asks cv2 for a constant that does not exist, :54)."""
 from __future__ import annotations
