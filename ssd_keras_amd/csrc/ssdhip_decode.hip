@@ -104,19 +104,36 @@ __device__ __forceinline__ float decode_center(float off, float var, float a_wh,
 
 // The body shared by scan_kernel (tile copied from y_pred) and scan_heads_kernel (tile built from the head outputs): `tile`
 // holds rows [a0, a0 + na) of image b as [C+12] floats in LDS, one thread per row; wave_cnt: LDS, (blockDim.x / 64) * G ints.
-__device__ __forceinline__ void scan_tile_body(const float* tile, int* wave_cnt, const DecodeParams& p, const int b, const int a0,
+//
+// `row` is the thread's [C+12] row behind an accessor.  LdsRow (CT == 0: the class count is p.C) reads LDS and takes the loops below as
+// they always were.  RegRow<C> (CT == C, scan_heads_rows_kernel) holds the row in registers: there every index has to be a constant, so
+// the class loops are plain unrolled loops over CT -- the eight-score groups of the LDS form exist to keep LDS reads in flight and
+// would only cost registers.  Same compares, ballots, counts, atomics and keys in both forms.
+struct LdsRow {
+    static constexpr int CT = 0;
+    const float* r;
+    __device__ __forceinline__ float operator[](int i) const { return r[i]; }
+};
+template <int C_>
+struct RegRow {
+    static constexpr int CT = C_;
+    float r[C_ + 12];
+    __device__ __forceinline__ float operator[](int i) const { return r[i]; }
+};
+
+template <typename Row>
+__device__ __forceinline__ void scan_tile_body(const Row& row, int* wave_cnt, const DecodeParams& p, const int b, const int a0,
                                                const int na, float4* __restrict__ boxes, u64* __restrict__ cand,
                                                int* __restrict__ cand_count, unsigned short* __restrict__ cls_out) {
+    constexpr int CT = Row::CT;
     const int TA = blockDim.x;
-    const int L = p.L;
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, nwaves = TA >> 6;
     PROF_DECL
     PROF_MARK(0)
 
     const bool active = tid < na;
-    const float* row = tile + (size_t)tid * L;
-    const int C = p.C;
+    const int C = CT ? CT : p.C;
 
     // ---- decode this thread's box (float32, the reference's operation order) ----
     int fast_cls = 0;
@@ -155,11 +172,21 @@ __device__ __forceinline__ void scan_tile_body(const float* tile, int* wave_cnt,
         if (p.class_agnostic) {                                    // first argmax / max over ALL classes, :291-293
             float best = row[0];
             int bi = 0;
+            if constexpr (CT > 0) {
+#pragma unroll
+                for (int c = 1; c < CT; ++c) {
+                    const float s = row[c];
+                    if (s > best) { best = s; bi = c; }
+                }
+#pragma unroll
+                for (int c = CT - 1; c >= 0; --c) if (row[c] != row[c]) { best = row[c]; bi = c; }   // descending: the FIRST NaN is set last
+            } else {
             for (int c = 1; c < C; ++c) {
                 const float s = row[c];
                 if (s > best) { best = s; bi = c; }
             }
             for (int c = 0; c < C; ++c) if (row[c] != row[c]) { best = row[c]; bi = c; break; }   // np.argmax: first NaN wins
+            }
             fast_cls = bi;
             fast_conf = best;
             cls_out[(size_t)b * p.N + a0 + tid] = (unsigned short)bi;
@@ -173,13 +200,29 @@ __device__ __forceinline__ void scan_tile_body(const float* tile, int* wave_cnt,
     const float t = p.thr_eff;
     const bool incl = p.thr_inclusive != 0;
     const bool fast_pred = active && (fast_cls != 0) && (incl ? (fast_conf >= t) : (fast_conf > t));
+    if constexpr (CT > 0) {
+        static_assert(CT - 1 <= 64, "one lane per class");
+        int mycnt = 0;
+        if (p.class_agnostic) {
+            mycnt = __popcll(__ballot(fast_pred));
+        } else {
+#pragma unroll
+            for (int j = 0; j < CT - 1; ++j) {
+                const float s = row[j + 1];
+                const bool pr = active && (incl ? (s >= t) : (s > t));
+                const int cnt = __popcll(__ballot(pr));
+                mycnt = lane == j ? cnt : mycnt;
+            }
+        }
+        if (lane < G) wave_cnt[wave * G + lane] = mycnt;
+    } else
     for (int gb = 0; gb < G; gb += 64) {
         const int ng = min(64, G - gb);
         int mycnt = 0;
         if (p.class_agnostic) {
             mycnt = __popcll(__ballot(fast_pred));
         } else {
-            const float* sc = row + gb + 1;
+            const float* sc = row.r + gb + 1;
             for (int j0 = 0; j0 < ng; j0 += 8) {                  // eight scores per step: their LDS reads are in flight together
                 float s8[8];
 #pragma unroll
@@ -212,10 +255,34 @@ __device__ __forceinline__ void scan_tile_body(const float* tile, int* wave_cnt,
     PROF_MARK(3)
     // ---- pass 2: write the keys (slot = wave base of the class + rank of the lane among the class's candidates) ----
     const u32 inv_idx = IDX_MASK - (u32)(a0 + tid);
+    if constexpr (CT > 0) {
+        const int mybase = lane < G ? wave_cnt[wave * G + lane] : 0;
+        if (p.class_agnostic) {
+            const u64 m = __ballot(fast_pred);
+            const int base_0 = __builtin_amdgcn_readlane(mybase, 0);
+            if (fast_pred) {
+                const int slot = base_0 + (int)__builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
+                cand[(size_t)b * G * p.N + slot] = ((u64)float_key(fast_conf) << IDX_BITS) | inv_idx;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < CT - 1; ++j) {
+                const float s = row[j + 1];
+                const bool pr = active && (incl ? (s >= t) : (s > t));
+                const u64 m = __ballot(pr);
+                if (m == 0) continue;
+                const int base_j = __builtin_amdgcn_readlane(mybase, j);
+                if (pr) {
+                    const int slot = base_j + (int)__builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u));
+                    cand[((size_t)b * G + j) * p.N + slot] = ((u64)float_key(s) << IDX_BITS) | inv_idx;
+                }
+            }
+        }
+    } else
     for (int gb = 0; gb < G; gb += 64) {
         const int ng = min(64, G - gb);
         const int mybase = lane < ng ? wave_cnt[wave * G + gb + lane] : 0;
-        const float* sc = row + gb + 1;
+        const float* sc = row.r + gb + 1;
         for (int j0 = 0; j0 < ng; j0 += 8) {
             float s8[8];
 #pragma unroll
@@ -268,7 +335,7 @@ __global__ __launch_bounds__(256) void scan_kernel(const float* __restrict__ y, 
     }
     int* wave_cnt = reinterpret_cast<int*>(smem_raw + (((size_t)TA * p.L + 4) * sizeof(float) + 15) / 16 * 16);
     __syncthreads();
-    scan_tile_body(tile, wave_cnt, p, b, a0, na, boxes, cand, cand_count, cls_out);
+    scan_tile_body(LdsRow{tile + (size_t)threadIdx.x * p.L}, wave_cnt, p, b, a0, na, boxes, cand, cand_count, cls_out);
 }
 
 // K3 for WIDE rows (C + 12 > 64 floats: SSD512 / COCO's 93).  scan_kernel stages whole rows: 64 rows x 93 floats = 24 KB per wave, six
@@ -392,7 +459,28 @@ __global__ __launch_bounds__(256) void scan_heads_kernel(HeadParams hp, const fl
     bf16_t* cl = reinterpret_cast<bf16_t*>(smem_raw + (size_t)hp.TA * p.L * sizeof(float));
     int* wave_cnt = reinterpret_cast<int*>(smem_raw + (head_tile_lds(hp.TA, p.C) + 15) / 16 * 16);
     head_build_rows(hp, anchors_var, l, b, a0, na, rows, cl, threadIdx.x, blockDim.x);
-    scan_tile_body(rows, wave_cnt, p, b, hp.anchor_off[l] + a0, na, boxes, cand, cand_count, cls_out);
+    scan_tile_body(LdsRow{rows + (size_t)threadIdx.x * p.L}, wave_cnt, p, b, hp.anchor_off[l] + a0, na, boxes, cand, cand_count, cls_out);
+}
+
+// scan_heads_kernel with the anchor's row in REGISTERS, for a compile-time class count and packed bf16 heads whose every tile comes in
+// by LDS-DMA (head_rows_all_dma; anything else keeps scan_heads_kernel).  There each row goes through LDS five times -- written with
+// bias and max, read and written for exp, again for the division, read by the count pass and by the key pass -- although no thread
+// reads another's row; the rows are in LDS only because C is a run-time value.  Here the thread pulls its C + 4 staged bf16 values into
+// registers (head_row_regs: the same operations in the same order) and goes straight on to the decode, the ballots and the keys.
+// LDS per workgroup: head_stage_bytes + the wave counts, 19.8 KB at C = 21 against 53.6 KB, and the launch bounds hold the kernel to
+// 96 VGPRs, so five workgroups of 256 reside on a CU: the 1 216 tiles of SSD300 / batch 32 are resident in one round (768 slots before).
+template <int C>
+__global__ __launch_bounds__(256, 5) void scan_heads_rows_kernel(HeadParams hp, const float* __restrict__ anchors_var, DecodeParams p,
+                                                                 float4* __restrict__ boxes, u64* __restrict__ cand,
+                                                                 int* __restrict__ cand_count, unsigned short* __restrict__ cls_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int b = blockIdx.y;
+    int l, a0, na;
+    head_tile_of(hp, (int)blockIdx.x, l, a0, na);
+    int* wave_cnt = reinterpret_cast<int*>(smem_raw + (head_stage_bytes(hp.TA, C) + 15) / 16 * 16);
+    RegRow<C> row;
+    head_row_regs<C>(hp, anchors_var, l, b, a0, na, smem_raw, threadIdx.x, blockDim.x, row.r);
+    scan_tile_body(row, wave_cnt, p, b, hp.anchor_off[l] + a0, na, boxes, cand, cand_count, cls_out);
 }
 
 // ======================================================================================
@@ -1560,6 +1648,15 @@ static int decode_run(const HeadSource* heads, int stages, const void* y_pred, i
         const int HT = heads->hp->TA;                 // one thread per row of the head tile
         const size_t lds = (head_tile_lds(HT, C) + 15) / 16 * 16 + (size_t)((HT + 63) / 64) * p.G * sizeof(int);
         if (lds > 160 * 1024) return SSDHIP_E_BADARG;
+        // the row-in-registers form where the class count has an instantiation and every tile is an LDS-DMA tile of 256 anchors;
+        // SSDHIP_SCAN_ROWS=lds keeps scan_heads_kernel (A/B, tests)
+        const char* rows_env = getenv("SSDHIP_SCAN_ROWS");
+        const bool rows_lds = rows_env && rows_env[0] == 'l' && rows_env[1] == 'd' && rows_env[2] == 's' && !rows_env[3];
+        if (!rows_lds && C == 21 && HT == 256 && heads->hp->C == C && head_rows_all_dma(*heads->hp, B, HT, heads->anchors_var)) {
+            const size_t rlds = (head_stage_bytes(HT, C) + 15) / 16 * 16 + (size_t)(HT / 64) * p.G * sizeof(int);
+            hipLaunchKernelGGL(scan_heads_rows_kernel<21>, dim3(heads->tiles, B), dim3(HT), rlds, stream, *heads->hp, heads->anchors_var,
+                               p, boxes, cand, cand_count, cls_map);
+        } else
         hipLaunchKernelGGL(scan_heads_kernel, dim3(heads->tiles, B), dim3(HT < 64 ? 64 : HT), lds, stream, *heads->hp,
                            heads->anchors_var, p, boxes, cand, cand_count, cls_map);
     } else if (p.L > 64 && !p.class_agnostic) {

@@ -1,5 +1,6 @@
 // Prediction assembly shared by head_kernel (csrc/ssdhip_layers.hip: rows -> y_pred in HBM) and scan_heads_kernel
-// (csrc/ssdhip_decode.hip: rows stay in LDS and are decoded at once).  Reference: Reshape + Concatenate + softmax + AnchorBoxes
+// (csrc/ssdhip_decode.hip: rows stay in LDS and are decoded at once; scan_heads_rows_kernel builds the same row in registers,
+// head_row_regs below).  Reference: Reshape + Concatenate + softmax + AnchorBoxes
 // + Concatenate, models/keras_ssd300.py:363-419 and keras_layers/keras_layer_AnchorBoxes.py:245-255.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -293,6 +294,93 @@ __device__ __forceinline__ void head_build_rows(const HeadParams& hp, const floa
         for (int k = 0; k < 8; ++k) r[C + 4 + k] = av[k];
     }
     __syncthreads();
+}
+
+// ---- the row in registers (scan_heads_rows_kernel, csrc/ssdhip_decode.hip) -------------------------------------------------------
+// head_build_rows' LDS-DMA branch with the class count C a compile-time value and one thread per anchor: the same staging (pixel rows
+// by tile_dma16, biases, the anchor's two float4 requested before the wait), then the thread's [C+12] row is built in r[] -- registers,
+// every index a constant after unrolling -- by the same operations in the same order: bf16(conv + bias), fmaxf in ascending class
+// order, expf, the double sum rounded once (head_sum), one true division per class.  No rows[] in LDS: a tile needs head_stage_bytes
+// only.  The caller has checked head_rows_all_dma(): every tile of the launch meets the `dma` condition of head_build_rows, and
+// anchors_var is 16-byte aligned.  Threads past na get a row of zeros.  `st`: head_stage_bytes(TA, C) of LDS, 16-byte aligned.
+template <int C>
+__device__ __forceinline__ void head_row_regs(const HeadParams& hp, const float* __restrict__ anchors_var, int l, int b, int a0, int na,
+                                              unsigned char* st, int tid, int nthreads, float (&r)[C + 12]) {
+    const int nb = hp.n_boxes[l];
+    const int stride = hp.conf_stride[l];
+    const int U = nb * (C + 4) * 2, cpr = (U + 15) >> 4, pitch = cpr * 16;
+    const int pix0 = a0 / nb, npx = (a0 + na - 1) / nb - pix0 + 1, nchunks = npx * cpr;
+    const size_t dma_area = (size_t)((nchunks + 63) >> 6) * 1024;
+    const size_t npix_l = (size_t)(hp.n_anchors[l] / nb);
+    const size_t src_bytes = (size_t)gridDim.y * npix_l * (size_t)stride * 2;
+    const u32 lds0 = (u32)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)st;
+    const i32x4 rs = tile_rsrc(hp.conf[l], (u32)src_bytes);
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 row0 = (u32)(((size_t)b * npix_l + pix0) * (size_t)stride * 2);
+    for (int q0 = wave * 64; q0 < nchunks; q0 += nthreads) {
+        const int q = q0 + lane, rr = q / cpr, j = q - rr * cpr;
+        tile_dma16(q < nchunks ? row0 + (u32)rr * (u32)(stride * 2) + (u32)j * 16u : TILE_OOB, rs, lds0 + (u32)q0 * 16u);
+    }
+    bf16_t* bs = reinterpret_cast<bf16_t*>(st + dma_area);                     // [nb C] conf bias | [nb 4] loc bias
+    const bool has_cb = hp.conf_bias[l] != nullptr, has_lb = hp.loc_bias[l] != nullptr;
+    if (has_cb) for (int i = tid; i < nb * C; i += nthreads) bs[i] = hp.conf_bias[l][i];
+    if (has_lb) for (int i = tid; i < nb * 4; i += nthreads) bs[nb * C + i] = hp.loc_bias[l][i];
+    float4 av0 = make_float4(0.f, 0.f, 0.f, 0.f), av1 = av0;
+    if (tid < na) {
+        const float4* avp = reinterpret_cast<const float4*>(anchors_var + (size_t)(hp.anchor_off[l] + a0 + tid) * 8);
+        av0 = avp[0]; av1 = avp[1];
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < C + 12; ++k) r[k] = 0.f;
+    if (tid < na) {
+        const int ga = a0 + tid, pix = ga / nb, box = ga - pix * nb;
+        const bf16_t* prow = reinterpret_cast<const bf16_t*>(st + (size_t)(pix - pix0) * pitch);
+        const bf16_t* src = prow + box * C;
+        const bf16_t* cb = bs + box * C;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float x = bf16_float(src[c]);
+            // the PyTorch path rounds conv + bias to bf16 before the float32 softmax: keep that rounding
+            r[c] = has_cb ? bf16_float(bf16_bits(x + bf16_float(cb[c]))) : x;
+            mx = fmaxf(mx, r[c]);
+        }
+        double acc = 0.0;                                   // (head_sum)
+#pragma unroll
+        for (int c = 0; c < C; ++c) { r[c] = expf(r[c] - mx); acc += (double)r[c]; }
+        const float sum = (float)acc;
+#pragma unroll
+        for (int c = 0; c < C; ++c) r[c] = r[c] / sum;
+        const bf16_t* lsrc = prow + nb * C + box * 4;
+        const bf16_t* lb = bs + nb * C + box * 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[C + k] = has_lb ? bf16_float(bf16_bits(bf16_float(lsrc[k]) + bf16_float(lb[k]))) : bf16_float(lsrc[k]);
+        r[C + 4] = av0.x; r[C + 5] = av0.y; r[C + 6] = av0.z; r[C + 7] = av0.w;
+        r[C + 8] = av1.x; r[C + 9] = av1.y; r[C + 10] = av1.z; r[C + 11] = av1.w;
+    }
+}
+
+// Host: true where EVERY tile of the launch (B images, `nthreads` threads per tile = hp.TA anchors) takes head_build_rows' LDS-DMA
+// branch -- its `dma` condition restated per tile -- and the anchors' float4 loads are aligned: what head_row_regs relies on.
+static inline bool head_rows_all_dma(const HeadParams& hp, int B, int nthreads, const float* anchors_var) {
+    if (!hp.row_dma || hp.src_f32 || (nthreads & 63) || nthreads != hp.TA || ((uintptr_t)anchors_var & 15)) return false;
+    const int C = hp.C, TA = hp.TA;
+    for (int l = 0; l < hp.n_layers; ++l) {
+        const int nb = hp.n_boxes[l], stride = hp.conf_stride[l];
+        const int U = nb * (C + 4) * 2, cpr = (U + 15) >> 4, pitch = cpr * 16;
+        const size_t src_bytes = (size_t)B * (size_t)(hp.n_anchors[l] / nb) * (size_t)stride * 2;
+        if (hp.loc[l] != hp.conf[l] + (size_t)nb * C || hp.loc_stride[l] != stride || (stride & 7) || stride * 2 < pitch ||
+            ((uintptr_t)hp.conf[l] & 15) || src_bytes >= 0x7fffff00ull)
+            return false;
+        for (int a0 = 0; a0 < hp.n_anchors[l]; a0 += TA) {
+            const int na = hp.n_anchors[l] - a0 < TA ? hp.n_anchors[l] - a0 : TA;
+            const int pix0 = a0 / nb, npx = (a0 + na - 1) / nb - pix0 + 1, nchunks = npx * cpr;
+            if ((size_t)((nchunks + 63) >> 6) * 1024 + (size_t)U > head_stage_bytes(TA, C)) return false;
+        }
+    }
+    return true;
 }
 
 // Host side: validate the per-layer arrays of the C ABI and fill HeadParams.  Returns SSDHIP_OK or SSDHIP_E_BADARG; *tiles_out =

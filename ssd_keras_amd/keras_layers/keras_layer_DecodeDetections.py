@@ -57,7 +57,7 @@ class DecodeDetections(nn.Module):
     @torch.no_grad()
     def forward_from_heads(self, confs, locs, conf_biases, loc_biases, n_boxes, anchors_var, n_classes):
         """The same layer fed by the predictor heads' bf16 outputs instead of the assembled `(batch, #boxes, #classes + 12)`
-        tensor: bias, softmax, anchors and the decode happen in one kernel (`scan_heads_kernel`), the
+        tensor: bias, softmax, anchors and the decode happen in one kernel (`scan_heads_rows_kernel` / `scan_heads_kernel`), the
         prediction tensor never exists in HBM.  Same result, bit for bit, as `forward(assembled tensor)`."""
         ev = None
         if self.timing_events is not None:

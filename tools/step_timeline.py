@@ -3,7 +3,8 @@ the next, with start offsets, durations and the hardware queue in microseconds.
 
 bench.py issues, in this order: eager warm-up steps, graph warm-ups, the TIMED steps (graph replays unless --graph 0), ten eager steps for
 `decode_ms_in_step`, the per-kernel decode timing (the first `scan_kernel` of the trace), then the same step on TAMED heads (three
-warm-ups, the timed replays, ten eager steps).  A step decodes from the head outputs (`scan_heads_kernel`); the per-kernel timing calls
+warm-ups, the timed replays, ten eager steps).  A step decodes from the head outputs (`scan_heads_rows_kernel<21>`, or `scan_heads_kernel`
+with SSDHIP_SCAN_ROWS=lds and in traces of earlier builds); the per-kernel timing calls
 and `raw_predictions` do not and are skipped.  Three timelines are written (the old tool took "the last step that contains
 scan_heads_kernel", which since the tamed-heads leg is a tamed step -- its NMS row was not the headline's):
 
@@ -36,7 +37,7 @@ def main(trace, out, timed_steps=10):
     starts = [i for i, r in enumerate(rows) if "ssdhip::preprocess" in r[2]]          # preprocess_kernel / preprocess3_kernel (round 5)
     if len(starts) < 2:
         raise SystemExit("no complete step in the trace")
-    steps = [(a, b) for a, b in zip(starts[:-1], starts[1:]) if any("scan_heads_kernel" in r[2] for r in rows[a:b])
+    steps = [(a, b) for a, b in zip(starts[:-1], starts[1:]) if any(("scan_heads_kernel" in r[2] or "scan_heads_rows_kernel" in r[2]) for r in rows[a:b])
              and not any("scan_kernel(" in r[2] for r in rows[a:b])]
     first_scan = next((i for i, r in enumerate(rows) if "scan_kernel(" in r[2]), len(rows))
     head = [p for p in steps if p[1] <= first_scan]                    # the headline workload's steps
