@@ -1246,6 +1246,26 @@ int ssdhip_image_resize_gather_turn_ragged_u8(const void* x, const long long* ta
                                               const double* wy_dev, int ny, const int* transposed_dev, const void* background_dev,
                                               void* stream);
 
+/* ---- baseline JPEG decoding of a batch (csrc/ssdhip_jpeg.hip, csrc/ssdhip_jpeg_entropy.h) ----------------------------------------------
+ * data_generator/jpeg_decode.py parses the markers on the host and uploads ONE descriptor buffer `desc_dev` (16-byte aligned parts at
+ * the given byte offsets): images [n_images] (struct ssdhip_jpeg_image), segments [n_segments] (struct ssdhip_jpeg_segment: one per
+ * image and restart interval), quantisation tables [n_qt][64] uint16 in natural order, Huffman tables [n_huff] in look-up form
+ * (struct ssdhip_jpeg_huff), the compressed bytes of every segment [data_bytes], and one status word per image, uploaded as 0.
+ * stages (bit mask, each one launch): 1 entropy decoding -- one lane per segment, lanes_per_wave (1..64) segments per 64-lane
+ * workgroup -- into coef_dev (int16 [total_blocks][64]); 2 dequantisation + islow IDCT + range limit into planes_dev
+ * (uint8 [total_blocks][64] as per-component planes); 4 fancy upsampling + YCbCr -> RGB, cropped, into each image's out_offset of
+ * out_dev [out_bytes] ((H, W, 3) or, one component, (H, W)).  max_blocks / max_pixels: the largest image's.  The result equals
+ * libjpeg's default decode bit for bit; an image whose status word is non-zero afterwards (SSDHIP_JPEG_ST_*: truncated or corrupt
+ * entropy data, values no 8-bit image produces, a descriptor that does not fit the buffers) has no defined pixels and belongs to the
+ * host decoder.  No read leaves a segment's byte range, no write leaves the image's blocks or its output slot, whatever the
+ * compressed bytes are.  SSDHIP_E_BADARG for null / misaligned pointers, counts <= 0, n_images > 65535, parts outside desc_bytes.
+ * ssdhip_jpeg_layout: words[0..3] = ints per image descriptor, ints per segment, bytes per Huffman table, the output alignment. */
+int ssdhip_jpeg_layout(int* words);
+int ssdhip_jpeg_decode_batch(void* desc_dev, long long desc_bytes, int n_images, int n_segments, int n_qt, int n_huff, int off_images,
+                             int off_segments, int off_qt, int off_huff, int off_data, int data_bytes, int off_status, int max_blocks,
+                             int max_pixels, long long total_blocks, int lanes_per_wave, int stages, void* coef_dev, void* planes_dev,
+                             void* out_dev, long long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

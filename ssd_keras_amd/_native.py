@@ -248,6 +248,8 @@ SIGNATURES = {
     "ssdhip_image_program_ragged_lut_u8": (_I, [_P, _P, _P, _I, _LL] + [_P] * 4),
     "ssdhip_image_program_hist_u8": (_I, [_P, _P, _I, _LL] + [_P] * 7),
     "ssdhip_image_equalize_tables": (_I, [_P, _P, _P, _I, _P]),
+    "ssdhip_jpeg_layout": (_I, [_INTP]),
+    "ssdhip_jpeg_decode_batch": (_I, [_P, _LL] + [_I] * 13 + [_LL, _I, _I] + [_P] * 3 + [_LL, _P]),
 }
 
 

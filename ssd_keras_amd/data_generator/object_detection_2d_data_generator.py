@@ -23,8 +23,18 @@ chains read too).
     tables built on the device --, the ragged gather, the second segment on its output (which may end in float32 or float64).  A batch
     the lazy images cannot compose (NotImplementedError) goes through the per-image loop from the same random state;
   * anything else: the reference's per-image loop over the package's transforms.
-Every path gives the per-image loop's pixels, labels, inverters and final `np.random` state.  Images are decoded by PIL on the host, as in
-the reference.  HDF5 datasets are not supported (h5py is not a dependency of this package); their parameter and methods raise
+Every path gives the per-image loop's pixels, labels, inverters and final `np.random` state.
+
+Images are decoded by PIL on the host, as in the reference, unless the generator's `decode` attribute is 'device' (not in the
+reference; `DataGenerator.with_decode('device', ...)` constructs one, `generator.decode = 'device'` switches one -- the constructor
+keeps the reference's parameter list): then the files of a batch are decoded together on the device (`jpeg_decode.decode_jpeg_batch`: baseline JPEGs, bit for
+bit PIL's pixels; every other file, and every file the device reports as damaged, is still PIL's).  The decoded images stay on the
+device -- no download, no second upload -- when all of them were decoded there and the list takes the 'gather' path or one of the
+ragged chain paths (`[SSDDataAugmentation]`, `[DataAugmentationVariableInputSize]`, `[DataAugmentationSatellite]`; for these three
+every image must have three channels); in every other case (the 'constant' and 'program' paths, the per-image loop, no
+transformations, a batch with a host-decoded member, grayscale images in front of a chain) they are downloaded and everything goes
+on as with `decode='host'`.  'original_images' are NumPy arrays either way, and `load_images_into_memory=True` decodes the file list
+on the device in chunks of `jpeg_decode.CHUNK` (256) files and keeps the same list of NumPy arrays.  HDF5 datasets are not supported (h5py is not a dependency of this package); their parameter and methods raise
 `DatasetError`.  The parsers' XML reader is `xml.etree.ElementTree` (the reference uses BeautifulSoup) with the same results."""
 from __future__ import annotations
 
@@ -116,7 +126,7 @@ class DataGenerator:
             self.dataset_size = len(self.filenames)
             self.dataset_indices = np.arange(self.dataset_size, dtype=np.int32)
             if load_images_into_memory:
-                self.images = [_load_image(f) for f in _progress(self.filenames, 'Loading images into memory', verbose)]
+                self.images = self._load_all(verbose)
         else:
             self.filenames = None
 
@@ -128,6 +138,29 @@ class DataGenerator:
         if hdf5_dataset_path is not None:
             self.hdf5_dataset_path = hdf5_dataset_path
             self.load_hdf5_dataset(verbose=verbose)
+
+    _decode = 'host'
+
+    @property
+    def decode(self):
+        '''Who decodes the image files: 'host' (PIL, as in the reference; the default) or 'device' (baseline JPEGs on the GPU,
+        `jpeg_decode.decode_jpeg_batch`; see the module docstring).  Not in the reference.'''
+        return self._decode
+
+    @decode.setter
+    def decode(self, value):
+        if not isinstance(value, str) or value not in ('host', 'device'):
+            raise ValueError("`decode` can be either 'host' (PIL, as in the reference) or 'device' (baseline JPEGs on the GPU).")
+        self._decode = value
+
+    @classmethod
+    def with_decode(cls, decode, *args, **kwargs):
+        '''`DataGenerator(*args, **kwargs)` with `decode` set BEFORE the constructor runs, so that `load_images_into_memory=True`
+        already decodes as asked.  The constructor itself keeps the reference's parameters.'''
+        self = cls.__new__(cls)
+        self.decode = decode
+        self.__init__(*args, **kwargs)
+        return self
 
     @staticmethod
     def _list_or_pickle(value, name):
@@ -145,7 +178,17 @@ class DataGenerator:
         self.dataset_size = len(self.filenames)
         self.dataset_indices = np.arange(self.dataset_size, dtype=np.int32)
         if self.load_images_into_memory:
-            self.images = [_load_image(f) for f in _progress(self.filenames, 'Loading images into memory', verbose)]
+            self.images = self._load_all(verbose)
+
+    def _load_all(self, verbose):
+        """Every file of the dataset as a NumPy array: PIL file by file, or (decode='device') the device decoder chunk by chunk."""
+        if self.decode != 'device':
+            return [_load_image(f) for f in _progress(self.filenames, 'Loading images into memory', verbose)]
+        from . import jpeg_decode
+        images = []
+        for start in _progress(range(0, len(self.filenames), jpeg_decode.CHUNK), 'Loading images into memory', verbose):
+            images += jpeg_decode.to_host(jpeg_decode.decode_jpeg_batch(self.filenames[start:start + jpeg_decode.CHUNK]))
+        return images
 
     def load_hdf5_dataset(self, verbose=True):
         '''Reference :241-285 (h5py): not supported here.'''
@@ -352,7 +395,7 @@ class DataGenerator:
         from .object_detection_2d_patch_sampling_ops import RandomPadFixedAR
         from .object_detection_2d_photometric_ops import ConvertTo3Channels
         kinds = [type(t) for t in transformations]
-        if not images or any(not isinstance(im, np.ndarray) or im.dtype != np.uint8 for im in images):
+        if not images or any(not DataGenerator._is_uint8_image(im) for im in images):
             return None
         if any(im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] not in (1, 3, 4)) for im in images):
             return None
@@ -369,6 +412,25 @@ class DataGenerator:
             if kinds == [DataAugmentationSatellite]:
                 return 'satellite'
         return 'program' if DataGenerator._composable(transformations, images) else None
+
+    @staticmethod
+    def _is_uint8_image(im):
+        """A uint8 NumPy array, or (decode='device') a CUDA uint8 tensor."""
+        if isinstance(im, np.ndarray):
+            return im.dtype == np.uint8
+        import torch
+        return torch.is_tensor(im) and im.is_cuda and im.dtype == torch.uint8
+
+    @staticmethod
+    def _stays_on_device(transformations, images, have_labels):
+        """Whether a batch the device decoded is transformed where it is (module docstring): every image a device tensor, and a batch
+        path that reads a ragged device batch."""
+        if not transformations or any(isinstance(im, np.ndarray) for im in images):
+            return False
+        path = DataGenerator._batch_path(transformations, images, have_labels)
+        if path == 'gather':
+            return True
+        return path in ('ssd', 'variable', 'satellite') and all(im.ndim == 3 and im.shape[2] == 3 for im in images)
 
     @staticmethod
     def _composable(transformations, images):
@@ -433,7 +495,7 @@ class DataGenerator:
         return img, lab, inv[::-1]
 
     def _transform_batch(self, path, transformations, images, labels, want_inverters):
-        """The batch paths: images (uint8 NumPy) and labels (arrays, or None) of the items that are transformed -> (CUDA (n, H, W, 3)
+        """The batch paths: images (uint8 NumPy; CUDA uint8 tensors for 'gather' and the ragged chains) and labels (arrays, or None) of the items that are transformed -> (CUDA (n, H, W, 3)
         batch -- uint8, or what a 'program' list ends in --, labels or None, inverters per item).  'program' raises NotImplementedError,
         with both random generators where they were, for a batch its lazy images cannot compose."""
         import torch
@@ -548,14 +610,24 @@ class DataGenerator:
                 batch_filenames = self.filenames[current:current + batch_size] if self.filenames is not None else None
             else:
                 batch_filenames = self.filenames[current:current + batch_size]
-                for filename in batch_filenames:
-                    batch_X.append(_load_image(filename))
+                if self.decode == 'device':
+                    from . import jpeg_decode
+                    batch_X = jpeg_decode.decode_jpeg_batch(batch_filenames)
+                    if not self._stays_on_device(transformations, batch_X, self.labels is not None):
+                        batch_X = jpeg_decode.to_host(batch_X)
+                else:
+                    for filename in batch_filenames:
+                        batch_X.append(_load_image(filename))
 
             batch_y = deepcopy(self.labels[current:current + batch_size]) if self.labels is not None else None
             batch_eval_neutral = self.eval_neutral[current:current + batch_size] if self.eval_neutral is not None else None
             batch_image_ids = self.image_ids[current:current + batch_size] if self.image_ids is not None else None
             if 'original_images' in returns:
-                batch_original_images = deepcopy(batch_X)
+                if any(not isinstance(im, np.ndarray) for im in batch_X):
+                    from . import jpeg_decode
+                    batch_original_images = jpeg_decode.to_host(batch_X)
+                else:
+                    batch_original_images = deepcopy(batch_X)
             if 'original_labels' in returns:
                 batch_original_labels = deepcopy(batch_y)
             current += batch_size
