@@ -1266,6 +1266,26 @@ int ssdhip_jpeg_decode_batch(void* desc_dev, long long desc_bytes, int n_images,
                              int max_pixels, long long total_blocks, int lanes_per_wave, int stages, void* coef_dev, void* planes_dev,
                              void* out_dev, long long out_bytes, void* stream);
 
+/* The same call with an entry-point index for files without restart markers (one segment, hence one lane above).  Two more parts of
+ * desc_dev: entries [n_entries] (struct ssdhip_jpeg_entry, 8 ints: image, byte, bit, first_mcu, n_mcus, pred0..2 -- where an MCU row
+ * starts in the batch's compressed bytes and the DC predictors there; an image's entries in a row, in MCU order) and one mode word
+ * per image: low 2 bits 0 = the per-segment path, 1 = indexed (the bits above: the image's segment), 2 = record (the bits above:
+ * the image's first row in ckpt_dev).  Stage 1 is two launches: jpeg_entropy_entry_kernel, one lane per entry
+ * (entry_lanes_per_wave per workgroup), each lane decoding its entry's MCUs and verifying that it ends exactly on the next entry
+ * (status SSDHIP_JPEG_ST_INDEX = 32 otherwise: a wrong index sets the status and never yields other pixels); and
+ * jpeg_entropy_record_kernel, one lane per segment of the other images (lanes_per_wave per workgroup; skipped for record_segments
+ * == 0): the sequential decode, which for mode 2 also writes the entry of every MCU row to ckpt_dev [ckpt_entries][8] ints (16-byte
+ * aligned; valid where the image's status stays 0).  Index fields are untrusted like the bytes: no access leaves the segment, the
+ * image's blocks or ckpt_dev.  Stages 2 and 4 are those of ssdhip_jpeg_decode_batch.
+ * ssdhip_jpeg_entry_layout: words[0..1] = ints per entry, the value of SSDHIP_JPEG_ST_INDEX. */
+int ssdhip_jpeg_entry_layout(int* words);
+int ssdhip_jpeg_decode_batch_indexed(void* desc_dev, long long desc_bytes, int n_images, int n_segments, int n_qt, int n_huff,
+                                     int off_images, int off_segments, int off_qt, int off_huff, int off_data, int data_bytes,
+                                     int off_status, int off_entries, int n_entries, int off_modes, void* ckpt_dev, int ckpt_entries,
+                                     int record_segments, int max_blocks, int max_pixels, long long total_blocks,
+                                     int entry_lanes_per_wave, int lanes_per_wave, int stages, void* coef_dev, void* planes_dev,
+                                     void* out_dev, long long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,8 @@ SIGNATURES = {
     "ssdhip_image_equalize_tables": (_I, [_P, _P, _P, _I, _P]),
     "ssdhip_jpeg_layout": (_I, [_INTP]),
     "ssdhip_jpeg_decode_batch": (_I, [_P, _LL] + [_I] * 13 + [_LL, _I, _I] + [_P] * 3 + [_LL, _P]),
+    "ssdhip_jpeg_entry_layout": (_I, [_INTP]),
+    "ssdhip_jpeg_decode_batch_indexed": (_I, [_P, _LL] + [_I] * 14 + [_P] + [_I] * 4 + [_LL] + [_I] * 3 + [_P] * 3 + [_LL, _P]),
 }
 
 

@@ -1,7 +1,8 @@
 // Baseline JPEG decoding of a batch on the device, bit for bit what libjpeg(-turbo) returns with its default settings (the "islow"
 // IDCT, "fancy" chroma upsampling, the 16-bit fixed-point YCbCr -> RGB tables): data_generator/jpeg_decode.py parses the markers on
 // the host and uploads ONE descriptor buffer; three launches turn it into the images.
-//   1. jpeg_entropy_kernel  one LANE per (image, restart segment): csrc/ssdhip_jpeg_entropy.h, int16 coefficients [block][64];
+//   1. jpeg_entropy_kernel  one LANE per (image, restart segment): csrc/ssdhip_jpeg_entropy.h, int16 coefficients [block][64]
+//                           (with an entry-point index: jpeg_entropy_entry_kernel + jpeg_entropy_record_kernel, section 1' below);
 //   2. jpeg_block_kernel    one thread per 8 x 8 block, the block in registers: dequantise, IDCT, range limit -> sample planes,
 //                           one per component, padded to whole blocks;
 //   3. jpeg_pixel_kernel    one thread per output pixel: upsample the chroma planes, convert, crop to H x W, store into the image's
@@ -19,6 +20,7 @@ namespace {
 static_assert(sizeof(ssdhip_jpeg_image) == 4 * SSDHIP_JPEG_IMAGE_WORDS, "image descriptor layout");
 static_assert(sizeof(ssdhip_jpeg_segment) == 4 * SSDHIP_JPEG_SEGMENT_WORDS, "segment descriptor layout");
 static_assert(sizeof(ssdhip_jpeg_huff) == SSDHIP_JPEG_HUFF_BYTES, "Huffman table layout");
+static_assert(sizeof(ssdhip_jpeg_entry) == 4 * SSDHIP_JPEG_ENTRY_WORDS, "entry layout");
 
 struct JpegBatch {
     const ssdhip_jpeg_image* images;
@@ -51,6 +53,69 @@ __global__ void __launch_bounds__(64) jpeg_entropy_kernel(JpegBatch b, int lanes
     const ssdhip_jpeg_segment seg = b.segments[s];
     if (seg.image < 0 || seg.image >= b.n_images) return;        // no image to blame: the host checks the table it builds
     const int st = ssdhip_jpeg_decode_segment(b.images + seg.image, &seg, b.huff, b.n_huff, b.data, b.data_bytes, coef, b.total_blocks);
+    if (st != 0) b.status[seg.image] = st;
+}
+
+// ---- 1'. entropy with an entry-point index (ssdhip_jpeg_decode_batch_indexed) -----------------------------------------------------------
+// A file without restart markers is one segment, hence one lane of the kernel above.  Its MCU rows can be decoded by a lane each once
+// the host knows where every row starts: the RECORD kernel decodes such a file sequentially, once, and writes those entries; from
+// then on the ENTRY kernel decodes it with one lane per entry, every lane checking that it ends on the next entry (header comment of
+// ssdhip_jpeg_entropy.h: a wrong entry can only set the status, never yield other coefficients).
+// modes[image]: low 2 bits 0 = the per-segment path, 1 = indexed, 2 = record; the bits above: for 1 the image's segment, for 2 the
+// image's first row in the checkpoint buffer.
+struct JpegIndexArgs {
+    const ssdhip_jpeg_entry* entries;  // [n_entries], an image's entries in a row, in MCU order
+    const int* modes;                  // [n_images]
+    ssdhip_jpeg_entry* ckpt;           // [ckpt_entries]
+    int n_entries, ckpt_entries;
+};
+
+__global__ void __launch_bounds__(64) jpeg_entropy_entry_kernel(JpegBatch b, JpegIndexArgs x, int lanes, short* coef) {
+    const int lane = threadIdx.x;
+    if (lane >= lanes) return;
+    const long long e = (long long)blockIdx.x * lanes + lane;
+    if (e >= x.n_entries) return;
+    const ssdhip_jpeg_entry entry = x.entries[e];
+    if (entry.image < 0 || entry.image >= b.n_images) return;    // no image to blame: the host checks the table it builds
+    const int mode = x.modes[entry.image];
+    const int s = mode >> 2;
+    int st;
+    if ((mode & 3) != 1 || s < 0 || s >= b.n_segments || b.segments[s].image != entry.image) {
+        st = SSDHIP_JPEG_ST_DESC;
+    } else {
+        const ssdhip_jpeg_segment seg = b.segments[s];
+        const bool first = e == 0 || x.entries[e - 1].image != entry.image;
+        const bool last = e + 1 >= x.n_entries || x.entries[e + 1].image != entry.image;
+        ssdhip_jpeg_entry next = entry;
+        if (!last) next = x.entries[e + 1];
+        st = ssdhip_jpeg_decode_span(b.images + entry.image, &seg, &entry, last ? nullptr : &next, first ? 1 : 0, b.huff, b.n_huff, b.data,
+                                     b.data_bytes, coef, b.total_blocks, nullptr, 0);
+    }
+    if (st != 0) b.status[entry.image] = st;
+}
+
+// One lane per segment of the images the entry kernel does not decode: the per-segment path as it is, or (mode 2) the same sequential
+// decode that also records the image's entries, one per MCU row, at ckpt[the image's first row + MCU row].
+__global__ void __launch_bounds__(64) jpeg_entropy_record_kernel(JpegBatch b, JpegIndexArgs x, int lanes, short* coef) {
+    const int lane = threadIdx.x;
+    if (lane >= lanes) return;
+    const long long s = (long long)blockIdx.x * lanes + lane;
+    if (s >= b.n_segments) return;
+    const ssdhip_jpeg_segment seg = b.segments[s];
+    if (seg.image < 0 || seg.image >= b.n_images) return;
+    const int mode = x.modes[seg.image];
+    if ((mode & 3) == 1) return;                                 // the entry kernel's
+    int st;
+    if ((mode & 3) == 2) {
+        const int base = mode >> 2;
+        if (base < 0 || base >= x.ckpt_entries)
+            st = SSDHIP_JPEG_ST_DESC;
+        else
+            st = ssdhip_jpeg_decode_span(b.images + seg.image, &seg, nullptr, nullptr, 0, b.huff, b.n_huff, b.data, b.data_bytes, coef,
+                                         b.total_blocks, x.ckpt + base, x.ckpt_entries - base);
+    } else {
+        st = ssdhip_jpeg_decode_segment(b.images + seg.image, &seg, b.huff, b.n_huff, b.data, b.data_bytes, coef, b.total_blocks);
+    }
     if (st != 0) b.status[seg.image] = st;
 }
 
@@ -217,25 +282,38 @@ extern "C" int ssdhip_jpeg_layout(int* words) {
     return SSDHIP_OK;
 }
 
-extern "C" int ssdhip_jpeg_decode_batch(void* desc_dev, long long desc_bytes, int n_images, int n_segments, int n_qt, int n_huff,
-                                        int off_images, int off_segments, int off_qt, int off_huff, int off_data, int data_bytes,
-                                        int off_status, int max_blocks, int max_pixels, long long total_blocks, int lanes_per_wave,
-                                        int stages, void* coef_dev, void* planes_dev, void* out_dev, long long out_bytes,
-                                        void* stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+extern "C" int ssdhip_jpeg_entry_layout(int* words) {
+    if (!words) return SSDHIP_E_BADARG;
+    words[0] = SSDHIP_JPEG_ENTRY_WORDS, words[1] = SSDHIP_JPEG_ST_INDEX;
+    return SSDHIP_OK;
+}
+
+namespace {
+
+// Both exports: check the arguments, then stage 1 (the per-segment kernel, or with `x` the entry and record kernels), 2 and 4.
+int jpeg_decode_batch(void* desc_dev, long long desc_bytes, int n_images, int n_segments, int n_qt, int n_huff, int off_images,
+                      int off_segments, int off_qt, int off_huff, int off_data, int data_bytes, int off_status, int max_blocks,
+                      int max_pixels, long long total_blocks, int lanes_per_wave, int stages, void* coef_dev, void* planes_dev,
+                      void* out_dev, long long out_bytes, hipStream_t stream, bool indexed, int off_entries, int n_entries, int off_modes,
+                      void* ckpt_dev, int ckpt_entries, int record_segments, int entry_lanes_per_wave) {
     if (!desc_dev || !coef_dev || !planes_dev || !out_dev || n_images <= 0 || n_images > 65535 || n_segments <= 0 || n_qt <= 0 ||
         n_huff <= 0 || data_bytes < 0 || max_blocks <= 0 || max_pixels <= 0 || total_blocks <= 0 || out_bytes <= 0 ||
         lanes_per_wave < 1 || lanes_per_wave > 64 || (stages & ~7) != 0)
         return SSDHIP_E_BADARG;
-    const long long parts[6][2] = {{off_images, 4LL * SSDHIP_JPEG_IMAGE_WORDS * n_images},
+    const long long parts[8][2] = {{off_images, 4LL * SSDHIP_JPEG_IMAGE_WORDS * n_images},
                                    {off_segments, 4LL * SSDHIP_JPEG_SEGMENT_WORDS * n_segments},
                                    {off_qt, 128LL * n_qt},
                                    {off_huff, (long long)SSDHIP_JPEG_HUFF_BYTES * n_huff},
                                    {off_data, data_bytes},
-                                   {off_status, 4LL * n_images}};
-    for (const auto& p : parts)
-        if (p[0] < 0 || (p[0] & 15) != 0 || p[0] + p[1] > desc_bytes) return SSDHIP_E_BADARG;
+                                   {off_status, 4LL * n_images},
+                                   {off_entries, 4LL * SSDHIP_JPEG_ENTRY_WORDS * n_entries},
+                                   {off_modes, 4LL * n_images}};
+    for (int k = 0; k < (indexed ? 8 : 6); ++k)
+        if (parts[k][0] < 0 || (parts[k][0] & 15) != 0 || parts[k][0] + parts[k][1] > desc_bytes) return SSDHIP_E_BADARG;
     if ((reinterpret_cast<uintptr_t>(desc_dev) | reinterpret_cast<uintptr_t>(coef_dev) | reinterpret_cast<uintptr_t>(planes_dev)) & 15)
+        return SSDHIP_E_BADARG;
+    if (indexed && (n_entries < 0 || ckpt_entries < 0 || (ckpt_entries > 0 && !ckpt_dev) || (reinterpret_cast<uintptr_t>(ckpt_dev) & 15) ||
+                    record_segments < 0 || record_segments > n_segments || entry_lanes_per_wave < 1 || entry_lanes_per_wave > 64))
         return SSDHIP_E_BADARG;
     unsigned char* base = static_cast<unsigned char*>(desc_dev);
     JpegBatch b;
@@ -247,9 +325,26 @@ extern "C" int ssdhip_jpeg_decode_batch(void* desc_dev, long long desc_bytes, in
     b.status = reinterpret_cast<int*>(base + off_status);
     b.n_images = n_images, b.n_segments = n_segments, b.n_qt = n_qt, b.n_huff = n_huff, b.data_bytes = data_bytes;
     b.total_blocks = total_blocks, b.out_bytes = out_bytes;
-    if (stages & 1) {
+    if ((stages & 1) && !indexed) {
         const unsigned int groups = (unsigned int)((n_segments + lanes_per_wave - 1) / lanes_per_wave);
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(groups), dim3(64), 0, stream, b, lanes_per_wave, static_cast<short*>(coef_dev));
+    }
+    if ((stages & 1) && indexed) {
+        JpegIndexArgs x;
+        x.entries = reinterpret_cast<const ssdhip_jpeg_entry*>(base + off_entries);
+        x.modes = reinterpret_cast<const int*>(base + off_modes);
+        x.ckpt = static_cast<ssdhip_jpeg_entry*>(ckpt_dev);
+        x.n_entries = n_entries, x.ckpt_entries = ckpt_entries;
+        if (n_entries > 0) {
+            const unsigned int groups = (unsigned int)((n_entries + entry_lanes_per_wave - 1) / entry_lanes_per_wave);
+            hipLaunchKernelGGL(jpeg_entropy_entry_kernel, dim3(groups), dim3(64), 0, stream, b, x, entry_lanes_per_wave,
+                               static_cast<short*>(coef_dev));
+        }
+        if (record_segments > 0) {                               // (0: every image has an index)
+            const unsigned int groups = (unsigned int)((n_segments + lanes_per_wave - 1) / lanes_per_wave);
+            hipLaunchKernelGGL(jpeg_entropy_record_kernel, dim3(groups), dim3(64), 0, stream, b, x, lanes_per_wave,
+                               static_cast<short*>(coef_dev));
+        }
     }
     if (stages & 2)
         hipLaunchKernelGGL(jpeg_block_kernel, dim3((unsigned int)((max_blocks + 255) / 256), (unsigned int)n_images), dim3(256), 0, stream,
@@ -258,4 +353,28 @@ extern "C" int ssdhip_jpeg_decode_batch(void* desc_dev, long long desc_bytes, in
         hipLaunchKernelGGL(jpeg_pixel_kernel, dim3((unsigned int)((max_pixels + 255) / 256), (unsigned int)n_images), dim3(256), 0, stream,
                            b, static_cast<const unsigned char*>(planes_dev), static_cast<unsigned char*>(out_dev));
     return hipGetLastError() == hipSuccess ? SSDHIP_OK : SSDHIP_E_LAUNCH;
+}
+
+}  // namespace
+
+extern "C" int ssdhip_jpeg_decode_batch(void* desc_dev, long long desc_bytes, int n_images, int n_segments, int n_qt, int n_huff,
+                                        int off_images, int off_segments, int off_qt, int off_huff, int off_data, int data_bytes,
+                                        int off_status, int max_blocks, int max_pixels, long long total_blocks, int lanes_per_wave,
+                                        int stages, void* coef_dev, void* planes_dev, void* out_dev, long long out_bytes,
+                                        void* stream_) {
+    return jpeg_decode_batch(desc_dev, desc_bytes, n_images, n_segments, n_qt, n_huff, off_images, off_segments, off_qt, off_huff, off_data,
+                             data_bytes, off_status, max_blocks, max_pixels, total_blocks, lanes_per_wave, stages, coef_dev, planes_dev,
+                             out_dev, out_bytes, static_cast<hipStream_t>(stream_), false, 0, 0, 0, nullptr, 0, 0, 1);
+}
+
+extern "C" int ssdhip_jpeg_decode_batch_indexed(void* desc_dev, long long desc_bytes, int n_images, int n_segments, int n_qt, int n_huff,
+                                                int off_images, int off_segments, int off_qt, int off_huff, int off_data, int data_bytes,
+                                                int off_status, int off_entries, int n_entries, int off_modes, void* ckpt_dev,
+                                                int ckpt_entries, int record_segments, int max_blocks, int max_pixels,
+                                                long long total_blocks, int entry_lanes_per_wave, int lanes_per_wave, int stages,
+                                                void* coef_dev, void* planes_dev, void* out_dev, long long out_bytes, void* stream_) {
+    return jpeg_decode_batch(desc_dev, desc_bytes, n_images, n_segments, n_qt, n_huff, off_images, off_segments, off_qt, off_huff, off_data,
+                             data_bytes, off_status, max_blocks, max_pixels, total_blocks, lanes_per_wave, stages, coef_dev, planes_dev,
+                             out_dev, out_bytes, static_cast<hipStream_t>(stream_), true, off_entries, n_entries, off_modes, ckpt_dev,
+                             ckpt_entries, record_segments, entry_lanes_per_wave);
 }

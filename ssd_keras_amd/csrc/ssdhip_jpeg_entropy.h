@@ -13,6 +13,14 @@
 //     segment too.  libjpeg only warns about those and goes on; here the image goes back to the host decoder, whose result or
 //     exception is what the caller sees.
 // The caller gets the status as the return value and stores it (ordinary stores; a non-zero word per image).
+//
+// A segment can also be entered at the start of any MCU row, given an ENTRY: where the next unread bit lies and what the DC predictors
+// are there (struct ssdhip_jpeg_entry).  `ssdhip_jpeg_decode_span` RECORDS the entries of a segment while it decodes it sequentially,
+// and later decodes one entry's MCUs alone, one lane per entry.  Each lane VERIFIES that it ends exactly where the next entry begins
+// (byte, bit, predictors, MCU number), the first entry must be the segment's own start and the last must end at its last MCU: so if
+// every lane returns 0, lane 0 decoded what the sequential decoder decodes, ended in the sequential decoder's state, which is lane
+// 1's entry, and so on -- the coefficients are the sequential ones by induction, whatever the entries were.  Entries are untrusted
+// input like the bytes: a field out of range is SSDHIP_JPEG_ST_DESC, an entry that does not chain SSDHIP_JPEG_ST_INDEX.
 #ifndef SSDHIP_JPEG_ENTROPY_H
 #define SSDHIP_JPEG_ENTROPY_H
 
@@ -27,10 +35,12 @@
 #define SSDHIP_JPEG_ST_RUN 4         /* a zero run or ZRL that passes coefficient 63                 */
 #define SSDHIP_JPEG_ST_RANGE 8       /* block stage: values no 8-bit image produces (ssdhip_jpeg.hip) */
 #define SSDHIP_JPEG_ST_DESC 16       /* a descriptor that does not describe the buffers              */
+#define SSDHIP_JPEG_ST_INDEX 32      /* an entry the lane in front of it does not end on (or a first / last entry that is none) */
 
 #define SSDHIP_JPEG_IMAGE_WORDS 24
 #define SSDHIP_JPEG_SEGMENT_WORDS 4
 #define SSDHIP_JPEG_HUFF_BYTES 912
+#define SSDHIP_JPEG_ENTRY_WORDS 8
 
 // One Huffman table in look-up form.  look[b]: (code length << 8) | symbol for the code that starts the 8 bits b, 0 if it is longer
 // than 8 bits; maxcode[l] the largest code of length l (-1: none), valoff[l] = index of its first symbol minus its first code.
@@ -53,6 +63,13 @@ struct ssdhip_jpeg_image {
 
 struct ssdhip_jpeg_segment {
     int image, begin, end, first_mcu;                            // begin / end: byte range in the batch's compressed bytes
+};
+
+// One entry point into a segment (SSDHIP_JPEG_ENTRY_WORDS ints): MCUs first_mcu .. first_mcu + n_mcus - 1 of `image` start at bit
+// `bit` (0..7, counted from the most significant) of the raw byte at offset `byte` of the batch's compressed bytes -- the byte that
+// holds the next unread bit, never the 00 of an FF 00 pair -- with the DC predictors pred0..2.
+struct ssdhip_jpeg_entry {
+    int image, byte, bit, first_mcu, n_mcus, pred0, pred1, pred2;
 };
 
 struct ssdhip_jpeg_bits {
@@ -85,8 +102,8 @@ SSDHIP_JPEG_HD static inline void ssdhip_jpeg_fill(ssdhip_jpeg_bits& r) {
                 if (r.pos < r.end && r.data[r.pos] == 0) {
                     ++r.pos;                                     // FF 00: a stuffed FF
                 } else {
-                    b = 0;                                       // a marker (or the end right behind FF): no data from here on
-                    r.pos = r.end;
+                    b = 0;                                       // a marker (or the end right behind FF): no data from here on,
+                    r.end = --r.pos;                             // and pos stays on the first byte that is none
                     r.fake += 8;
                 }
             }
@@ -133,13 +150,28 @@ SSDHIP_JPEG_HD static inline int ssdhip_jpeg_extend(unsigned int v, int s) {
     return s == 0 ? 0 : ((int)v < (1 << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v);
 }
 
-// Decode segment `seg` of image `im`: its MCUs first_mcu .. first_mcu + interval - 1 (clipped to the image), coefficients as int16
-// [block][64] in natural order into `coef` (the WHOLE workspace of `coef_blocks` blocks; this function zero-fills and writes only
-// the segment's own blocks, each checked against coef_blocks).  `huff`: the batch's n_huff tables, `data`: its data_bytes
-// compressed bytes.  Returns 0 or the status that stopped the segment.
-SSDHIP_JPEG_HD static inline int ssdhip_jpeg_decode_segment(const ssdhip_jpeg_image* im, const ssdhip_jpeg_segment* seg,
-                                                            const ssdhip_jpeg_huff* huff, int n_huff, const unsigned char* data,
-                                                            int data_bytes, short* coef, long long coef_blocks) {
+// Where the next unread bit lies in the raw bytes: the reader is `real` = nbits - fake genuine bits ahead of it, so step back from
+// pos over ceil(real / 8) data bytes (a trip count fixed before the loop starts, at most 8), taking FF 00 as the one byte it is.  A
+// 00 behind an FF is always the stuffing, never data.  Reads stay inside [begin, pos).
+SSDHIP_JPEG_HD static inline void ssdhip_jpeg_position(const ssdhip_jpeg_bits& r, int begin, int* byte, int* bit) {
+    const int real = r.nbits > r.fake ? r.nbits - r.fake : 0;
+    const int back = (real + 7) >> 3;
+    int q = r.pos;
+    for (int i = 0; i < back; ++i) {
+        if (q > begin) --q;
+        if (q > begin && q < r.pos && r.data[q] == 0 && r.data[q - 1] == 0xFF) --q;
+    }
+    *byte = q;
+    *bit = back * 8 - real;
+}
+
+// The one decoder behind ssdhip_jpeg_decode_segment and ssdhip_jpeg_decode_span (always inlined: each caller passes constants for
+// the modes it does not use).  entry == null: the segment from its start; else that entry's MCUs, `first` saying that no entry of the
+// segment precedes it.  next: the entry to end on (verifying mode).  ckpt: ckpt_rows entries to record into, [MCU row].
+SSDHIP_JPEG_HD static inline __attribute__((always_inline)) int ssdhip_jpeg_decode_core(
+    const ssdhip_jpeg_image* im, const ssdhip_jpeg_segment* seg, const ssdhip_jpeg_huff* huff, int n_huff, const unsigned char* data,
+    int data_bytes, short* coef, long long coef_blocks, const ssdhip_jpeg_entry* entry, int first, const ssdhip_jpeg_entry* next,
+    ssdhip_jpeg_entry* ckpt, int ckpt_rows) {
     const unsigned char natural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                        41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                        30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
@@ -150,15 +182,44 @@ SSDHIP_JPEG_HD static inline int ssdhip_jpeg_decode_segment(const ssdhip_jpeg_im
     const int total = mcux * mcuy;
     if (seg->first_mcu < 0 || seg->first_mcu >= total || seg->begin < 0 || seg->end < seg->begin || seg->end > data_bytes)
         return SSDHIP_JPEG_ST_DESC;
-    const int last_mcu = im->interval < total - seg->first_mcu ? seg->first_mcu + im->interval : total;
+    int last_mcu = im->interval < total - seg->first_mcu ? seg->first_mcu + im->interval : total;
+    int first_mcu = seg->first_mcu;
 
     ssdhip_jpeg_bits r;
     r.data = data, r.pos = seg->begin, r.end = seg->end, r.acc = 0, r.nbits = 0, r.fake = 0;
     int pred0 = 0, pred1 = 0, pred2 = 0;                         // (scalars, not arrays indexed by c: those would live in scratch memory)
     const int base1 = mcux * hs * mcuy * vs, base2 = base1 + mcux * mcuy;   // component grids inside the image's blocks
 
-    for (int mcu = seg->first_mcu; mcu < last_mcu; ++mcu) {
+    if (entry) {                                                 // every field is untrusted
+        const int bit = entry->bit & 7;
+        if (entry->first_mcu < first_mcu || entry->first_mcu >= last_mcu || entry->n_mcus < 1 ||
+            entry->n_mcus > last_mcu - entry->first_mcu || entry->byte < seg->begin || entry->byte > seg->end || bit != entry->bit)
+            return SSDHIP_JPEG_ST_DESC;
+        if (first && (entry->first_mcu != first_mcu || entry->byte != seg->begin || bit != 0 || entry->pred0 != 0 || entry->pred1 != 0 ||
+                      entry->pred2 != 0))
+            return SSDHIP_JPEG_ST_INDEX;
+        if (next ? next->first_mcu != entry->first_mcu + entry->n_mcus : entry->first_mcu + entry->n_mcus != last_mcu)
+            return SSDHIP_JPEG_ST_INDEX;
+        first_mcu = entry->first_mcu, last_mcu = entry->first_mcu + entry->n_mcus;
+        pred0 = entry->pred0, pred1 = entry->pred1, pred2 = entry->pred2;
+        r.pos = entry->byte;
+        if (bit != 0) {                                          // drop the bits of the first byte that belong to the MCU in front
+            ssdhip_jpeg_fill(r);
+            r.nbits -= bit;
+            if (r.nbits < r.fake) return SSDHIP_JPEG_ST_TRUNCATED;
+        }
+    }
+
+    for (int mcu = first_mcu; mcu < last_mcu; ++mcu) {
         const int my = mcu / mcux, mx = mcu - my * mcux;
+        if (ckpt && (mx == 0 || mcu == first_mcu)) {             // recording: the entry of this MCU row
+            if (my >= ckpt_rows) return SSDHIP_JPEG_ST_DESC;
+            ssdhip_jpeg_entry e;
+            ssdhip_jpeg_position(r, seg->begin, &e.byte, &e.bit);
+            e.image = seg->image, e.first_mcu = mcu, e.n_mcus = mcux - mx < last_mcu - mcu ? mcux - mx : last_mcu - mcu;
+            e.pred0 = pred0, e.pred1 = pred1, e.pred2 = pred2;
+            ckpt[my] = e;
+        }
         for (int c = 0; c < ncomp; ++c) {
             const int ch = c == 0 ? hs : 1, cv = c == 0 ? vs : 1;
             const int grid_base = c == 0 ? 0 : (c == 1 ? base1 : base2), grid_w = c == 0 ? mcux * hs : mcux;
@@ -201,7 +262,41 @@ SSDHIP_JPEG_HD static inline int ssdhip_jpeg_decode_segment(const ssdhip_jpeg_im
             }
         }
     }
+    if (next) {                                                  // verifying: this lane ends exactly where the next one was told to start
+        int byte, bit;
+        ssdhip_jpeg_position(r, seg->begin, &byte, &bit);
+        if (byte != next->byte || bit != next->bit || pred0 != next->pred0 || pred1 != next->pred1 || pred2 != next->pred2)
+            return SSDHIP_JPEG_ST_INDEX;
+    }
     return 0;
+}
+
+// Decode segment `seg` of image `im`: its MCUs first_mcu .. first_mcu + interval - 1 (clipped to the image), coefficients as int16
+// [block][64] in natural order into `coef` (the WHOLE workspace of `coef_blocks` blocks; this function zero-fills and writes only
+// the segment's own blocks, each checked against coef_blocks).  `huff`: the batch's n_huff tables, `data`: its data_bytes
+// compressed bytes.  Returns 0 or the status that stopped the segment.
+SSDHIP_JPEG_HD static inline int ssdhip_jpeg_decode_segment(const ssdhip_jpeg_image* im, const ssdhip_jpeg_segment* seg,
+                                                            const ssdhip_jpeg_huff* huff, int n_huff, const unsigned char* data,
+                                                            int data_bytes, short* coef, long long coef_blocks) {
+    return ssdhip_jpeg_decode_core(im, seg, huff, n_huff, data, data_bytes, coef, coef_blocks, nullptr, 0, nullptr, nullptr, 0);
+}
+
+// Two modes, both writing coefficients exactly as ssdhip_jpeg_decode_segment does (zero-filling every block they start).
+//   RECORDING (ckpt_out != null; entry, next_entry ignored): the whole segment, sequentially; at the start of MCU row `my` the entry
+//     that describes that point goes to ckpt_out[my] (my < ckpt_rows is checked).  Status 0 means every row's entry was written.
+//   SPAN (ckpt_out == null): the MCUs of `entry` only.  `first` != 0: no entry of the segment precedes it, so it must be the
+//     segment's start.  next_entry != null: the lane must end on it (VERIFYING, header comment); null: the entry must end at the
+//     segment's last MCU, and the sequential rules hold from there.  SSDHIP_JPEG_ST_DESC for a field outside the segment / image,
+//     SSDHIP_JPEG_ST_INDEX for an entry that does not chain; never a read or write out of range.
+SSDHIP_JPEG_HD static inline int ssdhip_jpeg_decode_span(const ssdhip_jpeg_image* im, const ssdhip_jpeg_segment* seg,
+                                                         const ssdhip_jpeg_entry* entry, const ssdhip_jpeg_entry* next_entry, int first,
+                                                         const ssdhip_jpeg_huff* huff, int n_huff, const unsigned char* data,
+                                                         int data_bytes, short* coef, long long coef_blocks,
+                                                         ssdhip_jpeg_entry* ckpt_out, int ckpt_rows) {
+    if (ckpt_out)
+        return ssdhip_jpeg_decode_core(im, seg, huff, n_huff, data, data_bytes, coef, coef_blocks, nullptr, 0, nullptr, ckpt_out, ckpt_rows);
+    if (!entry) return SSDHIP_JPEG_ST_DESC;
+    return ssdhip_jpeg_decode_core(im, seg, huff, n_huff, data, data_bytes, coef, coef_blocks, entry, first, next_entry, nullptr, 0);
 }
 
 #endif /* SSDHIP_JPEG_ENTROPY_H */

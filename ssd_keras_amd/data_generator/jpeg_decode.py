@@ -14,18 +14,29 @@ for progressive, lossless, arithmetic-coded and 12-bit files, CMYK / YCCK, Adobe
 factors, several scans, a table the scan names but the file lacks, a segment length that leaves the file -- and for anything that is
 no JPEG.  PIL decodes those as before, and it decodes every image whose device status word is set (truncated or corrupt entropy data,
 csrc/ssdhip_jpeg_entropy.h): PIL's own result, or its exception, is what the caller gets.
+
+A file without restart markers is one segment, so one lane decodes it however large the batch is.  Training reads the same files every
+epoch: with a `JpegIndex` (`decode_jpeg_batch(..., index=...)`) such a file is decoded sequentially ONCE while the device records
+where every MCU row starts (byte, bit, DC predictors: 32 bytes per row), and from its second sight on with one lane per MCU row.  Each
+lane checks that it ends exactly on the next row's entry, so a wrong or stale index cannot give other pixels: the file's status word is
+set, its entry is dropped and it is decoded again by the recording route in the same call.
 """
 from __future__ import annotations
 
 import ctypes
+import hashlib
 
 import numpy as np
 
 from .. import _native as nat
 
 # How often each thing happened since import (tests and tools read and reset these): images the device decoded, images PIL decoded
-# inside decode_jpeg_batch, device images copied back to the host by `to_host`.
-COUNTERS = {"device": 0, "host": 0, "downloaded": 0}
+# inside decode_jpeg_batch, device images copied back to the host by `to_host`; of the device's images, those decoded through their
+# index entry ("indexed") and those whose entry was recorded by the call ("recorded").
+COUNTERS = {"device": 0, "host": 0, "downloaded": 0, "indexed": 0, "recorded": 0}
+
+ST_INDEX = 32                   # SSDHIP_JPEG_ST_INDEX (csrc/ssdhip_jpeg_entropy.h)
+ENTRY_WORDS = 8                 # struct ssdhip_jpeg_entry: image, byte, bit, first_mcu, n_mcus, pred0, pred1, pred2
 
 CHUNK = 256                     # files per call when a whole dataset is decoded (DataGenerator(load_images_into_memory=True))
 _MAX_BYTES = 1 << 30            # compressed bytes / blocks per call: offsets are 32-bit ints on the device
@@ -251,14 +262,24 @@ def _align(v, a=16):
     return -(-v // a) * a
 
 
-def pack_plans(plans, datas, align=256):
+RECORD = "record"                # pack_plans(index_rows=[...]): decode this image sequentially and record its entries
+
+
+def pack_plans(plans, datas, align=256, index_rows=None):
     """The descriptor buffer of a batch (plans[i] of datas[i]) as the device reads it: (host uint8 array, dict of the launch's
-    arguments, [(out_offset, shape)] per image).  Parts are 16-byte aligned; the status words are the zeros at its end."""
+    arguments, [(out_offset, shape)] per image).  Parts are 16-byte aligned; the status words are the zeros at its end.
+
+    `index_rows` (ssdhip_jpeg_decode_batch_indexed; None: the buffer and the arguments are exactly those without it): per image None
+    (the per-segment path), RECORD, or the image's int32 (rows, 8) entries as a `JpegIndex` keeps them (`byte` counted from the start
+    of the scan's bytes).  Behind the status words the buffer then holds one mode word per image and the entry table (struct
+    ssdhip_jpeg_entry, `image` and `byte` set for this batch), and the arguments gain off_modes, off_entries, n_entries, ckpt_entries,
+    record_segments and ckpt_base (per image: its first row in the checkpoint buffer, or None)."""
     n = len(plans)
     images = np.zeros((n, 24), dtype=np.int32)
     qt_index, qt_list, huff_index, huff_list = {}, [], {}, []
     segments, chunks, outs = [], [], []
     data_pos = block_pos = out_pos = 0
+    modes, entries, ckpt_base, ckpt_pos, n_seg = np.zeros(n, dtype=np.int32), [], [None] * n, 0, 0
 
     def huff_id(t):
         i = huff_index.get(t)
@@ -280,6 +301,18 @@ def pack_plans(plans, datas, align=256):
         row[17], row[20] = block_pos, p.nblocks
         images[i:i + 1].view(np.int64)[0, 9] = out_pos
         seg = p._segments
+        if index_rows is not None and index_rows[i] is not None:
+            if isinstance(index_rows[i], str):
+                modes[i] = (ckpt_pos << 2) | 2
+                ckpt_base[i] = ckpt_pos
+                ckpt_pos += p.mcuy
+            else:
+                rows = np.array(index_rows[i], dtype=np.int64).reshape(-1, ENTRY_WORDS)
+                rows[:, 0] = i
+                rows[:, 1] += data_pos
+                entries.append(np.clip(rows, -2 ** 31, 2 ** 31 - 1))
+                modes[i] = (n_seg << 2) | 1
+        n_seg += len(seg)
         first, last = int(seg[0, 0]), int(seg[-1, 1])
         rows = np.empty((len(seg), 4), dtype=np.int64)
         rows[:, 0], rows[:, 1:3], rows[:, 3] = i, seg + (data_pos - first), np.arange(len(seg)) * p.interval
@@ -298,7 +331,13 @@ def pack_plans(plans, datas, align=256):
     off_huff = off_qt + _align(qt.nbytes)
     off_data = off_huff + _align(huff.nbytes)
     off_status = off_data + _align(data_pos)
-    host = np.zeros(off_status + _align(4 * n), dtype=np.uint8)
+    size = off_status + _align(4 * n)
+    if index_rows is not None:
+        entries = np.concatenate(entries).astype(np.int32) if entries else np.zeros((0, ENTRY_WORDS), dtype=np.int32)
+        off_modes = size
+        off_entries = off_modes + _align(4 * n)
+        size = off_entries + _align(entries.nbytes)
+    host = np.zeros(size, dtype=np.uint8)
     host[off_images:off_images + images.nbytes] = images.view(np.uint8).ravel()
     host[off_segments:off_segments + segments.nbytes] = segments.view(np.uint8).ravel()
     host[off_qt:off_qt + qt.nbytes] = qt.view(np.uint8).ravel()
@@ -308,6 +347,12 @@ def pack_plans(plans, datas, align=256):
                 off_segments=off_segments, off_qt=off_qt, off_huff=off_huff, off_data=off_data, data_bytes=data_pos, off_status=off_status,
                 max_blocks=max(p.nblocks for p in plans), max_pixels=max(p.height * p.width for p in plans), total_blocks=block_pos,
                 out_bytes=max(out_pos, 1))
+    if index_rows is not None:
+        host[off_modes:off_modes + 4 * n] = modes.view(np.uint8)
+        host[off_entries:off_entries + entries.nbytes] = entries.view(np.uint8).ravel()
+        indexed = (modes & 3) == 1
+        args.update(off_modes=off_modes, off_entries=off_entries, n_entries=len(entries), ckpt_entries=ckpt_pos, ckpt_base=ckpt_base,
+                    record_segments=int(sum(len(p._segments) for p, m in zip(plans, indexed) if not m)))
     return host, args, outs
 
 
@@ -325,6 +370,10 @@ def _check_layout():
         from ._image_ops import RAGGED_ALIGN
         if list(words) != [24, 4, 912, RAGGED_ALIGN]:
             raise nat.SsdHipError("libssdhip.so's JPEG descriptors are not this module's: rebuild it")
+        words = (ctypes.c_int * 2)()
+        nat.check(nat.load().ssdhip_jpeg_entry_layout(words), "ssdhip_jpeg_entry_layout")
+        if list(words) != [ENTRY_WORDS, ST_INDEX]:
+            raise nat.SsdHipError("libssdhip.so's JPEG index entries are not this module's: rebuild it")
         _layout_checked = True
 
 
@@ -344,59 +393,200 @@ def _read(source):
         return f.read()
 
 
-def decode_planned(plans, datas, device=None, stages=7, events=None):
+def decode_planned(plans, datas, device=None, stages=7, events=None, index_rows=None):
     """The device part of `decode_jpeg_batch` for files that all have a plan: -> (list of CUDA uint8 views into one output buffer,
     status (n,) int32 NumPy array).  `stages`: ssdhip_jpeg_decode_batch's bit mask; `events`: a callable that is called between the
-    upload and each stage's launch (tools/time_jpeg_decode.py records device events there)."""
+    upload and each stage's launch (tools/time_jpeg_decode.py records device events there).  With `index_rows` (`pack_plans`) the
+    call is ssdhip_jpeg_decode_batch_indexed and returns a third value: per image None, or for a RECORD image whose status is 0 its
+    recorded int32 (rows, 8) entries in `JpegIndex` form."""
     import torch
     _check_layout()
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
     from ._image_ops import RAGGED_ALIGN
-    host, a, outs = pack_plans(plans, datas, RAGGED_ALIGN)
+    host, a, outs = pack_plans(plans, datas, RAGGED_ALIGN, index_rows=index_rows)
     desc = torch.from_numpy(host).to(device)
     out = torch.empty((a["out_bytes"],), dtype=torch.uint8, device=device)
     coef = nat.workspaces.get(device, "jpeg_coef", a["total_blocks"] * 128)
     planes = nat.workspaces.get(device, "jpeg_planes", a["total_blocks"] * 64)
+    ckpt = None
+    if index_rows is not None and a["ckpt_entries"]:
+        ckpt = torch.empty((a["ckpt_entries"], ENTRY_WORDS), dtype=torch.int32, device=device)
     for stage in (1, 2, 4):
         if events is not None:
             events()
-        if stages & stage:
+        if not stages & stage:
+            continue
+        if index_rows is None:
             nat.launch("ssdhip_jpeg_decode_batch", device, nat._ptr(desc), desc.numel(), a["n_images"], a["n_segments"], a["n_qt"],
                        a["n_huff"], a["off_images"], a["off_segments"], a["off_qt"], a["off_huff"], a["off_data"], a["data_bytes"],
                        a["off_status"], a["max_blocks"], a["max_pixels"], a["total_blocks"], lanes_per_wave(a["n_segments"]), stage,
                        nat._ptr(coef), nat._ptr(planes), nat._ptr(out), a["out_bytes"])
+        else:
+            nat.launch("ssdhip_jpeg_decode_batch_indexed", device, nat._ptr(desc), desc.numel(), a["n_images"], a["n_segments"], a["n_qt"],
+                       a["n_huff"], a["off_images"], a["off_segments"], a["off_qt"], a["off_huff"], a["off_data"], a["data_bytes"],
+                       a["off_status"], a["off_entries"], a["n_entries"], a["off_modes"], nat._ptr(ckpt), a["ckpt_entries"],
+                       a["record_segments"], a["max_blocks"], a["max_pixels"], a["total_blocks"], lanes_per_wave(a["n_entries"]),
+                       lanes_per_wave(a["record_segments"]), stage, nat._ptr(coef), nat._ptr(planes), nat._ptr(out), a["out_bytes"])
     if events is not None:
         events()
     status = desc[a["off_status"]:a["off_status"] + 4 * a["n_images"]].cpu().numpy().view(np.int32)
     views = []
     for o, shape in outs:
         views.append(out[o:o + int(np.prod(shape))].view(*shape))
-    return views, status
+    if index_rows is None:
+        return views, status
+    recorded = [None] * len(plans)
+    if ckpt is not None and stages & 1:
+        rows = ckpt.cpu().numpy()
+        seg_begin = np.frombuffer(host, dtype=np.int32, count=4 * a["n_segments"], offset=a["off_segments"]).reshape(-1, 4)
+        begin_of = {int(r[0]): int(r[1]) for r in seg_begin[::-1]}           # image -> begin of its first segment
+        for i, (p, base) in enumerate(zip(plans, a["ckpt_base"])):
+            if base is not None and status[i] == 0:
+                mine = rows[base:base + p.mcuy].copy()
+                mine[:, 1] -= begin_of[i]
+                mine[:, 0] = 0
+                recorded[i] = mine
+    return views, status, recorded
 
 
-def decode_jpeg_batch(sources, device=None):
+class JpegIndex:
+    """Entry points of files without restart markers: key -> int32 (MCU rows, 8) array of struct ssdhip_jpeg_entry rows (`image` 0,
+    `byte` counted from the first byte of the scan's entropy-coded data).  The key of a file NAME is the name plus the file's length,
+    the key of bytes their digest (`key`).  An entry is only ever a hint: the device verifies it while it decodes (module
+    docstring), so a file that changed under its name, or an index loaded from elsewhere, costs one recording decode and nothing
+    else.  At most `max_files` entries are kept (the oldest go first); about 32 bytes per 8 or 16 image rows each."""
+
+    def __init__(self, max_files=1 << 20):
+        self.max_files = int(max_files)
+        self._rows = {}
+
+    @staticmethod
+    def key(source, data):
+        """The key of `source` (a file name, or bytes) whose content is `data`.  The digest of bytes covers their length, their
+        first 4 KiB (the headers and the start of the scan) and their last 4 KiB: enough to tell files apart at a fixed cost, and
+        an entry that is not the file's is rejected on the device anyway."""
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            h = hashlib.blake2b(len(data).to_bytes(8, "little"), digest_size=16)
+            h.update(data[:4096])
+            h.update(data[-4096:])
+            return "d:" + h.hexdigest()
+        return "f:%d:%s" % (len(data), source)
+
+    def __len__(self):
+        return len(self._rows)
+
+    def __contains__(self, key):
+        return key in self._rows
+
+    def __getitem__(self, key):
+        return self._rows[key]
+
+    def get(self, key):
+        return self._rows.get(key)
+
+    def __setitem__(self, key, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, ENTRY_WORDS)
+        self._rows.pop(key, None)
+        self._rows[key] = rows
+        while len(self._rows) > max(self.max_files, 0):
+            del self._rows[next(iter(self._rows))]
+
+    def pop(self, key, default=None):
+        return self._rows.pop(key, default)
+
+    def keys(self):
+        return list(self._rows)
+
+    def clear(self):
+        self._rows.clear()
+
+    def save(self, path):
+        """One .npz of plain arrays: the keys, the row count of each, all rows."""
+        keys = list(self._rows)
+        counts = np.array([len(self._rows[k]) for k in keys], dtype=np.int64)
+        rows = np.concatenate([self._rows[k] for k in keys]) if keys else np.zeros((0, ENTRY_WORDS), dtype=np.int32)
+        with open(path, "wb") as f:
+            np.savez(f, keys=np.array(keys, dtype=np.str_), counts=counts, rows=rows.astype(np.int32))
+
+    @classmethod
+    def load(cls, path, max_files=1 << 20):
+        self = cls(max_files)
+        with np.load(path, allow_pickle=False) as z:
+            keys, counts, rows = [str(k) for k in z["keys"]], z["counts"].astype(np.int64), z["rows"].astype(np.int32)
+        if rows.ndim != 2 or rows.shape[1] != ENTRY_WORDS or len(keys) != len(counts) or (counts < 0).any() or counts.sum() != len(rows):
+            raise ValueError("%s is no JpegIndex file" % path)
+        ends = np.cumsum(counts)
+        for k, n, e in zip(keys, counts, ends):
+            self[k] = rows[e - n:e].copy()
+        return self
+
+
+def _uses_index(plan):
+    """The index is for planned files without a restart interval and with at least two MCU rows (a lane per row is the gain); a
+    file that ends inside its scan is PIL's whatever the device makes of it."""
+    return plan.restart_interval == 0 and plan.mcuy >= 2 and plan.has_eoi
+
+
+def decode_jpeg_batch(sources, device=None, index=None):
     """File names or bytes -> one entry per source, in order: a CUDA uint8 tensor (H, W) / (H, W, 3) for every file the device
     decoded -- views into ONE output buffer, each on a RAGGED_ALIGN boundary, so `_image_ops.pack_ragged` copies them into place on
     the device --, and for a file without a plan, or one whose device status is non-zero, the NumPy array `_load_image` returns.  An
     exception `_load_image` raises is raised unchanged.  The batch's descriptors go up as ONE host buffer in one copy; the status
     words come back in one.  (A batch of more than 1 GiB of compressed bytes or 2^22 blocks is decoded as two; each half then has
-    its own output buffer.)"""
+    its own output buffer.)
+
+    `index`: a `JpegIndex`, used and filled in place (None: no file is indexed and the call is ssdhip_jpeg_decode_batch).  A file
+    without restart markers that has an entry is decoded through it; one that has none is decoded sequentially and its entry
+    recorded.  A file whose indexed decode reports any status loses its entry and is decoded again by the recording route -- all such
+    files of the call in ONE second launch, whose views lie in a second output buffer -- and goes to PIL only if that fails too."""
     sources = list(sources)
     datas = [_read(s) for s in sources]
     plans = [plan_jpeg(d) for d in datas]
     idx = [i for i, p in enumerate(plans) if p is not None]
     if len(idx) > 1 and (sum(len(datas[i]) for i in idx) > _MAX_BYTES or sum(plans[i].nblocks for i in idx) > _MAX_BLOCKS):
         half = len(sources) // 2
-        return decode_jpeg_batch(sources[:half], device) + decode_jpeg_batch(sources[half:], device)
+        return decode_jpeg_batch(sources[:half], device, index) + decode_jpeg_batch(sources[half:], device, index)
     results = [None] * len(sources)
-    if idx:
+    if idx and index is None:
         views, status = decode_planned([plans[i] for i in idx], [datas[i] for i in idx], device)
         for i, v, st in zip(idx, views, status):
             if st == 0 and plans[i].has_eoi:
                 results[i] = v
                 COUNTERS["device"] += 1
+    elif idx:
+        keys = {i: JpegIndex.key(sources[i], datas[i]) for i in idx if _uses_index(plans[i])}
+        rows = []
+        for i in idx:
+            known = index.get(keys[i]) if i in keys else None
+            if known is not None and len(known) != plans[i].mcuy:        # not this file's: no need to ask the device
+                index.pop(keys[i])
+                known = None
+            rows.append(None if i not in keys else (RECORD if known is None else known))
+        views, status, recorded = decode_planned([plans[i] for i in idx], [datas[i] for i in idx], device, index_rows=rows)
+        again = []
+        for i, v, st, r, rec in zip(idx, views, status, rows, recorded):
+            if st == 0 and plans[i].has_eoi:
+                results[i] = v
+                COUNTERS["device"] += 1
+                if rec is not None:
+                    index[keys[i]] = rec
+                    COUNTERS["recorded"] += 1
+                elif r is not None:
+                    COUNTERS["indexed"] += 1
+            elif r is not None and not isinstance(r, str):               # the index was rejected (or the file is damaged)
+                index.pop(keys[i])
+                again.append(i)
+        if again:
+            views, status, recorded = decode_planned([plans[i] for i in again], [datas[i] for i in again], device,
+                                                     index_rows=[RECORD] * len(again))
+            for i, v, st, rec in zip(again, views, status, recorded):
+                if st == 0:
+                    results[i] = v
+                    index[keys[i]] = rec
+                    COUNTERS["device"] += 1
+                    COUNTERS["recorded"] += 1
     for i, s in enumerate(sources):
         if results[i] is None:
             results[i] = _load_image(s)

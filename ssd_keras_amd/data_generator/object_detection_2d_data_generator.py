@@ -34,7 +34,10 @@ ragged chain paths (`[SSDDataAugmentation]`, `[DataAugmentationVariableInputSize
 every image must have three channels); in every other case (the 'constant' and 'program' paths, the per-image loop, no
 transformations, a batch with a host-decoded member, grayscale images in front of a chain) they are downloaded and everything goes
 on as with `decode='host'`.  'original_images' are NumPy arrays either way, and `load_images_into_memory=True` decodes the file list
-on the device in chunks of `jpeg_decode.CHUNK` (256) files and keeps the same list of NumPy arrays.  HDF5 datasets are not supported (h5py is not a dependency of this package); their parameter and methods raise
+on the device in chunks of `jpeg_decode.CHUNK` (256) files and keeps the same list of NumPy arrays.  A generator that decodes on the
+device keeps `jpeg_index`, the entry points of its files without restart markers: the first decode of such a file records them, every
+later one uses them (one lane per MCU row instead of one per file; same pixels), and `build_jpeg_index()` records them for the whole
+dataset ahead of training.  HDF5 datasets are not supported (h5py is not a dependency of this package); their parameter and methods raise
 `DatasetError`.  The parsers' XML reader is `xml.etree.ElementTree` (the reference uses BeautifulSoup) with the same results."""
 from __future__ import annotations
 
@@ -153,6 +156,34 @@ class DataGenerator:
             raise ValueError("`decode` can be either 'host' (PIL, as in the reference) or 'device' (baseline JPEGs on the GPU).")
         self._decode = value
 
+    _jpeg_index = None
+
+    @property
+    def jpeg_index(self):
+        '''The `jpeg_decode.JpegIndex` of this generator's files (decode = 'device'): entry points of the JPEGs without restart
+        markers, recorded the first time a file is decoded and used from then on (`generate()`, `load_images_into_memory`,
+        `build_jpeg_index`).  Assign a loaded one (`JpegIndex.load(path)`) to start warm; the device verifies every entry it
+        uses, so a stale one costs time only.  Not in the reference.'''
+        if self._jpeg_index is None:
+            from . import jpeg_decode
+            self._jpeg_index = jpeg_decode.JpegIndex()
+        return self._jpeg_index
+
+    @jpeg_index.setter
+    def jpeg_index(self, value):
+        self._jpeg_index = value
+
+    def build_jpeg_index(self, verbose=True):
+        '''Decode every file of the dataset once on the device, `jpeg_decode.CHUNK` files per call, so that `jpeg_index` holds
+        their entry points before training starts; the images themselves are dropped.  Returns the index.  Not in the reference.'''
+        from . import jpeg_decode
+        if self.filenames is None:
+            raise DatasetError("`build_jpeg_index()` needs the dataset's file names.")
+        index = self.jpeg_index
+        for start in _progress(range(0, len(self.filenames), jpeg_decode.CHUNK), 'Indexing JPEG files', verbose):
+            jpeg_decode.decode_jpeg_batch(self.filenames[start:start + jpeg_decode.CHUNK], index=index)
+        return index
+
     @classmethod
     def with_decode(cls, decode, *args, **kwargs):
         '''`DataGenerator(*args, **kwargs)` with `decode` set BEFORE the constructor runs, so that `load_images_into_memory=True`
@@ -187,7 +218,8 @@ class DataGenerator:
         from . import jpeg_decode
         images = []
         for start in _progress(range(0, len(self.filenames), jpeg_decode.CHUNK), 'Loading images into memory', verbose):
-            images += jpeg_decode.to_host(jpeg_decode.decode_jpeg_batch(self.filenames[start:start + jpeg_decode.CHUNK]))
+            images += jpeg_decode.to_host(jpeg_decode.decode_jpeg_batch(self.filenames[start:start + jpeg_decode.CHUNK],
+                                                                        index=self.jpeg_index))
         return images
 
     def load_hdf5_dataset(self, verbose=True):
@@ -612,7 +644,7 @@ class DataGenerator:
                 batch_filenames = self.filenames[current:current + batch_size]
                 if self.decode == 'device':
                     from . import jpeg_decode
-                    batch_X = jpeg_decode.decode_jpeg_batch(batch_filenames)
+                    batch_X = jpeg_decode.decode_jpeg_batch(batch_filenames, index=self.jpeg_index)
                     if not self._stays_on_device(transformations, batch_X, self.labels is not None):
                         batch_X = jpeg_decode.to_host(batch_X)
                 else:
