@@ -793,6 +793,22 @@ int ssdhip_image_resize_gather_cv_u8(const void* x, void* y, int B, int H, int W
  * Identity tables with pre / post set are an exact integer translation. */
 int ssdhip_image_warp_affine_u8(const void* x, void* y, int B, int H, int W, int Ho, int Wo, int C, const int* geo_dev, const int* xtab_dev,
                                 const int* ytab_dev, const void* background_dev, void* stream);
+/* ssdhip_image_warp_affine_u8's arithmetic for a RAGGED batch (below), one launch, every image its own sizes and tables; the geometry
+ * recorded in front of the warp is read through index maps.  x (x_bytes long), src_table: the ragged batch, C in {1, 3, 4}, read as the
+ * ragged gather reads it (C = 1 replicated, C = 4 alpha dropped).  y (y_bytes long, 4-byte aligned), dst_table [B][4] int64 = byte
+ * offset, Ho, Wo, 3: the ragged batch of 3-channel results; every byte of every image is written; rows with Wo % 4 == 0 at an offset
+ * that is a multiple of 4 are written as dwords.  tabs: one int32 buffer of n_tabs entries; meta [B][8] int32 = the offsets into it of
+ *   xtab (Wo x 2) and ytab (Ho x 2), as above,
+ *   xs (wa) and ys (ha): the warp reads a virtual ha x wa image whose position (q, p) shows source pixel (ys[q], xs[p]) of image b,
+ *     the padding colour where either entry is -1, black where either is -2,
+ * then wa, ha, the warp's border colour and the padding colour (R | G << 8 | B << 16).  A neighbour outside ha x wa reads the border
+ * colour, and so does whatever would address memory outside image b (a map entry below -2 or not below H / W, a src_table row that
+ * does not lie inside x): nothing is clamped.  An image whose dst_table row does not lie inside y, or whose meta row does not lie
+ * inside tabs, is left unwritten; callers check both on the host (the package's launcher does).  max_work = the largest
+ * ceil(Wo / 4) Ho of the batch.  SSDHIP_E_BADARG: a null pointer, B outside 1 .. 65535, y not 4-byte aligned, an empty buffer. */
+int ssdhip_image_warp_affine_ragged_u8(const void* x, long long x_bytes, const long long* src_table_dev, void* y, long long y_bytes,
+                                       const long long* dst_table_dev, int B, long long max_work, const int* tabs_dev, long long n_tabs,
+                                       const int* meta_dev, void* stream);
 /* Ragged batches: B uint8 images of different sizes concatenated in one device buffer; table [B][4] int64 = byte offset (a multiple of
  * 4; the package aligns to 256), H, W, C with C in {1, 3, 4}.
  * ssdhip_image_resize_gather_ragged_u8: ssdhip_image_resize_gather_cv_u8 with image b read through its table entry and ConvertTo3Channels

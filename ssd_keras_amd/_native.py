@@ -194,6 +194,7 @@ SIGNATURES = {
     "ssdhip_image_resize_cv_u8": (_I, [_P, _P] + [_I] * 8 + [_P, _P, _I, _P, _P, _I, _P]),
     "ssdhip_image_resize_gather_cv_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 3 + [_I, _P, _P, _I, _P, _P]),
     "ssdhip_image_warp_affine_u8": (_I, [_P, _P] + [_I] * 6 + [_P] * 5),
+    "ssdhip_image_warp_affine_ragged_u8": (_I, [_P, _LL, _P, _P, _LL, _P, _I, _LL, _P, _LL, _P, _P]),
     "ssdhip_image_resize_gather_ragged_u8": (_I, [_P, _P, _P] + [_I] * 3 + [_P] * 3 + [_I, _P, _P, _I, _P, _P]),
     "ssdhip_image_program_ragged_u8": (_I, [_P, _P, _P, _I, _LL] + [_P] * 3),
     "ssdhip_image_hist_u8": (_I, [_P, _LL, _I, _I, _P, _P]),
@@ -2587,6 +2588,45 @@ def image_warp_affine_u8(images, out_h, out_w, geo, xtab, ytab, background):
     launch("ssdhip_image_warp_affine_u8", dev, _ptr(images), _ptr(out), b, h, w, int(out_h), int(out_w), c, _ptr(geo), _ptr(xtab),
            _ptr(ytab), _ptr(bg))
     return out
+
+
+def image_warp_affine_ragged_u8(data, table, shapes, out_table, out_bytes, tabs, meta):
+    """ssdhip_image_warp_affine_ragged_u8 (csrc/ssdhip_warp.hip; the contract is in include/ssdhip.h): cv2.warpAffine for a ragged batch
+    (data, table as image_resize_gather_ragged_u8's; `shapes` its (H, W, C) on the host) in ONE launch.  out_table (B, 4) int64 = byte
+    offset, Ho, Wo, 3 of every result in a fresh buffer of out_bytes; tabs: one int32 array with every image's xtab (Wo x 2), ytab
+    (Ho x 2) and the index maps xs (wa), ys (ha) of the geometry in front of the warp; meta (B, 8) int32 = their four offsets, wa, ha,
+    the border and the padding colour (R | G << 8 | B << 16).  Everything the kernel will address is checked HERE, on the host, before
+    anything is uploaded or launched: ValueError for a map entry that is not a row / column of its image (or -1 / -2), for a table or
+    an output that does not lie inside its buffer, for a channel count other than 1 / 3 / 4.  Returns (the buffer, out_table on the
+    device): with the output shapes, a ragged batch."""
+    out_table = np.ascontiguousarray(out_table, dtype=np.int64)
+    tabs, meta = np.ascontiguousarray(tabs, dtype=np.int32), np.ascontiguousarray(meta, dtype=np.int32)
+    b, n, out_bytes = len(shapes), int(tabs.size), int(out_bytes)
+    if b < 1 or b > 65535 or tuple(out_table.shape) != (b, 4) or tuple(meta.shape) != (b, 8) or tabs.ndim != 1 or n < 1 or out_bytes < 1:
+        raise SsdHipError("out_table must be (B, 4), meta (B, 8), tabs one int32 array, for 1 .. 65535 images")
+    bad = ValueError("the recorded geometry is not of these images")
+    max_work = 0
+    for (h, w, c), (off, ho, wo, c3), m in zip(shapes, out_table.tolist(), meta.tolist()):
+        o_xt, o_yt, o_xs, o_ys, wa, ha = m[:6]
+        if c not in (1, 3, 4) or c3 != 3 or ho < 1 or wo < 1 or off < 0 or off + ho * wo * 3 > out_bytes:
+            raise bad
+        if min(o_xt, o_yt, o_xs, o_ys, wa, ha) < 0 or max(o_xt + 2 * wo, o_yt + 2 * ho, o_xs + wa, o_ys + ha) > n:
+            raise bad
+        for entries, limit in ((tabs[o_xs:o_xs + wa], w), (tabs[o_ys:o_ys + ha], h)):
+            if entries.size and (int(entries.min()) < -2 or int(entries.max()) >= limit):
+                raise bad
+        max_work = max(max_work, -(-wo // 4) * ho)
+    torch = _torch()
+    require_cuda(data, "data")
+    require_cuda(table, "table")
+    if data.dtype != torch.uint8 or data.dim() != 1 or table.dtype != torch.int64 or tuple(table.shape) != (b, 4):
+        raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
+    dev = data.device
+    out_table, tabs, meta = to_device(out_table, device=dev), to_device(tabs, device=dev), to_device(meta, device=dev)
+    out = torch.empty((out_bytes,), dtype=torch.uint8, device=dev)
+    launch("ssdhip_image_warp_affine_ragged_u8", dev, _ptr(data), int(data.numel()), _ptr(table.contiguous()), _ptr(out), out_bytes,
+           _ptr(out_table), b, max_work, _ptr(tabs), n, _ptr(meta))
+    return out, out_table
 
 
 def image_hist_u8(image, channel):

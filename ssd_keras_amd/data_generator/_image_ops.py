@@ -307,11 +307,127 @@ def run_ragged(packed, programs):
     return packed.like(out)
 
 
+# ---- lazy geometry with ONE resampling stage: Translate / Scale in a composed list ----------------------------------------------------
+class StagedGeoImage:
+    """A `GeoImage` that can also hold ONE cv2.warpAffine in front of the final resize: index maps `a` over the original image, the
+    `stage` (M float64 (2, 3), (out_h, out_w), border colour) over a's virtual image, and index maps `b` over the stage's output (with
+    the final resize).  The 8-bit rounding of the warp is part of the result, so the stage is a pixel pass of its own
+    (`warp_stage_ragged`: ssdhip_image_warp_affine_ragged_u8 into a ragged intermediate that the gather then reads through `b`).
+    Without a stage it is `a` and behaves as a GeoImage does.  What `warp` records:
+      * a translation by whole pixels that keeps the size (Translate; Scale(1)): under warpAffine's arithmetic an exact copy with the
+        border colour where the canvas is uncovered = `window(-dy, -dx, h, w, border)` on the current maps;
+      * Rotate's three matrices for the current size, border 0: `turn`, as GeoImage.warp;
+      * the first other matrix: the stage, unless a quarter turn sits in front of it (the kernel's maps are not transposed);
+      * a second one: NotImplementedError, like everything else the maps cannot hold (the generator then runs the per-image loop)."""
+
+    ndim = 3
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, a, stage=None, b=None):
+        self.a, self.stage, self.b = a, stage, b
+
+    @classmethod
+    def of(cls, height, width):
+        return cls(GeoImage.of(height, width))
+
+    @property
+    def top(self):
+        """The maps the next op applies to."""
+        return self.a if self.stage is None else self.b
+
+    def _on_top(self, maps):
+        return StagedGeoImage(maps, None, None) if self.stage is None else StagedGeoImage(self.a, self.stage, maps)
+
+    @property
+    def shape(self):
+        return self.top.shape
+
+    @property
+    def resized(self):
+        return self.top.resized
+
+    def __getitem__(self, key):
+        return self._on_top(self.top[key])
+
+    def window(self, top, left, height, width, background):
+        return self._on_top(self.top.window(top, left, height, width, background))
+
+    def turn(self, angle):
+        return self._on_top(self.top.turn(angle))
+
+    def resize(self, out_h, out_w, interp):
+        return self._on_top(self.top.resize(out_h, out_w, interp))
+
+    def warp(self, M, dsize, background):
+        top = self.top
+        if top.resized is not None:
+            raise TypeError("a resized lazy image is final")
+        h, w = len(top.ys), len(top.xs)
+        out_w, out_h = int(dsize[0]), int(dsize[1])
+        border = tuple(int(v) for v in border_value(background, 3))
+        m = np.asarray(M, dtype=np.float64)
+        if m.shape != (2, 3):
+            raise ValueError("a warp matrix is (2, 3)")
+        shift = _integer_shift(m)
+        if shift is not None and (out_h, out_w) == (h, w):
+            return self.window(-shift[1], -shift[0], h, w, border)
+        if border == (0, 0, 0):
+            for angle in (90, 180, 270):
+                ref, size = quarter_turn_matrix(h, w, angle)
+                if np.array_equal(m, ref) and (out_w, out_h) == size:
+                    return self.turn(angle)
+        if self.stage is not None:
+            raise NotImplementedError("two non-integer warps cannot be composed lazily")
+        if self.a.turned:
+            raise NotImplementedError("a warp after a rotation cannot be composed lazily")
+        if out_h < 1 or out_w < 1:
+            raise ValueError("a warp's output has at least one pixel")
+        return StagedGeoImage(self.a, (m.copy(), (out_h, out_w), border), GeoImage.of(out_h, out_w))
+
+
+def _rgb_word(colour):
+    r, g, b = (int(v) for v in colour)
+    return r | (g << 8) | (b << 16)
+
+
+def warp_stage_ragged(packed, geos):
+    """The stages of a batch of final StagedGeoImages over a ragged batch: ONE ssdhip_image_warp_affine_ragged_u8 launch into a fresh
+    ragged buffer of 3-channel images -> (that RaggedBatch, the GeoImages over ITS images for `gather_batch_ragged`).  An image without
+    a stage goes through the launch with identity tables and identity maps -- fx = fy = 0 gives the weight 32768, an exact copy, made
+    3-channel as the gather would read it -- and keeps its maps (they may hold a quarter turn, which the warp's maps cannot; the gather
+    executes it as ever).  The tables of the batch go up as one array."""
+    if len(geos) != len(packed):
+        raise ValueError("one lazy image per image of the batch")
+    parts, meta, out_table, out_shapes, after, pos, out_pos = [], [], [], [], [], 0, 0
+    for g, (h, w, _) in zip(geos, packed.shapes):
+        if g.stage is None:
+            xs, ys, M, (out_h, out_w), border, padding = np.arange(w), np.arange(h), _IDENTITY, (h, w), (0, 0, 0), (0, 0, 0)
+            after.append(g.a)
+        else:
+            M, (out_h, out_w), border = g.stage
+            xs, ys, padding = g.a.xs, g.a.ys, (g.a.background if g.a.background is not None else (0, 0, 0))
+            after.append(g.b)
+        xtab, ytab = warp_tables(M, out_h, out_w)
+        row = []
+        for part in (xtab, ytab, xs, ys):
+            part = np.asarray(part, dtype=np.int32).reshape(-1)
+            row.append(pos)
+            parts.append(part)
+            pos += part.size
+        meta.append(row + [len(xs), len(ys), _rgb_word(border), _rgb_word(padding)])
+        out_table.append((out_pos, out_h, out_w, 3))
+        out_shapes.append((out_h, out_w, 3))
+        out_pos += -(-out_h * out_w * 3 // RAGGED_ALIGN) * RAGGED_ALIGN
+    data, table = nat.image_warp_affine_ragged_u8(packed.data, packed.table, packed.shapes, np.array(out_table, dtype=np.int64), out_pos,
+                                                  np.concatenate(parts), np.array(meta, dtype=np.int32))
+    return RaggedBatch(data, table, out_shapes), after
+
+
 # ---- lazy photometry: the photometric ops of a composed list recorded around the recorded geometry ------------------------------------
 class ProgramImage:
     """An image that exists only as WHAT A TRANSFORMATION LIST DID TO IT: the photometric steps in front of the geometry (`pre`), the
-    geometry (a `GeoImage`), and the photometric steps behind it (`post`) -- executed for a whole batch by `run_program_batch`.  Steps are
-    the (name, argument) pairs of `encode` plus two that need a table: ("gamma", table) = cv2.LUT with a 256-entry uint8 table on all
+    geometry (a `GeoImage`; a `StagedGeoImage` when made with `warps=True`), and the photometric steps behind it (`post`) -- executed
+    for a whole batch by `run_program_batch`.  Steps are the (name, argument) pairs of `encode` plus two that need a table: ("gamma", table) = cv2.LUT with a 256-entry uint8 table on all
     three channels, ("equalize", channel) = cv2.equalizeHist on one channel.  Quacks like the array the ops expect: `shape`, `ndim` and
     row / column slicing are the GeoImage's, `dtype` is what the recorded steps leave (`end_dtype`), `image[:, :, order]` is ChannelSwap.
     What a NumPy image of that dtype would refuse is refused when it is recorded, with the same exception; what cannot be composed --
@@ -324,8 +440,9 @@ class ProgramImage:
         self.geo, self.pre, self.post, self.moved = geo, list(pre), list(post), bool(moved)
 
     @classmethod
-    def of(cls, height, width):
-        return cls(GeoImage.of(height, width))
+    def of(cls, height, width, warps=False):
+        """`warps`: the geometry is a `StagedGeoImage`, which also records Translate / Scale (below, behind cv2.warpAffine's tables)."""
+        return cls(StagedGeoImage.of(height, width) if warps else GeoImage.of(height, width))
 
     @property
     def shape(self):
@@ -446,7 +563,9 @@ def run_program_batch(images, lazies):
     """Execute a batch of ProgramImages over the uint8 host images they were recorded for -> the CUDA batch (B, H, W, 3), uint8, float32 or
     float64 as the programs end.  First segments on the ragged batch (nothing is launched when all are empty; 1- and 4-channel images are
     made 3-channel on the host when one is not), then the ragged gather (a copy-kind plan for a list without a resize: every image must
-    end in one size), then the second segments on the gather's output.  NotImplementedError for sizes or dtypes that differ."""
+    end in one size), then the second segments on the gather's output.  NotImplementedError for sizes or dtypes that differ.  When an image
+    of the batch carries a warp stage (`StagedGeoImage`), ONE warp launch for the whole batch sits between the first segments and the
+    gather (`warp_stage_ragged`); a batch without a stage takes exactly the launches above."""
     import torch
     if len(images) != len(lazies) or not lazies:
         raise ValueError("one lazy image per image of the batch")
@@ -475,6 +594,10 @@ def run_program_batch(images, lazies):
             lambda ops, args, luts: nat.image_program_ragged_u8(packed.data, packed.table, packed.max_pixels, ops, args, luts),
             lambda ops, args, luts, stop, channel, hist: nat.image_program_hist_u8(packed.data, packed.table, packed.max_pixels, ops, args,
                                                                                  luts, stop, channel, hist)))
+    if any(isinstance(g, StagedGeoImage) and g.stage is not None for g in geos):
+        packed, geos = warp_stage_ragged(packed, [g if isinstance(g, StagedGeoImage) else StagedGeoImage(g) for g in geos])
+    else:                                                                     # no stage in the batch: the launches of a list without warps
+        geos = [g.a if isinstance(g, StagedGeoImage) else g for g in geos]
     out = gather_batch_ragged(packed, geos)
     if any(posts):
         out_dtype = _torch_dtype(tags.pop())
@@ -667,7 +790,7 @@ def resize_plan(src_h, src_w, dst_h, dst_w, interp):
 
 def resize(image, out_h, out_w, interp):
     """cv2.resize(image, dsize=(out_w, out_h), interpolation=interp) for uint8 images: NumPy (H, W[, C]) or CUDA (B, H, W, C)."""
-    if isinstance(image, (GeoImage, ProgramImage)):
+    if isinstance(image, (GeoImage, StagedGeoImage, ProgramImage)):
         return image.resize(out_h, out_w, interp)
     if isinstance(image, np.ndarray):
         if image.dtype != np.uint8:
@@ -878,7 +1001,7 @@ def warp_batch(images, lazies):
 def warp_affine(image, M, dsize, background=0):
     """cv2.warpAffine(image, M, dsize=(width, height), borderMode=BORDER_CONSTANT, borderValue=background) for uint8 images: a NumPy
     (H, W[, C]) image (one upload, one launch, one download) or a `WarpImage` (recorded)."""
-    if isinstance(image, (WarpImage, GeoImage, ProgramImage)):
+    if isinstance(image, (WarpImage, GeoImage, StagedGeoImage, ProgramImage)):
         return image.warp(M, dsize, background)
     if not isinstance(image, np.ndarray):
         raise TypeError("warp_affine takes a NumPy image or a lazy WarpImage / GeoImage")

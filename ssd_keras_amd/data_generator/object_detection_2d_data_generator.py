@@ -22,6 +22,13 @@ chains read too).
     segment on the ragged batch -- Gamma and HistogramEqualization as look-up-table steps of the per-image programs, the equalisation
     tables built on the device --, the ragged gather, the second segment on its output (which may end in float32 or float64).  A batch
     the lazy images cannot compose (NotImplementedError) goes through the per-image loop from the same random state;
+  * with the generator's `compose_warps` attribute set (not in the reference; False by default, `generator.compose_warps = True`
+    switches it on): such a list may also hold `Translate` / `RandomTranslate` / `Scale` / `RandomScale` among its geometric ops,
+    e.g. `[ConvertTo3Channels, RandomTranslate, RandomScale, RandomFlip, Resize]` on images of mixed sizes.  The lazy images then
+    carry an `_image_ops.StagedGeoImage`: a translation by whole pixels is a window of the index maps, the first zoom one
+    cv2.warpAffine stage that the whole batch executes in ONE launch (`ssdhip_image_warp_affine_ragged_u8`) between the first
+    segment and the gather.  A second zoom, or one behind a quarter turn, is the loop's, like every other NotImplementedError.
+    Without the switch these lists take the per-image loop, as before;
   * anything else: the reference's per-image loop over the package's transforms.
 Every path gives the per-image loop's pixels, labels, inverters and final `np.random` state.
 
@@ -111,6 +118,7 @@ class DataGenerator:
         self.dataset_size = 0
         self.load_images_into_memory = load_images_into_memory
         self.images = None
+        self.compose_warps = False                      # not in the reference: lists with Translate / Scale as a device batch (module docstring)
 
         if filenames is not None:
             if isinstance(filenames, (list, tuple)):
@@ -427,9 +435,7 @@ class DataGenerator:
         from .object_detection_2d_patch_sampling_ops import RandomPadFixedAR
         from .object_detection_2d_photometric_ops import ConvertTo3Channels
         kinds = [type(t) for t in transformations]
-        if not images or any(not DataGenerator._is_uint8_image(im) for im in images):
-            return None
-        if any(im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] not in (1, 3, 4)) for im in images):
+        if not DataGenerator._batchable(images):
             return None
         if kinds in ([ConvertTo3Channels, Resize], [ConvertTo3Channels, RandomPadFixedAR, Resize]):
             return 'gather'
@@ -444,6 +450,22 @@ class DataGenerator:
             if kinds == [DataAugmentationSatellite]:
                 return 'satellite'
         return 'program' if DataGenerator._composable(transformations, images) else None
+
+    @staticmethod
+    def _batchable(images):
+        """What every batch path needs of a batch: uint8 images, (H, W) or (H, W, C) with C in 1 / 3 / 4."""
+        if not images or any(not DataGenerator._is_uint8_image(im) for im in images):
+            return False
+        return not any(im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] not in (1, 3, 4)) for im in images)
+
+    def _batch_path_of(self, transformations, images, have_labels):
+        """(`_batch_path`'s answer, whether the lazy images record warps): with `compose_warps` set, a list the paths above leave to the
+        loop takes the 'program' path when it is composable with Translate / Scale among the geometric ops."""
+        path = self._batch_path(transformations, images, have_labels)
+        if (path is None and self.compose_warps and self._batchable(images) and all(isinstance(im, np.ndarray) for im in images)
+                and self._composable(transformations, images, warps=True)):
+            return 'program', True
+        return path, False
 
     @staticmethod
     def _is_uint8_image(im):
@@ -465,9 +487,10 @@ class DataGenerator:
         return path in ('ssd', 'variable', 'satellite') and all(im.ndim == 3 and im.shape[2] == 3 for im in images)
 
     @staticmethod
-    def _composable(transformations, images):
+    def _composable(transformations, images, warps=False):
         """Whether a list is built from the package's own photometric, index-geometry and patch ops in an order the lazy images can
-        record (the 'program' path of the module docstring): decided from the elements' types and the images alone, before any draw."""
+        record (the 'program' path of the module docstring): decided from the elements' types and the images alone, before any draw.
+        `warps`: `Translate` / `RandomTranslate` / `Scale` / `RandomScale` count as geometric ops too (`compose_warps`)."""
         from . import object_detection_2d_geometric_ops as geo
         from . import object_detection_2d_patch_sampling_ops as patch
         from . import object_detection_2d_photometric_ops as photo
@@ -478,7 +501,9 @@ class DataGenerator:
         resizes = (geo.Resize, geo.ResizeRandomInterp)
         geometric = resizes + (geo.Flip, geo.RandomFlip, geo.Rotate, geo.RandomRotate, patch.CropPad, patch.Crop, patch.Pad,
                                patch.RandomPatch, patch.RandomPatchInf, patch.RandomMaxCropFixedAR, patch.RandomPadFixedAR)
-        kinds = [type(t) for t in transformations]
+        if warps:
+            geometric += (geo.Translate, geo.RandomTranslate, geo.Scale, geo.RandomScale)
+        kinds =[type(t) for t in transformations]
         if any(k not in photometric and k not in geometric and k is not photo.ConvertTo3Channels for k in kinds):
             return False
         if kinds[0] is not photo.ConvertTo3Channels and any(im.ndim != 3 or im.shape[2] != 3 for im in images):
@@ -526,10 +551,11 @@ class DataGenerator:
                 raise NotImplementedError("a transform that drops the image is the per-image loop's to handle")
         return img, lab, inv[::-1]
 
-    def _transform_batch(self, path, transformations, images, labels, want_inverters):
+    def _transform_batch(self, path, transformations, images, labels, want_inverters, warps=False):
         """The batch paths: images (uint8 NumPy; CUDA uint8 tensors for 'gather' and the ragged chains) and labels (arrays, or None) of the items that are transformed -> (CUDA (n, H, W, 3)
         batch -- uint8, or what a 'program' list ends in --, labels or None, inverters per item).  'program' raises NotImplementedError,
-        with both random generators where they were, for a batch its lazy images cannot compose."""
+        with both random generators where they were, for a batch its lazy images cannot compose; `warps`: its lazy images record
+        Translate / Scale too (`ProgramImage.of(..., warps=True)`)."""
         import torch
         from . import _image_ops as iop
         if path in ('ssd', 'variable', 'satellite'):
@@ -549,7 +575,7 @@ class DataGenerator:
             try:
                 lazies, out_labels, inverters = [], [], []
                 for k, im in enumerate(images):
-                    img, lab, inv = self._walk(transformations, iop.ProgramImage.of(int(im.shape[0]), int(im.shape[1])),
+                    img, lab, inv = self._walk(transformations, iop.ProgramImage.of(int(im.shape[0]), int(im.shape[1]), warps=warps),
                                                None if labels is None else labels[k], want_inverters)
                     lazies.append(img)
                     out_labels.append(lab)
@@ -667,7 +693,7 @@ class DataGenerator:
             batch_items_to_remove = []
             batch_inverse_transforms = []
             want_inverters = 'inverse_transform' in returns
-            path = self._batch_path(transformations, batch_X, self.labels is not None) if transformations else None
+            path, warps = self._batch_path_of(transformations, batch_X, self.labels is not None) if transformations else (None, False)
             processed = None                                   # the batch paths' CUDA batch of the transformed items
             if path is not None:
                 todo = []
@@ -682,7 +708,7 @@ class DataGenerator:
                     try:
                         processed, out_labels, inverters = self._transform_batch(
                             path, transformations, [batch_X[i] for i in todo], None if self.labels is None else [batch_y[i] for i in todo],
-                            want_inverters)
+                            want_inverters, warps)
                     except NotImplementedError:
                         if path != 'program':
                             raise
