@@ -2485,6 +2485,37 @@ def image_resize_cv_u8(images, out_h, out_w, kind, area, ix, wx, iy, wy):
     return out
 
 
+def _ragged_table(table, message, B=None, ok=True):
+    """The one check of a ragged batch's table -- a contiguous (B, 4) int64 CUDA tensor (byte offset, H, W, C; _image_ops.pack_ragged) --
+    raising the caller's `message`; `ok`: what the caller asks of the buffer beside it.  Returns B."""
+    require_cuda(table, "table")
+    if not ok or table.dtype != _torch().int64 or table.dim() != 2 or table.shape[1] != 4 or (B is not None and table.shape[0] != B):
+        raise SsdHipError(message)
+    return int(table.shape[0])
+
+
+def _gather_tables(dev, b, c, out_h, out_w, plans, ix, wx, iy, wy, background, message, transposed=None):
+    """What the three gathers share: plans, tap tables, background (and `transposed`) as contiguous tensors on `dev`, tables of one tap
+    widened to two (the entry points want room for the linear kernel's two taps), and the shape check, raising the caller's `message`."""
+    torch = _torch()
+    plans = to_device(plans, device=dev, dtype=torch.int32).contiguous()
+    ix = to_device(ix, device=dev, dtype=torch.int32).contiguous()
+    wx = to_device(wx, device=dev, dtype=torch.float64).contiguous()
+    iy = to_device(iy, device=dev, dtype=torch.int32).contiguous()
+    wy = to_device(wy, device=dev, dtype=torch.float64).contiguous()
+    bg = to_device(background, device=dev, dtype=torch.uint8).contiguous()
+    tr = None if transposed is None else to_device(transposed, device=dev, dtype=torch.int32).contiguous()
+    pad = lambda t: torch.cat([t, torch.zeros_like(t)], dim=2)
+    if ix.shape[2] < 2:
+        ix, wx = pad(ix), pad(wx)
+    if iy.shape[2] < 2:
+        iy, wy = pad(iy), pad(wy)
+    if (ix.shape != wx.shape or iy.shape != wy.shape or tuple(ix.shape[:2]) != (b, out_w) or tuple(iy.shape[:2]) != (b, out_h)
+            or tuple(bg.shape) != (b, c) or tuple(plans.shape) != (b, 4) or (tr is not None and tuple(tr.shape) != (b,))):
+        raise SsdHipError(message)
+    return plans, ix, wx, iy, wy, bg, tr
+
+
 def image_resize_gather_cv_u8(images, out_h, out_w, plans, ix, wx, iy, wy, background):
     """ssdhip_image_resize_gather_cv_u8: images (B, H, W, C) CUDA uint8; plans (B, 4) int32 [kind, area, taps per column, taps per row];
     per-image tables ix / wx (B, out_w, nx), iy / wy (B, out_h, ny) (index -1 = background), background (B, C) uint8."""
@@ -2494,21 +2525,8 @@ def image_resize_gather_cv_u8(images, out_h, out_w, plans, ix, wx, iy, wy, backg
         raise SsdHipError("images must be a contiguous (B, H, W, C) uint8 tensor")
     b, h, w, c = images.shape
     dev = images.device
-    plans = to_device(plans, device=dev, dtype=torch.int32).contiguous()
-    ix = to_device(ix, device=dev, dtype=torch.int32).contiguous()
-    wx = to_device(wx, device=dev, dtype=torch.float64).contiguous()
-    iy = to_device(iy, device=dev, dtype=torch.int32).contiguous()
-    wy = to_device(wy, device=dev, dtype=torch.float64).contiguous()
-    bg = to_device(background, device=dev, dtype=torch.uint8).contiguous()
-    if ix.shape[2] < 2:                                        # (the entry point wants room for the linear kernel's two taps)
-        pad = lambda t: torch.cat([t, torch.zeros_like(t)], dim=2)
-        ix, wx = pad(ix), pad(wx)
-    if iy.shape[2] < 2:
-        pad = lambda t: torch.cat([t, torch.zeros_like(t)], dim=2)
-        iy, wy = pad(iy), pad(wy)
-    if (ix.shape != wx.shape or iy.shape != wy.shape or tuple(ix.shape[:2]) != (b, out_w) or tuple(iy.shape[:2]) != (b, out_h)
-            or tuple(bg.shape) != (b, c) or tuple(plans.shape) != (b, 4)):
-        raise SsdHipError("plans must be (B, 4), tap tables (B, out_w, nx) / (B, out_h, ny), background (B, C)")
+    plans, ix, wx, iy, wy, bg, _ = _gather_tables(dev, b, c, out_h, out_w, plans, ix, wx, iy, wy, background,
+                                                  "plans must be (B, 4), tap tables (B, out_w, nx) / (B, out_h, ny), background (B, C)")
     out = torch.empty((b, out_h, out_w, c), dtype=torch.uint8, device=dev)
     launch("ssdhip_image_resize_gather_cv_u8", dev, _ptr(images), _ptr(out), b, h, w, out_h, out_w, c, _ptr(plans), _ptr(ix), _ptr(wx),
            int(ix.shape[2]), _ptr(iy), _ptr(wy), int(iy.shape[2]), _ptr(bg))
@@ -2521,24 +2539,10 @@ def image_resize_gather_ragged_u8(data, table, out_h, out_w, plans, ix, wx, iy, 
     (B, out_w, nx), iy / wy (B, out_h, ny) (index -1 = background), background (B, 3) uint8, as image_resize_gather_cv_u8's."""
     torch = _torch()
     require_cuda(data, "data")
-    require_cuda(table, "table")
-    if data.dtype != torch.uint8 or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4:
-        raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
-    b, dev = int(table.shape[0]), data.device
-    plans = to_device(plans, device=dev, dtype=torch.int32).contiguous()
-    ix = to_device(ix, device=dev, dtype=torch.int32).contiguous()
-    wx = to_device(wx, device=dev, dtype=torch.float64).contiguous()
-    iy = to_device(iy, device=dev, dtype=torch.int32).contiguous()
-    wy = to_device(wy, device=dev, dtype=torch.float64).contiguous()
-    bg = to_device(background, device=dev, dtype=torch.uint8).contiguous()
-    pad = lambda t: torch.cat([t, torch.zeros_like(t)], dim=2)
-    if ix.shape[2] < 2:
-        ix, wx = pad(ix), pad(wx)
-    if iy.shape[2] < 2:
-        iy, wy = pad(iy), pad(wy)
-    if (ix.shape != wx.shape or iy.shape != wy.shape or tuple(ix.shape[:2]) != (b, out_w) or tuple(iy.shape[:2]) != (b, out_h)
-            or tuple(bg.shape) != (b, 3) or tuple(plans.shape) != (b, 4)):
-        raise SsdHipError("plans must be (B, 4), tap tables (B, out_w, nx) / (B, out_h, ny), background (B, 3)")
+    b = _ragged_table(table, "a ragged batch is a uint8 buffer and a (B, 4) int64 table", ok=data.dtype == torch.uint8)
+    dev = data.device
+    plans, ix, wx, iy, wy, bg, _ = _gather_tables(dev, b, 3, out_h, out_w, plans, ix, wx, iy, wy, background,
+                                                  "plans must be (B, 4), tap tables (B, out_w, nx) / (B, out_h, ny), background (B, 3)")
     out = torch.empty((b, out_h, out_w, 3), dtype=torch.uint8, device=dev)
     launch("ssdhip_image_resize_gather_ragged_u8", dev, _ptr(data), _ptr(table), _ptr(out), b, int(out_h), int(out_w), _ptr(plans), _ptr(ix),
            _ptr(wx), int(ix.shape[2]), _ptr(iy), _ptr(wy), int(iy.shape[2]), _ptr(bg))
@@ -2551,10 +2555,8 @@ def image_program_ragged_u8(data, table, max_pixels, ops, args, luts=None):
     uint8 CUDA tensor): the tables of the programs' `lut` steps (ssdhip_image_program_ragged_lut_u8)."""
     torch = _torch()
     require_cuda(data, "data")
-    require_cuda(table, "table")
-    if data.dtype != torch.uint8 or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4:
-        raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
-    b, dev = int(table.shape[0]), data.device
+    b = _ragged_table(table, "a ragged batch is a uint8 buffer and a (B, 4) int64 table", ok=data.dtype == torch.uint8)
+    dev = data.device
     ops, args = _programs_to_device(ops, args, dev, IMG_U8, luts is not None)
     if tuple(ops.shape) != (b, IMG_PROG) or tuple(args.shape) != (b, IMG_PROG):
         raise SsdHipError("ops / args must be (%d, %d)" % (b, IMG_PROG))
@@ -2618,9 +2620,7 @@ def image_warp_affine_ragged_u8(data, table, shapes, out_table, out_bytes, tabs,
         max_work = max(max_work, -(-wo // 4) * ho)
     torch = _torch()
     require_cuda(data, "data")
-    require_cuda(table, "table")
-    if data.dtype != torch.uint8 or data.dim() != 1 or table.dtype != torch.int64 or tuple(table.shape) != (b, 4):
-        raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
+    _ragged_table(table, "a ragged batch is a uint8 buffer and a (B, 4) int64 table", b, ok=data.dtype == torch.uint8 and data.dim() == 1)
     dev = data.device
     out_table, tabs, meta = to_device(out_table, device=dev), to_device(tabs, device=dev), to_device(meta, device=dev)
     out = torch.empty((out_bytes,), dtype=torch.uint8, device=dev)
@@ -2655,47 +2655,104 @@ def image_lut_u8(image, table, channel_mask):
     return out
 
 
-# ---- the decisions of the original-SSD augmentation chain for a whole batch (csrc/ssdhip_augment.hip) ---------------------------------
+# ---- the decisions of the augmentation chains for a whole batch (csrc/ssdhip_augment.hip) ---------------------------------------------
 AUG_MAX_BOXES = 64
+CONST_AUG_GEO = 8                                     # geometry row: sequence, translated?, dx, dy, scaled?, factor, flipped?, zoom first?
+CONST_AUG_MAX_TRIALS = 64                             # the largest max(1, n_trials_max) the decision kernel takes
+VAR_AUG_CRITERION = {"center_point": 0, "iou": 1, "area": 2}      # SSDHIP_VAR_AUG_*
+
+
+def _fill_struct(q, params, inner=None):
+    """dict -> ctypes struct: a list or tuple goes element by element into the array field of its name.  `inner`: the name of a nested
+    struct that takes every field `q` does not have itself (ssdhip_sat_augment_params keeps the variable chain's in `.var`)."""
+    for k, v in params.items():
+        target = q if inner is None or hasattr(type(q), k) else getattr(q, inner)
+        if isinstance(v, (list, tuple)):
+            arr = getattr(target, k)
+            for i, e in enumerate(v):
+                arr[i] = e
+        else:
+            setattr(target, k, v)
+    return q
+
+
+def _decide(name, lead, mt_states, labels, n_labels, device, geo_dtype, geo_cols, message, mt_dims=(1, 2), programs=True,
+            turns=None):
+    """Every decision export behind one pack / upload / launch / download.  name: the export; lead: its arguments in front of the data
+    pointers (the structs by reference, B, n_boxes_max, the ragged table); mt_states (B, 625) (seeded) or (625,) (one stream) uint32
+    -- `mt_dims`: which of the two the export takes --, labels (B, 64, 5) float64, n_labels (B,) int32, turns (B,) int32 | None: NumPy
+    arrays, ONE upload; `message`: what any other shape raises.  The export's pointers are [turns,] mt, labels, n, [ops, args,] geometry, labels_out, n_out, mt_out, every section
+    aligned to its element: upload [labels f64 | mt u32, padded to 8 bytes | n i32 | turns i32], download [labels_out f64 | args f64 |
+    geometry (geo_dtype, geo_cols per image) | mt_out u32, padded | ops i32 | n_out i32].  Returns (ops (B, 16) int32, args (B, 16)
+    float64 -- the programs of image_program, None without `programs` --, geometry: device views of the download buffer, fetch)."""
+    torch = _torch()
+    B = int(labels.shape[0])
+    if (mt_states.ndim not in mt_dims or mt_states.shape != ((625,), (B, 625))[mt_states.ndim - 1] or labels.shape != (B, AUG_MAX_BOXES, 5)
+            or n_labels.shape != (B,)):
+        raise SsdHipError(message)
+    pad8 = lambda n: (n + 7) // 8 * 8
+    n_mt = mt_states.size * 4
+    nl, nm = B * AUG_MAX_BOXES * 5 * 8, pad8(n_mt)
+    i_mt, i_n, i_turns = nl, nl + nm, nl + nm + B * 4
+    host = np.zeros((i_turns + (0 if turns is None else B * 4),), dtype=np.uint8)
+    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
+    host[i_mt:i_mt + n_mt] = np.ascontiguousarray(mt_states, dtype=np.uint32).view(np.uint8).ravel()
+    host[i_n:i_turns] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
+    if turns is not None:
+        host[i_turns:] = np.ascontiguousarray(turns, dtype=np.int32).view(np.uint8).ravel()
+    dev_in = torch.from_numpy(host).to(device)
+    np_geo = np.dtype(geo_dtype)
+    na, no = (B * IMG_PROG * 8, B * IMG_PROG * 4) if programs else (0, 0)
+    ng = B * geo_cols * np_geo.itemsize
+    o_args = nl
+    o_geo = pad8(o_args + na)
+    o_mt = pad8(o_geo + ng)
+    o_ops = o_mt + nm
+    o_n = o_ops + no
+    dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
+    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
+    vp = ctypes.c_void_p
+    ptrs = ([vp(base_in + i_turns)] if turns is not None else []) + [vp(base_in + i_mt), vp(base_in), vp(base_in + i_n)]
+    if programs:
+        ptrs += [vp(base_out + o_ops), vp(base_out + o_args)]
+    ptrs += [vp(base_out + o_geo), vp(base_out), vp(base_out + o_n), vp(base_out + o_mt)]
+    launch(name, device, *lead, *ptrs)
+    geo_dev = dev_out[o_geo:o_geo + ng].view(getattr(torch, np_geo.name)).view(B, geo_cols)   # stays on the device for the plan builders
+    ops_dev = dev_out[o_ops:o_ops + no].view(torch.int32).view(B, IMG_PROG) if programs else None
+    args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG) if programs else None
+
+    def fetch():
+        """(geometry, labels_out, n_out, mt_states_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
+        out = dev_out.cpu().numpy()
+        return (out[o_geo:o_geo + ng].view(np_geo).reshape(B, geo_cols), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
+                out[o_n:].view(np.int32), out[o_mt:o_mt + n_mt].view(np.uint32).reshape(mt_states.shape).copy())
+    return ops_dev, args_dev, geo_dev, fetch
+
+
+def _decide_patch_chain(who, q, turns, mt_states, labels, n_labels, device, table):
+    """var_augment_decide and sat_augment_decide: one export family each (`ssdhip_<who>_decide[_stream[_ragged]]`), chosen by mt_states'
+    shape and `table`; the most boxes of any image rides in front of the table."""
+    B = int(labels.shape[0])
+    if table is not None:
+        _ragged_table(table, "%s_decide: table (B, 4) int64" % who, B)
+    lead = [ctypes.byref(q), B, int(n_labels.max()) if n_labels.size else 0]
+    if mt_states.ndim != 1:
+        name, lead = "ssdhip_%s_decide" % who, lead + [_ptr(table)]
+    elif table is None:
+        name = "ssdhip_%s_decide_stream" % who
+    else:
+        name, lead = "ssdhip_%s_decide_stream_ragged" % who, lead + [_ptr(table)]
+    return _decide(name, lead, mt_states, labels, n_labels, device, np.int32, 12,
+                   "%s_decide: mt_states (B, 625) or (625,), labels (B, 64, 5), n_labels (B,)" % who, turns=turns)
 
 
 def ssd_augment_decide(params, mt_states, labels, n_labels, device):
     """`ssdhip_ssd_augment_decide`: params a dict of the fields of ssdhip_augment_params; mt_states (B, 625) uint32, labels (B, 64, 5)
     float64, n_labels (B,) int32 NumPy arrays (ONE upload) -> (geometry (B, 12) int32 CUDA tensor, fetch) where fetch() downloads
     (geometry (B, 12) int32, labels_out (B, 64, 5) float64, n_out (B,) int32, mt_states_out (B, 625) uint32) as NumPy arrays."""
-    torch = _torch()
-    q = _AugParams()
-    for k, v in params.items():
-        if isinstance(v, (list, tuple)):
-            arr = getattr(q, k)
-            for i, e in enumerate(v):
-                arr[i] = e
-        else:
-            setattr(q, k, v)
-    B = int(mt_states.shape[0])
-    if mt_states.shape != (B, 625) or labels.shape != (B, AUG_MAX_BOXES, 5) or n_labels.shape != (B,):
-        raise SsdHipError("ssd_augment_decide: mt_states (B, 625), labels (B, 64, 5), n_labels (B,)")
-    # one packed upload: [labels f64 | mt u32 | n i32], one packed download: [labels_out f64 | mt_out u32 | geometry i32 | n_out i32]
-    nl, nm = B * AUG_MAX_BOXES * 5 * 8, B * 625 * 4
-    host = np.empty((nl + nm + B * 4,), dtype=np.uint8)
-    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
-    host[nl:nl + nm] = np.ascontiguousarray(mt_states, dtype=np.uint32).view(np.uint8).ravel()
-    host[nl + nm:] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
-    dev_in = torch.from_numpy(host).to(device)
-    no = nl + nm + B * 12 * 4 + B * 4
-    dev_out = torch.empty((no,), dtype=torch.uint8, device=device)
-    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
-    vp = ctypes.c_void_p
-    launch("ssdhip_ssd_augment_decide", device, ctypes.byref(q), B, vp(base_in + nl), vp(base_in), vp(base_in + nl + nm),
-           vp(base_out + nl + nm), vp(base_out), vp(base_out + nl + nm + B * 48), vp(base_out + nl))
-    geo_dev = dev_out[nl + nm:nl + nm + B * 48].view(torch.int32).view(B, 12)      # stays on the device for augment_plans
-
-    def fetch():
-        """(geometry, labels_out, n_out, mt_states_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
-        out = dev_out.cpu().numpy()
-        return (out[nl + nm:nl + nm + B * 48].view(np.int32).reshape(B, 12), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
-                out[nl + nm + B * 48:].view(np.int32), out[nl:nl + nm].view(np.uint32).reshape(B, 625))
-    return geo_dev, fetch
+    lead = [ctypes.byref(_fill_struct(_AugParams(), params)), int(labels.shape[0])]
+    return _decide("ssdhip_ssd_augment_decide", lead, mt_states, labels, n_labels, device, np.int32, 12,
+                   "ssd_augment_decide: mt_states (B, 625), labels (B, 64, 5), n_labels (B,)", mt_dims=(2,), programs=False)[2:]
 
 
 def ssd_augment_decide_stream(params, photo, mt_state, labels, n_labels, device):
@@ -2706,9 +2763,7 @@ def ssd_augment_decide_stream(params, photo, mt_state, labels, n_labels, device)
 def ssd_augment_decide_stream_ragged(params, photo, mt_state, labels, n_labels, table):
     """`ssdhip_ssd_augment_decide_stream_ragged`: as ssd_augment_decide_stream, image b's (H, W) from `table` (B, 4) int64 CUDA tensor
     (pack_ragged's: byte offset, H, W, C); params' img_height / img_width are the batch's largest."""
-    if tuple(table.shape) != (int(labels.shape[0]), 4) or table.dtype != _torch().int64:
-        raise SsdHipError("ssd_augment_decide_stream_ragged: table (B, 4) int64")
-    require_cuda(table, "table")
+    _ragged_table(table, "ssd_augment_decide_stream_ragged: table (B, 4) int64", int(labels.shape[0]))
     return _decide_stream(params, photo, mt_state, labels, n_labels, table.device, table)
 
 
@@ -2718,88 +2773,12 @@ def _decide_stream(params, photo, mt_state, labels, n_labels, device, table):
     mt_state (625,) uint32 (np.random.get_state(): the 624 key words + the position), labels (B, 64, 5) float64, n_labels (B,) int32.
     Returns (ops (B, 16) int32 and args (B, 16) float64 CUDA tensors = the programs of image_program, geometry (B, 12) int32 CUDA tensor,
     fetch) where fetch() downloads (geometry, labels_out, n_out, mt_state_out (625,)) as NumPy arrays."""
-    torch = _torch()
-    q = _AugParams()
-    for k, v in params.items():
-        if isinstance(v, (list, tuple)):
-            arr = getattr(q, k)
-            for i, e in enumerate(v):
-                arr[i] = e
-        else:
-            setattr(q, k, v)
-    ph = _AugPhoto()
-    for i in range(4):
-        ph.prob[i], ph.lower[i], ph.upper[i] = float(photo["prob"][i]), float(photo["lower"][i]), float(photo["upper"][i])
-    ph.swap_prob = float(photo["swap_prob"])
-    B = int(labels.shape[0])
-    if mt_state.shape != (625,) or labels.shape != (B, AUG_MAX_BOXES, 5) or n_labels.shape != (B,):
-        raise SsdHipError("ssd_augment_decide_stream: mt_state (625,), labels (B, 64, 5), n_labels (B,)")
-    # one packed upload: [labels f64 | mt u32 (625, padded to 632) | n i32];
-    # one packed download: [labels_out f64 | args f64 | mt_out u32 (632) | geometry i32 | ops i32 | n_out i32]
-    nl, nm = B * AUG_MAX_BOXES * 5 * 8, 632 * 4
-    host = np.zeros((nl + nm + B * 4,), dtype=np.uint8)
-    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
-    host[nl:nl + 625 * 4] = np.ascontiguousarray(mt_state, dtype=np.uint32).view(np.uint8).ravel()
-    host[nl + nm:] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
-    dev_in = torch.from_numpy(host).to(device)
-    na = B * IMG_PROG * 8
-    o_args, o_mt, o_geo, o_ops, o_n = nl, nl + na, nl + na + nm, nl + na + nm + B * 48, nl + na + nm + B * 48 + B * IMG_PROG * 4
-    dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
-    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
-    vp = ctypes.c_void_p
-    outs = (vp(base_in + nl), vp(base_in), vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args), vp(base_out + o_geo),
-            vp(base_out), vp(base_out + o_n), vp(base_out + o_mt))
-    if table is None:
-        launch("ssdhip_ssd_augment_decide_stream", device, ctypes.byref(q), ctypes.byref(ph), B, *outs)
-    else:
-        launch("ssdhip_ssd_augment_decide_stream_ragged", device, ctypes.byref(q), ctypes.byref(ph), B, _ptr(table), *outs)
-    geo_dev = dev_out[o_geo:o_geo + B * 48].view(torch.int32).view(B, 12)
-    ops_dev = dev_out[o_ops:o_ops + B * IMG_PROG * 4].view(torch.int32).view(B, IMG_PROG)
-    args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG)
-
-    def fetch():
-        """(geometry, labels_out, n_out, mt_state_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
-        out = dev_out.cpu().numpy()
-        return (out[o_geo:o_geo + B * 48].view(np.int32).reshape(B, 12), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
-                out[o_n:].view(np.int32), out[o_mt:o_mt + 625 * 4].view(np.uint32).copy())
-    return ops_dev, args_dev, geo_dev, fetch
-
-
-def augment_plans(geo_dev, H, W, out_h, out_w, n_taps):
-    """`ssdhip_augment_plans`: the gather launch's per-image plans (plans (B, 4) int32, ix, wx, iy, wy: CUDA tensors
-    (B, out_w | out_h, n_taps)) with cv2.resize's own arithmetic, built on the device from the geometry the decision kernels left there."""
-    torch = _torch()
-    B, dev = int(geo_dev.shape[0]), geo_dev.device
-    plans = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    ix = torch.empty((B, out_w, n_taps), dtype=torch.int32, device=dev)
-    wx = torch.empty((B, out_w, n_taps), dtype=torch.float64, device=dev)
-    iy = torch.empty((B, out_h, n_taps), dtype=torch.int32, device=dev)
-    wy = torch.empty((B, out_h, n_taps), dtype=torch.float64, device=dev)
-    launch("ssdhip_augment_plans", dev, _ptr(geo_dev), B, int(H), int(W), int(out_h), int(out_w), int(n_taps), _ptr(plans), _ptr(ix),
-           _ptr(wx), _ptr(iy), _ptr(wy))
-    return plans, ix, wx, iy, wy
-
-
-def augment_plans_ragged(geo_dev, table, out_h, out_w, n_taps):
-    """`ssdhip_augment_plans_ragged`: augment_plans for a ragged batch, image b's size from `table` (B, 4) int64 CUDA tensor."""
-    torch = _torch()
-    B, dev = int(geo_dev.shape[0]), geo_dev.device
-    require_cuda(table, "table")
-    if tuple(table.shape) != (B, 4) or table.dtype != torch.int64:
-        raise SsdHipError("augment_plans_ragged: table (B, 4) int64")
-    plans = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    ix = torch.empty((B, out_w, n_taps), dtype=torch.int32, device=dev)
-    wx = torch.empty((B, out_w, n_taps), dtype=torch.float64, device=dev)
-    iy = torch.empty((B, out_h, n_taps), dtype=torch.int32, device=dev)
-    wy = torch.empty((B, out_h, n_taps), dtype=torch.float64, device=dev)
-    launch("ssdhip_augment_plans_ragged", dev, _ptr(geo_dev), _ptr(table), B, int(out_h), int(out_w), int(n_taps), _ptr(plans), _ptr(ix),
-           _ptr(wx), _ptr(iy), _ptr(wy))
-    return plans, ix, wx, iy, wy
-
-
-# ---- the decisions of the constant-input-size chain for a whole batch (csrc/ssdhip_augment.hip) --------------------------------------
-CONST_AUG_GEO = 8                                     # geometry row: sequence, translated?, dx, dy, scaled?, factor, flipped?, zoom first?
-CONST_AUG_MAX_TRIALS = 64                             # the largest max(1, n_trials_max) the decision kernel takes
+    lead = [ctypes.byref(_fill_struct(_AugParams(), params)), ctypes.byref(_fill_struct(_AugPhoto(), photo)), int(labels.shape[0])]
+    name = "ssdhip_ssd_augment_decide_stream"
+    if table is not None:
+        name, lead = name + "_ragged", lead + [_ptr(table)]
+    return _decide(name, lead, mt_state, labels, n_labels, device, np.int32, 12,
+                   "ssd_augment_decide_stream: mt_state (625,), labels (B, 64, 5), n_labels (B,)", mt_dims=(1,))
 
 
 def const_augment_decide(params, mt_states, labels, n_labels, device):
@@ -2808,48 +2787,62 @@ def const_augment_decide(params, mt_states, labels, n_labels, device):
     (B, 64, 5) float64, n_labels (B,) int32 NumPy arrays (ONE upload).  Returns (ops (B, 16) int32 and args (B, 16) float64 CUDA tensors
     = the programs of image_program, geometry (B, 8) float64 CUDA tensor for const_augment_plans, fetch) where fetch() downloads
     (geometry (B, 8), labels_out (B, 64, 5), n_out (B,), mt_states_out (B, 625) | (625,)) as NumPy arrays."""
-    torch = _torch()
-    q = _ConstAugParams()
-    for k, v in params.items():
-        if isinstance(v, (list, tuple)):
-            arr = getattr(q, k)
-            for i, e in enumerate(v):
-                arr[i] = e
-        else:
-            setattr(q, k, v)
-    B = int(labels.shape[0])
-    stream_mode = mt_states.ndim == 1
-    if mt_states.shape != ((625,) if stream_mode else (B, 625)) or labels.shape != (B, AUG_MAX_BOXES, 5) or n_labels.shape != (B,):
-        raise SsdHipError("const_augment_decide: mt_states (B, 625) or (625,), labels (B, 64, 5), n_labels (B,)")
-    # one packed upload: [labels f64 | mt u32 (padded to 8 bytes) | n i32];
-    # one packed download: [labels_out f64 | args f64 | geometry f64 | mt_out u32 (padded) | ops i32 | n_out i32]
-    n_mt = mt_states.size * 4
-    nl, nm = B * AUG_MAX_BOXES * 5 * 8, (n_mt + 7) // 8 * 8
-    host = np.zeros((nl + nm + B * 4,), dtype=np.uint8)
-    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
-    host[nl:nl + n_mt] = np.ascontiguousarray(mt_states, dtype=np.uint32).view(np.uint8).ravel()
-    host[nl + nm:] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
-    dev_in = torch.from_numpy(host).to(device)
-    na, ng = B * IMG_PROG * 8, B * CONST_AUG_GEO * 8
-    o_args, o_geo, o_mt = nl, nl + na, nl + na + ng
-    o_ops = o_mt + nm
-    o_n = o_ops + B * IMG_PROG * 4
-    dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
-    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
-    vp = ctypes.c_void_p
-    launch("ssdhip_const_augment_decide_stream" if stream_mode else "ssdhip_const_augment_decide", device, ctypes.byref(q), B,
-           vp(base_in + nl), vp(base_in), vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args), vp(base_out + o_geo),
-           vp(base_out), vp(base_out + o_n), vp(base_out + o_mt))
-    ops_dev = dev_out[o_ops:o_ops + B * IMG_PROG * 4].view(torch.int32).view(B, IMG_PROG)
-    args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG)
-    geo_dev = dev_out[o_geo:o_geo + ng].view(torch.float64).view(B, CONST_AUG_GEO)
+    lead = [ctypes.byref(_fill_struct(_ConstAugParams(), params)), int(labels.shape[0])]
+    return _decide("ssdhip_const_augment_decide_stream" if mt_states.ndim == 1 else "ssdhip_const_augment_decide", lead, mt_states, labels,
+                   n_labels, device, np.float64, CONST_AUG_GEO,
+                   "const_augment_decide: mt_states (B, 625) or (625,), labels (B, 64, 5), n_labels (B,)")
 
-    def fetch():
-        """(geometry, labels_out, n_out, mt_states_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
-        out = dev_out.cpu().numpy()
-        return (out[o_geo:o_geo + ng].view(np.float64).reshape(B, CONST_AUG_GEO), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
-                out[o_n:].view(np.int32), out[o_mt:o_mt + n_mt].view(np.uint32).reshape(mt_states.shape).copy())
-    return ops_dev, args_dev, geo_dev, fetch
+
+def var_augment_decide(params, mt_states, labels, n_labels, device, table=None):
+    """`ssdhip_var_augment_decide` (mt_states (B, 625): image b on its own MT19937 state; `table` optional) or
+    `ssdhip_var_augment_decide_stream` / `ssdhip_var_augment_decide_stream_ragged` (mt_states (625,): the batch in order on one state;
+    without / with `table`).  params: a dict of the fields of ssdhip_var_augment_params (img_height / img_width only without a table);
+    table: the ragged batch's (B, 4) int64 CUDA tensor (pack_ragged's: byte offset, H, W, C); labels (B, 64, 5) float64, n_labels (B,)
+    int32 NumPy arrays (ONE upload).  Returns (ops (B, 16) int32 and args (B, 16) float64 CUDA tensors = the programs of image_program,
+    geometry (B, 12) int32 CUDA tensor for augment_plans[_ragged], fetch) where fetch() downloads (geometry (B, 12), labels_out
+    (B, 64, 5), n_out (B,), mt_states_out (B, 625) | (625,)) as NumPy arrays."""
+    return _decide_patch_chain("var_augment", _fill_struct(_VarAugParams(), params), None, mt_states, labels, n_labels, device, table)
+
+
+def sat_augment_decide(params, turns, mt_states, labels, n_labels, device, table=None):
+    """`ssdhip_sat_augment_decide` / `_stream` / `_stream_ragged`, chosen as var_augment_decide chooses: params a dict of
+    ssdhip_var_augment_params' fields plus `vflip_prob` and `rotate_prob`; turns (B,) the quarter turns (1 .. 3) drawn from Python's
+    `random` in advance (stream mode: the k-th image that rotates takes turns[k]; seeded: image b takes turns[b]).  Inputs, outputs and
+    fetch() as var_augment_decide's; the geometry (B, 12) int32 is the satellite record, for sat_augment_plans[_ragged]."""
+    B = int(labels.shape[0])
+    turns = np.ascontiguousarray(turns, dtype=np.int32)
+    if turns.shape != (B,) or (B and (turns.min() < 1 or turns.max() > 3)):
+        raise SsdHipError("sat_augment_decide: turns (B,) with values 1 .. 3")
+    return _decide_patch_chain("sat_augment", _fill_struct(_SatAugParams(), params, inner="var"), turns, mt_states, labels, n_labels, device,
+                               table)
+
+
+# ---- the gathers' plans, built on the device from the geometry the decision kernels left there -----------------------------------------
+def _tap_tables(B, out_h, out_w, n_taps, dev):
+    """The plan builders' outputs, uninitialised: plans (B, 4) int32, ix (int32) / wx (float64) (B, out_w, n_taps), iy / wy
+    (B, out_h, n_taps)."""
+    torch = _torch()
+    return (torch.empty((B, 4), dtype=torch.int32, device=dev),
+            torch.empty((B, out_w, n_taps), dtype=torch.int32, device=dev), torch.empty((B, out_w, n_taps), dtype=torch.float64, device=dev),
+            torch.empty((B, out_h, n_taps), dtype=torch.int32, device=dev), torch.empty((B, out_h, n_taps), dtype=torch.float64, device=dev))
+
+
+def augment_plans(geo_dev, H, W, out_h, out_w, n_taps):
+    """`ssdhip_augment_plans`: the gather launch's per-image plans (plans (B, 4) int32, ix, wx, iy, wy: CUDA tensors
+    (B, out_w | out_h, n_taps)) with cv2.resize's own arithmetic, built on the device from the geometry the decision kernels left there."""
+    B, dev = int(geo_dev.shape[0]), geo_dev.device
+    tables = _tap_tables(B, out_h, out_w, n_taps, dev)
+    launch("ssdhip_augment_plans", dev, _ptr(geo_dev), B, int(H), int(W), int(out_h), int(out_w), int(n_taps), *map(_ptr, tables))
+    return tables
+
+
+def augment_plans_ragged(geo_dev, table, out_h, out_w, n_taps):
+    """`ssdhip_augment_plans_ragged`: augment_plans for a ragged batch, image b's size from `table` (B, 4) int64 CUDA tensor."""
+    B, dev = int(geo_dev.shape[0]), geo_dev.device
+    _ragged_table(table, "augment_plans_ragged: table (B, 4) int64", B)
+    tables = _tap_tables(B, out_h, out_w, n_taps, dev)
+    launch("ssdhip_augment_plans_ragged", dev, _ptr(geo_dev), _ptr(table), B, int(out_h), int(out_w), int(n_taps), *map(_ptr, tables))
+    return tables
 
 
 def const_augment_plans(geo_dev, H, W):
@@ -2867,138 +2860,6 @@ def const_augment_plans(geo_dev, H, W):
     return geo, xtab, ytab
 
 
-# ---- the decisions of the variable-input-size chain for a whole batch (csrc/ssdhip_augment.hip) --------------------------------------
-VAR_AUG_CRITERION = {"center_point": 0, "iou": 1, "area": 2}      # SSDHIP_VAR_AUG_*
-
-
-def var_augment_decide(params, mt_states, labels, n_labels, device, table=None):
-    """`ssdhip_var_augment_decide` (mt_states (B, 625): image b on its own MT19937 state; `table` optional) or
-    `ssdhip_var_augment_decide_stream` / `ssdhip_var_augment_decide_stream_ragged` (mt_states (625,): the batch in order on one state;
-    without / with `table`).  params: a dict of the fields of ssdhip_var_augment_params (img_height / img_width only without a table);
-    table: the ragged batch's (B, 4) int64 CUDA tensor (pack_ragged's: byte offset, H, W, C); labels (B, 64, 5) float64, n_labels (B,)
-    int32 NumPy arrays (ONE upload).  Returns (ops (B, 16) int32 and args (B, 16) float64 CUDA tensors = the programs of image_program,
-    geometry (B, 12) int32 CUDA tensor for augment_plans[_ragged], fetch) where fetch() downloads (geometry (B, 12), labels_out
-    (B, 64, 5), n_out (B,), mt_states_out (B, 625) | (625,)) as NumPy arrays."""
-    torch = _torch()
-    q = _VarAugParams()
-    for k, v in params.items():
-        if isinstance(v, (list, tuple)):
-            arr = getattr(q, k)
-            for i, e in enumerate(v):
-                arr[i] = e
-        else:
-            setattr(q, k, v)
-    B = int(labels.shape[0])
-    stream_mode = mt_states.ndim == 1
-    if mt_states.shape != ((625,) if stream_mode else (B, 625)) or labels.shape != (B, AUG_MAX_BOXES, 5) or n_labels.shape != (B,):
-        raise SsdHipError("var_augment_decide: mt_states (B, 625) or (625,), labels (B, 64, 5), n_labels (B,)")
-    if table is not None:
-        require_cuda(table, "table")
-        if tuple(table.shape) != (B, 4) or table.dtype != torch.int64:
-            raise SsdHipError("var_augment_decide: table (B, 4) int64")
-    # one packed upload: [labels f64 | mt u32 (padded to 8 bytes) | n i32];
-    # one packed download: [labels_out f64 | args f64 | mt_out u32 (padded) | geometry i32 | ops i32 | n_out i32]
-    n_mt = mt_states.size * 4
-    nl, nm = B * AUG_MAX_BOXES * 5 * 8, (n_mt + 7) // 8 * 8
-    host = np.zeros((nl + nm + B * 4,), dtype=np.uint8)
-    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
-    host[nl:nl + n_mt] = np.ascontiguousarray(mt_states, dtype=np.uint32).view(np.uint8).ravel()
-    host[nl + nm:] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
-    dev_in = torch.from_numpy(host).to(device)
-    na, ng = B * IMG_PROG * 8, B * 12 * 4
-    o_args, o_mt = nl, nl + na
-    o_geo = o_mt + nm
-    o_ops = o_geo + ng
-    o_n = o_ops + B * IMG_PROG * 4
-    dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
-    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
-    vp = ctypes.c_void_p
-    ptrs = (vp(base_in + nl), vp(base_in), vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args), vp(base_out + o_geo),
-            vp(base_out), vp(base_out + o_n), vp(base_out + o_mt))
-    n_max = int(n_labels.max()) if B else 0
-    if not stream_mode:
-        launch("ssdhip_var_augment_decide", device, ctypes.byref(q), B, n_max, _ptr(table) if table is not None else None, *ptrs)
-    elif table is None:
-        launch("ssdhip_var_augment_decide_stream", device, ctypes.byref(q), B, n_max, *ptrs)
-    else:
-        launch("ssdhip_var_augment_decide_stream_ragged", device, ctypes.byref(q), B, n_max, _ptr(table), *ptrs)
-    ops_dev = dev_out[o_ops:o_ops + B * IMG_PROG * 4].view(torch.int32).view(B, IMG_PROG)
-    args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG)
-    geo_dev = dev_out[o_geo:o_geo + ng].view(torch.int32).view(B, 12)
-
-    def fetch():
-        """(geometry, labels_out, n_out, mt_states_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
-        out = dev_out.cpu().numpy()
-        return (out[o_geo:o_geo + ng].view(np.int32).reshape(B, 12), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
-                out[o_n:].view(np.int32), out[o_mt:o_mt + n_mt].view(np.uint32).reshape(mt_states.shape).copy())
-    return ops_dev, args_dev, geo_dev, fetch
-
-
-# ---- the decisions of the satellite chain for a whole batch (csrc/ssdhip_augment.hip) ------------------------------------------------
-def sat_augment_decide(params, turns, mt_states, labels, n_labels, device, table=None):
-    """`ssdhip_sat_augment_decide` / `_stream` / `_stream_ragged`, chosen as var_augment_decide chooses: params a dict of
-    ssdhip_var_augment_params' fields plus `vflip_prob` and `rotate_prob`; turns (B,) the quarter turns (1 .. 3) drawn from Python's
-    `random` in advance (stream mode: the k-th image that rotates takes turns[k]; seeded: image b takes turns[b]).  Inputs, outputs and
-    fetch() as var_augment_decide's; the geometry (B, 12) int32 is the satellite record, for sat_augment_plans[_ragged]."""
-    torch = _torch()
-    q = _SatAugParams()
-    for k, v in params.items():
-        target = q if k in ("vflip_prob", "rotate_prob") else q.var
-        if isinstance(v, (list, tuple)):
-            arr = getattr(target, k)
-            for i, e in enumerate(v):
-                arr[i] = e
-        else:
-            setattr(target, k, v)
-    B = int(labels.shape[0])
-    turns = np.ascontiguousarray(turns, dtype=np.int32)
-    stream_mode = mt_states.ndim == 1
-    if mt_states.shape != ((625,) if stream_mode else (B, 625)) or labels.shape != (B, AUG_MAX_BOXES, 5) or n_labels.shape != (B,):
-        raise SsdHipError("sat_augment_decide: mt_states (B, 625) or (625,), labels (B, 64, 5), n_labels (B,)")
-    if turns.shape != (B,) or (B and (turns.min() < 1 or turns.max() > 3)):
-        raise SsdHipError("sat_augment_decide: turns (B,) with values 1 .. 3")
-    if table is not None:
-        require_cuda(table, "table")
-        if tuple(table.shape) != (B, 4) or table.dtype != torch.int64:
-            raise SsdHipError("sat_augment_decide: table (B, 4) int64")
-    # one packed upload: [labels f64 | mt u32 (padded to 8 bytes) | n i32 | turns i32]; the download is var_augment_decide's
-    n_mt = mt_states.size * 4
-    nl, nm = B * AUG_MAX_BOXES * 5 * 8, (n_mt + 7) // 8 * 8
-    host = np.zeros((nl + nm + B * 8,), dtype=np.uint8)
-    host[:nl] = np.ascontiguousarray(labels, dtype=np.float64).view(np.uint8).ravel()
-    host[nl:nl + n_mt] = np.ascontiguousarray(mt_states, dtype=np.uint32).view(np.uint8).ravel()
-    host[nl + nm:nl + nm + B * 4] = np.ascontiguousarray(n_labels, dtype=np.int32).view(np.uint8).ravel()
-    host[nl + nm + B * 4:] = turns.view(np.uint8).ravel()
-    dev_in = torch.from_numpy(host).to(device)
-    na, ng = B * IMG_PROG * 8, B * 12 * 4
-    o_args, o_mt = nl, nl + na
-    o_geo = o_mt + nm
-    o_ops = o_geo + ng
-    o_n = o_ops + B * IMG_PROG * 4
-    dev_out = torch.empty((o_n + B * 4,), dtype=torch.uint8, device=device)
-    base_in, base_out = dev_in.data_ptr(), dev_out.data_ptr()
-    vp = ctypes.c_void_p
-    ptrs = (vp(base_in + nl + nm + B * 4), vp(base_in + nl), vp(base_in), vp(base_in + nl + nm), vp(base_out + o_ops), vp(base_out + o_args),
-            vp(base_out + o_geo), vp(base_out), vp(base_out + o_n), vp(base_out + o_mt))
-    n_max = int(n_labels.max()) if B else 0
-    if not stream_mode:
-        launch("ssdhip_sat_augment_decide", device, ctypes.byref(q), B, n_max, _ptr(table) if table is not None else None, *ptrs)
-    elif table is None:
-        launch("ssdhip_sat_augment_decide_stream", device, ctypes.byref(q), B, n_max, *ptrs)
-    else:
-        launch("ssdhip_sat_augment_decide_stream_ragged", device, ctypes.byref(q), B, n_max, _ptr(table), *ptrs)
-    ops_dev = dev_out[o_ops:o_ops + B * IMG_PROG * 4].view(torch.int32).view(B, IMG_PROG)
-    args_dev = dev_out[o_args:o_args + na].view(torch.float64).view(B, IMG_PROG)
-    geo_dev = dev_out[o_geo:o_geo + ng].view(torch.int32).view(B, 12)
-
-    def fetch():
-        """(geometry, labels_out, n_out, mt_states_out) as NumPy arrays: ONE download (a host synchronisation: call it last)."""
-        out = dev_out.cpu().numpy()
-        return (out[o_geo:o_geo + ng].view(np.int32).reshape(B, 12), out[:nl].view(np.float64).reshape(B, AUG_MAX_BOXES, 5),
-                out[o_n:].view(np.int32), out[o_mt:o_mt + n_mt].view(np.uint32).reshape(mt_states.shape).copy())
-    return ops_dev, args_dev, geo_dev, fetch
-
-
 def sat_augment_plans(geo_dev, out_h, out_w, n_taps, size=None, table=None):
     """`ssdhip_sat_augment_plans` (size = the batch's (H, W)) or `ssdhip_sat_augment_plans_ragged` (table (B, 4) int64 CUDA tensor):
     the turn gathers' per-image plans from the satellite chain's geometry -> (plans (B, 4), ix, wx, iy, wy, transposed (B,) int32)."""
@@ -3006,22 +2867,14 @@ def sat_augment_plans(geo_dev, out_h, out_w, n_taps, size=None, table=None):
     B, dev = int(geo_dev.shape[0]), geo_dev.device
     if (size is None) == (table is None):
         raise SsdHipError("sat_augment_plans: one of size and table")
-    plans = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    ix = torch.empty((B, out_w, n_taps), dtype=torch.int32, device=dev)
-    wx = torch.empty((B, out_w, n_taps), dtype=torch.float64, device=dev)
-    iy = torch.empty((B, out_h, n_taps), dtype=torch.int32, device=dev)
-    wy = torch.empty((B, out_h, n_taps), dtype=torch.float64, device=dev)
-    transposed = torch.empty((B,), dtype=torch.int32, device=dev)
+    tables = _tap_tables(B, out_h, out_w, n_taps, dev) + (torch.empty((B,), dtype=torch.int32, device=dev),)
     if table is None:
         launch("ssdhip_sat_augment_plans", dev, _ptr(geo_dev), B, int(size[0]), int(size[1]), int(out_h), int(out_w), int(n_taps),
-               _ptr(plans), _ptr(ix), _ptr(wx), _ptr(iy), _ptr(wy), _ptr(transposed))
+               *map(_ptr, tables))
     else:
-        require_cuda(table, "table")
-        if tuple(table.shape) != (B, 4) or table.dtype != torch.int64:
-            raise SsdHipError("sat_augment_plans: table (B, 4) int64")
-        launch("ssdhip_sat_augment_plans_ragged", dev, _ptr(geo_dev), _ptr(table), B, int(out_h), int(out_w), int(n_taps), _ptr(plans),
-               _ptr(ix), _ptr(wx), _ptr(iy), _ptr(wy), _ptr(transposed))
-    return plans, ix, wx, iy, wy, transposed
+        _ragged_table(table, "sat_augment_plans: table (B, 4) int64", B)
+        launch("ssdhip_sat_augment_plans_ragged", dev, _ptr(geo_dev), _ptr(table), B, int(out_h), int(out_w), int(n_taps), *map(_ptr, tables))
+    return tables
 
 
 def image_resize_gather_turn_u8(images, table, out_h, out_w, plans, ix, wx, iy, wy, transposed, background):
@@ -3036,25 +2889,10 @@ def image_resize_gather_turn_u8(images, table, out_h, out_w, plans, ix, wx, iy, 
             raise SsdHipError("images must be a contiguous (B, H, W, C) uint8 tensor")
         b, h, w, c = images.shape
     else:
-        require_cuda(table, "table")
-        if images.dtype != torch.uint8 or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4:
-            raise SsdHipError("a ragged batch is a uint8 buffer and a (B, 4) int64 table")
-        b, c = int(table.shape[0]), 3
-    plans = to_device(plans, device=dev, dtype=torch.int32).contiguous()
-    ix = to_device(ix, device=dev, dtype=torch.int32).contiguous()
-    wx = to_device(wx, device=dev, dtype=torch.float64).contiguous()
-    iy = to_device(iy, device=dev, dtype=torch.int32).contiguous()
-    wy = to_device(wy, device=dev, dtype=torch.float64).contiguous()
-    tr = to_device(transposed, device=dev, dtype=torch.int32).contiguous()
-    bg = to_device(background, device=dev, dtype=torch.uint8).contiguous()
-    pad = lambda t: torch.cat([t, torch.zeros_like(t)], dim=2)
-    if ix.shape[2] < 2:
-        ix, wx = pad(ix), pad(wx)
-    if iy.shape[2] < 2:
-        iy, wy = pad(iy), pad(wy)
-    if (ix.shape != wx.shape or iy.shape != wy.shape or tuple(ix.shape[:2]) != (b, out_w) or tuple(iy.shape[:2]) != (b, out_h)
-            or tuple(bg.shape) != (b, c) or tuple(plans.shape) != (b, 4) or tuple(tr.shape) != (b,)):
-        raise SsdHipError("plans must be (B, 4), tap tables (B, out_w, nx) / (B, out_h, ny), transposed (B,), background (B, C)")
+        b, c = _ragged_table(table, "a ragged batch is a uint8 buffer and a (B, 4) int64 table", ok=images.dtype == torch.uint8), 3
+    plans, ix, wx, iy, wy, bg, tr = _gather_tables(
+        dev, b, c, out_h, out_w, plans, ix, wx, iy, wy, background,
+        "plans must be (B, 4), tap tables (B, out_w, nx) / (B, out_h, ny), transposed (B,), background (B, C)", transposed)
     out = torch.empty((b, out_h, out_w, c), dtype=torch.uint8, device=dev)
     if table is None:
         launch("ssdhip_image_resize_gather_turn_cv_u8", dev, _ptr(images), _ptr(out), b, h, w, int(out_h), int(out_w), c, _ptr(plans),

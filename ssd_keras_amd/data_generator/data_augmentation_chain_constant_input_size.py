@@ -14,34 +14,13 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _chain_batch as cb
 from . import _image_ops as iop
+from ._chain_batch import _seed_states  # noqa: F401  (its home until the chains shared a module; still imported from here)
 from .object_detection_2d_geometric_ops import RandomFlip, RandomScale, RandomTranslate
 from .object_detection_2d_image_boxes_validation_utils import BoxFilter, ImageValidator
 from .object_detection_2d_photometric_ops import (ConvertColor, ConvertDataType, ConvertTo3Channels, RandomBrightness, RandomContrast,
                                                   RandomHue, RandomSaturation)
-
-
-def _seed_states(seeds):
-    """(B, 625) uint32: per seed the MT19937 state `np.random.seed(seed)` leaves in the global generator (624 key words + the position),
-    without touching that generator.  `RandomState.get_state()` builds its tuple in 50 - 180 us, more than the rest of a seeded batch
-    takes per image, so the words are read where NumPy keeps them (`MT19937().ctypes.state_address`: uint32 key[624], int pos); the
-    first row of every call is held against `get_state()`, and if NumPy ever lays the state out differently all rows come from it."""
-    import ctypes
-    bit_generator = np.random.MT19937()
-    rs = np.random.RandomState(bit_generator)
-    out = np.empty((len(seeds), 625), dtype=np.uint32)
-    direct = True
-    for i, seed in enumerate(seeds):
-        rs.seed(int(seed))
-        if direct:
-            out[i] = np.frombuffer(ctypes.string_at(bit_generator.ctypes.state_address, 2500), dtype=np.uint32)
-        if i == 0 or not direct:
-            st = rs.get_state()
-            if i == 0 and not (np.array_equal(out[0, :624], st[1]) and int(out[0, 624]) == st[2]):
-                direct = False
-            if not direct:
-                out[i, :624], out[i, 624] = st[1], st[2]
-    return out
 
 
 class DataAugmentationConstantInputSize:
@@ -137,13 +116,13 @@ class DataAugmentationConstantInputSize:
             image = transform(image)
         return image
 
-    def _device_params(self, labels=None, generator='MT19937'):
+    def _device_params(self, labels=None, generator='MT19937', shapes=None):
         """The chain's configuration as the fields of ssdhip_const_augment_params (without the image size), or None for anything the
         decision kernel (csrc/ssdhip_augment.hip) does not cover: an overlap criterion other than 'area', `border_pixels` other than
         'half', `n_boxes_min == 'all'`, more than 64 trials (`nat.CONST_AUG_MAX_TRIALS`), a probability outside [0, 1], bounds that are
         not a pair of numbers, ops that no longer share the chain's box filter / validator / clipping / background -- and, when `labels`
         is given, label arrays that are not (n, 5), of mixed dtype, not int64 / float64 or longer than `nat.AUG_MAX_BOXES`; `generator`:
-        the name of np.random's bit generator, MT19937 is the one the kernel steps."""
+        the name of np.random's bit generator, MT19937 is the one the kernel steps; `shapes` (the images' (H, W)) does not matter here."""
         from .. import _native as nat
         tr, zin, zout, fl = self.random_translate, self.random_zoom_in, self.random_zoom_out, self.random_flip
         bf, val = self.box_filter, self.image_validator
@@ -172,10 +151,7 @@ class DataAugmentationConstantInputSize:
             except (TypeError, ValueError):
                 ok = False
         if ok and labels is not None:
-            arrs = [np.asarray(lab) for lab in labels]
-            dtypes = {a.dtype for a in arrs}
-            ok = (len(dtypes) == 1 and next(iter(dtypes)) in (np.dtype(np.int64), np.dtype(np.float64))
-                  and all(a.ndim == 2 and a.shape[1] == 5 and a.shape[0] <= nat.AUG_MAX_BOXES for a in arrs))
+            ok = cb.labels_fit(labels)
         if not ok:
             return None
         return dict(photo_prob=[float(op.prob) for op in photo],
@@ -189,34 +165,28 @@ class DataAugmentationConstantInputSize:
                     n_boxes_min=int(val.n_boxes_min), validator_lower=float(val.bounds[0]), validator_upper=float(val.bounds[1]),
                     filter_lower=float(bf.overlap_bounds[0]), filter_upper=float(bf.overlap_bounds[1]), filter_min_area=float(bf.min_area))
 
-    def _augment_batch_device(self, images, labels, params, mt):
+    def _augment_batch_device(self, batch, packed, shapes, labels, params, mt):
         """The four launches behind `_device_params`: decisions (`ssdhip_const_augment_decide[_stream]`: mt (B, 625) = one generator
         state per image, (625,) = one for the batch), the photometric programs read from the device, the warp launch's tables
-        (`ssdhip_const_augment_plans`) and the warp; ONE download at the end.  Returns (batch, labels, generator state(s))."""
+        (`ssdhip_const_augment_plans`) and the warp, on the CUDA batch `batch` (the chain takes no lists: `packed` is None); ONE download
+        at the end.  Returns (batch, labels, generator state(s))."""
         import torch
         from .. import _native as nat
-        B, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
-        lf = self.labels_format
-        cols = [lf['class_id'], lf['xmin'], lf['ymin'], lf['xmax'], lf['ymax']]
-        arrs = [np.asarray(lab) for lab in labels]
-        lab_in = np.zeros((B, nat.AUG_MAX_BOXES, 5), dtype=np.float64)
-        n_in = np.empty((B,), dtype=np.int32)
-        for i, a in enumerate(arrs):
-            n_in[i] = a.shape[0]
-            if a.shape[0]:
-                lab_in[i, :a.shape[0]] = a[:, cols]
-        ops_dev, args_dev, geo_dev, fetch = nat.const_augment_decide(dict(params, img_height=h, img_width=w), mt, lab_in, n_in, images.device)
-        distorted = nat.image_program(images.contiguous(), ops_dev, args_dev, torch.uint8)         # both sequences end in 'to_u8'
+        (h, w), cols = shapes[0], cb.label_cols(self.labels_format)
+        arrs, lab_in, n_in = cb.pack_labels(labels, cols)
+        ops_dev, args_dev, geo_dev, fetch = nat.const_augment_decide(dict(params, img_height=h, img_width=w), mt, lab_in, n_in, batch.device)
+        distorted = nat.image_program(batch.contiguous(), ops_dev, args_dev, torch.uint8)          # both sequences end in 'to_u8'
         geo5, xtab, ytab = nat.const_augment_plans(geo_dev, h, w)
-        row = tuple(int(v) for v in iop.border_value(self.random_translate.background, 3))
-        bg = self.__dict__.get("_bg_rows")
-        if bg is None or bg[0] != (B, str(images.device), row):
-            bg = ((B, str(images.device), row), nat.to_device(np.repeat(np.array(row, dtype=np.uint8)[None], B, 0), device=images.device))
-            self.__dict__["_bg_rows"] = bg
-        out = nat.image_warp_affine_u8(distorted, h, w, geo5, xtab, ytab, bg[1])
+        bg = cb.background_rows(self, len(shapes), batch.device, iop.border_value(self.random_translate.background, 3))
+        out = nat.image_warp_affine_u8(distorted, h, w, geo5, xtab, ytab, bg)
         _, lab_out, n_out, mt_out = fetch()
-        inv, dt = np.argsort(cols), arrs[0].dtype
-        return out, [np.ascontiguousarray(lab_out[i, :int(n_out[i])][:, inv]).astype(dt) for i in range(B)], mt_out
+        return out, cb.unpack_labels(lab_out, n_out, cols, arrs[0].dtype), mt_out
+
+    def _augment_batch_host(self, batch, packed, shapes, labels, seeds):
+        """What `_device_params` does not cover: per image the sequence choice and the photometric draws, then the sequence's geometric ops
+        on a lazy image (`_image_ops.WarpImage`) -- under the image's seed when `seeds` is given -- and the pixels of the batch in two
+        launches.  Returns (batch, labels, the generator state behind each image (B, 625) | None without seeds)."""
+        return cb.host_batch(batch, packed, shapes, labels, seeds, lambda: self._draw()[1:], iop.WarpImage)
 
     def augment_batch(self, images, labels, seeds=None):
         """The chain on a device-resident batch: images (B, H, W, 3) CUDA uint8, labels a list of B label arrays -> ((B, H, W, 3) CUDA
@@ -232,57 +202,4 @@ class DataAugmentationConstantInputSize:
         `seeds=[s_0, ...]`: image i comes out exactly as `np.random.seed(s_i); chain(image_i, labels_i)` gives it, every image on its own
         stream (`ssdhip_const_augment_decide`: one wave per image), the global generator untouched; `_last_generator_states` (B, 625)
         holds the state behind each image.  What `_device_params` does not cover runs the per-image code under each seed."""
-        import os
-        import torch
-        if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3):
-            raise TypeError("augment_batch takes a (B, H, W, 3) CUDA uint8 batch")
-        if len(labels) != images.shape[0]:
-            raise ValueError("one label array per image")
-        if seeds is not None and len(seeds) != images.shape[0]:
-            raise ValueError("one seed per image")
-        self._sync_formats()
-        h, w = int(images.shape[1]), int(images.shape[2])
-        B = int(images.shape[0])
-        if seeds is not None:
-            params = self._device_params(labels) if B else None
-            if params is not None:
-                out, out_labels, mt_out = self._augment_batch_device(images, labels, params, _seed_states(seeds))
-                self.__dict__["_last_generator_states"] = mt_out
-                return out, out_labels
-            saved = np.random.get_state()
-            try:
-                programs, lazies, out_labels, states = [], [], [], np.empty((B, 625), dtype=np.uint32)
-                for i, (lab, seed) in enumerate(zip(labels, seeds)):
-                    np.random.seed(int(seed))
-                    _, steps, geometric = self._draw()
-                    img = iop.WarpImage.of(h, w)
-                    for transform in geometric:
-                        img, lab = transform(img, lab)
-                    programs.append(steps)
-                    lazies.append(img)
-                    out_labels.append(lab)
-                    st = np.random.get_state()
-                    states[i, :624], states[i, 624] = st[1], st[2]
-            finally:
-                np.random.set_state(saved)
-            self.__dict__["_last_generator_states"] = states
-            return iop.warp_batch(iop.run_batch(images, programs), lazies), out_labels
-        if os.environ.get("SSDHIP_AUG_HOST_STREAM", "0") != "1" and B:
-            state = np.random.get_state()
-            params = self._device_params(labels, generator=state[0])
-            if params is not None:
-                mt = np.empty((625,), dtype=np.uint32)
-                mt[:624], mt[624] = state[1], state[2]
-                out, out_labels, mt_out = self._augment_batch_device(images, labels, params, mt)
-                np.random.set_state((state[0], mt_out[:624], int(mt_out[624]), state[3], state[4]))   # the stream goes on behind the batch
-                return out, out_labels
-        programs, lazies, out_labels = [], [], []
-        for lab in labels:
-            _, steps, geometric = self._draw()
-            img = iop.WarpImage.of(h, w)
-            for transform in geometric:
-                img, lab = transform(img, lab)
-            programs.append(steps)
-            lazies.append(img)
-            out_labels.append(lab)
-        return iop.warp_batch(iop.run_batch(images, programs), lazies), out_labels
+        return cb.augment_batch(self, images, labels, seeds, lists=False)

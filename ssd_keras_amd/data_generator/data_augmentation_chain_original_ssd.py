@@ -16,6 +16,7 @@ import os
 
 import numpy as np
 
+from . import _chain_batch as cb
 from . import _image_ops as iop
 from .object_detection_2d_geometric_ops import (INTER_AREA, INTER_CUBIC, INTER_LANCZOS4, INTER_LINEAR, INTER_NEAREST, RandomFlip,
                                                 ResizeRandomInterp)
@@ -133,6 +134,17 @@ class SSDDataAugmentation:
                 image, labels = transform(image, labels)
         return (image, labels, inverters[::-1]) if return_inverter else (image, labels)
 
+    def _sync_formats(self):
+        for t in (self.expand, self.random_crop, self.random_flip, self.resize):
+            t.labels_format = self.labels_format
+
+    def _n_taps(self, shapes):
+        """Taps per output pixel of tables wide enough for the true area filter of the largest possible source (an expanded, uncropped
+        image) of images of these (H, W)."""
+        h_max, w_max = max(s[0] for s in shapes), max(s[1] for s in shapes)
+        max_scale = float(self.expand.expand.patch_coord_generator.max_scale)
+        return max(8, int(np.ceil(max_scale * max(h_max / int(self.resize.height), w_max / int(self.resize.width)))) + 2)
+
     def augment_batch(self, images, labels, seeds=None):
         """The whole chain on a device-resident batch: images (B, H, W, 3) CUDA uint8, labels a list of B
         (n_i, 5) arrays -> ((B, img_height, img_width, 3) CUDA uint8 batch, list of B label arrays).  TWO launches for the pixels of
@@ -147,17 +159,13 @@ class SSDDataAugmentation:
         photometric draws, and ONE launch (`ssdhip_ssd_augment_decide`, a wave per image consuming that image's MT19937 stream as NumPy
         does) takes every other decision of the chain -- expansion, the crop search with its IoU validation, flip, interpolation mode --
         and does the label arithmetic.  The global NumPy generator is left untouched."""
-        import torch
         if isinstance(images, (list, tuple)):
             if seeds is not None:
                 raise ValueError("seeds= takes a (B, H, W, 3) CUDA batch; a list of images runs on the global np.random stream")
             return self._augment_ragged(images, labels)
         if seeds is not None:
             return self._augment_batch_seeded(images, labels, seeds)
-        if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3):
-            raise TypeError("augment_batch takes a (B, H, W, 3) CUDA uint8 batch")
-        if len(labels) != images.shape[0]:
-            raise ValueError("one label array per image")
+        batch, _, shapes = cb.parse_batch(images, labels, lists=False)
         if os.environ.get("SSDHIP_AUG_HOST_STREAM", "0") != "1":
             # Round 6: the reference's own semantics -- ONE global np.random stream across the batch -- decided on the device: a single wave
             # walks the images in order on that stream (ssdhip_ssd_augment_decide_stream: photometric AND geometric decisions, label
@@ -166,19 +174,16 @@ class SSDDataAugmentation:
             done = self._augment_batch_seeded(images, labels, None)
             if done is not None:
                 return done
-        for t in (self.expand, self.random_crop, self.random_flip, self.resize):
-            t.labels_format = self.labels_format
-        h, w = int(images.shape[1]), int(images.shape[2])
-        programs, lazies, out_labels = [], [], []
-        for lab in labels:
-            programs.append(self.photometric_distortions.draw())         # the draws of this image's photometric part, then its geometry
-            img, lab = iop.GeoImage.of(h, w), np.asarray(lab)
-            for transform in (self.expand, self.random_crop, self.random_flip, self.resize):
-                img, lab = transform(img, lab)
-            lazies.append(img)
-            out_labels.append(lab)
-        distorted = iop.run_batch(images, programs)
-        return iop.gather_batch(distorted, lazies), out_labels
+        return self._augment_batch_host(batch, None, shapes, labels, None)[:2]
+
+    def _augment_batch_host(self, batch, packed, shapes, labels, seeds):
+        """The per-image chain's own code: per image the photometric draws, then expansion, crop, flip and resize on a lazy image -- under
+        the image's seed when `seeds` is given -- and the pixels of the batch in two launches.  Returns (batch, labels, the generator state
+        behind each image (B, 625) | None without seeds)."""
+        self._sync_formats()
+        geometric = (self.expand, self.random_crop, self.random_flip, self.resize)
+        return cb.host_batch(batch, packed, shapes, [np.asarray(lab) for lab in labels], seeds,
+                             lambda: (self.photometric_distortions.draw(), geometric), iop.GeoImage)
 
     def _augment_ragged(self, images, labels):
         """augment_batch for a LIST of (H_i, W_i, 3) uint8 images of different sizes (NumPy arrays or CUDA tensors): one upload
@@ -188,57 +193,28 @@ class SSDDataAugmentation:
         np.random state as calling the chain on image 0, 1, 2, ...; a configuration or label layout the kernel does not cover takes the
         per-image chain's own code (host decisions, the same two pixel launches)."""
         from .. import _native as nat
-        if len(labels) != len(images):
-            raise ValueError("one label array per image")
-        if any(len(im.shape) != 3 or int(im.shape[2]) != 3 for im in images):
-            raise TypeError("augment_batch takes a list of (H, W, 3) uint8 images")
-        for t in (self.expand, self.random_crop, self.random_flip, self.resize):
-            t.labels_format = self.labels_format
-        packed = iop.pack_ragged(list(images))
-        B = len(packed)
-        lf = self.labels_format
-        cols = [lf['class_id'], lf['xmin'], lf['ymin'], lf['xmax'], lf['ymax']]
-        arrs = [np.asarray(lab) for lab in labels]
-        h_max, w_max = max(s[0] for s in packed.shapes), max(s[1] for s in packed.shapes)
-        params, photo, state = self._seeded_params(h_max, w_max), self._photo_params(), np.random.get_state()
-        dtypes = {a.dtype for a in arrs}
-        fast = (params is not None and photo is not None and state[0] == 'MT19937' and len(dtypes) == 1
-                and next(iter(dtypes)) in (np.dtype(np.int64), np.dtype(np.float64)) and sorted(cols) == [0, 1, 2, 3, 4]
-                and all(a.ndim == 2 and a.shape[1] == 5 and a.shape[0] <= nat.AUG_MAX_BOXES for a in arrs))
-        out_h, out_w = int(self.resize.height), int(self.resize.width)
-        n_taps = max(8, int(np.ceil(float(self.expand.expand.patch_coord_generator.max_scale) * max(h_max / out_h, w_max / out_w))) + 2)
-        if not fast:
-            programs, lazies, out_labels = [], [], []
-            for (h, w, _), lab in zip(packed.shapes, arrs):
-                programs.append(self.photometric_distortions.draw())
-                img = iop.GeoImage.of(h, w)
-                for transform in (self.expand, self.random_crop, self.random_flip, self.resize):
-                    img, lab = transform(img, lab)
-                lazies.append(img)
-                out_labels.append(lab)
-            return iop.gather_batch_ragged(iop.run_ragged(packed, programs), lazies), out_labels
-        lab_in = np.zeros((B, nat.AUG_MAX_BOXES, 5), dtype=np.float64)
-        n_in = np.empty((B,), dtype=np.int32)
-        for i, a in enumerate(arrs):
-            n_in[i] = a.shape[0]
-            if a.shape[0]:
-                lab_in[i, :a.shape[0]] = a[:, cols]
-        mt = np.empty((625,), dtype=np.uint32)
-        mt[:624], mt[624] = state[1], state[2]
+        _, packed, shapes = cb.parse_batch(images, labels)
+        self._sync_formats()
+        B, cols = len(packed), cb.label_cols(self.labels_format)
+        h_max, w_max = max(s[0] for s in shapes), max(s[1] for s in shapes)
+        params, photo = self._seeded_params(h_max, w_max), self._photo_params()
+        name, mt, rest = cb.read_np_state()
+        if not (params is not None and photo is not None and name == 'MT19937' and sorted(cols) == [0, 1, 2, 3, 4] and cb.labels_fit(labels)):
+            return self._augment_batch_host(None, packed, shapes, labels, None)[:2]
+        out_h, out_w, n_taps = int(self.resize.height), int(self.resize.width), self._n_taps(shapes)
+        arrs, lab_in, n_in = cb.pack_labels(labels, cols)
         ops_dev, args_dev, geo_dev, fetch = nat.ssd_augment_decide_stream_ragged(params, photo, mt, lab_in, n_in, packed.table)
         distorted = packed.like(nat.image_program_ragged_u8(packed.data, packed.table, packed.max_pixels, ops_dev, args_dev))
-        inv = np.argsort(cols)
         if n_taps <= 64:
             plans, ix, wx, iy, wy = nat.augment_plans_ragged(geo_dev, packed.table, out_h, out_w, n_taps)
-            row = np.array([int(v) for v in self.expand.expand.background], dtype=np.uint8)
-            out = nat.image_resize_gather_ragged_u8(distorted.data, packed.table, out_h, out_w, plans, ix, wx, iy, wy, np.repeat(row[None], B, 0))
+            bg = cb.background_rows(self, B, packed.data.device, self.expand.expand.background)
+            out = nat.image_resize_gather_ragged_u8(distorted.data, packed.table, out_h, out_w, plans, ix, wx, iy, wy, bg)
             geo, lab_out, n_out, mt_out = fetch()
         else:                                            # (a source too large for the device-built tables: host-built geometry)
             geo, lab_out, n_out, mt_out = fetch()
-            out = iop.gather_batch_ragged(distorted, [self._lazy_of(geo[i], h, w) for i, (h, w, _) in enumerate(packed.shapes)])
-        dt = arrs[0].dtype
-        np.random.set_state((state[0], mt_out[:624], int(mt_out[624]), state[3], state[4]))
-        return out, [np.ascontiguousarray(lab_out[i, :int(n_out[i])][:, inv]).astype(dt) for i in range(B)]
+            out = iop.gather_batch_ragged(distorted, [self._lazy_of(geo[i], h, w) for i, (h, w) in enumerate(shapes)])
+        cb.put_np_state(name, mt_out, rest)
+        return out, cb.unpack_labels(lab_out, n_out, cols, arrs[0].dtype)
 
     def _lazy_of(self, g, h, w):
         """The GeoImage of one image's recorded geometry (a row of ssdhip_ssd_augment_decide*'s `geometry`)."""
@@ -284,69 +260,39 @@ class SSDDataAugmentation:
     def _augment_batch_seeded(self, images, labels, seeds):
         import torch
         from .. import _native as nat
-        if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3):
+        if not cb.is_cuda_batch(images):
             raise TypeError("augment_batch takes a (B, H, W, 3) CUDA uint8 batch")
         B, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
         stream_mode = seeds is None                      # one global generator for the whole batch (the reference's contract)
         if len(labels) != B or (not stream_mode and len(seeds) != B):
             raise ValueError("one label array and one seed per image")
-        lf = self.labels_format
-        cols = [lf['class_id'], lf['xmin'], lf['ymin'], lf['xmax'], lf['ymax']]
-        arrs = [np.asarray(lab) for lab in labels]
+        cols = cb.label_cols(self.labels_format)
         params = self._seeded_params(h, w)
-        dtypes = {a.dtype for a in arrs}
-        fast = (params is not None and len(dtypes) == 1 and next(iter(dtypes)) in (np.dtype(np.int64), np.dtype(np.float64))
-                and all(a.ndim == 2 and a.shape[1] == 5 and a.shape[0] <= nat.AUG_MAX_BOXES for a in arrs) and sorted(cols) == [0, 1, 2, 3, 4])
+        fast = params is not None and cb.labels_fit(labels) and sorted(cols) == [0, 1, 2, 3, 4]
         if stream_mode:
             photo = self._photo_params()
-            state = np.random.get_state()
-            if not fast or photo is None or state[0] != 'MT19937' or B == 0:
+            name, mt, rest = cb.read_np_state()
+            if not fast or photo is None or name != 'MT19937' or B == 0:
                 return None
-            lab_in = np.zeros((B, nat.AUG_MAX_BOXES, 5), dtype=np.float64)
-            n_in = np.empty((B,), dtype=np.int32)
-            for i, a in enumerate(arrs):
-                n_in[i] = a.shape[0]
-                if a.shape[0]:
-                    lab_in[i, :a.shape[0]] = a[:, cols]
-            mt = np.empty((625,), dtype=np.uint32)
-            mt[:624], mt[624] = state[1], state[2]
+            arrs, lab_in, n_in = cb.pack_labels(labels, cols)
             ops_dev, args_dev, geo_dev, fetch = nat.ssd_augment_decide_stream(params, photo, mt, lab_in, n_in, images.device)
             distorted = nat.image_program(images.contiguous(), ops_dev, args_dev, torch.uint8)     # both sequences end in 'to_u8'
             out, out_labels, mt_out = self._gather_from_decisions(images, distorted, geo_dev, fetch, arrs[0].dtype, cols, B, h, w)
-            np.random.set_state((state[0], mt_out[:624], int(mt_out[624]), state[3], state[4]))    # the stream goes on behind the batch
+            cb.put_np_state(name, mt_out, rest)          # the stream goes on behind the batch
             return out, out_labels
         saved = np.random.get_state()
         try:
             if not fast:                                 # anything the kernel does not cover: the per-image chain's own code, seeded per image
-                programs, lazies, out_labels = [], [], []
-                for t in (self.expand, self.random_crop, self.random_flip, self.resize):
-                    t.labels_format = self.labels_format
-                for lab, seed in zip(arrs, seeds):
-                    np.random.seed(int(seed))
-                    programs.append(self.photometric_distortions.draw())
-                    img = iop.GeoImage.of(h, w)
-                    for transform in (self.expand, self.random_crop, self.random_flip, self.resize):
-                        img, lab = transform(img, lab)
-                    lazies.append(img)
-                    out_labels.append(lab)
-                return iop.gather_batch(iop.run_batch(images, programs), lazies), out_labels
+                return self._augment_batch_host(images, None, [(h, w)] * B, labels, seeds)[:2]
             # ---- host: the photometric draws of every image under its own seed; the generator state behind them goes to the device ----
-            mt = np.empty((B, 625), dtype=np.uint32)
-            lab_in = np.zeros((B, nat.AUG_MAX_BOXES, 5), dtype=np.float64)
-            n_in = np.empty((B,), dtype=np.int32)
-            programs = []
+            mt, programs = np.empty((B, 625), dtype=np.uint32), []
             for i in range(B):
                 np.random.seed(int(seeds[i]))
                 programs.append(self.photometric_distortions.draw())
-                st = np.random.get_state()
-                mt[i, :624] = st[1]
-                mt[i, 624] = st[2]
-                a = arrs[i]
-                n_in[i] = a.shape[0]
-                if a.shape[0]:
-                    lab_in[i, :a.shape[0]] = a[:, cols]
+                cb.record_np_state(mt, i)
         finally:
             np.random.set_state(saved)
+        arrs, lab_in, n_in = cb.pack_labels(labels, cols)
         distorted = iop.run_batch(images, programs)
         geo_dev, fetch = nat.ssd_augment_decide(params, mt, lab_in, n_in, images.device)
         out, out_labels, mt_out = self._gather_from_decisions(images, distorted, geo_dev, fetch, arrs[0].dtype, cols, B, h, w)
@@ -368,34 +314,15 @@ class SSDDataAugmentation:
         """The pixel half behind the device-side decisions: tap tables built on the device from `geo_dev`, ONE gather launch, then the one
         download of the call (labels, geometry, generator state).  Returns (batch, labels, generator state(s))."""
         from .. import _native as nat
-        out_h, out_w = int(self.resize.height), int(self.resize.width)
-        # tap tables wide enough for the true area filter of the largest possible source (an expanded, uncropped image)
-        n_taps = max(8, int(np.ceil(float(self.expand.expand.patch_coord_generator.max_scale) * max(h / out_h, w / out_w))) + 2)
-        inv = np.argsort(cols)
+        out_h, out_w, n_taps = int(self.resize.height), int(self.resize.width), self._n_taps([(h, w)])
         if n_taps <= 64 and os.environ.get("SSDHIP_AUG_HOST_TAPS", "0") != "1":
             # ---- tap tables built on the device from the decisions, the gather launch behind them; the labels come back last (the only
             #      host synchronisation of the call) ------------------------------------------------------------------------------------
             plans, ix, wx, iy, wy = nat.augment_plans(geo_dev, h, w, out_h, out_w, n_taps)
-            bg = self.__dict__.get("_bg_rows")
-            if bg is None or bg[0] != (B, str(images.device)):
-                row = np.array([int(v) for v in self.expand.expand.background], dtype=np.uint8)
-                bg = ((B, str(images.device)), nat.to_device(np.repeat(row[None], B, 0), device=images.device))
-                self.__dict__["_bg_rows"] = bg
-            out = nat.image_resize_gather_cv_u8(distorted.contiguous(), out_h, out_w, plans, ix, wx, iy, wy, bg[1])
+            bg = cb.background_rows(self, B, images.device, self.expand.expand.background)
+            out = nat.image_resize_gather_cv_u8(distorted.contiguous(), out_h, out_w, plans, ix, wx, iy, wy, bg)
+            _, lab_out, n_out, mt_out = fetch()
+        else:                                            # the recorded geometry of every image -> one gather launch
             geo, lab_out, n_out, mt_out = fetch()
-            return out, [np.ascontiguousarray(lab_out[i, :int(n_out[i])][:, inv]).astype(dt) for i in range(B)], mt_out
-        geo, lab_out, n_out, mt_out = fetch()
-        # ---- the recorded geometry of every image -> one gather launch; the labels back in the caller's column order and dtype ----------
-        lazies, out_labels = [], []
-        for i in range(B):
-            g = geo[i]
-            img = iop.GeoImage.of(h, w)
-            if g[0]:
-                img = img.window(int(g[1]), int(g[2]), int(g[3]), int(g[4]), self.expand.expand.background)
-            if g[5]:
-                img = img.window(int(g[6]), int(g[7]), int(g[8]), int(g[9]), self.random_crop.random_crop.background)
-            if g[10]:
-                img = img[:, ::-1]
-            lazies.append(img.resize(self.resize.height, self.resize.width, int(g[11])))
-            out_labels.append(np.ascontiguousarray(lab_out[i, :int(n_out[i])][:, inv]).astype(dt))
-        return iop.gather_batch(distorted, lazies), out_labels, mt_out
+            out = iop.gather_batch(distorted, [self._lazy_of(geo[i], h, w) for i in range(B)])
+        return out, cb.unpack_labels(lab_out, n_out, cols, dt), mt_out

@@ -14,10 +14,8 @@ As in the reference, `__call__` without labels reaches for a `sequence1` the cla
 `background` argument never reaches RandomPatch (:114-121): what a patch adds around an image is RandomPatch's own default, black."""
 from __future__ import annotations
 
-import numpy as np
-
+from . import _chain_batch as cb
 from . import _image_ops as iop
-from .data_augmentation_chain_constant_input_size import _seed_states
 from .object_detection_2d_geometric_ops import RandomFlip, Resize
 from .object_detection_2d_image_boxes_validation_utils import BoxFilter, ImageValidator
 from .object_detection_2d_patch_sampling_ops import PatchCoordinateGenerator, RandomPatch
@@ -106,19 +104,12 @@ class DataAugmentationVariableInputSize:
 
     def _draw(self):
         """One image's photometric draws in the order of `transformations` -> its pixel program."""
-        return ([("to_f32", 0)] + self.random_brightness.draw() + self.random_contrast.draw() + [("to_u8", 0), ("rgb2hsv", 0), ("to_f32", 0)]
-                + self.random_saturation.draw() + self.random_hue.draw() + [("to_u8", 0), ("hsv2rgb", 0)])
+        return cb.photo_program(self)
 
     def _n_taps(self, shapes):
         """Taps per output pixel the device-built tables need for images of these (H, W): eight (Lanczos-4's) unless Resize runs in
         INTER_AREA, whose true area filter takes ceil(source / output extent) + 2 of the largest possible patch."""
-        if int(self.resize.interpolation_mode) != iop.INTER_AREA:
-            return 8
-        gen = self.random_patch.patch_coord_generator
-        h_max, w_max = max(s[0] for s in shapes), max(s[1] for s in shapes)
-        pw = float(gen.max_scale) * w_max
-        ph = pw / float(gen.min_aspect_ratio)
-        return max(8, int(np.ceil(max(max(ph, h_max) / self.resize.out_height, max(pw, w_max) / self.resize.out_width))) + 2)
+        return cb.patch_n_taps(self, shapes)
 
     def _device_params(self, labels=None, generator='MT19937', shapes=None):
         """The chain's configuration as the fields of ssdhip_var_augment_params (without the image size), or None for anything the
@@ -129,62 +120,7 @@ class DataAugmentationVariableInputSize:
         not int64 / float64 or longer than `nat.AUG_MAX_BOXES`; `generator`: the name of np.random's bit generator, MT19937 is the one
         the kernel steps; `shapes`: the images' (H, W) -- an image narrower than 4 px, one so small that a patch could come out empty,
         or (INTER_AREA only) sizes whose tap tables would pass 64 entries are not covered."""
-        from .. import _native as nat
-        rp, fl, rs = self.random_patch, self.random_flip, self.resize
-        gen, sp, val, bfr = rp.patch_coord_generator, rp.sample_patch, rp.image_validator, rs.box_filter
-        bf = sp.box_filter
-        photo = (self.random_brightness, self.random_contrast, self.random_saturation, self.random_hue)
-        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
-        whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-        pair = lambda v: isinstance(v, (list, tuple)) and len(v) == 2 and number(v[0]) and number(v[1]) and v[0] <= v[1]
-        ok = (generator == 'MT19937'
-              and isinstance(bf, BoxFilter) and isinstance(val, ImageValidator) and isinstance(bfr, BoxFilter)
-              and isinstance(gen, PatchCoordinateGenerator)
-              and bf.overlap_criterion == val.overlap_criterion and bf.overlap_criterion in nat.VAR_AUG_CRITERION
-              and bf.border_pixels == 'half' and val.border_pixels == 'half'
-              and bf.check_overlap and not bf.check_min_area and not bf.check_degenerate
-              and not bfr.check_overlap and bfr.check_min_area and bfr.check_degenerate and number(bfr.min_area)
-              and pair(bf.overlap_bounds) and pair(val.bounds)
-              and (val.n_boxes_min == 'all' or (whole(val.n_boxes_min) and val.n_boxes_min >= 1))
-              and whole(rp.n_trials_max) and rp.n_trials_max >= 0 and not rp.can_fail
-              and gen.must_match == 'w_ar' and not gen.scale_uniformly
-              and all(v is None for v in (gen.patch_ymin, gen.patch_xmin, gen.patch_height, gen.patch_width, gen.patch_aspect_ratio))
-              and number(gen.min_scale) and number(gen.max_scale) and 0 < gen.min_scale < gen.max_scale
-              and number(gen.min_aspect_ratio) and number(gen.max_aspect_ratio) and 0 < gen.min_aspect_ratio < gen.max_aspect_ratio
-              and all(number(op.prob) and 0.0 <= op.prob <= 1.0 for op in photo + (rp, fl))
-              and fl.dim == 'horizontal'
-              and whole(rs.interpolation_mode) and 0 <= rs.interpolation_mode <= 4
-              and whole(rs.out_height) and whole(rs.out_width) and rs.out_height > 0 and rs.out_width > 0
-              and sorted(self.labels_format.get(k, -1) for k in ('class_id', 'xmin', 'ymin', 'xmax', 'ymax')) == [0, 1, 2, 3, 4])
-        if ok:
-            try:
-                ok = len(tuple(int(v) for v in sp.background)) == 3
-            except (TypeError, ValueError):
-                ok = False
-        if ok and labels is not None:
-            arrs = [np.asarray(lab) for lab in labels]
-            dtypes = {a.dtype for a in arrs}
-            ok = (len(dtypes) == 1 and next(iter(dtypes)) in (np.dtype(np.int64), np.dtype(np.float64))
-                  and all(a.ndim == 2 and a.shape[1] == 5 and a.shape[0] <= nat.AUG_MAX_BOXES for a in arrs))
-        if ok and shapes is not None:
-            w_min = min(s[1] for s in shapes)
-            # the narrowest patch is int(min_scale * W) wide and int(width / aspect ratio) high: both must stay >= 1
-            ok = (w_min >= 4 and min(s[0] for s in shapes) >= 1 and int(gen.min_scale * w_min) >= max(1.0, gen.max_aspect_ratio)
-                  and self._n_taps(shapes) <= 64)
-        if not ok:
-            return None
-        return dict(photo_prob=[float(op.prob) for op in photo],
-                    photo_lower=[float(op.lower) for op in photo[:3]] + [-float(self.random_hue.max_delta)],
-                    photo_upper=[float(op.upper) for op in photo[:3]] + [float(self.random_hue.max_delta)],
-                    patch_prob=float(rp.prob), min_scale=float(gen.min_scale), max_scale=float(gen.max_scale),
-                    min_aspect_ratio=float(gen.min_aspect_ratio), max_aspect_ratio=float(gen.max_aspect_ratio),
-                    n_trials=int(rp.n_trials_max), clip_boxes=int(bool(sp.clip_boxes)),
-                    criterion=int(nat.VAR_AUG_CRITERION[bf.overlap_criterion]),
-                    n_boxes_min=0 if val.n_boxes_min == 'all' else int(val.n_boxes_min),
-                    validator_lower=float(val.bounds[0]), validator_upper=float(val.bounds[1]),
-                    filter_lower=float(bf.overlap_bounds[0]), filter_upper=float(bf.overlap_bounds[1]), flip_prob=float(fl.prob),
-                    out_height=int(rs.out_height), out_width=int(rs.out_width), interpolation=int(rs.interpolation_mode),
-                    resize_min_area=float(bfr.min_area))
+        return cb.patch_device_params(self, ((self.random_flip, 'horizontal'),), labels, generator, shapes)
 
     def _lazy_of(self, g, h, w):
         """The GeoImage of one image's recorded geometry (a row of ssdhip_var_augment_decide*'s `geometry`) over an h x w image."""
@@ -199,61 +135,14 @@ class DataAugmentationVariableInputSize:
         """The four launches behind `_device_params`: decisions (mt (B, 625) = one generator state per image, (625,) = one for the
         batch), the photometric programs read from the device, the tap tables and the gather -- on the CUDA batch `batch`, or on the
         ragged batch `packed`; ONE download at the end.  Returns (batch, labels, generator state(s))."""
-        import torch
-        from .. import _native as nat
-        B = len(shapes)
-        lf = self.labels_format
-        cols = [lf['class_id'], lf['xmin'], lf['ymin'], lf['xmax'], lf['ymax']]
-        arrs = [np.asarray(lab) for lab in labels]
-        lab_in = np.zeros((B, nat.AUG_MAX_BOXES, 5), dtype=np.float64)
-        n_in = np.empty((B,), dtype=np.int32)
-        for i, a in enumerate(arrs):
-            n_in[i] = a.shape[0]
-            if a.shape[0]:
-                lab_in[i, :a.shape[0]] = a[:, cols]
-        out_h, out_w, n_taps = int(self.resize.out_height), int(self.resize.out_width), self._n_taps(shapes)
-        device = batch.device if packed is None else packed.data.device
-        row = tuple(int(v) for v in self.random_patch.sample_patch.background)
-        bg = self.__dict__.get("_bg_rows")
-        if bg is None or bg[0] != (B, str(device), row):
-            bg = ((B, str(device), row), nat.to_device(np.repeat(np.array(row, dtype=np.uint8)[None], B, 0), device=device))
-            self.__dict__["_bg_rows"] = bg
-        if packed is None:
-            h, w = shapes[0]
-            ops_dev, args_dev, geo_dev, fetch = nat.var_augment_decide(dict(params, img_height=h, img_width=w), mt, lab_in, n_in, device)
-            distorted = nat.image_program(batch.contiguous(), ops_dev, args_dev, torch.uint8)
-            plans, ix, wx, iy, wy = nat.augment_plans(geo_dev, h, w, out_h, out_w, n_taps)
-            out = nat.image_resize_gather_cv_u8(distorted, out_h, out_w, plans, ix, wx, iy, wy, bg[1])
-        else:
-            ops_dev, args_dev, geo_dev, fetch = nat.var_augment_decide(params, mt, lab_in, n_in, device, table=packed.table)
-            distorted = nat.image_program_ragged_u8(packed.data, packed.table, packed.max_pixels, ops_dev, args_dev)
-            plans, ix, wx, iy, wy = nat.augment_plans_ragged(geo_dev, packed.table, out_h, out_w, n_taps)
-            out = nat.image_resize_gather_ragged_u8(distorted, packed.table, out_h, out_w, plans, ix, wx, iy, wy, bg[1])
-        _, lab_out, n_out, mt_out = fetch()
-        inv, dt = np.argsort(cols), arrs[0].dtype
-        return out, [np.ascontiguousarray(lab_out[i, :int(n_out[i])][:, inv]).astype(dt) for i in range(B)], mt_out
+        return cb.patch_device_batch(self, batch, packed, shapes, labels, params, mt)[:3]
 
     def _augment_batch_host(self, batch, packed, shapes, labels, seeds):
         """What `_device_params` does not cover: per image the photometric draws, then RandomPatch, RandomFlip and Resize's own code on
         a lazy image -- under the image's seed when `seeds` is given -- and the pixels of the batch in two launches.  Returns (batch,
         labels, the generator state behind each image (B, 625) | None without seeds)."""
-        programs, lazies, out_labels = [], [], []
-        states = None if seeds is None else np.empty((len(shapes), 625), dtype=np.uint32)
-        for i, ((h, w), lab) in enumerate(zip(shapes, labels)):
-            if seeds is not None:
-                np.random.seed(int(seeds[i]))
-            programs.append(self._draw())
-            img = iop.GeoImage.of(h, w)
-            for transform in (self.random_patch, self.random_flip, self.resize):
-                img, lab = transform(img, lab)
-            lazies.append(img)
-            out_labels.append(lab)
-            if seeds is not None:
-                st = np.random.get_state()
-                states[i, :624], states[i, 624] = st[1], st[2]
-        if packed is None:
-            return iop.gather_batch(iop.run_batch(batch, programs), lazies), out_labels, states
-        return iop.gather_batch_ragged(iop.run_ragged(packed, programs), lazies), out_labels, states
+        geometric = (self.random_patch, self.random_flip, self.resize)
+        return cb.host_batch(batch, packed, shapes, labels, seeds, lambda: (self._draw(), geometric), iop.GeoImage)
 
     def augment_batch(self, images, labels, seeds=None):
         """The chain on a batch: images a list of (H_i, W_i, 3) uint8 NumPy arrays / CUDA tensors of any sizes (they cross PCIe in one
@@ -270,46 +159,4 @@ class DataAugmentationVariableInputSize:
         stream (`ssdhip_var_augment_decide`: one wave per image), the global generator untouched, lists of mixed sizes included;
         `_last_generator_states` (B, 625) holds the state behind each image.  What `_device_params` does not cover runs the host code
         under each seed."""
-        import os
-        import torch
-        if isinstance(images, (list, tuple)):
-            if any(len(im.shape) != 3 or int(im.shape[2]) != 3 for im in images):
-                raise TypeError("augment_batch takes a list of (H, W, 3) uint8 images")
-            if len(labels) != len(images):
-                raise ValueError("one label array per image")
-            batch, packed = None, iop.pack_ragged(list(images))
-            shapes = [(h, w) for h, w, _ in packed.shapes]
-        else:
-            if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3):
-                raise TypeError("augment_batch takes a list of (H, W, 3) uint8 images or a (B, H, W, 3) CUDA uint8 batch")
-            if len(labels) != images.shape[0]:
-                raise ValueError("one label array per image")
-            batch, packed = images, None
-            shapes = [(int(images.shape[1]), int(images.shape[2]))] * int(images.shape[0])
-        B = len(shapes)
-        if seeds is not None and len(seeds) != B:
-            raise ValueError("one seed per image")
-        self._sync_formats()
-        if seeds is not None:
-            params = self._device_params(labels, shapes=shapes) if B else None
-            if params is not None:
-                out, out_labels, mt_out = self._augment_batch_device(batch, packed, shapes, labels, params, _seed_states(seeds))
-            else:
-                saved = np.random.get_state()
-                try:
-                    out, out_labels, mt_out = self._augment_batch_host(batch, packed, shapes, labels, seeds)
-                finally:
-                    np.random.set_state(saved)
-            self.__dict__["_last_generator_states"] = mt_out
-            return out, out_labels
-        if os.environ.get("SSDHIP_AUG_HOST_STREAM", "0") != "1" and B:
-            state = np.random.get_state()
-            params = self._device_params(labels, generator=state[0], shapes=shapes)
-            if params is not None:
-                mt = np.empty((625,), dtype=np.uint32)
-                mt[:624], mt[624] = state[1], state[2]
-                out, out_labels, mt_out = self._augment_batch_device(batch, packed, shapes, labels, params, mt)
-                np.random.set_state((state[0], mt_out[:624], int(mt_out[624]), state[3], state[4]))   # the stream goes on behind the batch
-                return out, out_labels
-        out, out_labels, _ = self._augment_batch_host(batch, packed, shapes, labels, None)
-        return out, out_labels
+        return cb.augment_batch(self, images, labels, seeds)

@@ -316,6 +316,48 @@ def test_augment_batch_with_seeds_equals_the_chain_under_each_seed(geometry):
 
 
 @pytest.mark.gpu
+def test_augment_batch_follows_a_changed_expansion_colour():
+    """The gathers' background rows are cached per (batch size, device, COLOUR): a chain whose expansion colour changes between two batches
+    of one size gathers the new colour -- on the seeded route, and on the ragged route (a list of two sizes on the global stream), which
+    takes its rows from the same cache.  Every image expands (probability 1) and none is cropped, so each result shows its canvas; both
+    calls == the per-image chain, the second with the new colour.  (`RandomPatch` hands its colour to its `CropPad` when it is built, and
+    the per-image chain pads with that copy: the change is made in both places.)"""
+    import torch
+    from ssd_keras_amd.data_generator.data_augmentation_chain_original_ssd import SSDDataAugmentation
+    rng = np.random.RandomState(31)
+    aug = SSDDataAugmentation(img_height=16, img_width=16)
+    aug.expand.expand.prob, aug.random_crop.random_crop.prob = 1.0, 0.0
+    old, new = (123, 117, 104), (7, 200, 33)
+    labels = [np.array([[3, 4, 5, 20, 18], [1, 10, 2, 30, 12]], dtype=np.int64), np.array([[2, 6, 6, 25, 20]], dtype=np.int64)]
+    seeds = [1234, 99]
+
+    def shows(pixels, colour):
+        return bool((np.asarray(pixels) == np.array(colour, dtype=np.uint8)).all(axis=-1).any())
+
+    def both_calls(images, batch_call, seeded):
+        for colour, other in ((old, new), (new, old)):
+            aug.expand.expand.background = aug.expand.expand.sample_patch.background = colour
+            want = []
+            np.random.seed(5)
+            for i, (img, lab) in enumerate(zip(images, labels)):
+                if seeded:
+                    np.random.seed(seeds[i])
+                want.append(aug(img, lab))
+            np.random.seed(5)
+            got_img, got_lab = batch_call()
+            g = got_img.cpu().numpy()
+            for i in range(len(images)):
+                assert np.array_equal(got_lab[i], want[i][1]) and got_lab[i].dtype == labels[i].dtype, (colour, i, got_lab[i], want[i][1])
+                assert np.array_equal(g[i], want[i][0]), "colour %r image %d: %d pixels differ" % (colour, i, int((g[i] != want[i][0]).sum()))
+            assert shows(g, colour) and not shows(g, other), (colour, other)
+
+    uniform = rng.randint(0, 256, size=(2, 24, 32, 3)).astype(np.uint8)
+    both_calls(uniform, lambda: aug.augment_batch(torch.from_numpy(uniform).cuda(), labels, seeds=seeds), seeded=True)
+    ragged = [rng.randint(0, 256, size=(24, 32, 3)).astype(np.uint8), rng.randint(0, 256, size=(20, 28, 3)).astype(np.uint8)]
+    both_calls(ragged, lambda: aug.augment_batch(ragged, labels), seeded=False)
+
+
+@pytest.mark.gpu
 def test_augment_batch_global_stream_on_the_device_equals_the_reference_chain():
     """Round 6: `augment_batch(images, labels)` WITHOUT seeds keeps the reference's contract -- one global np.random
     stream across the batch (object_detection_2d_data_generator.py:1050-1089 -> data_augmentation_chain_original_ssd.py:208-280) -- with

@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from ssd_keras_amd import _native as nat  # noqa: E402
 from ssd_keras_amd.data_generator import _image_ops as iop  # noqa: E402
+from ssd_keras_amd.data_generator import _chain_batch as cb  # noqa: E402
 from ssd_keras_amd.data_generator.data_augmentation_chain_constant_input_size import _seed_states  # noqa: E402
 from ssd_keras_amd.data_generator.data_augmentation_chain_satellite import DataAugmentationSatellite  # noqa: E402
 from tools.time_variable_chain import B, OUT, inputs  # noqa: E402
@@ -36,10 +37,7 @@ def launch_times(chain, images, labels, seeds, turns, reps=30):
     packed = iop.pack_ragged(list(images))
     shapes = [(h, w) for h, w, _ in packed.shapes]
     params = chain._device_params(labels, shapes=shapes)
-    lab_in = np.zeros((B, nat.AUG_MAX_BOXES, 5), dtype=np.float64)
-    n_in = np.array([len(lab) for lab in labels], dtype=np.int32)
-    for i, lab in enumerate(labels):
-        lab_in[i, :len(lab)] = lab
+    _, lab_in, n_in = cb.pack_labels(labels, cb.label_cols(chain.labels_format))
     device = packed.data.device
     bg = nat.to_device(np.zeros((B, 3), dtype=np.uint8), device=device)
     n_taps = chain._n_taps(shapes)
