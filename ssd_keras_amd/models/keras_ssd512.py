@@ -5,6 +5,8 @@ conv10_2 is a 4x4 'valid' convolution on a padded 2x2 map (:303-321); 24564 anch
 """
 from __future__ import annotations
 
+import copy
+
 import numpy as np
 from torch import nn
 
@@ -19,8 +21,10 @@ class SSD512(_VGGBase):
     def __init__(self, image_size, n_classes, mode, l2_regularization, scales, aspect_ratios, n_boxes, steps, offsets,
                  two_boxes_for_ar1, clip_boxes, variances, coords, normalize_coords, subtract_mean, divide_by_stddev,
                  swap_channels, confidence_thresh, iou_threshold, top_k, nms_max_output_size):
+        config = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
         super().__init__(image_size, n_classes, mode, l2_regularization, subtract_mean, divide_by_stddev, swap_channels,
                          confidence_thresh, iou_threshold, top_k, nms_max_output_size, coords, normalize_coords)
+        self._init_config = copy.deepcopy(config)         # the constructor's arguments: models/resample.py rebuilds with another n_classes
         self._build_vgg(self.img_channels)
         self.conv6_1, self.conv6_2 = nn.Conv2d(1024, 256, 1), nn.Conv2d(256, 512, 3, stride=2, padding=1)
         self.conv7_1, self.conv7_2 = nn.Conv2d(512, 128, 1), nn.Conv2d(128, 256, 3, stride=2, padding=1)

@@ -5,6 +5,8 @@ Seven conv + BatchNorm(eps 1e-3, Keras momentum 0.99) + ELU blocks with 2x2 'val
 """
 from __future__ import annotations
 
+import copy
+
 import numpy as np
 import torch
 from torch import nn
@@ -21,8 +23,10 @@ class SSD7(SSDModel):
     def __init__(self, image_size, n_classes, mode, l2_regularization, scales, aspect_ratios, n_boxes, steps, offsets,
                  two_boxes_for_ar1, clip_boxes, variances, coords, normalize_coords, subtract_mean, divide_by_stddev,
                  swap_channels, confidence_thresh, iou_threshold, top_k, nms_max_output_size):
+        config = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
         super().__init__(image_size, n_classes, mode, l2_regularization, subtract_mean, divide_by_stddev, swap_channels,
                          confidence_thresh, iou_threshold, top_k, nms_max_output_size, coords, normalize_coords)
+        self._init_config = copy.deepcopy(config)         # the constructor's arguments: models/resample.py rebuilds with another n_classes
         chans = (self.img_channels,) + self.WIDTHS
         self.convs = nn.ModuleList([nn.Conv2d(chans[i], chans[i + 1], 5 if i == 0 else 3, padding=2 if i == 0 else 1)
                                     for i in range(7)])

@@ -11,14 +11,20 @@ torch's is OIHW; BatchNormalization stores `gamma, beta, moving_mean, moving_var
 (keys "<layer>/<index>": `save_keras_weights_npz`, or `NPZ_CONVERSION` run once next to the Keras file) or the path of a Keras `.h5`
 weight file -- read with h5py where it is installed, otherwise with this package's own reader of the HDF5 subset Keras writes
 (models/hdf5_lite.py, round 6; `save_keras_weights_h5` writes the same container);
-`export_keras_weights(model)` is the inverse (dict).  `by_name` semantics as in Keras: layers missing from the source keep
+`export_keras_weights(model)` is the inverse (dict); `resample_keras_weights(source, destination, ...)` is the loop of the reference's
+weight_sampling_tutorial.ipynb, file to file: the classifier layers cut down or padded up to another set of classes
+(misc_utils/tensor_sampling_utils.py), everything else handed on as found.  `by_name` semantics as in Keras: layers missing from the source keep
 their initialisation, layers whose shapes do not match raise ValueError.
 """
 from __future__ import annotations
 
+import os
+import re
+
 import numpy as np
 import torch
 
+from ..misc_utils.tensor_sampling_utils import sample_tensors
 from . import hdf5_lite
 from .keras_ssd7 import SSD7
 
@@ -28,8 +34,13 @@ except ImportError:
     h5py = None
 
 
+def _axes(a, order):
+    """Reorder the axes of an array -- or of a tensor, on its device (models/resample.py runs the converters on the live parameters)."""
+    return a.permute(*order) if torch.is_tensor(a) else np.transpose(a, order)
+
+
 def _conv(c):
-    items = [(c.weight, lambda a: np.transpose(a, (3, 2, 0, 1)), lambda t: np.transpose(t, (2, 3, 1, 0)))]
+    items = [(c.weight, lambda a: _axes(a, (3, 2, 0, 1)), lambda t: _axes(t, (2, 3, 1, 0)))]
     if c.bias is not None:
         items.append((c.bias, lambda a: a, lambda t: t))
     return items
@@ -119,21 +130,40 @@ np.savez(sys.argv[2], **out)
 """
 
 
-def save_keras_weights_h5(source, path, backend="tensorflow", keras_version="2.2.4"):
+def save_keras_weights_h5(source, path, backend="tensorflow", keras_version="2.2.4", layer_names=None, weight_names=None, dtype=np.float32):
     """Write a `{layer_name: [arrays in Keras order]}` dict (or a model: its export_keras_weights) as a Keras weight FILE -- the layout
     `model.save_weights(path)` produces (keras/engine/saving.py save_weights_to_hdf5_group): root attributes `layer_names`, `backend`,
     `keras_version`; one group per layer with the attribute `weight_names` = ["<layer>/kernel:0", "<layer>/bias:0", ...] and the arrays
     as datasets under those paths -- through this package's HDF5 writer (models/hdf5_lite.py; no h5py).  Weight names follow Keras 2:
-    Conv2D kernel / bias, BatchNormalization gamma / beta / moving_mean / moving_variance, L2Normalization gamma."""
+    Conv2D kernel / bias, BatchNormalization gamma / beta / moving_mean / moving_variance, L2Normalization gamma.
+    What `resample_keras_weights` needs to hand a file on as it found it (each None / default = as before): `layer_names`, the root
+    attribute in full -- a layer named there without arrays in `source` (Keras lists its weightless layers too) gets its group with an
+    empty `weight_names`; `weight_names` = {layer: [names as in the source file]} instead of the Keras 2 names above; `dtype=None`
+    writes every array in its own dtype instead of float32."""
     weights = source if isinstance(source, dict) else export_keras_weights(source)
     conv, bn = ("kernel:0", "bias:0"), ("gamma:0", "beta:0", "moving_mean:0", "moving_variance:0")
+    order = list(weights) if layer_names is None else list(layer_names)
+    if set(weights) - set(order):
+        raise ValueError("layers missing from `layer_names`: {}".format(sorted(set(weights) - set(order))))
     groups = {}
-    for name, arrays in weights.items():
-        labels = bn if len(arrays) == 4 else (("gamma:0",) if (len(arrays) == 1 and np.asarray(arrays[0]).ndim == 1) else conv[:len(arrays)])
-        names = ["%s/%s" % (name, lab) for lab in labels]
-        groups[name] = {"attrs": {"weight_names": np.array([n.encode("utf-8") for n in names])},
-                        "groups": {name: {"datasets": {lab: np.asarray(a, dtype=np.float32) for lab, a in zip(labels, arrays)}}}}
-    root = {"attrs": {"layer_names": np.array([n.encode("utf-8") for n in weights]), "backend": np.bytes_(backend.encode("utf-8")),
+    for name in order:
+        arrays = weights.get(name, [])
+        if weight_names is not None and name in weight_names:
+            names = list(weight_names[name])
+            if len(names) != len(arrays):
+                raise ValueError("layer '{}': {} weight names for {} arrays".format(name, len(names), len(arrays)))
+        else:
+            labels = bn if len(arrays) == 4 else (("gamma:0",) if (len(arrays) == 1 and np.asarray(arrays[0]).ndim == 1) else conv[:len(arrays)])
+            names = ["%s/%s" % (name, lab) for lab in labels]
+        node = {"attrs": {"weight_names": np.array([n.encode("utf-8") for n in names]) if names else np.zeros((0,), "S1")}}
+        for wname, a in zip(names, arrays):
+            *parents, leaf = wname.split("/")
+            at = node
+            for part in parents:
+                at = at.setdefault("groups", {}).setdefault(part, {})
+            at.setdefault("datasets", {})[leaf] = np.asarray(a, dtype=dtype)
+        groups[name] = node
+    root = {"attrs": {"layer_names": np.array([n.encode("utf-8") for n in order]), "backend": np.bytes_(backend.encode("utf-8")),
                       "keras_version": np.bytes_(keras_version.encode("utf-8"))},
             "groups": groups}
     hdf5_lite.write(path, root)
@@ -155,6 +185,77 @@ def _read_npz(path):
                 raise ValueError("'{}': keys of a weight .npz read '<layer name>/<index>', got '{}'".format(path, key))
             out.setdefault(name, {})[int(idx)] = z[key]
     return {name: [parts[i] for i in range(len(parts))] for name, parts in out.items()}
+
+
+def _read_h5_attrs(path):
+    """What a Keras weight file says about itself beside the arrays `_read_h5` returns: (every name in `layer_names` -- the weightless
+    layers too --, {layer: weight_names}, backend or None, keras_version or None); of a `model.save()` file, its `model_weights` group's."""
+    f = hdf5_lite.File(path)
+    g = f["model_weights"] if "model_weights" in f else f.root
+    layer_names = _chunked_attr(g.attrs, "layer_names")
+    weight_names = {name: _chunked_attr(g[name].attrs, "weight_names") for name in layer_names}
+    one = lambda key: _strings(g.attrs[key])[0] if key in g.attrs and g.attrs[key] is not None else None
+    return layer_names, weight_names, one("backend"), one("keras_version")
+
+
+_CLASSIFIER = re.compile(r".*_mbox_conf|classes\d")              # SSD300 / SSD512: <source>_mbox_conf; SSD7: classes4 .. classes7
+
+
+def resample_keras_weights(source, destination, n_classes_source, classes_of_interest, classifier_names=None, init=('gaussian', 'zeros'),
+                           mean=0.0, stddev=0.005):
+    """The loop of the reference's weight_sampling_tutorial.ipynb as one call: copy the weight file `source` to `destination` with
+    every classifier layer cut down (or padded up) from `n_classes_source` classes -- background included, 81 for the COCO models --
+    to `classes_of_interest`, so that a model built for the new number of classes loads it (`load_keras_weights`) and fine-tunes
+    from trained weights.
+
+    source: a Keras .h5 weight file, a `model.save()` file (its `model_weights` group is read) or an .npz container.
+    destination: a weight file written by `save_keras_weights_h5`, or by `save_keras_weights_npz` for a name ending in .npz; must not
+        be `source`.  Model config and optimizer weights of a `model.save()` source are NOT carried over: the result is a weights
+        file, loaded with `load_keras_weights` / Keras' `load_weights`.
+    classes_of_interest: a list of source class indices in the order the new model numbers them (0, the background, first, as in the
+        tutorial) -- of a classifier with `out = n_boxes * n_classes_source` channels the channels
+        `[c + i * n_classes_source for i in range(n_boxes) for c in classes]` are kept; or an int, the new number of classes
+        (background included): `int(classes * out / n_classes_source)` channels are sub-sampled at random (channel 0 always kept) or
+        the old ones spread over that many, the gaps filled per `init` (kernel, bias) / `mean` / `stddev` -- both through
+        `sample_tensors([kernel, bias], [kh, kw, in, .], axes=[[3]], ...)`, consuming the global `np.random` stream as it does.
+    classifier_names: the layers to resample; None = every layer named `*_mbox_conf` or `classes<digit>`, in the file's order.
+    Kernel and bias are written in the source arrays' dtype (an up-sampled float64 result is rounded once); every other array, the
+    layer and weight names, `backend` and `keras_version` pass through untouched.  Returns {layer: (old out channels, new)}."""
+    if os.path.abspath(source) == os.path.abspath(destination) or (os.path.exists(destination) and os.path.samefile(source, destination)):
+        raise ValueError("`destination` is `source`: write the resampled weights to a new file")
+    if source.endswith(".npz"):
+        weights = _read_npz(source)
+        layer_names, weight_names, backend, keras_version = list(weights), None, None, None
+    else:
+        weights = _read_h5(source)
+        layer_names, weight_names, backend, keras_version = _read_h5_attrs(source)
+    if classifier_names is None:
+        classifier_names = [name for name in layer_names if name in weights and _CLASSIFIER.fullmatch(name)]
+        if not classifier_names:
+            raise ValueError("'{}' has no layer named '*_mbox_conf' or 'classes<digit>': name the classifiers".format(source))
+    changed, out = {}, dict(weights)
+    for name in classifier_names:
+        if name not in weights:
+            raise ValueError("'{}' has no weighted layer '{}'".format(source, name))
+        if len(weights[name]) != 2 or np.ndim(weights[name][0]) != 4 or np.ndim(weights[name][1]) != 1:
+            raise ValueError("layer '{}' is no Conv2D with a (kh, kw, in, out) kernel and an (out,) bias".format(name))
+        kernel, bias = weights[name]
+        kh, kw, cin, cout = kernel.shape
+        if cout % n_classes_source:
+            raise ValueError("layer '{}' has {} output channels, no multiple of {} source classes".format(name, cout, n_classes_source))
+        if isinstance(classes_of_interest, int):
+            last = int(classes_of_interest * cout / n_classes_source)
+        else:
+            last = [c + i * n_classes_source for i in range(cout // n_classes_source) for c in classes_of_interest]
+        new = sample_tensors([kernel, bias], [kh, kw, cin, last], axes=[[3]], init=init, mean=mean, stddev=stddev)
+        out[name] = [np.asarray(n, dtype=o.dtype) for n, o in zip(new, (kernel, bias))]
+        changed[name] = (cout, out[name][0].shape[3])
+    if destination.endswith(".npz"):
+        save_keras_weights_npz(out, destination)
+    else:
+        save_keras_weights_h5(out, destination, layer_names=layer_names, weight_names=weight_names, dtype=None,
+                              **{k: v for k, v in (("backend", backend), ("keras_version", keras_version)) if v is not None})
+    return changed
 
 
 def load_keras_weights(model, source, by_name=True, strict_shapes=True):
