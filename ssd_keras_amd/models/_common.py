@@ -30,7 +30,6 @@ from ._train_fns import (_AssembleTrainFn, _ConvBiasActFn, _ConvBiasActPoolFn, _
                          _conv_input_weight_grads)
 
 
-
 def conv_out(n, k, s=1, p=0, d=1):
     return (n + 2 * p - d * (k - 1) - 1) // s + 1
 
@@ -201,6 +200,8 @@ class SSDModel(PredictorHeads, nn.Module):
     def conv_act(self, conv, x, relu=True, link_in=None, link_out=None):
         """Conv2D(activation='relu' | None).  link_in / link_out (_ReluLink, training step only; see `relu_link`): x is the ReLU output of a
         layer that feeds nothing but this one / this layer's output feeds exactly one layer, which holds the same link as its link_in."""
+        if link_out is not None and not relu:
+            raise ValueError("link_out on a layer without ReLU: its consumer would mask the data gradient by an activation that has no threshold")
         if self._fused(x, conv):
             g = sel.geometry_of(conv, x)
             if sel.first_layer(g):
@@ -231,7 +232,6 @@ class SSDModel(PredictorHeads, nn.Module):
     def _fused_train(self, x, conv):
         return (self.fused_training and x.is_cuda and torch.is_grad_enabled() and conv.bias is not None and conv.groups == 1
                 and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)))
-
 
     def _bf16_shadow(self, conv, with_transposed=False):
         """bf16 copies of a convolution's float32 master weight (channels_last) and bias for the libssdhip kernels [+ the transposed,
@@ -284,11 +284,10 @@ class SSDModel(PredictorHeads, nn.Module):
 
     @staticmethod
     def relu_link():
-        """A link between two consecutive ReLU convolutions of the training step (the lower one's output feeds ONLY the upper one):
-        pass it as `link_out` of the lower layer's conv_act and `link_in` of the upper layer's conv_act / conv_act_pool.  None outside
-        autograd -- the inference paths take no links."""
+        """A link between two consecutive ReLU convolutions of the training step (the lower one's output feeds ONLY the upper one): pass it
+        as `link_out` of the lower layer's conv_act and `link_in` of the upper layer's conv_act / conv_act_pool.  None outside autograd -- the
+        inference paths take no links.  Gradients observed at a linked intermediate activation (hooks, `retain_grad`) are already masked by the layer below."""
         return _ReluLink() if torch.is_grad_enabled() else None
-
 
     def conv_act_pool(self, conv, x, kernel, stride, pad=0, ceil_mode=False, link_in=None):
         if self._fused(x, conv):
@@ -299,8 +298,7 @@ class SSDModel(PredictorHeads, nn.Module):
             name = (self._pick(("pool", tuple(x.shape), conv.out_channels, conv.kernel_size[0], conv.dilation[0], kernel, stride, pad),
                                cands) if len(cands) > 1 else "miopen")
             return cands[name]()
-        if (kernel == 2 and stride == 2 and pad == 0 and ceil_mode and self._fused_train(x, conv) and conv.out_channels % 8 == 0
-                and 256 % (conv.out_channels // 8) == 0 and not sel.on("NO_FUSED_POOL_BWD")):
+        if kernel == 2 and stride == 2 and pad == 0 and ceil_mode and self._fused_train(x, conv) and sel.pool_bwd_fused(sel.geometry_of(conv, x)):
             run, _name = self._train_thunk(conv, x, True)
             if run is not None:
                 wb, bb, wt = self._bf16_shadow(conv, with_transposed=True)
@@ -311,12 +309,8 @@ class SSDModel(PredictorHeads, nn.Module):
         """conv1_1 -> conv1_2 -> MaxPooling2D(2, 2, 'same') (models/keras_ssd300.py:274-276).  On the fused bf16 inference path the
         three can run as ONE kernel that never writes the 64-channel full-resolution map (csrc/ssdhip_conv64.hip, FRONT); timed once
         per shape against the two-kernel form."""
-        same3 = lambda c: (c.kernel_size == (3, 3) and c.stride == (1, 1) and c.padding == (1, 1) and c.dilation == (1, 1)
-                           and c.groups == 1 and c.bias is not None)
-        if (not sel.on("NO_CONV1_BLOCK") and sel.switch("CONV") in ("auto", "auto_miopen")
-                and self._fused(x, c1) and self._fused(x, c2) and same3(c1) and same3(c2)
-                and c1.in_channels == 3 and c1.out_channels == 64
-                and c2.in_channels == 64 and c2.out_channels % 64 == 0):
+        if (sel.switch("CONV") in ("auto", "auto_miopen") and self._fused(x, c1) and self._fused(x, c2)
+                and sel.conv1_block(sel.geometry_of(c1), sel.geometry_of(c2))):
             cands = {"separate": lambda: self.conv_act_pool(c2, self.conv_act(c1, x), 2, 2, ceil_mode=True),
                      "conv1_block": lambda: nat.conv1_block(x, c1.weight, c1.bias, c2.weight, c2.bias, relu=True, pool=True)}
             key = ("conv1_block", tuple(x.shape), c2.out_channels)

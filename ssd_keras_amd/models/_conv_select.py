@@ -1,10 +1,11 @@
-"""Which libssdhip kernels can run a convolution layer: ONE description for the inference path, its pooled form, the training step's
-forward and the data gradient (`SSDModel.conv_act` / `conv_act_pool` / `_train_thunk`, `_train_fns._conv_input_weight_grads`).
+"""Which libssdhip kernels can run a convolution layer: ONE description for the inference path, its pooled form and both halves of the
+training step (`SSDModel.conv_act` / `conv_act_pool` / `conv1_block_pool` / `_train_thunk`, the autograd nodes of `_train_fns`).
 
 A layer is a `Geometry` (plain ints), the kernels' limits are predicates of it, and `candidates` lists, in the order the autotune
 (`SSDModel._pick`) times them, every form offered to a context as `name -> (x, w, b) -> y`.  What differs between the contexts is data
-in that list ("igemm5 and splitk: inference only"), not a second copy of it.  `switch` / `on` read the SSDHIP_* environment switches of
-the models package (DESIGN.md lists them); they read os.environ at call time, nothing is cached.
+in that list ("igemm5 and splitk: inference only"), not a second copy of it.  The backward pass times nothing: `dgrad` and `WGRAD_FORMS`
+name its kernels in the order tried, the predicates below them say where the step's fused forms apply, and `_train_fns` maps the names to
+`_native` calls.  `switch` / `on` read the SSDHIP_* switches of the models package from os.environ at call time: no cache.
 """
 import os
 from collections import namedtuple
@@ -135,9 +136,8 @@ def image2(g):
 
 
 def own_dgrad(g):
-    """The data gradient of this layer runs on libssdhip's forward kernels with transposed / flipped filters (see
-    _conv_input_weight_grads): k in (1, 3), channel counts multiples of 64; stride 1 and 'same', or (round 6) a strided / 'valid'
-    3 x 3 layer behind an embedding launch."""
+    """The data gradient of this layer runs on libssdhip's forward kernels with transposed / flipped filters (see `dgrad`): k in (1, 3),
+    channel counts multiples of 64; stride 1 and 'same', or (round 6) a strided / 'valid' 3 x 3 layer behind an embedding launch."""
     return g is not None and g.groups == 1 and (dgrad_same(g) or dgrad_embedded(g))
 
 
@@ -249,3 +249,57 @@ def pooled_candidates(g, kernel, stride, pad, ceil_mode):
 def act_key(g, relu):
     """The autotune key of a plain layer (bench.py formats it positionally)."""
     return ("act", (g.batch, g.cin, g.h, g.w), g.cout, g.k, g.dilation, relu, g.stride, g.padding)
+
+
+# -- the training step's backward and its fused forms (no timing run: the first form that takes the layer) ---------------------------------
+def _same3(g):
+    return g is not None and g.k == 3 and (g.stride, g.padding, g.dilation) == (1, 1, 1) and g.cin % 64 == 0 and g.cout % 64 == 0
+
+
+# csrc/ssdhip_wgrad.hip: (name, the geometry's limit, on the device only, switches that turn it off) in the order tried
+WGRAD_FORMS = (
+    ("grid", _same3, False, ("NO_OWN_WGRAD",)),                                              # the padded position grid: 3 x 3 'same'
+    ("pixels", lambda g: g.k == 1 and (g.stride, g.padding) == (1, 0) and g.cin % 128 == 0 and g.cout % 128 == 0, True, ("NO_OWN_WGRAD",)),
+    # any other 3 x 3 as a tap-gathered pixel GEMM: fc6's dilation, the strided and the 'valid' extras
+    ("taps", lambda g: g.k == 3 and g.cin % 128 == 0 and g.cout % 128 == 0, True, ("NO_OWN_WGRAD", "NO_TAPS_BWD")),
+)
+
+
+def wgrad_forms(g, cuda):
+    """The weight-gradient kernels to try, by name: one that declines (None) hands the layer on, at last to the framework."""
+    return tuple(name for name, limit, device, off in WGRAD_FORMS if g is not None and limit(g) and (cuda or not device) and not any(map(on, off)))
+
+
+def dgrad(g, cuda, linked):
+    """The layer's data gradient on the forward kernels as (form, launch of the most specific form offered, masked); all None: the framework's.
+    form: "same", or "embedded" behind csrc/ssdhip_train.hip's embedding launch (device only; off with the tap-gathered kernels).  masked: the
+    slab kernel runs a 'same' layer whose input is linked (`_ReluLink`): its MSK epilogue masks dL/dx by x > 0 ("mask") and sums its channels ("sums")."""
+    if not own_dgrad(g) or on("NO_OWN_DGRAD") or not (dgrad_same(g) or (cuda and not on("NO_TAPS_BWD"))):
+        return None, None, None
+    forms = candidates(dgrad_geometry(g), False, DGRAD)
+    name = next(n for n in DGRAD_PRIORITY if n in forms)
+    masked = linked and name == "halo" and dgrad_same(g) and not on("NO_MASKED_DGRAD")
+    return ("same" if dgrad_same(g) else "embedded"), forms[name], ("mask" if on("NO_MASKED_SUMS") else "sums") if masked else None
+
+
+def pool_keep(g, cuda):
+    """Conv2D(relu) -> MaxPooling2D(2, 2, 'same') of the step as ONE launch that writes the activation AND the pooled map (KEEP): "c64"
+    (csrc/ssdhip_conv64.hip: conv1_2 -> pool1), "halo" (csrc/ssdhip_convh.hip: conv2_2 -> pool2, conv3_3 -> pool3) or None."""
+    if not (cuda and _same3(g)) or on("NO_POOL_KEEP"):
+        return None
+    return "c64" if c64(g) else "halo" if halo(g) and not on("NO_HALO_POOL_KEEP") else None
+
+
+def first_layer_bwd(g, relu, need_x, cuda):
+    """csrc/ssdhip_train.hip, conv1_1_bwd_kernel: ReLU mask, bias and weight gradient of the first layer, which has no data gradient, in ONE pass."""
+    return bool(relu and not need_x and cuda and first_layer(g) and not on("NO_CONV1_1_BWD"))
+
+
+def pool_bwd_fused(g):
+    """csrc/ssdhip_train.hip, maxpool2_relu_bwd_bias_kernel: 8 channels to a lane, whole pixels to a workgroup of 256 lanes."""
+    return g is not None and g.cout % 8 == 0 and 256 % (g.cout // 8) == 0 and not on("NO_FUSED_POOL_BWD")
+
+
+def conv1_block(g1, g2):
+    """csrc/ssdhip_conv64.hip, FRONT: the first layer and the 3 x 3 'same' layer of 64 input channels behind it (conv1_1 -> conv1_2)."""
+    return first_layer(g1) and _same3(g2) and c64(g2) and g2.groups == 1 and bool(g2.bias) and not on("NO_CONV1_BLOCK")

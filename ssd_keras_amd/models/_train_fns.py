@@ -2,7 +2,8 @@
 kernels of the inference path): one node per convolution layer [+ pooling], per pair of predictor heads, for the prediction assembly,
 for a max-pool, for what follows a convolution in a block of SSD7 (batch-statistics BatchNorm + ELU [+ pool],
 csrc/ssdhip_bntrain.hip), for that convolution itself (csrc/ssdhip_convbn.hip, ssdhip_wgrad7.hip) and for the pair of predictor heads
-of one of SSD7's source maps (csrc/ssdhip_heads7.hip).  `SSDModel` (models/_common.py) applies them; which forward kernel a layer runs is `_conv_select`'s choice."""
+of one of SSD7's source maps (csrc/ssdhip_heads7.hip).  `SSDModel` (models/_common.py) applies them; which kernel runs a layer's forward [+ pool]
+and its gradients is `_conv_select`'s choice: the convolution nodes here only map the names it returns to `_native` calls."""
 import torch
 
 from .. import _native as nat
@@ -22,20 +23,42 @@ class _ReluLink:
         self.partial = None      # the masked gradient's channel sums by workgroup ([rows, C] float32): the lower layer's bias-gradient partials
 
 
+# -- what the two convolution nodes share; their ctx.conf is (stride, padding, dilation, ..., dtype of weight, of bias | None, of x) --------
+def _bf16_operands(x, weight, bias, wb, bb):
+    """Forward prologue: x as a bf16 NHWC map; the shadow set's bf16 filters and bias (wb, bb), cast here where there is none at hand."""
+    xb = x.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    if wb is None:
+        wb = weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        bb = bias.detach().to(torch.bfloat16) if bias is not None else None
+    return xb, wb, bb
+
+
+def _node_result(ctx, gx, gw, gb):
+    """The gradients in the dtypes of x, weight and bias (needs_input_grad[2] is False where bias is None), None for the forward's other arguments."""
+    wdt, bdt, xdt = ctx.conf[-3:]
+    grads = (gx.to(xdt) if gx is not None else None), gw.to(wdt), (gb.to(bdt) if ctx.needs_input_grad[2] else None)
+    return grads + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
+def _node_backward(ctx, gy, partial, link_in):
+    """Backward epilogue, from the masked dL/dy and the per-workgroup partials of its channel sums (or None), which make the bias gradient."""
+    xb, wb, _y, wt = ctx.saved_tensors
+    want_gb = ctx.needs_input_grad[2]
+    gx, gw, gb = _conv_input_weight_grads(gy, xb, wb, *ctx.conf[:3], ctx.needs_input_grad[0], wt, partial if want_gb else None, link_in)
+    if want_gb and gb is None:
+        gb = nat.row_sums(partial) if partial is not None else gy.sum(dim=(0, 2, 3), dtype=torch.float32)
+    return _node_result(ctx, gx, gw, gb)
+
 
 class _ConvBiasActFn(torch.autograd.Function):
     """A convolution layer of the TRAINING step with libssdhip's MFMA kernel in the forward pass (convolution + bias + ReLU, one
     kernel, bf16 NHWC -- the same kernels the inference path runs) and libssdhip's data / weight gradients behind it
-    (`_conv_input_weight_grads`: since round 6 every layer of SSD300 / SSD512 except a 4 x 4 or grouped convolution; the framework's
-    convolution_backward is the fallback for what the kernels do not cover).  `run` is the libssdhip thunk picked for this layer
-    shape: (x_bf16, w_bf16, b_bf16) -> y."""
+    (`_conv_input_weight_grads`: since round 6 every layer of SSD300 / SSD512 except a 4 x 4 or grouped convolution, which fall to the
+    framework's convolution_backward).  `run` is the libssdhip thunk picked for this layer shape: (x_bf16, w_bf16, b_bf16) -> y."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, run, stride, padding, dilation, relu, wb=None, bb=None, wt=None, link_in=None, link_out=None):
-        xb = x.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        if wb is None:                                   # no bf16 shadow of the parameters at hand: cast here
-            wb = weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-            bb = bias.detach().to(torch.bfloat16) if bias is not None else None
+        xb, wb, bb = _bf16_operands(x, weight, bias, wb, bb)
         y = run(xb, wb, bb)
         # (wt: the data gradient's filters, built with the shadows -- None: built in backward; saved like the others so that autograd's
         #  version check covers it when the shadows are refreshed between this forward and its backward)
@@ -47,165 +70,94 @@ class _ConvBiasActFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        xb, wb, y, wt = ctx.saved_tensors
-        stride, padding, dilation, relu, wdt, bdt, xdt = ctx.conf
+        xb, wb, y, _wt = ctx.saved_tensors
+        relu = ctx.conf[3]
         gy = gy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        want_gb = bdt is not None and ctx.needs_input_grad[2]
-        partial = None
-        if (relu and not ctx.needs_input_grad[0] and gy.is_cuda and tuple(wb.shape) == (64, 3, 3, 3) and stride == (1, 1)
-                and padding == (1, 1) and dilation == (1, 1) and not sel.on("NO_CONV1_1_BWD")):
-            # the first layer: no data gradient, so the masked gradient is only ever summed -- ReLU mask, bias gradient and weight gradient
-            # in ONE pass that writes nothing but partial sums (csrc/ssdhip_train.hip, conv1_1_bwd_kernel)
-            gw, gb = nat.conv1_1_backward(gy, y, xb)
-            return None, gw.to(wdt), (gb.to(bdt) if want_gb else None), None, None, None, None, None, None, None, None, None, None
+        if sel.first_layer_bwd(sel.geometry_of_grads(wb, xb, *ctx.conf[:3]), relu, ctx.needs_input_grad[0], gy.is_cuda):
+            return _node_result(ctx, None, *nat.conv1_1_backward(gy, y, xb))
         link_in, link_out = ctx.links
-        if relu:
-            premasked = link_out is not None and link_out.masked
-            if link_out is not None:
-                partial, link_out.partial = link_out.partial, None
-                link_out.masked = False                  # consumed: the consumer's next backward sets it again
-            fused = None
-            if premasked:
-                # dL/dy arrived masked by y > 0 from the consumer's data-gradient kernel (_ReluLink), its channel sums beside it
-                if want_gb and partial is None:
-                    partial = nat.channel_sums_partial(gy)
-            else:
-                # ReLU mask and the per-workgroup channel sums of the bias gradient in ONE libssdhip pass (csrc/ssdhip_train.hip); the rows
-                # are added by the weight gradient's reduction launch where that is ours, by one framework reduction otherwise
-                fused = nat.relu_bwd_bias(gy, y, reduce=False)
-                if fused is not None:
-                    gy, partial = fused
-                else:
-                    gy = torch.ops.aten.threshold_backward(gy, y, 0)
-        gx, gw, gb = _conv_input_weight_grads(gy, xb, wb, stride, padding, dilation, ctx.needs_input_grad[0], wt,
-                                              partial if want_gb else None, link_in)
-        if want_gb:
-            if gb is None:
-                gb = nat.row_sums(partial) if partial is not None else gy.sum(dim=(0, 2, 3), dtype=torch.float32)
-            gb = gb.to(bdt)
-        else:
-            gb = None
-        return (gx.to(xdt) if gx is not None else None), gw.to(wdt), gb, None, None, None, None, None, None, None, None, None, None
+        premasked, partial = False, None
+        if relu and link_out is not None:                # consumed here: the consumer's next backward sets them again
+            premasked, partial = link_out.masked, link_out.partial
+            link_out.masked, link_out.partial = False, None
+        if premasked:
+            # dL/dy arrived masked by y > 0 from the consumer's data-gradient kernel (_ReluLink), its channel sums beside it
+            if partial is None and ctx.needs_input_grad[2]:
+                partial = nat.channel_sums_partial(gy)
+        elif relu:
+            # ReLU mask and the per-workgroup channel sums of the bias gradient in ONE libssdhip pass (csrc/ssdhip_train.hip)
+            fused = nat.relu_bwd_bias(gy, y, reduce=False)
+            gy, partial = fused if fused is not None else (torch.ops.aten.threshold_backward(gy, y, 0), partial)
+        return _node_backward(ctx, gy, partial, link_in)
 
 
-def _weight_grad(got, bias_partial):
-    """(dL/dw, dL/db) from what a weight-gradient entry returned: None (geometry not covered), dw, or (dw, db) when it was handed the
-    bias partials."""
-    return got if (got is not None and bias_partial is not None) else (got, None)
+# `_conv_select.WGRAD_FORMS` as launches: None (the kernel declines), dw, or (dw, db) when the bias partials ride in its reduction launch
+_WGRAD_LAUNCH = {
+    "grid": lambda g, xb, gy, partial: nat.conv3x3_wgrad(xb, gy, bias_partial=partial),
+    "pixels": lambda g, xb, gy, partial: nat.conv1x1_wgrad(xb, gy, bias_partial=partial),
+    "taps": lambda g, xb, gy, partial: nat.conv3x3_taps_wgrad(xb, gy, g.stride, g.padding, g.dilation, bias_partial=partial),
+}
 
 
 def _conv_input_weight_grads(gy, xb, wb, stride, padding, dilation, need_x, wt=None, bias_partial=None, link_in=None):
-    """dL/dx, dL/dw [and dL/db] of a convolution from the (masked) dL/dy.  Data gradient: a stride-1 'same' layer through the forward's
-    MFMA kernels on the transposed, tap-flipped filters -- the most specific form `_conv_select` offers that layer; a strided or 'valid'
-    3 x 3 layer the same way behind an embedding launch (round 6).  Weight gradient: the position-grid kernel (3 x 3 'same', incl.
-    fc6's dilation 6), the pixel GEMM (1 x 1), the tap-gathered pixel GEMM (any other 3 x 3) -- csrc/ssdhip_wgrad.hip.  What none of
-    them covers goes to aten.convolution_backward (MIOpen).
+    """dL/dx, dL/dw [and dL/db] of a convolution from the (masked) dL/dy, on the kernels `_conv_select` names (`dgrad`, `wgrad_forms`).
+    Data gradient: a stride-1 'same' layer through the forward's MFMA kernels on the transposed, tap-flipped filters; a strided or
+    'valid' 3 x 3 layer the same way behind an embedding launch (round 6).  What no kernel covers (3 input channels, predictor heads
+    whose channel counts are not multiples of 64) goes to aten.convolution_backward (MIOpen).
     bias_partial: per-workgroup channel sums of gy ([rows, Cout] float32); the third result is their ordered sum when the weight
-    gradient's reduction launch could add them on the side, None otherwise (the caller reduces them itself).
-    link_in (_ReluLink): xb is the ReLU output of a layer that feeds nothing else -- where the slab kernel runs the data gradient it
-    writes dL/dx masked by xb > 0 and sets the link (the layer below then skips its own mask pass)."""
+    gradient's reduction launch could add them on the side, None otherwise (the caller reduces them itself).  link_in (_ReluLink) is
+    set where the slab kernel wrote dL/dx masked by xb > 0 (the layer below then skips its own mask pass)."""
     gx = None
     g = sel.geometry_of_grads(wb, xb, stride, padding, dilation)
-    own_taps = not sel.on("NO_TAPS_BWD")
-    own_dgrad = g is not None and need_x and not sel.on("NO_OWN_DGRAD")
-    same = own_dgrad and sel.dgrad_same(g)
-    embedded = own_dgrad and sel.dgrad_embedded(g) and own_taps and gy.is_cuda
-    if embedded:
-        gy_full, gy = gy, nat.embed_strided(gy, xb.shape[2], xb.shape[3], stride[0], 1 - padding[0])
-    if same or embedded:
+    form, run, masked = sel.dgrad(g, gy.is_cuda, link_in is not None and gy.dtype == xb.dtype == torch.bfloat16) if need_x else (None,) * 3
+    if form:
+        gz = gy if form == "same" else nat.embed_strided(gy, xb.shape[2], xb.shape[3], stride[0], 1 - padding[0])
         if wt is None:                                   # (the shadow set hands the transposed filters over: csrc/ssdhip_optim.hip)
             wt = wb.flip(2, 3).permute(1, 0, 2, 3).contiguous(memory_format=torch.channels_last)
-        # small maps (conv5_x, fc6 with its dilation; round 6: the 1 x 1 fc7, conv6_1) through the image-resident kernel where it fills
-        # the chip, the deep 3x3 layers through the slab kernel, a 64-channel dL/dy (conv1_2) through the resident-filter kernel
-        forms = sel.candidates(sel.dgrad_geometry(g), False, sel.DGRAD)
-        name = next(n for n in sel.DGRAD_PRIORITY if n in forms)
-        masked = None
-        if (link_in is not None and name == "halo" and same and gy.dtype == torch.bfloat16 and xb.dtype == torch.bfloat16
-                and not sel.on("NO_MASKED_DGRAD")):
-            masked = nat.conv3x3_halo_masked(gy, wt, xb, sums=not sel.on("NO_MASKED_SUMS"))
-        if masked is not None:
-            gx, link_in.partial = masked if isinstance(masked, tuple) else (masked, None)
+        got = nat.conv3x3_halo_masked(gz, wt, xb, sums=masked == "sums") if masked else None
+        if got is not None:
+            gx, link_in.partial = got if isinstance(got, tuple) else (got, None)
             link_in.masked = True
         else:
-            gx = forms[name](gy, wt, None)
-    if embedded:
-        gy = gy_full
-    gw, gb = None, None
-    if g is not None and not sel.on("NO_OWN_WGRAD"):
-        # libssdhip's MFMA weight gradients (csrc/ssdhip_wgrad.hip; float32, fixed summation order; the bias partials ride in their
-        # reduction launch); None: geometry not covered (3 input channels, predictor heads whose channel counts are not multiples of 64)
-        by_64, by_128 = (g.cin % 64 == 0 and g.cout % 64 == 0), (g.cin % 128 == 0 and g.cout % 128 == 0)
-        if g.k == 3 and (g.stride, g.padding, g.dilation) == (1, 1, 1) and by_64:
-            gw, gb = _weight_grad(nat.conv3x3_wgrad(xb, gy, bias_partial=bias_partial), bias_partial)
-        if gw is None and g.k == 1 and (g.stride, g.padding) == (1, 0) and gy.is_cuda and by_128:
-            # the 1 x 1 layers (fc7, conv6_1 ... conv9_1): the weight gradient is a GEMM over the pixels (conv1x1_wgrad_kernel)
-            gw, gb = _weight_grad(nat.conv1x1_wgrad(xb, gy, bias_partial=bias_partial), bias_partial)
-        if gw is None and g.k == 3 and own_taps and gy.is_cuda and by_128:
-            # (round 6) the other 3 x 3 layers -- fc6's dilation, the strided and the 'valid' extras -- through the tap-gathered pixel
-            # GEMM (conv_taps_wgrad_kernel): with it the training step holds no framework convolution
-            gw, gb = _weight_grad(nat.conv3x3_taps_wgrad(xb, gy, g.stride, g.padding, g.dilation, bias_partial=bias_partial), bias_partial)
+            gx = run(gz, wt, None)
+    launches = (_WGRAD_LAUNCH[name](g, xb, gy, bias_partial) for name in sel.wgrad_forms(g, gy.is_cuda))
+    gw = next((got for got in launches if got is not None), None)          # the first form that does not decline
+    gw, gb = gw if (gw is not None and bias_partial is not None) else (gw, None)
     masks = [need_x and gx is None, gw is None, False]
     if masks[0] or masks[1]:
         gx_m, gw_m, _ = torch.ops.aten.convolution_backward(gy, xb, wb, None, list(stride), list(padding), list(dilation), False, [0, 0],
                                                             1, masks)
-        if gx is None and need_x:
-            gx = gx_m
-        if gw is None:
-            gw = gw_m
+        gx, gw = (gx_m if masks[0] else gx), (gw_m if masks[1] else gw)
     return gx, gw, gb
 
 
 class _ConvBiasActPoolFn(torch.autograd.Function):
-    """Conv2D(relu) -> MaxPooling2D(2, 2, 'same') of the TRAINING step (pool1 .. pool3) as one autograd node: forward = the layer's
-    MFMA kernel + the one-pass pooling kernel (conv1_2 -> pool1: ONE launch that writes both maps, round 6); backward = max-pool gradient, ReLU mask and bias gradient in ONE pass over the
-    full-resolution map (csrc/ssdhip_train.hip, maxpool2_relu_bwd_bias_kernel) -- the unmasked full-resolution gradient is never
-    written -- then the convolution's gradients as in _ConvBiasActFn."""
+    """Conv2D(relu) -> MaxPooling2D(2, 2, 'same') of the TRAINING step (pool1 .. pool3) as one autograd node: forward = ONE launch that
+    writes both maps where `_conv_select.pool_keep` has a form for the layer (round 6), the layer's MFMA kernel + the one-pass pooling
+    kernel otherwise; backward = max-pool gradient, ReLU mask and bias gradient in ONE pass over the full-resolution map (csrc/
+    ssdhip_train.hip, maxpool2_relu_bwd_bias_kernel: the unmasked gradient is never written), then the convolution's as in _ConvBiasActFn."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, run, stride, padding, dilation, wb=None, bb=None, wt=None, link_in=None):
-        xb = x.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        if wb is None:
-            wb = weight.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-            bb = bias.detach().to(torch.bfloat16) if bias is not None else None
+        xb, wb, bb = _bf16_operands(x, weight, bias, wb, bb)
         ctx.link_in = link_in
-        if (xb.shape[1] == 64 and wb.shape[2:] == (3, 3) and stride == (1, 1) and padding == (1, 1) and dilation == (1, 1)
-                and wb.shape[0] % 64 == 0 and xb.is_cuda and not sel.on("NO_POOL_KEEP")):
-            # round 6: conv1_2 -> pool1 as ONE launch that writes the activation AND the pooled map (csrc/ssdhip_conv64.hip, KEEP): the
-            # pooling pass read the 368 MB map back (~95 us of the step)
-            y, p = nat.conv3x3_c64_pool_keep(xb, wb, bb, relu=True)
-        else:
-            # fourth session: conv2_2 -> pool2 and conv3_3 -> pool3 the same way on the slab kernel (csrc/ssdhip_convh.hip, KEEP)
-            kept = None
-            if (xb.shape[1] % 128 == 0 and wb.shape[0] % 128 == 0 and wb.shape[2:] == (3, 3) and stride == (1, 1) and padding == (1, 1)
-                    and dilation == (1, 1) and xb.is_cuda and not sel.on("NO_POOL_KEEP")
-                    and not sel.on("NO_HALO") and not sel.on("NO_HALO_POOL_KEEP")):
-                kept = nat.conv3x3_halo_pool_keep(xb, wb, bb, relu=True)
-            if kept is not None:
-                y, p = kept
-            else:
-                y = run(xb, wb, bb)
-                p = nat.bias_act_maxpool(y, None, 2, 2, 0, True, relu=False)
+        keep = sel.pool_keep(sel.geometry_of_grads(wb, xb, stride, padding, dilation), xb.is_cuda)
+        kept = {"c64": nat.conv3x3_c64_pool_keep, "halo": nat.conv3x3_halo_pool_keep}[keep](xb, wb, bb, relu=True) if keep else None
+        if kept is None:                                 # (no such form for the layer, or the slab kernel declines)
+            y = run(xb, wb, bb)
+            kept = y, nat.bias_act_maxpool(y, None, 2, 2, 0, True, relu=False)
+        y, p = kept
         ctx.save_for_backward(xb, wb, y, wt)
         ctx.conf = (stride, padding, dilation, weight.dtype, None if bias is None else bias.dtype, x.dtype)
         return p
 
     @staticmethod
     def backward(ctx, gp):
-        xb, wb, y, wt = ctx.saved_tensors
-        stride, padding, dilation, wdt, bdt, xdt = ctx.conf
         gp = gp.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        fused = nat.maxpool2_relu_bwd_bias(y, gp, reduce=False)
+        fused = nat.maxpool2_relu_bwd_bias(ctx.saved_tensors[2], gp, reduce=False)
         if fused is None:
             raise RuntimeError("channel count not supported by the fused pooling backward (the forward checks it)")
-        gy, partial = fused
-        want_gb = bdt is not None and ctx.needs_input_grad[2]
-        gx, gw, gb = _conv_input_weight_grads(gy, xb, wb, stride, padding, dilation, ctx.needs_input_grad[0], wt,
-                                              partial if want_gb else None, ctx.link_in)
-        if want_gb:
-            gb = (gb if gb is not None else nat.row_sums(partial)).to(bdt)
-        else:
-            gb = None
-        return (gx.to(xdt) if gx is not None else None), gw.to(wdt), gb, None, None, None, None, None, None, None, None
+        return _node_backward(ctx, *fused, ctx.link_in)
 
 
 class _PackedHeadFn(torch.autograd.Function):

@@ -13,12 +13,13 @@ import contextlib
 import inspect
 import json
 import os
+import types
 
 import torch
 from torch import nn
 
 from ssd_keras_amd import _native as nat
-from ssd_keras_amd.models._common import SSDModel, _conv_input_weight_grads
+from ssd_keras_amd.models._common import SSDModel, _ConvBiasActFn, _ConvBiasActPoolFn, _conv_input_weight_grads
 
 TRACE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_dispatch_trace.json")
 RECORD_ENV = "CONV_DISPATCH_RECORD"          # set to the hash of the commit under trace: the test then WRITES the trace file
@@ -27,7 +28,8 @@ BATCHES = (1, 8, 16, 32)                     # 16: the threshold of the untimed 
 
 ENVS = (None, "SSDHIP_CONV=igemm", "SSDHIP_CONV=miopen", "SSDHIP_CONV=auto_miopen", "SSDHIP_PREFER=halo", "SSDHIP_NO_HALO=1",
         "SSDHIP_NO_IMAGE=1", "SSDHIP_IMAGE2=0", "SSDHIP_NO_SPLITK=1", "SSDHIP_GEMM_1X1=1", "SSDHIP_NO_OWN_DGRAD=1",
-        "SSDHIP_NO_TAPS_BWD=1", "SSDHIP_NO_OWN_WGRAD=1", "SSDHIP_NO_MASKED_DGRAD=1", "SSDHIP_NO_C64_DGRAD=1", "SSDHIP_NO_POOL_KEEP=1")
+        "SSDHIP_NO_TAPS_BWD=1", "SSDHIP_NO_OWN_WGRAD=1", "SSDHIP_NO_MASKED_DGRAD=1", "SSDHIP_NO_C64_DGRAD=1", "SSDHIP_NO_POOL_KEEP=1",
+        "SSDHIP_NO_CONV1_1_BWD=1", "SSDHIP_NO_MASKED_SUMS=1", "SSDHIP_NO_HALO_POOL_KEEP=1", "SSDHIP_NO_FUSED_POOL_BWD=1")
 
 
 def _geometries():
@@ -62,7 +64,16 @@ GEOMETRIES = _geometries()
 # (link_in, wt, bias_partial, need_x, weight-gradient kernels decline) of the _conv_input_weight_grads entries
 GRAD_FORMS = {"grads": (0, 0, 0, 1, 0), "grads+link": (1, 0, 0, 1, 0), "grads+wt": (0, 1, 0, 1, 0), "grads+partial": (0, 0, 1, 1, 0),
               "grads+link+wt+partial": (1, 1, 1, 1, 0), "grads-x": (0, 0, 1, 0, 0), "grads+declined": (0, 0, 1, 1, 1)}
-ENTRIES = ("act_relu", "act_lin", "pool_ceil", "pool_floor", "pool_3_1_1", "thunk", "train_pool") + tuple(GRAD_FORMS)
+# (relu, link_out: None absent / "out" present and unmasked / "masked" / "masked+partial", bias gradient wanted, need_x) of the
+# _ConvBiasActFn.backward entries.  (A layer without ReLU holds no link_out: its forward drops it.)
+LINK_OUT = (None, "out", "masked", "masked+partial")
+BWD_FORMS = {"bwd%s%s%s%s" % ("" if relu else "_lin", "+" + link if link else "", "" if gb else "-gb", "" if need_x else "-x"):
+             (relu, link, gb, need_x)
+             for relu in (1, 0) for link in (LINK_OUT if relu else (None,)) for gb in (1, 0) for need_x in (1, 0)}
+# (link_in, bias gradient wanted) of the _ConvBiasActPoolFn.backward entries
+POOL_BWD_FORMS = {"pool_bwd": (0, 1), "pool_bwd+link": (1, 1), "pool_bwd-gb": (0, 0)}
+ENTRIES = (("act_relu", "act_lin", "pool_ceil", "pool_floor", "pool_3_1_1", "thunk", "train_pool") + tuple(GRAD_FORMS) + tuple(BWD_FORMS)
+           + tuple(POOL_BWD_FORMS))
 
 
 class _Map(torch.Tensor):
@@ -163,6 +174,18 @@ def _halo_masked(a, st):
     return (y, _map((8, a["weight"].shape[0]), torch.float32)) if a["sums"] else y
 
 
+def _sums(c, reduce):
+    """The channel sums of a C-channel map ([rows, C] partials, or [C]); None where csrc/ssdhip_train.hip's passes decline the count."""
+    if c % 8 or 256 % (c // 8):
+        return None
+    return _map((c,) if reduce else (8, c), torch.float32, False)
+
+
+def _masked_and_sums(full, reduce):
+    sums = _sums(full.shape[1], reduce)
+    return None if sums is None else (_map(full.shape), sums)
+
+
 # what a launching function returns here: empty tensors of the real result's shape (a: its arguments by name, defaults filled in)
 RESULTS = {
     "conv2d_same": lambda a, st: _conv_result(a),
@@ -185,6 +208,11 @@ RESULTS = {
     "conv3x3_wgrad": lambda a, st: _wgrad_result(a, 3, st),
     "conv1x1_wgrad": lambda a, st: _wgrad_result(a, 1, st),
     "conv3x3_taps_wgrad": lambda a, st: _wgrad_result(a, 3, st),
+    "relu_bwd_bias": lambda a, st: _masked_and_sums(a["gy"], a["reduce"]),
+    "maxpool2_relu_bwd_bias": lambda a, st: _masked_and_sums(a["y"], a["reduce"]),
+    "channel_sums_partial": lambda a, st: _sums(a["gy"].shape[1], False),
+    "row_sums": lambda a, st: _map(a["partial"].shape[1:], torch.float32),
+    "conv1_1_backward": lambda a, st: (_map((64, 3, 3, 3), torch.float32), _map((64,), torch.float32)),
 }
 HOST_ONLY = ("conv2d_image_supported", "conv3x3_image_supported", "conv3x3_halo_plan", "assemble_backward_supported", "load",
              "lib_path", "check", "require_cuda")
@@ -302,8 +330,10 @@ class Tracer:
                 self.state["path"] = "training"
                 with torch.enable_grad():
                     res = _desc(m.conv_act_pool(conv, x, 2, 2, ceil_mode=True))
-            else:
+            elif entry in GRAD_FORMS:
                 res = self._grads(entry, conv, x)
+            else:
+                res = self._backward(entry, conv, x)
         except _Unexpected as e:
             res = "unexpected call: %s" % e
         keys = []
@@ -345,6 +375,41 @@ class Tracer:
         return {"grads": _desc(got), "link_masked": bool(link_in.masked) if link_in is not None else None,
                 "link_partial": _desc(link_in.partial) if link_in is not None else None}
 
+    def _backward(self, entry, conv, x):
+        """`backward` of the layer's autograd node [of the layer + pool node], called as the plain static method it is on what its
+        forward would have saved: the launches, the three leading gradients, how many results and the link's state afterwards."""
+        self.state["path"] = "training"
+        cin, cout, k, s, p, d = conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
+        y = _map((x.shape[0], cout, _out(x.shape[2], k, s, p, d), _out(x.shape[3], k, s, p, d)))
+        with torch.enable_grad():
+            link = self.model.relu_link()
+        # (dtypes that every gradient has to be cast to: the kernels return bf16 dL/dx and float32 dL/dw, dL/db)
+        dtypes = (torch.bfloat16, torch.bfloat16, torch.float32)
+        if entry in BWD_FORMS:
+            relu, state, gb, need_x = BWD_FORMS[entry]
+            if state is None:
+                link = None
+            else:
+                link.masked = state.startswith("masked")
+                link.partial = _map((8, cout), torch.float32, False) if state.endswith("partial") else None
+            ctx = types.SimpleNamespace(saved_tensors=(x, conv.weight, y if relu else None, None), links=(None, link),
+                                        conf=(conv.stride, conv.padding, conv.dilation, bool(relu)) + dtypes,
+                                        needs_input_grad=(bool(need_x), True, bool(gb)) + (False,) * 10)
+            node, g_out = _ConvBiasActFn, y
+        else:
+            link_in, gb = POOL_BWD_FORMS[entry]
+            link = link if link_in else None
+            ctx = types.SimpleNamespace(saved_tensors=(x, conv.weight, y, None), link_in=link, conf=(conv.stride, conv.padding, conv.dilation) + dtypes,
+                                        needs_input_grad=(True, True, bool(gb)) + (False,) * 8)
+            node, g_out = _ConvBiasActPoolFn, _map((y.shape[0], cout, (y.shape[2] + 1) // 2, (y.shape[3] + 1) // 2))
+        try:
+            got = node.backward(ctx, g_out)
+            res = {"grads": _desc(got[:3]), "results": len(got)}
+        except RuntimeError as e:                        # (the pooled node on a channel count its one-pass backward declines)
+            res = {"raises": "RuntimeError: %s" % e}
+        return dict(res, link_masked=bool(link.masked) if link is not None else None,
+                    link_partial=_desc(link.partial) if link is not None else None)
+
 
 def _name_keys(events, keys):
     """The events with every autotune key replaced by its place in `keys`: what is left no longer depends on the layer's size."""
@@ -363,7 +428,7 @@ def applies(entry, geometry):
         return GEOMETRIES[geometry][7] % 2 == 1          # ceil_mode=False on an odd map: no fused pooling epilogue
     if entry == "conv1_block":
         return geometry.startswith("conv1_2@")
-    if entry in GRAD_FORMS:
+    if entry in GRAD_FORMS or entry in BWD_FORMS or entry in POOL_BWD_FORMS:
         return GEOMETRIES[geometry][6] == 1              # (a grouped layer never reaches the gradients: SSDModel._fused_train)
     return True
 

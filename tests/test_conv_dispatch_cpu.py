@@ -27,6 +27,19 @@ def test_trace_covers_every_case(recorded):
     assert len(recorded["recorded_on_commit"]) == 40
 
 
+def test_link_out_on_a_layer_without_relu_is_refused():
+    """The consumer of a link masks its data gradient by this layer's output > 0: only the ReLU backward of a ReLU layer is that mask."""
+    model, conv = cdc.Tracer().model, cdc.nn.Conv2d(8, 8, 3, padding=1)
+    x = cdc.torch.zeros(1, 8, 4, 4)
+    with cdc.torch.enable_grad():
+        link = model.relu_link()
+        assert link is not None
+        with pytest.raises(ValueError, match="link_out"):
+            model.conv_act(conv, x, relu=False, link_out=link)
+        assert model.conv_act(conv, x, relu=True, link_out=link).shape == (1, 8, 4, 4)
+        assert model.conv_act(conv, x, relu=False).shape == (1, 8, 4, 4)
+
+
 @pytest.mark.parametrize("entry", cdc.ENTRIES + ("conv1_block",))
 def test_dispatch_matches_recorded_trace(recorded, entry):
     wrong, n = [], 0
