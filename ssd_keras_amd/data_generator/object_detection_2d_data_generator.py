@@ -49,13 +49,15 @@ dataset ahead of training.  HDF5 datasets are not supported (h5py is not a depen
 from __future__ import annotations
 
 import csv
+import functools
 import inspect
 import json
 import os
 import pickle
 import sys
+import types
 import warnings
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 from copy import deepcopy
 from xml.etree import ElementTree
 
@@ -92,6 +94,44 @@ def _load_image(filename):
     from PIL import Image
     with Image.open(filename) as image:
         return np.array(image, dtype=np.uint8)
+
+
+# how one batch of generate() is transformed: the batch path (None = the per-image loop), whether the 'program' path's lazy images
+# record warps, whether a batch the device decoded is read where it is (`DataGenerator._route`)
+_Route = namedtuple('_Route', 'path warps on_device')
+_RAGGED_CHAINS = ('ssd', 'variable', 'satellite')                  # the paths whose chain reads a ragged batch of images of any sizes
+_RETURNS = ('processed_images', 'encoded_labels', 'matched_anchors', 'processed_labels', 'filenames', 'image_ids', 'evaluation-neutral',
+            'inverse_transform', 'original_images', 'original_labels')     # the order of the list generate() yields
+
+
+@functools.lru_cache(maxsize=None)
+def _kinds():
+    """The classes `_batch_path` and `_composable` tell a list by, built on first use (the chain modules import this package's ops)."""
+    from . import object_detection_2d_geometric_ops as geo
+    from . import object_detection_2d_patch_sampling_ops as patch
+    from . import object_detection_2d_photometric_ops as photo
+    from .data_augmentation_chain_constant_input_size import DataAugmentationConstantInputSize
+    from .data_augmentation_chain_original_ssd import SSDDataAugmentation
+    from .data_augmentation_chain_satellite import DataAugmentationSatellite
+    from .data_augmentation_chain_variable_input_size import DataAugmentationVariableInputSize
+    fresh = (photo.ConvertColor, photo.ConvertDataType, photo.Brightness, photo.Contrast, photo.Gamma, photo.ChannelSwap, geo.Resize)
+    in_place = (photo.Hue, photo.RandomHue, photo.Saturation, photo.RandomSaturation, photo.HistogramEqualization,
+                photo.RandomHistogramEqualization)
+    photometric = fresh[:-1] + in_place + (photo.RandomBrightness, photo.RandomContrast, photo.RandomGamma, photo.RandomChannelSwap)
+    resizes = (geo.Resize, geo.ResizeRandomInterp)
+    geometric = resizes + (geo.Flip, geo.RandomFlip, geo.Rotate, geo.RandomRotate, patch.CropPad, patch.Crop, patch.Pad,
+                           patch.RandomPatch, patch.RandomPatchInf, patch.RandomMaxCropFixedAR, patch.RandomPadFixedAR)
+    return types.SimpleNamespace(
+        geo=geo, photo=photo, fresh=fresh, in_place=in_place, photometric=photometric, resizes=resizes, geometric=geometric,
+        warped=geometric + (geo.Translate, geo.RandomTranslate, geo.Scale, geo.RandomScale),
+        gather=([photo.ConvertTo3Channels, geo.Resize], [photo.ConvertTo3Channels, patch.RandomPadFixedAR, geo.Resize]),
+        ragged_chains={SSDDataAugmentation: 'ssd', DataAugmentationVariableInputSize: 'variable', DataAugmentationSatellite: 'satellite'},
+        constant=DataAugmentationConstantInputSize)
+
+
+def _is_ssd_encoder(label_encoder):
+    from ..ssd_encoder_decoder.ssd_input_encoder import SSDInputEncoder
+    return isinstance(label_encoder, SSDInputEncoder)
 
 
 class DataGenerator:
@@ -427,28 +467,17 @@ class DataGenerator:
     @staticmethod
     def _batch_path(transformations, images, have_labels):
         """Which batch path a transformation list takes (see the module docstring); None = the per-image loop."""
-        from .data_augmentation_chain_constant_input_size import DataAugmentationConstantInputSize
-        from .data_augmentation_chain_original_ssd import SSDDataAugmentation
-        from .data_augmentation_chain_satellite import DataAugmentationSatellite
-        from .data_augmentation_chain_variable_input_size import DataAugmentationVariableInputSize
-        from .object_detection_2d_geometric_ops import Resize
-        from .object_detection_2d_patch_sampling_ops import RandomPadFixedAR
-        from .object_detection_2d_photometric_ops import ConvertTo3Channels
+        k = _kinds()
         kinds = [type(t) for t in transformations]
         if not DataGenerator._batchable(images):
             return None
-        if kinds in ([ConvertTo3Channels, Resize], [ConvertTo3Channels, RandomPadFixedAR, Resize]):
+        if kinds in k.gather:
             return 'gather'
-        if have_labels:
-            if kinds == [SSDDataAugmentation]:
-                return 'ssd'
-            if (kinds == [DataAugmentationConstantInputSize] and len({im.shape for im in images}) == 1 and images[0].ndim == 3
-                    and images[0].shape[2] == 3):
+        if have_labels and len(kinds) == 1:
+            if kinds[0] in k.ragged_chains:
+                return k.ragged_chains[kinds[0]]
+            if kinds[0] is k.constant and len({im.shape for im in images}) == 1 and images[0].ndim == 3 and images[0].shape[2] == 3:
                 return 'constant'
-            if kinds == [DataAugmentationVariableInputSize]:
-                return 'variable'
-            if kinds == [DataAugmentationSatellite]:
-                return 'satellite'
         return 'program' if DataGenerator._composable(transformations, images) else None
 
     @staticmethod
@@ -459,13 +488,23 @@ class DataGenerator:
         return not any(im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] not in (1, 3, 4)) for im in images)
 
     def _batch_path_of(self, transformations, images, have_labels):
-        """(`_batch_path`'s answer, whether the lazy images record warps): with `compose_warps` set, a list the paths above leave to the
-        loop takes the 'program' path when it is composable with Translate / Scale among the geometric ops."""
+        """(`_batch_path`'s answer, whether the lazy images record warps) for images that stay what they are: `_route`'s first two."""
+        return self._route(transformations, images, have_labels)[:2]
+
+    def _route(self, transformations, images, have_labels, decoded=False):
+        """A batch's `_Route`, decided once and before anything is downloaded.  `path` is `_batch_path`'s answer, or, with
+        `compose_warps` set, 'program' for a list the paths above leave to the loop that is composable with Translate / Scale among
+        the geometric ops (`warps`: the lazy images record them).  That needs NumPy images -- which a batch the device `decoded` will
+        be by then: it is downloaded unless `on_device` says that its path reads it where it is.  The path found for the device
+        tensors is used for their downloads: `_batch_path` and `_composable` may look at dtype, ndim and shape only, never at
+        whether an image is a NumPy array or a CUDA tensor."""
+        if not transformations:
+            return _Route(None, False, False)
         path = self._batch_path(transformations, images, have_labels)
-        if (path is None and self.compose_warps and self._batchable(images) and all(isinstance(im, np.ndarray) for im in images)
-                and self._composable(transformations, images, warps=True)):
-            return 'program', True
-        return path, False
+        if (path is None and self.compose_warps and self._batchable(images)
+                and (decoded or all(isinstance(im, np.ndarray) for im in images)) and self._composable(transformations, images, warps=True)):
+            return _Route('program', True, False)
+        return _Route(path, False, self._stays_on_device(path, images))
 
     @staticmethod
     def _is_uint8_image(im):
@@ -476,66 +515,61 @@ class DataGenerator:
         return torch.is_tensor(im) and im.is_cuda and im.dtype == torch.uint8
 
     @staticmethod
-    def _stays_on_device(transformations, images, have_labels):
+    def _stays_on_device(path, images):
         """Whether a batch the device decoded is transformed where it is (module docstring): every image a device tensor, and a batch
         path that reads a ragged device batch."""
-        if not transformations or any(isinstance(im, np.ndarray) for im in images):
+        if any(isinstance(im, np.ndarray) for im in images):
             return False
-        path = DataGenerator._batch_path(transformations, images, have_labels)
-        if path == 'gather':
-            return True
-        return path in ('ssd', 'variable', 'satellite') and all(im.ndim == 3 and im.shape[2] == 3 for im in images)
+        return path == 'gather' or (path in _RAGGED_CHAINS and all(im.ndim == 3 and im.shape[2] == 3 for im in images))
 
     @staticmethod
     def _composable(transformations, images, warps=False):
         """Whether a list is built from the package's own photometric, index-geometry and patch ops in an order the lazy images can
         record (the 'program' path of the module docstring): decided from the elements' types and the images alone, before any draw.
         `warps`: `Translate` / `RandomTranslate` / `Scale` / `RandomScale` count as geometric ops too (`compose_warps`)."""
-        from . import object_detection_2d_geometric_ops as geo
-        from . import object_detection_2d_patch_sampling_ops as patch
-        from . import object_detection_2d_photometric_ops as photo
-        fresh = (photo.ConvertColor, photo.ConvertDataType, photo.Brightness, photo.Contrast, photo.Gamma, photo.ChannelSwap, geo.Resize)
-        in_place = (photo.Hue, photo.RandomHue, photo.Saturation, photo.RandomSaturation, photo.HistogramEqualization,
-                    photo.RandomHistogramEqualization)
-        photometric = fresh[:-1] + in_place + (photo.RandomBrightness, photo.RandomContrast, photo.RandomGamma, photo.RandomChannelSwap)
-        resizes = (geo.Resize, geo.ResizeRandomInterp)
-        geometric = resizes + (geo.Flip, geo.RandomFlip, geo.Rotate, geo.RandomRotate, patch.CropPad, patch.Crop, patch.Pad,
-                               patch.RandomPatch, patch.RandomPatchInf, patch.RandomMaxCropFixedAR, patch.RandomPadFixedAR)
-        if warps:
-            geometric += (geo.Translate, geo.RandomTranslate, geo.Scale, geo.RandomScale)
-        kinds =[type(t) for t in transformations]
-        if any(k not in photometric and k not in geometric and k is not photo.ConvertTo3Channels for k in kinds):
+        k = _kinds()
+        geo, photo, geometric = k.geo, k.photo, (k.warped if warps else k.geometric)
+        kinds = [type(t) for t in transformations]
+        if any(kind not in k.photometric and kind not in geometric and kind is not photo.ConvertTo3Channels for kind in kinds):
             return False
         if kinds[0] is not photo.ConvertTo3Channels and any(im.ndim != 3 or im.shape[2] != 3 for im in images):
             return False
         phase, resized, have_fresh = 0, False, False                   # phase: 0 photometric, 1 geometric, 2 photometric again
-        for t, k in zip(transformations, kinds):
-            if k is photo.ConvertTo3Channels:
+        for t, kind in zip(transformations, kinds):
+            if kind is photo.ConvertTo3Channels:
                 continue
-            if k in geometric:
+            if kind in geometric:
                 if phase == 2 or resized:                              # a lazy image is final after its resize
                     return False
-                phase, resized = 1, k in resizes
-                if k is geo.Rotate and t.angle not in (90, 180, 270):
+                phase, resized = 1, kind in k.resizes
+                if kind is geo.Rotate and t.angle not in (90, 180, 270):
                     return False
-                if k is geo.RandomRotate and any(a not in (90, 180, 270) for a in t.angles):
+                if kind is geo.RandomRotate and any(a not in (90, 180, 270) for a in t.angles):
                     return False
             else:
                 phase = 2 if phase else 0
-                if k is photo.ConvertColor and not t.keep_3ch:
+                if kind is photo.ConvertColor and not t.keep_3ch:
                     return False
-                if k in in_place and not have_fresh:                   # it would write into the dataset's own image in the loop
+                if kind in k.in_place and not have_fresh:              # it would write into the dataset's own image in the loop
                     return False
-            have_fresh = have_fresh or k in fresh
+            have_fresh = have_fresh or kind in k.fresh
         return True
 
     @staticmethod
-    def _walk(transformations, img, lab, want_inverters):
-        """The transforms' own host code on one (lazy) image: (image, labels, inverters in the order they are applied)."""
-        inv = []
-        for transform in transformations:
-            takes = want_inverters and ('return_inverter' in inspect.signature(transform).parameters)
-            if lab is not None:
+    def _takes_inverter(transformations, want_inverters):
+        """Per transform, whether `_walk` asks it for its inverter (reference :1070).  Asked once per batch, not per image,
+        and not once per `generate()`: the list is the caller's."""
+        return [want_inverters and 'return_inverter' in inspect.signature(transform).parameters for transform in transformations]
+
+    @staticmethod
+    def _walk(transformations, img, lab, takes_inverter, on_none=None):
+        """The transforms' own host code on one image (reference :1066-1089), the one place that calls a transform: with the labels
+        when the item came with any, asking for the inverter where `takes_inverter` says so -> (image, labels, inverters, the last
+        applied first).  After every transform that leaves no image (None) the caller's `on_none()` is called; unless it raises,
+        the next transform gets the None, as in the reference's loop."""
+        inv, labelled = [], lab is not None
+        for transform, takes in zip(transformations, takes_inverter):
+            if labelled:
                 if takes:
                     img, lab, inverter = transform(img, lab, return_inverter=True)
                     inv.append(inverter)
@@ -547,9 +581,24 @@ class DataGenerator:
                     inv.append(inverter)
                 else:
                     img = transform(img)
-            if img is None:
-                raise NotImplementedError("a transform that drops the image is the per-image loop's to handle")
+            if img is None and on_none is not None:
+                on_none()
         return img, lab, inv[::-1]
+
+    def _walk_batch(self, transformations, images, labels, want_inverters, lazy_of, execute):
+        """The tail 'gather' and 'program' share: the transforms' own host code on one lazy image per item (`lazy_of(height, width)`),
+        then `execute(lazies)`, the launches for the pixels -> what `_transform_batch` returns."""
+        def refuse():
+            raise NotImplementedError("a transform that drops the image is the per-image loop's to handle")
+        takes = self._takes_inverter(transformations, want_inverters)
+        lazies, out_labels, inverters = [], [], []
+        for k, im in enumerate(images):
+            img, lab, inv = self._walk(transformations, lazy_of(int(im.shape[0]), int(im.shape[1])), None if labels is None else labels[k],
+                                       takes, refuse)
+            lazies.append(img)
+            out_labels.append(lab)
+            inverters.append(inv)
+        return execute(lazies), (None if labels is None else out_labels), inverters
 
     def _transform_batch(self, path, transformations, images, labels, want_inverters, warps=False):
         """The batch paths: images (uint8 NumPy; CUDA uint8 tensors for 'gather' and the ragged chains) and labels (arrays, or None) of the items that are transformed -> (CUDA (n, H, W, 3)
@@ -558,59 +607,28 @@ class DataGenerator:
         Translate / Scale too (`ProgramImage.of(..., warps=True)`)."""
         import torch
         from . import _image_ops as iop
-        if path in ('ssd', 'variable', 'satellite'):
+        if path in _RAGGED_CHAINS or path == 'constant':           # a chain's own `augment_batch`; they differ in how it gets the images
             chain = transformations[0]
-            to_three = (chain.photometric_distortions if path == 'ssd' else chain).convert_to_3_channels
-            three = [im if (im.ndim == 3 and im.shape[2] == 3) else to_three(im) for im in images]
-            out, out_labels = chain.augment_batch(three, labels)
+            if path == 'constant':
+                batch = torch.from_numpy(np.stack(images)).to(torch.device('cuda', torch.cuda.current_device()))
+            else:
+                to_three = (chain.photometric_distortions if path == 'ssd' else chain).convert_to_3_channels
+                batch = [im if (im.ndim == 3 and im.shape[2] == 3) else to_three(im) for im in images]
+            out, out_labels = chain.augment_batch(batch, labels)
             return out, out_labels, [[] for _ in images]
-        if path == 'constant':
-            batch = torch.from_numpy(np.stack(images)).to(torch.device('cuda', torch.cuda.current_device()))
-            out, out_labels = transformations[0].augment_batch(batch, labels)
-            return out, out_labels, [[] for _ in images]
-        if path == 'program':
-            # the transforms' own host code on lazy images that also record the photometric steps, then a few launches for the batch
-            import random
-            states = np.random.get_state(), random.getstate()
-            try:
-                lazies, out_labels, inverters = [], [], []
-                for k, im in enumerate(images):
-                    img, lab, inv = self._walk(transformations, iop.ProgramImage.of(int(im.shape[0]), int(im.shape[1]), warps=warps),
-                                               None if labels is None else labels[k], want_inverters)
-                    lazies.append(img)
-                    out_labels.append(lab)
-                    inverters.append(inv)
-                out = iop.run_program_batch(images, lazies)
-            except NotImplementedError:
-                np.random.set_state(states[0])
-                random.setstate(states[1])
-                raise
-            return out, (None if labels is None else out_labels), inverters
-        # 'gather': the transforms' own host code on lazy images, then one launch for the pixels
-        lazies, out_labels, inverters = [], [], []
-        for k, im in enumerate(images):
-            img = iop.GeoImage.of(int(im.shape[0]), int(im.shape[1]))
-            lab = None if labels is None else labels[k]
-            inv = []
-            for transform in transformations:
-                takes = want_inverters and ('return_inverter' in inspect.signature(transform).parameters)
-                if lab is not None:
-                    if takes:
-                        img, lab, inverter = transform(img, lab, return_inverter=True)
-                        inv.append(inverter)
-                    else:
-                        img, lab = transform(img, lab)
-                else:
-                    if takes:
-                        img, inverter = transform(img, return_inverter=True)
-                        inv.append(inverter)
-                    else:
-                        img = transform(img)
-            lazies.append(img)
-            out_labels.append(lab)
-            inverters.append(inv[::-1])
-        out = iop.gather_batch_ragged(iop.pack_ragged(images), lazies)
-        return out, (None if labels is None else out_labels), inverters
+        if path == 'gather':                                       # lazy images that record the geometry, one launch for the pixels
+            return self._walk_batch(transformations, images, labels, want_inverters, iop.GeoImage.of,
+                                    lambda lazies: iop.gather_batch_ragged(iop.pack_ragged(images), lazies))
+        # 'program': lazy images that also record the photometric steps, then a few launches for the batch
+        import random
+        states = np.random.get_state(), random.getstate()
+        try:
+            return self._walk_batch(transformations, images, labels, want_inverters, functools.partial(iop.ProgramImage.of, warps=warps),
+                                    lambda lazies: iop.run_program_batch(images, lazies))
+        except NotImplementedError:
+            np.random.set_state(states[0])
+            random.setstate(states[1])
+            raise
 
     def generate(self,
                  batch_size=32,
@@ -625,27 +643,13 @@ class DataGenerator:
         'processed_labels', 'filenames', 'image_ids', 'evaluation-neutral', 'inverse_transform', 'original_images', 'original_labels'.
         `device` (not in the reference): 'processed_images' is the CUDA uint8 batch on that device, not downloaded, and 'encoded_labels'
         come from `SSDInputEncoder.encode_to_device` (float64, on the device).'''
-        from ..ssd_encoder_decoder.ssd_input_encoder import SSDInputEncoder
         if self.dataset_size == 0:
             raise DatasetError("Cannot generate batches because you did not load a dataset.")
-
-        if self.labels is None:
-            if any([ret in returns for ret in ['original_labels', 'processed_labels', 'encoded_labels', 'matched_anchors', 'evaluation-neutral']]):
-                warnings.warn("Since no labels were given, none of 'original_labels', 'processed_labels', 'evaluation-neutral', 'encoded_labels', and 'matched_anchors' " +
-                              "are possible returns, but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
-        elif label_encoder is None:
-            if any([ret in returns for ret in ['encoded_labels', 'matched_anchors']]):
-                warnings.warn("Since no label encoder was given, 'encoded_labels' and 'matched_anchors' aren't possible returns, " +
-                              "but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
-        elif not isinstance(label_encoder, SSDInputEncoder):
-            if 'matched_anchors' in returns:
-                warnings.warn("`label_encoder` is not an `SSDInputEncoder` object, therefore 'matched_anchors' is not a possible return, " +
-                              "but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
-
+        self._warn_of_impossible_returns(returns, label_encoder)
         if shuffle:
             self._shuffle()
-        if degenerate_box_handling == 'remove':
-            box_filter = BoxFilter(check_overlap=False, check_min_area=False, check_degenerate=True, labels_format=self.labels_format)
+        box_filter = (BoxFilter(check_overlap=False, check_min_area=False, check_degenerate=True, labels_format=self.labels_format)
+                      if degenerate_box_handling == 'remove' else None)
         if self.labels is not None:
             for transform in transformations:
                 transform.labels_format = self.labels_format
@@ -655,151 +659,127 @@ class DataGenerator:
 
         current = 0
         while True:
-            batch_X, batch_y = [], []
             if current >= self.dataset_size:
                 current = 0
                 if shuffle:
                     self._shuffle()
-
-            batch_indices = self.dataset_indices[current:current + batch_size]
-            if self.images is not None:
-                for i in batch_indices:
-                    batch_X.append(self.images[i])
-                batch_filenames = self.filenames[current:current + batch_size] if self.filenames is not None else None
-            else:
-                batch_filenames = self.filenames[current:current + batch_size]
-                if self.decode == 'device':
-                    from . import jpeg_decode
-                    batch_X = jpeg_decode.decode_jpeg_batch(batch_filenames, index=self.jpeg_index)
-                    if not self._stays_on_device(transformations, batch_X, self.labels is not None):
-                        batch_X = jpeg_decode.to_host(batch_X)
-                else:
-                    for filename in batch_filenames:
-                        batch_X.append(_load_image(filename))
-
-            batch_y = deepcopy(self.labels[current:current + batch_size]) if self.labels is not None else None
-            batch_eval_neutral = self.eval_neutral[current:current + batch_size] if self.eval_neutral is not None else None
-            batch_image_ids = self.image_ids[current:current + batch_size] if self.image_ids is not None else None
-            if 'original_images' in returns:
-                if any(not isinstance(im, np.ndarray) for im in batch_X):
-                    from . import jpeg_decode
-                    batch_original_images = jpeg_decode.to_host(batch_X)
-                else:
-                    batch_original_images = deepcopy(batch_X)
-            if 'original_labels' in returns:
-                batch_original_labels = deepcopy(batch_y)
+            span = slice(current, current + batch_size)
             current += batch_size
 
-            batch_items_to_remove = []
-            batch_inverse_transforms = []
-            want_inverters = 'inverse_transform' in returns
-            path, warps = self._batch_path_of(transformations, batch_X, self.labels is not None) if transformations else (None, False)
-            processed = None                                   # the batch paths' CUDA batch of the transformed items
-            if path is not None:
-                todo = []
-                for i in range(len(batch_X)):
-                    if self.labels is not None:
-                        batch_y[i] = np.array(batch_y[i])
-                        if (batch_y[i].size == 0) and not keep_images_without_gt:
-                            batch_items_to_remove.append(i)
-                            continue
-                    todo.append(i)
-                if todo:
-                    try:
-                        processed, out_labels, inverters = self._transform_batch(
-                            path, transformations, [batch_X[i] for i in todo], None if self.labels is None else [batch_y[i] for i in todo],
-                            want_inverters, warps)
-                    except NotImplementedError:
-                        if path != 'program':
-                            raise
-                        path, batch_items_to_remove = None, []     # this batch cannot be composed: the per-image loop, from the same draws
-                if path is not None:
-                    if todo:
-                        for k, i in enumerate(todo):
-                            batch_X[i] = k                         # a row of `processed`
-                            if self.labels is not None:
-                                batch_y[i] = out_labels[k]
-                    inv_of = dict(zip(todo, inverters)) if todo else {}
-                    batch_inverse_transforms = [inv_of.get(i, []) for i in range(len(batch_X))]
-                    for i in todo:
-                        self._check_degenerate(i, batch_y, degenerate_box_handling, box_filter if degenerate_box_handling == 'remove' else None,
-                                               keep_images_without_gt, batch_items_to_remove)
-            if path is None:
-                for i in range(len(batch_X)):
-                    if self.labels is not None:
-                        batch_y[i] = np.array(batch_y[i])
-                        if (batch_y[i].size == 0) and not keep_images_without_gt:
-                            batch_items_to_remove.append(i)
-                            batch_inverse_transforms.append([])
-                            continue
-                    if transformations:
-                        inverse_transforms = []
-                        for transform in transformations:
-                            if self.labels is not None:
-                                if want_inverters and ('return_inverter' in inspect.signature(transform).parameters):
-                                    batch_X[i], batch_y[i], inverse_transform = transform(batch_X[i], batch_y[i], return_inverter=True)
-                                    inverse_transforms.append(inverse_transform)
-                                else:
-                                    batch_X[i], batch_y[i] = transform(batch_X[i], batch_y[i])
-                                if batch_X[i] is None:
-                                    batch_items_to_remove.append(i)
-                                    batch_inverse_transforms.append([])
-                                    continue
-                            else:
-                                if want_inverters and ('return_inverter' in inspect.signature(transform).parameters):
-                                    batch_X[i], inverse_transform = transform(batch_X[i], return_inverter=True)
-                                    inverse_transforms.append(inverse_transform)
-                                else:
-                                    batch_X[i] = transform(batch_X[i])
-                        batch_inverse_transforms.append(inverse_transforms[::-1])
-                    self._check_degenerate(i, batch_y, degenerate_box_handling, box_filter if degenerate_box_handling == 'remove' else None,
-                                           keep_images_without_gt, batch_items_to_remove)
+            batch_X, batch_filenames, decoded = self._fetch(span)
+            route = self._route(transformations, batch_X, self.labels is not None, decoded)
+            if decoded and not route.on_device:
+                from . import jpeg_decode
+                batch_X = jpeg_decode.to_host(batch_X)
+            batch_y = deepcopy(self.labels[span]) if self.labels is not None else None
+            batch = {'processed_images': batch_X,                  # every list of the batch an item is removed from
+                     'processed_labels': batch_y,
+                     'filenames': batch_filenames,
+                     'image_ids': self.image_ids[span] if self.image_ids is not None else None,
+                     'evaluation-neutral': self.eval_neutral[span] if self.eval_neutral is not None else None,
+                     'original_images': self._host_copies(batch_X) if 'original_images' in returns else None,
+                     'original_labels': deepcopy(batch_y) if 'original_labels' in returns else None}
 
-            if batch_items_to_remove:
-                for j in sorted(batch_items_to_remove, reverse=True):
-                    batch_X.pop(j)
-                    batch_filenames.pop(j)
-                    if batch_inverse_transforms:
-                        batch_inverse_transforms.pop(j)
-                    if self.labels is not None:
-                        batch_y.pop(j)
-                    if self.image_ids is not None:
-                        batch_image_ids.pop(j)
-                    if self.eval_neutral is not None:
-                        batch_eval_neutral.pop(j)
-                    if 'original_images' in returns:
-                        batch_original_images.pop(j)
-                    if 'original_labels' in returns and self.labels is not None:
-                        batch_original_labels.pop(j)
+            processed, inverters, removed = self._transform(route, transformations, batch_X, batch_y, 'inverse_transform' in returns,
+                                                            keep_images_without_gt, degenerate_box_handling, box_filter)
+            batch['inverse_transform'] = inverters
+            for j in sorted(removed, reverse=True):                # reference :1118-1128: the file names whatever they are, the
+                for name, values in batch.items():                 # inverters while there are any, the others where they exist
+                    if values or name == 'filenames':
+                        values.pop(j)
+            batch['processed_images'] = self._assemble(batch_X, processed, device)
+            batch['encoded_labels'], batch['matched_anchors'] = self._encode(label_encoder, batch_y, 'matched_anchors' in returns, device)
+            yield [batch[name] for name in _RETURNS if name in returns]
 
-            batch_X = self._assemble(batch_X, processed, device)
-            if (batch_X.numel() if device is not None else batch_X.size) == 0:
-                raise DegenerateBatchError("You produced an empty batch. This might be because the images in the batch vary " +
-                                           "in their size and/or number of channels. Note that after all transformations " +
-                                           "(if any were given) have been applied to all images in the batch, all images " +
-                                           "must be homogenous in size along all axes.")
+    def _warn_of_impossible_returns(self, returns, label_encoder):
+        """Reference :886-905: the returns that will be None for want of labels, of an encoder, or of an `SSDInputEncoder`."""
+        if self.labels is None:
+            if any([ret in returns for ret in ['original_labels', 'processed_labels', 'encoded_labels', 'matched_anchors', 'evaluation-neutral']]):
+                warnings.warn("Since no labels were given, none of 'original_labels', 'processed_labels', 'evaluation-neutral', 'encoded_labels', and 'matched_anchors' " +
+                              "are possible returns, but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
+        elif label_encoder is None:
+            if any([ret in returns for ret in ['encoded_labels', 'matched_anchors']]):
+                warnings.warn("Since no label encoder was given, 'encoded_labels' and 'matched_anchors' aren't possible returns, " +
+                              "but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
+        elif not _is_ssd_encoder(label_encoder):
+            if 'matched_anchors' in returns:
+                warnings.warn("`label_encoder` is not an `SSDInputEncoder` object, therefore 'matched_anchors' is not a possible return, " +
+                              "but you set `returns = {}`. The impossible returns will be `None`.".format(returns))
 
-            batch_y_encoded, batch_matched_anchors = None, None
-            if not (label_encoder is None or self.labels is None):
-                if ('matched_anchors' in returns) and isinstance(label_encoder, SSDInputEncoder):
-                    batch_y_encoded, batch_matched_anchors = label_encoder(batch_y, diagnostics=True)
-                elif device is not None and isinstance(label_encoder, SSDInputEncoder):
-                    batch_y_encoded = label_encoder.encode_to_device(batch_y, device=device, want_f32=False, want_f64=True)[1]
-                else:
-                    batch_y_encoded = label_encoder(batch_y, diagnostics=False)
+    def _fetch(self, span):
+        """The images of the batch at `span` of the dataset (reference :998-1017): from memory, decoded by PIL, or (decode='device')
+        decoded on the device and still there -> (images, file names, whether the device decoded them)."""
+        if self.images is not None:
+            images = [self.images[i] for i in self.dataset_indices[span]]
+            return images, (self.filenames[span] if self.filenames is not None else None), False
+        filenames = self.filenames[span]
+        if self.decode == 'device':
+            from . import jpeg_decode
+            return jpeg_decode.decode_jpeg_batch(filenames, index=self.jpeg_index), filenames, True
+        return [_load_image(filename) for filename in filenames], filenames, False
 
-            ret = []
-            if 'processed_images' in returns: ret.append(batch_X)
-            if 'encoded_labels' in returns: ret.append(batch_y_encoded)
-            if 'matched_anchors' in returns: ret.append(batch_matched_anchors)
-            if 'processed_labels' in returns: ret.append(batch_y)
-            if 'filenames' in returns: ret.append(batch_filenames)
-            if 'image_ids' in returns: ret.append(batch_image_ids)
-            if 'evaluation-neutral' in returns: ret.append(batch_eval_neutral)
-            if 'inverse_transform' in returns: ret.append(batch_inverse_transforms)
-            if 'original_images' in returns: ret.append(batch_original_images)
-            if 'original_labels' in returns: ret.append(batch_original_labels)
-            yield ret
+    @staticmethod
+    def _host_copies(images):
+        """'original_images': NumPy arrays the transformations cannot reach (reference :1037)."""
+        if any(not isinstance(im, np.ndarray) for im in images):
+            from . import jpeg_decode
+            return jpeg_decode.to_host(images)
+        return deepcopy(images)
+
+    def _transform(self, route, transformations, batch_X, batch_y, want_inverters, keep_images_without_gt, handling, box_filter):
+        """Transforms the items of a batch in place, by the route's batch path or by the reference's per-image loop (:1050-1112) ->
+        (the batch path's CUDA batch -- batch_X then holds its row numbers -- or None, the reference's list of inverters, the items
+        to remove).  That list is the reference's with its quirks: one entry per item only when there are transformations (an item
+        without ground truth has its [] either way), and one more [] per transform that left an item without an image."""
+        have_labels = self.labels is not None
+        todo, removed = [], []
+        for i in range(len(batch_X)):
+            if have_labels:
+                batch_y[i] = np.array(batch_y[i])
+                if batch_y[i].size == 0 and not keep_images_without_gt:
+                    removed.append(i)
+                    continue
+            todo.append(i)
+        entries = {i: [[]] for i in removed}                       # per item, what the reference appends to its ONE list of inverters
+        processed = None
+        if route.path is not None and todo:
+            try:
+                processed, out_labels, out_inverters = self._transform_batch(
+                    route.path, transformations, [batch_X[i] for i in todo], [batch_y[i] for i in todo] if have_labels else None,
+                    want_inverters, route.warps)
+            except NotImplementedError:
+                if route.path != 'program':
+                    raise                                          # else this batch cannot be composed: the loop, from the same draws
+        takes = self._takes_inverter(transformations, want_inverters) if processed is None else None
+        for k, i in enumerate(todo):
+            if processed is not None:
+                batch_X[i], entries[i] = k, [out_inverters[k]]     # a row of `processed`
+                if have_labels:
+                    batch_y[i] = out_labels[k]
+            elif transformations:
+                entries[i] = []
+                def dropped(i=i):                                  # reference :1076-1078, once per transform that leaves no image
+                    removed.append(i)
+                    entries[i].append([])
+                batch_X[i], lab, inverters = self._walk(transformations, batch_X[i], batch_y[i] if have_labels else None, takes,
+                                                        dropped if have_labels else None)
+                entries[i].append(inverters)
+                if have_labels:
+                    batch_y[i] = lab
+            self._check_degenerate(i, batch_y, handling, box_filter, keep_images_without_gt, removed)
+        return processed, [entry for i in sorted(entries) for entry in entries[i]], removed
+
+    def _encode(self, label_encoder, batch_y, want_anchors, device):
+        """Reference :1146-1156 -> (encoded labels, matched anchors), None without an encoder or without labels; with `device`, an
+        `SSDInputEncoder` encodes there."""
+        if label_encoder is None or self.labels is None:
+            return None, None
+        if _is_ssd_encoder(label_encoder):
+            if want_anchors:
+                return label_encoder(batch_y, diagnostics=True)
+            if device is not None:
+                return label_encoder.encode_to_device(batch_y, device=device, want_f32=False, want_f64=True)[1], None
+        return label_encoder(batch_y, diagnostics=False), None
 
     def _check_degenerate(self, i, batch_y, handling, box_filter, keep_images_without_gt, batch_items_to_remove):
         """Reference :774-795: degenerate boxes of item i after the transformations -> a warning, or BoxFilter removes them."""
@@ -822,20 +802,24 @@ class DataGenerator:
     @staticmethod
     def _assemble(batch_X, processed, device):
         """The batch as the reference's `np.array(batch_X)`, or as a CUDA tensor on `device`.  With a batch path, batch_X holds row
-        numbers of `processed` (the images that survived removal)."""
-        if processed is None:
-            batch = np.array(batch_X)
-            if device is None:
-                return batch
-            import torch
-            return torch.from_numpy(np.ascontiguousarray(batch)).to(device)
-        rows = list(batch_X)
+        numbers of `processed` (the images that survived removal).  An empty batch is the reference's DegenerateBatchError."""
         if device is not None:
             import torch
-            t = processed.to(device)
-            return t if rows == list(range(int(t.shape[0]))) else t[torch.as_tensor(rows, dtype=torch.long, device=t.device)]
-        host = processed.cpu().numpy()
-        return host if rows == list(range(host.shape[0])) else host[rows]
+        if processed is None:
+            batch = np.array(batch_X)
+            if device is not None:
+                batch = torch.from_numpy(np.ascontiguousarray(batch)).to(device)
+        else:
+            rows = list(batch_X)
+            batch = processed.to(device) if device is not None else processed.cpu().numpy()
+            if rows != list(range(int(batch.shape[0]))):
+                batch = batch[rows] if device is None else batch[torch.as_tensor(rows, dtype=torch.long, device=batch.device)]
+        if (batch.numel() if device is not None else batch.size) == 0:
+            raise DegenerateBatchError("You produced an empty batch. This might be because the images in the batch vary " +
+                                       "in their size and/or number of channels. Note that after all transformations " +
+                                       "(if any were given) have been applied to all images in the batch, all images " +
+                                       "must be homogenous in size along all axes.")
+        return batch
 
     # ---- the dataset -----------------------------------------------------------------------------------------------------------------
     def save_dataset(self,

@@ -279,3 +279,40 @@ def test_a_list_without_warps_is_launched_as_before(monkeypatch):
         monkeypatch.undo()
     _assert_same(runs[1][0], runs[0][0])
     assert runs[1][1] == runs[0][1] and RAGGED not in runs[0][1] and runs[0][1]
+
+
+@pytest.mark.gpu
+def test_a_batch_the_device_decoded_takes_the_program_path_with_warps(monkeypatch, tmp_path):
+    """decode = 'device' with `compose_warps`: the route is decided on the device tensors, before they are downloaded for the 'program'
+    path, and it is the route of the host-decoded batch -- pixels (the device decoder's are PIL's), labels, inverters and both
+    generators' final states are equal, and both runs composed their batch with warps."""
+    from PIL import Image
+    from ssd_keras_amd.data_generator import jpeg_decode
+    from tests import np_jpeg
+    n = pc.ns()
+    names, labels = [], []
+    for k, (h, w) in enumerate([(16, 24), (24, 16), (17, 23), (24, 24)]):
+        names.append(str(tmp_path / ("im%d.jpg" % k)))
+        Image.fromarray(np_jpeg.make_array(h, w, "RGB", 90 + k)).save(names[-1], quality=85, subsampling=(2, 0, 1, 2)[k])
+        labels.append(np.array([[1 + k % 3, 2, 3, w - 3, h - 2]]))
+    entered, real = [], n.DataGenerator._transform_batch
+
+    def spy(self, path, transformations, images, labels, want_inverters, warps=False):
+        entered.append((path, warps))
+        return real(self, path, transformations, images, labels, want_inverters, warps)
+    monkeypatch.setattr(n.DataGenerator, "_transform_batch", spy)
+    stages = _record_stages(monkeypatch)
+
+    def files(decode):
+        def make(n):
+            g = n.DataGenerator(filenames=list(names), labels=[l.copy() for l in labels], verbose=False)
+            g.decode, g.compose_warps = decode, True
+            return g
+        return make
+    before = dict(jpeg_decode.COUNTERS)
+    host = pc.run_generate(n, files('host'), wc.list_i(n), seed=95, n_batches=1, batch_size=4)
+    assert jpeg_decode.COUNTERS == before
+    dev = pc.run_generate(n, files('device'), wc.list_i(n), seed=95, n_batches=1, batch_size=4)
+    assert jpeg_decode.COUNTERS["device"] - before["device"] == 4 and jpeg_decode.COUNTERS["host"] == before["host"]
+    _assert_same(dev, host)
+    assert entered == [('program', True)] * 2 and len(stages) == 2          # neither run fell back to the loop
