@@ -138,8 +138,26 @@ int ssdhip_encode(const double* anchors, const double* variances, const double* 
  *   keep_mask     [B,N] uint8: 1 where the anchor is a kept hard negative (its classification loss
  *                 enters the sum besides the positives') -- saved for backward
  *   backward: grad_y_pred [B,N,C+12] = d(sum_b grad_out[b]*loss[b]) / d y_pred (last 8 columns zero)
+ *
+ * 2 <= C <= SSDHIP_LOSS_MAX_CLASSES (background included): the smallest row tile, 64 anchors of y_true and of y_pred, must fit the
+ * 140 KiB of dynamic LDS both directions allow themselves.  Any other C is SSDHIP_E_BADARG from ssdhip_loss_forward,
+ * ssdhip_loss_backward and ssdhip_loss_plan, and 0 from ssdhip_loss_workspace_bytes.
+ *
+ * ssdhip_loss_plan reports which kernels a forward / backward call with these arguments launches, for tests that must know the path
+ * they exercise.  Host only: no HIP call, no pointer is dereferenced (only their alignment counts; grad_y_pred and keep_mask may be
+ * NULL = aligned).  It is computed by the function the two launchers use, so it is the plan BEFORE the per-device opt-in to more than
+ * 64 KiB of dynamic LDS that the streaming kernels make: should a device refuse it, the call runs the tiled kernel instead.  (The
+ * tiled kernels launch with up to 140 KiB as they are: C >= 116 is tested on gfx950, tests/test_loss_paths_gpu.py.)  It honours
+ * SSDHIP_LOSS_STREAM=0 like the launchers.
+ *   out[0] forward runs the streaming kernel (1) or the tiled one (0)      out[1] the same for backward
+ *   out[2] TA, anchors per tile of the tiled kernels (256, 128 or 64)      out[3] G, 1 KiB loads per array and 64-anchor tile (0: tiled forward)
+ *   out[4] the streaming grid (0: tiled forward)                           out[5] waves per streaming workgroup (0: tiled forward)
+ *   out[6] select pass blocks of 2048 values: ceil(B N / 2048)             out[7] keep-kernel blocks per image
  */
+#define SSDHIP_LOSS_MAX_CLASSES 267
 size_t ssdhip_loss_workspace_bytes(int B, int N, int C);
+int ssdhip_loss_plan(const void* y_true, const void* y_pred, const void* grad_y_pred, const void* keep_mask, int B, int N, int C,
+                     int* out);
 int ssdhip_loss_forward(const float* y_true, const float* y_pred, int B, int N, int C,
                         int neg_pos_ratio, int n_neg_min, float alpha,
                         float* loss_per_item, float* stats, unsigned char* keep_mask,

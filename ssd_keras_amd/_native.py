@@ -93,6 +93,7 @@ SIGNATURES = {
     "ssdhip_encode_workspace_bytes": (_SZ, [_I] * 4),
     "ssdhip_encode": (_I, [_P] * 4 + [_I] * 5 + [_D, _D, _I, _D, _D] + [_I] * 4 + [_P] * 4 + [_SZ, _P]),
     "ssdhip_loss_workspace_bytes": (_SZ, [_I] * 3),
+    "ssdhip_loss_plan": (_I, [_P] * 4 + [_I] * 3 + [_INTP]),
     "ssdhip_loss_forward": (_I, [_P, _P] + [_I] * 5 + [_F] + [_P] * 4 + [_SZ, _P]),
     "ssdhip_loss_backward": (_I, [_P] * 5 + [_I] * 3 + [_F, _P, _P]),
     "ssdhip_convert_coordinates": (_I, [_P, _I, _P, _LL] + [_I] * 4 + [_P]),

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void anchor_kernel(const float* __res
             const float ad = fabsf(d);
             loc += ad < 1.0f ? 0.5f * (d * d) : ad - 0.5f;
         }
-        const float neg = cls * t[0];                                   // neg_class_loss_all (:150)
+        const float neg = cls * t[0] + 0.0f;                            // neg_class_loss_all (:150); -0.0 + 0.0 = +0.0: float_key orders the two zeros, top_k does not
         cls_out[(size_t)b * N + a0 + tid] = cls;
         neg_out[(size_t)b * N + a0 + tid] = neg;
         s_poscls = (double)(cls * pos);
@@ -593,7 +593,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void anchor_stream_kernel(const float
                 const float ad = fabsf(d);
                 loc += ad < 1.0f ? 0.5f * (d * d) : ad - 0.5f;
             }
-            const float neg = cls * tr[0];                              // neg_class_loss_all (:150)
+            const float neg = cls * tr[0] + 0.0f;                       // neg_class_loss_all (:150); one zero only, as in anchor_kernel
             cls_out[(size_t)b * N + a0 + lane] = cls;
             neg_out[(size_t)b * N + a0 + lane] = neg;
             s_poscls = (double)(cls * pos);
@@ -704,13 +704,61 @@ __global__ __launch_bounds__(LOSS_THREADS) void backward_stream_kernel(const flo
     }
 }
 
+// What a forward / backward call launches, decided in one place for the two launchers and ssdhip_loss_plan.  No HIP call in here.
+constexpr size_t LOSS_LDS_MAX = 140 * 1024;         // dynamic LDS of a tiled kernel (its static part, 1.2 KB, comes out of the same 160 KB)
+
+static size_t loss_tiled_lds(int TA, int L) { return 2 * (((size_t)TA * L + 4 + 3) / 4 * 4) * sizeof(float) + 16; }
+static_assert(2 * ((size_t)64 * (SSDHIP_LOSS_MAX_CLASSES + 12) + 4) * 4 + 16 <= LOSS_LDS_MAX &&
+              2 * ((size_t)64 * (SSDHIP_LOSS_MAX_CLASSES + 13) + 4) * 4 + 16 > LOSS_LDS_MAX, "SSDHIP_LOSS_MAX_CLASSES (ssdhip.h) is the largest C whose 64-anchor tiles fit");
+
+static bool loss_shape_ok(int B, int N, int C) {
+    return B > 0 && N > 0 && C >= 2 && C <= SSDHIP_LOSS_MAX_CLASSES && (long long)B * N <= 0x7ffffff0LL;
+}
+
+// every keep block repeats the last digit search: a few fat blocks per image (about a chip's worth in all), not one per 256 anchors
+static int keep_grid_x(int B, int N) {
+    int gx = (N + 4 * LOSS_THREADS - 1) / (4 * LOSS_THREADS);
+    while (gx > 1 && gx * B > 512) --gx;
+    return gx > KEEP_BLOCKS ? KEEP_BLOCKS : gx;
+}
+
+struct LossPlan {
+    LossWs lay;
+    int TA, gx;
+    size_t lds;                   // the tiled kernels' dynamic LDS
+    StreamPlan fwd, bwd;          // .ok: that direction streams (before the > 64 KB opt-in)
+};
+
+// grad_y_pred / keep_mask: only the backward's streaming form looks at them (NULL counts as aligned)
+static LossPlan loss_plan(const void* y_true, const void* y_pred, const void* grad_y_pred, const void* keep_mask, int B, int N, int C) {
+    LossPlan p;
+    p.lay = loss_ws_layout(B, N, C);
+    p.TA = loss_tile(C + 12);
+    p.lds = loss_tiled_lds(p.TA, C + 12);
+    p.gx = keep_grid_x(B, N);
+    p.fwd = stream_plan(y_true, y_pred, B, N, C, 0);
+    p.bwd = stream_plan(y_true, y_pred, B, N, C, 256);
+    if (((uintptr_t)grad_y_pred & 15u) || ((uintptr_t)keep_mask & 3u)) p.bwd.ok = 0;
+    return p;
+}
+
 }  // namespace ssdhip
 
 using namespace ssdhip;
 
 extern "C" size_t ssdhip_loss_workspace_bytes(int B, int N, int C) {
-    if (B <= 0 || N <= 0 || C < 2) return 0;
+    if (!loss_shape_ok(B, N, C)) return 0;
     return loss_ws_layout(B, N, C).total;
+}
+
+extern "C" int ssdhip_loss_plan(const void* y_true, const void* y_pred, const void* grad_y_pred, const void* keep_mask,
+                                int B, int N, int C, int* out) {
+    if (!out || !loss_shape_ok(B, N, C)) return SSDHIP_E_BADARG;
+    const LossPlan p = loss_plan(y_true, y_pred, grad_y_pred, keep_mask, B, N, C);
+    out[0] = p.fwd.ok; out[1] = p.bwd.ok; out[2] = p.TA;
+    out[3] = p.fwd.ok ? p.fwd.G : 0; out[4] = p.fwd.ok ? p.fwd.grid : 0; out[5] = p.fwd.ok ? p.fwd.nw : 0;
+    out[6] = p.lay.nblk; out[7] = p.gx;
+    return SSDHIP_OK;
 }
 
 extern "C" int ssdhip_loss_forward(const float* y_true, const float* y_pred, int B, int N, int C,
@@ -718,9 +766,9 @@ extern "C" int ssdhip_loss_forward(const float* y_true, const float* y_pred, int
                                    float* loss_per_item, float* stats, unsigned char* keep_mask,
                                    void* ws, size_t ws_bytes, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!y_true || !y_pred || !loss_per_item || !stats || !keep_mask || B <= 0 || N <= 0 || C < 2) return SSDHIP_E_BADARG;
-    if ((long long)B * N > 0x7ffffff0LL) return SSDHIP_E_BADARG;
-    const LossWs lay = loss_ws_layout(B, N, C);
+    if (!y_true || !y_pred || !loss_per_item || !stats || !keep_mask || !loss_shape_ok(B, N, C)) return SSDHIP_E_BADARG;
+    const LossPlan pl = loss_plan(y_true, y_pred, nullptr, nullptr, B, N, C);
+    const LossWs& lay = pl.lay;
     if (!ws || ws_bytes < lay.total) return SSDHIP_E_WORKSPACE;
     unsigned char* base = static_cast<unsigned char*>(ws);
     double* sums = reinterpret_cast<double*>(base + lay.sums);
@@ -733,18 +781,14 @@ extern "C" int ssdhip_loss_forward(const float* y_true, const float* y_pred, int
     unsigned short* bcol = reinterpret_cast<unsigned short*>(base + lay.bcol);
     if (zero_async(ghist, ((size_t)L1_SHARDS * L1_BINS + 2 * SEL_BINS + (size_t)B) * sizeof(u32), stream) != hipSuccess) return SSDHIP_E_LAUNCH;    // the three levels' bins + L3's arrival counters (sums are plain stores)
 
-    const int L = C + 12;
-    const int TA = loss_tile(L);
-    const size_t lds = 2 * (((size_t)TA * L + 4 + 3) / 4 * 4) * sizeof(float) + 16;
-    if (lds > 140 * 1024) return SSDHIP_E_BADARG;
-    const StreamPlan sp = stream_plan(y_true, y_pred, B, N, C, 0);
+    const StreamPlan& sp = pl.fwd;
     int part_tiles = lay.tiles;
     if (sp.ok && stream_big_lds(reinterpret_cast<const void*>(anchor_stream_kernel), 0, sp.lds)) {
         hipLaunchKernelGGL(anchor_stream_kernel, dim3(sp.grid), dim3(64 * sp.nw), sp.lds, stream, y_true, y_pred, B, N, C, sp.tiles64, sp.G,
                            cls, neg, part, ghist);
         part_tiles = sp.tiles64;
     } else {
-        hipLaunchKernelGGL(anchor_kernel, dim3(lay.tiles, B), dim3(TA), lds, stream, y_true, y_pred, B, N, C, cls, neg, part, ghist);
+        hipLaunchKernelGGL(anchor_kernel, dim3(lay.tiles, B), dim3(pl.TA), pl.lds, stream, y_true, y_pred, B, N, C, cls, neg, part, ghist);
     }
     if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
     const int total = B * N;
@@ -753,11 +797,7 @@ extern "C" int ssdhip_loss_forward(const float* y_true, const float* y_pred, int
     if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
     hipLaunchKernelGGL(sel_pass3_kernel, dim3(lay.nblk), dim3(SELP_THREADS), 0, stream, neg, total, ghist, sel, bcol);
     if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
-    // every keep block repeats the last digit search: a few fat blocks per image (about a chip's worth in all), not one per 256 anchors
-    int gx = (N + 4 * LOSS_THREADS - 1) / (4 * LOSS_THREADS);
-    while (gx > 1 && gx * B > 512) --gx;
-    if (gx > KEEP_BLOCKS) gx = KEEP_BLOCKS;
-    hipLaunchKernelGGL(keep_kernel, dim3(gx, B), dim3(LOSS_THREADS), 0, stream, cls, neg, B, N, ghist, lay.nblk, bcol, sel, stats, keep_mask,
+    hipLaunchKernelGGL(keep_kernel, dim3(pl.gx, B), dim3(LOSS_THREADS), 0, stream, cls, neg, B, N, ghist, lay.nblk, bcol, sel, stats, keep_mask,
                        keep_part, ghist + L1_SHARDS * L1_BINS + 2 * SEL_BINS, sums, alpha, loss_per_item);
     if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;
     return SSDHIP_OK;
@@ -767,18 +807,14 @@ extern "C" int ssdhip_loss_backward(const float* y_true, const float* y_pred, co
                                     const float* stats, const float* grad_out, int B, int N, int C, float alpha,
                                     float* grad_y_pred, void* stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (!y_true || !y_pred || !keep_mask || !stats || !grad_out || !grad_y_pred || B <= 0 || N <= 0 || C < 2) return SSDHIP_E_BADARG;
-    const int L = C + 12;
-    const int TA = loss_tile(L);
-    const size_t lds = 2 * (((size_t)TA * L + 4 + 3) / 4 * 4) * sizeof(float) + 16;
-    if (lds > 150 * 1024) return SSDHIP_E_BADARG;
-    const StreamPlan sp = stream_plan(y_true, y_pred, B, N, C, 256);
-    if (sp.ok && !((uintptr_t)grad_y_pred & 15u) && !((uintptr_t)keep_mask & 3u) &&
-        stream_big_lds(reinterpret_cast<const void*>(backward_stream_kernel), 1, sp.lds)) {
+    if (!y_true || !y_pred || !keep_mask || !stats || !grad_out || !grad_y_pred || !loss_shape_ok(B, N, C)) return SSDHIP_E_BADARG;
+    const LossPlan pl = loss_plan(y_true, y_pred, grad_y_pred, keep_mask, B, N, C);
+    const StreamPlan& sp = pl.bwd;
+    if (sp.ok && stream_big_lds(reinterpret_cast<const void*>(backward_stream_kernel), 1, sp.lds)) {
         hipLaunchKernelGGL(backward_stream_kernel, dim3(sp.grid), dim3(64 * sp.nw), sp.lds, stream, y_true, y_pred, keep_mask, stats, grad_out,
                            B, N, C, sp.tiles64, sp.G, alpha, grad_y_pred);
     } else {
-        hipLaunchKernelGGL(backward_kernel, dim3((N + TA - 1) / TA, B), dim3(TA), lds, stream, y_true, y_pred, keep_mask, stats, grad_out,
+        hipLaunchKernelGGL(backward_kernel, dim3(pl.lay.tiles, B), dim3(pl.TA), pl.lds, stream, y_true, y_pred, keep_mask, stats, grad_out,
                            B, N, C, alpha, grad_y_pred);
     }
     if (hipGetLastError() != hipSuccess) return SSDHIP_E_LAUNCH;

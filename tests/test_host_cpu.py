@@ -299,6 +299,18 @@ def test_entry_points_reject_bad_arguments_before_launching(lib):
     loss = lib.ssdhip_loss_forward
     assert loss(a, a, 2, 10, 6, 3, 0, 1.0, a, a, a, a, 16, None) == -2                      # SSDHIP_E_WORKSPACE: too small
     assert loss(a, a, 2, 10, 1, 3, 0, 1.0, a, a, a, a, 1 << 20, None) == -1                 # C < 2
+    # the largest C the header states (SSDHIP_LOSS_MAX_CLASSES): one more is refused by both directions, the plan and the workspace size
+    hdr = open(os.path.join(ROOT, "include", "ssdhip.h")).read()
+    cmax = int(re.search(r"#define\s+SSDHIP_LOSS_MAX_CLASSES\s+(\d+)", hdr).group(1))
+    back = lib.ssdhip_loss_backward
+    plan = (ctypes.c_int * 8)()
+    assert cmax >= 250
+    assert loss(a, a, 2, 10, cmax + 1, 3, 0, 1.0, a, a, a, a, 1 << 30, None) == -1
+    assert back(a, a, a, a, a, 2, 10, cmax + 1, 1.0, a, None) == -1
+    assert back(a, a, a, a, a, 2, 10, 1, 1.0, a, None) == -1
+    assert lib.ssdhip_loss_plan(a, a, a, a, 2, 10, cmax + 1, plan) == -1 and lib.ssdhip_loss_workspace_bytes(2, 10, cmax + 1) == 0
+    assert lib.ssdhip_loss_plan(a, a, a, a, 2, 10, cmax, plan) == 0 and plan[2] == 64 and lib.ssdhip_loss_workspace_bytes(2, 10, cmax) > 0
+    assert loss(a, a, 2, 10, cmax, 3, 0, 1.0, a, a, a, a, 16, None) == -2                   # accepted as far as the workspace check
 
 
 def test_optimizer_steps_refuse_bad_arguments_before_anything_runs(lib):
