@@ -271,6 +271,46 @@ int ssdhip_coco_accumulate(const int* det_pair, const double* det_score, const i
                            size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluator.predict_on_dataset's collection on the device (csrc/ssdhip_evalcollect.hip, restated in tests/np_eval_collect.py): from
+ * the decoder's output to the inputs of ssdhip_match_predictions_multi without a host copy of the rows.
+ *
+ * The store: store_rows [capacity, 6] of `dtype` (the rows' own), store_image [capacity] int32 (dataset index of each row's image) and
+ * counters [SSDHIP_EVAL_COUNTERS] int32: [SSDHIP_EVAL_N_ROWS] rows appended so far (the append offset), [SSDHIP_EVAL_BAD_CLASS] rows
+ * whose class lies outside 1 .. n_classes or whose image index lies outside 0 .. n_images - 1, [SSDHIP_EVAL_OVERFLOW] 1 once an append
+ * did not fit, [SSDHIP_EVAL_CLASS_COUNT + c - 1] rows of class c.  ssdhip_eval_store_reset zeroes the counters with a kernel.
+ *
+ * ssdhip_eval_collect appends the valid rows of rows [B, R, 6] ([class, conf, xmin, ymin, xmax, ymax], SSDHIP_F32 or SSDHIP_F64) in
+ * (image, row) order.  Row r of image b is valid iff r < count[b] (count [B] int32, the decoder's), or, with count == NULL, iff its
+ * class != 0 (the inference model's zero padding; such rows need not be a prefix).  desc [B, SSDHIP_EVAL_DESC] float64, per image:
+ * the dataset index, the number of steps (<= SSDHIP_EVAL_MAX_STEPS), then per step (op, a_y, a_x) -- op 0 scale: v = rint(v * T(a)),
+ * op 1 shift: v = v + T(a), the y pair with a_y and the x pair with a_x, in the rows' dtype T, applied in order.  Then
+ * v = rint(v * T(10^n)) / T(10^n) for the four coordinates (n = coord_decimals) and the confidence (n = conf_decimals); 0 leaves the
+ * value alone, n <= 9.  The append offset is advanced on the device: no host read between appends.  An append that does not fit
+ * `capacity` writes nothing at all and sets the overflow flag.  B <= 1024, n_classes <= SSDHIP_EVAL_MAX_CLASSES; ws: 2 B ints.
+ *
+ * ssdhip_eval_pack: a stable counting sort of the first n store rows by class -> pred [out_rows, 5] float32 (conf, xmin, ymin, xmax,
+ * ymax; float64 rows are cast), segment [out_rows] = slot * n_images + image, slot [out_rows] = class - 1, starts [n_classes + 1]:
+ * class by class, inside a class in store order.  Rows counted under SSDHIP_EVAL_BAD_CLASS are left out; out_rows >= the number of
+ * the others (the sum of the class counts), nothing is written at or past out_rows.  The result does not depend on scheduling.
+ * SSDHIP_E_BADARG, with nothing launched and every output untouched, for an unknown dtype, a null pointer, or a size outside the above. */
+#define SSDHIP_EVAL_MAX_CLASSES 128
+#define SSDHIP_EVAL_N_ROWS 0
+#define SSDHIP_EVAL_BAD_CLASS 1
+#define SSDHIP_EVAL_OVERFLOW 2
+#define SSDHIP_EVAL_CLASS_COUNT 4
+#define SSDHIP_EVAL_COUNTERS (SSDHIP_EVAL_CLASS_COUNT + SSDHIP_EVAL_MAX_CLASSES)
+#define SSDHIP_EVAL_MAX_STEPS 4
+#define SSDHIP_EVAL_DESC (2 + 3 * SSDHIP_EVAL_MAX_STEPS)
+#define SSDHIP_EVAL_PACK_CHUNK 256
+int ssdhip_eval_store_reset(int* counters, void* stream);
+int ssdhip_eval_collect(const void* rows, int dtype, int B, int R, const int* count, const double* desc, int n_images, int n_classes,
+                        int coord_decimals, int conf_decimals, void* store_rows, int* store_image, int capacity, int* counters, void* ws,
+                        size_t ws_bytes, void* stream);
+size_t ssdhip_eval_pack_workspace_bytes(int n, int n_classes);
+int ssdhip_eval_pack(const void* store_rows, int dtype, const int* store_image, int n, int n_images, int n_classes, float* pred,
+                     int* segment, int* slot, int* starts, int out_rows, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Graph glue between the convolutions (bf16 activations, NHWC = torch channels_last; C % 8 == 0; pointers
  * 16-byte aligned).  Each call is ONE pass over the tensor where the framework path runs 2-7 elementwise kernels.
  *

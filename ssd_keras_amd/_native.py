@@ -112,6 +112,10 @@ SIGNATURES = {
     "ssdhip_coco_match": (_I, [_P] * 3 + [_I] + [_P] * 4 + [_I, _I, _P, _I, _P, _I, _I] + [_P] * 8 + [_SZ, _P]),
     "ssdhip_coco_accumulate_workspace_bytes": (_SZ, [_I, _I]),
     "ssdhip_coco_accumulate": (_I, [_P] * 4 + [_I, _P, _P] + [_I] * 4 + [_P, _I, _I, _P, _I] + [_P] * 4 + [_SZ, _P]),
+    "ssdhip_eval_store_reset": (_I, [_P, _P]),
+    "ssdhip_eval_collect": (_I, [_P] + [_I] * 3 + [_P, _P] + [_I] * 4 + [_P, _P, _I, _P, _P, _SZ, _P]),
+    "ssdhip_eval_pack_workspace_bytes": (_SZ, [_I, _I]),
+    "ssdhip_eval_pack": (_I, [_P, _I, _P] + [_I] * 3 + [_P] * 4 + [_I, _P, _SZ, _P]),
     "ssdhip_bias_act_nhwc_bf16": (_I, [_P] * 3 + [_LL, _I, _I, _P]),
     "ssdhip_bias_act_maxpool_nhwc_bf16": (_I, [_P] * 3 + [_I] * 10 + [_P]),
     "ssdhip_l2_normalize_nhwc_bf16": (_I, [_P] * 3 + [_LL, _I, _P]),
@@ -2260,6 +2264,73 @@ def match_predictions_all(pred, pred_segment, pred_class, class_start, gt_boxes,
            float(matching_iou_threshold), BORDER[border_pixels], *[ctypes.c_void_p(out[i].data_ptr()) for i in range(5)], _ptr(ws),
            ws.numel())
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Evaluator.predict_on_dataset's collection on the device (csrc/ssdhip_evalcollect.hip)
+# ------------------------------------------------------------------------------------------------
+EVAL_MAX_CLASSES, EVAL_MAX_STEPS, EVAL_PACK_CHUNK = 128, 4, 256                       # include/ssdhip.h's SSDHIP_EVAL_*
+EVAL_N_ROWS, EVAL_BAD_CLASS, EVAL_OVERFLOW, EVAL_CLASS_COUNT = 0, 1, 2, 4
+EVAL_COUNTERS, EVAL_DESC = EVAL_CLASS_COUNT + EVAL_MAX_CLASSES, 2 + 3 * EVAL_MAX_STEPS
+EVAL_SCALE, EVAL_SHIFT = 0, 1
+
+
+def eval_store_reset(counters):
+    """Zero a store's counters (int32 [EVAL_COUNTERS]) with a kernel."""
+    require_cuda(counters, "counters")
+    launch("ssdhip_eval_store_reset", counters.device, _ptr(counters))
+
+
+def eval_collect(rows, count, desc, n_images, n_classes, coord_decimals, conf_decimals, store_rows, store_image, counters, capacity=None):
+    """Append the valid rows of one batch to a store (ssdhip_eval_collect; nothing is read back).  CUDA tensors: rows (B, R, 6) float32
+    or float64, count (B,) int32 or None (then: class != 0), desc (B, EVAL_DESC) float64, store_rows (>= capacity, 6) of the rows'
+    dtype, store_image (>= capacity,) int32, counters (EVAL_COUNTERS,) int32."""
+    torch = _torch()
+    for t, name in ((rows, "rows"), (desc, "desc"), (store_rows, "store_rows"), (store_image, "store_image"), (counters, "counters")):
+        require_cuda(t, name)
+    if rows.dtype not in (torch.float32, torch.float64) or store_rows.dtype != rows.dtype or rows.dim() != 3 or rows.shape[2] != 6:
+        raise SsdHipError("rows must be (B, R, 6) float32 or float64, and the store of the same dtype")
+    B, R = int(rows.shape[0]), int(rows.shape[1])
+    if (desc.dtype != torch.float64 or tuple(desc.shape) != (B, EVAL_DESC) or store_image.dtype != torch.int32 or counters.dtype != torch.int32
+            or counters.numel() < EVAL_COUNTERS or (count is not None and (count.dtype != torch.int32 or count.numel() != B))):
+        raise SsdHipError("eval_collect: desc (B, %d) float64, store_image / counters / count int32" % EVAL_DESC)
+    cap = int(store_rows.shape[0]) if capacity is None else int(capacity)
+    if cap > min(int(store_rows.shape[0]), int(store_image.shape[0])):
+        raise SsdHipError("eval_collect: capacity %d exceeds the store" % cap)
+    dev = rows.device
+    ws = workspaces.get(dev, "eval_collect", 8 * 1024)
+    launch("ssdhip_eval_collect", dev, _ptr(rows), F32 if rows.dtype == torch.float32 else F64, B, R, _ptr(count), _ptr(desc), int(n_images),
+           int(n_classes), int(coord_decimals), int(conf_decimals), _ptr(store_rows), _ptr(store_image), cap, _ptr(counters), _ptr(ws),
+           ws.numel())
+
+
+def eval_pack(store_rows, store_image, n, n_images, n_classes, out_rows=None, outputs=None):
+    """The matcher's inputs from the first `n` rows of a store (ssdhip_eval_pack): (pred (out_rows, 5) float32, segment, slot
+    (out_rows,) int32, starts (n_classes + 1,) int32), class by class and in store order inside a class."""
+    torch = _torch()
+    lib = load()
+    require_cuda(store_rows, "store_rows")
+    require_cuda(store_image, "store_image")
+    if store_rows.dtype not in (torch.float32, torch.float64) or store_image.dtype != torch.int32:
+        raise SsdHipError("eval_pack: store_rows float32 or float64, store_image int32")
+    n = int(n)
+    if n > min(int(store_rows.shape[0]), int(store_image.shape[0])):
+        raise SsdHipError("eval_pack: n = %d exceeds the store" % n)
+    dev = store_rows.device
+    out_rows = n if out_rows is None else int(out_rows)
+    if outputs is None:
+        outputs = (torch.empty((out_rows, 5), dtype=torch.float32, device=dev), torch.empty((out_rows,), dtype=torch.int32, device=dev),
+                   torch.empty((out_rows,), dtype=torch.int32, device=dev), torch.empty((int(n_classes) + 1,), dtype=torch.int32, device=dev))
+    pred, segment, slot, starts = outputs
+    if min(int(pred.shape[0]), int(segment.shape[0]), int(slot.shape[0])) < out_rows or int(starts.shape[0]) < int(n_classes) + 1:
+        raise SsdHipError("eval_pack: outputs smaller than out_rows / n_classes + 1")
+    need = lib.ssdhip_eval_pack_workspace_bytes(n, int(n_classes))
+    if need == 0:
+        raise SsdHipError("eval_pack: unsupported n = %d, n_classes = %d" % (n, n_classes))
+    ws = workspaces.get(dev, "eval_pack", need)
+    launch("ssdhip_eval_pack", dev, _ptr(store_rows), F32 if store_rows.dtype == torch.float32 else F64, _ptr(store_image), n, int(n_images),
+           int(n_classes), _ptr(pred), _ptr(segment), _ptr(slot), _ptr(starts), out_rows, _ptr(ws), ws.numel())
+    return pred, segment, slot, starts
 
 
 # ------------------------------------------------------------------------------------------------

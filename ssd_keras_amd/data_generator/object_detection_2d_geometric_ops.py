@@ -52,6 +52,7 @@ class Resize:
             labels[:, [ymin + 1, ymax + 1]] = np.round(labels[:, [ymin + 1, ymax + 1]] * (img_height / out_h), decimals=0)
             labels[:, [xmin + 1, xmax + 1]] = np.round(labels[:, [xmin + 1, xmax + 1]] * (img_width / out_w), decimals=0)
             return labels
+        inverter.step = ('scale', img_height / out_h, img_width / out_w, (xmin + 1, ymin + 1, xmax + 1, ymax + 1))
 
         if labels is None:
             return (image, inverter) if return_inverter else image

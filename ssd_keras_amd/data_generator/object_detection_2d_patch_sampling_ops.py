@@ -92,6 +92,9 @@ def _identity_inverter(labels):
     return labels
 
 
+_identity_inverter.step = ('identity',)
+
+
 class CropPad:
     '''Crops and/or pads an image deterministically: the output is the `patch_height` x `patch_width` window whose top left corner
     sits at (`patch_ymin`, `patch_xmin`) of the image's coordinate system; what lies outside the image is `background`
@@ -142,6 +145,7 @@ class CropPad:
             predictions[:, [ymin + 1, ymax + 1]] += top
             predictions[:, [xmin + 1, xmax + 1]] += left
             return predictions
+        inverter.step = ('shift', top, left, (xmin + 1, ymin + 1, xmax + 1, ymax + 1))
 
         if labels is None:
             return (patch, inverter) if return_inverter else patch

@@ -16,7 +16,10 @@ Same constructor, method names, keyword arguments and attributes as the referenc
     cumulative lists one entry short, :616-620, and `compute_precision_recall` raises IndexError or mis-assigns classes);
   * `data_generator` is any object with `labels`, `image_ids`, `eval_neutral` (and, for `predict_on_dataset`, a
     `generate(...)` / `get_dataset_size()` pair with the reference generator's contract) -- the reference's own image
-    pipeline is outside this package.
+    pipeline is outside this package (SURVEY section 8);
+  * `predict_on_dataset` / `__call__` take `collect='host'` (the reference's loop, the default) or `'device'`, which keeps the
+    predictions on the GPU from the decoder to the matcher (csrc/ssdhip_evalcollect.hip); `prediction_results` is a property so that
+    the device route can build the lists on first read, and assigning to it (or `forget_packed_inputs()`) drops the device copy.
 """
 from __future__ import annotations
 
@@ -26,6 +29,99 @@ from math import ceil
 import numpy as np
 
 from .. import _native as nat
+
+
+class _DeviceCollection:
+    """`predict_on_dataset(collect='device')`'s store: the valid rows of every batch, inverted and rounded, in (image, row) order on
+    the device (csrc/ssdhip_evalcollect.hip).  Allocated at the first batch (`n_images x rows per image` rows of the rows' dtype);
+    nothing is read back before `finish()`."""
+
+    def __init__(self, n_classes, image_ids, index_of, round_confidences):
+        if n_classes > nat.EVAL_MAX_CLASSES:
+            raise ValueError("`collect='device'` handles up to {} classes.".format(nat.EVAL_MAX_CLASSES))
+        if round_confidences and not (isinstance(round_confidences, (int, np.integer)) and 0 < round_confidences <= 9):
+            raise ValueError("`collect='device'` rounds confidences to 1 .. 9 decimals.")
+        self.n_classes, self.image_ids, self.index_of = n_classes, image_ids, index_of
+        self.conf_decimals = int(round_confidences) if round_confidences else 0
+        self.rows = self.image = self.counters = None
+
+    @staticmethod
+    def program(inverters):
+        """An image's inverters (applied in order, `None` skipped) as the kernel's steps [(op, a_y, a_x)], from the `step` each of the
+        package's inverter closures carries: ('scale', s_y, s_x, columns), ('shift', d_y, d_x, columns) or ('identity',)."""
+        steps = []
+        for inverter in (inverters or []):
+            if inverter is None:
+                continue
+            step = getattr(inverter, 'step', None)
+            if step is None:
+                raise ValueError("`collect='device'` needs inverters that describe their step (the package's own transforms do), "
+                                 "but received {!r}.".format(inverter))
+            if step[0] == 'identity':
+                continue
+            kind, a_y, a_x, columns = step
+            if tuple(columns) != (2, 3, 4, 5):
+                raise ValueError("`collect='device'` needs inverters on the columns xmin, ymin, xmax, ymax = 2, 3, 4, 5.")
+            if kind == 'shift' and not (int(a_y) == a_y and int(a_x) == a_x and abs(a_y) < 2 ** 24 and abs(a_x) < 2 ** 24):
+                raise ValueError("`collect='device'` shifts by whole pixels.")
+            steps.append((nat.EVAL_SCALE if kind == 'scale' else nat.EVAL_SHIFT, float(a_y), float(a_x)))
+        if len(steps) > nat.EVAL_MAX_STEPS:
+            raise ValueError("`collect='device'` applies at most {} inverse steps per image.".format(nat.EVAL_MAX_STEPS))
+        return steps
+
+    def append(self, out, count, batch_image_ids, programs):
+        import torch
+        B, R = int(out.shape[0]), int(out.shape[1])
+        if len(batch_image_ids) != B or len(programs) != B:
+            raise ValueError("the batch has {} predictions for {} images".format(B, len(batch_image_ids)))
+        if self.rows is None:
+            capacity = max(1, len(self.image_ids) * R)
+            self.rows = torch.empty((capacity, 6), dtype=out.dtype, device=out.device)
+            self.image = torch.empty((capacity,), dtype=torch.int32, device=out.device)
+            self.counters = torch.empty((nat.EVAL_COUNTERS,), dtype=torch.int32, device=out.device)
+            nat.eval_store_reset(self.counters)
+        desc = np.zeros((B, nat.EVAL_DESC), dtype=np.float64)
+        for b, (image_id, steps) in enumerate(zip(batch_image_ids, programs)):
+            desc[b, 0], desc[b, 1] = self.index_of[str(image_id)], len(steps)
+            for k, step in enumerate(steps):
+                desc[b, 2 + 3 * k:5 + 3 * k] = step
+        nat.eval_collect(out, count, nat.to_device(desc, device=out.device), len(self.image_ids), self.n_classes, 1, self.conf_decimals,
+                         self.rows, self.image, self.counters)
+
+    def finish(self):
+        """ONE read of the counters, the refusals, the pack -> the memo `_packed_predictions` returns (plus `to_lists`, which builds
+        `prediction_results` from one download of the store)."""
+        import torch
+        n_classes, n_images = self.n_classes, len(self.image_ids)
+        if self.rows is None:                                      # a dataset without a batch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            self.rows, self.image = torch.empty((1, 6), dtype=torch.float64, device=dev), torch.empty((1,), dtype=torch.int32, device=dev)
+            counters = np.zeros((nat.EVAL_COUNTERS,), dtype=np.int64)
+        else:
+            counters = self.counters.cpu().numpy().astype(np.int64)
+        if counters[nat.EVAL_BAD_CLASS]:
+            raise IndexError("list index out of range")            # the host route's `results[class_id]`
+        if counters[nat.EVAL_OVERFLOW]:
+            raise RuntimeError("the device store of {} rows is full: the model returned more rows for an image than for the first "
+                               "batch's".format(int(self.rows.shape[0])))
+        n = int(counters[nat.EVAL_N_ROWS])
+        per_class = counters[nat.EVAL_CLASS_COUNT:nat.EVAL_CLASS_COUNT + n_classes]
+        starts = np.concatenate([[0], np.cumsum(per_class)]).astype(np.int64)
+        assert int(starts[-1]) == n, (starts, n)
+        pred, segment, slot, starts_dev = nat.eval_pack(self.rows, self.image, n, max(1, n_images), n_classes)
+        rows, image, image_ids = self.rows, self.image, self.image_ids
+
+        def to_lists():
+            table, index = rows[:n].cpu().numpy(), image[:n].cpu().numpy()
+            classes = table[:, 0].astype(np.int64)
+            results = [list()]
+            for class_id in range(1, n_classes + 1):
+                mine = np.flatnonzero(classes == class_id)
+                part = table[mine]
+                results.append(list(zip([image_ids[i] for i in index[mine]], *(part[:, j] for j in range(1, 6)))))
+            return results
+
+        return {"starts_host": starts, "pred": pred, "segment": segment, "slot": slot, "starts": starts_dev, "to_lists": to_lists}
 
 
 class Evaluator:
@@ -57,13 +153,13 @@ class Evaluator:
                  average_precision_mode='sample', num_recall_points=11, ignore_neutral_boxes=True, return_precisions=False,
                  return_recalls=False, return_average_precisions=False, verbose=True, decoding_confidence_thresh=0.01,
                  decoding_iou_threshold=0.45, decoding_top_k=200, decoding_pred_coords='centroids',
-                 decoding_normalize_coords=True):
+                 decoding_normalize_coords=True, collect='host'):
         '''Reference :94-256: the whole evaluation in one call.  Returns the mean average precision and, optionally, the
-        average precisions, precisions and recalls (in that order, as the reference does).'''
+        average precisions, precisions and recalls (in that order, as the reference does).  `collect`: see `predict_on_dataset`.'''
         # the five stages, each leaving its result on the instance exactly as the stand-alone methods do
         self.predict_on_dataset(img_height, img_width, batch_size, data_generator_mode, decoding_confidence_thresh,
                                 decoding_iou_threshold, decoding_top_k, decoding_pred_coords, decoding_normalize_coords,
-                                border_pixels, round_confidences, verbose)
+                                border_pixels, round_confidences, verbose, collect=collect)
         self.get_num_gt_per_class(ignore_neutral_boxes, verbose=False)
         self.match_predictions(ignore_neutral_boxes, matching_iou_threshold, border_pixels, sorting_algorithm, verbose)
         self.compute_precision_recall(verbose)
@@ -77,18 +173,31 @@ class Evaluator:
     def predict_on_dataset(self, img_height, img_width, batch_size, data_generator_mode='resize',
                            decoding_confidence_thresh=0.01, decoding_iou_threshold=0.45, decoding_top_k=200,
                            decoding_pred_coords='centroids', decoding_normalize_coords=True, decoding_border_pixels='include',
-                           round_confidences=False, verbose=True, ret=False):
+                           round_confidences=False, verbose=True, ret=False, collect='host'):
         '''Reference :258-424: run the model over `data_generator` and collect, per class, the tuples
         `(image_id, confidence, xmin, ymin, xmax, ymax)`.  The generator must honour the reference's `generate(batch_size,
         shuffle=False, transformations=..., label_encoder=None, returns={...}, keep_images_without_gt=True,
         degenerate_box_handling='remove')` contract (data_generator/object_detection_2d_data_generator.py's `DataGenerator`);
         `transformations` are the reference's lists (:320-330): `[ConvertTo3Channels, Resize]` for 'resize', `[ConvertTo3Channels,
-        RandomPadFixedAR, Resize]` for 'pad'.'''
+        RandomPadFixedAR, Resize]` for 'pad'.
+
+        `collect` (not in the reference): 'host' is the reference's loop.  'device' keeps everything between the generator and the
+        matcher on the GPU: the package's `DataGenerator` yields the batch on the device, the decoder's `(out, count)` stay there,
+        `ssdhip_eval_collect` applies each image's inverse transforms and the rounding and appends the rows to a device store, and
+        `ssdhip_eval_pack` turns the store into `match_predictions`' inputs; `prediction_results` is then built from one download
+        when it is first read, equal to the host route's element for element and type for type.  The model is fed the device batch
+        converted to float32 there -- the tensor the host route uploads --, so its output is the same bits.  'device' raises
+        ValueError for a generator that is not the package's `DataGenerator`, for `decoding_top_k='all'` in mode 'training', and
+        for an inverter that does not describe its step; IndexError where the host route raises it (a class beyond `n_classes`;
+        also for a class below 1, which the host route files under `results[class_id]`); RuntimeError if more rows arrive than
+        `n_images x rows per image`.'''
         import torch
         from ..data_generator.object_detection_2d_geometric_ops import Resize
         from ..data_generator.object_detection_2d_patch_sampling_ops import RandomPadFixedAR
         from ..data_generator.object_detection_2d_photometric_ops import ConvertTo3Channels
         from ..ssd_encoder_decoder.ssd_output_decoder import decode_detections
+        if collect not in ('host', 'device'):
+            raise ValueError("`collect` can be either of 'host' or 'device', but received '{}'.".format(collect))
         if data_generator_mode == 'resize':
             transformations = [ConvertTo3Channels(), Resize(height=img_height, width=img_width, labels_format=self.gt_format)]
         elif data_generator_mode == 'pad':
@@ -96,12 +205,15 @@ class Evaluator:
                                Resize(height=img_height, width=img_width, labels_format=self.gt_format)]
         else:
             raise ValueError("`data_generator_mode` can be either of 'resize' or 'pad', but received '{}'.".format(data_generator_mode))
-        pf = self.pred_format
+        on_device = collect == 'device'
+        if on_device:
+            self._check_device_collect(decoding_top_k)
         generator = self.data_generator.generate(batch_size=batch_size, shuffle=False, transformations=transformations,
                                                  label_encoder=None,
                                                  returns={'processed_images', 'image_ids', 'evaluation-neutral', 'inverse_transform',
                                                           'original_labels'},
-                                                 keep_images_without_gt=True, degenerate_box_handling='remove')
+                                                 keep_images_without_gt=True, degenerate_box_handling='remove',
+                                                 **({'device': torch.device('cuda', torch.cuda.current_device())} if on_device else {}))
         if self.data_generator.image_ids is None:
             self.data_generator.image_ids = list(range(self.data_generator.get_dataset_size()))
         results = [list() for _ in range(self.n_classes + 1)]
@@ -109,9 +221,22 @@ class Evaluator:
         n_batches = int(ceil(n_images / batch_size))
         if verbose:
             print("Number of images in the evaluation dataset: {}".format(n_images))
+        store = _DeviceCollection(self.n_classes, self.data_generator.image_ids, self._image_index(), round_confidences) if on_device else None
         for _ in range(n_batches):
             batch_X, batch_image_ids, _neutral, batch_inverse_transforms, _orig = next(generator)
             predict = getattr(self.model, 'predict', self.model)
+            if on_device:
+                programs = [store.program(inverters) for inverters in (batch_inverse_transforms or [[]] * len(batch_image_ids))]
+                with torch.no_grad():
+                    y_pred = predict(batch_X.to(torch.float32))          # what the host route feeds, converted where the batch is
+                if self.model_mode == 'training':
+                    out, count = self._decode_on_device(y_pred, decoding_confidence_thresh, decoding_iou_threshold, decoding_top_k,
+                                                        decoding_pred_coords, decoding_normalize_coords, img_height, img_width,
+                                                        decoding_border_pixels)
+                else:
+                    out, count = y_pred.float().contiguous(), None           # zero padding: rows of class 0 (:395-398)
+                store.append(out, count, batch_image_ids, programs)
+                continue
             with torch.no_grad():
                 y_pred = predict(batch_X if torch.is_tensor(batch_X) else torch.as_tensor(np.asarray(batch_X), dtype=torch.float32).cuda())
             if self.model_mode == 'training':
@@ -122,18 +247,68 @@ class Evaluator:
             else:
                 y_pred = y_pred.float().cpu().numpy()
                 y_pred = [y_pred[i][y_pred[i, :, 0] != 0] for i in range(len(y_pred))]       # drop the zero padding (:395-398)
-            if batch_inverse_transforms is not None:                                          # apply_inverse_transforms (:401)
-                y_pred = [self._invert(np.copy(y_pred[i]), batch_inverse_transforms[i]) for i in range(len(y_pred))]
-            for k, batch_item in enumerate(y_pred):
-                image_id = batch_image_ids[k]
-                for box in batch_item:
-                    class_id = int(box[pf['class_id']])
-                    confidence = round(box[pf['conf']], round_confidences) if round_confidences else box[pf['conf']]
-                    results[class_id].append((image_id, confidence, round(box[pf['xmin']], 1), round(box[pf['ymin']], 1),
-                                              round(box[pf['xmax']], 1), round(box[pf['ymax']], 1)))
-        self.prediction_results = results
+            self._collect_batch(results, y_pred, batch_image_ids, batch_inverse_transforms, round_confidences)
+        if on_device:
+            self.prediction_results = None
+            self.__dict__["_device_collection"] = store.finish()     # raises for an out-of-range class or an overflow
+        else:
+            self.prediction_results = results
         if ret:
-            return results
+            return self.prediction_results
+
+    def _collect_batch(self, results, y_pred, batch_image_ids, batch_inverse_transforms, round_confidences):
+        """The host route's work on one batch (reference :401-424): `y_pred` -- per image the (k, 6) array of its valid rows -- through
+        the images' inverters, rounded, and appended to the per-class lists `results`."""
+        pf = self.pred_format
+        if batch_inverse_transforms is not None:                                          # apply_inverse_transforms (:401)
+            y_pred = [self._invert(np.copy(y_pred[i]), batch_inverse_transforms[i]) for i in range(len(y_pred))]
+        for k, batch_item in enumerate(y_pred):
+            image_id = batch_image_ids[k]
+            for box in batch_item:
+                class_id = int(box[pf['class_id']])
+                confidence = round(box[pf['conf']], round_confidences) if round_confidences else box[pf['conf']]
+                results[class_id].append((image_id, confidence, round(box[pf['xmin']], 1), round(box[pf['ymin']], 1),
+                                          round(box[pf['xmax']], 1), round(box[pf['ymax']], 1)))
+
+    _DEVICE_PRED_FORMAT = {'class_id': 0, 'conf': 1, 'xmin': 2, 'ymin': 3, 'xmax': 4, 'ymax': 5}
+
+    def _check_device_collect(self, decoding_top_k):
+        """What `collect='device'` refuses, before anything runs."""
+        from ..data_generator.object_detection_2d_data_generator import DataGenerator
+        if not isinstance(self.data_generator, DataGenerator):
+            raise ValueError("`collect='device'` needs this package's `DataGenerator` (its `generate(..., device=...)` and the step "
+                             "descriptions of its inverters), but received a {}.".format(type(self.data_generator).__name__))
+        if self.model_mode == 'training' and (decoding_top_k == 'all' or int(decoding_top_k) < 1):
+            raise ValueError("`collect='device'` needs a fixed number of rows per image: `decoding_top_k='all'` is the host route's.")
+        if dict(self.pred_format) != self._DEVICE_PRED_FORMAT:
+            raise ValueError("`collect='device'` reads predictions as [class_id, conf, xmin, ymin, xmax, ymax].")
+
+    @staticmethod
+    def _decode_on_device(y_pred, confidence_thresh, iou_threshold, top_k, input_coords, normalize_coords, img_height, img_width,
+                          border_pixels):
+        """`decode_detections` up to its download: the decoder's float64 rows (B, top_k, 6) and count (B,), still on the device."""
+        from ..ssd_encoder_decoder import ssd_output_decoder as dec
+        y = dec._as_device(y_pred)
+        dec._check_common(y, normalize_coords, img_height, img_width, input_coords)
+        k = int(top_k)
+        out, count, _ = nat.decode(y, confidence_thresh, iou_threshold, k, 0, False, nat.SEM_NUMPY, input_coords, normalize_coords,
+                                   img_height, img_width, border_pixels, nat.F64, k)
+        return out, count
+
+    @property
+    def prediction_results(self):
+        """Per-class lists of `(image_id, confidence, xmin, ymin, xmax, ymax)` (entry 0: the background dummy).  After a device
+        collection they are built here, on the first read, from one download of the store.  Assigning drops the device copy."""
+        results = self.__dict__.get("_prediction_results")
+        store = self.__dict__.get("_device_collection")
+        if results is None and store is not None:
+            results = self.__dict__["_prediction_results"] = store["to_lists"]()
+        return results
+
+    @prediction_results.setter
+    def prediction_results(self, value):
+        self.__dict__["_prediction_results"] = value
+        self.__dict__.pop("_device_collection", None)
 
     @staticmethod
     def _invert(boxes, inverters):
@@ -185,7 +360,7 @@ class Evaluator:
         `cumulative_*` are their running sums.'''
         if self.data_generator.labels is None:
             raise ValueError("Matching predictions to ground truth boxes not possible, no ground truth given.")
-        if self.prediction_results is None:
+        if self.__dict__.get("_device_collection") is None and self.prediction_results is None:
             raise ValueError("There are no prediction results. You must run `predict_on_dataset()` before calling this method.")
         if border_pixels not in nat.BORDER:
             raise ValueError("`border_pixels` must be one of 'half', 'include' and 'exclude'")
@@ -229,6 +404,8 @@ class Evaluator:
     #      edits those lists IN PLACE without changing a length calls `forget_packed_inputs()`. --------------------------------------------
     def forget_packed_inputs(self):
         """Drop the device copies of the predictions and the ground truth (rebuilt by the next `match_predictions`)."""
+        if self.__dict__.get("_device_collection") is not None:
+            self.prediction_results = self.prediction_results    # keep the lists (built now if they never were), drop the device copy
         for name in ("_packed_pred_memo", "_packed_gt_memo", "_image_index_memo"):
             self.__dict__.pop(name, None)
 
@@ -242,6 +419,9 @@ class Evaluator:
 
     def _packed_predictions(self):
         import torch
+        collected = self.__dict__.get("_device_collection")
+        if collected is not None:                                 # predict_on_dataset(collect='device') packed them on the device
+            return collected
         results = self.prediction_results
         sig = (id(results), tuple(len(r) for r in results), id(self.data_generator.image_ids))
         memo = self.__dict__.get("_packed_pred_memo")

@@ -49,7 +49,7 @@ from . import _native as nat
 from .optimizers import _bump_versions
 
 __all__ = ["fit_generator", "regularized_param_groups", "Callback", "History", "ModelCheckpoint", "CSVLogger", "EarlyStopping",
-           "ReduceLROnPlateau", "LearningRateScheduler", "TerminateOnNaN"]
+           "ReduceLROnPlateau", "LearningRateScheduler", "TerminateOnNaN", "MeanAveragePrecision"]
 
 
 # ---- callbacks (keras/callbacks.py, Keras 2.2.4) ----------------------------------------------------------------------------------
@@ -335,6 +335,57 @@ class TerminateOnNaN(Callback):
         self.model.stop_training = True
 
 
+class MeanAveragePrecision(Callback):
+    """Not in Keras: the Pascal VOC mean average precision of the model on `data_generator` (a `DataGenerator` with labels) as
+    `logs[name]`, a Python float, every `period` epochs; on the other epochs the key is not set (a `ModelCheckpoint(save_best_only=True)`
+    or `EarlyStopping` monitoring it then warns and skips that epoch, as Keras does for a missing monitor -- give them the same period;
+    a `CSVLogger` takes its columns from the first epoch's keys, as Keras's does, so it logs the key only with `period=1`).
+    It must come before the callbacks that monitor it: callbacks run in list order and each sees what the ones before it put into
+    `logs`.  `fit_generator` itself runs it ahead of its `History`, so `history.history[name]` has one entry per evaluated epoch.
+
+    `on_epoch_end` puts the model in `eval()`, calls an `Evaluator(model, n_classes, data_generator, model_mode='training')` -- built
+    once, so the packed ground truth is reused -- with `collect` ('device': nothing between the decoder and the matcher leaves the GPU)
+    and `evaluator_kwargs` (`data_generator_mode`, `average_precision_mode`, `decoding_*`, ...; `verbose` defaults to False), and puts
+    `train()` back.  `fit_generator` has called its `settle()` by then, so the tensors the model derives for its inference path follow
+    the replayed weights.  Training is not disturbed: the evaluation runs under `no_grad` in `eval()` (BatchNorm's statistics and
+    `optimizer.iterations` do not move, no captured graph is touched), and the states of `np.random` and `random` -- which the 'pad'
+    mode's transformations draw from -- are put back."""
+
+    provides_logs = True
+
+    def __init__(self, data_generator, n_classes, img_height, img_width, batch_size, period=1, name="val_mAP", collect="device",
+                 **evaluator_kwargs):
+        super().__init__()
+        if period < 1:
+            raise ValueError("period must be at least 1")
+        self.data_generator, self.n_classes = data_generator, n_classes
+        self.img_height, self.img_width, self.batch_size = img_height, img_width, batch_size
+        self.period, self.name, self.collect = period, name, collect
+        self.evaluator_kwargs = dict(evaluator_kwargs)
+        self.evaluator_kwargs.setdefault("verbose", False)
+        self.evaluator = None
+
+    def on_epoch_end(self, epoch, logs=None):
+        if (epoch + 1) % self.period:
+            return
+        import random
+        from .eval_utils.average_precision_evaluator import Evaluator
+        model = self.model
+        if self.evaluator is None or self.evaluator.model is not model:
+            self.evaluator = Evaluator(model, self.n_classes, self.data_generator, model_mode="training")
+        was_training = model.training
+        states = np.random.get_state(), random.getstate()
+        model.eval()
+        try:
+            value = self.evaluator(self.img_height, self.img_width, self.batch_size, collect=self.collect, **self.evaluator_kwargs)
+        finally:
+            model.train(was_training)
+            np.random.set_state(states[0])
+            random.setstate(states[1])
+        if logs is not None:
+            logs[self.name] = float(value)
+
+
 # ---- the loop ----------------------------------------------------------------------------------------------------------------------
 def _conv_kernels(model):
     return [m.weight for m in model.modules() if isinstance(m, nn.Conv2d)]
@@ -576,7 +627,8 @@ def fit_generator(model, generator, steps_per_epoch, epochs=1, *, optimizer, los
     Per epoch, from `initial_epoch` to `epochs - 1`: `on_epoch_begin(epoch)`, `steps_per_epoch` steps, `validation_steps` validation
     steps (`model.eval()`, `no_grad`, their own capture and meter; BatchNorm's statistics are untouched and the model is put back in
     `train()`), `on_epoch_end(epoch, logs)` with `loss = sum / seen` of the meter, `val_loss` likewise (penalty included), and `lr`
-    where a learning-rate callback adds it.  `History` runs first, then `callbacks` in order; it is returned.
+    where a learning-rate callback adds it.  `History` runs first, then `callbacks` in order; it is returned.  Only a callback that
+    declares `provides_logs` (`MeanAveragePrecision`) runs ahead of `History`, so that its key is in `history.history`.
 
     With a `TerminateOnNaN` among the callbacks the meter is read every `nan_poll` steps; on a latched non-finite loss the loop stops
     there -- up to `nan_poll - 1` further updates have then been applied to weights that are already non-finite; Keras does not undo
@@ -592,7 +644,9 @@ def fit_generator(model, generator, steps_per_epoch, epochs=1, *, optimizer, los
     loop = _Loop(model, optimizer, loss, graph)
     _check_penalty_gradient(model, optimizer)
     history = History()
-    cbs = [history] + list(callbacks or [])
+    callbacks = list(callbacks or [])
+    metrics = [cb for cb in callbacks if getattr(cb, "provides_logs", False)]      # (MeanAveragePrecision: its key is part of the History)
+    cbs = metrics + [history] + [cb for cb in callbacks if cb not in metrics]
     terminators = [cb for cb in cbs if isinstance(cb, TerminateOnNaN)]
     params = {"epochs": epochs, "steps": steps_per_epoch, "verbose": verbose, "do_validation": validation_data is not None,
               "metrics": ["loss"] + (["val_loss"] if validation_data is not None else [])}
