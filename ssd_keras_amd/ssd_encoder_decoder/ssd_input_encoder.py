@@ -219,11 +219,13 @@ class SSDInputEncoder:
     def encode_packed(self, gt_d, off_d, n_gt, max_gt_per_image, batch_size, want_f32=True, want_f64=False, want_matches=False):
         '''The encoder kernels on labels that are ALREADY on the GPU in CSR form (e.g. produced by a device-side input pipeline):
         `gt_d` float64 (n_gt, 5) rows `[class, xmin, ymin, xmax, ymax]` of all images concatenated, `off_d` int32 (batch + 1,)
-        row offsets.  No host work, no PCIe traffic, nothing but `ssdhip_encode`'s two launches on the current stream; the caller
-        vouches for the checks `encode_to_device` makes on the host (no degenerate boxes, class ids in range, <= 1024 boxes per
-        image).  `max_gt_per_image` must be an UPPER bound of the per-image box counts in `off_d`: the kernels size their tables
-        with it and ignore an image's boxes beyond it (they never index past the tables; the targets of such an image are then
-        wrong, not the memory).  Returns (y_f32 | None, y_f64 | None, match_gt | None).'''
+        row offsets.  No host work, no PCIe traffic, nothing but `ssdhip_encode`'s three launches (one when the batch has no box
+        at all) on the current stream; the caller vouches for the checks `encode_to_device` makes on the host (no degenerate
+        boxes, class ids in range, <= 1024 boxes per image).  `max_gt_per_image` must be an UPPER bound of the per-image box
+        counts in `off_d`, at most `n_gt`: the kernels size their tables with it, and any upper bound gives the same bits.  With a
+        smaller bound every kernel takes `min(count, max_gt_per_image)` boxes of an image: an image with more is encoded from its
+        FIRST `max_gt_per_image` boxes alone, as if the others were not there; the other images and the memory around the
+        outputs are unaffected.  Returns (y_f32 | None, y_f64 | None, match_gt | None).'''
         import torch
         lib = nat.load()
         device = off_d.device

@@ -546,6 +546,34 @@ def gen_encoder():
     save("encoder", **out)
 
 
+def gen_encoder_edges():
+    """The reference's encoder on the tie, threshold, quirk and g > N cases of tests/encode_cases.py (the dyadic configuration), for the
+    three `coords` and both matching types: pins the ORACLE on the edges the device tests compare the kernels with it on.
+    A few long arrays instead of several per run (an .npz member costs more than most of these results): the images of all cases
+    in one ragged `gt`, `image_off` (cases + 1) into its images; run k = (case * 3 + coords) * 2 + matching owns
+    idx / rows [run_off[k] : run_off[k + 1]] (sparse_encoding) and, per image, sums / diag_sums [image_run_off[k] : image_run_off[k + 1]]."""
+    from tests import encode_cases as ec
+    images, image_off, idx_all, rows_all, run_off, sums_all, diag_all, image_run_off = [], [0], [], [], [0], [], [], [0]
+    for case in ec.GOLDEN:
+        images += case.gt
+        image_off.append(len(images))
+        for coords in ec.COORDS:
+            for matching in ec.MATCHING:
+                enc = encoder_from(case.config(coords=coords, matching_type=matching))
+                y, y_diag = enc([np.array(g) for g in case.gt], diagnostics=True)
+                idx, rows, sums = sparse_encoding(y, enc.n_classes, enc.background_id)
+                idx_all.append(idx.reshape(-1, 2))
+                rows_all.append(rows)
+                run_off.append(run_off[-1] + rows.shape[0])
+                sums_all.append(sums)
+                diag_all.append(y_diag.reshape(y.shape[0], -1).sum(axis=1))
+                image_run_off.append(image_run_off[-1] + y.shape[0])
+    gt_cat, gt_off = ragged(images, 5)
+    save("encoder_edges", cases=np.array([c.name for c in ec.GOLDEN]), gt=gt_cat, gt_off=gt_off, image_off=np.array(image_off),
+         idx=np.concatenate(idx_all).astype(np.int32), rows=np.concatenate(rows_all), run_off=np.array(run_off),
+         sums=np.concatenate(sums_all), diag_sums=np.concatenate(diag_all), image_run_off=np.array(image_run_off))
+
+
 def gen_decoder():
     out = {}
     cases = []
@@ -635,7 +663,7 @@ def gen_decoder():
 
 if __name__ == "__main__":
     # box_filter / patch_sampling import the reference's real data_generator package; gen_evaluator stubs what is left of it
-    gens = [gen_box_utils, gen_box_utils2, gen_box_filter, gen_patch_sampling, gen_image_ops, gen_coco_utils, gen_api_surface, gen_evaluator, gen_anchors, gen_encoder, gen_decoder]
+    gens = [gen_box_utils, gen_box_utils2, gen_box_filter, gen_patch_sampling, gen_image_ops, gen_coco_utils, gen_api_surface, gen_evaluator, gen_anchors, gen_encoder, gen_encoder_edges, gen_decoder]
     wanted = set(sys.argv[1:])
     for g in gens:
         if not wanted or g.__name__[4:] in wanted:

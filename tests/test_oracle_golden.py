@@ -112,6 +112,47 @@ def test_encoder():
             assert np.array_equal(mm >= 0, (cls_sum == 1) & (y[:, :, 0] == 0)), pre
 
 
+def test_encoder_edges():
+    """The oracle on the tie, threshold, quirk and g > N cases of tests/encode_cases.py == the reference (make_golden.gen_encoder_edges).
+    On the dyadic configuration 'corners' and 'minmax' involve no log: bit for bit.  'centroids': the class, anchor and variance
+    columns bit for bit, the offsets within the 1e-12 / 1e-13 of the device tests (np.log of another NumPy build)."""
+    from tests import encode_cases as ec
+    z = util.load("encoder_edges")
+    assert [str(s) for s in z["cases"]] == [c.name for c in ec.GOLDEN] and len(ec.GOLDEN) >= 16
+    images = util.unragged(z["gt"], z["gt_off"])
+    k = 0
+    for ci, case in enumerate(ec.GOLDEN):
+        stored = images[z["image_off"][ci]:z["image_off"][ci + 1]]
+        assert len(stored) == len(case.gt) and all(np.array_equal(a, b) for a, b in zip(stored, case.gt)), case
+        for coords in ec.COORDS:
+            for matching in ec.MATCHING:
+                what = (case, coords, matching)
+                y, mm = case.oracle(coords=coords, matching_type=matching)
+                idx, rows = z["idx"][z["run_off"][k]:z["run_off"][k + 1]], z["rows"][z["run_off"][k]:z["run_off"][k + 1]]
+                sums = z["sums"][z["image_run_off"][k]:z["image_run_off"][k + 1]]
+                k += 1
+                assert idx.shape[0] >= sum(min(g.shape[0], 1) for g in case.gt), what
+                sel = y[idx[:, 0], idx[:, 1], :]
+                C = y.shape[2] - 12
+                if coords == "centroids":
+                    assert np.array_equal(sel[:, :C], rows[:, :C]) and np.array_equal(sel[:, C + 4:], rows[:, C + 4:]), what
+                    np.testing.assert_allclose(sel[:, C:C + 4], rows[:, C:C + 4], rtol=1e-12, atol=1e-13)
+                    np.testing.assert_allclose(y.reshape(len(case.gt), -1).sum(axis=1), sums, rtol=1e-12)
+                else:
+                    assert np.array_equal(sel, rows), what
+                    assert np.array_equal(y.reshape(len(case.gt), -1).sum(axis=1), sums), what
+                # every other row is still the all-background template
+                mask = np.ones(y.shape[:2], bool)
+                mask[idx[:, 0], idx[:, 1]] = False
+                ora = orc.EncoderOracle(**case.config(coords=coords, matching_type=matching))
+                tmpl = ora.generate_encoding_template(len(case.gt))
+                tmpl[:, :, ora.background_id] = 1
+                tmpl[:, :, -12:-8] = 0
+                assert np.array_equal(y[mask], tmpl[mask]), what
+                assert np.array_equal(mm[mask], np.full(mask.sum(), -1)) and np.array_equal(mm == -2, y[:, :, :C].sum(axis=-1) == 0), what
+    assert k == 6 * len(ec.GOLDEN) and z["run_off"][k] == z["rows"].shape[0]
+
+
 def test_encoder_degenerate_box_raises():
     enc = _encoder(syn.TINY)
     with pytest.raises(orc.DegenerateBoxError):
